@@ -2,7 +2,12 @@
 """Headline benchmark: generator frames/s at 256^2, batch 8 per GPU (BASELINE.json metric,
 configs[1]: StyleGAN synthesis forward only, batch 8, 1x MI355X).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times EXACTLY K steps, optionally writes the last timed step's frames (``--dump-outputs DIR``:
+DIR/frames.npy, float32 [8,3,256,256], rank 0's replica; same arguments -> same weights, latents and noise) and prints the
+headline line (metric, value, unit, higher_is_better, dtype, ms_per_step).  Everything else below -- the roofline, the eager
+step, the CPU baseline, the extra objects, the data-parallel steps, and the median of 3 timed blocks -- runs with ``--full``.
 
 A step = one ``StyleGenerator.forward`` (mapping + 13 style affines + prologue + 12 fused 3x3 conv
 launches + toRGB) over one batch of 8 synthetic [6144] latents, inputs and weights resident in HBM,
@@ -14,7 +19,7 @@ timed region, MAX over ranks, rank 0 prints ONE JSON line.  Either the driver st
 --gpus N`` does it itself: the parent -- before any GPU call -- starts N fresh child ranks through
 torch.distributed.run, relays rank 0's line and exits with the children's return code (it never re-executes itself).
 
-Extra objects in the line (headline fields unchanged):
+Extra objects in the line with ``--full`` (headline fields unchanged):
   roofline       -- the dominant kernel (spkconv::conv_kernel, MFMA-bound): algorithmic conv FLOPs per
                     step / conv kernel time per step, timed live with HIP events on the launch stream.
   cpu_baseline   -- the CPU oracle (a port of the reference's algorithm, parity-pinned to it) timed
@@ -519,8 +524,15 @@ def main():
     ap.add_argument("--dp-steps", type=int, default=5, help="timed steps of the data-parallel training steps (N > 1)")
     ap.add_argument("--dp-algo", default="all_reduce", choices=("all_reduce", "rs_ag"), help="the gradient exchange of the "
                     "data-parallel steps: one all-reduce per bucket, or reduce-scatter + all-gather (dp.GradBucketReducer algo)")
-    ap.add_argument("--blocks", type=int, default=3, help="timed blocks of --steps steps each; the line reports the median block")
+    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps steps each; the line reports the median "
+                    "block (default 1; 3 with --full)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: roofline, eager step, "
+                    "CPU baseline, extra objects, data-parallel steps (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the frames of the last "
+                    "timed step (rank 0) to DIR/frames.npy, float32")
     args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 3 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))          # nothing above touched the GPU
@@ -588,11 +600,12 @@ def main():
         # EXACTLY --steps steps per timed block, barrier + synchronize on both sides, MAX over ranks; --blocks such blocks
         # back to back, the line carries the MEDIAN block (value / ms_per_step) and every block's figure beside it
         block_s = []
+        out = None
         for _ in range(max(1, args.blocks)):
             barrier()
             t0 = time.perf_counter()
             for _ in range(args.steps):
-                step()
+                out = step()
             barrier()
             el = time.perf_counter() - t0
             if dist is not None:
@@ -602,27 +615,33 @@ def main():
             block_s.append(el)
         elapsed = sorted(block_s)[len(block_s) // 2]
 
-        # ---- eager: the same step as an unchanged caller gets it (no graph) ----
-        for _ in range(3):
-            eager_step()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        n_eager = max(10, args.steps // 2)
-        for _ in range(n_eager):
-            eager_step()
-        torch.cuda.synchronize()
-        eager_ms = (time.perf_counter() - t1) / n_eager * 1e3
+        if args.dump_outputs and rank == 0 and out is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "frames.npy"), out.detach().float().cpu().numpy())
 
-        # ---- roofline of the dominant kernel ----
-        conv_ms, n_launch, headline_up_ms = conv_time_ms(gen, feats, L)
-        headline_plan = plan_of(gen)
-        roof_how = ("HIP events around 20 replays of the step's hipGraph minus 20 replays of the same launch list captured "
-                    "without its conv launches (spk_launch_list kind_mask)")
-        if conv_ms is None:
-            raise SystemExit("bench: the decoder did not run through its launch plan")
+        if args.full:
+            # ---- eager: the same step as an unchanged caller gets it (no graph) ----
+            for _ in range(3):
+                eager_step()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            n_eager = max(10, args.steps // 2)
+            for _ in range(n_eager):
+                eager_step()
+            torch.cuda.synchronize()
+            eager_ms = (time.perf_counter() - t1) / n_eager * 1e3
+
+            # ---- roofline of the dominant kernel ----
+            conv_ms, n_launch, headline_up_ms = conv_time_ms(gen, feats, L)
+            headline_plan = plan_of(gen)
+            roof_how = ("HIP events around 20 replays of the step's hipGraph minus 20 replays of the same launch list captured "
+                        "without its conv launches (spk_launch_list kind_mask)")
+            if conv_ms is None:
+                raise SystemExit("bench: the decoder did not run through its launch plan")
 
     extras = {}
-    if rank == 0 and world == 1 and not args.headline_only:
+    if rank == 0 and world == 1 and args.full and not args.headline_only:
         with torch.no_grad():
             # ---- the opt-in split-precision path on the headline workload ----
             gen.synthesis.precision = "bf16x3"
@@ -795,12 +814,6 @@ def main():
 
     line = None
     if rank == 0:
-        traffic = None
-        try:   # HBM bytes per conv launch from the committed PMC pass of this same command
-            with open(os.path.join(ROOT, "profiles", "conv_traffic.json")) as f:
-                traffic = json.load(f)["bytes_per_launch"]
-        except (OSError, KeyError, ValueError):
-            pass
         ms_per_step = elapsed / args.steps * 1e3
         line = {
             "metric": "generator frames/sec at 256^2, batch 8/GPU",
@@ -822,14 +835,22 @@ def main():
                        "launch": "hipGraph replay of the step" if graph is not None else "eager launches",
                        "conv3x3_algo": pkg.ops.CONV3X3_ALGO + " (fp32 Winograd F(2x2,3x3) where the kernel serves the layer, the direct fmaf-chain "
                                        "kernel elsewhere; SPK_CONV3X3_ALGO=direct: the direct kernel everywhere)"},
-            "roofline": conv_roofline(headline_plan, L, conv_ms, headline_up_ms, "spkwino::wino_kernel (fp32 Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32, layers >= 16^2; the 16^2 ones run their contraction in 4 slices + the split-K finisher) + "
-                                      "spkconv::conv_kernel<Cfg,3,3,1,MODE> (direct f32 MFMA implicit GEMM, the 8^2 layers)", traffic, ms_per_step,
-                                      {"measured_by": roof_how}),
-            "eager": {"what": "the same step without the hipGraph: one spk_launch_list call per forward (plan.DecoderPlan), as an "
-                              "unchanged `model.Gd(x)` caller runs it", "ms_per_step": round(eager_ms, 4),
-                      "frames_per_s_per_gpu": round(BATCH / eager_ms * 1e3, 2), "vs_graph": round(eager_ms / ms_per_step, 3)},
         }
-    if world > 1 and not args.headline_only:
+        if args.full:
+            traffic = None
+            try:   # HBM bytes per conv launch from the committed PMC pass of this same command
+                with open(os.path.join(ROOT, "profiles", "conv_traffic.json")) as f:
+                    traffic = json.load(f)["bytes_per_launch"]
+            except (OSError, KeyError, ValueError):
+                pass
+            line["roofline"] = conv_roofline(
+                headline_plan, L, conv_ms, headline_up_ms, "spkwino::wino_kernel (fp32 Winograd F(2x2,3x3) on v_mfma_f32_32x32x2_f32, layers >= 16^2; the 16^2 ones run their contraction in 4 slices + the split-K finisher) + "
+                "spkconv::conv_kernel<Cfg,3,3,1,MODE> (direct f32 MFMA implicit GEMM, the 8^2 layers)", traffic, ms_per_step,
+                {"measured_by": roof_how})
+            line["eager"] = {"what": "the same step without the hipGraph: one spk_launch_list call per forward (plan.DecoderPlan), as an "
+                                     "unchanged `model.Gd(x)` caller runs it", "ms_per_step": round(eager_ms, 4),
+                             "frames_per_s_per_gpu": round(BATCH / eager_ms * 1e3, 2), "vs_graph": round(eager_ms / ms_per_step, 3)}
+    if world > 1 and args.full and not args.headline_only:
         # The exchange runs on a transport this build container cannot rehearse (RCCL over xGMI needs N GPUs).  If it
         # stalls, the headline measurement above must still reach the driver: a watchdog thread on every rank prints rank
         # 0's line without the data-parallel objects and ends the process when the deadline passes (a stalled collective
@@ -926,7 +947,7 @@ def main():
 
     if rank == 0:
         line.update(extras)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(host_cores())
         print(json.dumps(line), flush=True)
     if dist is not None:

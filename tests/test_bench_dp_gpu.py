@@ -20,7 +20,7 @@ def test_bench_launches_its_own_ranks_and_times_the_gradient_exchange():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SPK_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "5", "--warmup", "2",
-                        "--dp-steps", "2", "--dp-algo", "rs_ag"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+                        "--dp-steps", "2", "--dp-algo", "rs_ag", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                     # rank 0 prints ONE line
@@ -56,7 +56,7 @@ def test_a_failing_rank_makes_the_whole_bench_exit_non_zero_and_keeps_the_headli
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SPK_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4", SPK_BENCH_DP_FAIL_RANK="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                        "--blocks", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--blocks", "1", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode != 0, (r.stdout[-2000:], r.stderr[-2000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])

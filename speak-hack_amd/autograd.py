@@ -11,6 +11,7 @@ instead of silently dropping the second-order term.
 from __future__ import annotations
 
 import contextlib
+import functools
 import weakref
 
 import torch
@@ -190,20 +191,14 @@ class FusedConvFn(torch.autograd.Function):
         keep = _needs(ctx, grad_mode)
         a = torch.empty((B, Cout, H, W), device=x.device, dtype=torch.float32) if keep else None
         pw = getattr(weight, "_spk_gate_of", weight)      # (behind a WeightGateFn: the parameter itself keys the packed images)
-        if ops.train_bf16x3(B, Cin, Cout, H, W):     # opt-in split-precision training (ops.train_conv_precision)
-            y = ops.conv3x3_bf16x3(x, packed.get_bf16x3(pw), Cout, bias=bias, noise_w=noise_w, noise=noise, style=style,
-                                   upsample=upsample, lrelu_slope=slope, out_pre=a, out_scale=w_scale)
-        elif ops.use_wino(B, Cin, Cout, H, W):       # fp32 Winograd (ops.CONV3X3_ALGO); a x2 layer reads the materialised x2 image
-            xin = ops.upsample2x_bilinear(x) if upsample else x
-            y = ops.conv3x3_wino(xin, packed.get_wino(pw), Cout, bias=bias, noise_w=noise_w, noise=noise, style=style,
-                                 lrelu_slope=slope, out_pre=a, out_scale=w_scale)
-            if upsample and keep and ops.use_wgrad_wino(B, Cin, Cout, H, W):
-                x = xin                               # the Winograd weight gradient reads the x2 image too: keep IT, not the source
-                ctx.x_was_up = True
-        else:
-            cfg = ops.conv2d_pick_config(3, 1, B, Cin, Cout, H, W)
-            y = ops.conv2d_fused(x, packed.get(pw, cfg), Cout, 3, 1, bias=bias, noise_w=noise_w, noise=noise,
-                                 style=style, upsample=upsample, lrelu_slope=slope, config=cfg, out_pre=a, out_scale=w_scale)
+        route = ops.conv3x3_route(B, Cin, Cout, H, W)
+        # a x2 layer on Winograd reads the materialised x2 image -- made here, so that the Winograd weight gradient can keep it
+        x2 = ops.upsample2x_bilinear(x) if upsample and route[0] == "wino" else None
+        y = ops.conv3x3(x if x2 is None else x2, packed.images(pw), Cout, route, upsample=upsample and x2 is None, bias=bias,
+                        noise_w=noise_w, noise=noise, style=style, lrelu_slope=slope, out_pre=a, out_scale=w_scale)
+        if x2 is not None and keep and ops.use_wgrad_wino(B, Cin, Cout, H, W):
+            x = x2                                    # the Winograd weight gradient reads the x2 image too: keep IT, not the source
+            ctx.x_was_up = True
         if keep:
             ctx.save_for_backward(x, weight, a, noise, style)
             ctx.conf = (upsample, slope, packed, bias is not None, noise_w is not None, float(w_scale))
@@ -229,13 +224,7 @@ class FusedConvFn(torch.autograd.Function):
         if pw is None:
             pw = weight
         if ctx.needs_input_grad[0]:
-            if ops.train_bf16x3(B, Cout, Cin, H, W):
-                dx = ops.conv3x3_bf16x3(dt, packed.get_bf16x3(pw, transpose_flip=True), Cin, out_scale=w_scale)
-            elif ops.use_wino(B, Cout, Cin, H, W):
-                dx = ops.conv3x3_wino(dt, packed.get_wino(pw, transpose_flip=True), Cin, out_scale=w_scale)
-            else:
-                cfg = ops.conv2d_pick_config(3, 1, B, Cout, Cin, H, W)
-                dx = ops.conv2d_fused(dt, packed.get(pw, cfg, transpose_flip=True), Cin, 3, 1, config=cfg, out_scale=w_scale)
+            dx = ops.conv3x3(dt, packed.images(pw), Cin, ops.conv3x3_route(B, Cout, Cin, H, W), transpose_flip=True, out_scale=w_scale)
             if upsample:
                 dx = ops.upsample2x_bilinear_bwd(dx)
         return dx, dw, dbias, dnw, None, dstyle, None, None, None, None, None
@@ -439,13 +428,7 @@ def _packed_of(weight, cfg, tf=False):
     if hit is None:
         if cache and next(iter(cache))[2:] != key[2:]:
             cache.clear()                 # the tensor was updated in place (a Parameter after an optimizer step): drop old images
-        if cfg == "wino":
-            hit = ops.pack_conv_weight_wino(weight.detach(), transpose_flip=bool(tf))
-        elif cfg == "bf16x3":
-            hit = ops.pack_conv_weight_bf16x3(weight.detach(), transpose_flip=bool(tf))
-        else:
-            hit = ops.pack_conv_weight(weight.detach(), cfg, transpose_flip=tf)
-        cache[key] = hit
+        hit = cache[key] = ops.pack_image(weight.detach(), cfg, tf)
     return hit
 
 
@@ -462,11 +445,8 @@ def _conv_plain(x, weight, k, stride):
     if ops.conv1x1_expand_ok(x, Cin, k, stride):                 # fromRGB: a store stream, not a contraction
         w0, sd = _sn_parts(weight)
         return ops.conv1x1_expand(x.contiguous(), w0, None, sd)
-    if k == 3 and stride == 1 and ops.train_bf16x3(B, Cin, Cout, Ho, Wo):
-        return ops.conv3x3_bf16x3(x.contiguous(), _packed(weight, "bf16x3")[0], Cout)
-    if k == 3 and stride == 1 and ops.use_wino(B, Cin, Cout, Ho, Wo):
-        wp, sd = _packed(weight, "wino")
-        return ops.conv3x3_wino(x.contiguous(), wp, Cout, out_scale_dev=sd)
+    if k == 3 and stride == 1:
+        return ops.conv3x3(x.contiguous(), functools.partial(_packed, weight), Cout, ops.conv3x3_route(B, Cin, Cout, Ho, Wo))
     cfg = ops.conv2d_pick_config(k, stride, B, Cin, Cout, Ho, Wo)
     wp, sd = _packed(weight, cfg)
     return ops.conv2d_fused(x, wp, Cout, k, stride, config=cfg, out_scale_dev=sd)
@@ -477,11 +457,9 @@ def _conv_dgrad(dt, weight, k, stride, in_hw):
     Cin = weight.shape[1]
     if k == 1 and stride == 1 and Cin <= 4:                      # fromRGB's data gradient: a 1x1 conv TO <= 4 channels (the toRGB kernel)
         return ops.conv1x1_small(dt.contiguous(), weight.detach().reshape(Cout, Cin).t().contiguous().view(Cin, Cout, 1, 1))
-    if k == 3 and stride == 1 and ops.train_bf16x3(B, Cout, Cin, in_hw[0], in_hw[1]):
-        return ops.conv3x3_bf16x3(dt, _packed(weight, "bf16x3", True)[0], Cin)
-    if k == 3 and stride == 1 and ops.use_wino(B, Cout, Cin, in_hw[0], in_hw[1]):
-        wp, sd = _packed(weight, "wino", True)
-        return ops.conv3x3_wino(dt.contiguous(), wp, Cin, out_scale_dev=sd)
+    if k == 3 and stride == 1:
+        return ops.conv3x3(dt.contiguous(), functools.partial(_packed, weight), Cin, ops.conv3x3_route(B, Cout, Cin, *in_hw),
+                           transpose_flip=True)
     cfg, tf = ops.dgrad_plan(k, stride, B, Cout, Cin, in_hw, dt.shape[-2:])
     wp, sd = _packed(weight, cfg, tf)
     return ops.conv2d_dgrad(dt, wp, Cin, k, stride, in_hw, cfg, out_scale_dev=sd)
@@ -530,11 +508,9 @@ class ConvBiasLReLUFn(torch.autograd.Function):
         if ops.conv1x1_expand_ok(x, Cin, k, stride):             # fromRGB (3 -> 64 at 256^2): a store stream, not a contraction
             w0, sd = _sn_parts(weight)
             y = ops.conv1x1_expand(x.contiguous(), w0, bias, sd, slope)
-        elif k == 3 and stride == 1 and ops.train_bf16x3(B, Cin, Cout, Ho, Wo):
-            y = ops.conv3x3_bf16x3(x.contiguous(), _packed(weight, "bf16x3")[0], Cout, bias=bias, lrelu_slope=slope)
-        elif k == 3 and stride == 1 and ops.use_wino(B, Cin, Cout, Ho, Wo):
-            wp, sd = _packed(weight, "wino")
-            y = ops.conv3x3_wino(x.contiguous(), wp, Cout, bias=bias, lrelu_slope=slope, out_scale_dev=sd)
+        elif k == 3 and stride == 1:
+            y = ops.conv3x3(x.contiguous(), functools.partial(_packed, weight), Cout, ops.conv3x3_route(B, Cin, Cout, Ho, Wo),
+                            bias=bias, lrelu_slope=slope)
         else:
             cfg = ops.conv2d_pick_config(k, stride, B, Cin, Cout, Ho, Wo)
             wp, sd = _packed(weight, cfg)
@@ -620,17 +596,11 @@ class ModConvFn(torch.autograd.Function):
         H, W = (2 * Hs, 2 * Ws) if upsample else (Hs, Ws)
         d = ops.modconv_demod(weight, s, scale) if demodulate else None
         pw = getattr(weight, "_spk_gate_of", weight)      # (behind a WeightGateFn: the parameter keys the packed images)
-        if ops.use_wino(B, Cin, Cout, H, W) and (not upsample or Ws % 4 == 0):
-            # fp32 Winograd with the modulation applied to the transformed input and the demodulation in the epilogue; a x2 layer
-            # reads the materialised upfirdn2d(up = 2, [1,3,3,1]) image
-            xin = ops.upsample2x(x, zero_border=True) if upsample else x
-            y = ops.conv3x3_wino(xin, packed.get_wino(pw), Cout, bias=bias, noise_w=noise_w, noise=noise, lrelu_slope=slope,
-                                 out_scale=scale, batch_scale=s.contiguous(), demod=d, act_gain=gain)
-        else:
-            cfg = ops.conv2d_pick_config(3, 1, B, Cin, Cout, H, W)
-            cfg = cfg + 4 if cfg < 4 else cfg
-            y = ops.conv2d_fused(x, packed.get(pw, cfg), Cout, 3, 1, bias=bias, noise_w=noise_w, noise=noise, lrelu_slope=slope,
-                                 out_scale=scale, batch_scale=s, demod=d, act_gain=gain, config=cfg, upsample=upsample, up_fir=True)
+        # on Winograd the modulation is applied to the transformed input and the demodulation in the epilogue; a x2 layer reads the
+        # materialised upfirdn2d(up = 2, [1,3,3,1]) image
+        route = ops.conv3x3_route(B, Cin, Cout, H, W, precision="f32", modulated=True, up_w=Ws if upsample else None)
+        y = ops.conv3x3(x, packed.images(pw), Cout, route, upsample=upsample, up_fir=True, bias=bias, noise_w=noise_w, noise=noise,
+                        lrelu_slope=slope, out_scale=scale, batch_scale=s.contiguous(), demod=d, act_gain=gain)
         if _needs(ctx, grad_mode):
             ctx.save_for_backward(x, weight, s, d, y, noise, bias, noise_w)
             ctx.conf = (scale, upsample, slope, gain, fir, packed)
@@ -650,14 +620,9 @@ class ModConvFn(torch.autograd.Function):
         need_dx, need_dw, need_ds = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         dx = dw = ds = None
         if need_dx or need_ds:
-            if ops.use_wino(B, Cout, Cin, H, W):
-                dxt = ops.conv3x3_wino(dt, packed.get_wino(getattr(weight, "_spk_gate_of", weight), transpose_flip=True), Cin,
-                                       out_scale=scale, batch_scale=dprime.contiguous())
-            else:
-                cfg = ops.conv2d_pick_config(3, 1, B, Cout, Cin, H, W)
-                cfg = cfg + 4 if cfg < 4 else cfg
-                dxt = ops.conv2d_fused(dt, packed.get(getattr(weight, "_spk_gate_of", weight), cfg, transpose_flip=True), Cin, 3, 1,
-                                       out_scale=scale, batch_scale=dprime, config=cfg)    # d (up(x) * s), at the output resolution
+            dxt = ops.conv3x3(dt, packed.images(getattr(weight, "_spk_gate_of", weight)), Cin,       # d (up(x) * s), at the output resolution
+                              ops.conv3x3_route(B, Cout, Cin, H, W, precision="f32", modulated=True), transpose_flip=True,
+                              out_scale=scale, batch_scale=dprime.contiguous())
             if upsample and (x.shape[-1] % 2 or dxt.data_ptr() % 16):                  # odd widths: the stand-alone adjoint
                 dxu = ops.upfirdn2d(dxt, torch.flip(fir, [0, 1]), up=1, down=2, pad=(1, 1))
                 dx, ds = ops.modconv_dx_finish(dxu, x, s, False, need_dx=need_dx)

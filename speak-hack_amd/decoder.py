@@ -199,9 +199,9 @@ class SynthesisNetwork(nn.Module):
                 res *= 2
                 for conv, pk in ((layer.conv1, layer._pk1), (layer.conv2, layer._pk2)):
                     Co, Ci = conv.weight.shape[:2]
-                    if not ops.train_bf16x3(B, Ci, Co, res, res) and ops.use_wino(B, Ci, Co, res, res):
+                    if ops.conv3x3_route(B, Ci, Co, res, res)[0] == "wino":
                         items.append((pk, conv.weight, False))
-                    if grad and not ops.train_bf16x3(B, Co, Ci, res, res) and ops.use_wino(B, Co, Ci, res, res):
+                    if grad and ops.conv3x3_route(B, Co, Ci, res, res)[0] == "wino":
                         items.append((pk, conv.weight, True))
             if items:
                 ops.prepack_wino(items)

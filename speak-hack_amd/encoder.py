@@ -134,8 +134,9 @@ class _ConvBN:
                                                                             in_affine=rec["in_affine"]))
         if not need_dx:
             return None
-        if (self.k == 3 and self.stride == 1 and half is None and ops.use_wino(B, Cout, Cin, H, W)
-                and dr.data_ptr() % 16 == 0 and (dx_out is None or dx_out.data_ptr() % 16 == 0)):
+        aligned = dr.data_ptr() % 16 == 0 and (dx_out is None or dx_out.data_ptr() % 16 == 0)
+        if (self.k == 3 and self.stride == 1 and half is None
+                and ops.conv3x3_route(B, Cout, Cin, H, W, precision="f32", wino_ok=aligned)[0] == "wino"):
             # fp32 Winograd F(2x2, 3x3) data gradient (ops.CONV3X3_ALGO)
             return ops.conv3x3_wino(dr.contiguous(), self.packed.get_wino(conv.weight, transpose_flip=True), Cin, out=dx_out, accumulate=accumulate)
         cfg, tf = ops.dgrad_plan(self.k, self.stride, B, Cout, Cin, (H, W), dr.shape[-2:], dx_out, accumulate)
@@ -302,8 +303,9 @@ class _GroupedConvBN:
             grads[self.convs[q].weight] = dw[q]
         if not need_dx:
             return None
-        if (self.k == 3 and self.stride == 1 and half is None and not self.shared_input and ops.use_wino(B, Cout, Cin, H, W, groups=G)
-                and dr.data_ptr() % 16 == 0 and (dx_out is None or dx_out.data_ptr() % 16 == 0)):
+        aligned = dr.data_ptr() % 16 == 0 and (dx_out is None or dx_out.data_ptr() % 16 == 0)
+        if (self.k == 3 and self.stride == 1 and half is None
+                and ops.conv3x3_route(B, Cout, Cin, H, W, precision="f32", groups=G, wino_ok=aligned and not self.shared_input)[0] == "wino"):
             # fp32 Winograd F(2x2, 3x3) data gradient, the G trunks as groups of one launch (ops.CONV3X3_ALGO)
             return ops.conv3x3_wino(dr.contiguous(), self.packed.get_wino(self._weights(), transpose_flip=True), Cin, groups=G,
                                     out=dx_out, accumulate=accumulate)

@@ -22,6 +22,95 @@ def _launch_conv2d(desc):
     L.check(L.lib().spk_conv2d_fwd(C.byref(desc), L.stream_ptr()), "spk_conv2d_fwd")
 
 
+def _run_conv2d(desc, ws_bytes, device):
+    """Eager tail of a conv launcher: the split-K scratch of this stream (``_workspace``) when the launch needs one, then the launch."""
+    if ws_bytes > 0:
+        ws = _workspace(device, ws_bytes)
+        desc.workspace, desc.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _launch_conv2d(desc)
+
+
+_KIND_FLAGS = L.CONV_WINOGRAD | L.CONV_BF16X3 | L.CONV_TRANSPOSE4X4_S2 | L.CONV_DGRAD_S2
+
+
+def conv_desc(x, w_packed, Cout, k=3, stride=1, *, flags=0, out=None, hw=None, bias=None, noise_w=None, noise=None, style=None,
+              style_stride=None, upsample=False, up_fir=False, lrelu_slope=None, out_scale=1.0, in_affine=None, batch_scale=None,
+              demod=None, act_gain=1.0, stats=None, out_pre=None, accumulate=False, accum_half=None, out_scale_dev=None, config=-1,
+              ksplit=0, groups=1, shared_input=False, rgb_w=None, rgb_bias=None, rgb_out=None):
+    """-> (``L.Conv2dDesc``, split-K workspace bytes): the one place a ``spk_conv2d_desc`` is assembled.
+
+    ``flags``: the kernel family -- 0 (the direct MFMA kernel), ``SPK_CONV_WINOGRAD``, ``SPK_CONV_BF16X3``,
+    ``SPK_CONV_TRANSPOSE4X4_S2`` or ``SPK_CONV_DGRAD_S2``; the epilogue and staging flags follow from the arguments (see
+    ``conv2d_fused``).  x is [B, groups*Cin (``shared_input``: Cin), Hin, Win]; the output size is the conv's own, twice the
+    input's (``upsample``), or ``hw``.  ``config`` < 0 on the direct kernel: the library's pick (+4 for a modulated conv).
+    ``out`` may be None (a plan patches y).  The workspace fields stay empty: an eager launch takes ``_workspace``, a plan
+    one buffer of its own; the byte count is < 0 where the Winograd kernel does not serve the shape."""
+    B, Cin, Hs, Ws = x.shape
+    G = int(groups)
+    if G > 1 and not shared_input:
+        if Cin % G:
+            raise L.SpkError(f"conv2d: {Cin} input channels do not split into {G} groups")
+        Cin //= G
+    if hw is not None:
+        H, W = hw
+    elif upsample:
+        H, W = 2 * Hs, 2 * Ws
+    else:
+        H, W = conv_out_size(Hs, k, stride), conv_out_size(Ws, k, stride)
+    if noise is not None and (noise_w is None or noise.numel() != B * H * W):
+        raise L.SpkError(f"conv2d: noise must be [B,1,H,W]={B, 1, H, W}, got {tuple(noise.shape)}")
+    if accum_half is not None and (tuple(accum_half.shape) != (B, G * Cout, (H + 1) // 2, (W + 1) // 2) or not accum_half.is_contiguous()):
+        raise L.SpkError(f"conv2d: accum_half must be a contiguous {(B, G * Cout, (H + 1) // 2, (W + 1) // 2)} tensor")
+    if batch_scale is not None and (tuple(batch_scale.shape) != (B, Cin) or in_affine is not None):   # the modulated convolution
+        raise L.SpkError("conv2d: batch_scale must be [B,Cin] and excludes in_affine")
+    if demod is not None and (batch_scale is None or tuple(demod.shape) != (B, Cout)):
+        raise L.SpkError("conv2d: demod must be [B,Cout] and goes with batch_scale")
+    slots = 0
+    if stats is not None:
+        slots = stats.numel() // (2 * G * Cout)
+        if (stats.dtype != torch.float64 or not stats.is_cuda or not stats.is_contiguous() or slots < 1
+                or stats.numel() != slots * 2 * G * Cout):
+            raise L.SpkError("conv2d: stats must be a contiguous float64 HIP tensor of slots*2*groups*Cout elements (see stats_slots)")
+    if style is not None and style_stride is None:
+        style_stride = style.stride(0) if style.dim() == 2 else 2 * Cout
+    flags |= ((L.EPI_BIAS if bias is not None else 0) | (L.EPI_NOISE if noise is not None else 0)
+              | (L.EPI_LRELU if lrelu_slope is not None else 0) | (L.EPI_STYLE if style is not None else 0)
+              | (L.CONV_UPSAMPLE2X | (L.CONV_UP_FIR1331 if up_fir else 0) if upsample else 0) | (L.EPI_ACCUM if accumulate else 0)
+              | (L.CONV_IN_AFFINE_RELU if in_affine is not None else 0) | (L.EPI_ACCUM_HALF if accum_half is not None else 0)
+              | (L.CONV_IN_BATCH_SCALE if batch_scale is not None else 0) | (L.EPI_STATS if stats is not None else 0)
+              | (L.EPI_TORGB if rgb_w is not None else 0))
+    kind = flags & _KIND_FLAGS
+    if kind & (L.CONV_BF16X3 | L.CONV_TRANSPOSE4X4_S2):
+        ksplit = 1                       # (kernels without a split contraction)
+    if kind == 0 and config < 0:
+        config = _modulated_config(conv2d_pick_config(k, stride, B, Cin, Cout, H, W), batch_scale is not None)
+    if kind == 0:
+        ws_bytes = L.lib().spk_conv2d_workspace_bytes_grouped(int(config), int(ksplit), k, k, stride, B, Cin, Cout, H, W, G)
+        if ws_bytes < 0:
+            raise L.SpkError(f"conv2d: config {config} cannot host k={k} s={stride} shape {(B, Cin, Cout, H, W)}")
+    elif kind == L.CONV_WINOGRAD:
+        ws_bytes = L.lib().spk_conv2d_wino_workspace_bytes(int(ksplit), B, Cin, G * Cout, H, W)
+    elif kind == L.CONV_DGRAD_S2:
+        ws_bytes = L.lib().spk_conv2d_dgrad_s2_workspace_bytes(B, Cin, Cout, Hs, Ws, H, W, G)
+    else:
+        ws_bytes = 0
+    d = L.Conv2dDesc(x=L.dptr(x, "x"), w_packed=w_packed.data_ptr() if w_packed.dtype == torch.uint8 else L.dptr(w_packed, "w_packed"),
+                     bias=L.dptr(bias, "bias"), noise_w=L.dptr(noise_w, "noise_w") if noise is not None else None,
+                     noise=L.dptr(noise, "noise"), style=_style_ptr(style),
+                     in_scale=L.dptr(in_affine[0], "in_scale") if in_affine is not None else L.dptr(batch_scale, "batch_scale"),
+                     in_shift=L.dptr(in_affine[1], "in_shift") if in_affine is not None else None,
+                     out_scale_bc=L.dptr(demod, "demod"), act_gain=float(act_gain),
+                     stats=stats.data_ptr() if stats is not None else None, y=L.dptr(out, "out"), y_pre=L.dptr(out_pre, "out_pre"),
+                     B=B, Cin=Cin, Cout=Cout, H=H, W=W, Hin=Hs, Win=Ws, kh=k, kw=k, stride=stride, style_stride=int(style_stride or 0),
+                     flags=flags, lrelu_slope=float(lrelu_slope if lrelu_slope is not None else 1.0), out_scale=float(out_scale),
+                     config=int(config), ksplit=int(ksplit), workspace=None, workspace_bytes=0, groups=G,
+                     group_in_stride=0 if (shared_input or G == 1) else Cin, stats_slots=slots,
+                     accum_half=L.dptr(accum_half, "accum_half"), out_scale_dev=L.dptr(out_scale_dev, "out_scale_dev"),
+                     rgb_w=L.dptr(rgb_w, "rgb weight"), rgb_bias=L.dptr(rgb_bias, "rgb bias"), rgb_y=L.dptr(rgb_out, "rgb_out"),
+                     rgb_channels=3 if rgb_w is not None else 0)
+    return d, ws_bytes
+
+
 # --------------------------------------------------------------------------------------------------
 class PackedConvWeight:
     """A [Cout,Cin,k,k] weight re-laid for one tile config of the MFMA conv kernel
@@ -33,37 +122,30 @@ class PackedConvWeight:
     def __init__(self):
         self._cache = {}
 
-    def get(self, weight: torch.Tensor, config: int, transpose_flip: bool = False) -> torch.Tensor:
-        key = (config, transpose_flip)
-        stamp = (weight.data_ptr(), weight._version, tuple(weight.shape))
-        hit = self._cache.get(key)
-        if hit is not None and hit[0] == stamp and hit[2]() is weight:
-            return hit[1]
-        packed = pack_conv_weight(weight.detach(), config, transpose_flip)
-        self._cache[key] = (stamp, packed, weakref.ref(weight))
-        return packed
-
-    def get_bf16x3(self, weight: torch.Tensor, transpose_flip: bool = False) -> torch.Tensor:
-        """The bf16 hi / lo image of the opt-in split-precision conv (``conv3x3_bf16x3``), cached the same way."""
-        key = ("bf16x3", bool(transpose_flip))
-        stamp = (weight.data_ptr(), weight._version, tuple(weight.shape))
-        hit = self._cache.get(key)
-        if hit is not None and hit[0] == stamp and hit[2]() is weight:
-            return hit[1]
-        packed = pack_conv_weight_bf16x3(weight.detach(), transpose_flip=transpose_flip)
-        self._cache[key] = (stamp, packed, weakref.ref(weight))
-        return packed
+    def get(self, weight: torch.Tensor, key, transpose_flip=False) -> torch.Tensor:
+        """The image ``key`` names (``pack_image``: a tile config of the direct kernel, "wino" or "bf16x3"), cached under
+        ``(key, transpose_flip)``."""
+        hit = self._hit(weight, (key, transpose_flip))
+        if hit is None:
+            hit = pack_image(weight.detach(), key, transpose_flip)
+            self._put(weight, (key, transpose_flip), hit)
+        return hit
 
     def get_wino(self, weight: torch.Tensor, transpose_flip: bool = False) -> torch.Tensor:
-        """The transformed image U = G g G^T of the fp32 Winograd conv (``conv3x3_wino``), cached the same way."""
-        key = ("wino", bool(transpose_flip))
-        stamp = (weight.data_ptr(), weight._version, tuple(weight.shape))
-        hit = self._cache.get(key)
-        if hit is not None and hit[0] == stamp and hit[2]() is weight:
+        return self.get(weight, "wino", bool(transpose_flip))
+
+    def images(self, weight):
+        """``weight``'s images for ``conv3x3``: ``images(key, transpose_flip)`` -> (image, None)."""
+        return lambda key, transpose_flip: (self.get(weight, key, transpose_flip), None)
+
+    def _hit(self, weight, cache_key):
+        hit = self._cache.get(cache_key)
+        if hit is not None and hit[0] == (weight.data_ptr(), weight._version, tuple(weight.shape)) and hit[2]() is weight:
             return hit[1]
-        packed = pack_conv_weight_wino(weight.detach(), transpose_flip=transpose_flip)
-        self._cache[key] = (stamp, packed, weakref.ref(weight))
-        return packed
+        return None
+
+    def _put(self, weight, cache_key, packed):
+        self._cache[cache_key] = ((weight.data_ptr(), weight._version, tuple(weight.shape)), packed, weakref.ref(weight))
 
     def clear(self):
         self._cache.clear()
@@ -220,79 +302,16 @@ def conv2d_fused(x, w_packed, Cout: int, k: int = 3, stride: int = 1, *, bias=No
     ``style``: rows [s0(Cout) | s1(Cout)] with row stride ``style_stride``.  ``stats``: fp64 [2*Cout],
     accumulates sum / sum of squares of y over (b,h,w) (BatchNorm batch statistics).
     """
-    B, Cin, Hs, Ws = x.shape
-    G = int(groups)
-    if G > 1 and not shared_input:
-        if Cin % G:
-            raise L.SpkError(f"conv2d_fused: {Cin} input channels do not split into {G} groups")
-        Cin //= G
-    if upsample:
-        H, W = 2 * Hs, 2 * Ws
-    else:
-        H, W = conv_out_size(Hs, k, stride), conv_out_size(Ws, k, stride)
+    B, _, Hs, Ws = x.shape
+    H, W = (2 * Hs, 2 * Ws) if upsample else (conv_out_size(Hs, k, stride), conv_out_size(Ws, k, stride))
     if out is None:
-        out = torch.empty((B, G * Cout, H, W), device=x.device, dtype=torch.float32)
-    flags = 0
-    if bias is not None:
-        flags |= L.EPI_BIAS
-    if noise is not None:
-        if noise_w is None or noise.numel() != B * H * W:
-            raise L.SpkError(f"conv2d_fused: noise must be [B,1,H,W]={B, 1, H, W}, got {tuple(noise.shape)}")
-        flags |= L.EPI_NOISE
-    if lrelu_slope is not None:
-        flags |= L.EPI_LRELU
-    if style is not None:
-        if style_stride is None:
-            style_stride = style.stride(0) if style.dim() == 2 else 2 * Cout
-        flags |= L.EPI_STYLE
-    if upsample:
-        flags |= L.CONV_UPSAMPLE2X | (L.CONV_UP_FIR1331 if up_fir else 0)
-    if accumulate:
-        flags |= L.EPI_ACCUM
-    if in_affine is not None:
-        flags |= L.CONV_IN_AFFINE_RELU
-    if accum_half is not None:
-        if tuple(accum_half.shape) != (B, G * Cout, (H + 1) // 2, (W + 1) // 2) or not accum_half.is_contiguous():
-            raise L.SpkError(f"conv2d_fused: accum_half must be a contiguous {(B, G * Cout, (H + 1) // 2, (W + 1) // 2)} tensor")
-        flags |= L.EPI_ACCUM_HALF
-    if batch_scale is not None:          # modulated convolution: s[B,Cin] applied to the input while staging
-        if tuple(batch_scale.shape) != (B, Cin) or in_affine is not None:
-            raise L.SpkError("conv2d_fused: batch_scale must be [B,Cin] and excludes in_affine")
-        flags |= L.CONV_IN_BATCH_SCALE
-    if demod is not None and tuple(demod.shape) != (B, Cout):
-        raise L.SpkError("conv2d_fused: demod must be [B,Cout]")
-    slots = 0
-    if stats is not None:
-        slots = stats.numel() // (2 * G * Cout)
-        if (stats.dtype != torch.float64 or not stats.is_cuda or not stats.is_contiguous() or slots < 1
-                or stats.numel() != slots * 2 * G * Cout):
-            raise L.SpkError("conv2d_fused: stats must be a contiguous float64 HIP tensor of slots*2*groups*Cout elements "
-                             "(see stats_slots)")
-        flags |= L.EPI_STATS
-    if config < 0:
-        config = conv2d_pick_config(k, stride, B, Cin, Cout, H, W)
-        if batch_scale is not None and config < 4:
-            config += 4                  # the modulated variant is built for the half-depth-chunk configs
-    ws_bytes = L.lib().spk_conv2d_workspace_bytes_grouped(int(config), int(ksplit), k, k, stride, B, Cin, Cout, H, W, G)
-    if ws_bytes < 0:
-        raise L.SpkError(f"conv2d_fused: config {config} cannot host k={k} s={stride} shape {(B, Cin, Cout, H, W)}")
-    ws = _workspace(x.device, ws_bytes) if ws_bytes > 0 else None
-    d = L.Conv2dDesc(x=L.dptr(x, "x"), w_packed=L.dptr(w_packed, "w_packed"), bias=L.dptr(bias, "bias"),
-                     noise_w=L.dptr(noise_w, "noise_w") if noise is not None else None,
-                     noise=L.dptr(noise, "noise"), style=_style_ptr(style),
-                     in_scale=(L.dptr(in_affine[0], "in_scale") if in_affine is not None
-                               else L.dptr(batch_scale, "batch_scale")),
-                     in_shift=L.dptr(in_affine[1], "in_shift") if in_affine is not None else None,
-                     out_scale_bc=L.dptr(demod, "demod"), act_gain=float(act_gain),
-                     stats=stats.data_ptr() if stats is not None else None, y=L.dptr(out, "out"),
-                     y_pre=L.dptr(out_pre, "out_pre"), B=B, Cin=Cin, Cout=Cout, H=H, W=W, Hin=Hs, Win=Ws, kh=k, kw=k, stride=stride,
-                     style_stride=int(style_stride or 0), flags=flags,
-                     lrelu_slope=float(lrelu_slope if lrelu_slope is not None else 1.0), out_scale=float(out_scale),
-                     config=int(config), ksplit=int(ksplit), workspace=ws.data_ptr() if ws is not None else None,
-                     workspace_bytes=ws.numel() * 4 if ws is not None else 0, groups=G,
-                     group_in_stride=0 if (shared_input or G == 1) else Cin, stats_slots=slots,
-                     accum_half=L.dptr(accum_half, "accum_half"), out_scale_dev=L.dptr(out_scale_dev, "out_scale_dev"))
-    _launch_conv2d(d)
+        out = torch.empty((B, int(groups) * Cout, H, W), device=x.device, dtype=torch.float32)
+    d, ws_bytes = conv_desc(x, w_packed, Cout, k, stride, out=out, bias=bias, noise_w=noise_w, noise=noise, style=style,
+                            style_stride=style_stride, upsample=upsample, up_fir=up_fir, lrelu_slope=lrelu_slope, out_scale=out_scale,
+                            in_affine=in_affine, stats=stats, config=config, ksplit=ksplit, accumulate=accumulate, out_pre=out_pre,
+                            batch_scale=batch_scale, demod=demod, act_gain=act_gain, groups=groups, shared_input=shared_input,
+                            accum_half=accum_half, out_scale_dev=out_scale_dev)
+    _run_conv2d(d, ws_bytes, x.device)
     return out
 
 
@@ -322,7 +341,10 @@ def pack_conv_weight_bf16x3(weight: torch.Tensor, out=None, transpose_flip=False
 # split hi + lo, fp32 accumulation: ~2e-5 per layer), weight gradients and everything else exact.  The reference's own training
 # config runs IRFD.forward under fp16 autocast (config.yaml:28, train.py:334); the default here stays exact fp32.
 TRAIN_CONV_PRECISION = "f32"
-TRAIN_BF16X3_MIN_PIXELS = 2048
+# layers with at least this many output pixels (batch x H x W) take the split-precision kernel when asked to: below it the
+# 64co x 256px blocks cannot fill 256 CUs without a split-K the bf16x3 kernel does not have (B = 8: the 16^2 layers up --
+# 93-96 us against 104-109 for the f32 kernel there, 83-88 against 40-43 at 8^2)
+BF16X3_MIN_PIXELS = 2048
 
 
 @contextlib.contextmanager
@@ -338,33 +360,17 @@ def train_conv_precision(precision: str):
         TRAIN_CONV_PRECISION = prev
 
 
-def train_bf16x3(B, Cin, Cout, H, W) -> bool:
-    """Whether a 3x3 stride-1 conv with this OUTPUT shape takes the split-precision kernel under the training switch."""
-    return (TRAIN_CONV_PRECISION == "bf16x3" and B * H * W >= TRAIN_BF16X3_MIN_PIXELS and bf16x3_supported(B, Cin, Cout, H, W)
-            and not (H * W <= 256 and use_wino(B, Cin, Cout, H, W)))      # (a <= 16^2 layer: the sliced fp32 Winograd launch is faster, and exact)
-
-
 def conv3x3_bf16x3(x, w_packed, Cout, *, bias=None, noise_w=None, noise=None, style=None, upsample=False, up_fir=False,
                    lrelu_slope=None, out_scale=1.0, batch_scale=None, demod=None, act_gain=1.0, out=None, out_pre=None):
     """Forward 3x3 stride-1 conv with the fused decoder epilogue on the bf16 matrix pipe, operands split hi + lo (three MFMAs
     per product, fp32 accumulation): ~3e-5 rel-L2 through the decoder, 5.3x the exact-f32 matrix rate.  ``out_pre``: also
     keep the value before the style stage (a training forward)."""
-    B, Cin, Hs, Ws = x.shape
-    H, W = (2 * Hs, 2 * Ws) if upsample else (Hs, Ws)
+    B, _, Hs, Ws = x.shape
     if out is None:
-        out = torch.empty((B, Cout, H, W), device=x.device, dtype=torch.float32)
-    flags = L.CONV_BF16X3 | (L.EPI_BIAS if bias is not None else 0) | (L.EPI_NOISE if noise is not None else 0) | \
-        (L.EPI_LRELU if lrelu_slope is not None else 0) | (L.EPI_STYLE if style is not None else 0) | \
-        (L.CONV_UPSAMPLE2X if upsample else 0) | (L.CONV_UP_FIR1331 if (upsample and up_fir) else 0) | \
-        (L.CONV_IN_BATCH_SCALE if batch_scale is not None else 0)
-    d = L.Conv2dDesc(x=L.dptr(x, "x"), w_packed=w_packed.data_ptr(), bias=L.dptr(bias, "bias"),
-                     noise_w=L.dptr(noise_w, "noise_w") if noise is not None else None, noise=L.dptr(noise, "noise"),
-                     style=_style_ptr(style), in_scale=L.dptr(batch_scale, "batch_scale"), in_shift=None,
-                     out_scale_bc=L.dptr(demod, "demod"), act_gain=float(act_gain), stats=None, y=L.dptr(out, "out"), y_pre=L.dptr(out_pre, "out_pre"),
-                     B=B, Cin=Cin, Cout=Cout, H=H, W=W, Hin=Hs, Win=Ws, kh=3, kw=3, stride=1,
-                     style_stride=int(style.stride(0)) if style is not None else 0, flags=flags,
-                     lrelu_slope=float(lrelu_slope if lrelu_slope is not None else 1.0), out_scale=float(out_scale), config=-1,
-                     ksplit=1, workspace=None, workspace_bytes=0, groups=1, group_in_stride=0, stats_slots=0)
+        out = torch.empty((B, Cout, 2 * Hs, 2 * Ws) if upsample else (B, Cout, Hs, Ws), device=x.device, dtype=torch.float32)
+    d, _ = conv_desc(x, w_packed, Cout, flags=L.CONV_BF16X3, out=out, bias=bias, noise_w=noise_w, noise=noise, style=style,
+                     upsample=upsample, up_fir=up_fir, lrelu_slope=lrelu_slope, out_scale=out_scale, batch_scale=batch_scale,
+                     demod=demod, act_gain=act_gain, out_pre=out_pre)
     _launch_conv2d(d)
     return out
 
@@ -448,28 +454,19 @@ def pack_conv_weights_wino_into(weights, outs, transpose_flip=False):
 def prepack_wino(items):
     """``items`` = [(PackedConvWeight cache, weight, transpose_flip), ...]: fill every STALE Winograd image in ONE launch
     (spk_conv2d_pack_weights_wino_list) -- the same bits ``get_wino`` would produce one launch at a time."""
-    todo = []
-    for pk, w, tf in items:
-        key = ("wino", bool(tf))
-        stamp = (w.data_ptr(), w._version, tuple(w.shape))
-        hit = pk._cache.get(key)
-        if hit is not None and hit[0] == stamp and hit[2]() is w:
-            continue
-        Cout, Cin = w.shape[:2]
-        n = (L.lib().spk_conv2d_packed_bytes_wino(Cout, Cin) if tf else L.lib().spk_conv2d_packed_bytes_wino(Cin, Cout)) // 4
-        todo.append((pk, key, stamp, w, bool(tf), torch.empty(n, device=w.device, dtype=torch.float32)))
+    todo = [(pk, w, bool(tf)) for pk, w, tf in items if pk._hit(w, ("wino", bool(tf))) is None]
     for i in range(0, len(todo), WINO_PACK_MAX):
         part = todo[i:i + WINO_PACK_MAX]
         n = len(part)
-        keep = [t[3].detach().contiguous() for t in part]          # (alive until the launch is queued)
-        ws = (C.c_void_p * n)(*[L.dptr(w_, "weight") for w_ in keep])
-        outs = (C.c_void_p * n)(*[t[5].data_ptr() for t in part])
-        cin = (C.c_int * n)(*[t[3].shape[1] for t in part])
-        cout = (C.c_int * n)(*[t[3].shape[0] for t in part])
-        tfs = (C.c_int * n)(*[1 if t[4] else 0 for t in part])
-        L.check(L.lib().spk_conv2d_pack_weights_wino_list(ws, outs, cin, cout, tfs, n, L.stream_ptr()), "spk_conv2d_pack_weights_wino_list")
-        for pk, key, stamp, w, tf, out in part:
-            pk._cache[key] = (stamp, out, weakref.ref(w))
+        keep = [w.detach().contiguous() for _, w, _ in part]          # (alive until the launch is queued)
+        outs = [empty_image("wino", w.shape[0] if tf else w.shape[1], w.shape[1] if tf else w.shape[0], w.device) for _, w, tf in part]
+        L.check(L.lib().spk_conv2d_pack_weights_wino_list((C.c_void_p * n)(*[L.dptr(w, "weight") for w in keep]),
+                                                          (C.c_void_p * n)(*[o.data_ptr() for o in outs]),
+                                                          (C.c_int * n)(*[w.shape[1] for w in keep]), (C.c_int * n)(*[w.shape[0] for w in keep]),
+                                                          (C.c_int * n)(*[1 if tf else 0 for _, _, tf in part]), n, L.stream_ptr()),
+                "spk_conv2d_pack_weights_wino_list")
+        for (pk, w, tf), out in zip(part, outs):
+            pk._put(w, ("wino", tf), out)
 
 
 def upsample2x(x, zero_border=False):
@@ -491,51 +488,89 @@ def conv3x3_wino(x, w_packed, Cout, *, bias=None, noise_w=None, noise=None, styl
     returns (out, rgb image), and with ``store_out=False`` (None, rgb image) -- the activation is then never written.
     ``groups`` > 1: that many independent convs in one launch (``Cout`` per group, x carries the groups' input channels side by side,
     ``w_packed`` = the groups' images one after another); plain or ``accumulate`` only -- the encoders' data gradients."""
-    B, Cx, H, W = x.shape
+    B, _, H, W = x.shape
     G = int(groups)
-    if Cx % G:
-        raise L.SpkError(f"conv3x3_wino: {Cx} input channels do not split into {G} groups")
-    Cin = Cx // G
     if G > 1 and any(t is not None for t in (bias, noise, style, out_pre, batch_scale, demod, rgb, lrelu_slope)):
         raise L.SpkError("conv3x3_wino: a grouped launch is plain (accumulate allowed)")
+    rgb_w2d, rgb_bias = None, None
     if rgb is not None:
         if Cout > 64 or out_pre is not None or accumulate or batch_scale is not None or tuple(rgb[0].shape[:2]) != (3, Cout):
             raise L.SpkError("conv3x3_wino: a fused toRGB needs Cout <= 64, weight [3,Cout,1,1], no out_pre / accumulate / modulation")
         if rgb_out is None:
             rgb_out = torch.empty((B, 3, H, W), device=x.device, dtype=torch.float32)
         ksplit = 1
-        rgb_w2d = rgb[0].detach().reshape(3, Cout).contiguous()      # (a local: alive until the launch is queued)
+        rgb_w2d, rgb_bias = rgb[0].detach().reshape(3, Cout).contiguous(), rgb[1]      # (a local: alive until the launch is queued)
     if out is None and (rgb is None or store_out):
         out = torch.empty((B, G * Cout, H, W), device=x.device, dtype=torch.float32)
-    if noise is not None and (noise_w is None or noise.numel() != B * H * W):
-        raise L.SpkError(f"conv3x3_wino: noise must be [B,1,H,W]={B, 1, H, W}, got {tuple(noise.shape)}")
-    if style is not None and style_stride is None:
-        style_stride = style.stride(0) if style.dim() == 2 else 2 * Cout
-    if batch_scale is not None and tuple(batch_scale.shape) != (B, Cin):
-        raise L.SpkError("conv3x3_wino: batch_scale must be [B,Cin]")
-    if demod is not None and (batch_scale is None or tuple(demod.shape) != (B, Cout)):
-        raise L.SpkError("conv3x3_wino: demod must be [B,Cout] and goes with batch_scale")
-    flags = L.CONV_WINOGRAD | (L.EPI_BIAS if bias is not None else 0) | (L.EPI_NOISE if noise is not None else 0) | \
-        (L.EPI_LRELU if lrelu_slope is not None else 0) | (L.EPI_STYLE if style is not None else 0) | (L.EPI_ACCUM if accumulate else 0) | \
-        (L.CONV_IN_BATCH_SCALE if batch_scale is not None else 0) | (L.EPI_TORGB if rgb is not None else 0)
-    d = L.Conv2dDesc(x=L.dptr(x, "x"), w_packed=L.dptr(w_packed, "w_packed"), bias=L.dptr(bias, "bias"),
-                     noise_w=L.dptr(noise_w, "noise_w") if noise is not None else None, noise=L.dptr(noise, "noise"),
-                     style=_style_ptr(style), in_scale=L.dptr(batch_scale, "batch_scale"), in_shift=None, out_scale_bc=L.dptr(demod, "demod"),
-                     act_gain=float(act_gain), stats=None,
-                     y=L.dptr(out, "out"), y_pre=L.dptr(out_pre, "out_pre"), B=B, Cin=Cin, Cout=Cout, H=H, W=W, Hin=H, Win=W,
-                     kh=3, kw=3, stride=1, style_stride=int(style_stride or 0), flags=flags,
-                     lrelu_slope=float(lrelu_slope if lrelu_slope is not None else 1.0), out_scale=float(out_scale), config=-1,
-                     ksplit=int(ksplit), workspace=None, workspace_bytes=0, groups=G, group_in_stride=Cin if G > 1 else 0, stats_slots=0,
-                     accum_half=None, out_scale_dev=L.dptr(out_scale_dev, "out_scale_dev"),
-                     rgb_w=L.dptr(rgb_w2d, "rgb weight") if rgb is not None else None,
-                     rgb_bias=L.dptr(rgb[1], "rgb bias") if rgb is not None and rgb[1] is not None else None,
-                     rgb_y=L.dptr(rgb_out, "rgb_out") if rgb is not None else None, rgb_channels=3 if rgb is not None else 0)
-    ws_bytes = L.lib().spk_conv2d_wino_workspace_bytes(int(ksplit), B, Cin, G * Cout, H, W)
-    if ws_bytes > 0:                        # few regions: the contraction runs in slices, partial sums through the split-K workspace
-        ws = _workspace(x.device, ws_bytes)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    _launch_conv2d(d)
+    d, ws_bytes = conv_desc(x, w_packed, Cout, flags=L.CONV_WINOGRAD, out=out, bias=bias, noise_w=noise_w, noise=noise, style=style,
+                            style_stride=style_stride, lrelu_slope=lrelu_slope, out_scale=out_scale, act_gain=act_gain, out_pre=out_pre,
+                            accumulate=accumulate, out_scale_dev=out_scale_dev, batch_scale=batch_scale, demod=demod, ksplit=ksplit,
+                            groups=G, rgb_w=rgb_w2d, rgb_bias=rgb_bias, rgb_out=rgb_out if rgb is not None else None)
+    _run_conv2d(d, ws_bytes, x.device)        # (few regions: the contraction runs in slices through the split-K workspace)
     return (out, rgb_out) if rgb is not None else out
+
+
+def _bf16x3_route(precision, B, Cin, Cout, H, W) -> bool:
+    return (precision == "bf16x3" and B * H * W >= BF16X3_MIN_PIXELS and bf16x3_supported(B, Cin, Cout, H, W)
+            and not (H * W <= 256 and use_wino(B, Cin, Cout, H, W)))      # (a <= 16^2 layer: the sliced fp32 Winograd launch is faster, and exact)
+
+
+def train_bf16x3(B, Cin, Cout, H, W) -> bool:
+    """Whether a 3x3 stride-1 conv with this OUTPUT shape takes the split-precision kernel under the training switch."""
+    return _bf16x3_route(TRAIN_CONV_PRECISION, B, Cin, Cout, H, W)
+
+
+def _modulated_config(config, modulated):
+    return config + 4 if modulated and config < 4 else config     # the modulated variant is built for the half-depth-chunk configs
+
+
+def conv3x3_route(B, Cin, Cout, H, W, *, precision=None, groups=1, modulated=False, up_w=None, wino_ok=True):
+    """-> ("bf16x3" | "wino" | "direct", tile config or -1): the kernel a 3x3 stride-1 conv with this OUTPUT shape runs on.
+    ``precision``: "f32" or "bf16x3" (None: the training switch ``TRAIN_CONV_PRECISION``; "f32" for callers that never take the
+    split-precision kernel).  What the chooser cannot see comes from the call site: ``modulated`` (a batch-scaled input: the
+    direct kernel's half-depth-chunk configs), ``up_w`` (the input width of a x2 layer whose Winograd form reads the
+    materialised x2 image: whole 4-pixel input rows only) and ``wino_ok`` (the caller can feed the Winograd kernel at all)."""
+    if _bf16x3_route(TRAIN_CONV_PRECISION if precision is None else precision, B, Cin, Cout, H, W):
+        return "bf16x3", -1
+    if wino_ok and (up_w is None or up_w % 4 == 0) and use_wino(B, Cin, Cout, H, W, groups):
+        return "wino", -1
+    return "direct", _modulated_config(conv2d_pick_config(3, 1, B, Cin, Cout, H, W), modulated)
+
+
+def conv3x3(x, images, Cout, route, *, transpose_flip=False, upsample=False, up_fir=False, **epilogue):
+    """One eager 3x3 stride-1 conv on the kernel ``route`` names (``conv3x3_route``).  ``images(key, transpose_flip)`` -> (the
+    packed image ``key`` names -- see ``pack_image`` --, a device scalar for ``out_scale_dev`` or None).  A x2 layer
+    (``upsample``) on the Winograd kernel first materialises its input: bilinear, or -- ``up_fir`` -- upfirdn2d(up=2,
+    [1,3,3,1]); the other kernels interpolate while staging.  ``epilogue``: the keywords of ``conv2d_fused``."""
+    kind, config = route
+    image, scale_dev = images(config if kind == "direct" else kind, transpose_flip)
+    if scale_dev is not None:
+        epilogue["out_scale_dev"] = scale_dev
+    if kind == "bf16x3":
+        return conv3x3_bf16x3(x, image, Cout, upsample=upsample, up_fir=up_fir, **epilogue)
+    if kind == "wino":
+        if upsample:
+            x = upsample2x(x, zero_border=True) if up_fir else upsample2x_bilinear(x)
+        return conv3x3_wino(x, image, Cout, **epilogue)
+    return conv2d_fused(x, image, Cout, 3, 1, config=config, upsample=upsample, up_fir=up_fir, **epilogue)
+
+
+def pack_image(weight: torch.Tensor, key, transpose_flip=False, out=None) -> torch.Tensor:
+    """The packed image ``key`` names: "wino" (``pack_conv_weight_wino``), "bf16x3" (``pack_conv_weight_bf16x3``) or a tile config
+    of the direct kernel (``pack_conv_weight``)."""
+    if key == "wino":
+        return pack_conv_weight_wino(weight, out=out, transpose_flip=transpose_flip)
+    if key == "bf16x3":
+        return pack_conv_weight_bf16x3(weight, out=out, transpose_flip=transpose_flip)
+    return pack_conv_weight(weight, key, transpose_flip, out=out)
+
+
+def empty_image(key, Cin, Cout, device) -> torch.Tensor:
+    """An unfilled buffer the size of the forward image ``key`` of a [Cout,Cin,3,3] weight (for ``pack_image(..., out=)``)."""
+    if key == "bf16x3":
+        return torch.empty(L.lib().spk_conv2d_packed_bytes_bf16x3(Cin, Cout), device=device, dtype=torch.uint8)
+    n = L.lib().spk_conv2d_packed_bytes_wino(Cin, Cout) // 4 if key == "wino" else L.lib().spk_conv2d_packed_floats(key, 3, 3, Cin, Cout)
+    return torch.empty(n, device=device, dtype=torch.float32)
 
 
 # 3x3 stride-1 spellings used by the decoder
@@ -1118,10 +1153,7 @@ def conv_transpose4x4_s2(x, weight, bias=None, packed=None):
     cfg = conv2d_pick_config(2, 1, B, Cin, 4 * Cout, H + 1, W + 1)
     wp = packed.get(weight, cfg, 3) if packed is not None else pack_conv_weight(weight, cfg, 3)
     out = torch.empty((B, Cout, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
-    d = L.Conv2dDesc(x=L.dptr(x, "x"), w_packed=L.dptr(wp, "w_packed"), bias=L.dptr(bias, "bias"), y=L.dptr(out, "out"), B=B, Cin=Cin,
-                     Cout=Cout, H=2 * H, W=2 * W, Hin=H, Win=W, kh=4, kw=4, stride=2,
-                     flags=L.CONV_TRANSPOSE4X4_S2 | (L.EPI_BIAS if bias is not None else 0), lrelu_slope=1.0, out_scale=1.0,
-                     config=int(cfg), ksplit=1, groups=1, group_in_stride=0)
+    d, _ = conv_desc(x, wp, Cout, 4, 2, flags=L.CONV_TRANSPOSE4X4_S2, out=out, hw=(2 * H, 2 * W), bias=bias, config=cfg)
     _launch_conv2d(d)
     return out
 
@@ -1203,16 +1235,9 @@ def _dgrad_s2_parity(g, weight_packed, Cin, in_hw, config, out, accumulate, grou
         out = torch.empty((B, G * Cin, H, W), device=g.device, dtype=torch.float32)
     elif tuple(out.shape) != (B, G * Cin, H, W) or not out.is_contiguous():
         raise L.SpkError("conv2d_dgrad: out must be a contiguous [B, groups*Cin, H, W] tensor")
-    d = L.Conv2dDesc(x=L.dptr(g, "g"), w_packed=L.dptr(weight_packed, "w_packed"), y=L.dptr(out, "out"), B=B, Cin=Cg // G,
-                     Cout=Cin, H=H, W=W, Hin=Hg, Win=Wg, kh=3, kw=3, stride=2,
-                     flags=L.CONV_DGRAD_S2 | (L.EPI_ACCUM if accumulate else 0), lrelu_slope=1.0, out_scale=1.0,
-                     config=int(config), ksplit=0, groups=G, group_in_stride=0 if G == 1 else Cg // G,
-                     out_scale_dev=L.dptr(out_scale_dev, "out_scale_dev"))
-    ws_bytes = L.lib().spk_conv2d_dgrad_s2_workspace_bytes(B, Cg // G, Cin, Hg, Wg, H, W, G)
-    if ws_bytes > 0:                # a small gradient plane: the exact-tap kernel runs its contraction in slices
-        ws = _workspace(g.device, ws_bytes)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    _launch_conv2d(d)
+    d, ws_bytes = conv_desc(g, weight_packed, Cin, 3, 2, flags=L.CONV_DGRAD_S2, out=out, hw=(H, W), accumulate=accumulate,
+                            config=config, groups=G, out_scale_dev=out_scale_dev)
+    _run_conv2d(d, ws_bytes, g.device)        # (a small gradient plane: the exact-tap kernel runs its contraction in slices)
     return out
 
 

@@ -62,100 +62,39 @@ class LaunchPlan:
     def track(self, *params):
         self._params.extend(params)
 
-    # layers with at least this many output pixels (batch x H x W) take the split-precision path when the plan asks for it:
-    # below it the 64co x 256px blocks cannot fill 256 CUs without a split-K the bf16x3 kernel does not have (B = 8: the
-    # 16^2 layers up -- 93-96 us against 104-109 for the f32 kernel there, 83-88 against 40-43 at 8^2)
-    BF16X3_MIN_PIXELS = 2048
-
     def conv(self, x, weight, Cout, *, bias=None, noise_w=None, noise=None, style=None, upsample=False, up_fir=False, slope=None,
              out, out_scale=1.0, batch_scale=None, demod=None, act_gain=1.0, precision="f32"):
-        """One fused 3x3 stride-1 conv launch (the descriptor ``ops.conv2d_fused`` would build), weights packed here.
-        ``precision`` "bf16x3": the opt-in split-precision kernel (include/spk.h SPK_CONV_BF16X3) where it serves the shape."""
+        """One fused 3x3 stride-1 conv launch on the kernel ``ops.conv3x3_route`` picks for ``precision``, weights packed here."""
         B, Cin, Hs, Ws = x.shape
         H, W = (2 * Hs, 2 * Ws) if upsample else (Hs, Ws)
-        # (bf16x3 where it is the FASTER form: a <= 16^2 layer runs quicker -- and exactly -- on the sliced fp32 Winograd kernel)
-        if (precision == "bf16x3" and B * H * W >= self.BF16X3_MIN_PIXELS and ops.bf16x3_supported(B, Cin, Cout, H, W)
-                and not (H * W <= 256 and ops.use_wino(B, Cin, Cout, H, W))):
-            packed = torch.empty(L.lib().spk_conv2d_packed_bytes_bf16x3(Cin, Cout), device=self.device, dtype=torch.uint8)
-            self.keep.append(packed)
-            self._refreshers.append(lambda w=weight, p=packed: ops.pack_conv_weight_bf16x3(w.detach(), out=p))
-            self.track(weight)
-            flags = L.CONV_BF16X3 | (L.EPI_BIAS if bias is not None else 0) | (L.EPI_NOISE if noise is not None else 0) | \
-                (L.EPI_LRELU if slope is not None else 0) | (L.EPI_STYLE if style is not None else 0) | \
-                (L.CONV_UPSAMPLE2X if upsample else 0) | (L.CONV_UP_FIR1331 if (upsample and up_fir) else 0) | \
-                (L.CONV_IN_BATCH_SCALE if batch_scale is not None else 0)
-            d = L.Conv2dDesc(x=x.data_ptr(), w_packed=packed.data_ptr(), bias=L.dptr(bias, "bias"),
-                             noise_w=L.dptr(noise_w, "noise_w") if noise is not None else None,
-                             noise=noise.data_ptr() if noise is not None else None,
-                             style=style.data_ptr() if style is not None else None,
-                             in_scale=batch_scale.data_ptr() if batch_scale is not None else None, in_shift=None,
-                             out_scale_bc=demod.data_ptr() if demod is not None else None, act_gain=float(act_gain), stats=None,
-                             y=out.data_ptr(), y_pre=None, B=B, Cin=Cin, Cout=Cout, H=H, W=W, Hin=Hs, Win=Ws, kh=3, kw=3, stride=1,
-                             style_stride=int(style.stride(0)) if style is not None else 0, flags=flags,
-                             lrelu_slope=float(slope if slope is not None else 1.0), out_scale=float(out_scale), config=-1,
-                             ksplit=1, workspace=None, workspace_bytes=0, groups=1, group_in_stride=0, stats_slots=0)
-            return self.add(L.OP_CONV2D, d)
-        if ops.use_wino(B, Cin, Cout, H, W) and (not upsample or Ws % 4 == 0):
-            # fp32 Winograd F(2x2, 3x3) (include/spk.h SPK_CONV_WINOGRAD); a x2 layer first writes its upsampled input (one
-            # HBM-bound launch: the separate nn.Upsample of styleganv1.py:621,624) -- the transform would cost more inside the
-            # MFMA kernel than this pass does beside it
-            if upsample:
-                need = B * Cin * H * W                    # one scratch image for all x2 layers: launches are stream-ordered
-                if self._up_scratch is None or self._up_scratch.numel() < need:
-                    self._up_scratch = self.buf(need)
-                    for a_, n_ in self._up_users:           # earlier, smaller users move into the larger buffer
-                        a_.y = self._up_scratch.data_ptr()
-                        n_.x = self._up_scratch.data_ptr()
-                xu = self._up_scratch[:need].view(B, Cin, H, W)
-                up_op = self.add(L.OP_UPSAMPLE2X, L.Upsample2xArgs(x=x.data_ptr(), y=xu.data_ptr(), planes=B * Cin, Hin=Hs, Win=Ws,
-                                                                   zero_border=1 if up_fir else 0))
-                x = xu
-            packed = self.buf(L.lib().spk_conv2d_packed_bytes_wino(Cin, Cout) // 4)
-            self._refreshers.append(lambda w=weight, p=packed: ops.pack_conv_weight_wino(w.detach(), out=p))
-            self.track(weight)
-            flags = L.CONV_WINOGRAD | (L.EPI_BIAS if bias is not None else 0) | (L.EPI_NOISE if noise is not None else 0) | \
-                (L.EPI_LRELU if slope is not None else 0) | (L.EPI_STYLE if style is not None else 0) | \
-                (L.CONV_IN_BATCH_SCALE if batch_scale is not None else 0)
-            d = L.Conv2dDesc(x=x.data_ptr(), w_packed=packed.data_ptr(), bias=L.dptr(bias, "bias"),
-                             noise_w=L.dptr(noise_w, "noise_w") if noise is not None else None,
-                             noise=noise.data_ptr() if noise is not None else None,
-                             style=style.data_ptr() if style is not None else None,
-                             in_scale=batch_scale.data_ptr() if batch_scale is not None else None, in_shift=None,
-                             out_scale_bc=demod.data_ptr() if demod is not None else None, act_gain=float(act_gain), stats=None,
-                             y=out.data_ptr(), y_pre=None, B=B, Cin=Cin, Cout=Cout, H=H, W=W, Hin=H, Win=W, kh=3, kw=3, stride=1,
-                             style_stride=int(style.stride(0)) if style is not None else 0, flags=flags,
-                             lrelu_slope=float(slope if slope is not None else 1.0), out_scale=float(out_scale), config=-1,
-                             ksplit=0, workspace=None, workspace_bytes=0, groups=1, group_in_stride=0, stats_slots=0)
-            # (few regions: the contraction runs in slices through the plan's split-K workspace, spk_conv2d_wino_ksplit)
-            self._ws_bytes = max(self._ws_bytes, L.lib().spk_conv2d_wino_workspace_bytes(0, B, Cin, Cout, H, W))
-            if upsample:
-                self._up_users.append((up_op, d))
-            return self.add(L.OP_CONV2D, d)
-        cfg = ops.conv2d_pick_config(3, 1, B, Cin, Cout, H, W)
-        if batch_scale is not None and cfg < 4:
-            cfg += 4
-        n = L.lib().spk_conv2d_packed_floats(cfg, 3, 3, Cin, Cout)
-        packed = self.buf(n)
-        self._refreshers.append(lambda w=weight, p=packed, c=cfg: ops.pack_conv_weight(w.detach(), c, out=p))
+        kind, cfg = ops.conv3x3_route(B, Cin, Cout, H, W, precision=precision, modulated=batch_scale is not None,
+                                      up_w=Ws if upsample else None)
+        up_op = None
+        if kind == "wino" and upsample:
+            # a x2 layer first writes its upsampled input (one HBM-bound launch: the separate nn.Upsample of
+            # styleganv1.py:621,624) -- the transform would cost more inside the MFMA kernel than this pass does beside it
+            need = B * Cin * H * W                    # one scratch image for all x2 layers: launches are stream-ordered
+            if self._up_scratch is None or self._up_scratch.numel() < need:
+                self._up_scratch = self.buf(need)
+                for a_, n_ in self._up_users:           # earlier, smaller users move into the larger buffer
+                    a_.y = self._up_scratch.data_ptr()
+                    n_.x = self._up_scratch.data_ptr()
+            xu = self._up_scratch[:need].view(B, Cin, H, W)
+            up_op = self.add(L.OP_UPSAMPLE2X, L.Upsample2xArgs(x=x.data_ptr(), y=xu.data_ptr(), planes=B * Cin, Hin=Hs, Win=Ws,
+                                                               zero_border=1 if up_fir else 0))
+            x, upsample = xu, False
+        key = cfg if kind == "direct" else kind
+        packed = ops.empty_image(key, Cin, Cout, self.device)
+        self.keep.append(packed)
+        self._refreshers.append(lambda w=weight, p=packed, k=key: ops.pack_image(w.detach(), k, out=p))
         self.track(weight)
-        ws_bytes = L.lib().spk_conv2d_workspace_bytes_grouped(int(cfg), 0, 3, 3, 1, B, Cin, Cout, H, W, 1)
-        if ws_bytes < 0:
-            raise L.SpkError(f"plan: config {cfg} cannot host 3x3 shape {(B, Cin, Cout, H, W)}")
-        self._ws_bytes = max(self._ws_bytes, ws_bytes)
-        flags = (L.EPI_BIAS if bias is not None else 0) | (L.EPI_NOISE if noise is not None else 0) | \
-                (L.EPI_LRELU if slope is not None else 0) | (L.EPI_STYLE if style is not None else 0) | \
-                (L.CONV_UPSAMPLE2X if upsample else 0) | (L.CONV_UP_FIR1331 if (upsample and up_fir) else 0) | \
-                (L.CONV_IN_BATCH_SCALE if batch_scale is not None else 0)
-        d = L.Conv2dDesc(x=x.data_ptr(), w_packed=packed.data_ptr(), bias=L.dptr(bias, "bias"),
-                         noise_w=L.dptr(noise_w, "noise_w") if noise is not None else None,
-                         noise=noise.data_ptr() if noise is not None else None,
-                         style=style.data_ptr() if style is not None else None,
-                         in_scale=batch_scale.data_ptr() if batch_scale is not None else None, in_shift=None,
-                         out_scale_bc=demod.data_ptr() if demod is not None else None, act_gain=float(act_gain), stats=None,
-                         y=out.data_ptr(), y_pre=None, B=B, Cin=Cin, Cout=Cout, H=H, W=W, Hin=Hs, Win=Ws, kh=3, kw=3, stride=1,
-                         style_stride=int(style.stride(0)) if style is not None else 0, flags=flags,
-                         lrelu_slope=float(slope if slope is not None else 1.0), out_scale=float(out_scale), config=int(cfg),
-                         ksplit=0, workspace=None, workspace_bytes=0, groups=1, group_in_stride=0, stats_slots=0)
+        d, ws_bytes = ops.conv_desc(x, packed, Cout, flags={"wino": L.CONV_WINOGRAD, "bf16x3": L.CONV_BF16X3}.get(kind, 0), out=out,
+                                    bias=bias, noise_w=noise_w, noise=noise, style=style, upsample=upsample, up_fir=up_fir,
+                                    lrelu_slope=slope, out_scale=out_scale, batch_scale=batch_scale, demod=demod, act_gain=act_gain,
+                                    config=cfg)
+        self._ws_bytes = max(self._ws_bytes, ws_bytes)      # (plan-wide split-K scratch, attached in ``finish``)
+        if up_op is not None:
+            self._up_users.append((up_op, d))
         return self.add(L.OP_CONV2D, d)
 
     def fc(self, x, lin_weight, lin_bias, wmul, bmul, slope, out):
@@ -296,7 +235,7 @@ class DecoderPlan(LaunchPlan):
                 self.track(conv.bias, nmod.weight)
                 # the LAST conv (64 channels at full resolution): fp32 Winograd with toRGB in its epilogue beats the bf16x3 kernel + a toRGB pass
                 last_conv = i == len(s.layers) - 1 and half == 1 and FUSE_TORGB and Cout <= 64 and s.to_rgb.weight.shape[0] == 3 and \
-                    ops.use_wino(B, x.shape[1], Cout, H, H) and ops.wino_ksplit(B, x.shape[1], Cout, H, H) == 1
+                    ops.conv3x3_route(B, x.shape[1], Cout, H, H, precision="f32")[0] == "wino" and ops.wino_ksplit(B, x.shape[1], Cout, H, H) == 1
                 d = self.conv(x, conv.weight, Cout, bias=conv.bias, noise_w=nmod.weight, noise=self.noise_views[k],
                               style=self.styles[k], upsample=up, slope=LRELU, out=y, precision="f32" if last_conv else precision)
                 self.noise_ops.append(d)

@@ -84,15 +84,10 @@ class ModulatedConv2d(nn.Module):
         if d is not None:        # a demodulation vector computed elsewhere (the grouped launch of the inference path)
             B, Cin, Hs, Ws = x.shape
             H, W = (2 * Hs, 2 * Ws) if upsample else (Hs, Ws)
-            if ops.use_wino(B, Cin, self.out_channel, H, W) and (not upsample or Ws % 4 == 0):
-                xin = ops.upsample2x(x, zero_border=True) if upsample else x.contiguous()
-                return ops.conv3x3_wino(xin, self._pk.get_wino(self.weight), self.out_channel, bias=bias, noise_w=noise_w, noise=noise,
-                                        lrelu_slope=lrelu, out_scale=self.scale, batch_scale=s.contiguous(), demod=d, act_gain=act_gain)
-            cfg = ops.conv2d_pick_config(3, 1, B, Cin, self.out_channel, H, W)
-            cfg = cfg + 4 if cfg < 4 else cfg
-            return ops.conv2d_fused(x.contiguous(), self._pk.get(self.weight, cfg), self.out_channel, 3, 1, bias=bias, noise_w=noise_w,
-                                    noise=noise, lrelu_slope=lrelu, out_scale=self.scale, batch_scale=s.contiguous(), demod=d,
-                                    act_gain=act_gain, config=cfg, upsample=upsample, up_fir=True)
+            route = ops.conv3x3_route(B, Cin, self.out_channel, H, W, precision="f32", modulated=True, up_w=Ws if upsample else None)
+            return ops.conv3x3(x.contiguous(), self._pk.images(self.weight), self.out_channel, route, upsample=upsample, up_fir=True,
+                               bias=bias, noise_w=noise_w, noise=noise, lrelu_slope=lrelu, out_scale=self.scale,
+                               batch_scale=s.contiguous(), demod=d, act_gain=act_gain)
         # upfirdn2d(up=2, [1,3,3,1]) is folded into the conv's input staging: no 4x tensor in HBM; the demodulation vector and
         # its adjoint are kernels inside the Function (spk_modconv_demod / spk_modconv_demod_bwd)
         # (``weight``: this conv's weight behind the generator's AG.gate_weights node, a training pass)

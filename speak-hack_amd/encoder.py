@@ -67,86 +67,6 @@ class Bottleneck(nn.Module):
         self.stride = stride
 
 
-class _ConvBN:
-    """One conv + its BatchNorm in the folded form."""
-
-    def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d):
-        self.conv, self.bn = conv, bn
-        self.k, self.stride = conv.kernel_size[0], conv.stride[0]
-        self.packed = ops.PackedConvWeight()
-
-    def fwd(self, x, in_affine, training, stats_pool, keep):
-        """-> record {y: raw conv output, affine: (scale, shift) its consumer applies, ...}."""
-        conv, bn = self.conv, self.bn
-        B, Cin, H, W = x.shape
-        Cout = conv.out_channels
-        Ho, Wo = ops.conv_out_size(H, self.k, self.stride), ops.conv_out_size(W, self.k, self.stride)
-        cfg = ops.conv2d_pick_config(self.k, self.stride, B, Cin, Cout, Ho, Wo)
-        stats = stats_pool.take(ops.stats_slots(cfg, self.k, self.stride, B, Cin, Cout, Ho, Wo) * 2 * Cout) if training else None
-        y = ops.conv2d_fused(x, self.packed.get(conv.weight, cfg), Cout, self.k, self.stride, in_affine=in_affine,
-                             stats=stats, config=cfg)
-        if training:
-            if bn.num_batches_tracked is not None:
-                if bn.momentum is None:
-                    bn.num_batches_tracked += 1                      # cumulative average: the count is needed right now
-                else:
-                    stats_pool.counters.append(bn.num_batches_tracked)   # bumped together at the end of the pass
-            momentum = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-            fin = ops.bn_finalize(stats, B * Ho * Wo, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum,
-                                  bn.eps, save=keep)
-        else:
-            fin = ops.bn_finalize(None, 1, bn.weight, bn.bias, bn.running_mean, bn.running_var, 0.0, bn.eps, save=keep)
-        rec = {"y": y, "affine": (fin[0], fin[1])}
-        if keep:
-            rec.update(x=x, in_affine=in_affine, mean=fin[2], invstd=fin[3], training=training)
-            if training:
-                rec.update(stats=stats[:2 * Cout], count=B * Ho * Wo, momentum=momentum)   # copy 0 = the totals now
-        return rec
-
-    def second_update(self, rec, counters, replay):
-        """The running-statistics update the reference's re-entrant checkpoint performs a second time when it re-runs
-        the forward inside backward (model.py:84-90): same batch sums, same arithmetic, without recomputing the conv.
-        Queued on ``replay``: every BatchNorm of the pass is updated by one launch (``ops.bn_replay_running``)."""
-        bn = self.bn
-        if not rec.get("training") or "stats" not in rec:
-            return
-        if bn.num_batches_tracked is not None:
-            counters.append(bn.num_batches_tracked)
-        replay.append((rec["momentum"], rec["stats"], rec["count"], bn.running_mean, bn.running_var))
-
-    def put_bn_grads(self, grads, dg, db):
-        grads[self.bn.weight], grads[self.bn.bias] = dg, db
-
-    def bn_bwd(self, rec, g, mask_mode, mask_src=None, want_dz=False, **kw):
-        """Gradient w.r.t. the raw conv output + BatchNorm parameter gradients (into ``grads``)."""
-        out = ops.bn_backward(g, rec["y"], rec["affine"], rec["mean"], rec["invstd"], mask_mode, mask_src,
-                              want_dz=want_dz, batch_stats=rec["training"], **kw)
-        return out
-
-    def conv_bwd(self, rec, dr, grads, need_dx, dx_out=None, accumulate=False, dilate=True, half=None, side=None):
-        """Weight gradient (into ``grads``) and, if asked, the gradient w.r.t. the conv's (staged) input.  ``dilate=False``
-        (a strided 1x1): that gradient stays at the conv's output size; ``half``: such a tensor, added at the even pixels."""
-        conv = self.conv
-        Cout, Cin = conv.out_channels, conv.in_channels
-        x = rec["x"]
-        B, _, H, W = x.shape
-        grads[conv.weight] = _wgrad_aside(side, dr, lambda: ops.conv2d_wgrad(dr, x, Cout, Cin, self.k, self.stride,
-                                                                            in_affine=rec["in_affine"]))
-        if not need_dx:
-            return None
-        aligned = dr.data_ptr() % 16 == 0 and (dx_out is None or dx_out.data_ptr() % 16 == 0)
-        if (self.k == 3 and self.stride == 1 and half is None
-                and ops.conv3x3_route(B, Cout, Cin, H, W, precision="f32", wino_ok=aligned)[0] == "wino"):
-            # fp32 Winograd F(2x2, 3x3) data gradient (ops.CONV3X3_ALGO)
-            return ops.conv3x3_wino(dr.contiguous(), self.packed.get_wino(conv.weight, transpose_flip=True), Cin, out=dx_out, accumulate=accumulate)
-        cfg, tf = ops.dgrad_plan(self.k, self.stride, B, Cout, Cin, (H, W), dr.shape[-2:], dx_out, accumulate)
-        if half is not None and (cfg not in ops.GEMM2_CONFIGS or W % 4):
-            dx_out, accumulate, half = ops.dilate2x(half, H, W), True, None     # the form that cannot add it in its epilogue
-            cfg, tf = ops.dgrad_plan(self.k, self.stride, B, Cout, Cin, (H, W), dr.shape[-2:], dx_out, accumulate)
-        return ops.conv2d_dgrad(dr, self.packed.get(conv.weight, cfg, transpose_flip=tf), Cin, self.k, self.stride,
-                                (H, W), cfg, out=dx_out, accumulate=accumulate, dilate=dilate, accum_half=half)
-
-
 class _StatsPool:
     """Zeroed fp64 pages per forward, sliced per BatchNorm (a few memsets instead of 53).  ``total`` = the sums of one
     copy of every BatchNorm; the high-resolution layers take several copies (``ops.stats_slots``), so the pool grows by
@@ -169,65 +89,40 @@ class _StatsPool:
         return out
 
 
-class _GroupPacked:
-    """The packed images of a group's weights one after another (what a grouped launch reads), cached like
-    ``ops.PackedConvWeight``."""
-
-    def __init__(self):
-        self._cache = {}
-
-    def get(self, weights, config, transpose_flip=False):
-        key = (config, transpose_flip)
-        stamp = tuple((w.data_ptr(), w._version) for w in weights)
-        hit = self._cache.get(key)
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
-        # one launch into the previous image's storage (same key = same size): no per-tensor packs, no concatenation
-        packed = ops.pack_conv_weights_list([w.detach() for w in weights], config, transpose_flip,
-                                            out=hit[1] if hit is not None else None)
-        self._cache[key] = (stamp, packed)
-        return packed
-
-    def get_wino(self, weights, transpose_flip=False):
-        """The groups' Winograd images U = G g G^T one after another (one list-pack launch), cached the same way."""
-        key = ("wino", bool(transpose_flip))
-        stamp = tuple((w.data_ptr(), w._version) for w in weights)
-        hit = self._cache.get(key)
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
-        Cout, Cin = weights[0].shape[:2]
-        n = (ops.L.lib().spk_conv2d_packed_bytes_wino(Cout, Cin) if transpose_flip else ops.L.lib().spk_conv2d_packed_bytes_wino(Cin, Cout)) // 4
-        packed = hit[1] if hit is not None else torch.empty(len(weights) * n, device=weights[0].device, dtype=torch.float32)
-        ops.pack_conv_weights_wino_into([w.detach() for w in weights], [packed[i * n:(i + 1) * n] for i in range(len(weights))], transpose_flip)
-        self._cache[key] = (stamp, packed)
-        return packed
-
-
 _PENDING_BN = "_pending_bn_grads"      # key (never a Parameter) under which per-image BatchNorm gradients wait for their fold
 
 
-class _GroupedConvBN:
-    """The same conv + BatchNorm position of G trunks as ONE grouped launch (channels of the groups side by side).
-    BatchNorm is per channel, so statistics, the folded affine, the residual add, the pools and the BatchNorm backward
-    need nothing new: they simply see G*C channels.  ``flat`` = (gamma, beta, running_mean, running_var) of the G
-    BatchNorms concatenated, provided per pass by ``GroupedTrunks``."""
+class _ConvBN:
+    """The same conv + BatchNorm position of G >= 1 trunks as ONE launch (G > 1: a grouped launch, the channels of the groups
+    side by side).  BatchNorm is per channel, so statistics, the folded affine, the residual add, the pools and the BatchNorm
+    backward need nothing new for G > 1: they simply see G*C channels.  G = 1 reads and updates the BatchNorm's own tensors;
+    G > 1 reads ``flat`` = (gamma, beta, running_mean, running_var) of the G BatchNorms concatenated, provided per pass by
+    ``GroupedTrunks``."""
 
     def __init__(self, members, shared_input=False):
-        self.convs, self.bns = [m.conv for m in members], [m.bn for m in members]
+        """``members``: the (conv, bn) pairs of the trunks, repeated once per image.  ``shared_input``: every group reads the
+        same input channels."""
+        self.convs, self.bns = [c for c, _ in members], [b for _, b in members]
         self.G = len(members)
-        self.uniq = []                       # distinct trunks among the members (members repeat once per image)
-        for m in members:
-            if not any(m is u for u in self.uniq):
-                self.uniq.append(m)
-        self.k, self.stride = members[0].k, members[0].stride
-        self.shared_input = shared_input
-        self.packed = _GroupPacked()
+        self.T = len({id(c) for c in self.convs})        # distinct trunks: the first T members
+        self.k, self.stride = self.convs[0].kernel_size[0], self.convs[0].stride[0]
+        self.shared_input = shared_input and self.G > 1
+        self.packed = ops.PackedConvWeight()
         self.flat = None
 
     def _weights(self):
         return [c.weight for c in self.convs]
 
+    def _per_trunk(self, t):
+        """``t`` (the distinct trunks' parts side by side along dim 0) as one tensor per trunk."""
+        return (t,) if self.T == 1 else t.view(self.T, -1, *t.shape[1:]).unbind(0)
+
+    def _bn_tensors(self):
+        bn = self.bns[0]
+        return self.flat if self.G > 1 else (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+
     def fwd(self, x, in_affine, training, stats_pool, keep):
+        """-> record {y: raw conv output, affine: (scale, shift) its consumer applies, ...}."""
         conv, bn, G = self.convs[0], self.bns[0], self.G
         B, _, H, W = x.shape
         Cin, Cout = conv.in_channels, conv.out_channels
@@ -236,34 +131,41 @@ class _GroupedConvBN:
         stats = stats_pool.take(ops.stats_slots(cfg, self.k, self.stride, B, Cin, Cout, Ho, Wo) * 2 * G * Cout) if training else None
         y = ops.conv2d_fused(x, self.packed.get(self._weights(), cfg), Cout, self.k, self.stride, in_affine=in_affine,
                              stats=stats, config=cfg, groups=G, shared_input=self.shared_input)
-        gamma, beta, rm, rv = self.flat
+        gamma, beta, rm, rv = self._bn_tensors()
         if training:
-            if bn.momentum is None:
-                raise NotImplementedError("grouped encoders: cumulative-average BatchNorm (momentum=None) is not supported")
-            # distinct counters only; the pass bumps them by the number of images it carries
-            stats_pool.counters.extend(b.num_batches_tracked for b in self.bns[:len(self.uniq)] if b.num_batches_tracked is not None)
-            fin = ops.bn_finalize(stats, B * Ho * Wo, gamma, beta, rm, rv, bn.momentum, bn.eps, save=keep)
+            momentum = bn.momentum
+            if momentum is None:
+                if G > 1:
+                    raise NotImplementedError("grouped encoders: cumulative-average BatchNorm (momentum=None) is not supported")
+                if bn.num_batches_tracked is not None:
+                    bn.num_batches_tracked += 1                  # cumulative average: the count is needed right now
+                momentum = 1.0 / float(bn.num_batches_tracked)
+            else:
+                # distinct counters only; the pass bumps them together at its end, by the number of images it carries
+                stats_pool.counters.extend(b.num_batches_tracked for b in self.bns[:self.T] if b.num_batches_tracked is not None)
+            fin = ops.bn_finalize(stats, B * Ho * Wo, gamma, beta, rm, rv, momentum, bn.eps, save=keep)
         else:
             fin = ops.bn_finalize(None, 1, gamma, beta, rm, rv, 0.0, bn.eps, save=keep)
         rec = {"y": y, "affine": (fin[0], fin[1])}
         if keep:
             rec.update(x=x, in_affine=in_affine, mean=fin[2], invstd=fin[3], training=training)
             if training:
-                rec.update(stats=stats[:2 * G * Cout], count=B * Ho * Wo, momentum=bn.momentum)   # copy 0 = the totals now
+                rec.update(stats=stats[:2 * G * Cout], count=B * Ho * Wo, momentum=momentum)   # copy 0 = the totals now
         return rec
 
     def second_update(self, rec, counters, replay):
+        """The running-statistics update the reference's re-entrant checkpoint performs a second time when it re-runs
+        the forward inside backward (model.py:84-90): same batch sums, same arithmetic, without recomputing the conv.
+        Queued on ``replay``: every BatchNorm of the pass is updated by one launch (``ops.bn_replay_running``)."""
         if not rec.get("training") or "stats" not in rec:
             return
-        counters.extend(b.num_batches_tracked for b in self.bns[:len(self.uniq)] if b.num_batches_tracked is not None)
-        gamma, beta, rm, rv = self.flat
-        replay.append((rec["momentum"], rec["stats"], rec["count"], rm, rv))
+        counters.extend(b.num_batches_tracked for b in self.bns[:self.T] if b.num_batches_tracked is not None)
+        replay.append((rec["momentum"], rec["stats"], rec["count"], *self._bn_tensors()[2:]))
 
     def put_bn_grads(self, grads, dg, db):
-        if self.G == len(self.uniq):
-            for q in range(len(self.uniq)):
-                bn = self.bns[q]
-                grads[bn.weight], grads[bn.bias] = dg.view(self.G, -1)[q], db.view(self.G, -1)[q]
+        if self.G == self.T:
+            for bn, g, b in zip(self.bns, self._per_trunk(dg), self._per_trunk(db)):
+                grads[bn.weight], grads[bn.bias] = g, b
         else:       # several images per trunk: folded for all layers at once at the end of the pass (flush_bn_grads)
             grads.setdefault(_PENDING_BN, []).append((self, dg, db))
 
@@ -274,11 +176,11 @@ class _GroupedConvBN:
         pend = grads.pop(_PENDING_BN, None)
         if not pend:
             return
-        imgs = pend[0][0].G // len(pend[0][0].uniq)
+        imgs = pend[0][0].G // pend[0][0].T
         flat = torch.cat([t.view(imgs, -1) for _, dg, db in pend for t in (dg, db)], 1).sum(0)
         off = 0
         for m, dg, db in pend:
-            T, n = len(m.uniq), dg.numel() // m.G
+            T, n = m.T, dg.numel() // m.G
             for which in range(2):
                 part = flat[off:off + T * n].view(T, n)
                 off += T * n
@@ -287,20 +189,21 @@ class _GroupedConvBN:
                     grads[bn.weight if which == 0 else bn.bias] = part[q]
 
     def bn_bwd(self, rec, g, mask_mode, mask_src=None, want_dz=False, **kw):
+        """Gradient w.r.t. the raw conv output + BatchNorm parameter gradients."""
         return ops.bn_backward(g, rec["y"], rec["affine"], rec["mean"], rec["invstd"], mask_mode, mask_src,
                                want_dz=want_dz, batch_stats=rec["training"], **kw)
 
     def conv_bwd(self, rec, dr, grads, need_dx, dx_out=None, accumulate=False, dilate=True, half=None, side=None):
-        conv, G = self.convs[0], self.G
+        """Weight gradients (into ``grads``) and, if asked, the gradient w.r.t. the conv's (staged) input.  ``dilate=False``
+        (a strided 1x1): that gradient stays at the conv's output size; ``half``: such a tensor, added at the even pixels."""
+        conv, G, T = self.convs[0], self.G, self.T
         Cout, Cin = conv.out_channels, conv.in_channels
         x = rec["x"]
         B, _, H, W = x.shape
-        T = len(self.uniq)
         dw = _wgrad_aside(side, dr, lambda: ops.conv2d_wgrad(dr, x, Cout, Cin, self.k, self.stride, in_affine=rec["in_affine"],
                                                              groups=G, shared_input=self.shared_input, fold=G // T))
-        dw = dw.view(T, Cout, Cin, self.k, self.k)
-        for q in range(T):
-            grads[self.convs[q].weight] = dw[q]
+        for c, dw_q in zip(self.convs, self._per_trunk(dw)):
+            grads[c.weight] = dw_q
         if not need_dx:
             return None
         aligned = dr.data_ptr() % 16 == 0 and (dx_out is None or dx_out.data_ptr() % 16 == 0)
@@ -323,7 +226,8 @@ class GroupedTrunks:
     ResNet-50 at batch 8 cannot fill 256 CUs).  Feature order = trunk order: [B, G*2048, 1, 1].  Parameters stay where
     they are (each trunk's own modules, so ``state_dict`` and checkpoints are unchanged); per pass the BatchNorm vectors
     are gathered into flat tensors with four ``torch.cat`` calls and the running statistics written back with two
-    ``torch._foreach_copy_`` calls."""
+    ``torch._foreach_copy_`` calls.  One trunk and one image (what ``ResNet50Trunk.forward`` runs) is the plain network:
+    every layer reads and updates its BatchNorm directly."""
 
     def __init__(self, trunks, images=1):
         """``images`` = 2: one pass takes TWO images (``group(x_s, x_t)``): the network then has 2*G groups -- every
@@ -332,8 +236,14 @@ class GroupedTrunks:
         running statistics receive the two momentum updates in the reference's order (x_s, then x_t)."""
         self.trunks = list(trunks)
         self.images = int(images)
+        self.groups = len(self.trunks) * self.images
         self._plan = None
-        self.recompute = False
+
+    @property
+    def recompute(self):
+        """See ``TrunkFn``: the trunks' own flag.  Two images per pass keep their activations (a recomputation would replay
+        the running-statistics updates in the forward's image order, not the checkpoint's)."""
+        return self.images == 1 and all(t.recompute for t in self.trunks)
 
     @property
     def training(self):
@@ -348,17 +258,14 @@ class GroupedTrunks:
         for t in self.trunks:
             yield from t.parameters()
 
+    # -- launch plan: built lazily so that parameter replacement (.to(), load_state_dict) is honoured
     def _build_plan(self):
-        plans = []
-        for t in self.trunks:
-            t._build_plan()
-            plans.append(t._plan)
         rep = self.images
-        stem = _GroupedConvBN([p[0] for p in plans] * rep, shared_input=(rep == 1))
-        blocks = []
-        for parts in zip(*[p[1] for p in plans]):
-            blocks.append(tuple(_GroupedConvBN([b[i] for b in parts] * rep) if parts[0][i] is not None else None for i in range(4)))
-        self._stats_total = rep * len(self.trunks) * self.trunks[0]._stats_total
+        stems, blocks = zip(*(t.conv_bn_pairs() for t in self.trunks))
+        stem = _ConvBN(list(stems) * rep, shared_input=(rep == 1))
+        blocks = [tuple(_ConvBN([b[i] for b in parts] * rep) if parts[0][i] is not None else None for i in range(4))
+                  for parts in zip(*blocks)]
+        self._stats_total = rep * sum(2 * m.num_features for t in self.trunks for m in t.modules() if isinstance(m, nn.BatchNorm2d))
         self._plan = (stem, blocks)
         self._members = [stem] + [c for blk in blocks for c in blk if c is not None]
 
@@ -386,7 +293,7 @@ class GroupedTrunks:
             #   = (1-m)*slice_a + slice_b - (1-m)*r0.
             bufs, a, b, pos = [], [], [], 0
             for m in ms:
-                T = len(m.uniq)
+                T = m.T
                 for q in range(T):
                     bufs.append(get(m.bns[q]))
                     s_img, t_img = parts[pos + q], parts[pos + T + q]
@@ -399,109 +306,11 @@ class GroupedTrunks:
             torch._foreach_add_(bufs, a, alpha=keep)
 
     def _run(self, x, keep):
-        if self._plan is None:
-            self._build_plan()
-        self._load_flats()
-        out = ResNet50Trunk._run(self, x, keep)
-        if self.training:
-            self._store_running()
-        return out
-
-    def _second_bn_update(self, recs):
-        self._load_flats()
-        ResNet50Trunk._second_bn_update(self, recs)
-        self._store_running(first_image_first=False)     # the checkpoint re-runs the later call (x_t) first
-
-    def _backward(self, recs, dfeat):
-        return ResNet50Trunk._backward(self, recs, dfeat)
-
-    def __call__(self, *xs):
-        if len(xs) != self.images:
-            raise ValueError(f"GroupedTrunks: expected {self.images} image batch(es), got {len(xs)}")
-        # one image: every group reads the same three channels; two: each group gets its own copy (3 channels, negligible)
-        x = xs[0] if self.images == 1 else torch.cat([x for x in xs for _ in self.trunks], dim=1)
-        return TrunkFn.apply(x, self, torch.is_grad_enabled(), *self.parameters())
-
-
-class TrunkFn(torch.autograd.Function):
-    """The trunk under the reference's ``checkpoint(E, x)`` (model.py:84-90).
-
-    ``trunk.recompute`` True: forward keeps the input only, backward re-runs the forward, then back-propagates -- the
-    reference's memory-saving schedule.  False (default here: 288 GB of HBM, ~1 GB of activations per B=8 pass): the
-    forward keeps the raw conv outputs, backward uses them directly and replays only the checkpoint's visible side
-    effect, the second running-statistics update of every BatchNorm.  Gradients and buffers are identical either way;
-    the stored form saves one encoder forward per pass."""
-
-    @staticmethod
-    def forward(ctx, x, trunk, grad_mode, *params):
-        need = grad_mode and any(ctx.needs_input_grad)
-        if need and not trunk.recompute:
-            y, ctx.recs = trunk._run(x, keep=True)
-            ctx.trunk, ctx.training = trunk, trunk.training
-            return y
-        y = trunk._run(x, keep=False)[0]
-        if need:
-            ctx.trunk, ctx.training, ctx.recs = trunk, trunk.training, None
-            ctx.save_for_backward(x)
-        return y
-
-    @staticmethod
-    def backward(ctx, dfeat):
-        trunk = ctx.trunk
-        if ctx.recs is not None:
-            recs, ctx.recs = ctx.recs, None
-            if ctx.training:
-                trunk._second_bn_update(recs)
-        else:
-            (x,) = ctx.saved_tensors
-            was_training = trunk.training
-            trunk.train(ctx.training)
-            try:
-                _, recs = trunk._run(x, keep=True)          # the checkpoint recomputation
-            finally:
-                trunk.train(was_training)
-        grads = trunk._backward(recs, dfeat.contiguous())
-        return (None, None, None) + tuple(grads.get(p) for p in trunk.parameters())
-
-
-class ResNet50Trunk(nn.Sequential):
-    recompute = False        # see TrunkFn: keep activations (default) or re-run the forward inside backward
-
-    def __init__(self):
-        layers = []
-        inplanes = 64
-        for li, (nblk, width) in enumerate(zip(LAYERS, WIDTHS)):
-            blocks = []
-            for bi in range(nblk):
-                blocks.append(Bottleneck(inplanes, width, 2 if (bi == 0 and li > 0) else 1, bi == 0))
-                inplanes = width * EXPANSION
-            layers.append(nn.Sequential(*blocks))
-        super().__init__(nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True),
-                         nn.MaxPool2d(3, stride=2, padding=1), *layers, nn.AdaptiveAvgPool2d(1))
-        # torchvision's ResNet.__init__ init: kaiming-normal fan_out convs, BN weight 1 / bias 0
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-        self._plan = None
-
-    # -- launch plan: built lazily so that parameter replacement (.to(), load_state_dict) is honoured
-    def _build_plan(self):
-        stem = _ConvBN(self[0], self[1])
-        blocks = []
-        for li in range(4):
-            for blk in self[4 + li]:
-                blocks.append((_ConvBN(blk.conv1, blk.bn1), _ConvBN(blk.conv2, blk.bn2), _ConvBN(blk.conv3, blk.bn3),
-                               _ConvBN(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None))
-        self._stats_total = 2 * sum(m.num_features for m in self.modules() if isinstance(m, nn.BatchNorm2d))
-        self._plan = (stem, blocks)
-
-    def forward(self, x):
-        return TrunkFn.apply(x, self, torch.is_grad_enabled(), *self.parameters())
-
-    def _run(self, x, keep):
         """Forward; with ``keep`` also returns what backward needs (raw conv outputs, block outputs, statistics)."""
         if self._plan is None:
             self._build_plan()
+        if self.groups > 1:
+            self._load_flats()
         stem, blocks = self._plan
         training = self.training
         x = x.contiguous()
@@ -523,10 +332,15 @@ class ResNet50Trunk(nn.Sequential):
                 recs["blocks"].append((r1, r2, r3, rd, out))
             cur = out
         if pool is not None and pool.counters:
-            torch._foreach_add_(pool.counters, getattr(self, "images", 1))   # 53 one-element kernels -> one fused launch
-        return ops.global_avgpool(cur), recs
+            torch._foreach_add_(pool.counters, self.images)   # 53 one-element kernels -> one fused launch
+        feat = ops.global_avgpool(cur)
+        if training and self.groups > 1:
+            self._store_running()
+        return feat, recs
 
     def _second_bn_update(self, recs):
+        if self.groups > 1:
+            self._load_flats()
         stem, blocks = self._plan
         counters, replay = [], []
         stem.second_update(recs["stem"], counters, replay)
@@ -539,10 +353,12 @@ class ResNet50Trunk(nn.Sequential):
         for mom in sorted({m for m, *_ in replay}):          # one launch for all BatchNorms (per momentum value: one)
             ops.bn_replay_running([it[1:] for it in replay if it[0] == mom], mom)
         if counters:
-            torch._foreach_add_(counters, getattr(self, "images", 1))
+            torch._foreach_add_(counters, self.images)
+        if self.groups > 1:
+            self._store_running(first_image_first=False)     # the checkpoint re-runs the later call (x_t) first
 
     def _backward(self, recs, dfeat):
-        """dfeat [B,2048,1,1] -> {parameter: gradient}."""
+        """dfeat [B,G*2048,1,1] -> {parameter: gradient}."""
         side = ops.side_stream(dfeat.device)           # the weight gradients' stream (joined before the gradients are returned)
         if side is not None and torch.cuda.is_current_stream_capturing():
             side = None                                # a stream capture stays on the capturing stream
@@ -583,7 +399,89 @@ class ResNet50Trunk(nn.Sequential):
         dr0, dg, db = stem.bn_bwd(s, dv0, ops.MASK_RECOMPUTE)
         stem.put_bn_grads(grads, dg, db)
         stem.conv_bwd(s, dr0, grads, need_dx=False, side=side)       # the image itself takes no gradient
-        _GroupedConvBN.flush_bn_grads(grads)
+        _ConvBN.flush_bn_grads(grads)
         if side is not None:
             torch.cuda.current_stream(dfeat.device).wait_stream(side)     # every weight gradient is complete behind this point
         return grads
+
+    def __call__(self, *xs):
+        if len(xs) != self.images:
+            raise ValueError(f"GroupedTrunks: expected {self.images} image batch(es), got {len(xs)}")
+        # one image: every group reads the same three channels; two: each group gets its own copy (3 channels, negligible)
+        x = xs[0] if self.images == 1 else torch.cat([x for x in xs for _ in self.trunks], dim=1)
+        return TrunkFn.apply(x, self, torch.is_grad_enabled(), *self.parameters())
+
+
+class TrunkFn(torch.autograd.Function):
+    """The trunks under the reference's ``checkpoint(E, x)`` (model.py:84-90).
+
+    ``trunk.recompute`` True: forward keeps the input only, backward re-runs the forward, then back-propagates -- the
+    reference's memory-saving schedule.  False (default here: 288 GB of HBM, ~1 GB of activations per B=8 pass): the
+    forward keeps the raw conv outputs, backward uses them directly and replays only the checkpoint's visible side
+    effect, the second running-statistics update of every BatchNorm.  Gradients and buffers are identical either way;
+    the stored form saves one encoder forward per pass."""
+
+    @staticmethod
+    def forward(ctx, x, trunk, grad_mode, *params):
+        need = grad_mode and any(ctx.needs_input_grad)
+        if need and not trunk.recompute:
+            y, ctx.recs = trunk._run(x, keep=True)
+            ctx.trunk, ctx.training = trunk, trunk.training
+            return y
+        y = trunk._run(x, keep=False)[0]
+        if need:
+            ctx.trunk, ctx.training, ctx.recs = trunk, trunk.training, None
+            ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        trunk = ctx.trunk
+        if ctx.recs is not None:
+            recs, ctx.recs = ctx.recs, None
+            if ctx.training:
+                trunk._second_bn_update(recs)
+        else:
+            (x,) = ctx.saved_tensors
+            was_training = trunk.training
+            trunk.train(ctx.training)
+            try:
+                _, recs = trunk._run(x, keep=True)          # the checkpoint recomputation
+            finally:
+                trunk.train(was_training)
+        grads = trunk._backward(recs, dfeat.contiguous())
+        return (None, None, None) + tuple(grads.get(p) for p in trunk.parameters())
+
+
+class ResNet50Trunk(nn.Sequential):
+    """The parameters of one trunk; ``forward`` runs them as a one-trunk ``GroupedTrunks``."""
+
+    recompute = False        # see TrunkFn: keep activations (default) or re-run the forward inside backward
+
+    def __init__(self):
+        layers = []
+        inplanes = 64
+        for li, (nblk, width) in enumerate(zip(LAYERS, WIDTHS)):
+            blocks = []
+            for bi in range(nblk):
+                blocks.append(Bottleneck(inplanes, width, 2 if (bi == 0 and li > 0) else 1, bi == 0))
+                inplanes = width * EXPANSION
+            layers.append(nn.Sequential(*blocks))
+        super().__init__(nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True),
+                         nn.MaxPool2d(3, stride=2, padding=1), *layers, nn.AdaptiveAvgPool2d(1))
+        # torchvision's ResNet.__init__ init: kaiming-normal fan_out convs, BN weight 1 / bias 0
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+
+    def conv_bn_pairs(self):
+        """-> ((stem conv, bn), [per Bottleneck: (conv1, bn1), (conv2, bn2), (conv3, bn3), downsample pair or None])."""
+        blocks = [((b.conv1, b.bn1), (b.conv2, b.bn2), (b.conv3, b.bn3), tuple(b.downsample) if b.downsample is not None else None)
+                  for li in range(4) for b in self[4 + li]]
+        return (self[0], self[1]), blocks
+
+    def forward(self, x):
+        group = self.__dict__.get("_group")        # (not a submodule: it only runs this trunk's own parameters)
+        if group is None:
+            group = self.__dict__["_group"] = GroupedTrunks([self])
+        return group(x)

@@ -113,39 +113,58 @@ def conv_desc(x, w_packed, Cout, k=3, stride=1, *, flags=0, out=None, hw=None, b
 
 # --------------------------------------------------------------------------------------------------
 class PackedConvWeight:
-    """A [Cout,Cin,k,k] weight re-laid for one tile config of the MFMA conv kernel
-    ([co_tile][ci_chunk][tap][ci][co], zero padded).  Re-packed when the source tensor changes: the cache is keyed
-    on the tensor OBJECT (a weak reference -- a fresh temporary such as ``w * scale`` can be handed the address, shape
-    and version 0 of last step's temporary by the caching allocator, so pointer + version alone would serve stale
-    weights after an optimizer step) plus its autograd version counter and storage pointer."""
+    """The packed images of a [Cout,Cin,k,k] weight (``pack_image``: a tile config of the MFMA conv kernel, "wino" or "bf16x3"),
+    or of a list of same-shape weights one after another (what a grouped launch reads).  Re-packed when a source tensor
+    changes: the cache is keyed on the tensor OBJECTS (weak references -- a fresh temporary such as ``w * scale`` can be handed
+    the address, shape and version 0 of last step's temporary by the caching allocator, so pointer + version alone would serve
+    stale weights after an optimizer step) plus their autograd version counters, storage pointers and shapes.  A stale image
+    of unchanged shapes is re-packed into its own storage."""
 
     def __init__(self):
         self._cache = {}
 
-    def get(self, weight: torch.Tensor, key, transpose_flip=False) -> torch.Tensor:
-        """The image ``key`` names (``pack_image``: a tile config of the direct kernel, "wino" or "bf16x3"), cached under
-        ``(key, transpose_flip)``."""
-        hit = self._hit(weight, (key, transpose_flip))
+    def get(self, weight, key, transpose_flip=False) -> torch.Tensor:
+        """The image ``key`` names of ``weight`` (a tensor, or a list of same-shape tensors: direct kernel or "wino"), cached
+        under ``(key, transpose_flip)``."""
+        ws = list(weight) if isinstance(weight, (list, tuple)) else [weight]
+        hit, out = self._lookup(ws, (key, transpose_flip))
         if hit is None:
-            hit = pack_image(weight.detach(), key, transpose_flip)
-            self._put(weight, (key, transpose_flip), hit)
+            ds = [w.detach() for w in ws]
+            if len(ds) == 1:
+                hit = pack_image(ds[0], key, transpose_flip, out=out)
+            elif key == "wino":         # one list launch: no per-weight packs, no concatenation
+                hit = out if out is not None else empty_image("wino", *_op_channels(ds[0], transpose_flip), ds[0].device, len(ds))
+                pack_conv_weights_wino_into(ds, list(hit.view(len(ds), -1)), transpose_flip)
+            else:
+                hit = pack_conv_weights_list(ds, key, transpose_flip, out=out)
+            self._put(ws, (key, transpose_flip), hit)
         return hit
 
-    def get_wino(self, weight: torch.Tensor, transpose_flip: bool = False) -> torch.Tensor:
+    def get_wino(self, weight, transpose_flip: bool = False) -> torch.Tensor:
         return self.get(weight, "wino", bool(transpose_flip))
 
     def images(self, weight):
         """``weight``'s images for ``conv3x3``: ``images(key, transpose_flip)`` -> (image, None)."""
         return lambda key, transpose_flip: (self.get(weight, key, transpose_flip), None)
 
-    def _hit(self, weight, cache_key):
-        hit = self._cache.get(cache_key)
-        if hit is not None and hit[0] == (weight.data_ptr(), weight._version, tuple(weight.shape)) and hit[2]() is weight:
-            return hit[1]
-        return None
+    @staticmethod
+    def _stamp(weights):
+        return [(w.data_ptr(), w._version, w.shape) for w in weights]
 
-    def _put(self, weight, cache_key, packed):
-        self._cache[cache_key] = ((weight.data_ptr(), weight._version, tuple(weight.shape)), packed, weakref.ref(weight))
+    def _lookup(self, weights, cache_key):
+        """-> (the cached image if no member changed, else None; on a miss, the old image's storage if a re-pack fits it)."""
+        hit = self._cache.get(cache_key)
+        if hit is None:
+            return None, None
+        stamp, image, refs = hit
+        now = self._stamp(weights)
+        if now == stamp and all(r() is w for r, w in zip(refs, weights)):
+            return image, None
+        same_size = [s[2] for s in now] == [s[2] for s in stamp] and image.device == weights[0].device
+        return None, image if same_size else None
+
+    def _put(self, weights, cache_key, image):
+        self._cache[cache_key] = (self._stamp(weights), image, [weakref.ref(w) for w in weights])
 
     def clear(self):
         self._cache.clear()
@@ -171,45 +190,30 @@ def conv2d_config_info(config: int):
 
 
 def pack_conv_weight(weight: torch.Tensor, config: int, transpose_flip=False, out=None) -> torch.Tensor:
-    """``transpose_flip``: False = the forward operator; True (1) = the data-gradient operator of a stride-1 conv (run
-    by the forward kernel); 2 = the four output-parity 2x2 kernels of a 3x3 STRIDE-2 conv's data gradient; 3 = those of a
-    ConvTranspose2d(4, stride 2, pad 1) forward (``weight`` is then [Cin,Cout,4,4])."""
-    Cout, Cin, kh, kw = weight.shape
-    tf = int(transpose_flip)
-    if tf == 2:
-        n = L.lib().spk_conv2d_packed_floats(config, 2, 2, Cout, 4 * Cin)
-    elif tf == 3:        # ConvTranspose2d weight [Cin,Cout,4,4] -> the four parity 2x2 kernels (SPK_CONV_TRANSPOSE4X4_S2)
-        Cin, Cout = weight.shape[:2]
-        n = L.lib().spk_conv2d_packed_floats(config, 2, 2, Cin, 4 * Cout)
-    else:
-        n = L.lib().spk_conv2d_packed_floats(config, kh, kw, Cout if tf else Cin, Cin if tf else Cout)
-    if n <= 0:
-        raise L.SpkError("spk_conv2d_packed_floats: bad arguments")
-    if out is None:
-        out = torch.empty(n, device=weight.device, dtype=torch.float32)
-    elif out.numel() != n or not out.is_contiguous() or out.device != weight.device:
-        raise L.SpkError(f"pack_conv_weight: out must be a contiguous buffer of {n} floats on {weight.device}")
-    L.check(L.lib().spk_conv2d_pack_weights(L.dptr(weight.contiguous(), "weight"), L.dptr(out), kh, kw, Cin, Cout,
-                                            config, tf, L.stream_ptr()),
-            "spk_conv2d_pack_weights")
-    return out
+    """``pack_conv_weights_list`` of one weight."""
+    return pack_conv_weights_list([weight], config, transpose_flip, out=out)
 
 
 PACK_LIST_MAX = 8
 
 
 def pack_conv_weights_list(weights, config: int, transpose_flip=False, out=None) -> torch.Tensor:
-    """The packed images of several same-shape weights one after another (what a grouped launch reads), ONE launch per
-    ``PACK_LIST_MAX`` tensors (``spk_conv2d_pack_weights_list``) instead of a pack per tensor and a concatenation."""
+    """The packed images of same-shape weights one after another (what a grouped launch reads), ONE launch per
+    ``PACK_LIST_MAX`` tensors (``spk_conv2d_pack_weights_list``).  ``transpose_flip``: False = the forward operator; True (1)
+    = the data-gradient operator of a stride-1 conv (run by the forward kernel); 2 = the four output-parity 2x2 kernels of a
+    3x3 STRIDE-2 conv's data gradient; 3 = those of a ConvTranspose2d(4, stride 2, pad 1) forward (the weights are then
+    [Cin,Cout,4,4])."""
     w0 = weights[0]
-    Cout, Cin, kh, kw = w0.shape
     tf = int(transpose_flip)
-    if tf == 2:          # the stride-2 data-gradient form (see pack_conv_weight)
-        n1 = L.lib().spk_conv2d_packed_floats(config, 2, 2, Cout, 4 * Cin)
-    elif tf == 3:
-        raise L.SpkError("pack_conv_weights_list: transpose_flip 0, 1 or 2")
+    if tf == 3:          # ConvTranspose2d weight [Cin,Cout,4,4] -> the four parity 2x2 kernels (SPK_CONV_TRANSPOSE4X4_S2)
+        Cin, Cout, kh, kw = w0.shape
+        n1 = L.lib().spk_conv2d_packed_floats(config, 2, 2, Cin, 4 * Cout)
     else:
-        n1 = L.lib().spk_conv2d_packed_floats(config, kh, kw, Cout if tf else Cin, Cin if tf else Cout)
+        Cout, Cin, kh, kw = w0.shape
+        if tf == 2:
+            n1 = L.lib().spk_conv2d_packed_floats(config, 2, 2, Cout, 4 * Cin)
+        else:
+            n1 = L.lib().spk_conv2d_packed_floats(config, kh, kw, Cout if tf else Cin, Cin if tf else Cout)
     if n1 <= 0:
         raise L.SpkError("spk_conv2d_packed_floats: bad arguments")
     if out is None:
@@ -217,13 +221,12 @@ def pack_conv_weights_list(weights, config: int, transpose_flip=False, out=None)
     elif out.numel() != n1 * len(weights) or not out.is_contiguous() or out.device != w0.device:
         raise L.SpkError(f"pack_conv_weights_list: out must be a contiguous buffer of {n1 * len(weights)} floats on {w0.device}")
     ws = [w.contiguous() for w in weights]
-    for w in ws:
-        if w.shape != w0.shape or w.dtype != torch.float32 or w.device != w0.device:
-            raise L.SpkError("pack_conv_weights_list: the weights must share shape, dtype and device")
+    if any(w.shape != w0.shape or w.device != w0.device for w in ws):
+        raise L.SpkError("pack_conv_weights_list: the weights must share shape and device")
     for i in range(0, len(ws), PACK_LIST_MAX):
         part = ws[i:i + PACK_LIST_MAX]
-        arr = (C.c_void_p * len(part))(*[w.data_ptr() for w in part])
-        L.check(L.lib().spk_conv2d_pack_weights_list(arr, len(part), out.data_ptr() + 4 * n1 * i, kh, kw, Cin, Cout, config, tf,
+        arr = (C.c_void_p * len(part))(*[L.dptr(w, "weight") for w in part])
+        L.check(L.lib().spk_conv2d_pack_weights_list(arr, len(part), L.dptr(out) + 4 * n1 * i, kh, kw, Cin, Cout, config, tf,
                                                      L.stream_ptr()),
                 "spk_conv2d_pack_weights_list")
     return out
@@ -438,35 +441,31 @@ WINO_PACK_MAX = 32
 
 def pack_conv_weights_wino_into(weights, outs, transpose_flip=False):
     """Winograd images of several [Cout,Cin,3,3] weights into the given buffers (views of one tensor for a grouped launch): one
-    spk_conv2d_pack_weights_wino_list launch per 32."""
+    spk_conv2d_pack_weights_wino_list launch per 32.  ``transpose_flip``: one flag for all, or one per weight."""
+    tfs = list(transpose_flip) if isinstance(transpose_flip, (list, tuple)) else [transpose_flip] * len(weights)
     for i in range(0, len(weights), WINO_PACK_MAX):
-        ws, os_ = weights[i:i + WINO_PACK_MAX], outs[i:i + WINO_PACK_MAX]
+        ws, os_, tf = weights[i:i + WINO_PACK_MAX], outs[i:i + WINO_PACK_MAX], tfs[i:i + WINO_PACK_MAX]
         n = len(ws)
-        keep = [w.contiguous() for w in ws]
+        keep = [w.contiguous() for w in ws]          # (alive until the launch is queued)
         L.check(L.lib().spk_conv2d_pack_weights_wino_list((C.c_void_p * n)(*[L.dptr(w, "weight") for w in keep]),
                                                           (C.c_void_p * n)(*[o.data_ptr() for o in os_]),
                                                           (C.c_int * n)(*[w.shape[1] for w in ws]), (C.c_int * n)(*[w.shape[0] for w in ws]),
-                                                          (C.c_int * n)(*[1 if transpose_flip else 0] * n), n, L.stream_ptr()),
+                                                          (C.c_int * n)(*[1 if t else 0 for t in tf]), n, L.stream_ptr()),
                 "spk_conv2d_pack_weights_wino_list")
-
 
 
 def prepack_wino(items):
     """``items`` = [(PackedConvWeight cache, weight, transpose_flip), ...]: fill every STALE Winograd image in ONE launch
     (spk_conv2d_pack_weights_wino_list) -- the same bits ``get_wino`` would produce one launch at a time."""
-    todo = [(pk, w, bool(tf)) for pk, w, tf in items if pk._hit(w, ("wino", bool(tf))) is None]
-    for i in range(0, len(todo), WINO_PACK_MAX):
-        part = todo[i:i + WINO_PACK_MAX]
-        n = len(part)
-        keep = [w.detach().contiguous() for _, w, _ in part]          # (alive until the launch is queued)
-        outs = [empty_image("wino", w.shape[0] if tf else w.shape[1], w.shape[1] if tf else w.shape[0], w.device) for _, w, tf in part]
-        L.check(L.lib().spk_conv2d_pack_weights_wino_list((C.c_void_p * n)(*[L.dptr(w, "weight") for w in keep]),
-                                                          (C.c_void_p * n)(*[o.data_ptr() for o in outs]),
-                                                          (C.c_int * n)(*[w.shape[1] for w in keep]), (C.c_int * n)(*[w.shape[0] for w in keep]),
-                                                          (C.c_int * n)(*[1 if tf else 0 for _, _, tf in part]), n, L.stream_ptr()),
-                "spk_conv2d_pack_weights_wino_list")
-        for (pk, w, tf), out in zip(part, outs):
-            pk._put(w, ("wino", tf), out)
+    todo = []
+    for pk, w, tf in items:
+        hit, out = pk._lookup([w], ("wino", bool(tf)))
+        if hit is None:
+            todo.append((pk, w, bool(tf), out if out is not None else empty_image("wino", *_op_channels(w, tf), w.device)))
+    if todo:
+        pack_conv_weights_wino_into([w.detach() for _, w, _, _ in todo], [out for *_, out in todo], [tf for _, _, tf, _ in todo])
+    for pk, w, tf, out in todo:
+        pk._put([w], ("wino", tf), out)
 
 
 def upsample2x(x, zero_border=False):
@@ -565,12 +564,18 @@ def pack_image(weight: torch.Tensor, key, transpose_flip=False, out=None) -> tor
     return pack_conv_weight(weight, key, transpose_flip, out=out)
 
 
-def empty_image(key, Cin, Cout, device) -> torch.Tensor:
-    """An unfilled buffer the size of the forward image ``key`` of a [Cout,Cin,3,3] weight (for ``pack_image(..., out=)``)."""
+def empty_image(key, Cin, Cout, device, count=1) -> torch.Tensor:
+    """An unfilled buffer the size of ``count`` forward images ``key`` of a [Cout,Cin,3,3] weight (for ``pack_image(..., out=)``)."""
     if key == "bf16x3":
-        return torch.empty(L.lib().spk_conv2d_packed_bytes_bf16x3(Cin, Cout), device=device, dtype=torch.uint8)
+        return torch.empty(count * L.lib().spk_conv2d_packed_bytes_bf16x3(Cin, Cout), device=device, dtype=torch.uint8)
     n = L.lib().spk_conv2d_packed_bytes_wino(Cin, Cout) // 4 if key == "wino" else L.lib().spk_conv2d_packed_floats(key, 3, 3, Cin, Cout)
-    return torch.empty(n, device=device, dtype=torch.float32)
+    return torch.empty(count * n, device=device, dtype=torch.float32)
+
+
+def _op_channels(weight, transpose_flip):
+    """(Cin, Cout) of the operator a [Cout,Cin,3,3] weight's image runs: the data-gradient operator exchanges them."""
+    Cout, Cin = weight.shape[:2]
+    return (Cout, Cin) if transpose_flip else (Cin, Cout)
 
 
 # 3x3 stride-1 spellings used by the decoder

@@ -68,15 +68,13 @@ def main():
         if first:
             t_d = 0.0
         elif k == 3 and s == 1 and ops.use_wino(B, Cout, Cin, H, H, groups=G):
-            # as encoder._GroupedConvBN.conv_bwd runs it: the G trunks as groups of one fp32 Winograd launch
-            nw = ops.L.lib().spk_conv2d_packed_bytes_wino(Cout, Cin) // 4
-            wtw = torch.empty(G * nw, device=dev)
-            ops.pack_conv_weights_wino_into(ws, [wtw[i * nw:(i + 1) * nw] for i in range(G)], transpose_flip=True)
+            # as encoder._ConvBN.conv_bwd runs it: the G trunks as groups of one fp32 Winograd launch
+            wtw = ops.PackedConvWeight().get_wino(ws, transpose_flip=True)
             t_d = timeit(lambda: ops.conv3x3_wino(g, wtw, Cin, groups=G))
         else:
             cfd, tf = ops.dgrad_plan(k, s, B, Cout, Cin, (H, H), (Ho, Ho))
             wt = torch.cat([ops.pack_conv_weight(w, cfd, tf) for w in ws])
-            # (a strided 1x1 -- the downsample convs: as encoder._backward runs it since round 3, the gradient stays at the conv's
+            # (a strided 1x1 -- the downsample convs: as encoder.GroupedTrunks._backward runs it since round 3, the gradient stays at the conv's
             # output size and conv1's data gradient adds it at the even pixels in its epilogue; no dilated copy)
             t_d = timeit(lambda: ops.conv2d_dgrad(g, wt, Cin, k, s, (H, H), cfd, groups=G, dilate=not (k == 1 and s == 2)))
         tf = lambda t: flops / (t * 1e-3) / 1e12 if t else 0.0

@@ -11,6 +11,7 @@
 #include "spk_common.hpp"
 
 #include <algorithm>
+#include <cstdint>
 
 namespace {
 
@@ -28,6 +29,12 @@ struct SnGroups {
     long long off_q[SPK_SN_MAX_GROUPS];    // per-column-block sums of squares of t / per-block partial dots (backward)
     int n;
 };
+
+// The float4 paths need every pointer they touch 16-byte aligned, not only a size that is a multiple of 4: the autograd
+// Function hands in the v vectors as split views of one flat buffer (fromRGB's C = 3 comes first, so every later v sits
+// 12 bytes off), and a caller may pass any tensor at a 4-byte offset.  The scalar loops compute the same values in the same
+// order, so which path a block takes does not change the result.
+__device__ __forceinline__ bool sn_al16(const float* p) { return ((uintptr_t)p & 15) == 0; }
 
 __device__ __forceinline__ int sn_find(const int* prefix, int n, int b) {
     int gi = 0;
@@ -129,7 +136,7 @@ __global__ __launch_bounds__(256) void sn_scale_kernel(const SnGroups a) {
     const spk_sn_group& q = a.g[gi];
     const float sigma = *q.sigma;
     const size_t n = (size_t)q.R * q.C, i0 = (size_t)(blockIdx.x - a.blk_e[gi]) * 1024 + threadIdx.x * 4;
-    if ((n & 3) == 0 && i0 + 3 < n) {
+    if ((n & 3) == 0 && i0 + 3 < n && sn_al16(q.w) && sn_al16(q.w_hat)) {
         const float4 w = *reinterpret_cast<const float4*>(q.w + i0);
         *reinterpret_cast<float4*>(q.w_hat + i0) = make_float4(w.x / sigma, w.y / sigma, w.z / sigma, w.w / sigma);
     } else {
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(256) void sn_bwd_dot_kernel(const SnGroups a, float
     const int b = blockIdx.x - a.blk_e[gi];
     const size_t n = (size_t)q.R * q.C, i0 = (size_t)b * 1024 + threadIdx.x * 4;
     float d = 0.f;
-    if ((n & 3) == 0 && i0 + 3 < n) {                                               // (16-byte accesses; the same summation order)
+    if ((n & 3) == 0 && i0 + 3 < n && sn_al16(q.w_hat) && sn_al16(q.w)) {          // (16-byte accesses; the same summation order)
         const float4 gq = *reinterpret_cast<const float4*>(q.w_hat + i0), wq = *reinterpret_cast<const float4*>(q.w + i0);
         d += gq.x * wq.x; d += gq.y * wq.y; d += gq.z * wq.z; d += gq.w * wq.w;
     } else {
@@ -167,7 +174,7 @@ __global__ __launch_bounds__(256) void sn_bwd_apply_kernel(const SnGroups a, con
     const float sigma = *q.sigma;
     const float coef = dot / sigma;
     const size_t n = (size_t)q.R * q.C, i0 = (size_t)(blockIdx.x - a.blk_e[gi]) * 1024 + threadIdx.x * 4;
-    if ((q.C & 3) == 0 && i0 + 3 < n) {              // rows are a multiple of 4 floats: the four elements share a row, 16-byte accesses
+    if ((q.C & 3) == 0 && i0 + 3 < n && sn_al16(q.w_hat) && sn_al16(q.v) && sn_al16(q.dw)) {   // rows are a multiple of 4 floats: the four elements share a row, 16-byte accesses
         const int r = (int)(i0 / q.C), c = (int)(i0 - (size_t)r * q.C);
         const float4 gq = *reinterpret_cast<const float4*>(q.w_hat + i0), vq = *reinterpret_cast<const float4*>(q.v + c);
         const float cu = coef * q.u[r];

@@ -551,6 +551,27 @@ int spk_pixelnorm_bwd(const float* x, const float* dy, float* dx, int B, int C, 
 int spk_blur2d_bwd(const float* dy, float* dx, const float* filter_host, int k, int64_t planes, int H, int W, int stride, void* stream);
 int spk_upscale2d_nearest_bwd(const float* dy, float* dx, int64_t planes, int H, int W, int factor, float gain, void* stream);
 
+/* ---- the ProGAN critic's own ops (stylegan.Discriminator, stylegan.py:181-263) ------------------------------------------
+ * spk_avgpool2x_blend_fwd: y = a * avgpool2x2(x) + b * z over `planes` planes (B*C) of [H,W] -> [H/2,W/2]; z [planes,H/2,W/2]
+ *   or NULL (then b is unused).  H and W must be even (SPK_EINVAL otherwise).  16-byte accesses when W % 8 == 0 and every
+ *   pointer is 16-byte aligned, else a scalar loop with the same results.
+ *   replaces: stylegan.py:203-205,246,258 (nn.AvgPool2d(2, 2); a = 1, z = NULL) and, with z, the fade-in
+ *   alpha * avg_pool(block(out)) + (1 - alpha) * downscaled of stylegan.py:219-222,247-252 (a = alpha, b = 1 - alpha).
+ * spk_avgpool2x_blend_bwd: its adjoint: dx[2i+u, 2j+v] = (a/4) * dy[i,j] (dx [planes,H,W]); dz = b * dy, or NULL when not wanted.
+ *   replaces: the autograd of the two call sites above. */
+int spk_avgpool2x_blend_fwd(const float* x, const float* z, float* y, float a, float b, int64_t planes, int H, int W, void* stream);
+int spk_avgpool2x_blend_bwd(const float* dy, float* dx, float* dz, float a, float b, int64_t planes, int H, int W, void* stream);
+/* spk_minibatch_std_fwd: y [B,C+1,HW] = cat([x, s], 1) with s = mean over the C*HW positions of the unbiased std over the batch
+ *   (torch.std(x, dim=0).mean(), broadcast to [B,1,HW]; B = 1 gives NaN as torch does).  Two launches: per-position mean / std,
+ *   then one workgroup for the mean, which also writes the extra channel; fixed summation order, bitwise reproducible.
+ *   `workspace` (>= spk_minibatch_std_workspace_bytes(C, HW), 16-byte aligned) receives mean[C*HW], std[C*HW] and s: keep it
+ *   for the adjoint.  replaces: stylegan.py:224-231 (Discriminator.minibatch_std).
+ * spk_minibatch_std_bwd: dx = dy[:, :C] + g/(C*HW) * (x - mean) / ((B-1) * std), g = sum_{b,hw} dy[b, C, hw] (each workgroup
+ *   sums g itself in a fixed order: one launch); `workspace` as the forward left it.  replaces: its autograd. */
+int64_t spk_minibatch_std_workspace_bytes(int C, int64_t HW);
+int spk_minibatch_std_fwd(const float* x, float* y, void* workspace, int B, int C, int64_t HW, void* stream);
+int spk_minibatch_std_bwd(const float* x, const float* dy, const void* workspace, float* dx, int B, int C, int64_t HW, void* stream);
+
 /* ---- spectral normalisation of many layers at once (StyleDiscriminator) ------------------------------------------------
  * One power iteration + division for up to SPK_SN_MAX_GROUPS weight matrices W[R, C] (R = Cout, C = Cin*kh*kw, row major):
  *   power_iteration != 0:  v <- normalize(W^T u), u <- normalize(W v)   (in place, eps inside max(|.|, eps))

@@ -3,10 +3,12 @@ kernels (include/spk.h); autograd only sequences them.  No torch math on activat
 torch arithmetic in a backward is on per-(batch,channel) scalars the kernels already reduced
 (e.g. summing ``[B,C]`` partials over ``B``).
 
-Double backward: the discriminator's Functions (``ConvBiasLReLUFn``, ``ConvDgradFn``, ``_LReluMaskFn``, ``FCFn``,
-``GlobalAvgPoolFn``) are built to be differentiated twice -- the R1 penalty of train.py:246-255 needs that.  Every other
+Double backward: the discriminators' Functions (``ConvBiasLReLUFn``, ``ConvDgradFn``, ``_LReluMaskFn``, ``FCFn``,
+``GlobalAvgPoolFn``, and for the ProGAN critic ``AvgPool2xBlendFn`` and ``MinibatchStdFn``) are built to be differentiated
+twice -- the R1 penalty of train.py:246-255 and a WGAN-GP penalty through stylegan.Discriminator need that.  Every other
 backward here runs raw kernels and is marked ``once_differentiable``: a ``create_graph=True`` pass through it raises
-instead of silently dropping the second-order term.
+instead of silently dropping the second-order term.  The one exception to "no torch math on activations": when
+``MinibatchStdFn``'s backward is itself recorded, it is written as differentiable torch ops on the critic's [B, C+1, 4, 4] tail.
 """
 from __future__ import annotations
 
@@ -438,121 +440,144 @@ def _sn_parts(weight):
     return (sn[0].detach(), sn[1]) if sn is not None else (weight.detach(), None)
 
 
-def _conv_plain(x, weight, k, stride):
+_SCALARS = {}
+
+
+def _scale_dev(sd, w_scale, device):
+    """``sd`` (a device scalar or None) times the host factor ``w_scale``, for the kernels that take a device scale only (the
+    fromRGB store stream).  One cached one-element tensor per (device, value); ``w_scale`` 1 leaves ``sd`` as it is."""
+    if w_scale == 1.0:
+        return sd
+    key = (device, float(w_scale))
+    t = _SCALARS.get(key)
+    if t is None:
+        t = _SCALARS[key] = torch.full((1,), float(w_scale), device=device, dtype=torch.float32)
+    return t if sd is None else sd * t
+
+
+def _conv_plain(x, weight, k, stride, w_scale=1.0):
     B, Cin, H, W = x.shape
     Cout = weight.shape[0]
     Ho, Wo = ops.conv_out_size(H, k, stride), ops.conv_out_size(W, k, stride)
     if ops.conv1x1_expand_ok(x, Cin, k, stride):                 # fromRGB: a store stream, not a contraction
         w0, sd = _sn_parts(weight)
-        return ops.conv1x1_expand(x.contiguous(), w0, None, sd)
+        return ops.conv1x1_expand(x.contiguous(), w0, None, _scale_dev(sd, w_scale, x.device))
     if k == 3 and stride == 1:
-        return ops.conv3x3(x.contiguous(), functools.partial(_packed, weight), Cout, ops.conv3x3_route(B, Cin, Cout, Ho, Wo))
+        return ops.conv3x3(x.contiguous(), functools.partial(_packed, weight), Cout, ops.conv3x3_route(B, Cin, Cout, Ho, Wo),
+                           out_scale=w_scale)
     cfg = ops.conv2d_pick_config(k, stride, B, Cin, Cout, Ho, Wo)
     wp, sd = _packed(weight, cfg)
-    return ops.conv2d_fused(x, wp, Cout, k, stride, config=cfg, out_scale_dev=sd)
+    return ops.conv2d_fused(x, wp, Cout, k, stride, config=cfg, out_scale_dev=sd, out_scale=w_scale)
 
 
-def _conv_dgrad(dt, weight, k, stride, in_hw):
+def _conv_dgrad(dt, weight, k, stride, in_hw, w_scale=1.0):
     B, Cout = dt.shape[:2]
     Cin = weight.shape[1]
     if k == 1 and stride == 1 and Cin <= 4:                      # fromRGB's data gradient: a 1x1 conv TO <= 4 channels (the toRGB kernel)
-        return ops.conv1x1_small(dt.contiguous(), weight.detach().reshape(Cout, Cin).t().contiguous().view(Cin, Cout, 1, 1))
+        return ops.conv1x1_small(dt.contiguous(), weight.detach().reshape(Cout, Cin).t().contiguous().view(Cin, Cout, 1, 1),
+                                 in_scale=w_scale)
     if k == 3 and stride == 1:
         return ops.conv3x3(dt.contiguous(), functools.partial(_packed, weight), Cin, ops.conv3x3_route(B, Cout, Cin, *in_hw),
-                           transpose_flip=True)
+                           transpose_flip=True, out_scale=w_scale)
     cfg, tf = ops.dgrad_plan(k, stride, B, Cout, Cin, in_hw, dt.shape[-2:])
     wp, sd = _packed(weight, cfg, tf)
-    return ops.conv2d_dgrad(dt, wp, Cin, k, stride, in_hw, cfg, out_scale_dev=sd)
+    return ops.conv2d_dgrad(dt, wp, Cin, k, stride, in_hw, cfg, out_scale_dev=sd, out_scale=w_scale)
 
 
 class ConvDgradFn(torch.autograd.Function):
     """dx = conv_transpose(dt, w) as a differentiable function of (dt, w): its adjoints are the forward conv
     (w.r.t. dt) and the weight-gradient kernel (w.r.t. w) -- the same MFMA kernels, so the R1 double backward of the
-    discriminator (d/dw of |dD/dx|^2) never leaves the HIP path."""
+    discriminator (d/dw of |dD/dx|^2) never leaves the HIP path.  ``w_scale``: the conv runs on ``weight * w_scale`` (as in
+    ``ConvBiasLReLUFn``)."""
 
     @staticmethod
-    def forward(ctx, dt, weight, k, stride, in_hw):
+    def forward(ctx, dt, weight, k, stride, in_hw, w_scale=1.0):
         ctx.save_for_backward(dt, weight)
-        ctx.conf = (k, stride)
-        return _conv_dgrad(dt, weight, k, stride, in_hw)
+        ctx.conf = (k, stride, w_scale)
+        return _conv_dgrad(dt, weight, k, stride, in_hw, w_scale)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         dt, weight = ctx.saved_tensors
-        k, stride = ctx.conf
+        k, stride, w_scale = ctx.conf
         g = g.contiguous()
         ddt = dw = None
         if ctx.needs_input_grad[1]:
             Co, Ci = weight.shape[:2]
             if getattr(weight, "_spk_sn", None) is not None:
-                dw = _wgrad_shared(weight, dt, g, lambda out, acc: ops.conv2d_wgrad(dt, g, Co, Ci, k, stride, out=out, accumulate=acc))
+                dw = _wgrad_shared(weight, dt, g, lambda out, acc: ops.conv2d_wgrad(dt, g, Co, Ci, k, stride, scale=w_scale, out=out,
+                                                                                    accumulate=acc))
             else:
-                dw = ops.conv2d_wgrad(dt, g, Co, Ci, k, stride)
+                dw = ops.conv2d_wgrad(dt, g, Co, Ci, k, stride, scale=w_scale)
         if ctx.needs_input_grad[0]:
-            ddt = _conv_plain(g, weight, k, stride)
-        return ddt, dw, None, None, None
+            ddt = _conv_plain(g, weight, k, stride, w_scale)
+        return ddt, dw, None, None, None, None
 
 
 class ConvBiasLReLUFn(torch.autograd.Function):
     """y = lrelu_slope(conv_kxk(x, w, stride) + bias) -- the discriminator's layers (styleganv1.py:662-695): one fused
     launch forward; backward on the epilogue-adjoint / dgrad / wgrad kernels.  When the backward itself is recorded
     (``create_graph=True``) the data path is rebuilt from ``_LReluMaskFn`` and ``ConvDgradFn`` so that it can be
-    differentiated once more; the parameter gradients of that pass are plain (non-differentiable) kernel outputs."""
+    differentiated once more; the parameter gradients of that pass are plain (non-differentiable) kernel outputs.
+    ``w_scale`` (host): the conv runs on ``weight * w_scale`` -- the equalised learning rate of stylegan.py:37,45-46 -- without
+    that product ever existing: it rides on ``out_scale`` forward, on the data gradient and on the weight gradient, so the packed
+    images stay those of the Parameter itself."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, k, stride, slope, grad_mode):
+    def forward(ctx, x, weight, bias, k, stride, slope, grad_mode, w_scale=1.0):
         B, Cin, H, W = x.shape
         Cout = weight.shape[0]
         Ho, Wo = ops.conv_out_size(H, k, stride), ops.conv_out_size(W, k, stride)
         if ops.conv1x1_expand_ok(x, Cin, k, stride):             # fromRGB (3 -> 64 at 256^2): a store stream, not a contraction
             w0, sd = _sn_parts(weight)
-            y = ops.conv1x1_expand(x.contiguous(), w0, bias, sd, slope)
+            y = ops.conv1x1_expand(x.contiguous(), w0, bias, _scale_dev(sd, w_scale, x.device), slope)
         elif k == 3 and stride == 1:
             y = ops.conv3x3(x.contiguous(), functools.partial(_packed, weight), Cout, ops.conv3x3_route(B, Cin, Cout, Ho, Wo),
-                            bias=bias, lrelu_slope=slope)
+                            bias=bias, lrelu_slope=slope, out_scale=w_scale)
         else:
             cfg = ops.conv2d_pick_config(k, stride, B, Cin, Cout, Ho, Wo)
             wp, sd = _packed(weight, cfg)
-            y = ops.conv2d_fused(x, wp, Cout, k, stride, bias=bias, lrelu_slope=slope, config=cfg, out_scale_dev=sd)
+            y = ops.conv2d_fused(x, wp, Cout, k, stride, bias=bias, lrelu_slope=slope, config=cfg, out_scale_dev=sd, out_scale=w_scale)
         if _needs(ctx, grad_mode):
             ctx.save_for_backward(x, weight, y)
-            ctx.conf = (k, stride, slope, bias is not None)
+            ctx.conf = (k, stride, slope, bias is not None, w_scale)
             ctx.bias_ref = bias               # (the Parameter: its gradient is shared by the passes of one backward, _first_or_add)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight, y = ctx.saved_tensors
-        k, stride, slope, has_bias = ctx.conf
+        k, stride, slope, has_bias, w_scale = ctx.conf
         Cout, Cin = weight.shape[:2]
         dx = dw = db = None
         if torch.is_grad_enabled():        # double backward requested: differentiable data path
             dt = _LReluMaskFn.apply(dy, y, slope) if slope is not None else dy.contiguous()
-            if ctx.needs_input_grad[0]:
-                dx = ConvDgradFn.apply(dt, weight, k, stride, tuple(x.shape[-2:]))     # a second user of this weight: see _wgrad_shared
+            if ctx.needs_input_grad[0]:     # a second user of this weight: see _wgrad_shared
+                dx = ConvDgradFn.apply(dt, weight, k, stride, tuple(x.shape[-2:]), w_scale)
             if not _INPUT_GRAD_ONLY:
                 with torch.no_grad():
                     dtd = dt.detach()
                     if ctx.needs_input_grad[1]:
-                        dw = ops.conv2d_wgrad(dtd, x, Cout, Cin, k, stride)
+                        dw = ops.conv2d_wgrad(dtd, x, Cout, Cin, k, stride, scale=w_scale)
                     if has_bias and ctx.needs_input_grad[2]:
                         db = dtd.sum((0, 2, 3))
-            return dx, dw, db, None, None, None, None
+            return dx, dw, db, None, None, None, None, None
         dt, sums = ops.epilogue_bwd(dy.contiguous(), y, None, None, slope if slope is not None else 1.0)
         if ctx.needs_input_grad[1]:
             if getattr(weight, "_spk_sn", None) is None:
-                dw = ops.conv2d_wgrad(dt, x, Cout, Cin, k, stride)
+                dw = ops.conv2d_wgrad(dt, x, Cout, Cin, k, stride, scale=w_scale)
             else:                                                 # consumed by SpectralNormAllFn.backward only: second stream
-                dw = _wgrad_shared(weight, dt, x, lambda out, acc: ops.conv2d_wgrad(dt, x, Cout, Cin, k, stride, out=out, accumulate=acc))
+                dw = _wgrad_shared(weight, dt, x, lambda out, acc: ops.conv2d_wgrad(dt, x, Cout, Cin, k, stride, scale=w_scale, out=out,
+                                                                                    accumulate=acc))
         if ctx.needs_input_grad[0]:
-            dx = _conv_dgrad(dt, weight, k, stride, tuple(x.shape[-2:]))
+            dx = _conv_dgrad(dt, weight, k, stride, tuple(x.shape[-2:]), w_scale)
         if has_bias and ctx.needs_input_grad[2]:
             if isinstance(ctx.bias_ref, torch.nn.Parameter):
                 db = _first_or_add(ctx.bias_ref, "_spk_db", lambda out: ops.plane_sums_reduce(sums, 2, out))
             else:
                 db = ops.plane_sums_reduce(sums, 2)
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
 class GlobalAvgPoolFn(torch.autograd.Function):
@@ -568,6 +593,66 @@ class GlobalAvgPoolFn(torch.autograd.Function):
     def backward(ctx, dy):
         B, C, H, W = ctx.shape
         return (dy / float(H * W)).expand(B, C, H, W)
+
+
+class AvgPool2xBlendFn(torch.autograd.Function):
+    """y = a * avgpool2x2(x) + b * z (z optional) -- the ProGAN critic's nn.AvgPool2d(2, 2) (stylegan.py:203-205,246,258) and,
+    with z, its fade-in alpha * avg_pool(block(out)) + (1 - alpha) * downscaled (stylegan.py:219-222,247-252), one launch.
+    The backward is ``AvgPool2xBlendBwdFn``, whose own adjoint is this pool again: differentiable to any order."""
+
+    @staticmethod
+    def forward(ctx, x, z, a, b):
+        ctx.conf = (float(a), float(b), z is not None)
+        return ops.avgpool2x_blend(x.contiguous(), None if z is None else z.contiguous(), a, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, b, has_z = ctx.conf
+        if has_z and ctx.needs_input_grad[1]:
+            dx, dz = AvgPool2xBlendBwdFn.apply(dy, a, b)
+        else:
+            dx, dz = AvgPool2xBlendBwdFn.apply(dy, a, None), None
+        return dx, dz, None, None
+
+
+class AvgPool2xBlendBwdFn(torch.autograd.Function):
+    """(dx, dz) = ((a/4) * dy spread over each 2x2 window, b * dy) -- one launch; ``b`` None: dx alone.  Linear in dy; its
+    adjoint is ``AvgPool2xBlendFn`` with the same (a, b)."""
+
+    @staticmethod
+    def forward(ctx, dy, a, b):
+        ctx.conf = (a, b)
+        dx, dz = ops.avgpool2x_blend_bwd(dy.contiguous(), a, 0.0 if b is None else b, need_dz=b is not None)
+        return dx if b is None else (dx, dz)
+
+    @staticmethod
+    def backward(ctx, gdx, gdz=None):
+        a, b = ctx.conf
+        return AvgPool2xBlendFn.apply(gdx, gdz if b is not None else None, a, 0.0 if b is None else b), None, None
+
+
+class MinibatchStdFn(torch.autograd.Function):
+    """y = cat([x, s], 1), s = torch.std(x, dim=0).mean() broadcast to [B, 1, H, W] -- Discriminator.minibatch_std,
+    stylegan.py:224-231.  Forward and first-order backward on the kernels (the forward leaves the per-position mean / std in a
+    workspace the adjoint reads).  When the backward is itself recorded (a gradient penalty), it is written as differentiable
+    torch ops -- on the critic's [B, C+1, 4, 4] tail only:  dx = dy[:, :C] + g/(C H W) * (x - mean) / ((B - 1) std),
+    g = the sum of dy[:, C]."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y, ws = ops.minibatch_std(x.contiguous())
+        ctx.save_for_backward(x)
+        ctx.ws = ws
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        B, C, H, W = x.shape
+        if torch.is_grad_enabled():
+            g = dy[:, C].sum()
+            return dy[:, :C] + (g / float(C * H * W)) * (x - x.mean(0)) / ((B - 1) * x.std(0))
+        return ops.minibatch_std_bwd(x.detach().contiguous(), dy.contiguous(), ctx.ws)
 
 
 def _scale_rows(t):
@@ -893,12 +978,20 @@ def bias_noise_style(x, bias, noise_w, noise, style, B):
     return BiasNoiseStyleFn.apply(x, bias, noise_w, noise, style, B, torch.is_grad_enabled())
 
 
-def conv_bias_lrelu(x, weight, bias, k, stride, slope):
-    return ConvBiasLReLUFn.apply(x, weight, bias, k, stride, slope, torch.is_grad_enabled())
+def conv_bias_lrelu(x, weight, bias, k, stride, slope, w_scale=1.0):
+    return ConvBiasLReLUFn.apply(x, weight, bias, k, stride, slope, torch.is_grad_enabled(), w_scale)
 
 
 def global_avgpool(x):
     return GlobalAvgPoolFn.apply(x)
+
+
+def avgpool2x_blend(x, z=None, a=1.0, b=0.0):
+    return AvgPool2xBlendFn.apply(x, z, a, b)
+
+
+def minibatch_std(x):
+    return MinibatchStdFn.apply(x)
 
 
 def mod_conv(x, weight, s, bias, noise_w, noise, scale, upsample, slope, gain, fir, packed, demodulate=True):

@@ -1170,6 +1170,49 @@ def fade_in_tanh(a, b, alpha):
     return y
 
 
+
+# ---- the ProGAN critic's own ops (csrc/progan_critic.hip) ---------------------------------------------------------------------------
+def avgpool2x_blend(x, z=None, a=1.0, b=0.0):
+    """y = a * avgpool2x2(x) + b * z (``z`` [B,C,H/2,W/2] or None): nn.AvgPool2d(2, 2) and the critic's fade-in in one pass."""
+    B, Cc, H, W = x.shape
+    y = torch.empty((B, Cc, H // 2, W // 2), device=x.device, dtype=torch.float32)
+    if z is not None and tuple(z.shape) != tuple(y.shape):
+        raise L.SpkError(f"avgpool2x_blend: z {tuple(z.shape)} must have the pooled shape {tuple(y.shape)}")
+    L.check(L.lib().spk_avgpool2x_blend_fwd(L.dptr(x, "x"), L.dptr(z, "z"), L.dptr(y), float(a), float(b), B * Cc, H, W,
+                                            L.stream_ptr()), "spk_avgpool2x_blend_fwd")
+    return y
+
+
+def avgpool2x_blend_bwd(dy, a=1.0, b=0.0, need_dz=False):
+    """Adjoint of ``avgpool2x_blend``: (dx = (a/4) * dy spread over each 2x2 window, dz = b * dy or None)."""
+    B, Cc, Ho, Wo = dy.shape
+    dx = torch.empty((B, Cc, 2 * Ho, 2 * Wo), device=dy.device, dtype=torch.float32)
+    dz = torch.empty_like(dy) if need_dz else None
+    L.check(L.lib().spk_avgpool2x_blend_bwd(L.dptr(dy, "dy"), L.dptr(dx), L.dptr(dz), float(a), float(b), B * Cc, 2 * Ho, 2 * Wo,
+                                            L.stream_ptr()), "spk_avgpool2x_blend_bwd")
+    return dx, dz
+
+
+def minibatch_std(x):
+    """-> (y = cat([x, torch.std(x, 0).mean() broadcast to [B,1,H,W]], 1), the workspace ``minibatch_std_bwd`` reads)."""
+    B, Cc, H, W = x.shape
+    y = torch.empty((B, Cc + 1, H, W), device=x.device, dtype=torch.float32)
+    nbytes = L.lib().spk_minibatch_std_workspace_bytes(Cc, H * W)
+    ws = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
+    L.check(L.lib().spk_minibatch_std_fwd(L.dptr(x, "x"), L.dptr(y), L.dptr(ws), B, Cc, H * W, L.stream_ptr()), "spk_minibatch_std_fwd")
+    return y, ws
+
+
+def minibatch_std_bwd(x, dy, ws):
+    """dx of ``minibatch_std`` from dy [B,C+1,H,W] and the forward's workspace (per-position mean / std)."""
+    B, Cc, H, W = x.shape
+    if tuple(dy.shape) != (B, Cc + 1, H, W):
+        raise L.SpkError(f"minibatch_std_bwd: gradient {tuple(dy.shape)} is not [B, C+1, H, W] of the input {tuple(x.shape)}")
+    dx = torch.empty_like(x)
+    L.check(L.lib().spk_minibatch_std_bwd(L.dptr(x, "x"), L.dptr(dy, "dy"), L.dptr(ws, "workspace"), L.dptr(dx), B, Cc, H * W,
+                                          L.stream_ptr()), "spk_minibatch_std_bwd")
+    return dx
+
 MASK_NONE, MASK_RECOMPUTE, MASK_TENSOR = 0, 1, 2
 
 
@@ -1230,7 +1273,7 @@ def dgrad_plan(k, stride, B, Cout, Cin, in_hw, g_hw, out=None, accumulate=False)
     return conv2d_pick_config(k, 1, B, Cout, Cin, hw[0], hw[1]), 1
 
 
-def _dgrad_s2_parity(g, weight_packed, Cin, in_hw, config, out, accumulate, groups, out_scale_dev=None):
+def _dgrad_s2_parity(g, weight_packed, Cin, in_hw, config, out, accumulate, groups, out_scale_dev=None, out_scale=1.0):
     B, Cg, Hg, Wg = g.shape
     G = int(groups)
     if Cg % G:
@@ -1241,7 +1284,7 @@ def _dgrad_s2_parity(g, weight_packed, Cin, in_hw, config, out, accumulate, grou
     elif tuple(out.shape) != (B, G * Cin, H, W) or not out.is_contiguous():
         raise L.SpkError("conv2d_dgrad: out must be a contiguous [B, groups*Cin, H, W] tensor")
     d, ws_bytes = conv_desc(g, weight_packed, Cin, 3, 2, flags=L.CONV_DGRAD_S2, out=out, hw=(H, W), accumulate=accumulate,
-                            config=config, groups=G, out_scale_dev=out_scale_dev)
+                            config=config, groups=G, out_scale_dev=out_scale_dev, out_scale=out_scale)
     _run_conv2d(d, ws_bytes, g.device)        # (a small gradient plane: the exact-tap kernel runs its contraction in slices)
     return out
 
@@ -1250,7 +1293,7 @@ GEMM2_CONFIGS = (14, 15)        # the lean GEMM form of a stride-1 1x1 (csrc/con
 
 
 def conv2d_dgrad(g, weight_packed_tf, Cin, k, stride, in_hw, config, out=None, accumulate=False, groups=1, dilate=True,
-                 accum_half=None, out_scale_dev=None):
+                 accum_half=None, out_scale_dev=None, out_scale=1.0):
     """Data gradient of a k x k conv.  Stride 1: the forward MFMA kernel on ``g`` with transpose-flipped weights.
     3x3 stride 2: by output parity (``SPK_CONV_DGRAD_S2``: dx[2m+py, 2n+px] needs 1/2/2/4 of the 9 taps; four 2x2
     kernels in one launch over the gradient's own pixels, stored interleaved).  1x1 stride 2 without a destination: at
@@ -1259,17 +1302,18 @@ def conv2d_dgrad(g, weight_packed_tf, Cin, k, stride, in_hw, config, out=None, a
     destination): the gradient stays at the output size; ``accum_half``: such a tensor, added at the even pixels by a stride-1
     1x1 data gradient running in the lean GEMM form (``GEMM2_CONFIGS``)."""
     if k == 3 and stride == 2:
-        return _dgrad_s2_parity(g, weight_packed_tf, Cin, in_hw, config, out, accumulate, groups, out_scale_dev)
+        return _dgrad_s2_parity(g, weight_packed_tf, Cin, in_hw, config, out, accumulate, groups, out_scale_dev, out_scale)
     if dgrad_at_output_size(k, stride, out, accumulate):
         # a strided 1x1 reads only the even input pixels: dx = dilate(W^T g), the contraction at the OUTPUT size
-        t = conv2d_fused(g, weight_packed_tf, Cin, 1, 1, config=config, groups=groups, out_scale_dev=out_scale_dev)
+        t = conv2d_fused(g, weight_packed_tf, Cin, 1, 1, config=config, groups=groups, out_scale_dev=out_scale_dev,
+                         out_scale=out_scale)
         return dilate2x(t, in_hw[0], in_hw[1]) if dilate else t      # not dilated: the caller adds it through ``accum_half``
     if stride == 2:
         # dx[i] = sum_k gd[i + k' - p] * w[k-1-k'] with gd[2o] = g[o], zeros elsewhere, extended to the input size
         # (an even-sized input has a last row/column no window's stride lattice reaches: it stays zero)
         g = dilate2x(g, in_hw[0], in_hw[1])
     return conv2d_fused(g, weight_packed_tf, Cin, k, 1, config=config, out=out, accumulate=accumulate, groups=groups,
-                        accum_half=accum_half, out_scale_dev=out_scale_dev)
+                        accum_half=accum_half, out_scale_dev=out_scale_dev, out_scale=out_scale)
 
 
 # ---- BatchNorm / pooling pieces of the ResNet-50 trunk ----------------------------------------------

@@ -8,8 +8,11 @@ on the HIP kernels (backward through ``autograd.FusedConvFn`` / ``InstanceNormAf
 * ``AdaIN`` = one per-plane kernel (instance-norm statistics + style scale/shift, stylegan.py:91-95);
 * rgb heads are the small-Cout 1x1 kernel; the fade-in is one tanh blend.  ``rgb(upsample(x))`` is computed as
   ``upsample(rgb(x))`` (a 1x1 conv and a bilinear resize commute) -- 4x fewer pixels through the 1x1.
-The reference ``Discriminator`` (stylegan.py:181-263) is out of scope; the class is kept as
-a parameter holder so checkpoints and imports resolve.
+``Discriminator`` (the critic, stylegan.py:181-263) runs forward, backward and a recorded (``create_graph``) backward for a
+gradient penalty on the HIP kernels: fromRGB and every 3x3 conv through ``autograd.ConvBiasLReLUFn`` with the equalised-lr
+scale as ``w_scale`` (fromRGB takes the ``conv1x1_expand`` store stream), the 2x2 average pool and the fade-in as one
+``AvgPool2xBlendFn`` launch, the minibatch-std channel as ``MinibatchStdFn``, and the final block's 4x4 valid conv on the 4x4
+map and its last 1x1 as ``FCFn``.
 """
 from __future__ import annotations
 
@@ -64,11 +67,17 @@ class WSConv2d(nn.Module):
             if train:       # conv(x * scale, w) = conv(x, w * scale): the scale rides on the (tiny) weight tensor
                 return AG.to_rgb(x.contiguous(), w * self.scale, self.bias)
             return ops.conv1x1_small(x.contiguous(), w, self.bias, in_scale=self.scale)
+        if k == 4 and self.conv.padding[0] == 0 and tuple(x.shape[-2:]) == (4, 4) and noise_w is None and not upsample:
+            return _valid4x4_fc(self, x, lrelu).view(x.shape[0], Cout, 1, 1)
         if self.conv.padding[0] != (k - 1) // 2 or k not in (1, 3):
-            raise NotImplementedError(f"WSConv2d: kernel {k} / padding {self.conv.padding} is not on the HIP path")
+            raise NotImplementedError(f"WSConv2d: kernel {k} / padding {self.conv.padding} on a {tuple(x.shape[-2:])} input is "
+                                      "not on the HIP path (3x3 / pad 1, 1x1 / pad 0, and 4x4 / pad 0 on a 4x4 map are)")
         if train:
+            if k == 1 and noise_w is None and not upsample:
+                # fromRGB (the critic): conv + bias (+ LeakyReLU), scale on the accumulator, differentiable twice
+                return AG.conv_bias_lrelu(x.contiguous(), w, self.bias, 1, 1, lrelu, self.scale)
             if k != 3:
-                raise NotImplementedError("WSConv2d backward: 3x3 and the 1x1 toRGB are on the HIP path")
+                raise NotImplementedError("WSConv2d backward: a 1x1 with noise or x2 is not on the HIP path")
             # the cache is keyed on the Parameter itself; the equalised-lr scale rides on the accumulator (and on dx / dw)
             return AG.fused_conv(x.contiguous(), w, self.bias, noise_w, noise, None, upsample, lrelu, self._pk, w_scale=self.scale)
         B, _, H, W = x.shape
@@ -76,6 +85,13 @@ class WSConv2d(nn.Module):
         cfg = ops.conv2d_pick_config(k, 1, B, Cin, Cout, Ho, Wo)
         return ops.conv2d_fused(x.contiguous(), self._pk.get(w, cfg), Cout, k, 1, bias=self.bias, noise_w=noise_w, noise=noise,
                                 lrelu_slope=lrelu, out_scale=self.scale, upsample=upsample, config=cfg)
+
+
+def _valid4x4_fc(m, x, slope):
+    """A 4x4 / pad 0 ``WSConv2d`` on a 4x4 map is an FC with K = 16 * Cin (the critic's final block, stylegan.py:207-215):
+    ``FCFn`` with the equalised-lr scale as ``wmul``, differentiable twice.  -> [B, Cout]."""
+    w = m.conv.weight
+    return AG.fc(x.contiguous().view(x.shape[0], -1), w.view(w.shape[0], -1), m.bias, m.scale, 1.0, 1.0 if slope is None else slope)
 
 
 class MappingNetwork(nn.Module):
@@ -221,7 +237,8 @@ class Generator(nn.Module):
 
 
 class Discriminator(nn.Module):
-    """Parameter holder with the reference's layout (stylegan.py:181-218); forward is out of scope."""
+    """The ProGAN critic, stylegan.py:181-263: same constructor, ``forward(x, alpha, steps)`` -> [B, 1] and state_dict keys
+    (``rgb_layers.8`` is ``initial_rgb``).  x is [B, 3, 4 * 2^steps, 4 * 2^steps]."""
 
     def __init__(self, in_channels, img_channels=3):
         super().__init__()
@@ -238,5 +255,33 @@ class Discriminator(nn.Module):
                                          WSConv2d(in_channels, in_channels, kernel_size=4, padding=0, stride=1),
                                          nn.LeakyReLU(0.2), WSConv2d(in_channels, 1, kernel_size=1, padding=0, stride=1))
 
+    @staticmethod
+    def _conv(m, x, k):
+        """leaky(m(x)) with slope 0.2 (stylegan.py:63-64,238,245)."""
+        return AG.conv_bias_lrelu(x, m.conv.weight, m.bias, k, 1, 0.2, m.scale)
+
+    def _block(self, i, x):
+        blk = self.prog_blocks[i]
+        return self._conv(blk.conv2, self._conv(blk.conv1, x, 3), 3)
+
+    def _final(self, out):
+        """minibatch_std, then final_block (stylegan.py:207-215,224-231,262-263): the 513-channel 3x3, the 4x4 valid conv as an
+        FC with LeakyReLU, the last 1x1 as an FC."""
+        c0, c1, c2 = self.final_block[0], self.final_block[2], self.final_block[4]
+        out = self._conv(c0, AG.minibatch_std(out), 3)
+        out = _valid4x4_fc(c1, out, 0.2)
+        return AG.fc(out, c2.conv.weight.view(1, -1), c2.bias, c2.scale, 1.0, 1.0)
+
     def forward(self, x, alpha, steps):
-        raise NotImplementedError("stylegan.Discriminator is outside the accelerated path (SURVEY.md 2 row 4)")
+        cur = len(self.prog_blocks) - steps
+        x = x.contiguous()
+        out = self._conv(self.rgb_layers[cur], x, 1)
+        if steps == 0:
+            return self._final(out)
+        # the downscaled branch pools the 3-channel image first, then its 1x1 (stylegan.py:246)
+        downscaled = self._conv(self.rgb_layers[cur + 1], AG.avgpool2x_blend(x), 1)
+        # fade_in(alpha, downscaled, avg_pool(block(out))) as one pool-and-blend launch (stylegan.py:219-222,247-252)
+        out = AG.avgpool2x_blend(self._block(cur, out), downscaled, alpha, 1 - alpha)
+        for step in range(cur + 1, len(self.prog_blocks)):
+            out = AG.avgpool2x_blend(self._block(step, out))
+        return self._final(out)

@@ -78,6 +78,12 @@ extern "C" {
                                       * synthesis block (styleganv1.py:607: self.to_rgb) runs inside the epilogue -- rgb_y[b,o] = rgb_bias[o] +
                                       * sum_co rgb_w[o,co] * y[b,co] on the epilogue's own registers; y may then be NULL (the activation is
                                       * neither stored nor re-read).  No y_pre / ACCUM / modulation, ksplit 1. */
+#define SPK_EPI_RESIDUAL 65536u       /* stride-1 1x1 convs only (tile configs 8-12, 14, 15; split-K: applied by the finisher): `residual`
+                                      * [B, groups*Cout, H, W] joins BEFORE the activation -- epi(v) = lrelu(out_scale*v + bias[co] +
+                                      * residual[b,co,h,w]) -- where SPK_EPI_ACCUM adds after it: relu(bn3(conv3(x)) + identity) at the end
+                                      * of a torchvision Bottleneck (model.py:60-62) once bn3 is folded into the weights and a bias.  With
+                                      * BIAS / LRELU / ACCUM on a plain input only (no STATS / NOISE / STYLE / IN_AFFINE_RELU / y_pre); 16-byte aligned
+                                      * on configs 12, 14, 15. */
 #define SPK_CONV_UP_FIR1331 512u     /* with UPSAMPLE2X: the x2 interpolation is upfirdn2d(up=2, FIR [1,3,3,1], pad (2,1)) --
                                       * the same (.75,.25) taps as bilinear, but neighbours outside the image are zero */
 
@@ -156,6 +162,7 @@ typedef struct spk_conv2d_desc {
     float* rgb_y;
     int32_t rgb_channels;
     int32_t reserved;
+    const float* residual;   /* SPK_EPI_RESIDUAL: [B, groups*Cout, H, W] (the layout of y), added before the activation; else NULL */
 } spk_conv2d_desc;
 
 int spk_conv2d_num_configs(void);
@@ -620,8 +627,11 @@ enum {
     SPK_OP_TORGB = 5,             /* desc: spk_torgb_args           -> spk_conv1x1_small_fwd / spk_torgb_mod_skip_fwd */
     SPK_OP_DEMOD_GROUPED = 6,     /* desc: spk_demod_grouped_args   -> spk_modconv_demod_grouped */
     SPK_OP_PIXELNORM = 7,         /* desc: spk_pixelnorm_args       -> spk_pixelnorm_fwd */
-    SPK_OP_UPSAMPLE2X = 8         /* desc: spk_upsample2x_args      -> spk_upsample2x_fwd (the x2 image of a block whose conv1
+    SPK_OP_UPSAMPLE2X = 8,        /* desc: spk_upsample2x_args      -> spk_upsample2x_fwd (the x2 image of a block whose conv1
                                    * runs as Winograd, styleganv1.py:621,624) */
+    SPK_OP_MAXPOOL3X3S2 = 9,      /* desc: spk_maxpool3x3s2_args    -> spk_maxpool3x3s2_fwd (resnet50.maxpool, model.py:62) */
+    SPK_OP_GLOBAL_AVGPOOL = 10    /* desc: spk_global_avgpool_args  -> spk_global_avgpool_fwd (resnet50.avgpool): with the two kinds a
+                                   * whole BatchNorm-folded trunk pass is one list */
 };
 typedef struct spk_op { int32_t kind; int32_t reserved; const void* desc; } spk_op;
 typedef struct spk_fc_args {
@@ -640,6 +650,10 @@ typedef struct spk_torgb_args {   /* mod NULL: plain 1x1 (styleganv1.py:607); el
 typedef struct spk_demod_grouped_args { const spk_demod_group* groups; int32_t n_groups, B; float eps; int32_t reserved; } spk_demod_grouped_args;
 typedef struct spk_pixelnorm_args { const float* x; float* y; int32_t B, C; int64_t HW; float eps; int32_t sqrt_form; } spk_pixelnorm_args;
 typedef struct spk_upsample2x_args { const float* x; float* y; int64_t planes; int32_t Hin, Win; int32_t zero_border, reserved; } spk_upsample2x_args;
+typedef struct spk_maxpool3x3s2_args {   /* in_scale / in_shift NULL: a plain input */
+    const float* x; const float* in_scale; const float* in_shift; float* y; int32_t B, C, Hin, Win;
+} spk_maxpool3x3s2_args;
+typedef struct spk_global_avgpool_args { const float* x; float* y; int64_t planes; int64_t HW; } spk_global_avgpool_args;
 int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask, void* stream);
 
 #ifdef __cplusplus

@@ -34,7 +34,8 @@ class Conv2dDesc(C.Structure):
                 ("out_scale_bc", C.c_void_p), ("act_gain", C.c_float),
                 ("groups", C.c_int32), ("group_in_stride", C.c_int32), ("stats_slots", C.c_int32),
                 ("accum_half", C.c_void_p), ("out_scale_dev", C.c_void_p),
-                ("rgb_w", C.c_void_p), ("rgb_bias", C.c_void_p), ("rgb_y", C.c_void_p), ("rgb_channels", C.c_int32), ("reserved", C.c_int32)]
+                ("rgb_w", C.c_void_p), ("rgb_bias", C.c_void_p), ("rgb_y", C.c_void_p), ("rgb_channels", C.c_int32), ("reserved", C.c_int32),
+                ("residual", C.c_void_p)]
 
 
 CONV_IN_BATCH_SCALE = 256
@@ -45,6 +46,7 @@ CONV_BF16X3 = 4096
 EPI_ACCUM_HALF = 8192
 CONV_WINOGRAD = 16384
 EPI_TORGB = 32768
+EPI_RESIDUAL = 65536
 
 
 FC_MAX_GROUPS = 16
@@ -83,6 +85,7 @@ class DemodGroup(C.Structure):
 
 # ---- launch lists (include/spk.h: spk_launch_list) ----
 OP_CONV2D, OP_FC, OP_FC_GROUPED, OP_BIAS_NOISE_STYLE, OP_TORGB, OP_DEMOD_GROUPED, OP_PIXELNORM, OP_UPSAMPLE2X = 1, 2, 3, 4, 5, 6, 7, 8
+OP_MAXPOOL3X3S2, OP_GLOBAL_AVGPOOL = 9, 10
 ALL_OPS = 0xFFFFFFFF
 
 
@@ -119,6 +122,15 @@ class DemodGroupedArgs(C.Structure):
 class Upsample2xArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("planes", C.c_int64), ("Hin", C.c_int32), ("Win", C.c_int32),
                 ("zero_border", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MaxPool3x3s2Args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("in_scale", C.c_void_p), ("in_shift", C.c_void_p), ("y", C.c_void_p), ("B", C.c_int32),
+                ("C", C.c_int32), ("Hin", C.c_int32), ("Win", C.c_int32)]
+
+
+class GlobalAvgPoolArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("planes", C.c_int64), ("HW", C.c_int64)]
 
 
 class PixelNormArgs(C.Structure):

@@ -6,7 +6,7 @@
 // 128co x 128px block (2x2 waves, each 2x2 MFMA tiles of 32x32), walks 32-channel k-tiles with 16-byte loads (4 + 4 per
 // thread per k-tile against 64 MFMAs per wave), LDS double-buffered with one barrier per k-tile, fragments read one k-step
 // ahead.  Pixels are the flattened (b, pix) axis; HW % 32 == 0 keeps every 32-pixel fragment row inside one image.
-// Epilogue as in the tap kernel: out_scale -> bias -> lrelu -> accumulate -> store -> BatchNorm sums (reduced across the
+// Epilogue as in the tap kernel: out_scale -> bias -> residual (SPK_EPI_RESIDUAL) -> lrelu -> accumulate -> store -> BatchNorm sums (reduced across the
 // waves in LDS, one copy per pixel tile).  Grouped launches as there (blockIdx.y = group * co tiles + co tile).
 //
 // Epilogue: the 128 x 128 block goes through LDS so that a channel row leaves as 512 contiguous bytes of 16-byte stores;
@@ -35,6 +35,7 @@ struct GemmArgs {
     const float* bias;
     const float* in_scale;
     const float* in_shift;
+    const float* residual;   // [B][Cy][HW] or NULL: added before the activation (SPK_EPI_RESIDUAL)
     double* stats;
     float* y;
     int B, Cin, Cout, HW;    // Cin / Cout per group
@@ -209,6 +210,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gemm_kernel(const GemmArgs p) 
     __syncthreads();
     const bool f_bias = p.flags & SPK_EPI_BIAS, f_lrelu = p.flags & SPK_EPI_LRELU;
     const bool f_accum = p.flags & SPK_EPI_ACCUM, f_stats = (p.flags & SPK_EPI_STATS) && !SPK_GLAB(16);
+    const bool f_res = p.residual != nullptr;
     const int ocol = (tid & 31) * 4;
     const long long Po = P0 + ocol;
     const bool o_ok = Po < p.n_px;
@@ -230,6 +232,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gemm_kernel(const GemmArgs p) 
             float4 v = *reinterpret_cast<const float4*>(ot + cl * OPITCH + ocol);
             const float bb = f_bias ? p.bias[cg] : 0.f;
             v.x = v.x * p.out_scale + bb; v.y = v.y * p.out_scale + bb; v.z = v.z * p.out_scale + bb; v.w = v.w * p.out_scale + bb;
+            if (f_res) {
+                const float4 q = *reinterpret_cast<const float4*>(p.residual + ooff + (size_t)cg * HW);
+                v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+            }
             if (f_lrelu) {
                 v.x = (v.x > 0.f ? v.x : v.x * p.slope) * p.act_gain; v.y = (v.y > 0.f ? v.y : v.y * p.slope) * p.act_gain;
                 v.z = (v.z > 0.f ? v.z : v.z * p.slope) * p.act_gain; v.w = (v.w > 0.f ? v.w : v.w * p.slope) * p.act_gain;
@@ -275,12 +281,15 @@ long long gemm1x1_pixel_tiles(int B, int H, int W) { return ((long long)B * H * 
 
 int run_1x1_gemm(const spk_conv2d_desc* d, hipStream_t stream) {
     SPK_REQUIRE(gemm1x1_takes(d->kh, d->stride, d->Cin, d->H, d->W), "conv2d: config 12 (GEMM form) takes stride-1 1x1 convs with Cin %% 4 == 0 and H*W %% 32 == 0");
-    SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU)) && !d->out_scale_bc && !d->y_pre,
-                "conv2d: config 12 (GEMM form) takes bias / lrelu / accum / stats / in-affine only");
+    SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_RESIDUAL)) && !d->out_scale_bc && !d->y_pre,
+                "conv2d: config 12 (GEMM form) takes bias / lrelu / accum / stats / in-affine / residual only");
+    SPK_REQUIRE(!(d->flags & SPK_EPI_RESIDUAL) || (reinterpret_cast<uintptr_t>(d->residual) & 15) == 0,
+                "conv2d: config 12 with SPK_EPI_RESIDUAL needs a 16-byte aligned residual");
     SPK_REQUIRE(((reinterpret_cast<uintptr_t>(d->x) | reinterpret_cast<uintptr_t>(d->w_packed) | reinterpret_cast<uintptr_t>(d->y)) & 15) == 0,
                 "conv2d: config 12 needs 16-byte aligned x, y and weights");
     GemmArgs a;
     a.x = d->x; a.w = d->w_packed; a.bias = d->bias; a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.stats = d->stats; a.y = d->y;
+    a.residual = (d->flags & SPK_EPI_RESIDUAL) ? d->residual : nullptr;
     a.B = d->B; a.Cin = d->Cin; a.Cout = d->Cout; a.HW = d->H * d->W; a.n_px = (long long)d->B * a.HW;
     a.G = d->groups > 1 ? d->groups : 1;
     a.gin = a.G > 1 ? d->group_in_stride : d->Cin;

@@ -23,7 +23,7 @@
 //     skips scale / bias / activation / statistics work that the launch does not ask for.
 // Three workgroups per CU (four for the 64-row tile).  ONE-dimensional grid, co tile fastest, each XCD walks a contiguous
 // run of work items: the co tiles of a pixel tile run back to back on one L2 and x is fetched from HBM once.
-// Epilogue: out_scale -> bias -> lrelu -> accumulate (y itself, or a HALF-RESOLUTION tensor added at the even pixels: the
+// Epilogue: out_scale -> bias -> residual (SPK_EPI_RESIDUAL: the Bottleneck's identity, before the activation) -> lrelu -> accumulate (y itself, or a HALF-RESOLUTION tensor added at the even pixels: the
 // data gradient of the block's stride-2 downsample conv, never dilated in memory) -> store -> BatchNorm sums.
 //
 // replaces: F.conv2d of every stride-1 1x1 conv of the torchvision trunk (conv1 / conv3 / downsample.0, model.py:60-62)
@@ -50,6 +50,7 @@ struct Gemm2Args {
     const float* in_scale;
     const float* in_shift;
     const float* acc_half;   // [B][Cy][Hh][Wh] or NULL: added at the even pixels (SPK_EPI_ACCUM_HALF)
+    const float* residual;   // [B][Cy][HW] or NULL: added before the activation (SPK_EPI_RESIDUAL)
     double* stats;
     float* y;
     int Cin, Cout, HW, W;    // Cin / Cout per group
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(256, (MT >= 4 ? 3 : 4)) void gemm2_kernel(const Gem
     float* const red = smem + PASS_ROWS * BP;               // [2][CO_T] row sums / sums of squares
     const bool f_bias = p.flags & SPK_EPI_BIAS, f_lrelu = p.flags & SPK_EPI_LRELU;
     const bool f_accum = p.flags & SPK_EPI_ACCUM, f_stats = p.flags & SPK_EPI_STATS;
-    const bool f_half = p.acc_half != nullptr;
+    const bool f_half = p.acc_half != nullptr, f_res = p.residual != nullptr;
     const bool f_affine = f_bias || p.out_scale != 1.f;
     const int rsub = tid >> 5, ocol = (tid & 31) * 4;
     const unsigned Po = P0 + (unsigned)ocol;
@@ -279,6 +280,7 @@ __global__ __launch_bounds__(256, (MT >= 4 ? 3 : 4)) void gemm2_kernel(const Gem
         float* const y_pass = p.y + (size_t)(grp * p.Cout + row0) * HW;                                 // uniform
         const float* const half_pass = f_half ? p.acc_half + (size_t)(grp * p.Cout + row0) * p.HWh : nullptr;
         const float* const bias_pass = f_bias ? p.bias + grp * p.Cout + row0 : nullptr;
+        const float* const res_pass = f_res ? p.residual + (size_t)(grp * p.Cout + row0) * HW : nullptr;       // addressed as y is
         auto rows = [&](auto masked_) {
             constexpr bool MASKED = decltype(masked_)::value;
             // fully unrolled: iteration i's LDS offsets are immediates, its global addresses a scalar base + the lane's constant offset
@@ -292,6 +294,10 @@ __global__ __launch_bounds__(256, (MT >= 4 ? 3 : 4)) void gemm2_kernel(const Gem
                     if (f_affine) {
                         const float bb = f_bias ? bias_pass[8 * i + rsub] : 0.f;
                         v0 = v0 * p.out_scale + bb; v1 = v1 * p.out_scale + bb; v2 = v2 * p.out_scale + bb; v3 = v3 * p.out_scale + bb;
+                    }
+                    if (f_res) {                             // one 16-byte load per lane and row
+                        const float4 q = *reinterpret_cast<const float4*>(res_pass + (size_t)(i * 8) * HW + o_lane);
+                        v0 += q.x; v1 += q.y; v2 += q.z; v3 += q.w;
                     }
                     if (f_lrelu) {
                         v0 = (v0 > 0.f ? v0 : v0 * p.slope) * p.act_gain; v1 = (v1 > 0.f ? v1 : v1 * p.slope) * p.act_gain;
@@ -416,9 +422,11 @@ int run_1x1_gemm2(const spk_conv2d_desc* d, hipStream_t stream) {
     SPK_REQUIRE(d->B * Cx * HWl < (1ll << 30) && d->B * Cy * HWl < (1ll << 30), "conv2d: configs 14 / 15 address x and y with 32-bit byte offsets");
     SPK_REQUIRE(!(d->flags & SPK_CONV_IN_AFFINE_RELU) || ((reinterpret_cast<uintptr_t>(d->in_scale) | reinterpret_cast<uintptr_t>(d->in_shift)) & 15) == 0,
                 "conv2d: configs 14 / 15 with IN_AFFINE_RELU need 16-byte aligned in_scale / in_shift");
-    SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_ACCUM_HALF)) &&
+    SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_ACCUM_HALF | SPK_EPI_RESIDUAL)) &&
                     !d->out_scale_bc && !d->y_pre,
-                "conv2d: configs 14 / 15 (GEMM form) take bias / lrelu / accum / accum-half / stats / in-affine only");
+                "conv2d: configs 14 / 15 (GEMM form) take bias / lrelu / accum / accum-half / stats / in-affine / residual only");
+    SPK_REQUIRE(!(d->flags & SPK_EPI_RESIDUAL) || (reinterpret_cast<uintptr_t>(d->residual) & 15) == 0,
+                "conv2d: configs 14 / 15 with SPK_EPI_RESIDUAL need a 16-byte aligned residual");
     SPK_REQUIRE(((reinterpret_cast<uintptr_t>(d->x) | reinterpret_cast<uintptr_t>(d->w_packed) | reinterpret_cast<uintptr_t>(d->y)) & 15) == 0,
                 "conv2d: configs 14 / 15 need 16-byte aligned x, y and weights");
     Gemm2Args a;
@@ -432,6 +440,7 @@ int run_1x1_gemm2(const spk_conv2d_desc* d, hipStream_t stream) {
     a.stats_slots = d->stats_slots > 1 ? d->stats_slots : 1;
     a.flags = d->flags; a.slope = d->lrelu_slope; a.out_scale = d->out_scale; a.act_gain = d->act_gain != 0.f ? d->act_gain : 1.f;
     a.acc_half = nullptr; a.Wh = a.HWh = 0;
+    a.residual = (d->flags & SPK_EPI_RESIDUAL) ? d->residual : nullptr;
     a.dbg = nullptr;
 #ifdef SPK_G2_LAB
     if (const char* e = getenv("SPK_G2_DBG")) a.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 10));

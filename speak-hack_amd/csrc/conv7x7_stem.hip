@@ -41,6 +41,7 @@ typedef __attribute__((address_space(3))) unsigned char st_lds_u8;
 struct StemArgs {
     const float* x; const float* w; float* y; double* stats;
     int B, Cx, gin, Cy, H, W, Hin, Win, tiles_x, tiles_y, stats_slots;
+    const float* bias; float slope;      // EPI instantiation: y = lrelu(conv + bias[co]) (a BatchNorm-folded stem: bn1 + relu)
 };
 
 template <int I, int N, class F>
@@ -51,7 +52,7 @@ __device__ __forceinline__ void st_static_for(F&& f) {
     }
 }
 
-template <bool STATS>
+template <bool STATS, bool EPI = false>
 __global__ __launch_bounds__(256, 2) void stem7x7s2_kernel(const StemArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -159,12 +160,19 @@ __global__ __launch_bounds__(256, 2) void stem7x7s2_kernel(const StemArgs p) {
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 float* yrow = p.y + (((size_t)b * p.Cy + (size_t)grp * 64 + n * 32 + l32) * p.H + oy) * p.W;
+                float bb = 0.f;
+                if constexpr (EPI) bb = p.bias ? p.bias[grp * 64 + n * 32 + l32] : 0.f;
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     const int ox = ox0 + 8 * q4 + 4 * half;
                     const bool in = oy < p.H && ox < p.W;                  // (W % 4 == 0: a group of four is in or out)
-                    const float v0 = acc[pr][n][16 * blk + 4 * q4], v1 = acc[pr][n][16 * blk + 4 * q4 + 1];
-                    const float v2 = acc[pr][n][16 * blk + 4 * q4 + 2], v3 = acc[pr][n][16 * blk + 4 * q4 + 3];
+                    float v0 = acc[pr][n][16 * blk + 4 * q4], v1 = acc[pr][n][16 * blk + 4 * q4 + 1];
+                    float v2 = acc[pr][n][16 * blk + 4 * q4 + 2], v3 = acc[pr][n][16 * blk + 4 * q4 + 3];
+                    if constexpr (EPI) {
+                        v0 += bb; v1 += bb; v2 += bb; v3 += bb;
+                        v0 = v0 > 0.f ? v0 : v0 * p.slope; v1 = v1 > 0.f ? v1 : v1 * p.slope;
+                        v2 = v2 > 0.f ? v2 : v2 * p.slope; v3 = v3 > 0.f ? v3 : v3 * p.slope;
+                    }
                     if (in) {
                         *reinterpret_cast<float4*>(yrow + ox) = make_float4(v0, v1, v2, v3);
                         if (STATS) {
@@ -237,8 +245,10 @@ int pack_stem(const PackList& list, int n, float* w_packed, int Cin, int Cout, i
 int run_stem(const spk_conv2d_desc* d, hipStream_t stream) {
     const int G = d->groups > 1 ? d->groups : 1;
     SPK_REQUIRE(stem_takes(d->kh, d->stride, d->Cin, d->Cout, d->H, d->W) && d->kw == 7, "conv2d: config %d is the 7x7 stride-2 stem (Cin 3, Cout 64, W %% 4 == 0)", kStemConfig);
-    SPK_REQUIRE(!(d->flags & ~SPK_EPI_STATS) && d->out_scale == 1.f && !d->out_scale_dev && !d->out_scale_bc && !d->y_pre,
-                "conv2d: the stem form takes SPK_EPI_STATS only");
+    const bool epi = d->flags & (SPK_EPI_BIAS | SPK_EPI_LRELU);
+    SPK_REQUIRE(!(d->flags & ~(SPK_EPI_STATS | SPK_EPI_BIAS | SPK_EPI_LRELU)) && !(epi && (d->flags & SPK_EPI_STATS)) && d->out_scale == 1.f &&
+                    !d->out_scale_dev && !d->out_scale_bc && !d->y_pre && (d->act_gain == 0.f || d->act_gain == 1.f),
+                "conv2d: the stem form takes SPK_EPI_STATS, or SPK_EPI_BIAS / SPK_EPI_LRELU (a BatchNorm-folded stem), only");
     SPK_REQUIRE(((reinterpret_cast<uintptr_t>(d->y) | reinterpret_cast<uintptr_t>(d->w_packed)) & 15) == 0, "conv2d: stem form: y and w_packed must be 16-byte aligned");
     SPK_REQUIRE((long long)d->Hin * d->Win * 3 < (1ll << 29), "conv2d: stem form: image too large for 32-bit offsets");
     StemArgs a;
@@ -249,14 +259,17 @@ int run_stem(const spk_conv2d_desc* d, hipStream_t stream) {
     a.Cy = G * 64;
     stem_tiles(d->H, d->W, &a.tiles_x, &a.tiles_y);
     a.stats_slots = d->stats_slots > 1 ? d->stats_slots : 1;
+    a.bias = (d->flags & SPK_EPI_BIAS) ? d->bias : nullptr;
+    a.slope = (d->flags & SPK_EPI_LRELU) ? d->lrelu_slope : 1.f;
     const long long tiles = (long long)a.tiles_x * a.tiles_y * d->B;
     SPK_REQUIRE(tiles < (1ll << 31), "conv2d: stem form: too many tiles");
-    auto kern = a.stats ? &stem7x7s2_kernel<true> : &stem7x7s2_kernel<false>;
-    static bool raised[2] = {false, false};
-    if (!raised[a.stats ? 1 : 0]) {
+    auto kern = a.stats ? &stem7x7s2_kernel<true> : (epi ? &stem7x7s2_kernel<false, true> : &stem7x7s2_kernel<false>);
+    static bool raised[3] = {false, false, false};
+    const int which = a.stats ? 1 : (epi ? 2 : 0);
+    if (!raised[which]) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised[a.stats ? 1 : 0] = true;
+        raised[which] = true;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)G), dim3(256), ST_LDS_BYTES, stream, a);
     return spk::check_launch("stem7x7s2_kernel");

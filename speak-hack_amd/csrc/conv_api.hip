@@ -8,6 +8,9 @@ namespace spkconv {
 // y = epi( sum_z ws[z] ): fixed summation order (bitwise reproducible), one element per thread.
 // BN statistics: a wave whose 64 elements share one output channel reduces with a butterfly and issues
 // one fp64 atomic; ragged waves fall back to per-lane atomics.
+// RES: the residual-before-activation stage (SPK_EPI_RESIDUAL) compiled in -- its own instantiation, so that the finisher every
+// other sliced launch runs keeps its registers.
+template <bool RES>
 __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const ConvArgs p, const float* __restrict__ ws, int ksplit) {
     const size_t HW = (size_t)p.H * p.W;
     const size_t total = (size_t)p.B * p.Cout * HW;
@@ -30,6 +33,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const ConvArgs p, 
             if (p.out_scale_bc) v *= p.out_scale_bc[(size_t)b * p.Cout + co];
             if (f_bias) v += p.bias[co];
             if (f_noise) v += p.noise_w[co] * p.noise[(size_t)b * HW + pix];
+            if constexpr (RES) v += p.residual[idx];        // before the activation
             if (f_lrelu) v = (v > 0.f ? v : v * p.slope) * p.act_gain;
             if (p.y_pre) p.y_pre[idx] = v;
             if (f_style) {
@@ -63,6 +67,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const ConvArgs p, 
 // Vector form for planes that are a multiple of 4 floats: one thread finishes 4 consecutive outputs of one (b, co)
 // plane with 16-byte loads of every slice; BatchNorm sums are reduced over the lanes that share the plane (the whole
 // wave, or a power-of-two lane segment for tiny planes) before the fp64 atomics.
+template <bool RES>
 __global__ __launch_bounds__(256) void splitk_epilogue_vec_kernel(const ConvArgs p, const float* __restrict__ ws, int ksplit) {
     const size_t HW = (size_t)p.H * p.W;
     const size_t total4 = (size_t)p.B * p.Cout * HW / 4, total = total4 * 4;
@@ -100,12 +105,18 @@ __global__ __launch_bounds__(256) void splitk_epilogue_vec_kernel(const ConvArgs
             }
             float4 nz = make_float4(0.f, 0.f, 0.f, 0.f), old = nz;
             if (f_noise) nz = *reinterpret_cast<const float4*>(p.noise + (size_t)b * HW + pix);
+            float resv[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (RES) {                             // before the activation
+                const float4 res = *reinterpret_cast<const float4*>(p.residual + idx);
+                resv[0] = res.x; resv[1] = res.y; resv[2] = res.z; resv[3] = res.w;
+            }
             if (f_accum) old = *reinterpret_cast<const float4*>(p.y + idx);
             const float nzv[4] = {nz.x, nz.y, nz.z, nz.w}, oldv[4] = {old.x, old.y, old.z, old.w};
             float pre[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float t = v[k] * scale + bb + nw * nzv[k];
+                if constexpr (RES) t += resv[k];
                 if (f_lrelu) t = (t > 0.f ? t : t * p.slope) * p.act_gain;
                 pre[k] = t;
                 if (f_style) t = t * s0 + s1;
@@ -137,14 +148,14 @@ int launch_splitk_epilogue(const ConvArgs& a_in, const float* ws, int ksplit, hi
     // lanes of a wave must split evenly into planes for the segmented sums: q4 a multiple of 64, or a power of two below
     const bool seg_ok = HW % 4 == 0 && (q4 % 64 == 0 || (q4 < 64 && (q4 & (q4 - 1)) == 0));
     const bool aligned = (uintptr_t)ws % 16 == 0 && (uintptr_t)a.y % 16 == 0 && (!a.y_pre || (uintptr_t)a.y_pre % 16 == 0) &&
-                         (!a.noise || (uintptr_t)a.noise % 16 == 0);
+                         (!a.noise || (uintptr_t)a.noise % 16 == 0) && (uintptr_t)a.residual % 16 == 0;
     if (seg_ok && aligned) {
         const unsigned blocks = (unsigned)std::min<size_t>((out_floats / 4 + 255) / 256, 256 * 8);
-        hipLaunchKernelGGL(splitk_epilogue_vec_kernel, dim3(blocks), dim3(256), 0, stream, a, ws, ksplit);
+        hipLaunchKernelGGL(a.residual ? splitk_epilogue_vec_kernel<true> : splitk_epilogue_vec_kernel<false>, dim3(blocks), dim3(256), 0, stream, a, ws, ksplit);
         return spk::check_launch("splitk_epilogue_vec_kernel");
     }
     const unsigned blocks = (unsigned)std::min<size_t>((out_floats + 255) / 256, 256 * 8);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, stream, a, ws, ksplit);
+    hipLaunchKernelGGL(a.residual ? splitk_epilogue_kernel<true> : splitk_epilogue_kernel<false>, dim3(blocks), dim3(256), 0, stream, a, ws, ksplit);
     return spk::check_launch("splitk_epilogue_kernel");
 }
 
@@ -589,10 +600,18 @@ int spk_conv2d_fwd(const spk_conv2d_desc* d, void* stream) {
     SPK_REQUIRE(!(d->flags & SPK_EPI_STATS) || d->stats, "conv2d: SPK_EPI_STATS without stats");
     SPK_REQUIRE(d->stats_slots >= 0 && d->stats_slots <= 65536, "conv2d: stats_slots must be in [0, 65536] (got %d)", d->stats_slots);
     SPK_REQUIRE(!aff || (d->in_scale && d->in_shift), "conv2d: IN_AFFINE_RELU without in_scale/in_shift");
+    if (d->flags & SPK_EPI_RESIDUAL) {
+        SPK_REQUIRE(d->kh == 1 && d->kw == 1 && d->stride == 1, "conv2d: SPK_EPI_RESIDUAL is an epilogue of the stride-1 1x1 convs only (got %dx%d stride %d)",
+                    d->kh, d->kw, d->stride);
+        SPK_REQUIRE(d->residual && (reinterpret_cast<uintptr_t>(d->residual) & 3) == 0, "conv2d: SPK_EPI_RESIDUAL without residual");
+        SPK_REQUIRE(!(d->flags & (SPK_EPI_STATS | SPK_EPI_NOISE | SPK_EPI_STYLE | SPK_EPI_ACCUM_HALF | SPK_CONV_IN_AFFINE_RELU)) && !d->y_pre,
+                    "conv2d: SPK_EPI_RESIDUAL goes with SPK_EPI_BIAS / LRELU / ACCUM on a plain input only (not STATS / NOISE / STYLE / "
+                    "ACCUM_HALF / IN_AFFINE_RELU / y_pre)");
+    }
     SPK_REQUIRE((long long)d->B * d->Cout * d->H * d->W < (1ll << 40), "conv2d: tensor too large");
     if (d->groups > 1) {
-        SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_ACCUM_HALF)) && !d->out_scale_bc,
-                    "conv2d: a grouped launch takes bias / lrelu / accum / accum-half / stats / in-affine only");
+        SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_ACCUM_HALF | SPK_EPI_RESIDUAL)) && !d->out_scale_bc,
+                    "conv2d: a grouped launch takes bias / lrelu / accum / accum-half / stats / in-affine / residual only");
         SPK_REQUIRE(d->group_in_stride == 0 || d->group_in_stride >= d->Cin, "conv2d: group_in_stride must be 0 (shared input) or >= Cin");
     }
     int cfg = d->config;
@@ -612,7 +631,7 @@ int spk_conv2d_fwd(const spk_conv2d_desc* d, void* stream) {
         return run_stem(&dd, s);
     }
     SPK_REQUIRE(!(d->flags & SPK_EPI_ACCUM_HALF), "conv2d: SPK_EPI_ACCUM_HALF is built into the GEMM form of a 1x1 (configs 14, 15)");
-    if (d->kh == 1) return run_1x1(d->stride, cfg, mode, &dd, s);
+    if (d->kh == 1) return run_1x1(d->stride, cfg, (d->flags & SPK_EPI_RESIDUAL) ? MODE_PLAIN_RESIDUAL : mode, &dd, s);
     if (d->kh == 3 && d->stride == 1) {
         if ((d->flags & SPK_EPI_STATS) && mode != MODE_AFFINE_RELU) {
             SPK_REQUIRE(mode == MODE_PLAIN, "conv2d: SPK_EPI_STATS on a 3x3 stride-1 conv goes with a plain or BatchNorm-folded input (not upsample / batch scale)");

@@ -5,6 +5,9 @@ namespace spkconv {
 
 template <class C, int S>
 static int by_mode(int mode, const spk_conv2d_desc* d, hipStream_t s) {
+    if constexpr (S == 1) {
+        if (mode == MODE_PLAIN_RESIDUAL) return run<C, 1, 1, 1, MODE_PLAIN_RESIDUAL>(d, s);
+    }
     return mode == MODE_AFFINE_RELU ? run<C, 1, 1, S, MODE_AFFINE_RELU>(d, s) : run<C, 1, 1, S, MODE_PLAIN>(d, s);
 }
 

@@ -38,7 +38,8 @@ typedef __attribute__((address_space(3))) float lds_f32_t;        // LDS-typed a
 
 // MODE_PLAIN_STATS: MODE_PLAIN of a 3x3 stride-1 conv with the BatchNorm-statistics epilogue compiled in (see HAS_STATS in
 // the kernel); every other kernel shape carries that epilogue in all its modes.
-enum Mode { MODE_PLAIN = 0, MODE_UPSAMPLE = 1, MODE_AFFINE_RELU = 2, MODE_BATCH_SCALE = 3, MODE_UPSAMPLE_BATCH_SCALE = 4, MODE_PLAIN_STATS = 5 };
+enum Mode { MODE_PLAIN = 0, MODE_UPSAMPLE = 1, MODE_AFFINE_RELU = 2, MODE_BATCH_SCALE = 3, MODE_UPSAMPLE_BATCH_SCALE = 4, MODE_PLAIN_STATS = 5,
+            MODE_PLAIN_RESIDUAL = 6 };   // MODE_PLAIN of a stride-1 1x1 conv with the residual-before-activation epilogue (SPK_EPI_RESIDUAL) compiled in
 
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -82,6 +83,7 @@ struct ConvArgs {
     int pshift;              // 2x2 (parity) kernels: 1 = window rows y-1, y / destination pixel (2y-1+py, 2x-1+px) -- the
                              // ConvTranspose2d(4, stride 2, pad 1) form; 0 = rows y, y+1 / (2y+py, 2x+px) -- the 3x3 s2 data gradient
     int staged;              // epilogue through LDS with 16-byte stores (set by the host when the tile / tensors allow it)
+    const float* residual;   // SPK_EPI_RESIDUAL (stride-1 1x1 instantiations and the split-K finisher): [B][Cy][H][W], added before the activation
 };
 
 template <int WM_, int WN_, int MT_, int NT_, int CIT_>
@@ -578,8 +580,13 @@ __global__ __launch_bounds__(C::NTHREADS) void conv_kernel(const ConvArgs p) {
     // decoders' hot kernels, which never ask for it: with its (runtime-dead) code inside, the 64 -> 64 @256^2 layer ran 3 %
     // slower (308 -> 318 us, +4 VGPRs; headline 3.71 -> 3.77 ms per step).  A plain 3x3 stride-1 conv that wants statistics
     // is the separate instantiation MODE_PLAIN_STATS (conv_inst_3x3s1_stats.hip).
-    constexpr bool HAS_STATS = !(KH == 3 && KW == 3 && S == 1) || MODE == MODE_AFFINE_RELU || MODE == MODE_PLAIN_STATS;
+    constexpr bool HAS_STATS = (!(KH == 3 && KW == 3 && S == 1) || MODE == MODE_AFFINE_RELU || MODE == MODE_PLAIN_STATS) && MODE != MODE_PLAIN_RESIDUAL;
     const bool f_accum = p.flags & SPK_EPI_ACCUM, f_stats = HAS_STATS && (p.flags & SPK_EPI_STATS) && !split;
+    // The residual-before-activation stage is an instantiation of its own, MODE_PLAIN_RESIDUAL (stride-1 1x1 only; the host rejects
+    // the flag elsewhere): as a runtime branch it cost the plain 1x1 kernels 4 VGPRs (104 -> 108 on the 128 x 128 tile, a wave per
+    // SIMD less).  It carries no statistics epilogue.  A split-K launch leaves the residual to the finisher.
+    constexpr bool HAS_RES = MODE == MODE_PLAIN_RESIDUAL;
+    const bool f_res = HAS_RES && (p.flags & SPK_EPI_RESIDUAL) && !split;
     const size_t HW = (size_t)p.H * p.W;
     const float osc = p.out_scale_dev ? p.out_scale * *p.out_scale_dev : p.out_scale;   // (uniform: one scalar load)
     if (p.staged) {
@@ -643,6 +650,10 @@ __global__ __launch_bounds__(C::NTHREADS) void conv_kernel(const ConvArgs p) {
                 if (f_noise) {
                     const float nwc = p.noise_w[cg];
                     v.x += nwc * nzv.x; v.y += nwc * nzv.y; v.z += nwc * nzv.z; v.w += nwc * nzv.w;
+                }
+                if (f_res) {
+                    const float4 q = *reinterpret_cast<const float4*>(p.residual + o0 + (size_t)cg * HW);
+                    v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
                 }
                 if (f_lrelu) {
                     v.x = (v.x > 0.f ? v.x : v.x * p.slope) * p.act_gain; v.y = (v.y > 0.f ? v.y : v.y * p.slope) * p.act_gain;
@@ -745,6 +756,7 @@ __global__ __launch_bounds__(C::NTHREADS) void conv_kernel(const ConvArgs p) {
                     if (BSC && p.out_scale_bc) v *= p.out_scale_bc[(size_t)pb[n] * p.Cy + cg];   // demodulation d[b,co]
                     v += bb;
                     if (f_noise) v += nwc * nz[n];
+                    if (f_res) v += p.residual[poff[n] + (size_t)cg * HW];
                     if (f_lrelu) v = (v > 0.f ? v : v * p.slope) * p.act_gain;
                     if (p.y_pre) p.y_pre[poff[n] + (size_t)cg * HW] = v;
                     if (f_style) v = v * (st[n][cg] + 1.f) + st[n][p.Cy + cg];
@@ -855,6 +867,7 @@ int run(const spk_conv2d_desc* d, hipStream_t stream, int Hd = 0, int Wd = 0, in
     a.Hd = Hd; a.Wd = Wd; a.pshift = pshift;
     a.x = d->x; a.wp = d->w_packed; a.bias = d->bias; a.noise_w = d->noise_w; a.noise = d->noise;
     a.style = d->style; a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.stats = d->stats; a.stats_slots = d->stats_slots > 1 ? d->stats_slots : 1; a.y = d->y; a.y_pre = d->y_pre; a.out_scale_bc = d->out_scale_bc;
+    a.residual = (d->flags & SPK_EPI_RESIDUAL) ? d->residual : nullptr;
     a.B = d->B; a.Cin = d->Cin; a.Cout = d->Cout; a.H = d->H; a.W = d->W; a.Hs = d->Hin; a.Ws = d->Win;
     a.G = d->groups > 1 ? d->groups : 1;
     a.gin = a.G > 1 ? d->group_in_stride : d->Cin;
@@ -898,7 +911,7 @@ int run(const spk_conv2d_desc* d, hipStream_t stream, int Hd = 0, int Wd = 0, in
         constexpr bool can_halve = C::MT == 2;
         const int rounds = same_slots(tile_bytes + red_bytes) ? 1 : ((can_halve && same_slots(tile_bytes / 2 + red_bytes)) ? 2 : 0);
         if (allow && rounds && KH != 2 && ksplit == 1 && g.TW >= 4 && d->W % 4 == 0 && C::NTHREADS % (C::PIX_T / 4) == 0 &&
-            (C::CO_T / rounds) % (C::NTHREADS / (C::PIX_T / 4)) == 0 && aligned(d->y) && aligned(d->y_pre) && aligned(d->noise)) {
+            (C::CO_T / rounds) % (C::NTHREADS / (C::PIX_T / 4)) == 0 && aligned(d->y) && aligned(d->y_pre) && aligned(d->noise) && aligned(a.residual)) {
             a.staged = rounds;
             g.lds_bytes = std::max(lds_now, tile_bytes / rounds + red_bytes);
         }

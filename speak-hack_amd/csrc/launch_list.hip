@@ -57,6 +57,16 @@ extern "C" int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask,
                 rc = spk_upsample2x_fwd(a->x, a->y, a->planes, a->Hin, a->Win, a->zero_border, stream);
                 break;
             }
+            case SPK_OP_MAXPOOL3X3S2: {
+                const spk_maxpool3x3s2_args* a = static_cast<const spk_maxpool3x3s2_args*>(op.desc);
+                rc = spk_maxpool3x3s2_fwd(a->x, a->in_scale, a->in_shift, a->y, a->B, a->C, a->Hin, a->Win, stream);
+                break;
+            }
+            case SPK_OP_GLOBAL_AVGPOOL: {
+                const spk_global_avgpool_args* a = static_cast<const spk_global_avgpool_args*>(op.desc);
+                rc = spk_global_avgpool_fwd(a->x, a->y, a->planes, a->HW, stream);
+                break;
+            }
             default:
                 return spk::fail(SPK_EUNSUPPORTED, "launch_list: op %d: unknown kind %d", i, op.kind);
         }

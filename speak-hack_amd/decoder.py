@@ -235,18 +235,10 @@ class StyleGenerator(nn.Module):
         train-mode mixing branch, or ``False`` to skip the branch."""
         L = self.synthesis.num_layers
         syn = self.synthesis
-        if (not self.training and syn.use_plan and features.is_cuda and features.dim() == 2 and len(syn.layers) * 2 + 1 <= ops.L.FC_MAX_GROUPS
+        if (not self.training and self.plan_serves(features)
                 and not (torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in self.parameters())))):
             # eval + no gradient: mapping, truncation and synthesis as ONE launch list (one crossing of the C boundary)
-            if noises is not None and len(noises) != 2 * len(syn.layers) + 1:
-                raise ValueError(f"expected {2 * len(syn.layers) + 1} noise tensors, got {len(noises)}")
-            B = features.size(0)
-            # (the truncation scale is folded into the style FCs' multipliers when the plan is built: part of the key)
-            key = (B, features.device, torch.cuda.current_stream(features.device).cuda_stream, "features", syn.precision,
-                   self.truncation_psi, self.truncation_cutoff)
-            p = PL.plan_for(self, key, lambda: PL.DecoderPlan(syn, B, features.device, generator=self, precision=syn.precision))
-            return p.run(features if features.stride(1) == 1 else features.contiguous(),
-                         None if noises is None else [n.contiguous() for n in noises])
+            return self.plan_forward(features, noises)
         w = self.mapping(features).unsqueeze(1).repeat(1, L, 1)
         if self.truncation_psi and self.truncation_cutoff:
             coefs = torch.ones_like(w)
@@ -263,6 +255,25 @@ class StyleGenerator(nn.Module):
                     # gradient of the mixed rows still flows into the first mapping pass (a reference quirk)
                     w[:, mix_layer:] = w2[:, mix_layer:]
         return self.synthesis(w, noises)
+
+    def plan_serves(self, features):
+        """Whether the inference launch plan can run these features (``plan_forward``)."""
+        syn = self.synthesis
+        return syn.use_plan and features.is_cuda and features.dim() == 2 and len(syn.layers) * 2 + 1 <= ops.L.FC_MAX_GROUPS
+
+    def plan_forward(self, features, noises=None):
+        """The eval forward -- mapping, truncation, synthesis; no style mixing, no host-RNG draw -- on the inference launch plan,
+        whatever ``self.training`` is (no module state is read or touched).  No gradient flows through it."""
+        syn = self.synthesis
+        if noises is not None and len(noises) != 2 * len(syn.layers) + 1:
+            raise ValueError(f"expected {2 * len(syn.layers) + 1} noise tensors, got {len(noises)}")
+        B = features.size(0)
+        # (the truncation scale is folded into the style FCs' multipliers when the plan is built: part of the key)
+        key = (B, features.device, torch.cuda.current_stream(features.device).cuda_stream, "features", syn.precision,
+               self.truncation_psi, self.truncation_cutoff)
+        p = PL.plan_for(self, key, lambda: PL.DecoderPlan(syn, B, features.device, generator=self, precision=syn.precision))
+        return p.run(features if features.stride(1) == 1 else features.contiguous(),
+                     None if noises is None else [n.contiguous() for n in noises])
 
     def forward_pair(self, features_a, features_b, noises_a=None, noises_b=None):
         """``(self(features_a, noises_a), self(features_b, noises_b))`` as ONE pass over the concatenated batch -- the two

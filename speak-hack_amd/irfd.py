@@ -21,7 +21,9 @@ import logging
 import torch
 import torch.nn as nn
 
+from . import _lib as L
 from . import autograd as AG
+from . import plan as PL
 from .decoder import StyleGenerator
 from .discriminator import StyleDiscriminator
 from .encoder import GroupedTrunks, ResNet50Trunk
@@ -70,6 +72,68 @@ class IRFD(nn.Module):
     def _emotion(self, fe):
         logits = AG.fc(fe.view(fe.size(0), -1), self.Cm.weight, self.Cm.bias, 1.0, 1.0, 1.0)
         return torch.softmax(logits, dim=1)
+
+    # ---- inference entry points (inference.py:60-76: Ei(identity_image), Ep(pose_video), Ee(emotion_video), then generate) ----
+    @torch.no_grad()
+    def encode(self, images, which):
+        """``images`` [B,3,H,W] -> features [B,2048,1,1] of the trunk ``which`` ("Ei" | "Ee" | "Ep") in eval arithmetic -- running
+        statistics in every BatchNorm whatever ``self.training`` is, no buffer updated -- on the trunk's BatchNorm-folded launch
+        plan (``plan.EncoderPlan``: one call across the C boundary)."""
+        if which not in ("Ei", "Ee", "Ep"):
+            raise ValueError(f"encode: which must be 'Ei', 'Ee' or 'Ep', got {which!r}")
+        if images.dim() != 4 or images.size(1) != 3 or images.size(0) < 1:
+            raise ValueError(f"encode: images must be [B,3,H,W], got {tuple(images.shape)}")
+        if not images.is_cuda or images.dtype != torch.float32:
+            raise L.SpkError(f"images: expected a float32 HIP tensor, got {images.dtype} on {images.device} (no CPU path)")
+        trunk = getattr(self, which)
+        B, _, H, W = images.shape
+        key = (B, H, W, images.device, torch.cuda.current_stream(images.device).cuda_stream, "encoder")
+        return PL.plan_for(trunk, key, lambda: PL.EncoderPlan(trunk, B, H, W, images.device)).run(images)
+
+    @torch.no_grad()
+    def reenact(self, identity_image, pose_frames, emotion_frames=None, *, noises=None, chunk=8):
+        """Talking-head frames: ``Gd(cat(Ei(identity).expand(T), Ee(emotion_frames), Ep(pose_frames)))`` in the feature order
+        of ``_prepare_generator_input(fi, fe, fp)`` (model.py:64-69,107), in eval arithmetic whatever ``self.training`` is: no
+        buffer update, no host-RNG draw, no swap, no style mixing, truncation as ``StyleGenerator.forward`` applies it in eval.
+        ``identity_image`` [1,3,H,W]; ``pose_frames`` / ``emotion_frames`` [T,3,H,W] (None: the pose frames); ``noises``: the
+        explicit list ``StyleGenerator.forward`` takes, for T frames (default: drawn on the device).  ``Ei`` runs once; the
+        frames go through the encoder and decoder plans ``chunk`` at a time.  -> frames [T,3,R,R] fp32."""
+        if identity_image.dim() != 4 or identity_image.size(0) != 1 or identity_image.size(1) != 3:
+            raise ValueError(f"reenact: identity_image must be [1,3,H,W], got {tuple(identity_image.shape)}")
+        if pose_frames.dim() != 4 or pose_frames.size(1) != 3 or pose_frames.size(0) < 1:
+            raise ValueError(f"reenact: pose_frames must be [T,3,H,W], got {tuple(pose_frames.shape)}")
+        if emotion_frames is None:
+            emotion_frames = pose_frames
+        if tuple(emotion_frames.shape) != tuple(pose_frames.shape):
+            raise ValueError(f"reenact: emotion_frames must match pose_frames {tuple(pose_frames.shape)}, got {tuple(emotion_frames.shape)}")
+        T, chunk = pose_frames.size(0), int(chunk)
+        if chunk < 1:
+            raise ValueError("reenact: chunk must be >= 1")
+        if noises is not None and any(n.size(0) != T for n in noises):
+            raise ValueError(f"reenact: every noise tensor must carry {T} frames")
+        fi = self.encode(identity_image, "Ei")
+        out = []
+        for t0 in range(0, T, chunk):
+            t1 = min(T, t0 + chunk)
+            fe, fp = self.encode(emotion_frames[t0:t1], "Ee"), self.encode(pose_frames[t0:t1], "Ep")
+            gin = self._prepare_generator_input(fi.expand(t1 - t0, -1, -1, -1), fe, fp)
+            out.append(self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises]))
+        return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+    def _decode_eval(self, gin, noises):
+        """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan
+        does not serve runs its eval branch with every submodule's own ``training`` flag saved and put back."""
+        Gd = self.Gd
+        if hasattr(Gd, "plan_serves") and Gd.plan_serves(gin):
+            return Gd.plan_forward(gin, noises)
+        flags = [(mod, mod.training) for mod in Gd.modules()]
+        try:
+            for mod, _ in flags:
+                mod.training = False
+            return Gd(gin, noises)
+        finally:
+            for mod, was in flags:
+                mod.training = was
 
     def forward(self, x_s, x_t, swap_type=None, noises_s=None, noises_t=None):
         """-> (x_s_recon, x_t_recon, fi_s, fe_s, fp_s, fi_t, fe_t, fp_t, emotion_pred_s, emotion_pred_t).

@@ -36,13 +36,14 @@ _KIND_FLAGS = L.CONV_WINOGRAD | L.CONV_BF16X3 | L.CONV_TRANSPOSE4X4_S2 | L.CONV_
 def conv_desc(x, w_packed, Cout, k=3, stride=1, *, flags=0, out=None, hw=None, bias=None, noise_w=None, noise=None, style=None,
               style_stride=None, upsample=False, up_fir=False, lrelu_slope=None, out_scale=1.0, in_affine=None, batch_scale=None,
               demod=None, act_gain=1.0, stats=None, out_pre=None, accumulate=False, accum_half=None, out_scale_dev=None, config=-1,
-              ksplit=0, groups=1, shared_input=False, rgb_w=None, rgb_bias=None, rgb_out=None):
+              ksplit=0, groups=1, shared_input=False, rgb_w=None, rgb_bias=None, rgb_out=None, residual=None):
     """-> (``L.Conv2dDesc``, split-K workspace bytes): the one place a ``spk_conv2d_desc`` is assembled.
 
     ``flags``: the kernel family -- 0 (the direct MFMA kernel), ``SPK_CONV_WINOGRAD``, ``SPK_CONV_BF16X3``,
     ``SPK_CONV_TRANSPOSE4X4_S2`` or ``SPK_CONV_DGRAD_S2``; the epilogue and staging flags follow from the arguments (see
     ``conv2d_fused``).  x is [B, groups*Cin (``shared_input``: Cin), Hin, Win]; the output size is the conv's own, twice the
     input's (``upsample``), or ``hw``.  ``config`` < 0 on the direct kernel: the library's pick (+4 for a modulated conv).
+    ``residual`` ([B, groups*Cout, H, W], a stride-1 1x1 conv only) joins before the activation (``SPK_EPI_RESIDUAL``).
     ``out`` may be None (a plan patches y).  The workspace fields stay empty: an eager launch takes ``_workspace``, a plan
     one buffer of its own; the byte count is < 0 where the Winograd kernel does not serve the shape."""
     B, Cin, Hs, Ws = x.shape
@@ -65,6 +66,8 @@ def conv_desc(x, w_packed, Cout, k=3, stride=1, *, flags=0, out=None, hw=None, b
         raise L.SpkError("conv2d: batch_scale must be [B,Cin] and excludes in_affine")
     if demod is not None and (batch_scale is None or tuple(demod.shape) != (B, Cout)):
         raise L.SpkError("conv2d: demod must be [B,Cout] and goes with batch_scale")
+    if residual is not None and (tuple(residual.shape) != (B, G * Cout, H, W) or k != 1 or stride != 1):
+        raise L.SpkError(f"conv2d: residual must be {(B, G * Cout, H, W)} and goes with a stride-1 1x1 conv")
     slots = 0
     if stats is not None:
         slots = stats.numel() // (2 * G * Cout)
@@ -78,7 +81,7 @@ def conv_desc(x, w_packed, Cout, k=3, stride=1, *, flags=0, out=None, hw=None, b
               | (L.CONV_UPSAMPLE2X | (L.CONV_UP_FIR1331 if up_fir else 0) if upsample else 0) | (L.EPI_ACCUM if accumulate else 0)
               | (L.CONV_IN_AFFINE_RELU if in_affine is not None else 0) | (L.EPI_ACCUM_HALF if accum_half is not None else 0)
               | (L.CONV_IN_BATCH_SCALE if batch_scale is not None else 0) | (L.EPI_STATS if stats is not None else 0)
-              | (L.EPI_TORGB if rgb_w is not None else 0))
+              | (L.EPI_TORGB if rgb_w is not None else 0) | (L.EPI_RESIDUAL if residual is not None else 0))
     kind = flags & _KIND_FLAGS
     if kind & (L.CONV_BF16X3 | L.CONV_TRANSPOSE4X4_S2):
         ksplit = 1                       # (kernels without a split contraction)
@@ -107,7 +110,7 @@ def conv_desc(x, w_packed, Cout, k=3, stride=1, *, flags=0, out=None, hw=None, b
                      group_in_stride=0 if (shared_input or G == 1) else Cin, stats_slots=slots,
                      accum_half=L.dptr(accum_half, "accum_half"), out_scale_dev=L.dptr(out_scale_dev, "out_scale_dev"),
                      rgb_w=L.dptr(rgb_w, "rgb weight"), rgb_bias=L.dptr(rgb_bias, "rgb bias"), rgb_y=L.dptr(rgb_out, "rgb_out"),
-                     rgb_channels=3 if rgb_w is not None else 0)
+                     rgb_channels=3 if rgb_w is not None else 0, residual=L.dptr(residual, "residual"))
     return d, ws_bytes
 
 

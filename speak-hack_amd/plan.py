@@ -457,3 +457,122 @@ class StyleGAN2Plan(LaunchPlan):
         self.torgb.y = y.data_ptr()
         self.launch(kind_mask)
         return y
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def fold_conv_bn(weight, gamma, beta, running_mean, running_var, eps):
+    """Eval-mode BatchNorm folded into the conv that feeds it: ``bn(conv(x, w)) == conv(x, w') + b'`` with
+    ``s = gamma * rsqrt(running_var + eps)``, ``w' = w * s[co]``, ``b' = beta - running_mean * s``.  Pure torch in the
+    tensors' own dtype and device (CPU tensors too) -> (w', b')."""
+    s = gamma * torch.rsqrt(running_var + eps)
+    return weight * s.view(-1, 1, 1, 1), beta - running_mean * s
+
+
+class EncoderPlan(LaunchPlan):
+    """One ``ResNet50Trunk`` (model.py:60-62) at one (B, H, W, device) in the reference's EVAL arithmetic -- running
+    statistics in every BatchNorm, no buffer updated -- as one launch list of 55 ops.  In eval a BatchNorm is a constant
+    per-channel affine, so it is folded into the weights and a bias (``fold_conv_bn``; the module's own parameters are left
+    alone) and every activation is materialised post-ReLU: a plain input for every conv, hence Winograd for the 3x3 stride-1
+    ones where ``ops.conv3x3_route`` picks it.  Stem 7x7 s2 (bias + ReLU) -> max-pool -> per Bottleneck conv1 1x1 (bias +
+    ReLU), conv2 3x3 (bias + ReLU), downsample 1x1 (bias) on the first block of a layer, conv3 1x1 with
+    ``relu(. + bias + identity)`` in its epilogue (``SPK_EPI_RESIDUAL``) -> global average pool.  The plan owns the folded,
+    packed weights (re-derived when a conv weight, a BatchNorm parameter or a running statistic changes) and its activation
+    buffers; a call allocates the returned features only."""
+
+    def __init__(self, trunk, B, H, W, device):
+        super().__init__(device)
+        self.trunk, self.B, self.H, self.W = trunk, B, H, W
+        size = ops.conv_out_size
+        (conv0, bn0), blocks = trunk.conv_bn_pairs()
+        # ---- shapes first: five buffers by role, each as large as its largest user ----
+        H1, W1 = size(H, 7, 2), size(W, 7, 2)
+        Hp, Wp = (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1
+        need = {"stem": B * conv0.out_channels * H1 * W1, "io": B * conv0.out_channels * Hp * Wp, "t1": 0, "t2": 0, "down": 0}
+        h, w = Hp, Wp
+        for (c1, _), (c2, _), (c3, _), down in blocks:
+            s = c2.stride[0]
+            ho, wo = size(h, 3, s), size(w, 3, s)
+            need["t1"] = max(need["t1"], B * c1.out_channels * h * w)
+            need["t2"] = max(need["t2"], B * c2.out_channels * ho * wo)
+            need["io"] = max(need["io"], B * c3.out_channels * ho * wo)
+            if down is not None:
+                need["down"] = max(need["down"], B * c3.out_channels * ho * wo)
+            h, w = ho, wo
+        stem_buf, t1_buf, t2_buf, down_buf = (self.buf(need[k]) for k in ("stem", "t1", "t2", "down"))
+        pp = [self.buf(need["io"]) for _ in range(2)]          # block inputs / outputs ping-pong (the input is the residual)
+
+        def view(buf, Cc, hh, ww):
+            return buf[:B * Cc * hh * ww].view(B, Cc, hh, ww)
+
+        # ---- ops ----
+        x0 = torch.empty((B, 3, H, W), device=device, dtype=torch.float32)   # shape carrier; the input pointer is patched per call
+        y = view(stem_buf, conv0.out_channels, H1, W1)
+        self.stem = self.folded_conv(x0, conv0, bn0, y, relu=True)
+        cur = view(pp[0], conv0.out_channels, Hp, Wp)
+        self.add(L.OP_MAXPOOL3X3S2, L.MaxPool3x3s2Args(x=y.data_ptr(), in_scale=None, in_shift=None, y=cur.data_ptr(), B=B,
+                                                        C=conv0.out_channels, Hin=H1, Win=W1))
+        side = 0
+        for (c1, b1), (c2, b2), (c3, b3), down in blocks:
+            h, w = cur.shape[2:]
+            s = c2.stride[0]
+            ho, wo = size(h, 3, s), size(w, 3, s)
+            t1 = view(t1_buf, c1.out_channels, h, w)
+            self.folded_conv(cur, c1, b1, t1, relu=True)
+            t2 = view(t2_buf, c2.out_channels, ho, wo)
+            self.folded_conv(t1, c2, b2, t2, relu=True)
+            identity = cur
+            if down is not None:
+                identity = view(down_buf, c3.out_channels, ho, wo)
+                self.folded_conv(cur, down[0], down[1], identity, relu=False)
+            out = view(pp[1 - side], c3.out_channels, ho, wo)
+            self.folded_conv(t2, c3, b3, out, relu=True, residual=identity)
+            cur, side = out, 1 - side
+        self.feat_shape = (B, cur.shape[1], 1, 1)
+        self.avg = self.add(L.OP_GLOBAL_AVGPOOL, L.GlobalAvgPoolArgs(x=cur.data_ptr(), y=None, planes=B * cur.shape[1],
+                                                                     HW=cur.shape[2] * cur.shape[3]))
+        self.finish(trunk)
+
+    def folded_conv(self, x, conv, bn, out, *, relu, residual=None):
+        """One conv launch on BatchNorm-folded weights: ``out = [relu](conv(x, w') + b' [+ residual])``."""
+        B, Cin, Hs, Ws = x.shape
+        Cout, k, stride = conv.out_channels, conv.kernel_size[0], conv.stride[0]
+        H, W = out.shape[2:]
+        if k == 3 and stride == 1:
+            kind, cfg = ops.conv3x3_route(B, Cin, Cout, H, W, precision="f32")
+        else:
+            kind, cfg = "direct", ops.conv2d_pick_config(k, stride, B, Cin, Cout, H, W)
+        key = cfg if kind == "direct" else kind
+        n = L.lib().spk_conv2d_packed_bytes_wino(Cin, Cout) // 4 if kind == "wino" else L.lib().spk_conv2d_packed_floats(cfg, k, k, Cin, Cout)
+        if n <= 0:
+            raise L.SpkError(f"EncoderPlan: config {cfg} packs no {k}x{k} kernel of {Cin} -> {Cout} channels")
+        packed, bias = self.buf(n), self.buf(Cout)
+        tracked = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        if bn.num_batches_tracked is not None:
+            # a training forward of the trunk writes the running statistics from inside a kernel (no version bump); its
+            # counter update is a torch op, so the counter's version tells
+            tracked.append(bn.num_batches_tracked)
+
+        def refresh(conv=conv, bn=bn, packed=packed, bias=bias, key=key):
+            wf, bf = fold_conv_bn(conv.weight.detach(), bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
+            bias.copy_(bf)
+            ops.pack_image(wf.contiguous(), key, out=packed)
+
+        self._refreshers.append(refresh)
+        self.track(*tracked)
+        d, ws_bytes = ops.conv_desc(x, packed, Cout, k, stride, flags=L.CONV_WINOGRAD if kind == "wino" else 0, out=out, bias=bias,
+                                    lrelu_slope=0.0 if relu else None, residual=residual, config=cfg)
+        self._ws_bytes = max(self._ws_bytes, ws_bytes)
+        return self.add(L.OP_CONV2D, d)
+
+    def run(self, images, kind_mask=L.ALL_OPS):
+        """images [B,3,H,W] -> features [B,2048,1,1] (a fresh tensor)."""
+        if tuple(images.shape) != (self.B, 3, self.H, self.W):
+            raise ValueError(f"EncoderPlan: built for {(self.B, 3, self.H, self.W)}, got {tuple(images.shape)}")
+        self.refresh()
+        self.captured = self.captured or torch.cuda.is_current_stream_capturing()
+        images = images.contiguous()
+        self.stem.x = L.dptr(images, "images")
+        y = torch.empty(self.feat_shape, device=self.device, dtype=torch.float32)
+        self.avg.y = y.data_ptr()
+        self.launch(kind_mask)
+        return y

@@ -67,7 +67,7 @@ extern "C" {
                                   * spends 36 -- the algorithm the reference's own backend (MIOpen under PyTorch-ROCm) runs for an
                                   * fp32 3x3 nn.Conv2d (styleganv1.py:615-616,625,630,662-672).  Differs from the direct form in
                                   * summation order and the +-1 / 0.5 transforms only (1e-6-class rel-L2 per layer).  Plain input
-                                  * (no UPSAMPLE2X / IN_AFFINE_RELU / IN_BATCH_SCALE), ungrouped, H % 8 == 0, W % 32 == 0,
+                                  * or UPSAMPLE2X (bilinear, spk_conv2d_wino_up_supported; no IN_AFFINE_RELU), ungrouped, H % 8 == 0, W % 32 == 0,
                                   * Cin % 8 == 0; flags BIAS / NOISE / LRELU / STYLE / ACCUM, y_pre, out_scale(_dev).
                                   * w_packed from spk_conv2d_pack_weights_wino; config / ksplit ignored. */
 #define SPK_EPI_ACCUM_HALF 8192u     /* y += accum_half at the EVEN pixels: accum_half is [B, groups*Cout, ceil(H/2), ceil(W/2)], element
@@ -235,6 +235,10 @@ int spk_conv2d_pack_weights_wino(const float* w, float* w_packed, int Cin, int C
 int spk_conv2d_pack_weights_wino_list(const float* const* w, float* const* w_packed, const int* Cin, const int* Cout, const int* transpose_flip,
                                       int n, void* stream);
 int spk_conv2d_wino_supported(int B, int Cin, int Cout, int H, int W);
+/* ... | SPK_CONV_UPSAMPLE2X: conv3x3(bilinear_x2(x)) with the interpolation inside the kernel's input transform -- x is the
+ * low-resolution tensor [B, Cin, H/2, W/2] (Hin = H/2, Win = W/2), no x2 image exists.  Plain launches only: not with
+ * SPK_CONV_IN_BATCH_SCALE, SPK_CONV_UP_FIR1331 or groups > 1.  Whether the OUTPUT shape H x W is served: */
+int spk_conv2d_wino_up_supported(int B, int Cin, int Cout, int H, int W);
 /* Regions are 32 x 8 output pixels, or 16 x 16 where the image is narrower than 32.  A problem with too few (region, channel tile)
  * pairs to fill the CUs runs its channel contraction in `ksplit` slices: spk_conv2d_wino_ksplit(want, ...) = the count the launch
  * will use for desc->ksplit = want (0 = automatic; 1 = no split), ..._workspace_bytes the partial-sum workspace it then needs in

@@ -194,8 +194,9 @@ class FusedConvFn(torch.autograd.Function):
         a = torch.empty((B, Cout, H, W), device=x.device, dtype=torch.float32) if keep else None
         pw = getattr(weight, "_spk_gate_of", weight)      # (behind a WeightGateFn: the parameter itself keys the packed images)
         route = ops.conv3x3_route(B, Cin, Cout, H, W)
-        # a x2 layer on Winograd reads the materialised x2 image -- made here, so that the Winograd weight gradient can keep it
-        x2 = ops.upsample2x_bilinear(x) if upsample and route[0] == "wino" else None
+        # training: a x2 layer on Winograd reads the materialised x2 image -- made here, so that the Winograd weight gradient can
+        # keep it.  Nothing to keep (inference, launch by launch): ops.conv3x3 decides as the plans do (ops.wino_fuse_x2)
+        x2 = ops.upsample2x_bilinear(x) if upsample and route[0] == "wino" and keep else None
         y = ops.conv3x3(x if x2 is None else x2, packed.images(pw), Cout, route, upsample=upsample and x2 is None, bias=bias,
                         noise_w=noise_w, noise=noise, style=style, lrelu_slope=slope, out_pre=a, out_scale=w_scale)
         if x2 is not None and keep and ops.use_wgrad_wino(B, Cin, Cout, H, W):

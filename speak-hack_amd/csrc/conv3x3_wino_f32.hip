@@ -26,6 +26,8 @@
 // LDS: 2 x 32 KB (U) + 2 x 32 KB (V) + 2 x 11 KB (raw) = 150 KB.  Vector instructions per chunk of 64 MFMAs: 64 adds.
 // Epilogue: output transform and the f32 kernel's epilogue element for element (out_scale, bias, noise, LeakyReLU, [y_pre], style,
 // [accumulate]) in registers; a lane stores its tile's 2 x 2 pixels as two 8-byte stores, 16 lanes a whole 128-byte line.
+// A bilinear x2 layer (SPK_CONV_UPSAMPLE2X, template parameter UP) reads the low-resolution tensor: B^T (bilinear) B collapses into one
+// 4 x 3 matrix per dimension (up1d_), 49 vector ops per plane on a 3 x 3 raw window; no x2 image exists.
 #include "conv_mfma_f32.hpp"
 
 namespace spkwino {
@@ -36,6 +38,7 @@ using spkconv::static_for;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) f32x2 lds_f32x2_t;
+typedef __attribute__((address_space(3))) f32x2 __attribute__((aligned(4))) lds_f32x2u_t;     // an 8-byte LDS access at any 4-byte address
 
 constexpr int CO_T = 64, CI_T = 8, NTILE = 64, NT = 256;
 // region shapes (64 tiles each): WIDE = 32 x 8 output pixels (16 x 4 tiles) -- whole 128-byte output lines; SQUARE = 16 x 16 (8 x 8 tiles)
@@ -54,6 +57,10 @@ constexpr int LDS_FLOATS = RGBW_OFF + 3 * CO_T;
 constexpr int LDS_BYTES = LDS_FLOATS * 4;                                    // 155 648
 constexpr int RGB_PART_OFF = V_OFF + V_FLOATS;                               // toRGB partial sums [4 channel groups][64 tiles][3][4 px]: V slot 1, idle during an epilogue
 static_assert(RAW_GATHERS == 11 && 34 * 10 <= RAW_PLANE && 18 * 18 <= RAW_PLANE, "geometry");
+// UP (a bilinear x2 layer, SPK_CONV_UPSAMPLE2X): the raw plane is the LOW-resolution window of the region with a one-pixel halo --
+// 18 x 6 (WIDE) / 10 x 10 (SQUARE) floats at a pitch of 128 inside the wave's 704: a wave's two planes = 4 gathers
+constexpr int UP_PLANE = 128, UP_GATHERS = 2 * UP_PLANE / 64;
+static_assert(18 * 6 <= UP_PLANE && 10 * 10 <= UP_PLANE && 2 * UP_PLANE <= RAW_WAVE, "geometry");
 constexpr int U_DMA = U_FLOATS * 4 / 1024 / 4;                               // 1 KB blocks per wave and chunk (8)
 
 struct Args {
@@ -166,6 +173,26 @@ __global__ void pack_wino_list_kernel(const PackWinoList a) {
 __device__ __forceinline__ float fadd_(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float fsub_(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
+// UP: the 1-D input transform of a tile of a bilinear x2 layer, from the tile's three LOW-resolution pixels.  The tile's 4-wide window
+// of the x2 image, times 4, is (3a + b, a + 3b, 3b + c, b + 3c) for raw neighbours a, b, c (align_corners=False: taps 1/4, 3/4; at an
+// image edge the missing neighbour is the edge pixel itself: the gather's business), and B^T of it
+//   o0 = 3a - 2b - c,  o1 = a + 6b + c,  o2 = c - a,  o3 = a + 2b - 3c
+// With e = c - a, s = a + c: o1 = 6b + s, o2 = e, o0 = (s - kL b) - 2e, o3 = -2e - (s - kR b), kL = kR = 2.  The conv's ZERO padding of
+// the x2 image -- window element 0 (3) of a tile in the image's first (last) tile column is 0, not the clamped interpolation -- is
+// kL = 6 (kR = 6): with a = b, o0 = (3 - kL) b - c = -3b - c.  7 vector ops for 3 -> 4 values; nkl / nkr hold -kL / -kR.  Two passes
+// (rows, columns) give 16 V: the factor is exact and leaves through out_scale.
+__device__ __forceinline__ void up1d_(float a, float b, float c, float nkl, float nkr, float six, float& o0, float& o1, float& o2, float& o3) {
+    float e, s, hl, hr;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(e) : "v"(c), "v"(a));
+    asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(a), "v"(c));
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(o1) : "v"(b), "s"(six), "v"(s));
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(hl) : "v"(b), "v"(nkl), "v"(s));
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(hr) : "v"(b), "v"(nkr), "v"(s));
+    asm("v_fma_f32 %0, %1, -2.0, %2" : "=v"(o0) : "v"(e), "v"(hl));
+    asm("v_fma_f32 %0, %1, -2.0, -%2" : "=v"(o3) : "v"(e), "v"(hr));
+    o2 = e;
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a fence: it waits for vmcnt(0) too, i.e. for every global
 // STORE the wave has issued -- behind the epilogue's stores that is a full HBM write latency (~5 000 cycles, measured with
 // tools/lab_wino_phases.py) with the matrix pipe idle, twice per region.
@@ -179,9 +206,14 @@ __device__ __forceinline__ void lds_barrier() {
 // RGB (SPK_EPI_TORGB): the layer's 64 output channels sit in ONE workgroup (Cout <= 64), so the 1x1 conv to 3 channels that follows the
 // last block (styleganv1.py:607) is a reduction over the epilogue's own registers: 12 fused multiply-adds per channel row, the four
 // channel groups (2 waves x 2 half-waves) meet through LDS.  The 134 MB activation is then neither re-read nor -- y == NULL -- written.
-template <bool MOD, int SHAPE, bool RGB = false>
+// UP (SPK_CONV_UPSAMPLE2X, plain launches): p.x is the LOW-resolution tensor [B, Cx, H/2, W/2]; everything that speaks of the output
+// keeps H, W.  Raw plane, gathers and input transform change (up1d_), nothing behind V does.
+template <bool MOD, int SHAPE, bool RGB = false, bool UP = false>
 __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
-    constexpr int RW = region_w(SHAPE), RH = region_h(SHAPE), TXN = RW / 2, RAW_W = RW + 2, RAW_H = RH + 2, RAW_USED = RAW_W * RAW_H;
+    static_assert(!(UP && MOD), "the modulated conv keeps its x2 pass");
+    constexpr int RW = region_w(SHAPE), RH = region_h(SHAPE), TXN = RW / 2, TYN = RH / 2;
+    constexpr int RAW_W = UP ? RW / 2 + 2 : RW + 2, RAW_H = UP ? RH / 2 + 2 : RH + 2, RAW_USED = RAW_W * RAW_H;
+    constexpr int PLANE = UP ? UP_PLANE : RAW_PLANE, NG = UP ? UP_GATHERS : RAW_GATHERS;       // a raw plane's pitch; a wave's gathers per chunk
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -198,10 +230,12 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     const int reg_begin = xcd * share_q + min(xcd, share_r), reg_end = reg_begin + share_q + (xcd < share_r ? 1 : 0);
     const int grp = (int)blockIdx.y / p.co_tiles_g, co_tile = (int)blockIdx.y - grp * p.co_tiles_g, co0 = co_tile * CO_T;     // co0: within the group
     const size_t HW = (size_t)p.H * p.W;
+    const int Win = UP ? p.W >> 1 : p.W;                   // the input's row pitch / plane size
+    const size_t HWin = UP ? HW >> 2 : HW;
 
-    // ---- the raw gathers: byte offsets of this lane's 11 elements (plane j of channel wave + 4 j), or out of range ----
+    // ---- the raw gathers: byte offsets of this lane's 11 (UP: 4) elements (plane j of channel wave + 4 j), or out of range ----
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)p.x_bytes, 0x00020000);
-    unsigned voff[RAW_GATHERS], voff_next[RAW_GATHERS];   // the gathers of the region being requested / of the region after it
+    unsigned voff[NG], voff_next[NG];   // the gathers of the region being requested / of the region after it
     auto region_coords = [&](int item, int& b_, int& y0_, int& x0_, int& kb_) {
         const int reg = item / p.ksplit;
         kb_ = (item - reg * p.ksplit) * p.cps;               // first chunk of the item's slice
@@ -214,23 +248,36 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     // per lane and gather, once: the element's byte offset from the region's origin pixel in plane 0 of the image (wraps for the
     // halo's row -1 / column -1: the sum with the origin is in range whenever the element exists), and which image edges would
     // put it outside (bit 0: region at the top edge, 1: bottom, 2: left, 3: right, 4: the pitch's padding -- never loaded)
-    unsigned rel[RAW_GATHERS], edge[RAW_GATHERS];
+    unsigned rel[NG], edge[NG];
 #pragma unroll
-    for (int k = 0; k < RAW_GATHERS; ++k) {
+    for (int k = 0; k < NG; ++k) {
         const int e = k * 64 + lane;
-        const int j = e >= RAW_PLANE ? 1 : 0, q = e - j * RAW_PLANE;
+        const int j = e >= PLANE ? 1 : 0, q = e - j * PLANE;
         const int r = q / RAW_W, c = q - r * RAW_W;
-        rel[k] = ((unsigned)(wave + 4 * j) * (unsigned)HW + (unsigned)((r - 1) * p.W + (c - 1))) * 4u;
+        rel[k] = ((unsigned)(wave + 4 * j) * (unsigned)HWin + (unsigned)((r - 1) * Win + (c - 1))) * 4u;
         edge[k] = (r == 0 ? 1u : 0u) | (r == RAW_H - 1 ? 2u : 0u) | (c == 0 ? 4u : 0u) | (c == RAW_W - 1 ? 8u : 0u) | (q >= RAW_USED ? 16u : 0u);
     }
-    auto set_voff = [&](unsigned (&vo)[RAW_GATHERS], int b_, int y0_, int x0_) {
+    auto set_voff = [&](unsigned (&vo)[NG], int b_, int y0_, int x0_) {
         // (host: the whole tensor is below 2^29 floats)
-        const unsigned origin = (((unsigned)b_ * (unsigned)p.Cx + (unsigned)(grp * p.gin)) * (unsigned)HW + (unsigned)(y0_ * p.W + x0_)) * 4u;
+        const unsigned origin = (((unsigned)b_ * (unsigned)p.Cx + (unsigned)(grp * p.gin)) * (unsigned)HWin +
+                                 (unsigned)(UP ? (y0_ >> 1) * Win + (x0_ >> 1) : y0_ * p.W + x0_)) * 4u;
         const unsigned at = (y0_ == 0 ? 1u : 0u) | (y0_ + RH >= p.H ? 2u : 0u) | (x0_ == 0 ? 4u : 0u) | (x0_ + RW >= p.W ? 8u : 0u) | 16u;
+        if constexpr (UP) {
+            // a halo element outside the image reads the CLAMPED neighbour (the bilinear pass's edge rule): one row / one column
+            // back inside -- always in range; the zero padding of the x2 image is the edge tiles' coefficient (set_nk)
+            const unsigned row_bytes = (unsigned)Win * 4u;
 #pragma unroll
-        for (int k = 0; k < RAW_GATHERS; ++k) vo[k] = (edge[k] & at) ? 0x80000000u : origin + rel[k];
+            for (int k = 0; k < NG; ++k) {
+                const unsigned h = edge[k] & at;
+                vo[k] = (h & 16u) ? 0x80000000u
+                                  : origin + rel[k] + ((h & 1u) ? row_bytes : 0u) - ((h & 2u) ? row_bytes : 0u) + ((h & 4u) ? 4u : 0u) - ((h & 8u) ? 4u : 0u);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NG; ++k) vo[k] = (edge[k] & at) ? 0x80000000u : origin + rel[k];
+        }
     };
-    const unsigned chunk_bytes = (unsigned)(CI_T * HW * 4);
+    const unsigned chunk_bytes = (unsigned)(CI_T * HWin * 4);
     const float* wsrc = p.wp + (size_t)blockIdx.y * p.n_chunks * U_FLOATS;
 
     // LDS-DMA as inline assembly: the compiler treats a pending `... lds` load as a flat access that may complete out of order
@@ -262,6 +309,26 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     int raw_rd = (RAW_OFF + wave * RAW_WAVE + 2 * ty_l * RAW_W + 2 * tx_l) >> 1;   // in float pairs; + slot * RAW_FLOATS + j * RAW_PLANE + r * 34 + {0, 2}
     int v_wr = V_OFF + wave * NTILE + lane;                         // + slot * V_FLOATS + (xi * 8 + 4 j) * 64
     asm volatile("" : "+v"(a_base), "+v"(b_base), "+v"(raw_rd), "+v"(v_wr));
+    // UP: a lane (tile ty_l, tx_l) reads rows ty_l .. ty_l + 2, columns tx_l .. tx_l + 2 of the haloed low-resolution plane: 4-byte
+    // aligned only (ds_read2_b32 + ds_read_b32, whose offsets reach 1 KB: one base per raw slot and plane)
+    int raw_u[2][2];
+    float nk[4] = {-2.f, -2.f, -2.f, -2.f}, nkn[4] = {-2.f, -2.f, -2.f, -2.f};             // -kT, -kB, -kL, -kR of this lane's tile in the item whose planes are being transformed / in the next item
+    const float six = 6.f;
+    auto set_nk = [&](float (&k_)[4], int y0_, int x0_) {
+        k_[0] = (y0_ == 0 && ty_l == 0) ? -6.f : -2.f;
+        k_[1] = (y0_ + RH >= p.H && ty_l == TYN - 1) ? -6.f : -2.f;
+        k_[2] = (x0_ == 0 && tx_l == 0) ? -6.f : -2.f;
+        k_[3] = (x0_ + RW >= p.W && tx_l == TXN - 1) ? -6.f : -2.f;
+    };
+    if constexpr (UP) {
+#pragma unroll
+        for (int rs = 0; rs < 2; ++rs)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                raw_u[rs][j] = RAW_OFF + wave * RAW_WAVE + ty_l * RAW_W + tx_l + rs * RAW_FLOATS + j * PLANE;
+                asm volatile("" : "+v"(raw_u[rs][j]));
+            }
+    }
 
     f32x16 acc[16];
     f32x16 zero16;
@@ -290,6 +357,19 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
         tv[j_][4 * (i_)] = fsub_(tq[j_][4 * (i_)], tq[j_][4 * (i_) + 2]); tv[j_][4 * (i_) + 1] = fadd_(tq[j_][4 * (i_) + 1], tq[j_][4 * (i_) + 2]); \
         tv[j_][4 * (i_) + 2] = fsub_(tq[j_][4 * (i_) + 2], tq[j_][4 * (i_) + 1]); tv[j_][4 * (i_) + 3] = fsub_(tq[j_][4 * (i_) + 1], tq[j_][4 * (i_) + 3]); \
     }
+    // UP: three raw rows of three; the 1-D transform along each raw row (tq: 3 x 4), then along each of the 4 columns (tv: 4 x 4)
+#define WINO_U_READ(rs_, j_, r_)                                                                                        \
+    {                                                                                                                   \
+        const volatile lds_f32_t* q_ = (const volatile lds_f32_t*)0 + (raw_u[rs_][j_] + (r_) * RAW_W);                  \
+        const f32x2 lo_ = *reinterpret_cast<const volatile lds_f32x2u_t*>(q_);                                          \
+        d[j_][3 * (r_) + 0] = lo_.x; d[j_][3 * (r_) + 1] = lo_.y; d[j_][3 * (r_) + 2] = q_[2];                          \
+    }
+#define WINO_U_H(j_, r_, nk_)                                                                                           \
+    up1d_(d[j_][3 * (r_)], d[j_][3 * (r_) + 1], d[j_][3 * (r_) + 2], (nk_)[2], (nk_)[3], six,                           \
+          tq[j_][4 * (r_)], tq[j_][4 * (r_) + 1], tq[j_][4 * (r_) + 2], tq[j_][4 * (r_) + 3]);
+#define WINO_U_V(j_, c_, nk_)                                                                                           \
+    up1d_(tq[j_][c_], tq[j_][4 + (c_)], tq[j_][8 + (c_)], (nk_)[0], (nk_)[1], six,                                      \
+          tv[j_][c_], tv[j_][4 + (c_)], tv[j_][8 + (c_)], tv[j_][12 + (c_)]);
 #define WINO_T_WRITE(vs_, j_, xi_)                                                                                      \
     *((volatile lds_f32_t*)0 + (v_wr + ((vs_) * V_FLOATS + ((xi_) * CI_T + 4 * (j_)) * NTILE))) = tv[j_][xi_];
 
@@ -304,15 +384,22 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     b_cur = b;
     kb_cur = kb;
     set_voff(voff, b, y0, x0);
+    if constexpr (UP) set_nk(nk, y0, x0);
     // ---- first region: U_0, raw_0, raw_1 requested; raw_0 -> V_0 ----
     static_for<0, U_DMA>([&](auto k) { WINO_DMA_U(kb, 0, decltype(k)::value); });
-    static_for<0, RAW_GATHERS>([&](auto k) { WINO_DMA_RAW(voff[decltype(k)::value], kb, 0, decltype(k)::value); });
-    static_for<0, RAW_GATHERS>([&](auto k) { WINO_DMA_RAW(voff[decltype(k)::value], kb + 1, 1, decltype(k)::value); });
+    static_for<0, NG>([&](auto k) { WINO_DMA_RAW(voff[decltype(k)::value], kb, 0, decltype(k)::value); });
+    static_for<0, NG>([&](auto k) { WINO_DMA_RAW(voff[decltype(k)::value], kb + 1, 1, decltype(k)::value); });
     __builtin_amdgcn_s_waitcnt(0x0f70);              // vmcnt(0): this wave's DMA has landed (its raw planes are its own)
     static_for<0, 2>([&](auto j) {
-        static_for<0, 4>([&](auto r) { WINO_T_READ(0, decltype(j)::value, decltype(r)::value); });
-        static_for<0, 4>([&](auto c) { WINO_T_ROWS(decltype(j)::value, decltype(c)::value); });
-        static_for<0, 4>([&](auto i) { WINO_T_COLS(decltype(j)::value, decltype(i)::value); });
+        if constexpr (UP) {
+            static_for<0, 3>([&](auto r) { WINO_U_READ(0, decltype(j)::value, decltype(r)::value); });
+            static_for<0, 3>([&](auto r) { WINO_U_H(decltype(j)::value, decltype(r)::value, nk); });
+            static_for<0, 4>([&](auto c) { WINO_U_V(decltype(j)::value, decltype(c)::value, nk); });
+        } else {
+            static_for<0, 4>([&](auto r) { WINO_T_READ(0, decltype(j)::value, decltype(r)::value); });
+            static_for<0, 4>([&](auto c) { WINO_T_ROWS(decltype(j)::value, decltype(c)::value); });
+            static_for<0, 4>([&](auto i) { WINO_T_COLS(decltype(j)::value, decltype(i)::value); });
+        }
         if constexpr (MOD) {
             const float sc0_ = p.in_scale[(size_t)b * p.Cin + kb * CI_T + wave + 4 * decltype(j)::value];
             static_for<0, 4>([&](auto i) { WINO_T_SCALE(decltype(j)::value, decltype(i)::value, sc0_); });
@@ -337,7 +424,8 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
         fa[reg_] = *((const volatile lds_f32_t*)0 + (a_base + ((slot_) * U_FLOATS + (xi_ * CI_T + 2 * kk_) * CO_T)));   \
         fb[reg_] = *((const volatile lds_f32_t*)0 + (b_base + ((slot_) * V_FLOATS + (xi_ * CI_T + 2 * kk_) * NTILE)));  \
     }
-    auto chunk_body = [&](auto slot_c, auto first_c, const int i) __attribute__((always_inline)) {
+    // nk_: UP -- the edge coefficients of the item the planes of chunk c1 belong to
+    auto chunk_body = [&](auto slot_c, auto first_c, const int i, const float (&nk_)[4]) __attribute__((always_inline)) {
         constexpr int S = decltype(slot_c)::value, O = 1 - S;     // this chunk's slot; the other one receives the next chunk
         constexpr bool FIRST = decltype(first_c)::value;          // a region's first chunk: its first 16 MFMAs START the accumulators (C = 0)
         const int c1 = i + 1 < n ? kb_cur + i + 1 : kb;           // the stream's next chunk (weights: the same channel tile; past n: the next item's first)
@@ -357,13 +445,19 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
             // requests: the next chunk's weights into the other U slot, the raw planes of the chunk after it into THIS raw
             // slot (its planes became this chunk's V one chunk ago)
             if constexpr (s < U_DMA) { WINO_DMA_U(c1, O, s); }
-            else if constexpr (s < U_DMA + RAW_GATHERS) { WINO_DMA_RAW(voff[s - U_DMA], c2, S, s - U_DMA); }
+            else if constexpr (s < U_DMA + NG) { WINO_DMA_RAW(voff[s - U_DMA], c2, S, s - U_DMA); }
             // raw slot O -> V slot O.  plane 0: reads behind MFMAs 2-5, adds 8-15, writes 16-23; plane 1: 12-15, 24-31, 32-39
             static_for<0, 2>([&](auto j_c) {
                 constexpr int j = decltype(j_c)::value, tr = 2 + 10 * j, ta = 8 + 16 * j;
+                if constexpr (UP) {           // (the same slots: 3 reads, 3 + 4 times the 7 ops of up1d_, one call behind one MFMA)
+                    if constexpr (s >= tr && s < tr + 3) { WINO_U_READ(O, j, s - tr); }
+                    if constexpr (s >= ta && s < ta + 3) { WINO_U_H(j, s - ta, nk_); }
+                    if constexpr (s >= ta + 4 && s < ta + 8) { WINO_U_V(j, s - ta - 4, nk_); }
+                } else {
                 if constexpr (s >= tr && s < tr + 4) { WINO_T_READ(O, j, s - tr); }
                 if constexpr (s >= ta && s < ta + 4) { WINO_T_ROWS(j, s - ta); }
                 if constexpr (s >= ta + 4 && s < ta + 8) { WINO_T_COLS(j, s - ta - 4); if constexpr (MOD) { WINO_T_SCALE(j, s - ta - 4, msc[j]); } }
+                }
                 if constexpr (s >= ta + 8 && s < ta + 16) { WINO_T_WRITE(O, j, 2 * (s - ta - 8)); WINO_T_WRITE(O, j, 2 * (s - ta - 8) + 1); }
             });
             __builtin_amdgcn_sched_barrier(0);
@@ -429,6 +523,10 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
             region_coords(reg, b, y0, x0, kb);
         }
         set_voff(voff_next, b, y0, x0);
+        if constexpr (UP) {              // (this item's coefficients from its own coordinates; the next item's beside its offsets)
+            set_nk(nk, cur_y0, cur_x0);
+            set_nk(nkn, y0, x0);
+        }
 
         // (host: n is even.)  From the last pair of chunks on, every raw request belongs to the next region: its offsets move in,
         // once, by selects (no branch in the body).
@@ -439,9 +537,16 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
         for (int i = 0; i < n; i += 2) {
             const bool last_pair = i + 2 >= n;
 #pragma unroll
-            for (int k = 0; k < RAW_GATHERS; ++k) voff[k] = last_pair ? voff_next[k] : voff[k];
-            chunk_body(std::integral_constant<int, 0>{}, F_{}, i);
-            chunk_body(std::integral_constant<int, 1>{}, F_{}, i + 1);
+            for (int k = 0; k < NG; ++k) voff[k] = last_pair ? voff_next[k] : voff[k];
+            chunk_body(std::integral_constant<int, 0>{}, F_{}, i, nk);
+            if constexpr (UP) {          // a region's last chunk transforms the first planes of the NEXT item
+                float nk2[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) nk2[k] = last_pair ? nkn[k] : nk[k];
+                chunk_body(std::integral_constant<int, 1>{}, F_{}, i + 1, nk2);
+            } else {
+                chunk_body(std::integral_constant<int, 1>{}, F_{}, i + 1, nk);
+            }
         }
 
         // ---- epilogue, in registers: output transform Y = A^T M A (A^T = [1,1,1,0; 0,1,-1,-1]) of one channel row at a time, then the
@@ -556,6 +661,9 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     }
 #undef WINO_FRAG
 #undef WINO_T_WRITE
+#undef WINO_U_V
+#undef WINO_U_H
+#undef WINO_U_READ
 #undef WINO_T_COLS
 #undef WINO_T_SCALE
 #undef WINO_T_ROWS
@@ -606,11 +714,23 @@ int spk_conv2d_pack_weights_wino_list(const float* const* w, float* const* w_pac
     return spk::check_launch("pack_wino_list_kernel");
 }
 
-int spk_conv2d_wino_supported(int B, int Cin, int Cout, int H, int W) {
+static int wino_geometry_ok(int B, int Cin, int Cout, int H, int W) {        // everything but the size of the tensor the gathers read
     if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
     if (wino_shape(H, W) < 0) return 0;     // whole 32 x 8 or 16 x 16 pixel regions
     if (Cin % (2 * CI_T)) return 0; // whole chunks (the gathers of a ragged last chunk would reach past the tensor), an even number of them
+    return 1;
+}
+
+int spk_conv2d_wino_supported(int B, int Cin, int Cout, int H, int W) {
+    if (!wino_geometry_ok(B, Cin, Cout, H, W)) return 0;
     if ((long long)B * Cin * H * W * 4 >= (1ll << 31)) return 0;          // 32-bit buffer offsets, bit 31 = "out of range"
+    return 1;
+}
+
+// SPK_CONV_WINOGRAD | SPK_CONV_UPSAMPLE2X: OUTPUT shape H x W of conv3x3(bilinear_x2(x)), x = [B, Cin, H/2, W/2]
+int spk_conv2d_wino_up_supported(int B, int Cin, int Cout, int H, int W) {
+    if (!wino_geometry_ok(B, Cin, Cout, H, W) || (H & 1) || (W & 1)) return 0;
+    if ((long long)B * Cin * (H / 2) * (W / 2) * 4 >= (1ll << 31)) return 0;      // the 2 GB limit is the INPUT tensor's: the gathers read it
     return 1;
 }
 
@@ -619,7 +739,7 @@ int spk_conv2d_wino_supported(int B, int Cin, int Cout, int H, int W) {
 // many if the chunk count allows.  1 = no split.  A split launch writes partial sums [ksplit][B][Cout][H][W] into the workspace and
 // the direct kernels' split-K finisher applies the epilogue.
 int spk_conv2d_wino_ksplit(int want, int B, int Cin, int Cout, int H, int W) {
-    if (!spk_conv2d_wino_supported(B, Cin, Cout, H, W)) return -1;
+    if (!wino_geometry_ok(B, Cin, Cout, H, W)) return -1;      // (the byte limit is the launch's: it knows which tensor the gathers read)
     const int shape = wino_shape(H, W), n_chunks = Cin / CI_T;
     const long long pairs = (long long)B * (H / region_h(shape)) * (W / region_w(shape)) * spk::ceil_div(Cout, CO_T);
     auto ok = [&](int ks) { return ks >= 1 && n_chunks % (2 * ks) == 0 && n_chunks / ks >= 4; };
@@ -644,14 +764,18 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     SPK_REQUIRE(d && d->x && d->w_packed, "conv2d winograd: null pointer");
     SPK_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 1, "conv2d winograd: 3x3 stride-1 kernels only");
     const int G = d->groups > 1 ? d->groups : 1;
+    const bool up = d->flags & SPK_CONV_UPSAMPLE2X;
+    SPK_REQUIRE(!up || (G == 1 && !(d->flags & (SPK_CONV_IN_BATCH_SCALE | SPK_CONV_UP_FIR1331))),
+                "conv2d winograd: SPK_CONV_UPSAMPLE2X is the bilinear x2 of a plain launch (no IN_BATCH_SCALE, no UP_FIR1331, no groups): "
+                "pass the x2 image (spk_upsample2x_fwd)");
     SPK_REQUIRE(G == 1 || !(d->flags & ~(SPK_CONV_WINOGRAD | SPK_EPI_ACCUM)), "conv2d winograd: a grouped launch takes SPK_EPI_ACCUM only (the encoders' "
                 "data gradients)");
     const int gin = G > 1 ? d->group_in_stride : d->Cin, Cx = gin * (G - 1) + d->Cin, Cy = G * d->Cout;
     SPK_REQUIRE(G == 1 || gin >= d->Cin, "conv2d winograd: groups read disjoint channels");
     const unsigned epi = SPK_EPI_BIAS | SPK_EPI_NOISE | SPK_EPI_LRELU | SPK_EPI_STYLE | SPK_EPI_ACCUM;
-    const unsigned allowed = SPK_CONV_WINOGRAD | epi | SPK_CONV_IN_BATCH_SCALE | SPK_EPI_TORGB;
+    const unsigned allowed = SPK_CONV_WINOGRAD | epi | SPK_CONV_IN_BATCH_SCALE | SPK_EPI_TORGB | SPK_CONV_UPSAMPLE2X;
     SPK_REQUIRE(!(d->flags & ~allowed) && !d->stats && !d->accum_half,
-                "conv2d winograd: plain or batch-scaled input; epilogue flags bias, noise, lrelu, style, accum, torgb");
+                "conv2d winograd: plain, bilinear x2 or batch-scaled input; epilogue flags bias, noise, lrelu, style, accum, torgb");
     const bool mod = d->flags & SPK_CONV_IN_BATCH_SCALE, rgb = d->flags & SPK_EPI_TORGB;
     SPK_REQUIRE(d->y || rgb, "conv2d winograd: null pointer");
     if (rgb)
@@ -660,8 +784,12 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
                     "conv2d winograd: SPK_EPI_TORGB needs rgb_w [3][Cout], rgb_y [B,3,H,W], Cout <= 64 (one channel tile), no y_pre / accumulate / modulation");
     SPK_REQUIRE(!mod || d->in_scale, "conv2d winograd: IN_BATCH_SCALE without in_scale[B,Cin]");
     SPK_REQUIRE(!d->out_scale_bc || mod, "conv2d winograd: out_scale_bc (demodulation) goes with SPK_CONV_IN_BATCH_SCALE");
-    SPK_REQUIRE(d->H == d->Hin && d->W == d->Win, "conv2d winograd: output size must equal the input size");
-    SPK_REQUIRE(spk_conv2d_wino_supported(d->B, d->Cin, d->Cout, d->H, d->W) && (long long)d->B * Cx * d->H * d->W * 4 < (1ll << 31),
+    if (up)
+        SPK_REQUIRE(d->H == 2 * d->Hin && d->W == 2 * d->Win && spk_conv2d_wino_up_supported(d->B, d->Cin, d->Cout, d->H, d->W),
+                    "conv2d winograd: SPK_CONV_UPSAMPLE2X needs an output of twice the input size, %dx%d -> %dx%d", d->Hin, d->Win, d->H, d->W);
+    else
+        SPK_REQUIRE(d->H == d->Hin && d->W == d->Win, "conv2d winograd: output size must equal the input size");
+    SPK_REQUIRE(wino_geometry_ok(d->B, d->Cin, d->Cout, d->H, d->W) && (long long)d->B * Cx * d->Hin * d->Win * 4 < (1ll << 31),
                 "conv2d winograd: %dx%d is not a whole number of 32 x 8 or 16 x 16 regions (or the input exceeds 2 GB)", d->H, d->W);
     SPK_REQUIRE(!(d->flags & SPK_EPI_BIAS) || d->bias, "conv2d winograd: SPK_EPI_BIAS without bias");
     SPK_REQUIRE(!(d->flags & SPK_EPI_NOISE) || (d->noise && d->noise_w), "conv2d winograd: SPK_EPI_NOISE without noise");
@@ -687,8 +815,9 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     a.n_chunks = spk::ceil_div(d->Cin, CI_T);
     a.ksplit = ks; a.cps = a.n_chunks / ks; a.slice_floats = 0;
     a.style_stride = d->style_stride; a.flags = d->flags;
-    a.x_bytes = (unsigned)((long long)d->B * Cx * d->H * d->W * 4);
-    a.slope = d->lrelu_slope; a.out_scale = d->out_scale; a.act_gain = d->act_gain != 0.f ? d->act_gain : 1.f;
+    a.x_bytes = (unsigned)((long long)d->B * Cx * d->Hin * d->Win * 4);
+    const float up_scale = up ? 0.0625f : 1.f;      // UP: the input transform yields 16 V (up1d_)
+    a.slope = d->lrelu_slope; a.out_scale = d->out_scale * up_scale; a.act_gain = d->act_gain != 0.f ? d->act_gain : 1.f;
     SPK_REQUIRE(!rgb || ks == 1, "conv2d winograd: SPK_EPI_TORGB with a sliced contraction (%d slices): pass ksplit = 1 or run the 1x1 separately", ks);
     if (ks > 1) {       // partial sums, raw: the whole epilogue (and the demodulation) belongs to the finisher
         a.y = static_cast<float*>(d->workspace); a.y_pre = nullptr; a.out_scale_dev = nullptr; a.out_scale_bc = nullptr;
@@ -697,8 +826,11 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     void (*kern)(const Args) = mod ? (shape == SQUARE ? &wino_kernel<true, SQUARE> : &wino_kernel<true, WIDE>)
                                : rgb ? (shape == SQUARE ? &wino_kernel<false, SQUARE, true> : &wino_kernel<false, WIDE, true>)
                                      : (shape == SQUARE ? &wino_kernel<false, SQUARE> : &wino_kernel<false, WIDE>);
-    static bool raised[6] = {false, false, false, false, false, false};
-    const int which = (mod ? 2 : rgb ? 4 : 0) + (shape == SQUARE ? 1 : 0);
+    if (up)
+        kern = rgb ? (shape == SQUARE ? &wino_kernel<false, SQUARE, true, true> : &wino_kernel<false, WIDE, true, true>)
+                   : (shape == SQUARE ? &wino_kernel<false, SQUARE, false, true> : &wino_kernel<false, WIDE, false, true>);
+    static bool raised[10] = {false, false, false, false, false, false, false, false, false, false};
+    const int which = (mod ? 2 : rgb ? 4 : 0) + (shape == SQUARE ? 1 : 0) + (up ? (rgb ? 4 : 6) : 0);
     if (!raised[which]) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
@@ -727,7 +859,7 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     spkconv::ConvArgs f = {};
     f.bias = d->bias; f.noise_w = d->noise_w; f.noise = d->noise; f.style = d->style; f.out_scale_bc = d->out_scale_bc;
     f.y = d->y; f.y_pre = d->y_pre; f.B = d->B; f.Cin = d->Cin; f.Cout = d->Cout; f.Cy = Cy; f.Cx = Cx; f.G = G; f.H = d->H; f.W = d->W;
-    f.style_stride = d->style_stride; f.flags = d->flags & epi; f.slope = d->lrelu_slope; f.out_scale = d->out_scale;
+    f.style_stride = d->style_stride; f.flags = d->flags & epi; f.slope = d->lrelu_slope; f.out_scale = d->out_scale * up_scale;
     f.act_gain = a.act_gain; f.out_scale_dev = d->out_scale_dev;
     return spkconv::launch_splitk_epilogue(f, static_cast<const float*>(d->workspace), ks, (hipStream_t)stream);
 }

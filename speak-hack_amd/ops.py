@@ -387,6 +387,9 @@ def conv3x3_bf16x3(x, w_packed, Cout, *, bias=None, noise_w=None, noise=None, st
 # previous rounds' arithmetic, bit for bit).  Both are fp32 operands, fp32 products, fp32 accumulation.
 CONV3X3_ALGO = os.environ.get("SPK_CONV3X3_ALGO", "auto")
 WINO_MIN_WORKGROUPS = 192          # one workgroup per CU: below ~3/4 of a round the direct kernel's split-K wins
+# A bilinear x2 layer on the Winograd kernel: 1 -- the interpolation is part of the kernel's input transform (SPK_CONV_WINOGRAD |
+# SPK_CONV_UPSAMPLE2X: the launch reads the low-resolution tensor, no x2 image exists); 0 -- the x2 image is written first.
+WINO_FUSE_X2 = os.environ.get("SPK_WINO_FUSE_X2", "1") != "0"
 
 
 @contextlib.contextmanager
@@ -421,6 +424,13 @@ def wino_ksplit(B, Cin, Cout, H, W, want=0) -> int:
 def wino_supported(B, Cin, Cout, H, W) -> bool:
     """Whether the fp32 Winograd kernel serves a 3x3 stride-1 conv with this OUTPUT shape (whole 32 x 8 regions, Cin % 16 == 0)."""
     return bool(L.lib().spk_conv2d_wino_supported(B, Cin, Cout, H, W))
+
+
+def wino_fuse_x2(B, Cin, Cout, H, W, up_fir=False, modulated=False) -> bool:
+    """Whether a x2 layer with this OUTPUT shape that ``conv3x3_route`` sent to the Winograd kernel interpolates inside the
+    kernel's input transform (plain bilinear layers only: the upfirdn2d form and a ``modulated`` conv -- a batch-scaled input --
+    keep their pass) -- the one place the eager path and the plans ask."""
+    return bool(WINO_FUSE_X2 and not up_fir and not modulated and L.lib().spk_conv2d_wino_up_supported(B, Cin, Cout, H, W))
 
 
 def pack_conv_weight_wino(weight: torch.Tensor, out=None, transpose_flip=False) -> torch.Tensor:
@@ -483,14 +493,18 @@ def upsample2x(x, zero_border=False):
 
 def conv3x3_wino(x, w_packed, Cout, *, bias=None, noise_w=None, noise=None, style=None, style_stride=None, lrelu_slope=None,
                  out_scale=1.0, act_gain=1.0, out=None, out_pre=None, accumulate=False, out_scale_dev=None, batch_scale=None, demod=None,
-                 ksplit=0, rgb=None, rgb_out=None, store_out=True, groups=1):
+                 ksplit=0, rgb=None, rgb_out=None, store_out=True, groups=1, upsample=False):
     """3x3 stride-1 pad-1 conv with the fused decoder epilogue as Winograd F(2x2, 3x3): fp32 throughout, 2.25x fewer matrix
     instructions than the direct form, 1e-6-class rel-L2 against it.  ``w_packed`` from ``pack_conv_weight_wino``.
+    ``upsample``: the conv of bilinear_x2(x) -- x is the low-resolution tensor, the interpolation happens in the input transform
+    (plain launches only: no ``batch_scale``, no ``groups``).
     ``rgb`` = (weight [3,Cout,1,1], bias [3] | None): the 1x1 conv of styleganv1.py:607 inside the epilogue (Cout <= 64, unsliced);
     returns (out, rgb image), and with ``store_out=False`` (None, rgb image) -- the activation is then never written.
     ``groups`` > 1: that many independent convs in one launch (``Cout`` per group, x carries the groups' input channels side by side,
     ``w_packed`` = the groups' images one after another); plain or ``accumulate`` only -- the encoders' data gradients."""
     B, _, H, W = x.shape
+    if upsample:
+        H, W = 2 * H, 2 * W
     G = int(groups)
     if G > 1 and any(t is not None for t in (bias, noise, style, out_pre, batch_scale, demod, rgb, lrelu_slope)):
         raise L.SpkError("conv3x3_wino: a grouped launch is plain (accumulate allowed)")
@@ -507,7 +521,7 @@ def conv3x3_wino(x, w_packed, Cout, *, bias=None, noise_w=None, noise=None, styl
     d, ws_bytes = conv_desc(x, w_packed, Cout, flags=L.CONV_WINOGRAD, out=out, bias=bias, noise_w=noise_w, noise=noise, style=style,
                             style_stride=style_stride, lrelu_slope=lrelu_slope, out_scale=out_scale, act_gain=act_gain, out_pre=out_pre,
                             accumulate=accumulate, out_scale_dev=out_scale_dev, batch_scale=batch_scale, demod=demod, ksplit=ksplit,
-                            groups=G, rgb_w=rgb_w2d, rgb_bias=rgb_bias, rgb_out=rgb_out if rgb is not None else None)
+                            groups=G, rgb_w=rgb_w2d, rgb_bias=rgb_bias, rgb_out=rgb_out if rgb is not None else None, upsample=upsample)
     _run_conv2d(d, ws_bytes, x.device)        # (few regions: the contraction runs in slices through the split-K workspace)
     return (out, rgb_out) if rgb is not None else out
 
@@ -541,9 +555,10 @@ def conv3x3_route(B, Cin, Cout, H, W, *, precision=None, groups=1, modulated=Fal
 
 def conv3x3(x, images, Cout, route, *, transpose_flip=False, upsample=False, up_fir=False, **epilogue):
     """One eager 3x3 stride-1 conv on the kernel ``route`` names (``conv3x3_route``).  ``images(key, transpose_flip)`` -> (the
-    packed image ``key`` names -- see ``pack_image`` --, a device scalar for ``out_scale_dev`` or None).  A x2 layer
-    (``upsample``) on the Winograd kernel first materialises its input: bilinear, or -- ``up_fir`` -- upfirdn2d(up=2,
-    [1,3,3,1]); the other kernels interpolate while staging.  ``epilogue``: the keywords of ``conv2d_fused``."""
+    packed image ``key`` names -- see ``pack_image`` --, a device scalar for ``out_scale_dev`` or None).  A bilinear x2 layer
+    (``upsample``) on the Winograd kernel interpolates inside the input transform (``wino_fuse_x2``); otherwise -- ``up_fir``:
+    upfirdn2d(up=2, [1,3,3,1]), a modulated conv, ``SPK_WINO_FUSE_X2=0`` -- it first materialises its input.  The other kernels
+    interpolate while staging.  ``epilogue``: the keywords of ``conv2d_fused``."""
     kind, config = route
     image, scale_dev = images(config if kind == "direct" else kind, transpose_flip)
     if scale_dev is not None:
@@ -551,6 +566,9 @@ def conv3x3(x, images, Cout, route, *, transpose_flip=False, upsample=False, up_
     if kind == "bf16x3":
         return conv3x3_bf16x3(x, image, Cout, upsample=upsample, up_fir=up_fir, **epilogue)
     if kind == "wino":
+        if upsample and wino_fuse_x2(x.shape[0], x.shape[1], Cout, 2 * x.shape[2], 2 * x.shape[3], up_fir,
+                                     modulated=epilogue.get("batch_scale") is not None):
+            return conv3x3_wino(x, image, Cout, upsample=True, **epilogue)
         if upsample:
             x = upsample2x(x, zero_border=True) if up_fir else upsample2x_bilinear(x)
         return conv3x3_wino(x, image, Cout, **epilogue)

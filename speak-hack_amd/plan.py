@@ -70,9 +70,11 @@ class LaunchPlan:
         kind, cfg = ops.conv3x3_route(B, Cin, Cout, H, W, precision=precision, modulated=batch_scale is not None,
                                       up_w=Ws if upsample else None)
         up_op = None
-        if kind == "wino" and upsample:
-            # a x2 layer first writes its upsampled input (one HBM-bound launch: the separate nn.Upsample of
-            # styleganv1.py:621,624) -- the transform would cost more inside the MFMA kernel than this pass does beside it
+        if kind == "wino" and upsample and ops.wino_fuse_x2(B, Cin, Cout, H, W, up_fir, modulated=batch_scale is not None):
+            pass      # the interpolation is part of the kernel's input transform: the descriptor below carries both flags
+        elif kind == "wino" and upsample:
+            # the upfirdn2d form, a modulated conv, SPK_WINO_FUSE_X2=0: the layer first writes its upsampled input (one HBM-bound
+            # launch: the separate nn.Upsample of styleganv1.py:621,624)
             need = B * Cin * H * W                    # one scratch image for all x2 layers: launches are stream-ordered
             if self._up_scratch is None or self._up_scratch.numel() < need:
                 self._up_scratch = self.buf(need)
@@ -320,7 +322,7 @@ def plan_for(owner, key, build):
     buffers stay where the graph's kernels will read and write them (as ``ops._workspace`` retires outgrown scratch).  Such
     a graph replays the weights as they were packed at ITS capture: re-capture after an optimizer step."""
     cache = owner.__dict__.setdefault("_plans", {})
-    key = key + (ops.CONV3X3_ALGO,)
+    key = key + (ops.CONV3X3_ALGO, ops.WINO_FUSE_X2)
     plan = cache.pop(key, None)
     if plan is None or not plan.valid_for():
         _drop(plan)

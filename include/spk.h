@@ -614,6 +614,33 @@ int spk_spectral_norm_bwd_grouped(const spk_sn_group* groups, int n_groups, void
  * conv + bias + LeakyReLU layer (styleganv1.py:662-672), accumulated in place across the passes of one backward. */
 int spk_plane_sums_reduce(const float* sums, int B, int rows, int C, int row, float* out, int accumulate, void* stream);
 
+/* ---- the video-frame edge: uint8 HWC frames in and out (csrc/frame_io.hip) --------------------------------------------------
+ * spk_resize_table: one axis of the separable triangle filter of torch.nn.functional.interpolate(mode="bilinear",
+ *   align_corners=False, antialias=True) (what transforms.Resize applies to a tensor) for n_in -> n_out samples, built in fp64 on
+ *   the HOST: with s = n_in / n_out, support = max(s, 1), centre = s (o + 0.5): first = max(0, int(centre - support + 0.5)),
+ *   last = min(n_in, int(centre + support + 0.5)), w_j ~ max(0, 1 - |(j - centre + 0.5) / support|) for j in [first, last),
+ *   normalised to sum 1, zero weights at either end dropped.  first_host / count_host [n_out]; w_host (fp64) and / or w_f32_host
+ *   [n_out][taps], zero padded, taps >= spk_resize_table_taps(n_in, n_out) (the widest window).  The fp32 rows are the fp64
+ *   ones rounded to nearest and then moved by whole ulps until every row sums to exactly 1.  No device work.
+ * spk_frames_u8_to_f32: crop + antialiased bilinear resize + normalise + HWC -> CHW in one pass.  src: N uint8 images of
+ *   Hin x Win pixels, pixel stride 3, image_stride / row_stride in BYTES (a crop box is a pointer offset plus the strides of
+ *   the uncropped frames; any byte address is legal); the six tables are DEVICE copies of spk_resize_table's (fp32 weights);
+ *   dst [N,3,Hout,Wout] contiguous:
+ *     dst[n,c,oy,ox] = scale_c * sum_iy sum_ix w_y[oy,iy] w_x[ox,ix] src[n,iy,ix,c'] + shift_c,  c' = swap_rb ? 2 - c : c.
+ *   scale 2/255, shift -1 = ToTensor + Normalize(0.5, 0.5).  Sums run in fp64 (taps_x + taps_y additions per output).
+ *   replaces: inference.py:29-33,46-58 (cv2.cvtColor, transforms.Resize, ToTensor, Normalize per frame).
+ * spk_frames_f32_to_u8: quantise + CHW -> HWC: dst[n,y,x,c'] = rint(min(max((src[n,c,y,x] - lo) * k, 0), 255)) in that order
+ *   of fp32 operations (ties to even; NaN -> 0), k = 255 / (hi - lo) rounded to fp32 by the caller; src [N,3,H,W] contiguous,
+ *   dst uint8 [N,H,W,3] contiguous at any byte address.  replaces: inference.py:78-86 (save_video's scaling, cast, transpose
+ *   and cvtColor; the reference multiplies by 255 without offset or clamp, which wraps on a tanh-range frame). */
+int spk_resize_table_taps(int n_in, int n_out);
+int spk_resize_table(int n_in, int n_out, int taps, int32_t* first_host, int32_t* count_host, double* w_host, float* w_f32_host);
+int spk_frames_u8_to_f32(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int Hin, int Win, int swap_rb,
+                         const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y, const int32_t* first_x,
+                         const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout, float scale0,
+                         float scale1, float scale2, float shift0, float shift1, float shift2, void* stream);
+int spk_frames_f32_to_u8(const float* src, uint8_t* dst, int N, int H, int W, int swap_rb, float lo, float k, void* stream);
+
 /* ---- launch lists: a whole module forward per C call ---------------------------------------------------------------
  * The reference's callers run a decoder pass as one Python call (model.py:113-114 `self.Gd(gen_input)`,
  * styleganv1.py:593-610 SynthesisNetwork.forward); behind it sit ~25 kernel launches whose descriptors depend only on
@@ -634,8 +661,9 @@ enum {
     SPK_OP_UPSAMPLE2X = 8,        /* desc: spk_upsample2x_args      -> spk_upsample2x_fwd (the x2 image of a block whose conv1
                                    * runs as Winograd, styleganv1.py:621,624) */
     SPK_OP_MAXPOOL3X3S2 = 9,      /* desc: spk_maxpool3x3s2_args    -> spk_maxpool3x3s2_fwd (resnet50.maxpool, model.py:62) */
-    SPK_OP_GLOBAL_AVGPOOL = 10    /* desc: spk_global_avgpool_args  -> spk_global_avgpool_fwd (resnet50.avgpool): with the two kinds a
+    SPK_OP_GLOBAL_AVGPOOL = 10,   /* desc: spk_global_avgpool_args  -> spk_global_avgpool_fwd (resnet50.avgpool): with the two kinds a
                                    * whole BatchNorm-folded trunk pass is one list */
+    SPK_OP_FRAMES_TO_U8 = 11      /* desc: spk_frames_to_u8_args    -> spk_frames_f32_to_u8 (a decoder plan that ends in uint8 HWC frames) */
 };
 typedef struct spk_op { int32_t kind; int32_t reserved; const void* desc; } spk_op;
 typedef struct spk_fc_args {
@@ -658,6 +686,7 @@ typedef struct spk_maxpool3x3s2_args {   /* in_scale / in_shift NULL: a plain in
     const float* x; const float* in_scale; const float* in_shift; float* y; int32_t B, C, Hin, Win;
 } spk_maxpool3x3s2_args;
 typedef struct spk_global_avgpool_args { const float* x; float* y; int64_t planes; int64_t HW; } spk_global_avgpool_args;
+typedef struct spk_frames_to_u8_args { const float* x; uint8_t* y; int32_t N, H, W, swap_rb; float lo, k; } spk_frames_to_u8_args;
 int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask, void* stream);
 
 #ifdef __cplusplus

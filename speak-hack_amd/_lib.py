@@ -86,6 +86,7 @@ class DemodGroup(C.Structure):
 # ---- launch lists (include/spk.h: spk_launch_list) ----
 OP_CONV2D, OP_FC, OP_FC_GROUPED, OP_BIAS_NOISE_STYLE, OP_TORGB, OP_DEMOD_GROUPED, OP_PIXELNORM, OP_UPSAMPLE2X = 1, 2, 3, 4, 5, 6, 7, 8
 OP_MAXPOOL3X3S2, OP_GLOBAL_AVGPOOL = 9, 10
+OP_FRAMES_TO_U8 = 11
 ALL_OPS = 0xFFFFFFFF
 
 
@@ -131,6 +132,12 @@ class MaxPool3x3s2Args(C.Structure):
 
 class GlobalAvgPoolArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("planes", C.c_int64), ("HW", C.c_int64)]
+
+
+class FramesToU8Args(C.Structure):
+    """``spk_frames_to_u8_args`` (include/spk.h)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("swap_rb", C.c_int32),
+                ("lo", C.c_float), ("k", C.c_float)]
 
 
 class PixelNormArgs(C.Structure):
@@ -267,6 +274,12 @@ _PROTOTYPES = {
     "spk_upsample2x_bilinear_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "spk_plane_sums_reduce": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "spk_upsample2x_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "spk_resize_table_taps": (C.c_int, [C.c_int, C.c_int]),
+    "spk_resize_table": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spk_frames_u8_to_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_f32_to_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
 }
 
 _lib = None

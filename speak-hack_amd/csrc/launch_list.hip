@@ -67,6 +67,11 @@ extern "C" int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask,
                 rc = spk_global_avgpool_fwd(a->x, a->y, a->planes, a->HW, stream);
                 break;
             }
+            case SPK_OP_FRAMES_TO_U8: {
+                const spk_frames_to_u8_args* a = static_cast<const spk_frames_to_u8_args*>(op.desc);
+                rc = spk_frames_f32_to_u8(a->x, a->y, a->N, a->H, a->W, a->swap_rb, a->lo, a->k, stream);
+                break;
+            }
             default:
                 return spk::fail(SPK_EUNSUPPORTED, "launch_list: op %d: unknown kind %d", i, op.kind);
         }

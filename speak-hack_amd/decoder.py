@@ -261,9 +261,10 @@ class StyleGenerator(nn.Module):
         syn = self.synthesis
         return syn.use_plan and features.is_cuda and features.dim() == 2 and len(syn.layers) * 2 + 1 <= ops.L.FC_MAX_GROUPS
 
-    def plan_forward(self, features, noises=None):
+    def plan_forward(self, features, noises=None, *, output="f32", value_range=(-1, 1), swap_rb=False):
         """The eval forward -- mapping, truncation, synthesis; no style mixing, no host-RNG draw -- on the inference launch plan,
-        whatever ``self.training`` is (no module state is read or touched).  No gradient flows through it."""
+        whatever ``self.training`` is (no module state is read or touched).  No gradient flows through it.  ``output="uint8"``:
+        the plan ends in the quantising op and returns uint8 [B,R,R,3] frames (``plan.DecoderPlan``)."""
         syn = self.synthesis
         if noises is not None and len(noises) != 2 * len(syn.layers) + 1:
             raise ValueError(f"expected {2 * len(syn.layers) + 1} noise tensors, got {len(noises)}")
@@ -271,7 +272,10 @@ class StyleGenerator(nn.Module):
         # (the truncation scale is folded into the style FCs' multipliers when the plan is built: part of the key)
         key = (B, features.device, torch.cuda.current_stream(features.device).cuda_stream, "features", syn.precision,
                self.truncation_psi, self.truncation_cutoff)
-        p = PL.plan_for(self, key, lambda: PL.DecoderPlan(syn, B, features.device, generator=self, precision=syn.precision))
+        if output != "f32":
+            key += (output, float(value_range[0]), float(value_range[1]), bool(swap_rb))
+        p = PL.plan_for(self, key, lambda: PL.DecoderPlan(syn, B, features.device, generator=self, precision=syn.precision,
+                                                          output=output, value_range=value_range, swap_rb=swap_rb))
         return p.run(features if features.stride(1) == 1 else features.contiguous(),
                      None if noises is None else [n.contiguous() for n in noises])
 

@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import autograd as AG
+from . import ops
 from . import plan as PL
 from .decoder import StyleGenerator
 from .discriminator import StyleDiscriminator
@@ -91,13 +92,21 @@ class IRFD(nn.Module):
         return PL.plan_for(trunk, key, lambda: PL.EncoderPlan(trunk, B, H, W, images.device)).run(images)
 
     @torch.no_grad()
-    def reenact(self, identity_image, pose_frames, emotion_frames=None, *, noises=None, chunk=8):
+    def reenact(self, identity_image, pose_frames, emotion_frames=None, *, noises=None, chunk=8, output="f32", channel_order="rgb"):
         """Talking-head frames: ``Gd(cat(Ei(identity).expand(T), Ee(emotion_frames), Ep(pose_frames)))`` in the feature order
         of ``_prepare_generator_input(fi, fe, fp)`` (model.py:64-69,107), in eval arithmetic whatever ``self.training`` is: no
         buffer update, no host-RNG draw, no swap, no style mixing, truncation as ``StyleGenerator.forward`` applies it in eval.
         ``identity_image`` [1,3,H,W]; ``pose_frames`` / ``emotion_frames`` [T,3,H,W] (None: the pose frames); ``noises``: the
         explicit list ``StyleGenerator.forward`` takes, for T frames (default: drawn on the device).  ``Ei`` runs once; the
-        frames go through the encoder and decoder plans ``chunk`` at a time.  -> frames [T,3,R,R] fp32."""
+        frames go through the encoder and decoder plans ``chunk`` at a time.  -> frames [T,3,R,R] fp32; with ``output="uint8"``
+        uint8 [T,R,R,3] in ``channel_order`` ("rgb" | "bgr"), quantised from (-1, 1) by the last op of the decoder plan --
+        ``ops.frames_to_u8`` of the fp32 result, bit for bit."""
+        if output not in ("f32", "uint8"):
+            raise ValueError(f"reenact: output must be 'f32' or 'uint8', got {output!r}")
+        if channel_order not in ("rgb", "bgr"):
+            raise ValueError(f"reenact: channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+        if output == "f32" and channel_order != "rgb":
+            raise ValueError("reenact: channel_order applies to uint8 output only")
         if identity_image.dim() != 4 or identity_image.size(0) != 1 or identity_image.size(1) != 3:
             raise ValueError(f"reenact: identity_image must be [1,3,H,W], got {tuple(identity_image.shape)}")
         if pose_frames.dim() != 4 or pose_frames.size(1) != 3 or pose_frames.size(0) < 1:
@@ -117,23 +126,38 @@ class IRFD(nn.Module):
             t1 = min(T, t0 + chunk)
             fe, fp = self.encode(emotion_frames[t0:t1], "Ee"), self.encode(pose_frames[t0:t1], "Ep")
             gin = self._prepare_generator_input(fi.expand(t1 - t0, -1, -1, -1), fe, fp)
-            out.append(self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises]))
+            out.append(self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises], output, channel_order))
         return out[0] if len(out) == 1 else torch.cat(out, 0)
 
-    def _decode_eval(self, gin, noises):
+    @torch.no_grad()
+    def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8):
+        """``reenact`` from and to video frames as a decoder and a video writer hold them (inference.py:29-33,46-58,78-86):
+        uint8 HWC frames of any size on the device in, uint8 [T,R,R,3] out, both in ``channel_order`` ("bgr": ``cv2``'s).
+        Nothing but ``ops.frames_from_u8`` -> ``reenact(output="uint8")``: ``identity_u8`` [H,W,3] or [1,H,W,3] is resized whole
+        to ``size``; ``pose_u8`` / ``emotion_u8`` [T,H,W,3] are cropped to ``crop=(y0, x0, h, w)`` (one box for all frames) and
+        resized; ``emotion_u8=None``: the pose frames, resized once."""
+        ident = ops.frames_from_u8(identity_u8, size, channel_order=channel_order)
+        pose = ops.frames_from_u8(pose_u8, size, crop=crop, channel_order=channel_order)
+        emo = None if emotion_u8 is None else ops.frames_from_u8(emotion_u8, size, crop=crop, channel_order=channel_order)
+        return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output="uint8", channel_order=channel_order)
+
+    def _decode_eval(self, gin, noises, output="f32", channel_order="rgb"):
         """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan
         does not serve runs its eval branch with every submodule's own ``training`` flag saved and put back."""
         Gd = self.Gd
         if hasattr(Gd, "plan_serves") and Gd.plan_serves(gin):
-            return Gd.plan_forward(gin, noises)
+            if output == "f32":
+                return Gd.plan_forward(gin, noises)
+            return Gd.plan_forward(gin, noises, output=output, swap_rb=channel_order == "bgr")
         flags = [(mod, mod.training) for mod in Gd.modules()]
         try:
             for mod, _ in flags:
                 mod.training = False
-            return Gd(gin, noises)
+            y = Gd(gin, noises)
         finally:
             for mod, was in flags:
                 mod.training = was
+        return y if output == "f32" else ops.frames_to_u8(y, channel_order=channel_order)
 
     def forward(self, x_s, x_t, swap_type=None, noises_s=None, noises_t=None):
         """-> (x_s_recon, x_t_recon, fi_s, fe_s, fp_s, fi_t, fe_t, fp_t, emotion_pred_s, emotion_pred_t).

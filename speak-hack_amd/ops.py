@@ -1410,3 +1410,126 @@ def global_avgpool(x):
     L.check(L.lib().spk_global_avgpool_fwd(L.dptr(x, "x"), L.dptr(out), B * Cc, H * W, L.stream_ptr()),
             "spk_global_avgpool_fwd")
     return out
+
+
+# ---- the video-frame edge: uint8 HWC frames in and out (csrc/frame_io.hip) ------------------------------------------------
+def _channel_swap(channel_order) -> int:
+    if channel_order not in ("rgb", "bgr"):
+        raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+    return 1 if channel_order == "bgr" else 0
+
+
+def _resize_table(n_in, n_out, dtype):
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resize_tables: sizes must be >= 1, got {n_in} -> {n_out}")
+    lib = L.lib()
+    taps = lib.spk_resize_table_taps(n_in, n_out)
+    if taps < 1:
+        raise L.SpkError(f"spk_resize_table_taps failed ({taps}): {lib.spk_last_error().decode()}")
+    first, count = torch.empty(n_out, dtype=torch.int32), torch.empty(n_out, dtype=torch.int32)
+    w = torch.empty((n_out, taps), dtype=dtype)
+    w64, w32 = (w.data_ptr(), None) if dtype == torch.float64 else (None, w.data_ptr())
+    L.check(lib.spk_resize_table(n_in, n_out, taps, first.data_ptr(), count.data_ptr(), w64, w32), "spk_resize_table")
+    return first, count, w
+
+
+def resize_tables(n_in, n_out):
+    """One axis of the separable triangle filter of ``F.interpolate(mode="bilinear", align_corners=False, antialias=True)``
+    for ``n_in -> n_out`` samples, built in fp64 on the host (``spk_resize_table``): output ``o`` is
+    ``sum_j w[o, j] * x[first[o] + j]`` over ``j < count[o]``.  -> CPU tensors ``first`` int32 [n_out], ``count`` int32 [n_out],
+    ``w`` float64 [n_out, taps], zero padded to the widest window."""
+    return _resize_table(n_in, n_out, torch.float64)
+
+
+def resize_tables_f32(n_in, n_out):
+    """The same table as the kernel reads it: fp32 weights, every row summing to exactly 1."""
+    return _resize_table(n_in, n_out, torch.float32)
+
+
+_resize_cache = {}
+
+
+def _device_resize_tables(Hin, Win, Hout, Wout, device):
+    key = (Hin, Win, Hout, Wout, device)
+    t = _resize_cache.get(key)
+    if t is None:
+        if len(_resize_cache) >= 32:
+            _resize_cache.pop(next(iter(_resize_cache)))
+        ty, tx = resize_tables_f32(Hin, Hout), resize_tables_f32(Win, Wout)
+        t = _resize_cache[key] = tuple(a.to(device) for a in ty) + tuple(a.to(device) for a in tx)
+    return t
+
+
+def _triple(v, name):
+    v = [float(v)] * 3 if isinstance(v, (int, float)) else [float(a) for a in v]
+    if len(v) != 3:
+        raise ValueError(f"{name} must be a number or three numbers")
+    return v
+
+
+def frames_from_u8(frames_u8, size, *, crop=None, channel_order="rgb", mean=0.5, std=0.5):
+    """uint8 HWC video frames -> the network's input, one launch (``spk_frames_u8_to_f32``): crop, antialiased bilinear resize
+    to ``size`` x ``size`` (a number, or ``(H, W)``), ``(x / 255 - mean) / std`` per channel and HWC -> CHW -- ``transforms.Resize``
+    + ``ToTensor`` + ``Normalize`` of inference.py:29-33 with the ``cv2.cvtColor`` of :53 (``channel_order="bgr"``: the frames are
+    BGR, the result is RGB).  ``frames_u8``: uint8 [N,H,W,3] (or [H,W,3]) on the device, pixels packed (any row / frame stride:
+    slices of a larger frame are read in place); ``crop=(y0, x0, h, w)``: one box for all frames.  -> float32 [N,3,size,size]."""
+    if frames_u8.dim() == 3:
+        frames_u8 = frames_u8.unsqueeze(0)
+    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
+        raise ValueError(f"frames_from_u8: frames must be [N,H,W,3], got {tuple(frames_u8.shape)}")
+    Hout, Wout = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if Hout < 1 or Wout < 1:
+        raise ValueError(f"frames_from_u8: size must be >= 1, got {size}")
+    swap = _channel_swap(channel_order)
+    mean, std = _triple(mean, "mean"), _triple(std, "std")
+    if any(s == 0 for s in std):
+        raise ValueError("frames_from_u8: std must be non-zero")
+    if crop is not None:
+        y0, x0, h, w = (int(v) for v in crop)
+        if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > frames_u8.size(1) or x0 + w > frames_u8.size(2):
+            raise ValueError(f"frames_from_u8: crop {tuple(crop)} leaves the {frames_u8.size(1)} x {frames_u8.size(2)} frame")
+        frames_u8 = frames_u8[:, y0:y0 + h, x0:x0 + w]
+    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
+        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
+    N, Hin, Win, _ = frames_u8.shape
+    if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * Win or (N > 1 and frames_u8.stride(0) < 0):
+        frames_u8 = frames_u8.contiguous()
+    fy, cy, wy, fx, cx, wx = _device_resize_tables(Hin, Win, Hout, Wout, frames_u8.device)
+    scale = [1.0 / (255.0 * s) for s in std]
+    shift = [-m / s for m, s in zip(mean, std)]
+    out = torch.empty((N, 3, Hout, Wout), device=frames_u8.device, dtype=torch.float32)
+    L.check(L.lib().spk_frames_u8_to_f32(frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), N, Hin, Win,
+                                         swap, fy.data_ptr(), cy.data_ptr(), wy.data_ptr(), wy.size(1), fx.data_ptr(), cx.data_ptr(),
+                                         wx.data_ptr(), wx.size(1), out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()),
+            "spk_frames_u8_to_f32")
+    return out
+
+
+def quant_range(value_range):
+    """``(lo, k)`` of ``q = rint(clamp((x - lo) * k, 0, 255))`` for frames in ``value_range = (lo, hi)``."""
+    lo, hi = float(value_range[0]), float(value_range[1])
+    if not hi > lo:
+        raise ValueError(f"value_range must be increasing, got {tuple(value_range)}")
+    return lo, 255.0 / (hi - lo)
+
+
+def frames_to_u8(x, *, value_range=(-1, 1), channel_order="rgb", out=None):
+    """Network frames -> uint8 HWC for a video writer, one launch (``spk_frames_f32_to_u8``): float32 [N,3,H,W] in
+    ``value_range`` (the decoder's (-1, 1), or (0, 1)) -> uint8 [N,H,W,3], ``channel_order="bgr"`` for ``cv2.VideoWriter``;
+    bit for bit ``((x - lo) * (255 / (hi - lo))).clamp(0, 255).round().to(torch.uint8)``, ties to even; NaN -> 0.  The
+    reference's ``save_video`` (inference.py:78-86) multiplies by 255 and casts without offset or clamp, which wraps around on a
+    frame in (-1, 1); that is deliberately not reproduced.  ``out``: a uint8 tensor [N,H,W,3] to write (contiguous, any byte
+    offset)."""
+    if x.dim() != 4 or x.size(1) != 3 or x.size(0) < 1:
+        raise ValueError(f"frames_to_u8: x must be [N,3,H,W], got {tuple(x.shape)}")
+    swap = _channel_swap(channel_order)
+    lo, k = quant_range(value_range)
+    N, _, H, W = x.shape
+    xp = L.dptr(x, "x")
+    if out is None:
+        out = torch.empty((N, H, W, 3), device=x.device, dtype=torch.uint8)
+    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous():
+        raise L.SpkError(f"out: expected a contiguous uint8 HIP tensor {(N, H, W, 3)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    L.check(L.lib().spk_frames_f32_to_u8(xp, out.data_ptr(), N, H, W, swap, lo, k, L.stream_ptr()), "spk_frames_f32_to_u8")
+    return out

@@ -170,12 +170,17 @@ class LaunchPlan:
 class DecoderPlan(LaunchPlan):
     """``SynthesisNetwork.forward`` (styleganv1.py:593-610), optionally preceded by ``StyleGenerator``'s mapping stack and
     truncation (styleganv1.py:528-543): 8 FC launches (with the mapping), one grouped launch for the 13+ style affines,
-    the constant prologue, 2 fused conv launches per block, toRGB."""
+    the constant prologue, 2 fused conv launches per block, toRGB.  ``output="uint8"``: the fp32 frame goes to a plan-owned
+    buffer and one more op (``SPK_OP_FRAMES_TO_U8``) quantises it from ``value_range`` into the uint8 [B,R,R,3] frames
+    ``run`` returns (``swap_rb``: B, G, R order) -- what ``ops.frames_to_u8`` makes of the fp32 result, bit for bit."""
 
-    def __init__(self, synthesis, B, device, generator=None, precision="f32"):
+    def __init__(self, synthesis, B, device, generator=None, precision="f32", output="f32", value_range=(-1, 1), swap_rb=False):
         super().__init__(device)
+        if output not in ("f32", "uint8"):
+            raise ValueError(f"DecoderPlan: output must be 'f32' or 'uint8', got {output!r}")
         s = self.synthesis = synthesis
         self.precision = precision
+        self.output = output
         self.B, self.with_mapping = B, generator is not None
         mods = [s.style_mod] + [m for layer in s.layers for m in (layer.style_mod1, layer.style_mod2)]
         if len(mods) > L.FC_MAX_GROUPS:
@@ -259,6 +264,18 @@ class DecoderPlan(LaunchPlan):
             self.torgb = self.add(L.OP_TORGB, L.ToRGBArgs(x=x.data_ptr(), w=L.dptr(s.to_rgb.weight, "weight"), mod=None,
                                                           bias=L.dptr(s.to_rgb.bias, "bias"), skip=None, y=None, B=B, C=Cc, O=O,
                                                           H=x.shape[2], W=x.shape[3], in_scale=1.0))
+        self.to_u8 = None
+        if output == "uint8":
+            if O != 3:
+                raise L.SpkError(f"DecoderPlan: uint8 frames need 3 output channels, toRGB has {O}")
+            lo, k = ops.quant_range(value_range)
+            self.rgb_buf = self.buf(*self.out_shape)
+            if self.rgb_fused is not None:
+                self.rgb_fused.rgb_y = self.rgb_buf.data_ptr()
+            else:
+                self.torgb.y = self.rgb_buf.data_ptr()
+            self.to_u8 = self.add(L.OP_FRAMES_TO_U8, L.FramesToU8Args(x=self.rgb_buf.data_ptr(), y=None, N=B, H=x.shape[2], W=x.shape[3],
+                                                                       swap_rb=1 if swap_rb else 0, lo=lo, k=k))
         self.finish(*([synthesis] + ([generator] if generator is not None else [])))
 
     @staticmethod
@@ -298,11 +315,16 @@ class DecoderPlan(LaunchPlan):
                 if nz.numel() != nv.numel():
                     raise L.SpkError(f"noise must be {tuple(nv.shape)}, got {tuple(nz.shape)}")
                 d.noise = L.dptr(nz, "noise")
-        y = torch.empty(self.out_shape, device=self.device, dtype=torch.float32)
-        if self.rgb_fused is not None:
-            self.rgb_fused.rgb_y = y.data_ptr()
+        if self.to_u8 is not None:
+            Bo, _, Ho, Wo = self.out_shape
+            y = torch.empty((Bo, Ho, Wo, 3), device=self.device, dtype=torch.uint8)
+            self.to_u8.y = y.data_ptr()
         else:
-            self.torgb.y = y.data_ptr()
+            y = torch.empty(self.out_shape, device=self.device, dtype=torch.float32)
+            if self.rgb_fused is not None:
+                self.rgb_fused.rgb_y = y.data_ptr()
+            else:
+                self.torgb.y = y.data_ptr()
         self.launch(kind_mask)
         return y
 

@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""The video-frame edge of the inference path (csrc/frame_io.hip).
+
+(1) ``ops.frames_from_u8`` and ``ops.frames_to_u8`` alone, beside the time their bytes take at 4.5 TB/s (as tools/bench_pointwise.py
+    does for the other memory-bound helpers): 8 frames of 1080 x 1920 BGR -> 256^2, 8 frames of 256^2 RGB -> 256^2, 8 frames of
+    256^2 fp32 -> uint8.
+(2) ``IRFD.reenact_video`` against the eager composition on the same GPU -- torch ``interpolate(antialias=True)`` + normalise +
+    ``IRFD.reenact`` + torch quantise / permute -- alternating in one process: T = 64 frames, chunks of 8, 1080 x 1920 BGR and
+    256 x 256 RGB input, device-synchronised, after warm-up.  Both produce uint8 [T,256,256,3]; they are compared too (the
+    resize filters agree to fp32 rounding, so a few bytes may differ by one step).
+(3) What crosses the C boundary / the ATen dispatcher at the edge, per call.
+
+    python tools/bench_frame_io.py [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+from torch.utils._python_dispatch import TorchDispatchMode
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM = 4.5e12        # bytes / s, the figure tools/bench_pointwise.py uses
+
+
+class CountAten(TorchDispatchMode):
+    def __init__(self):
+        super().__init__()
+        self.n = 0
+
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        self.n += 1
+        return func(*args, **(kwargs or {}))
+
+
+def eager_in(u8, size, bgr):
+    x = u8.permute(0, 3, 1, 2)
+    if bgr:
+        x = x.flip(1)
+    x = F.interpolate(x.float(), size=(size, size), mode="bilinear", align_corners=False, antialias=True)
+    return (x / 255 - 0.5) / 0.5
+
+
+def eager_out(y, bgr):
+    q = ((y + 1) * 127.5).clamp(0, 255).round().to(torch.uint8)
+    if bgr:
+        q = q.flip(1)
+    return q.permute(0, 2, 3, 1).contiguous()
+
+
+def device_time(fn, n=20, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n * 1e-3
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--chunk", type=int, default=8)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    import importlib
+    import model
+    from oracle import irfd_ref as IR
+    from oracle.weights_recipe import fill_state_dict
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    T, chunk, size = args.frames, args.chunk, 256
+    g = torch.Generator().manual_seed(0)
+    lines = [f"bench_frame_io: {torch.cuda.get_device_name(0)}, fp32, HBM time at {HBM / 1e12:.1f} TB/s"]
+
+    # ---- (1) the kernels alone ----
+    for name, shape, order in (("1080x1920 BGR", (chunk, 1080, 1920, 3), "bgr"), ("256x256 RGB", (chunk, 256, 256, 3), "rgb")):
+        u = torch.randint(0, 256, shape, generator=g, dtype=torch.uint8).to(dev)
+        t = device_time(lambda: ops.frames_from_u8(u, size, channel_order=order))
+        te = device_time(lambda: eager_in(u, size, order == "bgr"))
+        nbytes = u.numel() + chunk * 3 * size * size * 4
+        lines.append(f"frames_from_u8 {chunk} x {name} -> 256^2: {t * 1e6:8.1f} us, {nbytes / 1e6:6.1f} MB -> HBM time {nbytes / HBM * 1e6:6.1f} us "
+                     f"({nbytes / HBM / t * 100:5.1f} % of it); the torch ops it replaces: {te * 1e6:8.1f} us")
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    t = device_time(lambda: ops.frames_to_u8(x, channel_order="bgr"))
+    te = device_time(lambda: eager_out(x, True))
+    nbytes = x.numel() * 4 + x.numel()
+    lines.append(f"frames_to_u8   {chunk} x 256^2 fp32 -> uint8 BGR: {t * 1e6:8.1f} us, {nbytes / 1e6:6.1f} MB -> HBM time {nbytes / HBM * 1e6:6.1f} us "
+                 f"({nbytes / HBM / t * 100:5.1f} % of it); the torch ops it replaces: {te * 1e6:8.1f} us")
+
+    # ---- (2) reenact_video against the eager composition ----
+    m = model.IRFD()
+    sd = IR.irfd_recipe_state_dict()
+    sd.update({"Gd." + k: v for k, v in fill_state_dict(m.Gd.state_dict(), prefix="Gd.").items()})
+    m.load_state_dict(sd, strict=False)
+    m.to(dev).eval()
+    for name, hw, order in (("1080x1920 BGR", (1080, 1920), "bgr"), ("256x256 RGB", (256, 256), "rgb")):
+        bgr = order == "bgr"
+        ident = torch.randint(0, 256, (1, *hw, 3), generator=g, dtype=torch.uint8).to(dev)
+        video = torch.randint(0, 256, (T, *hw, 3), generator=g, dtype=torch.uint8).to(dev)
+        noises = [torch.randn(T, 1, 4 << (i + 1) // 2, 4 << (i + 1) // 2, generator=g).to(dev) for i in range(13)]
+
+        def ours():
+            return m.reenact_video(ident, video, size=size, channel_order=order, noises=noises, chunk=chunk)
+
+        def eager():
+            out = m.reenact(eager_in(ident, size, bgr), eager_in(video, size, bgr), noises=noises, chunk=chunk)
+            return eager_out(out, bgr)
+
+        with torch.no_grad():
+            for _ in range(args.warmup):
+                a, b = ours(), eager()
+            diff = (a.int() - b.int()).abs()
+            times = {"reenact_video": [], "eager": []}
+            for _ in range(args.repeats):                    # alternating: drift hits both alike
+                times["reenact_video"].append(wall(ours))
+                times["eager"].append(wall(eager))
+            c_ours, c_eager = CountAten(), CountAten()
+            with c_ours:
+                ours()
+            with c_eager:
+                eager()
+        lines.append(f"T = {T} frames of {name}, chunk {chunk}, {args.repeats} alternating repeats after {args.warmup} warm-up rounds:")
+        for n in ("reenact_video", "eager"):
+            ts = sorted(times[n])
+            med = statistics.median(ts)
+            lines.append(f"  {n:14s} median {med * 1e3:8.2f} ms  min {ts[0] * 1e3:8.2f}  max {ts[-1] * 1e3:8.2f}  spread "
+                         f"{(ts[-1] - ts[0]) / med * 100:5.1f} %  -> {T / med:8.1f} frames/s")
+        mo, me = statistics.median(times["reenact_video"]), statistics.median(times["eager"])
+        lines.append(f"  reenact_video / eager = {mo / me:.3f}; bytes that differ: {int((diff > 0).sum())} of {diff.numel()} (largest step {int(diff.max())}); "
+                     f"ATen calls per run: {c_ours.n} against {c_eager.n} ({T // chunk} chunks)")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

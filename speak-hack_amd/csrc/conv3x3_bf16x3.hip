@@ -665,6 +665,9 @@ int spk_conv2d_bf16x3_fwd(const spk_conv2d_desc* d, void* stream) {
     SPK_REQUIRE(!(d->flags & SPK_EPI_NOISE) || (d->noise && d->noise_w), "conv2d bf16x3: SPK_EPI_NOISE without noise");
     SPK_REQUIRE(!(d->flags & SPK_EPI_STYLE) || d->style, "conv2d bf16x3: SPK_EPI_STYLE without style");
     SPK_REQUIRE(!(d->flags & SPK_CONV_IN_BATCH_SCALE) || d->in_scale, "conv2d bf16x3: IN_BATCH_SCALE without in_scale");
+    SPK_REQUIRE(!d->out_scale_bc || (d->flags & SPK_CONV_IN_BATCH_SCALE), "conv2d bf16x3: out_scale_bc (demodulation) goes with "
+                "SPK_CONV_IN_BATCH_SCALE (the modulated convolution)");
+    SPK_REQUIRE(!d->out_scale_dev, "conv2d bf16x3: out_scale_dev is not read by this kernel (fold the scalar into out_scale)");
     const Geo g = geometry(d->B, d->H, d->W);
     SPK_REQUIRE(g.ok, "conv2d bf16x3: tile geometry does not fit %dx%d", d->H, d->W);
     SPK_REQUIRE((size_t)g.TB * d->Cin * d->Hin * d->Win < (1ull << 30), "conv2d bf16x3: image group too large for 32-bit offsets");

@@ -641,6 +641,46 @@ int spk_frames_u8_to_f32(const uint8_t* src, int64_t image_stride, int64_t row_s
                          float scale1, float scale2, float shift0, float shift1, float shift2, void* stream);
 int spk_frames_f32_to_u8(const float* src, uint8_t* dst, int N, int H, int W, int swap_rb, float lo, float k, void* stream);
 
+/* ---- counter-based decoder noise (csrc/noise.hip) ----------------------------------------------------------------------------
+ * The noise planes of a synthesis pass as a pure function of (seed, frame, layer, pixel): no generator state, so a clip comes
+ * out the same whatever the chunking or the sharding over devices, and a fixed-noise clip is every frame on one frame index.
+ * replaces: the torch.randn inside ApplyNoise.forward (styleganv1.py:448-456), 13 draws per SynthesisNetwork.forward.
+ *
+ * THE DEFINITION (public contract).  For a 64-bit seed, a signed 64-bit frame >= 0, a layer >= 0 and pixel p = h*W + w of a plane:
+ *   q = p >> 2, lane = p & 3;
+ *   bits[0..3] = Philox4x32-10(ctr, key), ctr = (q, frame & 0xffffffff, layer, frame >> 32), key = (seed & 0xffffffff, seed >> 32):
+ *     ten rounds of  (c0, c1, c2, c3) <- (hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)),
+ *     M0 = 0xD2511F53, M1 = 0xCD9E8D57 (32 x 32 -> 64-bit products), with (k0, k1) += (0x9E3779B9, 0xBB67AE85) between rounds;
+ *   u_i = ((bits[i] >> 9) + 0.5) * 2^-23   (exact in fp32, strictly inside (0, 1), so |z| <= sqrt(48 ln 2) = 5.77);
+ *   Box-Muller: z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1); z2, z3 from (u2, u3) in the same way;
+ *   the value of pixel p is z[lane].
+ * Known answers of the block function, (ctr; key) -> bits:
+ *   (0, 0, 0, 0; 0, 0)                                              -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *   (ffffffff x 4; ffffffff x 2)                                    -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *   (243f6a88 85a308d3 13198a2e 03707344; a4093822 299f31d0)        -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * The kernel evaluates the normals in fp32 (logf, sqrtf, sincospi(2 u)): within 1e-5 of the fp64 evaluation of the definition
+ * (measured on an MI355X: 5.9e-7 at most), and the same bits for the same (seed, frame, layer, p) whatever else
+ * the launch fills.
+ *
+ * spk_noise_bits_host: bits[0..3] of block q, computed on the HOST by the routine the kernel compiles (no device work).  The
+ *   arguments are mapped onto the counter by two's complement without a range check, so every test vector above is reachable.
+ * spk_noise_fill: one launch fills the planes of n_layers layers: layer l (id layer0 + l) takes the next B*hw[l] floats of dst, laid out
+ *   [b][p]; batch row b is frame frame0 + b*frame_step (frame_step 1: fresh noise per frame; 0: fixed noise, every row that of
+ *   frame0).  A thread owns one block = four consecutive pixels of one row: one float4 store where every plane length of the
+ *   launch is a multiple of 4 and dst is 16-byte aligned, scalar stores with a tail otherwise.  Refused before any launch
+ *   (SPK_EINVAL): a null dst, B < 1, n_layers outside [1, SPK_NOISE_MAX_LAYERS], hw < 1 (or > 2^34: q is 32 bits), a negative
+ *   frame0 / layer0 / frame_step, a frame_step other than 0 or 1. */
+#define SPK_NOISE_MAX_LAYERS 16
+typedef struct spk_noise_fill_args {
+    float* dst;
+    uint64_t seed;
+    int64_t frame0;
+    int32_t B, frame_step, n_layers, layer0;
+    int64_t hw[SPK_NOISE_MAX_LAYERS];
+} spk_noise_fill_args;
+int spk_noise_bits_host(uint64_t seed, int64_t frame, int32_t layer, uint32_t q, uint32_t out[4]);
+int spk_noise_fill(const spk_noise_fill_args* args, void* stream);
+
 /* ---- launch lists: a whole module forward per C call ---------------------------------------------------------------
  * The reference's callers run a decoder pass as one Python call (model.py:113-114 `self.Gd(gen_input)`,
  * styleganv1.py:593-610 SynthesisNetwork.forward); behind it sit ~25 kernel launches whose descriptors depend only on
@@ -663,7 +703,9 @@ enum {
     SPK_OP_MAXPOOL3X3S2 = 9,      /* desc: spk_maxpool3x3s2_args    -> spk_maxpool3x3s2_fwd (resnet50.maxpool, model.py:62) */
     SPK_OP_GLOBAL_AVGPOOL = 10,   /* desc: spk_global_avgpool_args  -> spk_global_avgpool_fwd (resnet50.avgpool): with the two kinds a
                                    * whole BatchNorm-folded trunk pass is one list */
-    SPK_OP_FRAMES_TO_U8 = 11      /* desc: spk_frames_to_u8_args    -> spk_frames_f32_to_u8 (a decoder plan that ends in uint8 HWC frames) */
+    SPK_OP_FRAMES_TO_U8 = 11,     /* desc: spk_frames_to_u8_args    -> spk_frames_f32_to_u8 (a decoder plan that ends in uint8 HWC frames) */
+    SPK_OP_NOISE_FILL = SPK_OP_FRAMES_TO_U8 + 1   /* = 12.  desc: spk_noise_fill_args -> spk_noise_fill (the first op of a seeded
+                                   * decoder plan: with it the forward holds no launch outside the list) */
 };
 typedef struct spk_op { int32_t kind; int32_t reserved; const void* desc; } spk_op;
 typedef struct spk_fc_args {

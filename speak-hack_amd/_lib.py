@@ -87,7 +87,16 @@ class DemodGroup(C.Structure):
 OP_CONV2D, OP_FC, OP_FC_GROUPED, OP_BIAS_NOISE_STYLE, OP_TORGB, OP_DEMOD_GROUPED, OP_PIXELNORM, OP_UPSAMPLE2X = 1, 2, 3, 4, 5, 6, 7, 8
 OP_MAXPOOL3X3S2, OP_GLOBAL_AVGPOOL = 9, 10
 OP_FRAMES_TO_U8 = 11
+OP_NOISE_FILL = 12
 ALL_OPS = 0xFFFFFFFF
+
+NOISE_MAX_LAYERS = 16
+
+
+class NoiseFillArgs(C.Structure):
+    """``spk_noise_fill_args`` (include/spk.h)."""
+    _fields_ = [("dst", C.c_void_p), ("seed", C.c_uint64), ("frame0", C.c_int64), ("B", C.c_int32), ("frame_step", C.c_int32),
+                ("n_layers", C.c_int32), ("layer0", C.c_int32), ("hw", C.c_int64 * NOISE_MAX_LAYERS)]
 
 
 class Op(C.Structure):
@@ -280,6 +289,8 @@ _PROTOTYPES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
     "spk_frames_f32_to_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "spk_noise_bits_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "spk_noise_fill": (C.c_int, [C.POINTER(NoiseFillArgs), C.c_void_p]),
 }
 
 _lib = None

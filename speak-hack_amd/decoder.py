@@ -151,18 +151,32 @@ class SynthesisNetwork(nn.Module):
     def _inference(self, x):
         return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
 
-    def forward(self, w, noises=None):
+    def forward(self, w, noises=None, *, seed=None, frame0=0, fixed_noise=False):
         """``w``: [B, num_layers, 512]; ``noises``: optional list of the 2*len(layers)+1 noise
-        tensors in call order (drawn on the device when omitted, as the reference does)."""
+        tensors in call order (drawn on the device when omitted, as the reference does).  ``seed`` (0 <= seed < 2**64; not
+        together with ``noises``): the noise is ``ops.decoder_noise(self.noise_shapes(B), seed, frame0=frame0,
+        fixed=fixed_noise)`` -- a function of (seed, frame0 + row, layer, pixel), the device generator untouched -- drawn
+        inside the launch list of a seeded plan."""
         B = w.size(0)
         w = w.contiguous()
         if noises is not None and len(noises) != 2 * len(self.layers) + 1:
             raise ValueError(f"expected {2 * len(self.layers) + 1} noise tensors, got {len(noises)}")
+        if seed is not None:
+            if noises is not None:
+                raise ValueError("pass either seed or noises, not both")
+            ops.check_seed(seed, frame0)
+        elif fixed_noise:
+            raise ValueError("fixed_noise needs a seed")
         if self.use_plan and w.is_cuda and len(self.layers) * 2 + 1 <= ops.L.FC_MAX_GROUPS and self._inference(w):
             key = (B, w.device, torch.cuda.current_stream(w.device).cuda_stream, "w", self.precision)
-            p = PL.plan_for(self, key, lambda: PL.DecoderPlan(self, B, w.device, precision=self.precision))
-            return p.run(w, None if noises is None else [n.contiguous() for n in noises])
-        if noises is None:
+            if seed is None:
+                p = PL.plan_for(self, key, lambda: PL.DecoderPlan(self, B, w.device, precision=self.precision))
+                return p.run(w, None if noises is None else [n.contiguous() for n in noises])
+            p = PL.plan_for(self, key + ("seeded",), lambda: PL.DecoderPlan(self, B, w.device, precision=self.precision, seeded=True))
+            return p.run(w, seed=seed, frame0=frame0, fixed_noise=fixed_noise)
+        if seed is not None:
+            noises = ops.decoder_noise(self.noise_shapes(B), seed, frame0=frame0, fixed=fixed_noise, device=w.device)
+        elif noises is None:
             # one device draw for the whole step, cut into the 13 per-layer tensors (the reference draws them one by
             # one inside ApplyNoise.forward, styleganv1.py:455; device RNG streams are not comparable across
             # implementations anyway -- parity tests pass explicit noise)
@@ -230,15 +244,16 @@ class StyleGenerator(nn.Module):
         self.bn = None
         self.logger = logging.getLogger(__name__)
 
-    def forward(self, features, noises=None, style_mix=None):
+    def forward(self, features, noises=None, style_mix=None, *, seed=None, frame0=0, fixed_noise=False):
         """``style_mix`` (optional, tests): ``(mix_features, mix_layer)`` replacing the three RNG draws of the
-        train-mode mixing branch, or ``False`` to skip the branch."""
+        train-mode mixing branch, or ``False`` to skip the branch.  ``seed`` / ``frame0`` / ``fixed_noise``: seeded noise, as
+        ``SynthesisNetwork.forward`` takes them."""
         L = self.synthesis.num_layers
         syn = self.synthesis
         if (not self.training and self.plan_serves(features)
                 and not (torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in self.parameters())))):
             # eval + no gradient: mapping, truncation and synthesis as ONE launch list (one crossing of the C boundary)
-            return self.plan_forward(features, noises)
+            return self.plan_forward(features, noises, seed=seed, frame0=frame0, fixed_noise=fixed_noise)
         w = self.mapping(features).unsqueeze(1).repeat(1, L, 1)
         if self.truncation_psi and self.truncation_cutoff:
             coefs = torch.ones_like(w)
@@ -254,30 +269,44 @@ class StyleGenerator(nn.Module):
                     # in place and under no_grad, as the reference: autograd never sees the overwrite, so the
                     # gradient of the mixed rows still flows into the first mapping pass (a reference quirk)
                     w[:, mix_layer:] = w2[:, mix_layer:]
-        return self.synthesis(w, noises)
+        return self.synthesis(w, noises, seed=seed, frame0=frame0, fixed_noise=fixed_noise)
 
     def plan_serves(self, features):
         """Whether the inference launch plan can run these features (``plan_forward``)."""
         syn = self.synthesis
         return syn.use_plan and features.is_cuda and features.dim() == 2 and len(syn.layers) * 2 + 1 <= ops.L.FC_MAX_GROUPS
 
-    def plan_forward(self, features, noises=None, *, output="f32", value_range=(-1, 1), swap_rb=False):
+    def plan_forward(self, features, noises=None, *, output="f32", value_range=(-1, 1), swap_rb=False, seed=None, frame0=0,
+                     fixed_noise=False):
         """The eval forward -- mapping, truncation, synthesis; no style mixing, no host-RNG draw -- on the inference launch plan,
         whatever ``self.training`` is (no module state is read or touched).  No gradient flows through it.  ``output="uint8"``:
-        the plan ends in the quantising op and returns uint8 [B,R,R,3] frames (``plan.DecoderPlan``)."""
+        the plan ends in the quantising op and returns uint8 [B,R,R,3] frames (``plan.DecoderPlan``).  ``seed``: a seeded plan
+        (a cache entry of its own) draws the noise of ``ops.decoder_noise(shapes, seed, frame0=frame0, fixed=fixed_noise)`` as
+        the first op of its list."""
         syn = self.synthesis
         if noises is not None and len(noises) != 2 * len(syn.layers) + 1:
             raise ValueError(f"expected {2 * len(syn.layers) + 1} noise tensors, got {len(noises)}")
+        if seed is not None:
+            if noises is not None:
+                raise ValueError("pass either seed or noises, not both")
+            ops.check_seed(seed, frame0)
+        elif fixed_noise:
+            raise ValueError("fixed_noise needs a seed")
         B = features.size(0)
         # (the truncation scale is folded into the style FCs' multipliers when the plan is built: part of the key)
         key = (B, features.device, torch.cuda.current_stream(features.device).cuda_stream, "features", syn.precision,
                self.truncation_psi, self.truncation_cutoff)
         if output != "f32":
             key += (output, float(value_range[0]), float(value_range[1]), bool(swap_rb))
+        if seed is not None:
+            key += ("seeded",)
         p = PL.plan_for(self, key, lambda: PL.DecoderPlan(syn, B, features.device, generator=self, precision=syn.precision,
-                                                          output=output, value_range=value_range, swap_rb=swap_rb))
-        return p.run(features if features.stride(1) == 1 else features.contiguous(),
-                     None if noises is None else [n.contiguous() for n in noises])
+                                                          output=output, value_range=value_range, swap_rb=swap_rb,
+                                                          seeded=seed is not None))
+        features = features if features.stride(1) == 1 else features.contiguous()
+        if seed is not None:
+            return p.run(features, seed=seed, frame0=frame0, fixed_noise=fixed_noise)
+        return p.run(features, None if noises is None else [n.contiguous() for n in noises])
 
     def forward_pair(self, features_a, features_b, noises_a=None, noises_b=None):
         """``(self(features_a, noises_a), self(features_b, noises_b))`` as ONE pass over the concatenated batch -- the two

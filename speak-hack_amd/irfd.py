@@ -92,7 +92,8 @@ class IRFD(nn.Module):
         return PL.plan_for(trunk, key, lambda: PL.EncoderPlan(trunk, B, H, W, images.device)).run(images)
 
     @torch.no_grad()
-    def reenact(self, identity_image, pose_frames, emotion_frames=None, *, noises=None, chunk=8, output="f32", channel_order="rgb"):
+    def reenact(self, identity_image, pose_frames, emotion_frames=None, *, noises=None, chunk=8, output="f32", channel_order="rgb",
+                seed=None, noise="fresh", frame0=0):
         """Talking-head frames: ``Gd(cat(Ei(identity).expand(T), Ee(emotion_frames), Ep(pose_frames)))`` in the feature order
         of ``_prepare_generator_input(fi, fe, fp)`` (model.py:64-69,107), in eval arithmetic whatever ``self.training`` is: no
         buffer update, no host-RNG draw, no swap, no style mixing, truncation as ``StyleGenerator.forward`` applies it in eval.
@@ -100,9 +101,26 @@ class IRFD(nn.Module):
         explicit list ``StyleGenerator.forward`` takes, for T frames (default: drawn on the device).  ``Ei`` runs once; the
         frames go through the encoder and decoder plans ``chunk`` at a time.  -> frames [T,3,R,R] fp32; with ``output="uint8"``
         uint8 [T,R,R,3] in ``channel_order`` ("rgb" | "bgr"), quantised from (-1, 1) by the last op of the decoder plan --
-        ``ops.frames_to_u8`` of the fp32 result, bit for bit."""
+        ``ops.frames_to_u8`` of the fp32 result, bit for bit.
+
+        ``seed`` (0 <= seed < 2**64; not together with ``noises``): reproducible noise, a function of (seed, frame index,
+        layer, pixel) drawn inside the decoder's launch list (``ops.decoder_noise`` gives the same tensors explicitly); the
+        device generator is not touched.  Frame ``t`` of the clip has frame index ``frame0 + t`` whatever ``chunk`` is, so
+        frames ``[a, b)`` of a longer clip may be rendered elsewhere with ``frame0=a``.  ``noise="fixed"`` (needs a seed): every
+        frame uses frame index ``frame0`` -- one noise image per layer held over the clip, as StyleGAN video pipelines do
+        against boiling texture; ``"fresh"`` (default): new noise on every frame."""
         if output not in ("f32", "uint8"):
             raise ValueError(f"reenact: output must be 'f32' or 'uint8', got {output!r}")
+        if noise not in ("fresh", "fixed"):
+            raise ValueError(f"reenact: noise must be 'fresh' or 'fixed', got {noise!r}")
+        if seed is None and noise == "fixed":
+            raise ValueError("reenact: noise='fixed' needs a seed")
+        if seed is not None:
+            if noises is not None:
+                raise ValueError("reenact: pass either seed or noises, not both")
+            ops.check_seed(seed, frame0, "reenact: seed")
+        elif frame0 != 0:
+            raise ValueError("reenact: frame0 applies to seeded noise only")
         if channel_order not in ("rgb", "bgr"):
             raise ValueError(f"reenact: channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
         if output == "f32" and channel_order != "rgb":
@@ -126,34 +144,47 @@ class IRFD(nn.Module):
             t1 = min(T, t0 + chunk)
             fe, fp = self.encode(emotion_frames[t0:t1], "Ee"), self.encode(pose_frames[t0:t1], "Ep")
             gin = self._prepare_generator_input(fi.expand(t1 - t0, -1, -1, -1), fe, fp)
-            out.append(self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises], output, channel_order))
+            seeded = None if seed is None else dict(seed=seed, frame0=frame0 if noise == "fixed" else frame0 + t0, fixed_noise=noise == "fixed")
+            out.append(self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises], output, channel_order, seeded))
         return out[0] if len(out) == 1 else torch.cat(out, 0)
 
     @torch.no_grad()
-    def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8):
+    def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8,
+                      seed=None, noise="fresh", frame0=0):
         """``reenact`` from and to video frames as a decoder and a video writer hold them (inference.py:29-33,46-58,78-86):
         uint8 HWC frames of any size on the device in, uint8 [T,R,R,3] out, both in ``channel_order`` ("bgr": ``cv2``'s).
         Nothing but ``ops.frames_from_u8`` -> ``reenact(output="uint8")``: ``identity_u8`` [H,W,3] or [1,H,W,3] is resized whole
         to ``size``; ``pose_u8`` / ``emotion_u8`` [T,H,W,3] are cropped to ``crop=(y0, x0, h, w)`` (one box for all frames) and
-        resized; ``emotion_u8=None``: the pose frames, resized once."""
+        resized; ``emotion_u8=None``: the pose frames, resized once.  ``seed`` / ``noise`` / ``frame0``: as ``reenact``."""
+        if noise not in ("fresh", "fixed"):
+            raise ValueError(f"reenact_video: noise must be 'fresh' or 'fixed', got {noise!r}")
+        if seed is None and noise == "fixed":
+            raise ValueError("reenact_video: noise='fixed' needs a seed")
+        if seed is not None:
+            if noises is not None:
+                raise ValueError("reenact_video: pass either seed or noises, not both")
+            ops.check_seed(seed, frame0, "reenact_video: seed")
         ident = ops.frames_from_u8(identity_u8, size, channel_order=channel_order)
         pose = ops.frames_from_u8(pose_u8, size, crop=crop, channel_order=channel_order)
         emo = None if emotion_u8 is None else ops.frames_from_u8(emotion_u8, size, crop=crop, channel_order=channel_order)
-        return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output="uint8", channel_order=channel_order)
+        return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output="uint8", channel_order=channel_order, seed=seed,
+                            noise=noise, frame0=frame0)
 
-    def _decode_eval(self, gin, noises, output="f32", channel_order="rgb"):
+    def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None):
         """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan
-        does not serve runs its eval branch with every submodule's own ``training`` flag saved and put back."""
+        does not serve runs its eval branch with every submodule's own ``training`` flag saved and put back.  ``seeded``: the
+        ``seed`` / ``frame0`` / ``fixed_noise`` keywords of a seeded call (``StyleGenerator`` decoders), else None."""
         Gd = self.Gd
+        seeded = seeded or {}
         if hasattr(Gd, "plan_serves") and Gd.plan_serves(gin):
             if output == "f32":
-                return Gd.plan_forward(gin, noises)
-            return Gd.plan_forward(gin, noises, output=output, swap_rb=channel_order == "bgr")
+                return Gd.plan_forward(gin, noises, **seeded)
+            return Gd.plan_forward(gin, noises, output=output, swap_rb=channel_order == "bgr", **seeded)
         flags = [(mod, mod.training) for mod in Gd.modules()]
         try:
             for mod, _ in flags:
                 mod.training = False
-            y = Gd(gin, noises)
+            y = Gd(gin, noises, **seeded)
         finally:
             for mod, was in flags:
                 mod.training = was

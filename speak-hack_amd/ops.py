@@ -1533,3 +1533,52 @@ def frames_to_u8(x, *, value_range=(-1, 1), channel_order="rgb", out=None):
         raise L.SpkError(f"out: expected a contiguous uint8 HIP tensor {(N, H, W, 3)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
     L.check(L.lib().spk_frames_f32_to_u8(xp, out.data_ptr(), N, H, W, swap, lo, k, L.stream_ptr()), "spk_frames_f32_to_u8")
     return out
+
+
+# ---- counter-based decoder noise (csrc/noise.hip; the definition is in include/spk.h) ---------------------------------------
+def check_seed(seed, frame0=0, what="seed"):
+    """A noise seed is an integer in [0, 2**64); a frame index a non-negative integer below 2**62.  -> (seed, frame0)."""
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{what} must be an integer with 0 <= seed < 2**64, got {seed!r}")
+    if isinstance(frame0, bool) or not isinstance(frame0, int) or not 0 <= frame0 < 2 ** 62:
+        raise ValueError(f"frame0 must be an integer with 0 <= frame0 < 2**62, got {frame0!r}")
+    return seed, frame0
+
+
+def noise_fill_args(dst_ptr, hw, B, *, seed=0, frame0=0, fixed=False, layer0=0):
+    """``spk_noise_fill_args`` for planes of ``hw[l]`` pixels (layer ids ``layer0 + l``), ``B`` rows each."""
+    hw = [int(v) for v in hw]
+    if not 1 <= len(hw) <= L.NOISE_MAX_LAYERS:
+        raise L.SpkError(f"noise_fill: between 1 and {L.NOISE_MAX_LAYERS} layers per launch, got {len(hw)}")
+    a = L.NoiseFillArgs(dst=dst_ptr, seed=seed, frame0=frame0, B=B, frame_step=0 if fixed else 1, n_layers=len(hw), layer0=layer0)
+    for l, v in enumerate(hw):
+        a.hw[l] = v
+    return a
+
+
+def noise_fill(dst, hw, B, seed, *, frame0=0, fixed=False, layer0=0):
+    """Fill ``dst`` (a float32 HIP tensor of ``B * sum(hw)`` elements, any 4-byte alignment) with the noise of layers
+    ``layer0 .. layer0 + len(hw) - 1``, layer ``l`` laid out ``[B, hw[l]]`` after the layers before it, in ONE launch
+    (``spk_noise_fill``): row ``b`` is frame ``frame0 + b``, or frame ``frame0`` in every row with ``fixed``.  -> ``dst``."""
+    seed, frame0 = check_seed(seed, frame0)
+    if dst.numel() != B * sum(int(v) for v in hw):
+        raise L.SpkError(f"noise_fill: dst holds {dst.numel()} floats, the layers need {B * sum(int(v) for v in hw)}")
+    a = noise_fill_args(L.dptr(dst, "dst"), hw, B, seed=seed, frame0=frame0, fixed=fixed, layer0=layer0)
+    L.check(L.lib().spk_noise_fill(C.byref(a), L.stream_ptr()), "spk_noise_fill")
+    return dst
+
+
+def decoder_noise(shapes, seed, *, frame0=0, fixed=False, device):
+    """The explicit noise list of a decoder pass from a seed: ``shapes`` is what ``SynthesisNetwork.noise_shapes(B)`` returns;
+    -> the list of [B,1,H,W] tensors (views of one flat buffer, one launch) whose value at row ``b``, layer ``l``, pixel ``p`` is
+    the function of ``(seed, frame0 + b, l, p)`` include/spk.h defines -- ``fixed``: frame ``frame0`` in every row.  What a
+    seeded plan (``plan.DecoderPlan(seeded=True)``) draws inside its launch list, bit for bit."""
+    seed, frame0 = check_seed(seed, frame0)
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    if not shapes or any(len(s) != 4 or s[1] != 1 or s[0] != shapes[0][0] for s in shapes):
+        raise ValueError(f"decoder_noise: shapes must be [B,1,H,W] with one B, got {shapes}")
+    B = shapes[0][0]
+    hw = [s[2] * s[3] for s in shapes]
+    flat = torch.empty(B * sum(hw), device=device, dtype=torch.float32)
+    noise_fill(flat, hw, B, seed, frame0=frame0, fixed=fixed)
+    return [t.view(s) for t, s in zip(flat.split([B * v for v in hw]), shapes)]

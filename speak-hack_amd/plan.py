@@ -172,15 +172,21 @@ class DecoderPlan(LaunchPlan):
     truncation (styleganv1.py:528-543): 8 FC launches (with the mapping), one grouped launch for the 13+ style affines,
     the constant prologue, 2 fused conv launches per block, toRGB.  ``output="uint8"``: the fp32 frame goes to a plan-owned
     buffer and one more op (``SPK_OP_FRAMES_TO_U8``) quantises it from ``value_range`` into the uint8 [B,R,R,3] frames
-    ``run`` returns (``swap_rb``: B, G, R order) -- what ``ops.frames_to_u8`` makes of the fp32 result, bit for bit."""
+    ``run`` returns (``swap_rb``: B, G, R order) -- what ``ops.frames_to_u8`` makes of the fp32 result, bit for bit.
+    ``seeded=True``: the list starts with ``SPK_OP_NOISE_FILL`` (csrc/noise.hip), which writes ``noise_flat`` from the
+    ``seed`` / ``frame0`` each ``run`` patches into its descriptor -- the noise of ``ops.decoder_noise``, bit for bit, and the
+    forward is the launch list alone (no ATen draw, the device generator untouched).  A seeded plan runs seeded calls only, an
+    unseeded one (the default: built and run exactly as before) unseeded calls only."""
 
-    def __init__(self, synthesis, B, device, generator=None, precision="f32", output="f32", value_range=(-1, 1), swap_rb=False):
+    def __init__(self, synthesis, B, device, generator=None, precision="f32", output="f32", value_range=(-1, 1), swap_rb=False,
+                 seeded=False):
         super().__init__(device)
         if output not in ("f32", "uint8"):
             raise ValueError(f"DecoderPlan: output must be 'f32' or 'uint8', got {output!r}")
         s = self.synthesis = synthesis
         self.precision = precision
         self.output = output
+        self.seeded = bool(seeded)
         self.B, self.with_mapping = B, generator is not None
         mods = [s.style_mod] + [m for layer in s.layers for m in (layer.style_mod1, layer.style_mod2)]
         if len(mods) > L.FC_MAX_GROUPS:
@@ -219,6 +225,10 @@ class DecoderPlan(LaunchPlan):
         sizes = [sh[0] * sh[2] * sh[3] for sh in shapes]
         self.noise_flat = self.buf(sum(sizes))
         self.noise_views = [t.view(sh) for t, sh in zip(self.noise_flat.split(sizes), shapes)]
+        self.noise_fill = None
+        if self.seeded:        # the draw is the FIRST op of the list; seed / frame0 / frame_step are patched per call
+            self.noise_fill = ops.noise_fill_args(self.noise_flat.data_ptr(), [sh[2] * sh[3] for sh in shapes], B)
+            self.ops.insert(0, (L.OP_NOISE_FILL, self.noise_fill))
         # ---- prologue (styleganv1.py:596-599) ----
         C0 = s.const_input.shape[1]
         pp = [self.buf(B * max(self._act_floats(s)))  for _ in range(2)]
@@ -288,8 +298,17 @@ class DecoderPlan(LaunchPlan):
             sizes.append(layer.out_channels * res * res)
         return sizes
 
-    def run(self, x, noises=None, kind_mask=L.ALL_OPS):
-        """``x``: features [B,input_dim] (plan built with the generator) or dlatents w [B,L,512]."""
+    def run(self, x, noises=None, kind_mask=L.ALL_OPS, *, seed=None, frame0=0, fixed_noise=False):
+        """``x``: features [B,input_dim] (plan built with the generator) or dlatents w [B,L,512].  A seeded plan takes ``seed``
+        (0 <= seed < 2**64), ``frame0`` (row b is frame ``frame0 + b``) and ``fixed_noise`` (every row is frame ``frame0``) and
+        patches them into the noise op's descriptor, as pointers are patched; ``seed`` together with ``noises`` is a
+        ``ValueError``.  A hipGraph capture of a seeded run bakes ``seed`` and ``frame0`` into the graph, as it bakes addresses:
+        every replay draws the noise of the captured call."""
+        if seed is not None and noises is not None:
+            raise ValueError("DecoderPlan.run: pass either seed or noises, not both")
+        if self.seeded != (seed is not None):
+            raise ValueError("DecoderPlan.run: a seeded plan needs a seed (and no explicit noise)" if self.seeded else
+                             "DecoderPlan.run: seed given to an unseeded plan (build it with seeded=True)")
         self.refresh()
         self.captured = self.captured or torch.cuda.is_current_stream_capturing()
         if self.with_mapping:
@@ -304,7 +323,11 @@ class DecoderPlan(LaunchPlan):
             base, row, bs = x.data_ptr(), x.stride(1) * 4, x.stride(0)
             for j, g in enumerate(self.style_groups):
                 g.x, g.x_stride = base + j * row, bs
-        if noises is None:
+        if self.seeded:
+            a = self.noise_fill         # (the 13 noise pointers stay on noise_views: a seeded plan never sees explicit noise)
+            a.seed, a.frame0 = ops.check_seed(seed, frame0)
+            a.frame_step = 0 if fixed_noise else 1
+        elif noises is None:
             self.noise_flat.normal_()
             for d, nv in zip(self.noise_ops, self.noise_views):
                 d.noise = nv.data_ptr()

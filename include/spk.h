@@ -632,7 +632,31 @@ int spk_plane_sums_reduce(const float* sums, int B, int rows, int C, int row, fl
  * spk_frames_f32_to_u8: quantise + CHW -> HWC: dst[n,y,x,c'] = rint(min(max((src[n,c,y,x] - lo) * k, 0), 255)) in that order
  *   of fp32 operations (ties to even; NaN -> 0), k = 255 / (hi - lo) rounded to fp32 by the caller; src [N,3,H,W] contiguous,
  *   dst uint8 [N,H,W,3] contiguous at any byte address.  replaces: inference.py:78-86 (save_video's scaling, cast, transpose
- *   and cvtColor; the reference multiplies by 255 without offset or clamp, which wraps on a tanh-range frame). */
+ *   and cvtColor; the reference multiplies by 255 without offset or clamp, which wraps on a tanh-range frame).
+ * spk_frames_u8_to_f32_boxes: spk_frames_u8_to_f32 for a box that moves: src is the origin of N frames of H x W pixels (strides
+ *   in bytes as above) and boxes_yx a DEVICE int32 [N][2] array of (y0, x0), frame n's Hin x Win box, as a tracker on the device
+ *   leaves it (no host round trip).  Each origin is clamped into [0, H - Hin] x [0, W - Win], so the box always lies in the
+ *   frame; H >= Hin and W >= Win.  The same kernel body and arithmetic: for in-frame origins the result of frame n is the
+ *   result of spk_frames_u8_to_f32 on that box, bit for bit.
+ * spk_feather_table: the 1-D edge ramp of a pasted box, built in fp64 on the HOST and rounded to fp32:
+ *     a[i] = min(1, (min(i, n - 1 - i) + 1) / (feather + 1)),  i < n;  feather >= 0 a real number, 0 gives all ones.
+ * spk_frames_paste_u8: the inverse of the crop: resize N generated frames src [N,3,Hs,Ws] (fp32, contiguous) to the box size
+ *   h x w, quantise, feather-blend into the uint8 frames the boxes came from, CHW -> HWC, in one launch without allocation or
+ *   synchronisation.  dst: N frames of H x W pixels that already hold the background, pixel stride 3, image_stride / row_stride
+ *   in BYTES, any byte address (N > 1: image_stride >= (H - 1) row_stride + 3 W, the frames must not overlap).  Frame n's box
+ *   starts at (Y0_n, X0_n) = (y0, x0), or at boxes_yx[n] when boxes_yx (a DEVICE int32 [N][2] array) is not NULL.  For box
+ *   pixel (y, x), channel c, c' = swap_rb ? 2 - c : c:
+ *     v  = sum_iy sum_ix w_y[y,iy] w_x[x,ix] src[n,c,iy,ix]                     fp64 sums
+ *     q  = min(max(((float)v - lo) * k, 0), 255)                               fp32 in that order, as spk_frames_f32_to_u8 (NaN -> 0)
+ *     b  = dst[n, Y0_n + y, X0_n + x, c']                                      the background byte
+ *     m  = a_y[y] * a_x[x]                                                     the fp32 tables promoted to fp64
+ *     dst[n, Y0_n + y, X0_n + x, c'] = (uint8) rint(fma(m, q - b, b))          fp64, ties to even
+ *   The six resize tables are DEVICE copies of spk_resize_table's for Hs -> h and Ws -> w (antialiased: shrinking and
+ *   enlarging); a_y [h] / a_x [w] are DEVICE copies of spk_feather_table's, both NULL: m = 1.  With identity tables and no
+ *   feather the result is spk_frames_f32_to_u8's bit for bit.  Every box pixel outside the H x W frame is SKIPPED: no origin,
+ *   however wrong, causes an out-of-bounds access.  A thread reads the one background byte it overwrites, so pasting in place
+ *   has no hazard.  replaces: interpolate + mask + blend + round + to(uint8) + permute on fp32 copies of full-size frames at
+ *   inference.py:78-86. */
 int spk_resize_table_taps(int n_in, int n_out);
 int spk_resize_table(int n_in, int n_out, int taps, int32_t* first_host, int32_t* count_host, double* w_host, float* w_f32_host);
 int spk_frames_u8_to_f32(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int Hin, int Win, int swap_rb,
@@ -640,6 +664,15 @@ int spk_frames_u8_to_f32(const uint8_t* src, int64_t image_stride, int64_t row_s
                          const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout, float scale0,
                          float scale1, float scale2, float shift0, float shift1, float shift2, void* stream);
 int spk_frames_f32_to_u8(const float* src, uint8_t* dst, int N, int H, int W, int swap_rb, float lo, float k, void* stream);
+int spk_frames_u8_to_f32_boxes(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int H, int W, const int32_t* boxes_yx,
+                               int Hin, int Win, int swap_rb, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
+                               const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout,
+                               float scale0, float scale1, float scale2, float shift0, float shift1, float shift2, void* stream);
+int spk_feather_table(int n, double feather, float* a_host);
+int spk_frames_paste_u8(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W,
+                        int h, int w, int y0, int x0, const int32_t* boxes_yx, int swap_rb, const int32_t* first_y, const int32_t* count_y,
+                        const float* w_y, int taps_y, const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x,
+                        const float* a_y, const float* a_x, float lo, float k, void* stream);
 
 /* ---- counter-based decoder noise (csrc/noise.hip) ----------------------------------------------------------------------------
  * The noise planes of a synthesis pass as a pure function of (seed, frame, layer, pixel): no generator state, so a clip comes

@@ -4,7 +4,9 @@
 // the host, and inference.py:78-86 turns the result back into uint8 HWC for the video writer.  On the device that edge is a
 // chain of eleven ATen launches per chunk and fp32 traffic over the host link; here it is two kernels:
 //   frames_u8_to_f32: crop (pointer + strides) + antialiased bilinear resize + normalise + HWC -> CHW, one pass, no scratch;
-//   frames_f32_to_u8: quantise + CHW -> HWC, one pass.
+//   frames_f32_to_u8: quantise + CHW -> HWC, one pass;
+//   frames_paste_u8: the inverse of the crop -- resize to the box + quantise + feather-blend into the uint8 frame the box came
+//   from + CHW -> HWC, one pass, the box origin per frame (by value, or from a device array a tracker wrote).
 // The resize is separable and table driven: the taps of both axes come from the caller (spk_resize_table, built in fp64 on
 // the host), so the kernel holds no filter arithmetic.
 #include "spk_common.hpp"
@@ -79,8 +81,11 @@ struct Affine3 { float scale[3], shift[3]; };
 // into the accumulators of the output rows whose window holds the row.  Sums are kept in fp64 (full-rate FMA on this chip, and
 // the kernel is bound by its byte loads): with rows that sum to exactly 1 a constant frame comes out as that constant, and the
 // longest chain of one output is taps_x + taps_y additions.  No LDS, no scratch; horizontal work is redone only where the
-// windows of neighbouring strips overlap.
+// windows of neighbouring strips overlap.  BOXES: src is the frame origin and the Hin x Win box of frame n starts at
+// boxes_yx[n] = (y0, x0), clamped so that the box stays inside the H x W frame (a tracker's box cannot send a load out of bounds).
+template <bool BOXES>
 __global__ __launch_bounds__(256) void frames_u8_to_f32_kernel(const uint8_t* __restrict__ src, long long image_stride, long long row_stride,
+                                                               const int* __restrict__ boxes_yx, int H, int W,
                                                                int Hin, int Win, int swap_rb, const int* __restrict__ first_y,
                                                                const int* __restrict__ count_y, const float* __restrict__ w_y, int taps_y,
                                                                const int* __restrict__ first_x, const int* __restrict__ count_x,
@@ -107,6 +112,10 @@ __global__ __launch_bounds__(256) void frames_u8_to_f32_kernel(const uint8_t* __
 #pragma unroll
         for (int k = 0; k < STRIP; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
         const uint8_t* img = src + n * image_stride + (long long)fx * 3;
+        if (BOXES) {
+            const int y0 = min(max(boxes_yx[2 * n], 0), H - Hin), x0 = min(max(boxes_yx[2 * n + 1], 0), W - Win);
+            img += (long long)y0 * row_stride + (long long)x0 * 3;
+        }
         const float* wx = w_x + (long long)ox * taps_x;
         for (int iy = row_lo; iy < row_hi; ++iy) {
             const uint8_t* p = img + (long long)iy * row_stride;
@@ -194,6 +203,62 @@ __global__ __launch_bounds__(256) void frames_f32_to_u8_kernel(const float* __re
     }
 }
 
+// The inverse of the crop.  A thread owns one pixel (y, x) of the h x w box of one frame, all three channels (x fastest: a wave
+// writes 192 consecutive bytes of a frame row).  It resizes the fp32 source to its pixel with the same tables and the same fp64
+// sums as the input kernel (an enlarging box has at most 2 x 2 taps), quantises in the fp32 order of quant_u8 without the
+// rounding, reads the background byte it is about to overwrite -- and no other, so the frames may be pasted in place --
+// and stores rint(b + m (q - b)) in fp64 (one fused multiply-add), m = a_y[y] a_x[x] the feather (both tables null: m = 1).  The box origin is
+// (y0, x0) or, with boxes_yx, frame n's pair of a device array; frame coordinates are formed in 64 bits and every pixel that
+// falls outside the H x W frame is skipped, so no origin can send a store (or the load in front of it) out of bounds.  The
+// frames are byte addressed at any offset (3 * X0 + row_stride * Y0 has no alignment), so loads and stores are bytes.
+__global__ __launch_bounds__(256) void frames_paste_u8_kernel(const float* __restrict__ src, int Hs, int Ws, uint8_t* dst, long long image_stride,
+                                                              long long row_stride, int H, int W, int h, int w, int y0, int x0,
+                                                              const int* __restrict__ boxes_yx, int swap_rb, const int* __restrict__ first_y,
+                                                              const int* __restrict__ count_y, const float* __restrict__ w_y, int taps_y,
+                                                              const int* __restrict__ first_x, const int* __restrict__ count_x,
+                                                              const float* __restrict__ w_x, int taps_x, const float* __restrict__ a_y,
+                                                              const float* __restrict__ a_x, float lo, float k, long long total) {
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(idx % w);
+        const int y = (int)((idx / w) % h);
+        const long long n = idx / ((long long)w * h);
+        const long long Y = (long long)(boxes_yx ? boxes_yx[2 * n] : y0) + y, X = (long long)(boxes_yx ? boxes_yx[2 * n + 1] : x0) + x;
+        if (Y < 0 || Y >= H || X < 0 || X >= W) continue;
+        // the tables are the caller's: clamp every window into the source so that no table can send a load out of bounds
+        const int fx = min(max(first_x[x], 0), Ws - 1), cx = max(min(min(count_x[x], taps_x), Ws - fx), 0);
+        const int fy = min(max(first_y[y], 0), Hs - 1), cy = max(min(min(count_y[y], taps_y), Hs - fy), 0);
+        const float* wx = w_x + (long long)x * taps_x;
+        const float* wy = w_y + (long long)y * taps_y;
+        const long long plane = (long long)Hs * Ws;
+        const float* in = src + n * 3 * plane + (long long)fy * Ws + fx;
+        double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+        for (int i = 0; i < cy; ++i) {
+            const float* p = in + (long long)i * Ws;
+            double h0 = 0.0, h1 = 0.0, h2 = 0.0;
+            for (int j = 0; j < cx; ++j) {
+                const double wj = (double)wx[j];
+                h0 = fma(wj, (double)p[j], h0);
+                h1 = fma(wj, (double)p[plane + j], h1);
+                h2 = fma(wj, (double)p[2 * plane + j], h2);
+            }
+            const double wi = (double)wy[i];
+            v0 = fma(wi, h0, v0);
+            v1 = fma(wi, h1, v1);
+            v2 = fma(wi, h2, v2);
+        }
+        const double m = a_y ? (double)a_y[y] * (double)a_x[x] : 1.0;
+        uint8_t* out = dst + n * image_stride + Y * row_stride + X * 3;
+        const double v[3] = {v0, v1, v2};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int cd = swap_rb ? 2 - c : c;
+            const float q = fminf(fmaxf(__fmul_rn(__fsub_rn((float)v[c], lo), k), 0.f), 255.f);
+            const double b = (double)out[cd];
+            out[cd] = (uint8_t)(int)rint(fmin(fmax(fma(m, (double)q - b, b), 0.0), 255.0));      // (the clamp: a foreign feather table)
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -244,10 +309,32 @@ int spk_frames_u8_to_f32(const uint8_t* src, int64_t image_stride, int64_t row_s
     const int strips = spk::ceil_div(Hout, STRIP);
     const long long total = (long long)N * strips * Wout;
     Affine3 af = {{scale0, scale1, scale2}, {shift0, shift1, shift2}};
-    hipLaunchKernelGGL(frames_u8_to_f32_kernel, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
-                       (hipStream_t)stream, src, (long long)image_stride, (long long)row_stride, Hin, Win, swap_rb, first_y, count_y, w_y,
-                       taps_y, first_x, count_x, w_x, taps_x, dst, Hout, Wout, strips, total, af);
+    hipLaunchKernelGGL(frames_u8_to_f32_kernel<false>, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, src, (long long)image_stride, (long long)row_stride, (const int*)nullptr, Hin, Win, Hin, Win,
+                       swap_rb, first_y, count_y, w_y, taps_y, first_x, count_x, w_x, taps_x, dst, Hout, Wout, strips, total, af);
     return spk::check_launch("frames_u8_to_f32_kernel");
+}
+
+int spk_frames_u8_to_f32_boxes(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int H, int W, const int32_t* boxes_yx,
+                               int Hin, int Win, int swap_rb, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
+                               const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout,
+                               float scale0, float scale1, float scale2, float shift0, float shift1, float shift2, void* stream) {
+    SPK_REQUIRE(src && dst, "frames_u8_to_f32_boxes: null frame pointer");
+    SPK_REQUIRE(boxes_yx, "frames_u8_to_f32_boxes: null box origin array");
+    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_u8_to_f32_boxes: null table pointer");
+    SPK_REQUIRE(N >= 1 && Hin >= 1 && Win >= 1 && Hout >= 1 && Wout >= 1,
+                "frames_u8_to_f32_boxes: N / H / W must be >= 1 (N %d, %d x %d -> %d x %d)", N, Hin, Win, Hout, Wout);
+    SPK_REQUIRE(H >= Hin && W >= Win, "frames_u8_to_f32_boxes: the %d x %d box does not fit the %d x %d frame", Hin, Win, H, W);
+    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_u8_to_f32_boxes: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
+    SPK_REQUIRE(row_stride >= 3ll * W, "frames_u8_to_f32_boxes: row stride %lld is smaller than 3 * W = %lld", (long long)row_stride, 3ll * W);
+    SPK_REQUIRE(image_stride >= 0, "frames_u8_to_f32_boxes: negative image stride");
+    const int strips = spk::ceil_div(Hout, STRIP);
+    const long long total = (long long)N * strips * Wout;
+    Affine3 af = {{scale0, scale1, scale2}, {shift0, shift1, shift2}};
+    hipLaunchKernelGGL(frames_u8_to_f32_kernel<true>, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, src, (long long)image_stride, (long long)row_stride, (const int*)boxes_yx, H, W, Hin, Win, swap_rb,
+                       first_y, count_y, w_y, taps_y, first_x, count_x, w_x, taps_x, dst, Hout, Wout, strips, total, af);
+    return spk::check_launch("frames_u8_to_f32_kernel<boxes>");
 }
 
 int spk_frames_f32_to_u8(const float* src, uint8_t* dst, int N, int H, int W, int swap_rb, float lo, float k, void* stream) {
@@ -262,6 +349,36 @@ int spk_frames_f32_to_u8(const float* src, uint8_t* dst, int N, int H, int W, in
     else if (mode == 1) hipLaunchKernelGGL(frames_f32_to_u8_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, HW, groups, total, swap_rb, lo, k);
     else hipLaunchKernelGGL(frames_f32_to_u8_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, HW, groups, total, swap_rb, lo, k);
     return spk::check_launch("frames_f32_to_u8_kernel");
+}
+
+int spk_feather_table(int n, double feather, float* a_host) {
+    SPK_REQUIRE(n >= 1, "feather_table: n must be >= 1 (got %d)", n);
+    SPK_REQUIRE(std::isfinite(feather) && feather >= 0.0, "feather_table: feather must be a finite number >= 0 (got %g)", feather);
+    SPK_REQUIRE(a_host, "feather_table: null table pointer");
+    for (int i = 0; i < n; ++i) a_host[i] = (float)std::min(1.0, (double)(std::min(i, n - 1 - i) + 1) / (feather + 1.0));
+    return SPK_OK;
+}
+
+int spk_frames_paste_u8(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W,
+                        int h, int w, int y0, int x0, const int32_t* boxes_yx, int swap_rb, const int32_t* first_y, const int32_t* count_y,
+                        const float* w_y, int taps_y, const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x,
+                        const float* a_y, const float* a_x, float lo, float k, void* stream) {
+    SPK_REQUIRE(src && dst, "frames_paste_u8: null frame pointer");
+    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_paste_u8: null table pointer");
+    SPK_REQUIRE((a_y == nullptr) == (a_x == nullptr), "frames_paste_u8: the feather tables are both given or both null");
+    SPK_REQUIRE(N >= 1 && Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1 && h >= 1 && w >= 1,
+                "frames_paste_u8: N / H / W must be >= 1 (N %d, source %d x %d, box %d x %d, frame %d x %d)", N, Hs, Ws, h, w, H, W);
+    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_paste_u8: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
+    SPK_REQUIRE(row_stride >= 3ll * W, "frames_paste_u8: row stride %lld is smaller than 3 * W = %lld", (long long)row_stride, 3ll * W);
+    SPK_REQUIRE(N == 1 || image_stride >= (long long)(H - 1) * row_stride + 3ll * W,
+                "frames_paste_u8: image stride %lld makes the frames overlap (%d rows of stride %lld)", (long long)image_stride, H,
+                (long long)row_stride);
+    SPK_REQUIRE(std::isfinite(lo) && std::isfinite(k) && k > 0.f, "frames_paste_u8: the value range must be finite and increasing");
+    const long long total = (long long)N * h * w;
+    hipLaunchKernelGGL(frames_paste_u8_kernel, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, src, Hs, Ws, dst, N > 1 ? (long long)image_stride : 0ll, (long long)row_stride, H, W, h, w, y0, x0,
+                       (const int*)boxes_yx, swap_rb, first_y, count_y, w_y, taps_y, first_x, count_x, w_x, taps_x, a_y, a_x, lo, k, total);
+    return spk::check_launch("frames_paste_u8_kernel");
 }
 
 }  // extern "C"

@@ -109,6 +109,12 @@ class IRFD(nn.Module):
         frames ``[a, b)`` of a longer clip may be rendered elsewhere with ``frame0=a``.  ``noise="fixed"`` (needs a seed): every
         frame uses frame index ``frame0`` -- one noise image per layer held over the clip, as StyleGAN video pipelines do
         against boiling texture; ``"fresh"`` (default): new noise on every frame."""
+        out = [y for _, _, y in self._reenact_chunks(identity_image, pose_frames, emotion_frames, noises, chunk, output, channel_order,
+                                                     seed, noise, frame0)]
+        return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+    def _reenact_chunks(self, identity_image, pose_frames, emotion_frames, noises, chunk, output, channel_order, seed, noise, frame0):
+        """``reenact``'s argument checks and chunk loop: yields ``(t0, t1, frames of [t0, t1))``."""
         if output not in ("f32", "uint8"):
             raise ValueError(f"reenact: output must be 'f32' or 'uint8', got {output!r}")
         if noise not in ("fresh", "fixed"):
@@ -139,23 +145,36 @@ class IRFD(nn.Module):
         if noises is not None and any(n.size(0) != T for n in noises):
             raise ValueError(f"reenact: every noise tensor must carry {T} frames")
         fi = self.encode(identity_image, "Ei")
-        out = []
         for t0 in range(0, T, chunk):
             t1 = min(T, t0 + chunk)
             fe, fp = self.encode(emotion_frames[t0:t1], "Ee"), self.encode(pose_frames[t0:t1], "Ep")
             gin = self._prepare_generator_input(fi.expand(t1 - t0, -1, -1, -1), fe, fp)
             seeded = None if seed is None else dict(seed=seed, frame0=frame0 if noise == "fixed" else frame0 + t0, fixed_noise=noise == "fixed")
-            out.append(self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises], output, channel_order, seeded))
-        return out[0] if len(out) == 1 else torch.cat(out, 0)
+            yield t0, t1, self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises], output, channel_order, seeded)
 
     @torch.no_grad()
     def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8,
-                      seed=None, noise="fresh", frame0=0):
+                      seed=None, noise="fresh", frame0=0, paste=False, feather=0, inplace=False):
         """``reenact`` from and to video frames as a decoder and a video writer hold them (inference.py:29-33,46-58,78-86):
         uint8 HWC frames of any size on the device in, uint8 [T,R,R,3] out, both in ``channel_order`` ("bgr": ``cv2``'s).
         Nothing but ``ops.frames_from_u8`` -> ``reenact(output="uint8")``: ``identity_u8`` [H,W,3] or [1,H,W,3] is resized whole
-        to ``size``; ``pose_u8`` / ``emotion_u8`` [T,H,W,3] are cropped to ``crop=(y0, x0, h, w)`` (one box for all frames) and
-        resized; ``emotion_u8=None``: the pose frames, resized once.  ``seed`` / ``noise`` / ``frame0``: as ``reenact``."""
+        to ``size``; ``pose_u8`` / ``emotion_u8`` [T,H,W,3] are cropped to ``crop`` and resized; ``emotion_u8=None``: the pose
+        frames, resized once.  ``crop``: ``(y0, x0, h, w)``, one box for all frames; a host sequence / CPU integer tensor
+        ``[T,4]``, a tracker's box per frame, all of one size; or ``(boxes_yx, h, w)`` with a device int32 ``[T,2]`` tensor of
+        origins (``ops.frames_from_u8``).  ``seed`` / ``noise`` / ``frame0``: as ``reenact``.
+
+        ``paste=True``: the full frames back -- uint8 [T,H,W,3], the pose frames with every generated face resized to its box
+        and pasted where the crop came from (``crop=None``: the whole frame), blended over ``feather`` pixels at the box's
+        edge (``ops.frames_paste_u8``).  The result is one clone of ``pose_u8`` (``inplace=True``: ``pose_u8`` itself); each
+        chunk's fp32 decoder result is pasted straight into its slice, one ``spk_frames_paste_u8`` launch per chunk, and
+        per-frame boxes are taken per frame, so the result does not depend on ``chunk``."""
+        feather = float(feather)
+        if inplace and not paste:
+            raise ValueError("reenact_video: inplace applies to paste=True only")
+        if not paste and feather != 0:
+            raise ValueError("reenact_video: feather applies to paste=True only")
+        if not (0.0 <= feather < float("inf")):
+            raise ValueError(f"reenact_video: feather must be a finite number >= 0, got {feather}")
         if noise not in ("fresh", "fixed"):
             raise ValueError(f"reenact_video: noise must be 'fresh' or 'fixed', got {noise!r}")
         if seed is None and noise == "fixed":
@@ -164,11 +183,28 @@ class IRFD(nn.Module):
             if noises is not None:
                 raise ValueError("reenact_video: pass either seed or noises, not both")
             ops.check_seed(seed, frame0, "reenact_video: seed")
+        if crop is not None or paste:
+            if pose_u8.dim() != 4 or pose_u8.size(3) != 3 or pose_u8.size(0) < 1:
+                raise ValueError(f"reenact_video: pose_u8 must be [T,H,W,3], got {tuple(pose_u8.shape)}")
+            if inplace and not ops._packed_pixels(pose_u8):
+                raise L.SpkError(f"reenact_video: inplace needs packed pixels and rows / frames that do not overlap, got strides {pose_u8.stride()}")
+            T, H, W = pose_u8.shape[:3]
+            origins, h, w = ops.parse_boxes((0, 0, H, W) if crop is None else crop, T, H, W, "reenact_video: crop")
+            if not isinstance(origins, tuple) and not origins.is_cuda and pose_u8.is_cuda:
+                origins = origins.to(pose_u8.device)                       # host boxes: checked above, uploaded once for both edges
+            crop = (*origins, h, w) if isinstance(origins, tuple) else (origins, h, w)
         ident = ops.frames_from_u8(identity_u8, size, channel_order=channel_order)
         pose = ops.frames_from_u8(pose_u8, size, crop=crop, channel_order=channel_order)
         emo = None if emotion_u8 is None else ops.frames_from_u8(emotion_u8, size, crop=crop, channel_order=channel_order)
-        return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output="uint8", channel_order=channel_order, seed=seed,
-                            noise=noise, frame0=frame0)
+        if not paste:
+            return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output="uint8", channel_order=channel_order, seed=seed,
+                                noise=noise, frame0=frame0)
+        frames = pose_u8 if inplace else pose_u8.clone(memory_format=torch.contiguous_format)
+        for t0, t1, y in self._reenact_chunks(ident, pose, emo, noises, chunk, "f32", "rgb", seed, noise, frame0):
+            part = frames[t0:t1]
+            ops.frames_paste_u8(y, part, crop if len(crop) == 4 else (crop[0][t0:t1], h, w), feather=feather, channel_order=channel_order,
+                                out=part)
+        return frames
 
     def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None):
         """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan

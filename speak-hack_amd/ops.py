@@ -1468,12 +1468,91 @@ def _triple(v, name):
     return v
 
 
+def feather_tables(n, feather):
+    """The 1-D edge ramp of a pasted box (``spk_feather_table``, built in fp64 on the host, rounded to fp32):
+    ``a[i] = min(1, (min(i, n - 1 - i) + 1) / (feather + 1))``; ``feather >= 0`` is a real number, 0 gives all ones.  A pasted
+    pixel ``(y, x)`` is blended with weight ``a_y[y] * a_x[x]``.  -> CPU float32 tensor [n]."""
+    n, feather = int(n), float(feather)
+    if n < 1:
+        raise ValueError(f"feather_tables: n must be >= 1, got {n}")
+    if not (0.0 <= feather < float("inf")):
+        raise ValueError(f"feather_tables: feather must be a finite number >= 0, got {feather}")
+    a = torch.empty(n, dtype=torch.float32)
+    L.check(L.lib().spk_feather_table(n, feather, a.data_ptr()), "spk_feather_table")
+    return a
+
+
+_feather_cache = {}
+
+
+def _device_feather_tables(h, w, feather, device):
+    key = (h, w, feather, device)
+    t = _feather_cache.get(key)
+    if t is None:
+        if len(_feather_cache) >= 32:
+            _feather_cache.pop(next(iter(_feather_cache)))
+        t = _feather_cache[key] = (feather_tables(h, feather).to(device), feather_tables(w, feather).to(device))
+    return t
+
+
+def parse_boxes(box, N, H, W, what="box", inside=True):
+    """The three forms a launcher takes a box in, for ``N`` frames of ``H`` x ``W`` pixels, checked on the host:
+    ``(y0, x0, h, w)``, one box for all frames; a host sequence or CPU integer tensor ``[N,4]`` of such rows, one per frame,
+    whose ``h, w`` are all equal (a call has one filter table); ``(boxes_yx, h, w)`` with a DEVICE int32 tensor ``[N,2]`` of
+    origins, which is not read here (the kernels clamp / skip).  Host boxes that leave the frame raise ``ValueError``.
+    ``inside``: the device form's ``h x w`` must fit the frame too (the input kernel clamps origins; the paste kernel skips).
+    -> ``(origins, h, w)``: ``origins`` is ``(y0, x0)``, a CPU int32 tensor [N,2] still to be uploaded, or the device tensor."""
+    def in_frame(y0, x0, h, w):
+        if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
+            raise ValueError(f"{what}: box {(y0, x0, h, w)} leaves the {H} x {W} frame")
+
+    if isinstance(box, (tuple, list)) and len(box) == 3 and isinstance(box[0], torch.Tensor):
+        yx, h, w = box[0], int(box[1]), int(box[2])
+        if yx.dtype != torch.int32 or tuple(yx.shape) != (N, 2):
+            raise ValueError(f"{what}: box origins must be an int32 tensor [{N},2], got {yx.dtype} {tuple(yx.shape)}")
+        if h < 1 or w < 1 or (inside and (h > H or w > W)):
+            raise ValueError(f"{what}: a {h} x {w} box does not fit the {H} x {W} frame")
+        if yx.is_cuda and not yx.is_contiguous():
+            yx = yx.contiguous()
+        return yx, h, w
+    if isinstance(box, torch.Tensor):
+        if box.is_cuda or box.is_floating_point() or box.dim() != 2:
+            raise ValueError(f"{what}: a tensor of boxes must be a CPU integer tensor [N,4] (device origins go as (boxes_yx, h, w))")
+        box = box.tolist()
+    box = list(box)
+    if len(box) == 4 and not isinstance(box[0], (tuple, list)):
+        y0, x0, h, w = (int(v) for v in box)
+        in_frame(y0, x0, h, w)
+        return (y0, x0), h, w
+    rows = [tuple(int(v) for v in r) for r in box]
+    if len(rows) != N or any(len(r) != 4 for r in rows):
+        raise ValueError(f"{what}: per-frame boxes must be [{N},4] rows of (y0, x0, h, w), got {len(rows)} rows")
+    h, w = rows[0][2], rows[0][3]
+    if any((r[2], r[3]) != (h, w) for r in rows):
+        raise ValueError(f"{what}: the boxes of one call must have one size (a call has one filter table per axis), "
+                         f"got {sorted(set((r[2], r[3]) for r in rows))}")
+    for r in rows:
+        in_frame(*r)
+    return torch.tensor([r[:2] for r in rows], dtype=torch.int32), h, w
+
+
+def _packed_pixels(frames_u8):
+    """uint8 [N,H,W,3] with packed pixels and rows / frames that do not overlap: what the kernels address by byte strides."""
+    N, H, W, _ = frames_u8.shape
+    return frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3 and frames_u8.stride(1) >= 3 * W and \
+        (N == 1 or frames_u8.stride(0) >= (H - 1) * frames_u8.stride(1) + 3 * W)
+
+
 def frames_from_u8(frames_u8, size, *, crop=None, channel_order="rgb", mean=0.5, std=0.5):
     """uint8 HWC video frames -> the network's input, one launch (``spk_frames_u8_to_f32``): crop, antialiased bilinear resize
     to ``size`` x ``size`` (a number, or ``(H, W)``), ``(x / 255 - mean) / std`` per channel and HWC -> CHW -- ``transforms.Resize``
     + ``ToTensor`` + ``Normalize`` of inference.py:29-33 with the ``cv2.cvtColor`` of :53 (``channel_order="bgr"``: the frames are
     BGR, the result is RGB).  ``frames_u8``: uint8 [N,H,W,3] (or [H,W,3]) on the device, pixels packed (any row / frame stride:
-    slices of a larger frame are read in place); ``crop=(y0, x0, h, w)``: one box for all frames.  -> float32 [N,3,size,size]."""
+    slices of a larger frame are read in place); ``crop=(y0, x0, h, w)``: one box for all frames; a host sequence or CPU integer
+    tensor ``[N,4]``: a box per frame, all of one size (``ValueError`` otherwise: a call has one filter table), checked on the
+    host and uploaded once; ``(boxes_yx, h, w)`` with a device int32 ``[N,2]`` tensor: origins a tracker left on the device,
+    not read on the host -- the kernel clamps each so that the box stays inside the frame (``spk_frames_u8_to_f32_boxes``).
+    -> float32 [N,3,size,size]."""
     if frames_u8.dim() == 3:
         frames_u8 = frames_u8.unsqueeze(0)
     if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
@@ -1485,20 +1564,34 @@ def frames_from_u8(frames_u8, size, *, crop=None, channel_order="rgb", mean=0.5,
     mean, std = _triple(mean, "mean"), _triple(std, "std")
     if any(s == 0 for s in std):
         raise ValueError("frames_from_u8: std must be non-zero")
+    boxes = None
     if crop is not None:
-        y0, x0, h, w = (int(v) for v in crop)
-        if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > frames_u8.size(1) or x0 + w > frames_u8.size(2):
-            raise ValueError(f"frames_from_u8: crop {tuple(crop)} leaves the {frames_u8.size(1)} x {frames_u8.size(2)} frame")
-        frames_u8 = frames_u8[:, y0:y0 + h, x0:x0 + w]
+        origins, h, w = parse_boxes(crop, frames_u8.size(0), frames_u8.size(1), frames_u8.size(2), "frames_from_u8: crop")
+        if isinstance(origins, tuple):
+            y0, x0 = origins
+            frames_u8 = frames_u8[:, y0:y0 + h, x0:x0 + w]
+        else:
+            boxes = origins
     if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
         raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
     N, Hin, Win, _ = frames_u8.shape
     if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * Win or (N > 1 and frames_u8.stride(0) < 0):
         frames_u8 = frames_u8.contiguous()
-    fy, cy, wy, fx, cx, wx = _device_resize_tables(Hin, Win, Hout, Wout, frames_u8.device)
     scale = [1.0 / (255.0 * s) for s in std]
     shift = [-m / s for m, s in zip(mean, std)]
     out = torch.empty((N, 3, Hout, Wout), device=frames_u8.device, dtype=torch.float32)
+    if boxes is not None:
+        if boxes.device != frames_u8.device:
+            if boxes.is_cuda:
+                raise L.SpkError(f"frames_from_u8: box origins on {boxes.device}, frames on {frames_u8.device}")
+            boxes = boxes.to(frames_u8.device)
+        fy, cy, wy, fx, cx, wx = _device_resize_tables(h, w, Hout, Wout, frames_u8.device)
+        L.check(L.lib().spk_frames_u8_to_f32_boxes(frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), N, Hin, Win,
+                                                   boxes.data_ptr(), h, w, swap, fy.data_ptr(), cy.data_ptr(), wy.data_ptr(), wy.size(1),
+                                                   fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), wx.size(1), out.data_ptr(), Hout, Wout,
+                                                   *scale, *shift, L.stream_ptr()), "spk_frames_u8_to_f32_boxes")
+        return out
+    fy, cy, wy, fx, cx, wx = _device_resize_tables(Hin, Win, Hout, Wout, frames_u8.device)
     L.check(L.lib().spk_frames_u8_to_f32(frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), N, Hin, Win,
                                          swap, fy.data_ptr(), cy.data_ptr(), wy.data_ptr(), wy.size(1), fx.data_ptr(), cx.data_ptr(),
                                          wx.data_ptr(), wx.size(1), out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()),
@@ -1532,6 +1625,59 @@ def frames_to_u8(x, *, value_range=(-1, 1), channel_order="rgb", out=None):
     elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous():
         raise L.SpkError(f"out: expected a contiguous uint8 HIP tensor {(N, H, W, 3)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
     L.check(L.lib().spk_frames_f32_to_u8(xp, out.data_ptr(), N, H, W, swap, lo, k, L.stream_ptr()), "spk_frames_f32_to_u8")
+    return out
+
+
+def frames_paste_u8(x, frames_u8, box, *, feather=0, value_range=(-1, 1), channel_order="rgb", out=None):
+    """Generated frames back into the video they were cropped from, one launch (``spk_frames_paste_u8``): float32 [N,3,Hs,Ws]
+    in ``value_range`` is resized to the box size ``h x w`` (antialiased bilinear: shrinking and enlarging), quantised as
+    ``frames_to_u8`` does and blended over the pixels of ``frames_u8`` (uint8 [N,H,W,3] on the device, pixels packed, any row /
+    frame stride) inside the box: ``rint(b + m (q - b))`` with ``m = a_y[y] a_x[x]`` of ``feather_tables`` (``feather=0``: the box
+    replaces the background).  ``box``: ``(y0, x0, h, w)``; a host sequence / CPU integer tensor ``[N,4]`` of one size, checked
+    on the host and uploaded once; or ``(boxes_yx, h, w)`` with a device int32 ``[N,2]`` tensor, not read on the host -- box
+    pixels that fall outside the frame are skipped.  ``channel_order="bgr"``: the frames are BGR, ``x`` is RGB.  ``out=None``:
+    the result is a clone of ``frames_u8``; ``out=frames_u8``: pasted in place through its strides; another ``out`` first
+    receives a copy of ``frames_u8``.  -> uint8 [N,H,W,3]."""
+    if x.dim() != 4 or x.size(1) != 3 or x.size(0) < 1:
+        raise ValueError(f"frames_paste_u8: x must be [N,3,H,W], got {tuple(x.shape)}")
+    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != x.size(0):
+        raise ValueError(f"frames_paste_u8: frames must be [{x.size(0)},H,W,3], got {tuple(frames_u8.shape)}")
+    swap = _channel_swap(channel_order)
+    lo, k = quant_range(value_range)
+    feather = float(feather)
+    if not (0.0 <= feather < float("inf")):
+        raise ValueError(f"frames_paste_u8: feather must be a finite number >= 0, got {feather}")
+    N, _, Hs, Ws = x.shape
+    H, W = frames_u8.size(1), frames_u8.size(2)
+    origins, h, w = parse_boxes(box, N, H, W, "frames_paste_u8: box", inside=False)
+    xp = L.dptr(x, "x")
+    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
+        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
+    copy = out is not None and out is not frames_u8 and out.data_ptr() != frames_u8.data_ptr()
+    if out is None:
+        out = frames_u8.clone(memory_format=torch.contiguous_format)
+    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames_u8.shape):
+        raise L.SpkError(f"out: expected a uint8 HIP tensor {tuple(frames_u8.shape)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if not _packed_pixels(out):
+        raise L.SpkError(f"out: pixels must be packed and rows / frames must not overlap, got strides {out.stride()}")
+    if isinstance(origins, tuple):
+        (y0, x0), boxes = origins, None
+    else:
+        y0 = x0 = 0
+        if origins.device != x.device:
+            if origins.is_cuda:
+                raise L.SpkError(f"frames_paste_u8: box origins on {origins.device}, frames on {x.device}")
+            origins = origins.to(x.device)
+        boxes = origins
+    if copy:
+        out.copy_(frames_u8)
+    fy, cy, wy, fx, cx, wx = _device_resize_tables(Hs, Ws, h, w, x.device)
+    ay, ax = _device_feather_tables(h, w, feather, x.device) if feather > 0 else (None, None)
+    L.check(L.lib().spk_frames_paste_u8(xp, N, Hs, Ws, out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), H, W, h, w, y0, x0,
+                                        None if boxes is None else boxes.data_ptr(), swap, fy.data_ptr(), cy.data_ptr(), wy.data_ptr(),
+                                        wy.size(1), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), wx.size(1),
+                                        None if ay is None else ay.data_ptr(), None if ax is None else ax.data_ptr(), lo, k,
+                                        L.stream_ptr()), "spk_frames_paste_u8")
     return out
 
 

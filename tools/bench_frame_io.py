@@ -10,7 +10,13 @@
     resize filters agree to fp32 rounding, so a few bytes may differ by one step).
 (3) What crosses the C boundary / the ATen dispatcher at the edge, per call.
 
-    python tools/bench_frame_io.py [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
+``--paste``: the full-frame way out instead.  (1) ``ops.frames_paste_u8`` alone beside the HBM time of its bytes: 8 generated
+    256^2 frames into 400 x 400 tracked boxes (device origins, feather 16) of 1080 x 1920 BGR frames, in place.
+(2) ``IRFD.reenact_video(paste=True)`` against the eager torch composition of the same result -- per-frame crops, ``interpolate``
+    in, ``IRFD.reenact``, ``interpolate`` to the box, quantise, mask, blend, round, cast and permute into a clone of the video --
+    T = 64, chunk 8, 1080 x 1920 BGR, a 400 x 400 box that moves; alternating, with the ATen calls of both.
+
+    python tools/bench_frame_io.py [--paste] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
 import os
@@ -52,6 +58,92 @@ def eager_out(y, bgr):
     return q.permute(0, 2, 3, 1).contiguous()
 
 
+def eager_paste(y, video_out, boxes, h, w, feather, bgr):
+    """The torch composition ``ops.frames_paste_u8`` replaces, on fp32 copies: resize to the box, quantise, blend, round, cast."""
+    q = ((F.interpolate(y, size=(h, w), mode="bilinear", align_corners=False, antialias=True) + 1) * 127.5).clamp(0, 255)
+    if bgr:
+        q = q.flip(1)
+    q = q.permute(0, 2, 3, 1)
+    i, j = torch.arange(h, device=y.device), torch.arange(w, device=y.device)
+    ay = ((torch.minimum(i, h - 1 - i) + 1) / (feather + 1.0)).clamp(max=1.0)
+    ax = ((torch.minimum(j, w - 1 - j) + 1) / (feather + 1.0)).clamp(max=1.0)
+    m = (ay.view(h, 1) * ax.view(1, w)).unsqueeze(-1)
+    for n, (y0, x0) in enumerate(boxes):
+        b = video_out[n, y0:y0 + h, x0:x0 + w].float()
+        video_out[n, y0:y0 + h, x0:x0 + w] = (b + m * (q[n] - b)).round().to(torch.uint8)
+
+
+def bench_paste(args, lines):
+    import importlib
+    import model
+    from oracle import irfd_ref as IR
+    from oracle.weights_recipe import fill_state_dict
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    T, chunk, size, Hf, Wf, h, w, feather = args.frames, args.chunk, 256, 1080, 1920, 400, 400, 16
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(T)]                  # a head that moves
+    yx = torch.tensor(boxes, dtype=torch.int32, device=dev)
+
+    # ---- (1) the kernel alone ----
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    video = torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    t = device_time(lambda: ops.frames_paste_u8(x, video, (yx[:chunk], h, w), feather=feather, channel_order="bgr", out=video))
+    scratch = video.clone()
+    te = device_time(lambda: eager_paste(x, scratch, boxes[:chunk], h, w, feather, True))
+    nbytes = x.numel() * 4 + 2 * chunk * h * w * 3
+    lines.append(f"frames_paste_u8 {chunk} x 256^2 fp32 -> {h}x{w} boxes of {Hf}x{Wf} BGR, feather {feather}, in place: {t * 1e6:8.1f} us, "
+                 f"{nbytes / 1e6:6.1f} MB -> HBM time {nbytes / HBM * 1e6:6.1f} us ({nbytes / HBM / t * 100:5.1f} % of it); "
+                 f"the torch ops it replaces: {te * 1e6:8.1f} us")
+
+    # ---- (2) reenact_video(paste=True) against the eager composition ----
+    m = model.IRFD()
+    sd = IR.irfd_recipe_state_dict()
+    sd.update({"Gd." + k: v for k, v in fill_state_dict(m.Gd.state_dict(), prefix="Gd.").items()})
+    m.load_state_dict(sd, strict=False)
+    m.to(dev).eval()
+    ident = torch.randint(0, 256, (1, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    video = torch.randint(0, 256, (T, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    noises = [torch.randn(T, 1, 4 << (i + 1) // 2, 4 << (i + 1) // 2, generator=g).to(dev) for i in range(13)]
+
+    def ours():
+        return m.reenact_video(ident, video, size=size, crop=(yx, h, w), channel_order="bgr", noises=noises, chunk=chunk, paste=True,
+                               feather=feather)
+
+    def eager():
+        crops = torch.stack([video[n, y0:y0 + h, x0:x0 + w] for n, (y0, x0) in enumerate(boxes)])
+        y = m.reenact(eager_in(ident, size, True), eager_in(crops, size, True), noises=noises, chunk=chunk)
+        out = video.clone()
+        for t0 in range(0, T, chunk):
+            eager_paste(y[t0:t0 + chunk], out[t0:t0 + chunk], boxes[t0:t0 + chunk], h, w, feather, True)
+        return out
+
+    with torch.no_grad():
+        for _ in range(args.warmup):
+            a, b = ours(), eager()
+        diff = (a.int() - b.int()).abs()
+        times = {"paste=True": [], "eager": []}
+        for _ in range(args.repeats):                    # alternating: drift hits both alike
+            times["paste=True"].append(wall(ours))
+            times["eager"].append(wall(eager))
+        c_ours, c_eager = CountAten(), CountAten()
+        with c_ours:
+            ours()
+        with c_eager:
+            eager()
+    lines.append(f"T = {T} frames of {Hf}x{Wf} BGR, a {h}x{w} tracked box, feather {feather}, chunk {chunk}, {args.repeats} alternating repeats "
+                 f"after {args.warmup} warm-up rounds:")
+    for n in ("paste=True", "eager"):
+        ts = sorted(times[n])
+        med = statistics.median(ts)
+        lines.append(f"  {n:14s} median {med * 1e3:8.2f} ms  min {ts[0] * 1e3:8.2f}  max {ts[-1] * 1e3:8.2f}  spread "
+                     f"{(ts[-1] - ts[0]) / med * 100:5.1f} %  -> {T / med:8.1f} frames/s")
+    mo, me = statistics.median(times["paste=True"]), statistics.median(times["eager"])
+    lines.append(f"  reenact_video(paste=True) / eager = {mo / me:.3f}; bytes that differ: {int((diff > 0).sum())} of {diff.numel()} "
+                 f"(largest step {int(diff.max())}); ATen calls per run: {c_ours.n} against {c_eager.n} ({T // chunk} chunks)")
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -80,9 +172,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--paste", action="store_true", help="the full-frame way out: frames_paste_u8 and reenact_video(paste=True)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.paste:
+        lines = [f"bench_frame_io --paste: {torch.cuda.get_device_name(0)}, fp32, HBM time at {HBM / 1e12:.1f} TB/s"]
+        bench_paste(args, lines)
+        return report(lines, args.out)
     import importlib
     import model
     from oracle import irfd_ref as IR
@@ -150,11 +247,15 @@ def main():
         mo, me = statistics.median(times["reenact_video"]), statistics.median(times["eager"])
         lines.append(f"  reenact_video / eager = {mo / me:.3f}; bytes that differ: {int((diff > 0).sum())} of {diff.numel()} (largest step {int(diff.max())}); "
                      f"ATen calls per run: {c_ours.n} against {c_eager.n} ({T // chunk} chunks)")
+    report(lines, args.out)
+
+
+def report(lines, out):
     text = "\n".join(lines)
     print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(text + "\n")
 
 

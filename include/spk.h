@@ -211,6 +211,26 @@ int spk_conv2d_pack_weights(const float* w, float* w_packed, int kh, int kw, int
 int spk_conv2d_pack_weights_list(const float* const* ws, int n, float* w_packed, int kh, int kw, int Cin, int Cout, int config,
                                  int transpose_flip, void* stream);
 int spk_conv2d_fwd(const spk_conv2d_desc* desc, void* stream);
+/* The form spk_conv2d_fwd(desc) would take, answered by the launch path's own statements on the host: nothing is launched and no
+ * device is touched (pointers are read for their ALIGNMENT only, so any values of the right alignment do; a sliced launch still
+ * needs workspace / workspace_bytes to be set).  Served: every descriptor that runs the tap kernel (tile configs 0-11, the 2x2
+ * parity forms of SPK_CONV_DGRAD_S2 / SPK_CONV_TRANSPOSE4X4_S2 included); SPK_CONV_WINOGRAD descriptors and the exact-tap data
+ * gradient (config 13) fill ksplit / finisher / finisher_seg (config = -1 / 13, everything else 0).  The GEMM forms of a 1x1,
+ * the stem kernel and SPK_CONV_BF16X3 are refused.
+ *   mode: the kernel's input-stage build (0 plain, 1 x2, 2 affine+ReLU, 3 batch scale, 4 x2 + batch scale, 5 plain with
+ *         BatchNorm sums, 6 plain with the residual epilogue)
+ *   staged: the epilogue's store form -- 0 dword stores, 1 through an LDS tile, 2 through an LDS tile in two halves
+ *   finisher: 0 none (unsliced), 1 the scalar split-K finisher, 2 the vector one; finisher_seg: lanes of a wave that share one
+ *         plane in the vector finisher's BatchNorm sums (1..64; 0 otherwise) */
+typedef struct spk_conv2d_form {
+    int32_t config, mode, TW, TH, TB;
+    int32_t n_chunks, ksplit, chunks_per_split, last_split_chunks;
+    int32_t ragged_last_chunk, fixed_geometry, one_slot_ring, staged;
+    int32_t grid_x, grid_y, grid_z;
+    int32_t finisher, finisher_seg;
+    int64_t lds_bytes;
+} spk_conv2d_form;
+int spk_conv2d_launch_form(const spk_conv2d_desc* desc, spk_conv2d_form* out);
 /* The SPK_CONV_BF16X3 path: packed image size in BYTES / packer (w is the fp32 [Cout,Cin,3,3] parameter; the hi / lo split
  * happens here, once per weight update) / whether a shape is served / the launch itself (spk_conv2d_fwd forwards to it). */
 int64_t spk_conv2d_packed_bytes_bf16x3(int Cin, int Cout);

@@ -38,6 +38,13 @@ class Conv2dDesc(C.Structure):
                 ("residual", C.c_void_p)]
 
 
+class Conv2dForm(C.Structure):
+    """Mirror of spk_conv2d_form (include/spk.h): what ``spk_conv2d_launch_form`` answers."""
+    _fields_ = [(n, C.c_int32) for n in ("config", "mode", "TW", "TH", "TB", "n_chunks", "ksplit", "chunks_per_split", "last_split_chunks",
+                                         "ragged_last_chunk", "fixed_geometry", "one_slot_ring", "staged", "grid_x", "grid_y", "grid_z",
+                                         "finisher", "finisher_seg")] + [("lds_bytes", C.c_int64)]
+
+
 CONV_IN_BATCH_SCALE = 256
 CONV_UP_FIR1331 = 512
 CONV_DGRAD_S2 = 1024
@@ -251,6 +258,7 @@ _PROTOTYPES = {
     "spk_conv2d_pack_weights_list": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_int, C.c_int, C.c_void_p]),
     "spk_conv2d_fwd": (C.c_int, [C.POINTER(Conv2dDesc), C.c_void_p]),
+    "spk_conv2d_launch_form": (C.c_int, [C.POINTER(Conv2dDesc), C.POINTER(Conv2dForm)]),
     "spk_conv2d_packed_bytes_bf16x3": (C.c_int64, [C.c_int, C.c_int]),
     "spk_conv2d_pack_weights_bf16x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "spk_conv2d_pack_weights_bf16x3_tf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

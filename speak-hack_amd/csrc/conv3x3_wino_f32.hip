@@ -823,6 +823,14 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
         a.y = static_cast<float*>(d->workspace); a.y_pre = nullptr; a.out_scale_dev = nullptr; a.out_scale_bc = nullptr;
         a.flags = d->flags & ~epi; a.out_scale = 1.f; a.slice_floats = out_floats;
     }
+    spkconv::ConvArgs f = {};       // the finisher's arguments
+    if (ks > 1) {
+        f.bias = d->bias; f.noise_w = d->noise_w; f.noise = d->noise; f.style = d->style; f.out_scale_bc = d->out_scale_bc;
+        f.y = d->y; f.y_pre = d->y_pre; f.B = d->B; f.Cin = d->Cin; f.Cout = d->Cout; f.Cy = Cy; f.Cx = Cx; f.G = G; f.H = d->H; f.W = d->W;
+        f.style_stride = d->style_stride; f.flags = d->flags & epi; f.slope = d->lrelu_slope; f.out_scale = d->out_scale * up_scale;
+        f.act_gain = a.act_gain; f.out_scale_dev = d->out_scale_dev;
+    }
+    if (spkconv::form_probe) return spkconv::report_sliced_form(f, static_cast<const float*>(d->workspace), ks);
     void (*kern)(const Args) = mod ? (shape == SQUARE ? &wino_kernel<true, SQUARE> : &wino_kernel<true, WIDE>)
                                : rgb ? (shape == SQUARE ? &wino_kernel<false, SQUARE, true> : &wino_kernel<false, WIDE, true>)
                                      : (shape == SQUARE ? &wino_kernel<false, SQUARE> : &wino_kernel<false, WIDE>);
@@ -856,11 +864,6 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     hipLaunchKernelGGL(kern, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
     int rc = spk::check_launch("wino_kernel");
     if (rc != SPK_OK || ks == 1) return rc;
-    spkconv::ConvArgs f = {};
-    f.bias = d->bias; f.noise_w = d->noise_w; f.noise = d->noise; f.style = d->style; f.out_scale_bc = d->out_scale_bc;
-    f.y = d->y; f.y_pre = d->y_pre; f.B = d->B; f.Cin = d->Cin; f.Cout = d->Cout; f.Cy = Cy; f.Cx = Cx; f.G = G; f.H = d->H; f.W = d->W;
-    f.style_stride = d->style_stride; f.flags = d->flags & epi; f.slope = d->lrelu_slope; f.out_scale = d->out_scale * up_scale;
-    f.act_gain = a.act_gain; f.out_scale_dev = d->out_scale_dev;
     return spkconv::launch_splitk_epilogue(f, static_cast<const float*>(d->workspace), ks, (hipStream_t)stream);
 }
 

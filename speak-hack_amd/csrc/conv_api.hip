@@ -140,16 +140,33 @@ __global__ __launch_bounds__(256) void splitk_epilogue_vec_kernel(const ConvArgs
     }
 }
 
-int launch_splitk_epilogue(const ConvArgs& a_in, const float* ws, int ksplit, hipStream_t stream) {
-    ConvArgs a = a_in;
-    a.Cout = a_in.Cy;            // the finisher walks the output tensor: every group's channels
-    const size_t out_floats = (size_t)a.B * a.Cout * a.H * a.W;
+int splitk_finisher(const ConvArgs& a, const float* ws, int* seg) {
     const size_t HW = (size_t)a.H * a.W, q4 = HW / 4;
     // lanes of a wave must split evenly into planes for the segmented sums: q4 a multiple of 64, or a power of two below
     const bool seg_ok = HW % 4 == 0 && (q4 % 64 == 0 || (q4 < 64 && (q4 & (q4 - 1)) == 0));
     const bool aligned = (uintptr_t)ws % 16 == 0 && (uintptr_t)a.y % 16 == 0 && (!a.y_pre || (uintptr_t)a.y_pre % 16 == 0) &&
                          (!a.noise || (uintptr_t)a.noise % 16 == 0) && (uintptr_t)a.residual % 16 == 0;
-    if (seg_ok && aligned) {
+    *seg = seg_ok && aligned ? (q4 >= 64 ? 64 : (int)q4) : 0;      // (the vector kernel's own `seg`)
+    return seg_ok && aligned ? 2 : 1;
+}
+
+thread_local spk_conv2d_form* form_probe = nullptr;
+
+int report_sliced_form(const ConvArgs& finisher_args, const float* ws, int ksplit) {
+    spk_conv2d_form& f = *form_probe;
+    int seg = 0;
+    f.ksplit = ksplit;
+    f.finisher = ksplit > 1 ? splitk_finisher(finisher_args, ws, &seg) : 0;
+    f.finisher_seg = seg;
+    return SPK_OK;
+}
+
+int launch_splitk_epilogue(const ConvArgs& a_in, const float* ws, int ksplit, hipStream_t stream) {
+    ConvArgs a = a_in;
+    a.Cout = a_in.Cy;            // the finisher walks the output tensor: every group's channels
+    const size_t out_floats = (size_t)a.B * a.Cout * a.H * a.W;
+    int seg;
+    if (splitk_finisher(a, ws, &seg) == 2) {
         const unsigned blocks = (unsigned)std::min<size_t>((out_floats / 4 + 255) / 256, 256 * 8);
         hipLaunchKernelGGL(a.residual ? splitk_epilogue_vec_kernel<true> : splitk_epilogue_vec_kernel<false>, dim3(blocks), dim3(256), 0, stream, a, ws, ksplit);
         return spk::check_launch("splitk_epilogue_vec_kernel");
@@ -540,6 +557,17 @@ int spk_conv2d_pack_weights_list(const float* const* ws, int n, float* w_packed,
     return spk::check_launch("pack_weights_kernel");
 }
 
+int spk_conv2d_launch_form(const spk_conv2d_desc* d, spk_conv2d_form* out) {
+    SPK_REQUIRE(d && out, "conv2d launch form: null pointer");
+    SPK_REQUIRE(!(d->flags & SPK_CONV_BF16X3), "conv2d launch form: SPK_CONV_BF16X3 launches are not served");
+    *out = spk_conv2d_form{};
+    out->config = -1;
+    form_probe = out;            // the launch path answers where it would launch (run(), spk_conv2d_wino_fwd, run_dgrad_s2_fused)
+    const int rc = spk_conv2d_fwd(d, nullptr);
+    form_probe = nullptr;
+    return rc;
+}
+
 int spk_conv2d_fwd(const spk_conv2d_desc* d, void* stream) {
     SPK_REQUIRE(d, "conv2d: null descriptor");
     if (d->flags & SPK_CONV_BF16X3) return spk_conv2d_bf16x3_fwd(d, stream);
@@ -624,6 +652,7 @@ int spk_conv2d_fwd(const spk_conv2d_desc* d, void* stream) {
     const int mode = ups ? (bsc ? MODE_UPSAMPLE_BATCH_SCALE : MODE_UPSAMPLE) : (aff ? MODE_AFFINE_RELU : (bsc ? MODE_BATCH_SCALE : MODE_PLAIN));
     hipStream_t s = (hipStream_t)stream;
     SPK_REQUIRE(!d->out_scale_dev || !(cfg == kGemmConfig || is_gemm2(cfg)), "conv2d: out_scale_dev is built into the tap kernels (not the GEMM forms of a 1x1)");
+    SPK_REQUIRE(!form_probe || !(cfg == kGemmConfig || is_gemm2(cfg) || cfg == kStemConfig), "conv2d launch form: config %d is not a tap-kernel config", cfg);
     if (cfg == kGemmConfig) return run_1x1_gemm(&dd, s);
     if (is_gemm2(cfg)) return run_1x1_gemm2(&dd, s);
     if (cfg == kStemConfig) {

@@ -812,7 +812,7 @@ __global__ __launch_bounds__(C::NTHREADS) void conv_kernel(const ConvArgs p) {
 struct Geometry {
     int TW, TH, TB, PLANE, tiles_x, tiles_y, tiles_b, n_chunks, co_tiles;
     size_t lds_bytes;
-    bool ok;
+    bool ok, one_slot;
 };
 
 template <class C, int KH, int KW, int S>
@@ -835,8 +835,8 @@ Geometry geometry(int B, int Cin, int Cout, int H, int W) {
     g.n_chunks = spk::ceil_div(Cin, C::CI_T);
     g.co_tiles = spk::ceil_div(Cout, C::CO_T);
     const size_t in_floats = ((size_t)C::CI_T * g.TB * g.PLANE + 3) & ~(size_t)3;
-    const bool one_slot = KH * KW > 9 && g.n_chunks == 1;   // rolled-loop kernel with a single chunk: no ring needed
-    g.lds_bytes = (one_slot ? 1 : 3) * (SH::W_FLOATS + in_floats + 4) * sizeof(float);   // three-slot ring
+    g.one_slot = KH * KW > 9 && g.n_chunks == 1;   // rolled-loop kernel with a single chunk: no ring needed
+    g.lds_bytes = (g.one_slot ? 1 : 3) * (SH::W_FLOATS + in_floats + 4) * sizeof(float);   // three-slot ring
     if (g.lds_bytes > 160 * 1024) g.ok = false;
     return g;
 }
@@ -859,6 +859,26 @@ inline int resolve_ksplit(const Geometry& g, int requested, int* chunks_per_spli
 }
 
 int launch_splitk_epilogue(const ConvArgs& a, const float* ws, int ksplit, hipStream_t stream);
+// the finisher launch_splitk_epilogue runs for these tensors: 2 = vector (*seg lanes of a wave share a plane), 1 = scalar (*seg = 0)
+int splitk_finisher(const ConvArgs& a, const float* ws, int* seg);
+
+// spk_conv2d_launch_form: while set (on the calling thread), the launch paths answer here where they would launch and return
+extern thread_local spk_conv2d_form* form_probe;
+int report_sliced_form(const ConvArgs& finisher_args, const float* ws, int ksplit);   // Winograd / config 13: the finisher alone
+
+inline int report_form(int config, int mode, const Geometry& g, const ConvArgs& a, float* y, int ksplit, bool ragged, bool use_fg,
+                       long long gx, const float* ws) {
+    spk_conv2d_form& f = *form_probe;
+    f.config = config; f.mode = mode; f.TW = g.TW; f.TH = g.TH; f.TB = g.TB;
+    f.n_chunks = g.n_chunks; f.chunks_per_split = a.chunks_per_split;
+    f.last_split_chunks = g.n_chunks - (ksplit - 1) * a.chunks_per_split;
+    f.ragged_last_chunk = ragged; f.fixed_geometry = use_fg; f.one_slot_ring = g.one_slot; f.staged = a.staged;
+    f.grid_x = (int)gx; f.grid_y = g.co_tiles; f.grid_z = ksplit;
+    f.lds_bytes = (int64_t)g.lds_bytes;
+    ConvArgs fin = a;
+    fin.y = y;
+    return report_sliced_form(fin, ws, ksplit);
+}
 
 // Fill ConvArgs from the public descriptor, pick geometry / split-K, launch (and the split-K epilogue).
 template <class C, int KH, int KW, int S, int MODE, bool TRY_FG = false>
@@ -927,6 +947,10 @@ int run(const spk_conv2d_desc* d, hipStream_t stream, int Hd = 0, int Wd = 0, in
     if constexpr (TRY_FG) {
         if (use_fg) kern = &conv_kernel<C, KH, KW, S, MODE, true>;
     }
+    const long long gx = (long long)g.tiles_x * g.tiles_y * g.tiles_b;
+    SPK_REQUIRE(gx < (1ll << 31), "conv2d: grid too large");
+    if (form_probe)
+        return report_form(d->config, MODE, g, a, d->y, ksplit, d->Cin % C::CI_T != 0, use_fg, gx, static_cast<const float*>(d->workspace));
     if (g.lds_bytes > 64 * 1024) {  // dynamic LDS above 64 KiB needs the attribute raised (once per kernel)
         static const void* raised[2] = {nullptr, nullptr};
         const void* kp = reinterpret_cast<const void*>(kern);
@@ -936,8 +960,6 @@ int run(const spk_conv2d_desc* d, hipStream_t stream, int Hd = 0, int Wd = 0, in
             raised[raised[0] ? 1 : 0] = kp;
         }
     }
-    const long long gx = (long long)g.tiles_x * g.tiles_y * g.tiles_b;
-    SPK_REQUIRE(gx < (1ll << 31), "conv2d: grid too large");
     dim3 grid((unsigned)gx, (unsigned)g.co_tiles, (unsigned)ksplit);
     hipLaunchKernelGGL(kern, grid, dim3(C::NTHREADS), g.lds_bytes, stream, a);
     int rc = spk::check_launch("conv_kernel");

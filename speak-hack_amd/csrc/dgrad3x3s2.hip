@@ -252,13 +252,17 @@ int run_dgrad_s2_fused(const spk_conv2d_desc* d, hipStream_t stream) {
     a.slice_floats = split ? out_floats : 0;
     const int nz = split ? spk::ceil_div(a.n_chunks, a.cps) : 1;
     if (split) { a.y = static_cast<float*>(d->workspace); a.accumulate = 0; a.out_scale = 1.f; a.out_scale_dev = nullptr; }
+    ConvArgs f = {};                // the finisher's arguments
+    f.y = static_cast<float*>(d->y); f.B = d->B; f.Cin = d->Cin; f.Cout = d->Cout; f.Cy = a.Cy; f.Cx = a.Cg; f.G = a.G; f.H = d->H; f.W = d->W;
+    f.flags = d->flags & SPK_EPI_ACCUM; f.slope = 1.f; f.out_scale = d->out_scale; f.act_gain = 1.f; f.out_scale_dev = d->out_scale_dev;
+    if (form_probe) {
+        form_probe->config = kDgradS2Config;
+        return report_sliced_form(f, static_cast<const float*>(d->workspace), nz);
+    }
     dim3 grid((unsigned)gx, (unsigned)(a.G * a.co_tiles_g), (unsigned)nz);
     hipLaunchKernelGGL(dgrad3x3s2_kernel, grid, dim3(256), 2 * STAGE * sizeof(float), stream, a);
     int rc = spk::check_launch("dgrad3x3s2_kernel");
     if (rc != SPK_OK || !split) return rc;
-    ConvArgs f = {};
-    f.y = static_cast<float*>(d->y); f.B = d->B; f.Cin = d->Cin; f.Cout = d->Cout; f.Cy = a.Cy; f.Cx = a.Cg; f.G = a.G; f.H = d->H; f.W = d->W;
-    f.flags = d->flags & SPK_EPI_ACCUM; f.slope = 1.f; f.out_scale = d->out_scale; f.act_gain = 1.f; f.out_scale_dev = d->out_scale_dev;
     return launch_splitk_epilogue(f, static_cast<const float*>(d->workspace), nz, stream);
 }
 

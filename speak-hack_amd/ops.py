@@ -114,6 +114,23 @@ def conv_desc(x, w_packed, Cout, k=3, stride=1, *, flags=0, out=None, hw=None, b
     return d, ws_bytes
 
 
+def desc_launch_form(desc, ws_bytes=0, workspace_ptr=256):
+    """The form ``spk_conv2d_fwd(desc)`` would take, as a dict of the ``spk_conv2d_form`` fields (``spk_conv2d_launch_form``: the
+    launch path's own decisions, nothing is launched).  A sliced launch is asked about with ``workspace_ptr`` standing for its
+    scratch: only the pointer's alignment is read."""
+    if ws_bytes > 0 and not desc.workspace:
+        desc.workspace, desc.workspace_bytes = workspace_ptr, ws_bytes
+    form = L.Conv2dForm()
+    L.check(L.lib().spk_conv2d_launch_form(C.byref(desc), C.byref(form)), "spk_conv2d_launch_form")
+    return {name: getattr(form, name) for name, _ in L.Conv2dForm._fields_}
+
+
+def conv_launch_form(*args, workspace_ptr=256, **kw):
+    """``desc_launch_form`` of the descriptor ``conv_desc(*args, **kw)`` assembles."""
+    d, ws_bytes = conv_desc(*args, **kw)
+    return desc_launch_form(d, ws_bytes, workspace_ptr)
+
+
 # --------------------------------------------------------------------------------------------------
 class PackedConvWeight:
     """The packed images of a [Cout,Cin,k,k] weight (``pack_image``: a tile config of the MFMA conv kernel, "wino" or "bf16x3"),

@@ -694,6 +694,68 @@ int spk_frames_paste_u8(const float* src, int N, int Hs, int Ws, uint8_t* dst, i
                         const float* w_y, int taps_y, const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x,
                         const float* a_y, const float* a_x, float lo, float k, void* stream);
 
+/* ---- the video-frame edge in NV12 form (csrc/frame_nv12.hip) ---------------------------------------------------------------------
+ * What a hardware decoder or encoder holds in device memory, in and out of the network without a packed-RGB detour.
+ *
+ * NV12 FRAMES.  N frames of H x W pixels, H and W even: a Y plane uint8 [H][W] (pixel stride 1) and a UV plane uint8 [H/2][W/2][2]
+ * (U then V), each given by base pointer, image stride and row stride in BYTES (a row pitch wider than the image is the rule).  A
+ * (U, V) pair is packed and 2-byte aligned: an odd UV base or an odd UV stride is refused.  Chroma is sited by REPLICATION: pixel
+ * (Y, X) has chroma sample (Y >> 1, X >> 1) -- on the way in and on the way out; a box origin may be odd.
+ *
+ * COLOUR.  spk_yuv_coeffs builds, on the HOST in fp64 from the primaries alone, the two 3 x 4 affine maps in BYTE units between
+ * R'G'B' 0..255 and the Y, U (Cb), V (Cr) bytes, rows [a0 a1 a2 offset]: to_rgb rows R, G, B over (y, u, v, 1); from_rgb rows
+ * Y, U, V over (r, g, b, 1); either pointer may be NULL.  standard 601: (Kr, Kb) = (0.299, 0.114); 709: (0.2126, 0.0722);
+ * Kg = 1 - Kr - Kb;  E'y = Kr R + Kg G + Kb B,  E'cb = (B - E'y) / (2 (1 - Kb)),  E'cr = (R - E'y) / (2 (1 - Kr));
+ * limited range (full_range 0): Y = 16 + 219 E'y, C = 128 + 224 E'c;  full range: Y = 255 E'y, C = 128 + 255 E'c.
+ * to_rgb is the closed-form inverse (to_rgb o from_rgb = identity to 1e-12).  601 limited is what
+ * cv2.cvtColor(..., COLOR_YUV2BGR_NV12) assumes (in fixed point: bit parity with it is not a goal).  Known answers, to_rgb limited:
+ * 601: 255/219, 1.596027, -0.391762, -0.812968, 2.017232;  709: 255/219, 1.792741, -0.213249, -0.532909, 2.112402.
+ * A row is applied as ONE fp64 fma chain from the offset:  row . (p0, p1, p2, 1) = fma(a2, p2, fma(a1, p1, fma(a0, p0, offset))).
+ *
+ * spk_frames_nv12_to_f32: crop + antialiased bilinear resize + colour + normalise -> CHW in one pass.  Frame n's Hin x Win box
+ *   starts at (y0, x0), or at boxes_yx[n] when boxes_yx (a DEVICE int32 [N][2] array) is not NULL; either origin is clamped into
+ *   [0, H - Hin] x [0, W - Win] (H >= Hin, W >= Win), and every window is clamped into the box, so no origin and no table can send
+ *   a load out of bounds.  The six tables are DEVICE copies of spk_resize_table's for Hin -> Hout and Win -> Wout.  Per output
+ *   pixel the three component fields of the box -- Y[Y][X], U[Y >> 1][X >> 1], V[Y >> 1][X >> 1] -- are summed with the table weights
+ *   in fp64 exactly as spk_frames_u8_to_f32 sums its three bytes, giving (y, u, v); then, for c = R, G, B,
+ *     rgb_c = min(max(to_rgb_c . (y, u, v, 1), 0), 255)                         fp64
+ *     dst[n, c', oy, ox] = (float) fma(scale_c', rgb_c, shift_c')               c' = swap_rb ? 2 - c : c (the plane order of dst)
+ *   The clamp is applied AFTER the resize: the resize and the matrix are both linear and commute, so this equals converting and
+ *   clamping every source pixel wherever all pixels of a window are in gamut (out-of-gamut YUV triples, which a decoder does not
+ *   produce for real pictures, are clamped once per output pixel instead of once per source pixel).
+ * spk_frames_paste_nv12: the inverse of the crop: resize src [N,3,Hs,Ws] (fp32 R, G, B planes, contiguous) to the box size h x w,
+ *   quantise, convert and feather-blend into the surfaces the boxes came from, in one launch.  Origins by value or from boxes_yx as
+ *   above, NOT clamped: every pixel outside the H x W frame is skipped before any load.  For box pixel p = (y, x) inside the frame:
+ *     v_c = sum_iy sum_ix w_y[y,iy] w_x[x,ix] src[n,c,iy,ix]                     fp64 sums, as spk_frames_paste_u8
+ *     q_c = min(max(((float)v_c - lo) * k, 0), 255)                             fp32 in that order, not rounded (NaN -> 0)
+ *     e   = from_rgb . (q_R, q_G, q_B, 1)                                       fp64: (e_y, e_u, e_v)
+ *     m_p = a_y[y] * a_x[x]                                                     fp32 tables promoted to fp64; both NULL: m_p = 1
+ *   luma:    Y' = rint(min(max(fma(1 - m_p, b, m_p * e_y), 0), 255))            b: the byte being overwritten
+ *   chroma of sample s: over the pixels of its 2 x 2 block that lie in the box and in the frame, in row-major order,
+ *            acc = fma(0.25 m_p, e_c,p, acc) from 0,  S = sum 0.25 m_p,
+ *            C' = rint(min(max(fma(1 - S, b_c, acc), 0), 255))                  a sample with no such pixel is not touched
+ *   A convex combination: an unfeathered paste of a whole block has m = 1 and S = 1, the background's weight is exactly 0, and the
+ *   result is the plain conversion Y = rint(clamp(e_y)), C = rint(clamp(mean of the four e_c)) by arithmetic.  A thread reads only
+ *   bytes it writes, so pasting in place is legal; N > 1: the frames of a plane must not overlap.
+ * spk_frames_f32_to_nv12: the whole-frame case (h x w = Hs x Ws = H x W at the origin, no feather) without tables: bit for bit
+ *   spk_frames_paste_nv12 with identity tables.
+ * Refused before any launch (SPK_EINVAL, spk_last_error): null pointers, N < 1, odd H / W, an odd UV base or stride, a row stride
+ *   below the row's W bytes, overlapping frames on the way out, a box larger than the frame on the way in, tap counts < 1, a value
+ *   range that is not finite and increasing, a standard other than 601 / 709, a full_range other than 0 / 1. */
+int spk_yuv_coeffs(int standard, int full_range, double to_rgb[12], double from_rgb[12]);
+int spk_frames_nv12_to_f32(const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, const uint8_t* uv, int64_t uv_image_stride,
+                           int64_t uv_row_stride, int N, int H, int W, const int32_t* boxes_yx, int y0, int x0, int Hin, int Win, int swap_rb,
+                           int standard, int full_range, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
+                           const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout,
+                           float scale0, float scale1, float scale2, float shift0, float shift1, float shift2, void* stream);
+int spk_frames_f32_to_nv12(const float* src, int N, int H, int W, uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, uint8_t* uv,
+                           int64_t uv_image_stride, int64_t uv_row_stride, int standard, int full_range, float lo, float k, void* stream);
+int spk_frames_paste_nv12(const float* src, int N, int Hs, int Ws, uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, uint8_t* uv,
+                          int64_t uv_image_stride, int64_t uv_row_stride, int H, int W, int h, int w, int y0, int x0, const int32_t* boxes_yx,
+                          int standard, int full_range, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
+                          const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, const float* a_y, const float* a_x,
+                          float lo, float k, void* stream);
+
 /* ---- counter-based decoder noise (csrc/noise.hip) ----------------------------------------------------------------------------
  * The noise planes of a synthesis pass as a pure function of (seed, frame, layer, pixel): no generator state, so a clip comes
  * out the same whatever the chunking or the sharding over devices, and a fixed-noise clip is every frame on one frame index.
@@ -782,6 +844,13 @@ typedef struct spk_maxpool3x3s2_args {   /* in_scale / in_shift NULL: a plain in
 } spk_maxpool3x3s2_args;
 typedef struct spk_global_avgpool_args { const float* x; float* y; int64_t planes; int64_t HW; } spk_global_avgpool_args;
 typedef struct spk_frames_to_u8_args { const float* x; uint8_t* y; int32_t N, H, W, swap_rb; float lo, k; } spk_frames_to_u8_args;
+/* The op kinds continue (kind 13).  desc: spk_frames_to_nv12_args -> spk_frames_f32_to_nv12 (a decoder plan that ends in NV12
+ * surfaces: x [N,3,H,W] fp32, the Y and UV planes by pointer and byte strides). */
+enum { SPK_OP_FRAMES_TO_NV12 = SPK_OP_NOISE_FILL + 1 };
+typedef struct spk_frames_to_nv12_args {
+    const float* x; uint8_t* y; uint8_t* uv; int64_t y_image_stride, y_row_stride, uv_image_stride, uv_row_stride;
+    int32_t N, H, W, standard, full_range; float lo, k; int32_t reserved;
+} spk_frames_to_nv12_args;
 int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask, void* stream);
 
 #ifdef __cplusplus

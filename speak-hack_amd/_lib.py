@@ -95,6 +95,7 @@ OP_CONV2D, OP_FC, OP_FC_GROUPED, OP_BIAS_NOISE_STYLE, OP_TORGB, OP_DEMOD_GROUPED
 OP_MAXPOOL3X3S2, OP_GLOBAL_AVGPOOL = 9, 10
 OP_FRAMES_TO_U8 = 11
 OP_NOISE_FILL = 12
+OP_FRAMES_TO_NV12 = 13
 ALL_OPS = 0xFFFFFFFF
 
 NOISE_MAX_LAYERS = 16
@@ -154,6 +155,13 @@ class FramesToU8Args(C.Structure):
     """``spk_frames_to_u8_args`` (include/spk.h)."""
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("swap_rb", C.c_int32),
                 ("lo", C.c_float), ("k", C.c_float)]
+
+
+class FramesToNv12Args(C.Structure):
+    """``spk_frames_to_nv12_args`` (include/spk.h)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("uv", C.c_void_p), ("y_image_stride", C.c_int64), ("y_row_stride", C.c_int64),
+                ("uv_image_stride", C.c_int64), ("uv_row_stride", C.c_int64), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("standard", C.c_int32), ("full_range", C.c_int32), ("lo", C.c_float), ("k", C.c_float), ("reserved", C.c_int32)]
 
 
 class PixelNormArgs(C.Structure):
@@ -305,6 +313,17 @@ _PROTOTYPES = {
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    "spk_yuv_coeffs": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "spk_frames_nv12_to_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_f32_to_nv12": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "spk_frames_paste_nv12": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
     "spk_noise_bits_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "spk_noise_fill": (C.c_int, [C.POINTER(NoiseFillArgs), C.c_void_p]),
 }

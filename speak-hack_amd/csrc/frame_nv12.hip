@@ -1,0 +1,326 @@
+// The video-frame edge in NV12 form: what a hardware decoder / encoder holds in device memory -- a full-resolution Y plane and a
+// half-resolution interleaved UV plane, each with its own row pitch -- in and out of the network without a packed-RGB detour.
+//   frames_nv12_to_f32: crop (origin by value or per frame from a device array) + antialiased bilinear resize of the three
+//   component fields + YUV -> RGB + normalise -> CHW, one pass, no scratch;
+//   frames_paste_nv12: resize to the box + quantise + RGB -> YUV + feather-blend into the surface the box came from, one pass,
+//   one thread per chroma block (2 x 2 luma pixels); frames_f32_to_nv12 is its whole-frame case without tables.
+// Definitions (siting, colour matrices, the order of every operation) are in include/spk.h.  The resize tables are those of
+// csrc/frame_io.hip (spk_resize_table, spk_feather_table): this file holds no filter arithmetic and links without that one.
+#include "spk_common.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+namespace {
+
+constexpr int STRIP = 8;            // output rows a thread of the resize owns
+constexpr int GRID_CAP = 2048;      // workgroups per launch; the rest of the work is a grid-stride trip
+
+struct Affine3 { float scale[3], shift[3]; };
+struct Mat34 { double m[12]; };     // three rows [a0 a1 a2 offset], byte units
+
+// row c of a 3 x 4 affine map applied to (p0, p1, p2, 1): one fp64 fma chain that starts from the offset
+__device__ __forceinline__ double affine_row(const Mat34& M, int c, double p0, double p1, double p2) {
+    return fma(M.m[4 * c + 2], p2, fma(M.m[4 * c + 1], p1, fma(M.m[4 * c], p0, M.m[4 * c + 3])));
+}
+
+// (Kr, Kb) of a standard; false: unknown
+bool primaries(int standard, double* kr, double* kb) {
+    if (standard == 601) { *kr = 0.299; *kb = 0.114; return true; }
+    if (standard == 709) { *kr = 0.2126; *kb = 0.0722; return true; }
+    return false;
+}
+
+void yuv_coeffs(double kr, double kb, bool full, double* to_rgb, double* from_rgb) {
+    const double kg = 1.0 - kr - kb;
+    const double sy = full ? 1.0 : 219.0 / 255.0, sc = full ? 1.0 : 224.0 / 255.0, oy = full ? 0.0 : 16.0;
+    if (from_rgb) {
+        const double cb = sc / (2.0 * (1.0 - kb)), cr = sc / (2.0 * (1.0 - kr));
+        const double f[12] = {sy * kr, sy * kg, sy * kb, oy,
+                              -kr * cb, -kg * cb, (1.0 - kb) * cb, 128.0,
+                              (1.0 - kr) * cr, -kg * cr, -kb * cr, 128.0};
+        std::copy(f, f + 12, from_rgb);
+    }
+    if (to_rgb) {
+        const double ay = 1.0 / sy, rv = 2.0 * (1.0 - kr) / sc, bu = 2.0 * (1.0 - kb) / sc;
+        const double gu = -kb * bu / kg, gv = -kr * rv / kg;
+        const double t[12] = {ay, 0.0, rv, -(ay * oy + 128.0 * rv),
+                              ay, gu, gv, -(ay * oy + 128.0 * (gu + gv)),
+                              ay, bu, 0.0, -(ay * oy + 128.0 * bu)};
+        std::copy(t, t + 12, to_rgb);
+    }
+}
+
+// ---- in ----
+// A thread owns output column ox of one STRIP-row strip of one frame, as frames_u8_to_f32_kernel does, and carries the three
+// component fields Y, U, V of the box through the separable sum in fp64 (same tables, same order of additions); the colour matrix,
+// the clamp and the normalisation follow the resize (both are linear, so they commute up to the clamp: see include/spk.h).  Per
+// input row the luma window is byte loads (a box column has no alignment); the chroma window is 16-bit loads of packed (U, V)
+// pairs, a pair serving the two luma columns above it, and its horizontal sums are formed once per chroma row: a chroma row
+// serves two luma rows.  The origin is clamped so that the Hin x Win box lies inside the H x W frame and every window is clamped
+// into the box, so neither a tracker's origin nor a foreign table can send a load out of bounds.
+__global__ __launch_bounds__(256) void frames_nv12_to_f32_kernel(const uint8_t* __restrict__ yp, long long y_image_stride, long long y_row_stride,
+                                                                 const uint8_t* __restrict__ uvp, long long uv_image_stride,
+                                                                 long long uv_row_stride, const int* __restrict__ boxes_yx, int y0, int x0,
+                                                                 int H, int W, int Hin, int Win, int swap_rb,
+                                                                 const int* __restrict__ first_y, const int* __restrict__ count_y,
+                                                                 const float* __restrict__ w_y, int taps_y, const int* __restrict__ first_x,
+                                                                 const int* __restrict__ count_x, const float* __restrict__ w_x, int taps_x,
+                                                                 float* __restrict__ dst, int Hout, int Wout, int strips, long long total,
+                                                                 Affine3 af, Mat34 to_rgb) {
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const int ox = (int)(idx % Wout);
+        const int strip = (int)((idx / Wout) % strips);
+        const long long n = idx / ((long long)Wout * strips);
+        const int oy0 = strip * STRIP;
+        const int fx = min(max(first_x[ox], 0), Win - 1);
+        const int cx = max(min(min(count_x[ox], taps_x), Win - fx), 0);
+        int fy[STRIP], cy[STRIP];
+        int row_lo = Hin, row_hi = 0;
+#pragma unroll
+        for (int k = 0; k < STRIP; ++k) {
+            const int oy = min(oy0 + k, Hout - 1);
+            fy[k] = min(max(first_y[oy], 0), Hin - 1);
+            cy[k] = oy0 + k < Hout ? max(min(min(count_y[oy], taps_y), Hin - fy[k]), 0) : 0;
+            if (cy[k] > 0) { row_lo = min(row_lo, fy[k]); row_hi = max(row_hi, fy[k] + cy[k]); }
+        }
+        double acc[STRIP][3];
+#pragma unroll
+        for (int k = 0; k < STRIP; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
+        const int Y0 = min(max(boxes_yx ? boxes_yx[2 * n] : y0, 0), H - Hin), X0 = min(max(boxes_yx ? boxes_yx[2 * n + 1] : x0, 0), W - Win);
+        const int Xs = X0 + fx;                                  // frame column of the window's first tap
+        const uint8_t* luma = yp + n * y_image_stride + Xs;
+        const uint8_t* chroma = uvp + n * uv_image_stride;
+        const float* wx = w_x + (long long)ox * taps_x;
+        double hu = 0.0, hv = 0.0;
+        for (int iy = row_lo; iy < row_hi; ++iy) {
+            const int Yf = Y0 + iy;
+            if (iy == row_lo || !(Yf & 1)) {                     // a new chroma row: its sums serve this luma row and the next
+                const uint8_t* c = chroma + (long long)(Yf >> 1) * uv_row_stride;
+                unsigned pair = 0;
+                hu = hv = 0.0;
+                for (int j = 0; j < cx; ++j) {
+                    const int X = Xs + j;
+                    if (j == 0 || !(X & 1)) pair = *reinterpret_cast<const uint16_t*>(c + (X & ~1));
+                    const double w = (double)wx[j];
+                    hu = fma(w, (double)(pair & 0xffu), hu);
+                    hv = fma(w, (double)(pair >> 8), hv);
+                }
+            }
+            const uint8_t* p = luma + (long long)Yf * y_row_stride;
+            double hy = 0.0;
+            for (int j = 0; j < cx; ++j) hy = fma((double)wx[j], (double)p[j], hy);
+#pragma unroll
+            for (int k = 0; k < STRIP; ++k) {
+                const int j = iy - fy[k];
+                if ((unsigned)j < (unsigned)cy[k]) {
+                    const double w = (double)w_y[(long long)(oy0 + k) * taps_y + j];
+                    acc[k][0] = fma(w, hy, acc[k][0]);
+                    acc[k][1] = fma(w, hu, acc[k][1]);
+                    acc[k][2] = fma(w, hv, acc[k][2]);
+                }
+            }
+        }
+        const long long plane = (long long)Hout * Wout;
+        float* out = dst + n * 3 * plane + ox;
+#pragma unroll
+        for (int k = 0; k < STRIP; ++k) {
+            if (oy0 + k >= Hout) break;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {                        // c: R, G, B
+                const double rgb = fmin(fmax(affine_row(to_rgb, c, acc[k][0], acc[k][1], acc[k][2]), 0.0), 255.0);
+                const int cd = swap_rb ? 2 - c : c;
+                out[cd * plane + (long long)(oy0 + k) * Wout] = (float)fma((double)af.scale[cd], rgb, (double)af.shift[cd]);
+            }
+        }
+    }
+}
+
+// ---- out ----
+// A thread owns one chroma sample of one frame and the 2 x 2 luma pixels under it (x fastest: a wave writes 64 consecutive UV
+// pairs and two runs of 128 consecutive Y bytes).  blocks_y x blocks_x = (h / 2 + 1) x (w / 2 + 1) blocks per frame cover a box of
+// either parity (with device origins the host cannot know it); block (by, bx) is chroma sample (floor(Y0 / 2) + by,
+// floor(X0 / 2) + bx).  H and W are even, so a block lies wholly inside or wholly outside the frame: a block outside is skipped
+// before any load, and so is every pixel of a block that the box does not hold.  Per pixel: the fp64 resize of the fp32 source with
+// the tables and sums of frames_paste_u8_kernel (RESIZE false: the source pixel itself, which is what identity tables give), the
+// fp32 quantise chain without its rounding, RGB -> YUV in fp64, the luma byte blended and stored; the chroma terms are added up
+// over the block's pixels in row-major order and blended into the one UV pair the thread reads and writes (16 bits).  A thread
+// reads no byte it does not write, so the surfaces may be pasted in place.
+template <bool RESIZE>
+__global__ __launch_bounds__(256) void frames_paste_nv12_kernel(const float* __restrict__ src, int Hs, int Ws, uint8_t* yp, long long y_image_stride,
+                                                                long long y_row_stride, uint8_t* uvp, long long uv_image_stride,
+                                                                long long uv_row_stride, int H, int W, int h, int w, int y0, int x0,
+                                                                const int* __restrict__ boxes_yx, const int* __restrict__ first_y,
+                                                                const int* __restrict__ count_y, const float* __restrict__ w_y, int taps_y,
+                                                                const int* __restrict__ first_x, const int* __restrict__ count_x,
+                                                                const float* __restrict__ w_x, int taps_x, const float* __restrict__ a_y,
+                                                                const float* __restrict__ a_x, float lo, float k, int blocks_y, int blocks_x,
+                                                                long long total, Mat34 from_rgb) {
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const int bx = (int)(idx % blocks_x);
+        const int by = (int)((idx / blocks_x) % blocks_y);
+        const long long n = idx / ((long long)blocks_x * blocks_y);
+        const long long Y0 = boxes_yx ? boxes_yx[2 * n] : y0, X0 = boxes_yx ? boxes_yx[2 * n + 1] : x0;
+        const long long CY = (Y0 - (Y0 & 1)) / 2 + by, CX = (X0 - (X0 & 1)) / 2 + bx;       // floor(origin / 2) + block
+        if (CY < 0 || CY >= H / 2 || CX < 0 || CX >= W / 2) continue;
+        const long long plane = (long long)Hs * Ws;
+        const float* img = src + n * 3 * plane;
+        uint8_t* luma = yp + n * y_image_stride;
+        double acc_u = 0.0, acc_v = 0.0, S = 0.0;
+        bool any = false;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {                            // row-major over the block
+            const long long Yf = 2 * CY + (d >> 1), Xf = 2 * CX + (d & 1);
+            const long long yl = Yf - Y0, xl = Xf - X0;
+            if (yl < 0 || yl >= h || xl < 0 || xl >= w) continue;
+            const int y = (int)yl, x = (int)xl;
+            double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+            if (RESIZE) {
+                // the tables are the caller's: clamp every window into the source so that no table can send a load out of bounds
+                const int fx = min(max(first_x[x], 0), Ws - 1), cx = max(min(min(count_x[x], taps_x), Ws - fx), 0);
+                const int fy = min(max(first_y[y], 0), Hs - 1), cy = max(min(min(count_y[y], taps_y), Hs - fy), 0);
+                const float* wx = w_x + (long long)x * taps_x;
+                const float* wy = w_y + (long long)y * taps_y;
+                const float* in = img + (long long)fy * Ws + fx;
+                for (int i = 0; i < cy; ++i) {
+                    const float* p = in + (long long)i * Ws;
+                    double h0 = 0.0, h1 = 0.0, h2 = 0.0;
+                    for (int j = 0; j < cx; ++j) {
+                        const double wj = (double)wx[j];
+                        h0 = fma(wj, (double)p[j], h0);
+                        h1 = fma(wj, (double)p[plane + j], h1);
+                        h2 = fma(wj, (double)p[2 * plane + j], h2);
+                    }
+                    const double wi = (double)wy[i];
+                    v0 = fma(wi, h0, v0);
+                    v1 = fma(wi, h1, v1);
+                    v2 = fma(wi, h2, v2);
+                }
+            } else {
+                const float* in = img + (long long)y * Ws + x;
+                v0 = (double)in[0]; v1 = (double)in[plane]; v2 = (double)in[2 * plane];
+            }
+            const double q0 = (double)fminf(fmaxf(__fmul_rn(__fsub_rn((float)v0, lo), k), 0.f), 255.f);
+            const double q1 = (double)fminf(fmaxf(__fmul_rn(__fsub_rn((float)v1, lo), k), 0.f), 255.f);
+            const double q2 = (double)fminf(fmaxf(__fmul_rn(__fsub_rn((float)v2, lo), k), 0.f), 255.f);
+            const double e_y = affine_row(from_rgb, 0, q0, q1, q2), e_u = affine_row(from_rgb, 1, q0, q1, q2),
+                         e_v = affine_row(from_rgb, 2, q0, q1, q2);
+            const double m = a_y ? (double)a_y[y] * (double)a_x[x] : 1.0;
+            uint8_t* py = luma + Yf * y_row_stride + Xf;
+            *py = (uint8_t)(int)rint(fmin(fmax(fma(1.0 - m, (double)*py, m * e_y), 0.0), 255.0));
+            const double qm = 0.25 * m;
+            acc_u = fma(qm, e_u, acc_u);
+            acc_v = fma(qm, e_v, acc_v);
+            S += qm;
+            any = true;
+        }
+        if (!any) continue;
+        uint16_t* pc = reinterpret_cast<uint16_t*>(uvp + n * uv_image_stride + CY * uv_row_stride + CX * 2);
+        const unsigned pair = *pc;
+        const unsigned u = (unsigned)(int)rint(fmin(fmax(fma(1.0 - S, (double)(pair & 0xffu), acc_u), 0.0), 255.0));
+        const unsigned v = (unsigned)(int)rint(fmin(fmax(fma(1.0 - S, (double)(pair >> 8), acc_v), 0.0), 255.0));
+        *pc = (uint16_t)(u | v << 8);
+    }
+}
+
+// the checks every NV12 surface argument gets; 0: fine
+int check_surface(const char* who, const void* y, int64_t y_image_stride, int64_t y_row_stride, const void* uv, int64_t uv_image_stride,
+                  int64_t uv_row_stride, int N, int H, int W, bool written) {
+    SPK_REQUIRE(y && uv, "%s: null plane pointer", who);
+    SPK_REQUIRE(N >= 1 && H >= 2 && W >= 2, "%s: N must be >= 1 and H, W >= 2 (N %d, %d x %d)", who, N, H, W);
+    SPK_REQUIRE(H % 2 == 0 && W % 2 == 0, "%s: NV12 frames have an even height and width (got %d x %d)", who, H, W);
+    SPK_REQUIRE((uintptr_t)uv % 2 == 0, "%s: the UV plane must be 2-byte aligned", who);
+    SPK_REQUIRE(uv_row_stride % 2 == 0 && uv_image_stride % 2 == 0, "%s: the UV strides must be even (row %lld, image %lld)", who,
+                (long long)uv_row_stride, (long long)uv_image_stride);
+    SPK_REQUIRE(y_row_stride >= (long long)W, "%s: Y row stride %lld is smaller than W = %d", who, (long long)y_row_stride, W);
+    SPK_REQUIRE(uv_row_stride >= (long long)W, "%s: UV row stride %lld is smaller than the row's %d bytes", who, (long long)uv_row_stride, W);
+    if (written) {
+        SPK_REQUIRE(N == 1 || (y_image_stride >= (long long)(H - 1) * y_row_stride + W && uv_image_stride >= (long long)(H / 2 - 1) * uv_row_stride + W),
+                    "%s: image strides %lld / %lld make the frames overlap (%d rows of stride %lld / %lld)", who, (long long)y_image_stride,
+                    (long long)uv_image_stride, H, (long long)y_row_stride, (long long)uv_row_stride);
+    } else {
+        SPK_REQUIRE(y_image_stride >= 0 && uv_image_stride >= 0, "%s: negative image stride", who);
+    }
+    return SPK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spk_yuv_coeffs(int standard, int full_range, double to_rgb[12], double from_rgb[12]) {
+    double kr, kb;
+    SPK_REQUIRE(primaries(standard, &kr, &kb), "yuv_coeffs: standard must be 601 or 709 (got %d)", standard);
+    SPK_REQUIRE(full_range == 0 || full_range == 1, "yuv_coeffs: full_range must be 0 or 1 (got %d)", full_range);
+    SPK_REQUIRE(to_rgb || from_rgb, "yuv_coeffs: null matrix pointers");
+    yuv_coeffs(kr, kb, full_range != 0, to_rgb, from_rgb);
+    return SPK_OK;
+}
+
+int spk_frames_nv12_to_f32(const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, const uint8_t* uv, int64_t uv_image_stride,
+                           int64_t uv_row_stride, int N, int H, int W, const int32_t* boxes_yx, int y0, int x0, int Hin, int Win, int swap_rb,
+                           int standard, int full_range, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
+                           const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout,
+                           float scale0, float scale1, float scale2, float shift0, float shift1, float shift2, void* stream) {
+    if (int rc = check_surface("frames_nv12_to_f32", y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, N, H, W, false)) return rc;
+    SPK_REQUIRE(dst, "frames_nv12_to_f32: null frame pointer");
+    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_nv12_to_f32: null table pointer");
+    SPK_REQUIRE(Hin >= 1 && Win >= 1 && Hout >= 1 && Wout >= 1, "frames_nv12_to_f32: box and output sizes must be >= 1 (%d x %d -> %d x %d)", Hin,
+                Win, Hout, Wout);
+    SPK_REQUIRE(H >= Hin && W >= Win, "frames_nv12_to_f32: the %d x %d box does not fit the %d x %d frame", Hin, Win, H, W);
+    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_nv12_to_f32: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
+    Mat34 M;
+    if (int rc = spk_yuv_coeffs(standard, full_range, M.m, nullptr)) return rc;
+    const int strips = spk::ceil_div(Hout, STRIP);
+    const long long total = (long long)N * strips * Wout;
+    Affine3 af = {{scale0, scale1, scale2}, {shift0, shift1, shift2}};
+    hipLaunchKernelGGL(frames_nv12_to_f32_kernel, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, y, N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv,
+                       N > 1 ? (long long)uv_image_stride : 0ll, (long long)uv_row_stride, (const int*)boxes_yx, y0, x0, H, W, Hin, Win, swap_rb,
+                       first_y, count_y, w_y, taps_y, first_x, count_x, w_x, taps_x, dst, Hout, Wout, strips, total, af, M);
+    return spk::check_launch("frames_nv12_to_f32_kernel");
+}
+
+int spk_frames_paste_nv12(const float* src, int N, int Hs, int Ws, uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, uint8_t* uv,
+                          int64_t uv_image_stride, int64_t uv_row_stride, int H, int W, int h, int w, int y0, int x0, const int32_t* boxes_yx,
+                          int standard, int full_range, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
+                          const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, const float* a_y, const float* a_x,
+                          float lo, float k, void* stream) {
+    SPK_REQUIRE(src, "frames_paste_nv12: null frame pointer");
+    if (int rc = check_surface("frames_paste_nv12", y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, N, H, W, true)) return rc;
+    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_paste_nv12: null table pointer");
+    SPK_REQUIRE((a_y == nullptr) == (a_x == nullptr), "frames_paste_nv12: the feather tables are both given or both null");
+    SPK_REQUIRE(Hs >= 1 && Ws >= 1 && h >= 1 && w >= 1, "frames_paste_nv12: source and box sizes must be >= 1 (source %d x %d, box %d x %d)", Hs, Ws,
+                h, w);
+    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_paste_nv12: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
+    SPK_REQUIRE(std::isfinite(lo) && std::isfinite(k) && k > 0.f, "frames_paste_nv12: the value range must be finite and increasing");
+    Mat34 M;
+    if (int rc = spk_yuv_coeffs(standard, full_range, nullptr, M.m)) return rc;
+    const int blocks_y = h / 2 + 1, blocks_x = w / 2 + 1;
+    const long long total = (long long)N * blocks_y * blocks_x;
+    hipLaunchKernelGGL(frames_paste_nv12_kernel<true>, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, src, Hs, Ws, y, N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv,
+                       N > 1 ? (long long)uv_image_stride : 0ll, (long long)uv_row_stride, H, W, h, w, y0, x0, (const int*)boxes_yx, first_y, count_y,
+                       w_y, taps_y, first_x, count_x, w_x, taps_x, a_y, a_x, lo, k, blocks_y, blocks_x, total, M);
+    return spk::check_launch("frames_paste_nv12_kernel");
+}
+
+int spk_frames_f32_to_nv12(const float* src, int N, int H, int W, uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, uint8_t* uv,
+                           int64_t uv_image_stride, int64_t uv_row_stride, int standard, int full_range, float lo, float k, void* stream) {
+    SPK_REQUIRE(src, "frames_f32_to_nv12: null frame pointer");
+    if (int rc = check_surface("frames_f32_to_nv12", y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, N, H, W, true)) return rc;
+    SPK_REQUIRE(std::isfinite(lo) && std::isfinite(k) && k > 0.f, "frames_f32_to_nv12: the value range must be finite and increasing");
+    Mat34 M;
+    if (int rc = spk_yuv_coeffs(standard, full_range, nullptr, M.m)) return rc;
+    const int blocks_y = H / 2, blocks_x = W / 2;            // the origin is (0, 0): the blocks of the frame, none empty
+    const long long total = (long long)N * blocks_y * blocks_x;
+    hipLaunchKernelGGL(frames_paste_nv12_kernel<false>, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, src, H, W, y, N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv,
+                       N > 1 ? (long long)uv_image_stride : 0ll, (long long)uv_row_stride, H, W, H, W, 0, 0, (const int*)nullptr, (const int*)nullptr,
+                       (const int*)nullptr, (const float*)nullptr, 1, (const int*)nullptr, (const int*)nullptr, (const float*)nullptr, 1,
+                       (const float*)nullptr, (const float*)nullptr, lo, k, blocks_y, blocks_x, total, M);
+    return spk::check_launch("frames_paste_nv12_kernel<whole frame>");
+}
+
+}  // extern "C"

@@ -72,6 +72,12 @@ extern "C" int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask,
                 rc = spk_frames_f32_to_u8(a->x, a->y, a->N, a->H, a->W, a->swap_rb, a->lo, a->k, stream);
                 break;
             }
+            case SPK_OP_FRAMES_TO_NV12: {
+                const spk_frames_to_nv12_args* a = static_cast<const spk_frames_to_nv12_args*>(op.desc);
+                rc = spk_frames_f32_to_nv12(a->x, a->N, a->H, a->W, a->y, a->y_image_stride, a->y_row_stride, a->uv, a->uv_image_stride,
+                                            a->uv_row_stride, a->standard, a->full_range, a->lo, a->k, stream);
+                break;
+            }
             case SPK_OP_NOISE_FILL:
                 rc = spk_noise_fill(static_cast<const spk_noise_fill_args*>(op.desc), stream);
                 break;

@@ -277,10 +277,11 @@ class StyleGenerator(nn.Module):
         return syn.use_plan and features.is_cuda and features.dim() == 2 and len(syn.layers) * 2 + 1 <= ops.L.FC_MAX_GROUPS
 
     def plan_forward(self, features, noises=None, *, output="f32", value_range=(-1, 1), swap_rb=False, seed=None, frame0=0,
-                     fixed_noise=False):
+                     fixed_noise=False, standard="bt601", full_range=False):
         """The eval forward -- mapping, truncation, synthesis; no style mixing, no host-RNG draw -- on the inference launch plan,
         whatever ``self.training`` is (no module state is read or touched).  No gradient flows through it.  ``output="uint8"``:
-        the plan ends in the quantising op and returns uint8 [B,R,R,3] frames (``plan.DecoderPlan``).  ``seed``: a seeded plan
+        the plan ends in the quantising op and returns uint8 [B,R,R,3] frames (``plan.DecoderPlan``); ``output="nv12"``: it ends in
+        the NV12 op and returns uint8 [B,3R/2,R] surfaces in the colour of ``standard`` / ``full_range``.  ``seed``: a seeded plan
         (a cache entry of its own) draws the noise of ``ops.decoder_noise(shapes, seed, frame0=frame0, fixed=fixed_noise)`` as
         the first op of its list."""
         syn = self.synthesis
@@ -296,13 +297,15 @@ class StyleGenerator(nn.Module):
         # (the truncation scale is folded into the style FCs' multipliers when the plan is built: part of the key)
         key = (B, features.device, torch.cuda.current_stream(features.device).cuda_stream, "features", syn.precision,
                self.truncation_psi, self.truncation_cutoff)
-        if output != "f32":
+        if output == "nv12":
+            key += (output, float(value_range[0]), float(value_range[1]), *ops._yuv_standard(standard, full_range))
+        elif output != "f32":
             key += (output, float(value_range[0]), float(value_range[1]), bool(swap_rb))
         if seed is not None:
             key += ("seeded",)
         p = PL.plan_for(self, key, lambda: PL.DecoderPlan(syn, B, features.device, generator=self, precision=syn.precision,
                                                           output=output, value_range=value_range, swap_rb=swap_rb,
-                                                          seeded=seed is not None))
+                                                          seeded=seed is not None, standard=standard, full_range=full_range))
         features = features if features.stride(1) == 1 else features.contiguous()
         if seed is not None:
             return p.run(features, seed=seed, frame0=frame0, fixed_noise=fixed_noise)

@@ -93,7 +93,7 @@ class IRFD(nn.Module):
 
     @torch.no_grad()
     def reenact(self, identity_image, pose_frames, emotion_frames=None, *, noises=None, chunk=8, output="f32", channel_order="rgb",
-                seed=None, noise="fresh", frame0=0):
+                seed=None, noise="fresh", frame0=0, standard="bt601", full_range=False):
         """Talking-head frames: ``Gd(cat(Ei(identity).expand(T), Ee(emotion_frames), Ep(pose_frames)))`` in the feature order
         of ``_prepare_generator_input(fi, fe, fp)`` (model.py:64-69,107), in eval arithmetic whatever ``self.training`` is: no
         buffer update, no host-RNG draw, no swap, no style mixing, truncation as ``StyleGenerator.forward`` applies it in eval.
@@ -101,7 +101,9 @@ class IRFD(nn.Module):
         explicit list ``StyleGenerator.forward`` takes, for T frames (default: drawn on the device).  ``Ei`` runs once; the
         frames go through the encoder and decoder plans ``chunk`` at a time.  -> frames [T,3,R,R] fp32; with ``output="uint8"``
         uint8 [T,R,R,3] in ``channel_order`` ("rgb" | "bgr"), quantised from (-1, 1) by the last op of the decoder plan --
-        ``ops.frames_to_u8`` of the fp32 result, bit for bit.
+        ``ops.frames_to_u8`` of the fp32 result, bit for bit.  ``output="nv12"``: uint8 [T,3R/2,R] NV12 surfaces (rows ``R..`` are the
+        interleaved UV plane) in the colour of ``standard`` ("bt601" | "bt709") / ``full_range``, converted by the last op of the
+        decoder plan -- ``ops.frames_to_nv12`` of the fp32 result, bit for bit.
 
         ``seed`` (0 <= seed < 2**64; not together with ``noises``): reproducible noise, a function of (seed, frame index,
         layer, pixel) drawn inside the decoder's launch list (``ops.decoder_noise`` gives the same tensors explicitly); the
@@ -109,14 +111,18 @@ class IRFD(nn.Module):
         frames ``[a, b)`` of a longer clip may be rendered elsewhere with ``frame0=a``.  ``noise="fixed"`` (needs a seed): every
         frame uses frame index ``frame0`` -- one noise image per layer held over the clip, as StyleGAN video pipelines do
         against boiling texture; ``"fresh"`` (default): new noise on every frame."""
+        if output != "nv12" and (standard != "bt601" or full_range):
+            raise ValueError("reenact: standard / full_range apply to nv12 output only")
         out = [y for _, _, y in self._reenact_chunks(identity_image, pose_frames, emotion_frames, noises, chunk, output, channel_order,
-                                                     seed, noise, frame0)]
+                                                     seed, noise, frame0, (standard, full_range))]
         return out[0] if len(out) == 1 else torch.cat(out, 0)
 
-    def _reenact_chunks(self, identity_image, pose_frames, emotion_frames, noises, chunk, output, channel_order, seed, noise, frame0):
+    def _reenact_chunks(self, identity_image, pose_frames, emotion_frames, noises, chunk, output, channel_order, seed, noise, frame0,
+                        colour=("bt601", False)):
         """``reenact``'s argument checks and chunk loop: yields ``(t0, t1, frames of [t0, t1))``."""
-        if output not in ("f32", "uint8"):
-            raise ValueError(f"reenact: output must be 'f32' or 'uint8', got {output!r}")
+        if output not in ("f32", "uint8", "nv12"):
+            raise ValueError(f"reenact: output must be 'f32', 'uint8' or 'nv12', got {output!r}")
+        ops._yuv_standard(*colour)
         if noise not in ("fresh", "fixed"):
             raise ValueError(f"reenact: noise must be 'fresh' or 'fixed', got {noise!r}")
         if seed is None and noise == "fixed":
@@ -129,7 +135,7 @@ class IRFD(nn.Module):
             raise ValueError("reenact: frame0 applies to seeded noise only")
         if channel_order not in ("rgb", "bgr"):
             raise ValueError(f"reenact: channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
-        if output == "f32" and channel_order != "rgb":
+        if output != "uint8" and channel_order != "rgb":
             raise ValueError("reenact: channel_order applies to uint8 output only")
         if identity_image.dim() != 4 or identity_image.size(0) != 1 or identity_image.size(1) != 3:
             raise ValueError(f"reenact: identity_image must be [1,3,H,W], got {tuple(identity_image.shape)}")
@@ -150,11 +156,12 @@ class IRFD(nn.Module):
             fe, fp = self.encode(emotion_frames[t0:t1], "Ee"), self.encode(pose_frames[t0:t1], "Ep")
             gin = self._prepare_generator_input(fi.expand(t1 - t0, -1, -1, -1), fe, fp)
             seeded = None if seed is None else dict(seed=seed, frame0=frame0 if noise == "fixed" else frame0 + t0, fixed_noise=noise == "fixed")
-            yield t0, t1, self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises], output, channel_order, seeded)
+            yield t0, t1, self._decode_eval(gin, None if noises is None else [n[t0:t1] for n in noises], output, channel_order, seeded, colour)
 
     @torch.no_grad()
     def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8,
-                      seed=None, noise="fresh", frame0=0, paste=False, feather=0, inplace=False):
+                      seed=None, noise="fresh", frame0=0, paste=False, feather=0, inplace=False, pixel_format="rgb24", standard="bt601",
+                      full_range=False):
         """``reenact`` from and to video frames as a decoder and a video writer hold them (inference.py:29-33,46-58,78-86):
         uint8 HWC frames of any size on the device in, uint8 [T,R,R,3] out, both in ``channel_order`` ("bgr": ``cv2``'s).
         Nothing but ``ops.frames_from_u8`` -> ``reenact(output="uint8")``: ``identity_u8`` [H,W,3] or [1,H,W,3] is resized whole
@@ -167,7 +174,19 @@ class IRFD(nn.Module):
         and pasted where the crop came from (``crop=None``: the whole frame), blended over ``feather`` pixels at the box's
         edge (``ops.frames_paste_u8``).  The result is one clone of ``pose_u8`` (``inplace=True``: ``pose_u8`` itself); each
         chunk's fp32 decoder result is pasted straight into its slice, one ``spk_frames_paste_u8`` launch per chunk, and
-        per-frame boxes are taken per frame, so the result does not depend on ``chunk``."""
+        per-frame boxes are taken per frame, so the result does not depend on ``chunk``.
+
+        ``pixel_format="nv12"``: ``pose_u8`` / ``emotion_u8`` are NV12 as a hardware decoder leaves them -- one uint8 tensor
+        ``[T,3H/2,W]`` (any row pitch; rows ``H..`` are the UV plane) or a pair ``(y [T,H,W], uv [T,H/2,W/2,2])``
+        (``ops.nv12_planes``), in the colour of ``standard`` ("bt601" | "bt709") / ``full_range`` -- and so is the result:
+        ``[T,3R/2,R]``, or with ``paste=True`` the pose surfaces with every face pasted back (``ops.frames_from_nv12``,
+        ``reenact(output="nv12")``, ``ops.frames_paste_nv12``: one launch per chunk).  The identity image stays a uint8 HWC photo
+        in ``channel_order``; ``crop`` keeps its three forms and may have an odd origin."""
+        if pixel_format not in ("rgb24", "nv12"):
+            raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
+        if pixel_format == "rgb24" and (standard != "bt601" or full_range):
+            raise ValueError("reenact_video: standard / full_range apply to pixel_format='nv12' only")
+        ops._yuv_standard(standard, full_range)
         feather = float(feather)
         if inplace and not paste:
             raise ValueError("reenact_video: inplace applies to paste=True only")
@@ -183,6 +202,9 @@ class IRFD(nn.Module):
             if noises is not None:
                 raise ValueError("reenact_video: pass either seed or noises, not both")
             ops.check_seed(seed, frame0, "reenact_video: seed")
+        if pixel_format == "nv12":
+            return self._reenact_video_nv12(identity_u8, pose_u8, emotion_u8, size, crop, channel_order, noises, chunk, seed, noise, frame0,
+                                            paste, feather, inplace, (standard, full_range))
         if crop is not None or paste:
             if pose_u8.dim() != 4 or pose_u8.size(3) != 3 or pose_u8.size(0) < 1:
                 raise ValueError(f"reenact_video: pose_u8 must be [T,H,W,3], got {tuple(pose_u8.shape)}")
@@ -206,7 +228,38 @@ class IRFD(nn.Module):
                                 out=part)
         return frames
 
-    def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None):
+    def _reenact_video_nv12(self, identity_u8, pose_nv12, emotion_nv12, size, crop, channel_order, noises, chunk, seed, noise, frame0,
+                            paste, feather, inplace, colour):
+        """``reenact_video`` on NV12 surfaces (its arguments are checked there)."""
+        standard, full_range = colour
+        py, puv = ops.nv12_planes(pose_nv12)
+        T, H, W = py.shape
+        origins, h, w = ops.parse_boxes((0, 0, H, W) if crop is None else crop, T, H, W, "reenact_video: crop")
+        if not isinstance(origins, tuple) and not origins.is_cuda and py.is_cuda:
+            origins = origins.to(py.device)                               # host boxes: checked above, uploaded once for both edges
+        crop = (*origins, h, w) if isinstance(origins, tuple) else (origins, h, w)
+        if inplace:
+            ops._nv12_strides(py, puv, "reenact_video: inplace", written=True)
+        ident = ops.frames_from_u8(identity_u8, size, channel_order=channel_order)
+        pose = ops.frames_from_nv12((py, puv), size, crop=crop, standard=standard, full_range=full_range)
+        emo = None if emotion_nv12 is None else ops.frames_from_nv12(emotion_nv12, size, crop=crop, standard=standard, full_range=full_range)
+        if not paste:
+            return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output="nv12", seed=seed, noise=noise, frame0=frame0,
+                                standard=standard, full_range=full_range)
+        if inplace:
+            frames, fy, fuv = pose_nv12, py, puv
+        else:                                                             # one clone: a packed surface per frame
+            frames = torch.empty((T, 3 * H // 2, W), device=py.device, dtype=torch.uint8)
+            fy, fuv = ops.nv12_planes(frames)
+            fy.copy_(py)
+            fuv.copy_(puv)
+        for t0, t1, y in self._reenact_chunks(ident, pose, emo, noises, chunk, "f32", "rgb", seed, noise, frame0):
+            part = (fy[t0:t1], fuv[t0:t1])
+            ops.frames_paste_nv12(y, part, crop if len(crop) == 4 else (crop[0][t0:t1], h, w), feather=feather, standard=standard,
+                                  full_range=full_range, out=part)
+        return frames
+
+    def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None, colour=("bt601", False)):
         """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan
         does not serve runs its eval branch with every submodule's own ``training`` flag saved and put back.  ``seeded``: the
         ``seed`` / ``frame0`` / ``fixed_noise`` keywords of a seeded call (``StyleGenerator`` decoders), else None."""
@@ -215,6 +268,8 @@ class IRFD(nn.Module):
         if hasattr(Gd, "plan_serves") and Gd.plan_serves(gin):
             if output == "f32":
                 return Gd.plan_forward(gin, noises, **seeded)
+            if output == "nv12":
+                return Gd.plan_forward(gin, noises, output=output, standard=colour[0], full_range=colour[1], **seeded)
             return Gd.plan_forward(gin, noises, output=output, swap_rb=channel_order == "bgr", **seeded)
         flags = [(mod, mod.training) for mod in Gd.modules()]
         try:
@@ -224,6 +279,8 @@ class IRFD(nn.Module):
         finally:
             for mod, was in flags:
                 mod.training = was
+        if output == "nv12":
+            return ops.frames_to_nv12(y, standard=colour[0], full_range=colour[1])
         return y if output == "f32" else ops.frames_to_u8(y, channel_order=channel_order)
 
     def forward(self, x_s, x_t, swap_type=None, noises_s=None, noises_t=None):

@@ -1698,6 +1698,190 @@ def frames_paste_u8(x, frames_u8, box, *, feather=0, value_range=(-1, 1), channe
     return out
 
 
+# ---- the video-frame edge in NV12 form (csrc/frame_nv12.hip; the definitions are in include/spk.h) -----------------------------
+def _yuv_standard(standard, full_range):
+    if standard not in ("bt601", "bt709"):
+        raise ValueError(f"standard must be 'bt601' or 'bt709', got {standard!r}")
+    if not isinstance(full_range, (bool, int)) or full_range not in (0, 1):
+        raise ValueError(f"full_range must be a bool, got {full_range!r}")
+    return (601 if standard == "bt601" else 709), int(full_range)
+
+
+def yuv_coeffs(standard="bt601", full_range=False):
+    """The two 3 x 4 affine maps in byte units between R'G'B' 0..255 and the Y, U, V bytes (``spk_yuv_coeffs``, built in fp64 on the
+    host from the primaries): ``to_rgb`` rows R, G, B over ``(y, u, v, 1)``; ``from_rgb`` rows Y, U, V over ``(r, g, b, 1)``.
+    ``standard``: "bt601" | "bt709"; limited range (Y 16..235, C 16..240) unless ``full_range``.  -> two CPU float64 tensors [3,4]."""
+    std, full = _yuv_standard(standard, full_range)
+    to_rgb, from_rgb = (C.c_double * 12)(), (C.c_double * 12)()
+    L.check(L.lib().spk_yuv_coeffs(std, full, to_rgb, from_rgb), "spk_yuv_coeffs")
+    return torch.tensor(list(to_rgb), dtype=torch.float64).view(3, 4), torch.tensor(list(from_rgb), dtype=torch.float64).view(3, 4)
+
+
+def nv12_planes(nv12):
+    """The two planes of NV12 frames as views.  ``nv12``: one uint8 tensor ``[N, 3H/2, W]`` (or ``[3H/2, W]``), a decoder surface
+    with unit pixel stride and any row pitch whose rows ``H..`` are the UV plane; or a pair ``(y [N,H,W], uv [N,H/2,W/2,2])``
+    (planes that live apart).  ``H`` and ``W`` are even.  -> ``(y [N,H,W], uv [N,H/2,W/2,2])``, no copy."""
+    if isinstance(nv12, (tuple, list)):
+        if len(nv12) != 2 or not all(isinstance(t, torch.Tensor) for t in nv12):
+            raise ValueError("nv12: a pair must be (y [N,H,W], uv [N,H/2,W/2,2])")
+        y, uv = nv12
+        if y.dim() == 2 and uv.dim() == 3:
+            y, uv = y.unsqueeze(0), uv.unsqueeze(0)
+        if y.dim() != 3 or uv.dim() != 4 or y.size(0) < 1 or y.size(1) % 2 or y.size(2) % 2 or y.size(1) < 2 or y.size(2) < 2 or \
+                tuple(uv.shape) != (y.size(0), y.size(1) // 2, y.size(2) // 2, 2):
+            raise ValueError(f"nv12: planes must be y [N,H,W] and uv [N,H/2,W/2,2] with even H, W, got {tuple(y.shape)} and {tuple(uv.shape)}")
+        if y.dtype != torch.uint8 or uv.dtype != torch.uint8 or y.device != uv.device:
+            raise ValueError(f"nv12: planes must be uint8 tensors on one device, got {y.dtype} on {y.device} and {uv.dtype} on {uv.device}")
+        return y, uv
+    if not isinstance(nv12, torch.Tensor):
+        raise ValueError("nv12: expected a uint8 tensor [N,3H/2,W] or a pair of planes")
+    buf = nv12.unsqueeze(0) if nv12.dim() == 2 else nv12
+    if buf.dim() != 3 or buf.size(0) < 1 or buf.size(1) % 3 or buf.size(1) < 3 or buf.size(2) % 2 or buf.size(2) < 2:
+        raise ValueError(f"nv12: a surface must be [N,3H/2,W] with even H, W, got {tuple(nv12.shape)}")
+    if buf.dtype != torch.uint8:
+        raise ValueError(f"nv12: a surface must be uint8, got {buf.dtype}")
+    N, W = buf.size(0), buf.size(2)
+    H = buf.size(1) // 3 * 2
+    if buf.stride(2) != 1:
+        raise ValueError(f"nv12: a surface must have unit pixel stride, got strides {buf.stride()}")
+    return buf[:, :H], buf[:, H:].unflatten(2, (W // 2, 2))
+
+
+def _nv12_strides(y, uv, what, written):
+    """Byte strides of the two planes as the kernels take them, checked on the host."""
+    N, H, W = y.shape
+    if not y.is_cuda or y.dtype != torch.uint8 or not uv.is_cuda:
+        raise L.SpkError(f"{what}: expected uint8 HIP tensors, got {y.dtype} on {y.device} (no CPU path)")
+    if y.stride(2) != 1 or uv.stride(3) != 1 or uv.stride(2) != 2:
+        raise L.SpkError(f"{what}: the Y pixel stride must be 1 and a UV pair packed, got strides {y.stride()} and {uv.stride()}")
+    ys, us = (y.stride(0) if N > 1 else 0, y.stride(1)), (uv.stride(0) if N > 1 else 0, uv.stride(1))
+    if ys[1] < W or us[1] < W or uv.data_ptr() % 2 or us[0] % 2 or us[1] % 2:
+        raise L.SpkError(f"{what}: rows must hold W = {W} bytes and the UV plane be 2-byte aligned with even strides, "
+                         f"got strides {y.stride()} and {uv.stride()}")
+    if N > 1 and (ys[0] < 0 or us[0] < 0 or (written and (ys[0] < (H - 1) * ys[1] + W or us[0] < (H // 2 - 1) * us[1] + W))):
+        raise L.SpkError(f"{what}: frames must not overlap, got strides {y.stride()} and {uv.stride()}")
+    return ys, us
+
+
+def frames_from_nv12(nv12, size, *, crop=None, channel_order="rgb", mean=0.5, std=0.5, standard="bt601", full_range=False):
+    """NV12 video frames -> the network's input, one launch (``spk_frames_nv12_to_f32``): crop, antialiased bilinear resize of the
+    Y, U and V fields to ``size`` x ``size`` (a number, or ``(H, W)``), YUV -> RGB (``yuv_coeffs``), clamp to 0..255 and
+    ``(x / 255 - mean) / std`` per channel, CHW.  ``nv12``: what ``nv12_planes`` takes, on the device, read in place through its
+    strides.  ``crop``: the three forms of ``parse_boxes``; an origin may be odd (chroma is sited by replication: pixel ``(Y, X)``
+    has sample ``(Y >> 1, X >> 1)``); device origins are clamped by the kernel so that the box stays inside the frame.
+    ``channel_order`` only says which plane order the network input has ("bgr": planes B, G, R).  -> float32 [N,3,size,size]."""
+    y, uv = nv12_planes(nv12)
+    N, H, W = y.shape
+    Hout, Wout = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if Hout < 1 or Wout < 1:
+        raise ValueError(f"frames_from_nv12: size must be >= 1, got {size}")
+    swap = _channel_swap(channel_order)
+    code, full = _yuv_standard(standard, full_range)
+    mean, std = _triple(mean, "mean"), _triple(std, "std")
+    if any(s == 0 for s in std):
+        raise ValueError("frames_from_nv12: std must be non-zero")
+    origins, h, w = parse_boxes((0, 0, H, W) if crop is None else crop, N, H, W, "frames_from_nv12: crop")
+    ys, us = _nv12_strides(y, uv, "frames_from_nv12", written=False)
+    if isinstance(origins, tuple):
+        (y0, x0), boxes = origins, None
+    else:
+        y0 = x0 = 0
+        if origins.device != y.device:
+            if origins.is_cuda:
+                raise L.SpkError(f"frames_from_nv12: box origins on {origins.device}, frames on {y.device}")
+            origins = origins.to(y.device)
+        boxes = origins
+    scale = [1.0 / (255.0 * s) for s in std]
+    shift = [-m / s for m, s in zip(mean, std)]
+    out = torch.empty((N, 3, Hout, Wout), device=y.device, dtype=torch.float32)
+    fy, cy, wy, fx, cx, wx = _device_resize_tables(h, w, Hout, Wout, y.device)
+    L.check(L.lib().spk_frames_nv12_to_f32(y.data_ptr(), ys[0], ys[1], uv.data_ptr(), us[0], us[1], N, H, W,
+                                           None if boxes is None else boxes.data_ptr(), y0, x0, h, w, swap, code, full, fy.data_ptr(),
+                                           cy.data_ptr(), wy.data_ptr(), wy.size(1), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), wx.size(1),
+                                           out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()), "spk_frames_nv12_to_f32")
+    return out
+
+
+def _nv12_out(out, N, H, W, device, what):
+    """The surface a launcher writes: ``out`` (what ``nv12_planes`` takes) or a fresh packed ``[N, 3H/2, W]`` buffer.
+    -> ``(result, y, uv)``."""
+    if out is None:
+        out = torch.empty((N, 3 * H // 2, W), device=device, dtype=torch.uint8)
+    y, uv = nv12_planes(out)
+    if tuple(y.shape) != (N, H, W):
+        raise L.SpkError(f"{what}: out must hold {N} NV12 frames of {H} x {W}, got planes {tuple(y.shape)}")
+    return out, y, uv
+
+
+def frames_to_nv12(x, *, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
+    """Network frames -> NV12 for a hardware encoder, one launch (``spk_frames_f32_to_nv12``): float32 [N,3,H,W] (R, G, B planes,
+    ``H`` and ``W`` even) in ``value_range`` is quantised as ``frames_to_u8`` does without its rounding, converted with
+    ``from_rgb`` of ``yuv_coeffs`` in fp64, and stored as ``Y = rint(clamp(e_y))`` per pixel and ``C = rint(clamp(mean of the four
+    e_c))`` per 2 x 2 block.  ``out``: what ``nv12_planes`` takes (any row pitch).  -> uint8 [N, 3H/2, W], or ``out``."""
+    if x.dim() != 4 or x.size(1) != 3 or x.size(0) < 1:
+        raise ValueError(f"frames_to_nv12: x must be [N,3,H,W], got {tuple(x.shape)}")
+    N, _, H, W = x.shape
+    if H % 2 or W % 2 or H < 2 or W < 2:
+        raise ValueError(f"frames_to_nv12: NV12 frames have an even height and width, got {H} x {W}")
+    lo, k = quant_range(value_range)
+    code, full = _yuv_standard(standard, full_range)
+    xp = L.dptr(x, "x")
+    out, y, uv = _nv12_out(out, N, H, W, x.device, "frames_to_nv12")
+    ys, us = _nv12_strides(y, uv, "frames_to_nv12: out", written=True)
+    L.check(L.lib().spk_frames_f32_to_nv12(xp, N, H, W, y.data_ptr(), ys[0], ys[1], uv.data_ptr(), us[0], us[1], code, full, lo, k,
+                                           L.stream_ptr()), "spk_frames_f32_to_nv12")
+    return out
+
+
+def frames_paste_nv12(x, nv12, box, *, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
+    """Generated frames back into the NV12 video they were cropped from, one launch (``spk_frames_paste_nv12``): float32
+    [N,3,Hs,Ws] in ``value_range`` is resized to the box size ``h x w``, quantised, converted to YUV and blended over the box with
+    weight ``m = a_y[y] a_x[x]`` of ``feather_tables``: luma per pixel, chroma per 2 x 2 block as the quarter-weighted sum of the
+    block's box pixels over the sample underneath (include/spk.h has the arithmetic).  ``box``: the three forms of
+    ``parse_boxes``; origins may be odd; box pixels outside the frame are skipped.  ``out=None``: the result is a packed clone of
+    ``nv12``; ``out=nv12`` (the same tensor, or the same pair of planes): pasted in place through its strides; another ``out``
+    first receives a copy.  -> uint8 [N, 3H/2, W], or ``out``."""
+    if x.dim() != 4 or x.size(1) != 3 or x.size(0) < 1:
+        raise ValueError(f"frames_paste_nv12: x must be [N,3,H,W], got {tuple(x.shape)}")
+    sy, suv = nv12_planes(nv12)
+    N, _, Hs, Ws = x.shape
+    if sy.size(0) != N:
+        raise ValueError(f"frames_paste_nv12: {N} generated frames, {sy.size(0)} NV12 frames")
+    H, W = sy.shape[1:]
+    lo, k = quant_range(value_range)
+    code, full = _yuv_standard(standard, full_range)
+    feather = float(feather)
+    if not (0.0 <= feather < float("inf")):
+        raise ValueError(f"frames_paste_nv12: feather must be a finite number >= 0, got {feather}")
+    origins, h, w = parse_boxes(box, N, H, W, "frames_paste_nv12: box", inside=False)
+    xp = L.dptr(x, "x")
+    if not sy.is_cuda:
+        raise L.SpkError(f"frames: expected uint8 HIP tensors, got {sy.dtype} on {sy.device} (no CPU path)")
+    out, y, uv = _nv12_out(out, N, H, W, x.device, "frames_paste_nv12")
+    ys, us = _nv12_strides(y, uv, "frames_paste_nv12: out", written=True)
+    if isinstance(origins, tuple):
+        (y0, x0), boxes = origins, None
+    else:
+        y0 = x0 = 0
+        if origins.device != x.device:
+            if origins.is_cuda:
+                raise L.SpkError(f"frames_paste_nv12: box origins on {origins.device}, frames on {x.device}")
+            origins = origins.to(x.device)
+        boxes = origins
+    if y.data_ptr() != sy.data_ptr() or y.stride() != sy.stride():
+        y.copy_(sy)
+    if uv.data_ptr() != suv.data_ptr() or uv.stride() != suv.stride():
+        uv.copy_(suv)
+    fy, cy, wy, fx, cx, wx = _device_resize_tables(Hs, Ws, h, w, x.device)
+    ay, ax = _device_feather_tables(h, w, feather, x.device) if feather > 0 else (None, None)
+    L.check(L.lib().spk_frames_paste_nv12(xp, N, Hs, Ws, y.data_ptr(), ys[0], ys[1], uv.data_ptr(), us[0], us[1], H, W, h, w, y0, x0,
+                                          None if boxes is None else boxes.data_ptr(), code, full, fy.data_ptr(), cy.data_ptr(),
+                                          wy.data_ptr(), wy.size(1), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), wx.size(1),
+                                          None if ay is None else ay.data_ptr(), None if ax is None else ax.data_ptr(), lo, k,
+                                          L.stream_ptr()), "spk_frames_paste_nv12")
+    return out
+
+
 # ---- counter-based decoder noise (csrc/noise.hip; the definition is in include/spk.h) ---------------------------------------
 def check_seed(seed, frame0=0, what="seed"):
     """A noise seed is an integer in [0, 2**64); a frame index a non-negative integer below 2**62.  -> (seed, frame0)."""

@@ -173,16 +173,19 @@ class DecoderPlan(LaunchPlan):
     the constant prologue, 2 fused conv launches per block, toRGB.  ``output="uint8"``: the fp32 frame goes to a plan-owned
     buffer and one more op (``SPK_OP_FRAMES_TO_U8``) quantises it from ``value_range`` into the uint8 [B,R,R,3] frames
     ``run`` returns (``swap_rb``: B, G, R order) -- what ``ops.frames_to_u8`` makes of the fp32 result, bit for bit.
+    ``output="nv12"``: the same buffer and one ``SPK_OP_FRAMES_TO_NV12`` instead, which converts it from ``value_range`` with the
+    colour matrix of ``standard`` / ``full_range`` into the uint8 [B,3R/2,R] NV12 surfaces ``run`` returns -- ``ops.frames_to_nv12``
+    of the fp32 result, bit for bit.
     ``seeded=True``: the list starts with ``SPK_OP_NOISE_FILL`` (csrc/noise.hip), which writes ``noise_flat`` from the
     ``seed`` / ``frame0`` each ``run`` patches into its descriptor -- the noise of ``ops.decoder_noise``, bit for bit, and the
     forward is the launch list alone (no ATen draw, the device generator untouched).  A seeded plan runs seeded calls only, an
     unseeded one (the default: built and run exactly as before) unseeded calls only."""
 
     def __init__(self, synthesis, B, device, generator=None, precision="f32", output="f32", value_range=(-1, 1), swap_rb=False,
-                 seeded=False):
+                 seeded=False, standard="bt601", full_range=False):
         super().__init__(device)
-        if output not in ("f32", "uint8"):
-            raise ValueError(f"DecoderPlan: output must be 'f32' or 'uint8', got {output!r}")
+        if output not in ("f32", "uint8", "nv12"):
+            raise ValueError(f"DecoderPlan: output must be 'f32', 'uint8' or 'nv12', got {output!r}")
         s = self.synthesis = synthesis
         self.precision = precision
         self.output = output
@@ -274,16 +277,25 @@ class DecoderPlan(LaunchPlan):
             self.torgb = self.add(L.OP_TORGB, L.ToRGBArgs(x=x.data_ptr(), w=L.dptr(s.to_rgb.weight, "weight"), mod=None,
                                                           bias=L.dptr(s.to_rgb.bias, "bias"), skip=None, y=None, B=B, C=Cc, O=O,
                                                           H=x.shape[2], W=x.shape[3], in_scale=1.0))
-        self.to_u8 = None
-        if output == "uint8":
+        self.to_u8 = self.to_nv12 = None
+        if output != "f32":
             if O != 3:
-                raise L.SpkError(f"DecoderPlan: uint8 frames need 3 output channels, toRGB has {O}")
+                raise L.SpkError(f"DecoderPlan: {output} frames need 3 output channels, toRGB has {O}")
             lo, k = ops.quant_range(value_range)
             self.rgb_buf = self.buf(*self.out_shape)
             if self.rgb_fused is not None:
                 self.rgb_fused.rgb_y = self.rgb_buf.data_ptr()
             else:
                 self.torgb.y = self.rgb_buf.data_ptr()
+        if output == "nv12":
+            code, full = ops._yuv_standard(standard, full_range)
+            Ho, Wo = x.shape[2], x.shape[3]
+            if swap_rb:
+                raise ValueError("DecoderPlan: swap_rb applies to uint8 output only")
+            self.to_nv12 = self.add(L.OP_FRAMES_TO_NV12, L.FramesToNv12Args(
+                x=self.rgb_buf.data_ptr(), y=None, uv=None, y_image_stride=3 * Ho // 2 * Wo, y_row_stride=Wo, uv_image_stride=3 * Ho // 2 * Wo,
+                uv_row_stride=Wo, N=B, H=Ho, W=Wo, standard=code, full_range=full, lo=lo, k=k, reserved=0))
+        if output == "uint8":
             self.to_u8 = self.add(L.OP_FRAMES_TO_U8, L.FramesToU8Args(x=self.rgb_buf.data_ptr(), y=None, N=B, H=x.shape[2], W=x.shape[3],
                                                                        swap_rb=1 if swap_rb else 0, lo=lo, k=k))
         self.finish(*([synthesis] + ([generator] if generator is not None else [])))
@@ -342,6 +354,10 @@ class DecoderPlan(LaunchPlan):
             Bo, _, Ho, Wo = self.out_shape
             y = torch.empty((Bo, Ho, Wo, 3), device=self.device, dtype=torch.uint8)
             self.to_u8.y = y.data_ptr()
+        elif self.to_nv12 is not None:
+            Bo, _, Ho, Wo = self.out_shape
+            y = torch.empty((Bo, 3 * Ho // 2, Wo), device=self.device, dtype=torch.uint8)      # packed surfaces: rows Ho.. are the UV plane
+            self.to_nv12.y, self.to_nv12.uv = y.data_ptr(), y.data_ptr() + Ho * Wo
         else:
             y = torch.empty(self.out_shape, device=self.device, dtype=torch.float32)
             if self.rgb_fused is not None:

@@ -16,7 +16,14 @@
     in, ``IRFD.reenact``, ``interpolate`` to the box, quantise, mask, blend, round, cast and permute into a clone of the video --
     T = 64, chunk 8, 1080 x 1920 BGR, a 400 x 400 box that moves; alternating, with the ATen calls of both.
 
-    python tools/bench_frame_io.py [--paste] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
+``--nv12``: the NV12 form of the edge (csrc/frame_nv12.hip).  (1) ``ops.frames_from_nv12`` (whole 1080 x 1920 surfaces and 400 x 400
+    tracked boxes -> 256^2), ``ops.frames_to_nv12`` (256^2) and ``ops.frames_paste_nv12`` (256^2 into 400 x 400 tracked boxes, feather
+    16, in place), each beside the HBM time of its bytes.  (2) ``IRFD.reenact_video(pixel_format="nv12", paste=True)`` against the
+    route a user has without it: torch NV12 -> BGR, ``reenact_video(paste=True)`` on packed frames, torch BGR -> NV12 (chunk by
+    chunk, so that the fp32 temporaries of the torch conversions stay at a chunk's size); both produce NV12 surfaces; alternating,
+    with the ATen calls of both.
+
+    python tools/bench_frame_io.py [--paste | --nv12] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
 import os
@@ -144,6 +151,116 @@ def bench_paste(args, lines):
                  f"(largest step {int(diff.max())}); ATen calls per run: {c_ours.n} against {c_eager.n} ({T // chunk} chunks)")
 
 
+def torch_nv12_to_bgr(surf, to_rgb):
+    """NV12 surfaces [N,3H/2,W] -> packed BGR uint8 [N,H,W,3] with torch ops: replicate chroma, matrix, clamp, round, cast, permute."""
+    N, R, W = surf.shape
+    H = R // 3 * 2
+    y = surf[:, :H].float()
+    uv = surf[:, H:].view(N, H // 2, W // 2, 2).float().repeat_interleave(2, 1).repeat_interleave(2, 2)
+    yuv = torch.stack([y, uv[..., 0], uv[..., 1]], -1)
+    rgb = (yuv @ to_rgb[:, :3].T + to_rgb[:, 3]).clamp(0, 255).round().to(torch.uint8)
+    return rgb.flip(-1).contiguous()
+
+
+def torch_bgr_to_nv12(bgr, from_rgb):
+    """Packed BGR uint8 [N,H,W,3] -> NV12 surfaces [N,3H/2,W] with torch ops: matrix, 2 x 2 mean of the chroma, round, cast."""
+    N, H, W, _ = bgr.shape
+    yuv = bgr.flip(-1).float() @ from_rgb[:, :3].T + from_rgb[:, 3]
+    out = torch.empty((N, 3 * H // 2, W), dtype=torch.uint8, device=bgr.device)
+    out[:, :H] = yuv[..., 0].clamp(0, 255).round().to(torch.uint8)
+    c = F.avg_pool2d(yuv[..., 1:].permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
+    out[:, H:] = c.clamp(0, 255).round().to(torch.uint8).reshape(N, H // 2, W)
+    return out
+
+
+def bench_nv12(args, lines):
+    import importlib
+    import model
+    from oracle import irfd_ref as IR
+    from oracle.weights_recipe import fill_state_dict
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    T, chunk, size, Hf, Wf, h, w, feather = args.frames, args.chunk, 256, 1080, 1920, 400, 400, 16
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(T)]                  # a head that moves, origins of both parities
+    yx = torch.tensor(boxes, dtype=torch.int32, device=dev)
+    to_rgb, from_rgb = (t.float().to(dev) for t in ops.yuv_coeffs())
+
+    def line(name, t, nbytes, te=None):
+        lines.append(f"{name}: {t * 1e6:8.1f} us, {nbytes / 1e6:6.1f} MB -> HBM time {nbytes / HBM * 1e6:6.1f} us ({nbytes / HBM / t * 100:5.1f} % of it)"
+                     + ("" if te is None else f"; the torch ops it replaces: {te * 1e6:8.1f} us"))
+
+    # ---- (1) the kernels alone ----
+    surf = torch.randint(0, 256, (chunk, 3 * Hf // 2, Wf), generator=g, dtype=torch.uint8).to(dev)
+    out_bytes = chunk * 3 * size * size * 4
+    t = device_time(lambda: ops.frames_from_nv12(surf, size))
+    te = device_time(lambda: eager_in(torch_nv12_to_bgr(surf, to_rgb), size, True))
+    line(f"frames_from_nv12 {chunk} x {Hf}x{Wf} -> 256^2", t, surf.numel() + out_bytes, te)
+    t = device_time(lambda: ops.frames_from_nv12(surf, size, crop=(yx[:chunk], h, w)))
+    line(f"frames_from_nv12 {chunk} x {h}x{w} tracked boxes of {Hf}x{Wf} -> 256^2", t, chunk * h * w * 3 // 2 + out_bytes)
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    t = device_time(lambda: ops.frames_to_nv12(x))
+    te = device_time(lambda: torch_bgr_to_nv12(eager_out(x, True), from_rgb))
+    line(f"frames_to_nv12   {chunk} x 256^2 fp32 -> NV12", t, x.numel() * 4 + chunk * size * size * 3 // 2, te)
+    t = device_time(lambda: ops.frames_paste_nv12(x, surf, (yx[:chunk], h, w), feather=feather, out=surf))
+    line(f"frames_paste_nv12 {chunk} x 256^2 fp32 -> {h}x{w} boxes of {Hf}x{Wf} NV12, feather {feather}, in place", t,
+         x.numel() * 4 + 2 * chunk * h * w * 3 // 2)
+
+    # ---- (2) reenact_video(pixel_format="nv12", paste=True) against the route through packed BGR ----
+    m = model.IRFD()
+    sd = IR.irfd_recipe_state_dict()
+    sd.update({"Gd." + k: v for k, v in fill_state_dict(m.Gd.state_dict(), prefix="Gd.").items()})
+    m.load_state_dict(sd, strict=False)
+    m.to(dev).eval()
+    ident = torch.randint(0, 256, (1, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    # an in-gamut video: random BGR constant over each chroma block, converted chunk by chunk (random YUV bytes are mostly out of
+    # gamut, and a route through BGR bytes would clamp them)
+    video = torch.empty((T, 3 * Hf // 2, Wf), dtype=torch.uint8, device=dev)
+    for t0 in range(0, T, chunk):
+        coarse = torch.randint(0, 256, (min(chunk, T - t0), Hf // 2, Wf // 2, 3), generator=g, dtype=torch.uint8).to(dev)
+        video[t0:t0 + chunk] = torch_bgr_to_nv12(coarse.repeat_interleave(2, 1).repeat_interleave(2, 2), from_rgb)
+    noises = [torch.randn(T, 1, 4 << (i + 1) // 2, 4 << (i + 1) // 2, generator=g).to(dev) for i in range(13)]
+    kw = dict(size=size, channel_order="bgr", chunk=chunk, paste=True, feather=feather)
+
+    def ours():
+        return m.reenact_video(ident, video, crop=(yx, h, w), noises=noises, pixel_format="nv12", **kw)
+
+    def through_bgr():
+        out = torch.empty_like(video)
+        for t0 in range(0, T, chunk):
+            bgr = torch_nv12_to_bgr(video[t0:t0 + chunk], to_rgb)
+            pasted = m.reenact_video(ident, bgr, crop=(yx[t0:t0 + chunk], h, w), noises=[n[t0:t0 + chunk] for n in noises], inplace=True, **kw)
+            out[t0:t0 + chunk] = torch_bgr_to_nv12(pasted, from_rgb)
+        return out
+
+    names = ("pixel_format=nv12", "through BGR")
+    with torch.no_grad():
+        for _ in range(args.warmup):
+            a, b = ours(), through_bgr()
+        diff = (a.int() - b.int()).abs()
+        times = {n: [] for n in names}
+        for _ in range(args.repeats):                    # alternating: drift hits both alike
+            times[names[0]].append(wall(ours))
+            times[names[1]].append(wall(through_bgr))
+        c_ours, c_other = CountAten(), CountAten()
+        with c_ours:
+            ours()
+        with c_other:
+            through_bgr()
+    lines.append(f"T = {T} NV12 frames of {Hf}x{Wf}, a {h}x{w} tracked box, feather {feather}, chunk {chunk}, {args.repeats} alternating repeats "
+                 f"after {args.warmup} warm-up rounds:")
+    for n in names:
+        ts = sorted(times[n])
+        med = statistics.median(ts)
+        lines.append(f"  {n:18s} median {med * 1e3:8.2f} ms  min {ts[0] * 1e3:8.2f}  max {ts[-1] * 1e3:8.2f}  spread "
+                     f"{(ts[-1] - ts[0]) / med * 100:5.1f} %  -> {T / med:8.1f} frames/s")
+    mo, me = statistics.median(times[names[0]]), statistics.median(times[names[1]])
+    lines.append(f"  pixel_format=nv12 / through BGR = {mo / me:.3f}; bytes that differ: {int((diff > 0).sum())} of {diff.numel()} "
+                 f"(largest step {int(diff.max())}; the route through BGR rounds every pixel of the frame twice more); ATen calls per run: "
+                 f"{c_ours.n} against {c_other.n} ({T // chunk} chunks)")
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -173,9 +290,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     ap.add_argument("--paste", action="store_true", help="the full-frame way out: frames_paste_u8 and reenact_video(paste=True)")
+    ap.add_argument("--nv12", action="store_true", help="the NV12 form of the edge: its kernels and reenact_video(pixel_format='nv12', paste=True)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.nv12:
+        lines = [f"bench_frame_io --nv12: {torch.cuda.get_device_name(0)}, fp32, HBM time at {HBM / 1e12:.1f} TB/s"]
+        bench_nv12(args, lines)
+        return report(lines, args.out)
     if args.paste:
         lines = [f"bench_frame_io --paste: {torch.cuda.get_device_name(0)}, fp32, HBM time at {HBM / 1e12:.1f} TB/s"]
         bench_paste(args, lines)

@@ -6,7 +6,8 @@ The directory name carries a hyphen, so import it with
 ``model`` / ``styleganv1`` / ``stylegan`` (same names as the reference's files).
 
 Only what the path needs lives here: ``csrc/`` (HIP kernels + the C ABI of include/spk.h),
-``_lib`` (ctypes binding), ``ops`` (launchers) and the host-side mirrors of the reference modules.
+``_lib`` (ctypes binding), ``ops`` (launchers; those of the video-frame edge are in ``frames``) and the host-side mirrors of the
+reference modules.
 """
 from . import _lib, ops  # noqa: F401
 from .decoder import (FC, ApplyNoise, ApplyStyle, StyleGenerator, SynthesisBlock,  # noqa: F401

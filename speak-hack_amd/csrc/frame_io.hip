@@ -9,17 +9,13 @@
 //   from + CHW -> HWC, one pass, the box origin per frame (by value, or from a device array a tracker wrote).
 // The resize is separable and table driven: the taps of both axes come from the caller (spk_resize_table, built in fp64 on
 // the host), so the kernel holds no filter arithmetic.
-#include "spk_common.hpp"
+#include "frame_common.hpp"
 
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
 #include <vector>
 
 namespace {
 
-constexpr int STRIP = 8;            // output rows a thread of the resize owns
-constexpr int GRID_CAP = 2048;      // workgroups per launch; the rest of the work is a grid-stride trip
+using namespace spk::frame;
 
 // ---- host: the triangle filter of F.interpolate(mode="bilinear", align_corners=False, antialias=True), one output sample ----
 // window [first, first + count) and its normalised weights (zero weights at either end dropped); returns count
@@ -74,8 +70,6 @@ void round_row_f32(const double* w, int count, float* out) {
 }
 
 // ---- device ----
-struct Affine3 { float scale[3], shift[3]; };
-
 // A thread owns output column ox of one STRIP-row strip of one frame, all three channels.  It walks the input rows the strip's
 // vertical windows cover once: the horizontal sum of a row from byte loads (one weight load serves the three channels), added
 // into the accumulators of the output rows whose window holds the row.  Sums are kept in fp64 (full-rate FMA on this chip, and
@@ -85,78 +79,44 @@ struct Affine3 { float scale[3], shift[3]; };
 // boxes_yx[n] = (y0, x0), clamped so that the box stays inside the H x W frame (a tracker's box cannot send a load out of bounds).
 template <bool BOXES>
 __global__ __launch_bounds__(256) void frames_u8_to_f32_kernel(const uint8_t* __restrict__ src, long long image_stride, long long row_stride,
-                                                               const int* __restrict__ boxes_yx, int H, int W,
-                                                               int Hin, int Win, int swap_rb, const int* __restrict__ first_y,
-                                                               const int* __restrict__ count_y, const float* __restrict__ w_y, int taps_y,
-                                                               const int* __restrict__ first_x, const int* __restrict__ count_x,
-                                                               const float* __restrict__ w_x, int taps_x, float* __restrict__ dst,
-                                                               int Hout, int Wout, int strips, long long total, Affine3 af) {
+                                                               const int* __restrict__ boxes_yx, int H, int W, int Hin, int Win, int swap_rb,
+                                                               ResizeTables t, float* __restrict__ dst, int Hout, int Wout, int strips,
+                                                               long long total, Affine3 af) {
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int ox = (int)(idx % Wout);
-        const int strip = (int)((idx / Wout) % strips);
-        const long long n = idx / ((long long)Wout * strips);
-        const int oy0 = strip * STRIP;
-        // the tables are the caller's: clamp every window into the image so that no table can send a load out of bounds
-        const int fx = min(max(first_x[ox], 0), Win - 1);
-        const int cx = max(min(min(count_x[ox], taps_x), Win - fx), 0);
-        int fy[STRIP], cy[STRIP];
-        int row_lo = Hin, row_hi = 0;
-#pragma unroll
-        for (int k = 0; k < STRIP; ++k) {
-            const int oy = min(oy0 + k, Hout - 1);
-            fy[k] = min(max(first_y[oy], 0), Hin - 1);
-            cy[k] = oy0 + k < Hout ? max(min(min(count_y[oy], taps_y), Hin - fy[k]), 0) : 0;
-            if (cy[k] > 0) { row_lo = min(row_lo, fy[k]); row_hi = max(row_hi, fy[k] + cy[k]); }
-        }
+        const Strip s = strip_prologue(idx, t, Hin, Win, Hout, Wout, strips);
         double acc[STRIP][3];
 #pragma unroll
         for (int k = 0; k < STRIP; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
-        const uint8_t* img = src + n * image_stride + (long long)fx * 3;
+        const uint8_t* img = src + s.n * image_stride + (long long)s.fx * 3;
         if (BOXES) {
-            const int y0 = min(max(boxes_yx[2 * n], 0), H - Hin), x0 = min(max(boxes_yx[2 * n + 1], 0), W - Win);
+            const Origin o = box_origin(boxes_yx, s.n, 0, 0);
+            const int y0 = min(max(o.y, 0), H - Hin), x0 = min(max(o.x, 0), W - Win);
             img += (long long)y0 * row_stride + (long long)x0 * 3;
         }
-        const float* wx = w_x + (long long)ox * taps_x;
-        for (int iy = row_lo; iy < row_hi; ++iy) {
+        const float* wx = t.w_x + (long long)s.ox * t.taps_x;
+        for (int iy = s.row_lo; iy < s.row_hi; ++iy) {
             const uint8_t* p = img + (long long)iy * row_stride;
             double h0 = 0.0, h1 = 0.0, h2 = 0.0;
-            for (int j = 0; j < cx; ++j) {
+            for (int j = 0; j < s.cx; ++j) {
                 const double w = (double)wx[j];
                 h0 = fma(w, (double)p[3 * j], h0);
                 h1 = fma(w, (double)p[3 * j + 1], h1);
                 h2 = fma(w, (double)p[3 * j + 2], h2);
             }
-#pragma unroll
-            for (int k = 0; k < STRIP; ++k) {
-                const int j = iy - fy[k];
-                if ((unsigned)j < (unsigned)cy[k]) {
-                    const double w = (double)w_y[(long long)(oy0 + k) * taps_y + j];
-                    acc[k][0] = fma(w, h0, acc[k][0]);
-                    acc[k][1] = fma(w, h1, acc[k][1]);
-                    acc[k][2] = fma(w, h2, acc[k][2]);
-                }
-            }
+            strip_accumulate(acc, s, t, iy, h0, h1, h2);
         }
         const long long plane = (long long)Hout * Wout;
-        float* out = dst + n * 3 * plane + ox;
+        float* out = dst + s.n * 3 * plane + s.ox;
 #pragma unroll
         for (int k = 0; k < STRIP; ++k) {
-            if (oy0 + k >= Hout) break;
+            if (s.oy0 + k >= Hout) break;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const int cd = swap_rb ? 2 - c : c;              // source channel c lands in plane cd
-                out[cd * plane + (long long)(oy0 + k) * Wout] = (float)fma((double)af.scale[cd], acc[k][c], (double)af.shift[cd]);
+                out[cd * plane + (long long)(s.oy0 + k) * Wout] = (float)fma((double)af.scale[cd], acc[k][c], (double)af.shift[cd]);
             }
         }
     }
-}
-
-// q = rint(min(max((x - lo) * k, 0), 255)) in exactly this order of fp32 operations (a subtraction and a multiplication cannot
-// contract into an FMA), the bits of torch's ((x - lo) * k).clamp(0, 255).round().to(torch.uint8), ties to even.  fmaxf returns
-// its other operand for a NaN: NaN -> 0.
-__device__ __forceinline__ unsigned quant_u8(float x, float lo, float k) {
-    const float v = __fmul_rn(__fsub_rn(x, lo), k);
-    return (unsigned)rintf(fminf(fmaxf(v, 0.f), 255.f));
 }
 
 // A thread takes four pixels of a frame (pixels counted over the H*W plane).  MODE 2: three float4 loads, three dword stores
@@ -213,50 +173,49 @@ __global__ __launch_bounds__(256) void frames_f32_to_u8_kernel(const float* __re
 // frames are byte addressed at any offset (3 * X0 + row_stride * Y0 has no alignment), so loads and stores are bytes.
 __global__ __launch_bounds__(256) void frames_paste_u8_kernel(const float* __restrict__ src, int Hs, int Ws, uint8_t* dst, long long image_stride,
                                                               long long row_stride, int H, int W, int h, int w, int y0, int x0,
-                                                              const int* __restrict__ boxes_yx, int swap_rb, const int* __restrict__ first_y,
-                                                              const int* __restrict__ count_y, const float* __restrict__ w_y, int taps_y,
-                                                              const int* __restrict__ first_x, const int* __restrict__ count_x,
-                                                              const float* __restrict__ w_x, int taps_x, const float* __restrict__ a_y,
-                                                              const float* __restrict__ a_x, float lo, float k, long long total) {
+                                                              const int* __restrict__ boxes_yx, int swap_rb, ResizeTables t,
+                                                              const float* __restrict__ a_y, const float* __restrict__ a_x, float lo, float k,
+                                                              long long total) {
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const int x = (int)(idx % w);
         const int y = (int)((idx / w) % h);
         const long long n = idx / ((long long)w * h);
-        const long long Y = (long long)(boxes_yx ? boxes_yx[2 * n] : y0) + y, X = (long long)(boxes_yx ? boxes_yx[2 * n + 1] : x0) + x;
+        const Origin o = box_origin(boxes_yx, n, y0, x0);
+        const long long Y = (long long)o.y + y, X = (long long)o.x + x;
         if (Y < 0 || Y >= H || X < 0 || X >= W) continue;
-        // the tables are the caller's: clamp every window into the source so that no table can send a load out of bounds
-        const int fx = min(max(first_x[x], 0), Ws - 1), cx = max(min(min(count_x[x], taps_x), Ws - fx), 0);
-        const int fy = min(max(first_y[y], 0), Hs - 1), cy = max(min(min(count_y[y], taps_y), Hs - fy), 0);
-        const float* wx = w_x + (long long)x * taps_x;
-        const float* wy = w_y + (long long)y * taps_y;
         const long long plane = (long long)Hs * Ws;
-        const float* in = src + n * 3 * plane + (long long)fy * Ws + fx;
-        double v0 = 0.0, v1 = 0.0, v2 = 0.0;
-        for (int i = 0; i < cy; ++i) {
-            const float* p = in + (long long)i * Ws;
-            double h0 = 0.0, h1 = 0.0, h2 = 0.0;
-            for (int j = 0; j < cx; ++j) {
-                const double wj = (double)wx[j];
-                h0 = fma(wj, (double)p[j], h0);
-                h1 = fma(wj, (double)p[plane + j], h1);
-                h2 = fma(wj, (double)p[2 * plane + j], h2);
-            }
-            const double wi = (double)wy[i];
-            v0 = fma(wi, h0, v0);
-            v1 = fma(wi, h1, v1);
-            v2 = fma(wi, h2, v2);
-        }
+        double v[3];
+        resize_point(src + n * 3 * plane, plane, Hs, Ws, t, y, x, v[0], v[1], v[2]);
         const double m = a_y ? (double)a_y[y] * (double)a_x[x] : 1.0;
         uint8_t* out = dst + n * image_stride + Y * row_stride + X * 3;
-        const double v[3] = {v0, v1, v2};
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const int cd = swap_rb ? 2 - c : c;
-            const float q = fminf(fmaxf(__fmul_rn(__fsub_rn((float)v[c], lo), k), 0.f), 255.f);
+            const float q = quant_unrounded((float)v[c], lo, k);
             const double b = (double)out[cd];
             out[cd] = (uint8_t)(int)rint(fmin(fmax(fma(m, (double)q - b, b), 0.0), 255.0));      // (the clamp: a foreign feather table)
         }
     }
+}
+
+// spk_frames_u8_to_f32 and spk_frames_u8_to_f32_boxes: without boxes the box is the frame (H x W = Hin x Win)
+int launch_u8_to_f32(const char* who, bool boxes, const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int H, int W,
+                     const int32_t* boxes_yx, int Hin, int Win, int swap_rb, const ResizeTables& t, float* dst, int Hout, int Wout,
+                     const Affine3& af, void* stream) {
+    SPK_REQUIRE(src && dst, "%s: null frame pointer", who);
+    SPK_REQUIRE(!boxes || boxes_yx, "%s: null box origin array", who);
+    if (int rc = check_tables(who, t)) return rc;
+    SPK_REQUIRE(N >= 1 && Hin >= 1 && Win >= 1 && Hout >= 1 && Wout >= 1, "%s: N / H / W must be >= 1 (N %d, %d x %d -> %d x %d)", who, N, Hin,
+                Win, Hout, Wout);
+    SPK_REQUIRE(H >= Hin && W >= Win, "%s: the %d x %d box does not fit the %d x %d frame", who, Hin, Win, H, W);
+    SPK_REQUIRE(row_stride >= 3ll * W, "%s: row stride %lld is smaller than 3 * W = %lld", who, (long long)row_stride, 3ll * W);
+    SPK_REQUIRE(image_stride >= 0, "%s: negative image stride", who);
+    const int strips = spk::ceil_div(Hout, STRIP);
+    const long long total = (long long)N * strips * Wout;
+    hipLaunchKernelGGL(boxes ? frames_u8_to_f32_kernel<true> : frames_u8_to_f32_kernel<false>, grid_for(total), dim3(256), 0, (hipStream_t)stream,
+                       src, (long long)image_stride, (long long)row_stride, (const int*)boxes_yx, H, W, Hin, Win, swap_rb, t, dst, Hout, Wout,
+                       strips, total, af);
+    return spk::check_launch(boxes ? "frames_u8_to_f32_kernel<boxes>" : "frames_u8_to_f32_kernel");
 }
 
 }  // namespace
@@ -298,53 +257,28 @@ int spk_frames_u8_to_f32(const uint8_t* src, int64_t image_stride, int64_t row_s
                          const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y, const int32_t* first_x,
                          const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout, float scale0,
                          float scale1, float scale2, float shift0, float shift1, float shift2, void* stream) {
-    SPK_REQUIRE(src && dst, "frames_u8_to_f32: null frame pointer");
-    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_u8_to_f32: null table pointer");
-    SPK_REQUIRE(N >= 1 && Hin >= 1 && Win >= 1 && Hout >= 1 && Wout >= 1, "frames_u8_to_f32: N / H / W must be >= 1 (N %d, %d x %d -> %d x %d)",
-                N, Hin, Win, Hout, Wout);
-    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_u8_to_f32: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
-    SPK_REQUIRE(row_stride >= 3ll * Win, "frames_u8_to_f32: row stride %lld is smaller than 3 * Win = %lld", (long long)row_stride,
-                3ll * Win);
-    SPK_REQUIRE(image_stride >= 0, "frames_u8_to_f32: negative image stride");
-    const int strips = spk::ceil_div(Hout, STRIP);
-    const long long total = (long long)N * strips * Wout;
-    Affine3 af = {{scale0, scale1, scale2}, {shift0, shift1, shift2}};
-    hipLaunchKernelGGL(frames_u8_to_f32_kernel<false>, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
-                       (hipStream_t)stream, src, (long long)image_stride, (long long)row_stride, (const int*)nullptr, Hin, Win, Hin, Win,
-                       swap_rb, first_y, count_y, w_y, taps_y, first_x, count_x, w_x, taps_x, dst, Hout, Wout, strips, total, af);
-    return spk::check_launch("frames_u8_to_f32_kernel");
+    return launch_u8_to_f32("frames_u8_to_f32", false, src, image_stride, row_stride, N, Hin, Win, nullptr, Hin, Win, swap_rb,
+                            {first_y, count_y, w_y, first_x, count_x, w_x, taps_y, taps_x}, dst, Hout, Wout,
+                            {{scale0, scale1, scale2}, {shift0, shift1, shift2}}, stream);
 }
 
 int spk_frames_u8_to_f32_boxes(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int H, int W, const int32_t* boxes_yx,
                                int Hin, int Win, int swap_rb, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
                                const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout,
                                float scale0, float scale1, float scale2, float shift0, float shift1, float shift2, void* stream) {
-    SPK_REQUIRE(src && dst, "frames_u8_to_f32_boxes: null frame pointer");
-    SPK_REQUIRE(boxes_yx, "frames_u8_to_f32_boxes: null box origin array");
-    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_u8_to_f32_boxes: null table pointer");
-    SPK_REQUIRE(N >= 1 && Hin >= 1 && Win >= 1 && Hout >= 1 && Wout >= 1,
-                "frames_u8_to_f32_boxes: N / H / W must be >= 1 (N %d, %d x %d -> %d x %d)", N, Hin, Win, Hout, Wout);
-    SPK_REQUIRE(H >= Hin && W >= Win, "frames_u8_to_f32_boxes: the %d x %d box does not fit the %d x %d frame", Hin, Win, H, W);
-    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_u8_to_f32_boxes: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
-    SPK_REQUIRE(row_stride >= 3ll * W, "frames_u8_to_f32_boxes: row stride %lld is smaller than 3 * W = %lld", (long long)row_stride, 3ll * W);
-    SPK_REQUIRE(image_stride >= 0, "frames_u8_to_f32_boxes: negative image stride");
-    const int strips = spk::ceil_div(Hout, STRIP);
-    const long long total = (long long)N * strips * Wout;
-    Affine3 af = {{scale0, scale1, scale2}, {shift0, shift1, shift2}};
-    hipLaunchKernelGGL(frames_u8_to_f32_kernel<true>, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
-                       (hipStream_t)stream, src, (long long)image_stride, (long long)row_stride, (const int*)boxes_yx, H, W, Hin, Win, swap_rb,
-                       first_y, count_y, w_y, taps_y, first_x, count_x, w_x, taps_x, dst, Hout, Wout, strips, total, af);
-    return spk::check_launch("frames_u8_to_f32_kernel<boxes>");
+    return launch_u8_to_f32("frames_u8_to_f32_boxes", true, src, image_stride, row_stride, N, H, W, boxes_yx, Hin, Win, swap_rb,
+                            {first_y, count_y, w_y, first_x, count_x, w_x, taps_y, taps_x}, dst, Hout, Wout,
+                            {{scale0, scale1, scale2}, {shift0, shift1, shift2}}, stream);
 }
 
 int spk_frames_f32_to_u8(const float* src, uint8_t* dst, int N, int H, int W, int swap_rb, float lo, float k, void* stream) {
     SPK_REQUIRE(src && dst, "frames_f32_to_u8: null frame pointer");
     SPK_REQUIRE(N >= 1 && H >= 1 && W >= 1, "frames_f32_to_u8: N / H / W must be >= 1 (N %d, %d x %d)", N, H, W);
-    SPK_REQUIRE(std::isfinite(lo) && std::isfinite(k) && k > 0.f, "frames_f32_to_u8: the value range must be finite and increasing");
+    if (int rc = check_range("frames_f32_to_u8", lo, k)) return rc;
     const long long HW = (long long)H * W, groups = (HW + 3) / 4, total = (long long)N * groups;
     const bool vec_in = HW % 4 == 0 && (uintptr_t)src % 16 == 0;
     const int mode = !vec_in ? 0 : (uintptr_t)dst % 4 == 0 ? 2 : 1;
-    const dim3 grid((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP));
+    const dim3 grid = grid_for(total);
     if (mode == 2) hipLaunchKernelGGL(frames_f32_to_u8_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, HW, groups, total, swap_rb, lo, k);
     else if (mode == 1) hipLaunchKernelGGL(frames_f32_to_u8_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, HW, groups, total, swap_rb, lo, k);
     else hipLaunchKernelGGL(frames_f32_to_u8_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, src, dst, HW, groups, total, swap_rb, lo, k);
@@ -363,21 +297,21 @@ int spk_frames_paste_u8(const float* src, int N, int Hs, int Ws, uint8_t* dst, i
                         int h, int w, int y0, int x0, const int32_t* boxes_yx, int swap_rb, const int32_t* first_y, const int32_t* count_y,
                         const float* w_y, int taps_y, const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x,
                         const float* a_y, const float* a_x, float lo, float k, void* stream) {
-    SPK_REQUIRE(src && dst, "frames_paste_u8: null frame pointer");
-    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_paste_u8: null table pointer");
-    SPK_REQUIRE((a_y == nullptr) == (a_x == nullptr), "frames_paste_u8: the feather tables are both given or both null");
+    const char* who = "frames_paste_u8";
+    const ResizeTables t = {first_y, count_y, w_y, first_x, count_x, w_x, taps_y, taps_x};
+    SPK_REQUIRE(src && dst, "%s: null frame pointer", who);
+    if (int rc = check_tables(who, t)) return rc;
+    SPK_REQUIRE((a_y == nullptr) == (a_x == nullptr), "%s: the feather tables are both given or both null", who);
     SPK_REQUIRE(N >= 1 && Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1 && h >= 1 && w >= 1,
-                "frames_paste_u8: N / H / W must be >= 1 (N %d, source %d x %d, box %d x %d, frame %d x %d)", N, Hs, Ws, h, w, H, W);
-    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_paste_u8: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
-    SPK_REQUIRE(row_stride >= 3ll * W, "frames_paste_u8: row stride %lld is smaller than 3 * W = %lld", (long long)row_stride, 3ll * W);
+                "%s: N / H / W must be >= 1 (N %d, source %d x %d, box %d x %d, frame %d x %d)", who, N, Hs, Ws, h, w, H, W);
+    SPK_REQUIRE(row_stride >= 3ll * W, "%s: row stride %lld is smaller than 3 * W = %lld", who, (long long)row_stride, 3ll * W);
     SPK_REQUIRE(N == 1 || image_stride >= (long long)(H - 1) * row_stride + 3ll * W,
-                "frames_paste_u8: image stride %lld makes the frames overlap (%d rows of stride %lld)", (long long)image_stride, H,
-                (long long)row_stride);
-    SPK_REQUIRE(std::isfinite(lo) && std::isfinite(k) && k > 0.f, "frames_paste_u8: the value range must be finite and increasing");
+                "%s: image stride %lld makes the frames overlap (%d rows of stride %lld)", who, (long long)image_stride, H, (long long)row_stride);
+    if (int rc = check_range(who, lo, k)) return rc;
     const long long total = (long long)N * h * w;
-    hipLaunchKernelGGL(frames_paste_u8_kernel, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
-                       (hipStream_t)stream, src, Hs, Ws, dst, N > 1 ? (long long)image_stride : 0ll, (long long)row_stride, H, W, h, w, y0, x0,
-                       (const int*)boxes_yx, swap_rb, first_y, count_y, w_y, taps_y, first_x, count_x, w_x, taps_x, a_y, a_x, lo, k, total);
+    hipLaunchKernelGGL(frames_paste_u8_kernel, grid_for(total), dim3(256), 0, (hipStream_t)stream, src, Hs, Ws, dst,
+                       N > 1 ? (long long)image_stride : 0ll, (long long)row_stride, H, W, h, w, y0, x0, (const int*)boxes_yx, swap_rb, t, a_y, a_x,
+                       lo, k, total);
     return spk::check_launch("frames_paste_u8_kernel");
 }
 

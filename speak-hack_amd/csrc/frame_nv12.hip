@@ -5,19 +5,14 @@
 //   frames_paste_nv12: resize to the box + quantise + RGB -> YUV + feather-blend into the surface the box came from, one pass,
 //   one thread per chroma block (2 x 2 luma pixels); frames_f32_to_nv12 is its whole-frame case without tables.
 // Definitions (siting, colour matrices, the order of every operation) are in include/spk.h.  The resize tables are those of
-// csrc/frame_io.hip (spk_resize_table, spk_feather_table): this file holds no filter arithmetic and links without that one.
-#include "spk_common.hpp"
-
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
+// csrc/frame_io.hip (spk_resize_table, spk_feather_table): this file holds no filter arithmetic and links without that one; what
+// the two share is in csrc/frame_common.hpp.
+#include "frame_common.hpp"
 
 namespace {
 
-constexpr int STRIP = 8;            // output rows a thread of the resize owns
-constexpr int GRID_CAP = 2048;      // workgroups per launch; the rest of the work is a grid-stride trip
+using namespace spk::frame;
 
-struct Affine3 { float scale[3], shift[3]; };
 struct Mat34 { double m[12]; };     // three rows [a0 a1 a2 offset], byte units
 
 // row c of a 3 x 4 affine map applied to (p0, p1, p2, 1): one fp64 fma chain that starts from the offset
@@ -63,44 +58,28 @@ void yuv_coeffs(double kr, double kb, bool full, double* to_rgb, double* from_rg
 __global__ __launch_bounds__(256) void frames_nv12_to_f32_kernel(const uint8_t* __restrict__ yp, long long y_image_stride, long long y_row_stride,
                                                                  const uint8_t* __restrict__ uvp, long long uv_image_stride,
                                                                  long long uv_row_stride, const int* __restrict__ boxes_yx, int y0, int x0,
-                                                                 int H, int W, int Hin, int Win, int swap_rb,
-                                                                 const int* __restrict__ first_y, const int* __restrict__ count_y,
-                                                                 const float* __restrict__ w_y, int taps_y, const int* __restrict__ first_x,
-                                                                 const int* __restrict__ count_x, const float* __restrict__ w_x, int taps_x,
+                                                                 int H, int W, int Hin, int Win, int swap_rb, ResizeTables t,
                                                                  float* __restrict__ dst, int Hout, int Wout, int strips, long long total,
                                                                  Affine3 af, Mat34 to_rgb) {
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const int ox = (int)(idx % Wout);
-        const int strip = (int)((idx / Wout) % strips);
-        const long long n = idx / ((long long)Wout * strips);
-        const int oy0 = strip * STRIP;
-        const int fx = min(max(first_x[ox], 0), Win - 1);
-        const int cx = max(min(min(count_x[ox], taps_x), Win - fx), 0);
-        int fy[STRIP], cy[STRIP];
-        int row_lo = Hin, row_hi = 0;
-#pragma unroll
-        for (int k = 0; k < STRIP; ++k) {
-            const int oy = min(oy0 + k, Hout - 1);
-            fy[k] = min(max(first_y[oy], 0), Hin - 1);
-            cy[k] = oy0 + k < Hout ? max(min(min(count_y[oy], taps_y), Hin - fy[k]), 0) : 0;
-            if (cy[k] > 0) { row_lo = min(row_lo, fy[k]); row_hi = max(row_hi, fy[k] + cy[k]); }
-        }
+        const Strip s = strip_prologue(idx, t, Hin, Win, Hout, Wout, strips);
         double acc[STRIP][3];
 #pragma unroll
         for (int k = 0; k < STRIP; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 0.0;
-        const int Y0 = min(max(boxes_yx ? boxes_yx[2 * n] : y0, 0), H - Hin), X0 = min(max(boxes_yx ? boxes_yx[2 * n + 1] : x0, 0), W - Win);
-        const int Xs = X0 + fx;                                  // frame column of the window's first tap
-        const uint8_t* luma = yp + n * y_image_stride + Xs;
-        const uint8_t* chroma = uvp + n * uv_image_stride;
-        const float* wx = w_x + (long long)ox * taps_x;
+        const Origin o = box_origin(boxes_yx, s.n, y0, x0);
+        const int Y0 = min(max(o.y, 0), H - Hin), X0 = min(max(o.x, 0), W - Win);
+        const int Xs = X0 + s.fx;                                // frame column of the window's first tap
+        const uint8_t* luma = yp + s.n * y_image_stride + Xs;
+        const uint8_t* chroma = uvp + s.n * uv_image_stride;
+        const float* wx = t.w_x + (long long)s.ox * t.taps_x;
         double hu = 0.0, hv = 0.0;
-        for (int iy = row_lo; iy < row_hi; ++iy) {
+        for (int iy = s.row_lo; iy < s.row_hi; ++iy) {
             const int Yf = Y0 + iy;
-            if (iy == row_lo || !(Yf & 1)) {                     // a new chroma row: its sums serve this luma row and the next
+            if (iy == s.row_lo || !(Yf & 1)) {                   // a new chroma row: its sums serve this luma row and the next
                 const uint8_t* c = chroma + (long long)(Yf >> 1) * uv_row_stride;
                 unsigned pair = 0;
                 hu = hv = 0.0;
-                for (int j = 0; j < cx; ++j) {
+                for (int j = 0; j < s.cx; ++j) {
                     const int X = Xs + j;
                     if (j == 0 || !(X & 1)) pair = *reinterpret_cast<const uint16_t*>(c + (X & ~1));
                     const double w = (double)wx[j];
@@ -110,28 +89,19 @@ __global__ __launch_bounds__(256) void frames_nv12_to_f32_kernel(const uint8_t* 
             }
             const uint8_t* p = luma + (long long)Yf * y_row_stride;
             double hy = 0.0;
-            for (int j = 0; j < cx; ++j) hy = fma((double)wx[j], (double)p[j], hy);
-#pragma unroll
-            for (int k = 0; k < STRIP; ++k) {
-                const int j = iy - fy[k];
-                if ((unsigned)j < (unsigned)cy[k]) {
-                    const double w = (double)w_y[(long long)(oy0 + k) * taps_y + j];
-                    acc[k][0] = fma(w, hy, acc[k][0]);
-                    acc[k][1] = fma(w, hu, acc[k][1]);
-                    acc[k][2] = fma(w, hv, acc[k][2]);
-                }
-            }
+            for (int j = 0; j < s.cx; ++j) hy = fma((double)wx[j], (double)p[j], hy);
+            strip_accumulate(acc, s, t, iy, hy, hu, hv);
         }
         const long long plane = (long long)Hout * Wout;
-        float* out = dst + n * 3 * plane + ox;
+        float* out = dst + s.n * 3 * plane + s.ox;
 #pragma unroll
         for (int k = 0; k < STRIP; ++k) {
-            if (oy0 + k >= Hout) break;
+            if (s.oy0 + k >= Hout) break;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {                        // c: R, G, B
                 const double rgb = fmin(fmax(affine_row(to_rgb, c, acc[k][0], acc[k][1], acc[k][2]), 0.0), 255.0);
                 const int cd = swap_rb ? 2 - c : c;
-                out[cd * plane + (long long)(oy0 + k) * Wout] = (float)fma((double)af.scale[cd], rgb, (double)af.shift[cd]);
+                out[cd * plane + (long long)(s.oy0 + k) * Wout] = (float)fma((double)af.scale[cd], rgb, (double)af.shift[cd]);
             }
         }
     }
@@ -151,17 +121,15 @@ template <bool RESIZE>
 __global__ __launch_bounds__(256) void frames_paste_nv12_kernel(const float* __restrict__ src, int Hs, int Ws, uint8_t* yp, long long y_image_stride,
                                                                 long long y_row_stride, uint8_t* uvp, long long uv_image_stride,
                                                                 long long uv_row_stride, int H, int W, int h, int w, int y0, int x0,
-                                                                const int* __restrict__ boxes_yx, const int* __restrict__ first_y,
-                                                                const int* __restrict__ count_y, const float* __restrict__ w_y, int taps_y,
-                                                                const int* __restrict__ first_x, const int* __restrict__ count_x,
-                                                                const float* __restrict__ w_x, int taps_x, const float* __restrict__ a_y,
-                                                                const float* __restrict__ a_x, float lo, float k, int blocks_y, int blocks_x,
-                                                                long long total, Mat34 from_rgb) {
+                                                                const int* __restrict__ boxes_yx, ResizeTables t,
+                                                                const float* __restrict__ a_y, const float* __restrict__ a_x, float lo, float k,
+                                                                int blocks_y, int blocks_x, long long total, Mat34 from_rgb) {
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const int bx = (int)(idx % blocks_x);
         const int by = (int)((idx / blocks_x) % blocks_y);
         const long long n = idx / ((long long)blocks_x * blocks_y);
-        const long long Y0 = boxes_yx ? boxes_yx[2 * n] : y0, X0 = boxes_yx ? boxes_yx[2 * n + 1] : x0;
+        const Origin o = box_origin(boxes_yx, n, y0, x0);
+        const long long Y0 = o.y, X0 = o.x;
         const long long CY = (Y0 - (Y0 & 1)) / 2 + by, CX = (X0 - (X0 & 1)) / 2 + bx;       // floor(origin / 2) + block
         if (CY < 0 || CY >= H / 2 || CX < 0 || CX >= W / 2) continue;
         const long long plane = (long long)Hs * Ws;
@@ -177,33 +145,14 @@ __global__ __launch_bounds__(256) void frames_paste_nv12_kernel(const float* __r
             const int y = (int)yl, x = (int)xl;
             double v0 = 0.0, v1 = 0.0, v2 = 0.0;
             if (RESIZE) {
-                // the tables are the caller's: clamp every window into the source so that no table can send a load out of bounds
-                const int fx = min(max(first_x[x], 0), Ws - 1), cx = max(min(min(count_x[x], taps_x), Ws - fx), 0);
-                const int fy = min(max(first_y[y], 0), Hs - 1), cy = max(min(min(count_y[y], taps_y), Hs - fy), 0);
-                const float* wx = w_x + (long long)x * taps_x;
-                const float* wy = w_y + (long long)y * taps_y;
-                const float* in = img + (long long)fy * Ws + fx;
-                for (int i = 0; i < cy; ++i) {
-                    const float* p = in + (long long)i * Ws;
-                    double h0 = 0.0, h1 = 0.0, h2 = 0.0;
-                    for (int j = 0; j < cx; ++j) {
-                        const double wj = (double)wx[j];
-                        h0 = fma(wj, (double)p[j], h0);
-                        h1 = fma(wj, (double)p[plane + j], h1);
-                        h2 = fma(wj, (double)p[2 * plane + j], h2);
-                    }
-                    const double wi = (double)wy[i];
-                    v0 = fma(wi, h0, v0);
-                    v1 = fma(wi, h1, v1);
-                    v2 = fma(wi, h2, v2);
-                }
+                resize_point(img, plane, Hs, Ws, t, y, x, v0, v1, v2);
             } else {
                 const float* in = img + (long long)y * Ws + x;
                 v0 = (double)in[0]; v1 = (double)in[plane]; v2 = (double)in[2 * plane];
             }
-            const double q0 = (double)fminf(fmaxf(__fmul_rn(__fsub_rn((float)v0, lo), k), 0.f), 255.f);
-            const double q1 = (double)fminf(fmaxf(__fmul_rn(__fsub_rn((float)v1, lo), k), 0.f), 255.f);
-            const double q2 = (double)fminf(fmaxf(__fmul_rn(__fsub_rn((float)v2, lo), k), 0.f), 255.f);
+            const double q0 = (double)quant_unrounded((float)v0, lo, k);
+            const double q1 = (double)quant_unrounded((float)v1, lo, k);
+            const double q2 = (double)quant_unrounded((float)v2, lo, k);
             const double e_y = affine_row(from_rgb, 0, q0, q1, q2), e_u = affine_row(from_rgb, 1, q0, q1, q2),
                          e_v = affine_row(from_rgb, 2, q0, q1, q2);
             const double m = a_y ? (double)a_y[y] * (double)a_x[x] : 1.0;
@@ -263,22 +212,22 @@ int spk_frames_nv12_to_f32(const uint8_t* y, int64_t y_image_stride, int64_t y_r
                            int standard, int full_range, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
                            const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout,
                            float scale0, float scale1, float scale2, float shift0, float shift1, float shift2, void* stream) {
-    if (int rc = check_surface("frames_nv12_to_f32", y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, N, H, W, false)) return rc;
-    SPK_REQUIRE(dst, "frames_nv12_to_f32: null frame pointer");
-    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_nv12_to_f32: null table pointer");
-    SPK_REQUIRE(Hin >= 1 && Win >= 1 && Hout >= 1 && Wout >= 1, "frames_nv12_to_f32: box and output sizes must be >= 1 (%d x %d -> %d x %d)", Hin,
-                Win, Hout, Wout);
-    SPK_REQUIRE(H >= Hin && W >= Win, "frames_nv12_to_f32: the %d x %d box does not fit the %d x %d frame", Hin, Win, H, W);
-    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_nv12_to_f32: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
+    const char* who = "frames_nv12_to_f32";
+    const ResizeTables t = {first_y, count_y, w_y, first_x, count_x, w_x, taps_y, taps_x};
+    if (int rc = check_surface(who, y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, N, H, W, false)) return rc;
+    SPK_REQUIRE(dst, "%s: null frame pointer", who);
+    if (int rc = check_tables(who, t)) return rc;
+    SPK_REQUIRE(Hin >= 1 && Win >= 1 && Hout >= 1 && Wout >= 1, "%s: box and output sizes must be >= 1 (%d x %d -> %d x %d)", who, Hin, Win, Hout,
+                Wout);
+    SPK_REQUIRE(H >= Hin && W >= Win, "%s: the %d x %d box does not fit the %d x %d frame", who, Hin, Win, H, W);
     Mat34 M;
     if (int rc = spk_yuv_coeffs(standard, full_range, M.m, nullptr)) return rc;
     const int strips = spk::ceil_div(Hout, STRIP);
     const long long total = (long long)N * strips * Wout;
     Affine3 af = {{scale0, scale1, scale2}, {shift0, shift1, shift2}};
-    hipLaunchKernelGGL(frames_nv12_to_f32_kernel, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
-                       (hipStream_t)stream, y, N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv,
-                       N > 1 ? (long long)uv_image_stride : 0ll, (long long)uv_row_stride, (const int*)boxes_yx, y0, x0, H, W, Hin, Win, swap_rb,
-                       first_y, count_y, w_y, taps_y, first_x, count_x, w_x, taps_x, dst, Hout, Wout, strips, total, af, M);
+    hipLaunchKernelGGL(frames_nv12_to_f32_kernel, grid_for(total), dim3(256), 0, (hipStream_t)stream, y, N > 1 ? (long long)y_image_stride : 0ll,
+                       (long long)y_row_stride, uv, N > 1 ? (long long)uv_image_stride : 0ll, (long long)uv_row_stride, (const int*)boxes_yx, y0, x0,
+                       H, W, Hin, Win, swap_rb, t, dst, Hout, Wout, strips, total, af, M);
     return spk::check_launch("frames_nv12_to_f32_kernel");
 }
 
@@ -287,22 +236,21 @@ int spk_frames_paste_nv12(const float* src, int N, int Hs, int Ws, uint8_t* y, i
                           int standard, int full_range, const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y,
                           const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, const float* a_y, const float* a_x,
                           float lo, float k, void* stream) {
-    SPK_REQUIRE(src, "frames_paste_nv12: null frame pointer");
-    if (int rc = check_surface("frames_paste_nv12", y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, N, H, W, true)) return rc;
-    SPK_REQUIRE(first_y && count_y && w_y && first_x && count_x && w_x, "frames_paste_nv12: null table pointer");
-    SPK_REQUIRE((a_y == nullptr) == (a_x == nullptr), "frames_paste_nv12: the feather tables are both given or both null");
-    SPK_REQUIRE(Hs >= 1 && Ws >= 1 && h >= 1 && w >= 1, "frames_paste_nv12: source and box sizes must be >= 1 (source %d x %d, box %d x %d)", Hs, Ws,
-                h, w);
-    SPK_REQUIRE(taps_y >= 1 && taps_x >= 1, "frames_paste_nv12: tap count must be >= 1 (got %d, %d)", taps_y, taps_x);
-    SPK_REQUIRE(std::isfinite(lo) && std::isfinite(k) && k > 0.f, "frames_paste_nv12: the value range must be finite and increasing");
+    const char* who = "frames_paste_nv12";
+    const ResizeTables t = {first_y, count_y, w_y, first_x, count_x, w_x, taps_y, taps_x};
+    SPK_REQUIRE(src, "%s: null frame pointer", who);
+    if (int rc = check_surface(who, y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, N, H, W, true)) return rc;
+    if (int rc = check_tables(who, t)) return rc;
+    SPK_REQUIRE((a_y == nullptr) == (a_x == nullptr), "%s: the feather tables are both given or both null", who);
+    SPK_REQUIRE(Hs >= 1 && Ws >= 1 && h >= 1 && w >= 1, "%s: source and box sizes must be >= 1 (source %d x %d, box %d x %d)", who, Hs, Ws, h, w);
+    if (int rc = check_range(who, lo, k)) return rc;
     Mat34 M;
     if (int rc = spk_yuv_coeffs(standard, full_range, nullptr, M.m)) return rc;
     const int blocks_y = h / 2 + 1, blocks_x = w / 2 + 1;
     const long long total = (long long)N * blocks_y * blocks_x;
-    hipLaunchKernelGGL(frames_paste_nv12_kernel<true>, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
-                       (hipStream_t)stream, src, Hs, Ws, y, N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv,
-                       N > 1 ? (long long)uv_image_stride : 0ll, (long long)uv_row_stride, H, W, h, w, y0, x0, (const int*)boxes_yx, first_y, count_y,
-                       w_y, taps_y, first_x, count_x, w_x, taps_x, a_y, a_x, lo, k, blocks_y, blocks_x, total, M);
+    hipLaunchKernelGGL(frames_paste_nv12_kernel<true>, grid_for(total), dim3(256), 0, (hipStream_t)stream, src, Hs, Ws, y,
+                       N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv, N > 1 ? (long long)uv_image_stride : 0ll,
+                       (long long)uv_row_stride, H, W, h, w, y0, x0, (const int*)boxes_yx, t, a_y, a_x, lo, k, blocks_y, blocks_x, total, M);
     return spk::check_launch("frames_paste_nv12_kernel");
 }
 
@@ -310,15 +258,14 @@ int spk_frames_f32_to_nv12(const float* src, int N, int H, int W, uint8_t* y, in
                            int64_t uv_image_stride, int64_t uv_row_stride, int standard, int full_range, float lo, float k, void* stream) {
     SPK_REQUIRE(src, "frames_f32_to_nv12: null frame pointer");
     if (int rc = check_surface("frames_f32_to_nv12", y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, N, H, W, true)) return rc;
-    SPK_REQUIRE(std::isfinite(lo) && std::isfinite(k) && k > 0.f, "frames_f32_to_nv12: the value range must be finite and increasing");
+    if (int rc = check_range("frames_f32_to_nv12", lo, k)) return rc;
     Mat34 M;
     if (int rc = spk_yuv_coeffs(standard, full_range, nullptr, M.m)) return rc;
     const int blocks_y = H / 2, blocks_x = W / 2;            // the origin is (0, 0): the blocks of the frame, none empty
     const long long total = (long long)N * blocks_y * blocks_x;
-    hipLaunchKernelGGL(frames_paste_nv12_kernel<false>, dim3((unsigned)std::min((total + 255) / 256, (long long)GRID_CAP)), dim3(256), 0,
-                       (hipStream_t)stream, src, H, W, y, N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv,
-                       N > 1 ? (long long)uv_image_stride : 0ll, (long long)uv_row_stride, H, W, H, W, 0, 0, (const int*)nullptr, (const int*)nullptr,
-                       (const int*)nullptr, (const float*)nullptr, 1, (const int*)nullptr, (const int*)nullptr, (const float*)nullptr, 1,
+    hipLaunchKernelGGL(frames_paste_nv12_kernel<false>, grid_for(total), dim3(256), 0, (hipStream_t)stream, src, H, W, y,
+                       N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv, N > 1 ? (long long)uv_image_stride : 0ll,
+                       (long long)uv_row_stride, H, W, H, W, 0, 0, (const int*)nullptr, ResizeTables{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1},
                        (const float*)nullptr, (const float*)nullptr, lo, k, blocks_y, blocks_x, total, M);
     return spk::check_launch("frames_paste_nv12_kernel<whole frame>");
 }

@@ -22,6 +22,7 @@ import math
 import torch
 import torch.nn as nn
 
+from . import frames as FR
 from . import ops
 from . import autograd as AG
 from . import plan as PL
@@ -298,7 +299,7 @@ class StyleGenerator(nn.Module):
         key = (B, features.device, torch.cuda.current_stream(features.device).cuda_stream, "features", syn.precision,
                self.truncation_psi, self.truncation_cutoff)
         if output == "nv12":
-            key += (output, float(value_range[0]), float(value_range[1]), *ops._yuv_standard(standard, full_range))
+            key += (output, float(value_range[0]), float(value_range[1]), *FR.yuv_standard(standard, full_range))
         elif output != "f32":
             key += (output, float(value_range[0]), float(value_range[1]), bool(swap_rb))
         if seed is not None:

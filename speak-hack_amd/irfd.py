@@ -23,11 +23,24 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import autograd as AG
+from . import frames as FR
 from . import ops
 from . import plan as PL
 from .decoder import StyleGenerator
 from .discriminator import StyleDiscriminator
 from .encoder import GroupedTrunks, ResNet50Trunk
+
+
+def _check_noise(what, noise, seed, noises, frame0):
+    """The noise arguments of ``reenact`` / ``reenact_video`` (``what``: the caller's prefix), checked before any launch."""
+    if noise not in ("fresh", "fixed"):
+        raise ValueError(f"{what}: noise must be 'fresh' or 'fixed', got {noise!r}")
+    if seed is None and noise == "fixed":
+        raise ValueError(f"{what}: noise='fixed' needs a seed")
+    if seed is not None:
+        if noises is not None:
+            raise ValueError(f"{what}: pass either seed or noises, not both")
+        ops.check_seed(seed, frame0, f"{what}: seed")
 
 
 class IRFD(nn.Module):
@@ -122,16 +135,9 @@ class IRFD(nn.Module):
         """``reenact``'s argument checks and chunk loop: yields ``(t0, t1, frames of [t0, t1))``."""
         if output not in ("f32", "uint8", "nv12"):
             raise ValueError(f"reenact: output must be 'f32', 'uint8' or 'nv12', got {output!r}")
-        ops._yuv_standard(*colour)
-        if noise not in ("fresh", "fixed"):
-            raise ValueError(f"reenact: noise must be 'fresh' or 'fixed', got {noise!r}")
-        if seed is None and noise == "fixed":
-            raise ValueError("reenact: noise='fixed' needs a seed")
-        if seed is not None:
-            if noises is not None:
-                raise ValueError("reenact: pass either seed or noises, not both")
-            ops.check_seed(seed, frame0, "reenact: seed")
-        elif frame0 != 0:
+        FR.yuv_standard(*colour)
+        _check_noise("reenact", noise, seed, noises, frame0)
+        if seed is None and frame0 != 0:
             raise ValueError("reenact: frame0 applies to seeded noise only")
         if channel_order not in ("rgb", "bgr"):
             raise ValueError(f"reenact: channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
@@ -182,82 +188,36 @@ class IRFD(nn.Module):
         ``[T,3R/2,R]``, or with ``paste=True`` the pose surfaces with every face pasted back (``ops.frames_from_nv12``,
         ``reenact(output="nv12")``, ``ops.frames_paste_nv12``: one launch per chunk).  The identity image stays a uint8 HWC photo
         in ``channel_order``; ``crop`` keeps its three forms and may have an odd origin."""
-        if pixel_format not in ("rgb24", "nv12"):
+        if pixel_format not in FR.PIXEL_FORMATS:
             raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
         if pixel_format == "rgb24" and (standard != "bt601" or full_range):
             raise ValueError("reenact_video: standard / full_range apply to pixel_format='nv12' only")
-        ops._yuv_standard(standard, full_range)
+        FR.yuv_standard(standard, full_range)
         feather = float(feather)
         if inplace and not paste:
             raise ValueError("reenact_video: inplace applies to paste=True only")
         if not paste and feather != 0:
             raise ValueError("reenact_video: feather applies to paste=True only")
-        if not (0.0 <= feather < float("inf")):
-            raise ValueError(f"reenact_video: feather must be a finite number >= 0, got {feather}")
-        if noise not in ("fresh", "fixed"):
-            raise ValueError(f"reenact_video: noise must be 'fresh' or 'fixed', got {noise!r}")
-        if seed is None and noise == "fixed":
-            raise ValueError("reenact_video: noise='fixed' needs a seed")
-        if seed is not None:
-            if noises is not None:
-                raise ValueError("reenact_video: pass either seed or noises, not both")
-            ops.check_seed(seed, frame0, "reenact_video: seed")
-        if pixel_format == "nv12":
-            return self._reenact_video_nv12(identity_u8, pose_u8, emotion_u8, size, crop, channel_order, noises, chunk, seed, noise, frame0,
-                                            paste, feather, inplace, (standard, full_range))
-        if crop is not None or paste:
-            if pose_u8.dim() != 4 or pose_u8.size(3) != 3 or pose_u8.size(0) < 1:
-                raise ValueError(f"reenact_video: pose_u8 must be [T,H,W,3], got {tuple(pose_u8.shape)}")
-            if inplace and not ops._packed_pixels(pose_u8):
-                raise L.SpkError(f"reenact_video: inplace needs packed pixels and rows / frames that do not overlap, got strides {pose_u8.stride()}")
-            T, H, W = pose_u8.shape[:3]
-            origins, h, w = ops.parse_boxes((0, 0, H, W) if crop is None else crop, T, H, W, "reenact_video: crop")
-            if not isinstance(origins, tuple) and not origins.is_cuda and pose_u8.is_cuda:
-                origins = origins.to(pose_u8.device)                       # host boxes: checked above, uploaded once for both edges
+        FR.check_feather(feather, "reenact_video")
+        _check_noise("reenact_video", noise, seed, noises, frame0)
+        fmt = FR.PIXEL_FORMATS[pixel_format](channel_order, standard, full_range)
+        pose_in = pose_u8
+        if crop is not None or paste or fmt.needs_box:
+            pose_in, device, T, H, W = fmt.open(pose_u8, inplace)
+            origins, h, w = FR.parse_boxes((0, 0, H, W) if crop is None else crop, T, H, W, "reenact_video: crop")
+            if not isinstance(origins, tuple) and not origins.is_cuda and device.type == "cuda":
+                origins = origins.to(device)                               # host boxes: checked above, uploaded once for both edges
             crop = (*origins, h, w) if isinstance(origins, tuple) else (origins, h, w)
-        ident = ops.frames_from_u8(identity_u8, size, channel_order=channel_order)
-        pose = ops.frames_from_u8(pose_u8, size, crop=crop, channel_order=channel_order)
-        emo = None if emotion_u8 is None else ops.frames_from_u8(emotion_u8, size, crop=crop, channel_order=channel_order)
+        ident = FR.frames_from_u8(identity_u8, size, channel_order=channel_order)
+        pose = fmt.network_input(pose_in, size, crop)
+        emo = None if emotion_u8 is None else fmt.network_input(emotion_u8, size, crop)
         if not paste:
-            return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output="uint8", channel_order=channel_order, seed=seed,
-                                noise=noise, frame0=frame0)
-        frames = pose_u8 if inplace else pose_u8.clone(memory_format=torch.contiguous_format)
+            return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output=fmt.output, seed=seed, noise=noise, frame0=frame0,
+                                **fmt.args)
+        result, out = (pose_u8, pose_in) if inplace else fmt.clone(pose_in)
         for t0, t1, y in self._reenact_chunks(ident, pose, emo, noises, chunk, "f32", "rgb", seed, noise, frame0):
-            part = frames[t0:t1]
-            ops.frames_paste_u8(y, part, crop if len(crop) == 4 else (crop[0][t0:t1], h, w), feather=feather, channel_order=channel_order,
-                                out=part)
-        return frames
-
-    def _reenact_video_nv12(self, identity_u8, pose_nv12, emotion_nv12, size, crop, channel_order, noises, chunk, seed, noise, frame0,
-                            paste, feather, inplace, colour):
-        """``reenact_video`` on NV12 surfaces (its arguments are checked there)."""
-        standard, full_range = colour
-        py, puv = ops.nv12_planes(pose_nv12)
-        T, H, W = py.shape
-        origins, h, w = ops.parse_boxes((0, 0, H, W) if crop is None else crop, T, H, W, "reenact_video: crop")
-        if not isinstance(origins, tuple) and not origins.is_cuda and py.is_cuda:
-            origins = origins.to(py.device)                               # host boxes: checked above, uploaded once for both edges
-        crop = (*origins, h, w) if isinstance(origins, tuple) else (origins, h, w)
-        if inplace:
-            ops._nv12_strides(py, puv, "reenact_video: inplace", written=True)
-        ident = ops.frames_from_u8(identity_u8, size, channel_order=channel_order)
-        pose = ops.frames_from_nv12((py, puv), size, crop=crop, standard=standard, full_range=full_range)
-        emo = None if emotion_nv12 is None else ops.frames_from_nv12(emotion_nv12, size, crop=crop, standard=standard, full_range=full_range)
-        if not paste:
-            return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output="nv12", seed=seed, noise=noise, frame0=frame0,
-                                standard=standard, full_range=full_range)
-        if inplace:
-            frames, fy, fuv = pose_nv12, py, puv
-        else:                                                             # one clone: a packed surface per frame
-            frames = torch.empty((T, 3 * H // 2, W), device=py.device, dtype=torch.uint8)
-            fy, fuv = ops.nv12_planes(frames)
-            fy.copy_(py)
-            fuv.copy_(puv)
-        for t0, t1, y in self._reenact_chunks(ident, pose, emo, noises, chunk, "f32", "rgb", seed, noise, frame0):
-            part = (fy[t0:t1], fuv[t0:t1])
-            ops.frames_paste_nv12(y, part, crop if len(crop) == 4 else (crop[0][t0:t1], h, w), feather=feather, standard=standard,
-                                  full_range=full_range, out=part)
-        return frames
+            fmt.paste(y, out, t0, t1, crop if len(crop) == 4 else (crop[0][t0:t1], h, w), feather)
+        return result
 
     def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None, colour=("bt601", False)):
         """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan
@@ -266,11 +226,9 @@ class IRFD(nn.Module):
         Gd = self.Gd
         seeded = seeded or {}
         if hasattr(Gd, "plan_serves") and Gd.plan_serves(gin):
-            if output == "f32":
-                return Gd.plan_forward(gin, noises, **seeded)
-            if output == "nv12":
-                return Gd.plan_forward(gin, noises, output=output, standard=colour[0], full_range=colour[1], **seeded)
-            return Gd.plan_forward(gin, noises, output=output, swap_rb=channel_order == "bgr", **seeded)
+            how = {"f32": {}, "uint8": dict(output=output, swap_rb=channel_order == "bgr"),
+                   "nv12": dict(output=output, standard=colour[0], full_range=colour[1])}[output]
+            return Gd.plan_forward(gin, noises, **how, **seeded)
         flags = [(mod, mod.training) for mod in Gd.modules()]
         try:
             for mod, _ in flags:

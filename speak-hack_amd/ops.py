@@ -13,7 +13,9 @@ import os
 import torch
 
 from . import _lib as L
-
+# the video-frame edge lives in frames.py; ops.frames_from_u8 and the rest stay the documented API
+from .frames import (resize_tables, resize_tables_f32, feather_tables, parse_boxes, frames_from_u8, quant_range, frames_to_u8,  # noqa: F401
+                     frames_paste_u8, yuv_coeffs, nv12_planes, frames_from_nv12, frames_to_nv12, frames_paste_nv12)
 
 
 def _launch_conv2d(desc):
@@ -1426,459 +1428,6 @@ def global_avgpool(x):
     out = torch.empty((B, Cc, 1, 1), device=x.device, dtype=torch.float32)
     L.check(L.lib().spk_global_avgpool_fwd(L.dptr(x, "x"), L.dptr(out), B * Cc, H * W, L.stream_ptr()),
             "spk_global_avgpool_fwd")
-    return out
-
-
-# ---- the video-frame edge: uint8 HWC frames in and out (csrc/frame_io.hip) ------------------------------------------------
-def _channel_swap(channel_order) -> int:
-    if channel_order not in ("rgb", "bgr"):
-        raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
-    return 1 if channel_order == "bgr" else 0
-
-
-def _resize_table(n_in, n_out, dtype):
-    n_in, n_out = int(n_in), int(n_out)
-    if n_in < 1 or n_out < 1:
-        raise ValueError(f"resize_tables: sizes must be >= 1, got {n_in} -> {n_out}")
-    lib = L.lib()
-    taps = lib.spk_resize_table_taps(n_in, n_out)
-    if taps < 1:
-        raise L.SpkError(f"spk_resize_table_taps failed ({taps}): {lib.spk_last_error().decode()}")
-    first, count = torch.empty(n_out, dtype=torch.int32), torch.empty(n_out, dtype=torch.int32)
-    w = torch.empty((n_out, taps), dtype=dtype)
-    w64, w32 = (w.data_ptr(), None) if dtype == torch.float64 else (None, w.data_ptr())
-    L.check(lib.spk_resize_table(n_in, n_out, taps, first.data_ptr(), count.data_ptr(), w64, w32), "spk_resize_table")
-    return first, count, w
-
-
-def resize_tables(n_in, n_out):
-    """One axis of the separable triangle filter of ``F.interpolate(mode="bilinear", align_corners=False, antialias=True)``
-    for ``n_in -> n_out`` samples, built in fp64 on the host (``spk_resize_table``): output ``o`` is
-    ``sum_j w[o, j] * x[first[o] + j]`` over ``j < count[o]``.  -> CPU tensors ``first`` int32 [n_out], ``count`` int32 [n_out],
-    ``w`` float64 [n_out, taps], zero padded to the widest window."""
-    return _resize_table(n_in, n_out, torch.float64)
-
-
-def resize_tables_f32(n_in, n_out):
-    """The same table as the kernel reads it: fp32 weights, every row summing to exactly 1."""
-    return _resize_table(n_in, n_out, torch.float32)
-
-
-_resize_cache = {}
-
-
-def _device_resize_tables(Hin, Win, Hout, Wout, device):
-    key = (Hin, Win, Hout, Wout, device)
-    t = _resize_cache.get(key)
-    if t is None:
-        if len(_resize_cache) >= 32:
-            _resize_cache.pop(next(iter(_resize_cache)))
-        ty, tx = resize_tables_f32(Hin, Hout), resize_tables_f32(Win, Wout)
-        t = _resize_cache[key] = tuple(a.to(device) for a in ty) + tuple(a.to(device) for a in tx)
-    return t
-
-
-def _triple(v, name):
-    v = [float(v)] * 3 if isinstance(v, (int, float)) else [float(a) for a in v]
-    if len(v) != 3:
-        raise ValueError(f"{name} must be a number or three numbers")
-    return v
-
-
-def feather_tables(n, feather):
-    """The 1-D edge ramp of a pasted box (``spk_feather_table``, built in fp64 on the host, rounded to fp32):
-    ``a[i] = min(1, (min(i, n - 1 - i) + 1) / (feather + 1))``; ``feather >= 0`` is a real number, 0 gives all ones.  A pasted
-    pixel ``(y, x)`` is blended with weight ``a_y[y] * a_x[x]``.  -> CPU float32 tensor [n]."""
-    n, feather = int(n), float(feather)
-    if n < 1:
-        raise ValueError(f"feather_tables: n must be >= 1, got {n}")
-    if not (0.0 <= feather < float("inf")):
-        raise ValueError(f"feather_tables: feather must be a finite number >= 0, got {feather}")
-    a = torch.empty(n, dtype=torch.float32)
-    L.check(L.lib().spk_feather_table(n, feather, a.data_ptr()), "spk_feather_table")
-    return a
-
-
-_feather_cache = {}
-
-
-def _device_feather_tables(h, w, feather, device):
-    key = (h, w, feather, device)
-    t = _feather_cache.get(key)
-    if t is None:
-        if len(_feather_cache) >= 32:
-            _feather_cache.pop(next(iter(_feather_cache)))
-        t = _feather_cache[key] = (feather_tables(h, feather).to(device), feather_tables(w, feather).to(device))
-    return t
-
-
-def parse_boxes(box, N, H, W, what="box", inside=True):
-    """The three forms a launcher takes a box in, for ``N`` frames of ``H`` x ``W`` pixels, checked on the host:
-    ``(y0, x0, h, w)``, one box for all frames; a host sequence or CPU integer tensor ``[N,4]`` of such rows, one per frame,
-    whose ``h, w`` are all equal (a call has one filter table); ``(boxes_yx, h, w)`` with a DEVICE int32 tensor ``[N,2]`` of
-    origins, which is not read here (the kernels clamp / skip).  Host boxes that leave the frame raise ``ValueError``.
-    ``inside``: the device form's ``h x w`` must fit the frame too (the input kernel clamps origins; the paste kernel skips).
-    -> ``(origins, h, w)``: ``origins`` is ``(y0, x0)``, a CPU int32 tensor [N,2] still to be uploaded, or the device tensor."""
-    def in_frame(y0, x0, h, w):
-        if y0 < 0 or x0 < 0 or h < 1 or w < 1 or y0 + h > H or x0 + w > W:
-            raise ValueError(f"{what}: box {(y0, x0, h, w)} leaves the {H} x {W} frame")
-
-    if isinstance(box, (tuple, list)) and len(box) == 3 and isinstance(box[0], torch.Tensor):
-        yx, h, w = box[0], int(box[1]), int(box[2])
-        if yx.dtype != torch.int32 or tuple(yx.shape) != (N, 2):
-            raise ValueError(f"{what}: box origins must be an int32 tensor [{N},2], got {yx.dtype} {tuple(yx.shape)}")
-        if h < 1 or w < 1 or (inside and (h > H or w > W)):
-            raise ValueError(f"{what}: a {h} x {w} box does not fit the {H} x {W} frame")
-        if yx.is_cuda and not yx.is_contiguous():
-            yx = yx.contiguous()
-        return yx, h, w
-    if isinstance(box, torch.Tensor):
-        if box.is_cuda or box.is_floating_point() or box.dim() != 2:
-            raise ValueError(f"{what}: a tensor of boxes must be a CPU integer tensor [N,4] (device origins go as (boxes_yx, h, w))")
-        box = box.tolist()
-    box = list(box)
-    if len(box) == 4 and not isinstance(box[0], (tuple, list)):
-        y0, x0, h, w = (int(v) for v in box)
-        in_frame(y0, x0, h, w)
-        return (y0, x0), h, w
-    rows = [tuple(int(v) for v in r) for r in box]
-    if len(rows) != N or any(len(r) != 4 for r in rows):
-        raise ValueError(f"{what}: per-frame boxes must be [{N},4] rows of (y0, x0, h, w), got {len(rows)} rows")
-    h, w = rows[0][2], rows[0][3]
-    if any((r[2], r[3]) != (h, w) for r in rows):
-        raise ValueError(f"{what}: the boxes of one call must have one size (a call has one filter table per axis), "
-                         f"got {sorted(set((r[2], r[3]) for r in rows))}")
-    for r in rows:
-        in_frame(*r)
-    return torch.tensor([r[:2] for r in rows], dtype=torch.int32), h, w
-
-
-def _packed_pixels(frames_u8):
-    """uint8 [N,H,W,3] with packed pixels and rows / frames that do not overlap: what the kernels address by byte strides."""
-    N, H, W, _ = frames_u8.shape
-    return frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3 and frames_u8.stride(1) >= 3 * W and \
-        (N == 1 or frames_u8.stride(0) >= (H - 1) * frames_u8.stride(1) + 3 * W)
-
-
-def frames_from_u8(frames_u8, size, *, crop=None, channel_order="rgb", mean=0.5, std=0.5):
-    """uint8 HWC video frames -> the network's input, one launch (``spk_frames_u8_to_f32``): crop, antialiased bilinear resize
-    to ``size`` x ``size`` (a number, or ``(H, W)``), ``(x / 255 - mean) / std`` per channel and HWC -> CHW -- ``transforms.Resize``
-    + ``ToTensor`` + ``Normalize`` of inference.py:29-33 with the ``cv2.cvtColor`` of :53 (``channel_order="bgr"``: the frames are
-    BGR, the result is RGB).  ``frames_u8``: uint8 [N,H,W,3] (or [H,W,3]) on the device, pixels packed (any row / frame stride:
-    slices of a larger frame are read in place); ``crop=(y0, x0, h, w)``: one box for all frames; a host sequence or CPU integer
-    tensor ``[N,4]``: a box per frame, all of one size (``ValueError`` otherwise: a call has one filter table), checked on the
-    host and uploaded once; ``(boxes_yx, h, w)`` with a device int32 ``[N,2]`` tensor: origins a tracker left on the device,
-    not read on the host -- the kernel clamps each so that the box stays inside the frame (``spk_frames_u8_to_f32_boxes``).
-    -> float32 [N,3,size,size]."""
-    if frames_u8.dim() == 3:
-        frames_u8 = frames_u8.unsqueeze(0)
-    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
-        raise ValueError(f"frames_from_u8: frames must be [N,H,W,3], got {tuple(frames_u8.shape)}")
-    Hout, Wout = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-    if Hout < 1 or Wout < 1:
-        raise ValueError(f"frames_from_u8: size must be >= 1, got {size}")
-    swap = _channel_swap(channel_order)
-    mean, std = _triple(mean, "mean"), _triple(std, "std")
-    if any(s == 0 for s in std):
-        raise ValueError("frames_from_u8: std must be non-zero")
-    boxes = None
-    if crop is not None:
-        origins, h, w = parse_boxes(crop, frames_u8.size(0), frames_u8.size(1), frames_u8.size(2), "frames_from_u8: crop")
-        if isinstance(origins, tuple):
-            y0, x0 = origins
-            frames_u8 = frames_u8[:, y0:y0 + h, x0:x0 + w]
-        else:
-            boxes = origins
-    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
-        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
-    N, Hin, Win, _ = frames_u8.shape
-    if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * Win or (N > 1 and frames_u8.stride(0) < 0):
-        frames_u8 = frames_u8.contiguous()
-    scale = [1.0 / (255.0 * s) for s in std]
-    shift = [-m / s for m, s in zip(mean, std)]
-    out = torch.empty((N, 3, Hout, Wout), device=frames_u8.device, dtype=torch.float32)
-    if boxes is not None:
-        if boxes.device != frames_u8.device:
-            if boxes.is_cuda:
-                raise L.SpkError(f"frames_from_u8: box origins on {boxes.device}, frames on {frames_u8.device}")
-            boxes = boxes.to(frames_u8.device)
-        fy, cy, wy, fx, cx, wx = _device_resize_tables(h, w, Hout, Wout, frames_u8.device)
-        L.check(L.lib().spk_frames_u8_to_f32_boxes(frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), N, Hin, Win,
-                                                   boxes.data_ptr(), h, w, swap, fy.data_ptr(), cy.data_ptr(), wy.data_ptr(), wy.size(1),
-                                                   fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), wx.size(1), out.data_ptr(), Hout, Wout,
-                                                   *scale, *shift, L.stream_ptr()), "spk_frames_u8_to_f32_boxes")
-        return out
-    fy, cy, wy, fx, cx, wx = _device_resize_tables(Hin, Win, Hout, Wout, frames_u8.device)
-    L.check(L.lib().spk_frames_u8_to_f32(frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), N, Hin, Win,
-                                         swap, fy.data_ptr(), cy.data_ptr(), wy.data_ptr(), wy.size(1), fx.data_ptr(), cx.data_ptr(),
-                                         wx.data_ptr(), wx.size(1), out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()),
-            "spk_frames_u8_to_f32")
-    return out
-
-
-def quant_range(value_range):
-    """``(lo, k)`` of ``q = rint(clamp((x - lo) * k, 0, 255))`` for frames in ``value_range = (lo, hi)``."""
-    lo, hi = float(value_range[0]), float(value_range[1])
-    if not hi > lo:
-        raise ValueError(f"value_range must be increasing, got {tuple(value_range)}")
-    return lo, 255.0 / (hi - lo)
-
-
-def frames_to_u8(x, *, value_range=(-1, 1), channel_order="rgb", out=None):
-    """Network frames -> uint8 HWC for a video writer, one launch (``spk_frames_f32_to_u8``): float32 [N,3,H,W] in
-    ``value_range`` (the decoder's (-1, 1), or (0, 1)) -> uint8 [N,H,W,3], ``channel_order="bgr"`` for ``cv2.VideoWriter``;
-    bit for bit ``((x - lo) * (255 / (hi - lo))).clamp(0, 255).round().to(torch.uint8)``, ties to even; NaN -> 0.  The
-    reference's ``save_video`` (inference.py:78-86) multiplies by 255 and casts without offset or clamp, which wraps around on a
-    frame in (-1, 1); that is deliberately not reproduced.  ``out``: a uint8 tensor [N,H,W,3] to write (contiguous, any byte
-    offset)."""
-    if x.dim() != 4 or x.size(1) != 3 or x.size(0) < 1:
-        raise ValueError(f"frames_to_u8: x must be [N,3,H,W], got {tuple(x.shape)}")
-    swap = _channel_swap(channel_order)
-    lo, k = quant_range(value_range)
-    N, _, H, W = x.shape
-    xp = L.dptr(x, "x")
-    if out is None:
-        out = torch.empty((N, H, W, 3), device=x.device, dtype=torch.uint8)
-    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous():
-        raise L.SpkError(f"out: expected a contiguous uint8 HIP tensor {(N, H, W, 3)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    L.check(L.lib().spk_frames_f32_to_u8(xp, out.data_ptr(), N, H, W, swap, lo, k, L.stream_ptr()), "spk_frames_f32_to_u8")
-    return out
-
-
-def frames_paste_u8(x, frames_u8, box, *, feather=0, value_range=(-1, 1), channel_order="rgb", out=None):
-    """Generated frames back into the video they were cropped from, one launch (``spk_frames_paste_u8``): float32 [N,3,Hs,Ws]
-    in ``value_range`` is resized to the box size ``h x w`` (antialiased bilinear: shrinking and enlarging), quantised as
-    ``frames_to_u8`` does and blended over the pixels of ``frames_u8`` (uint8 [N,H,W,3] on the device, pixels packed, any row /
-    frame stride) inside the box: ``rint(b + m (q - b))`` with ``m = a_y[y] a_x[x]`` of ``feather_tables`` (``feather=0``: the box
-    replaces the background).  ``box``: ``(y0, x0, h, w)``; a host sequence / CPU integer tensor ``[N,4]`` of one size, checked
-    on the host and uploaded once; or ``(boxes_yx, h, w)`` with a device int32 ``[N,2]`` tensor, not read on the host -- box
-    pixels that fall outside the frame are skipped.  ``channel_order="bgr"``: the frames are BGR, ``x`` is RGB.  ``out=None``:
-    the result is a clone of ``frames_u8``; ``out=frames_u8``: pasted in place through its strides; another ``out`` first
-    receives a copy of ``frames_u8``.  -> uint8 [N,H,W,3]."""
-    if x.dim() != 4 or x.size(1) != 3 or x.size(0) < 1:
-        raise ValueError(f"frames_paste_u8: x must be [N,3,H,W], got {tuple(x.shape)}")
-    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != x.size(0):
-        raise ValueError(f"frames_paste_u8: frames must be [{x.size(0)},H,W,3], got {tuple(frames_u8.shape)}")
-    swap = _channel_swap(channel_order)
-    lo, k = quant_range(value_range)
-    feather = float(feather)
-    if not (0.0 <= feather < float("inf")):
-        raise ValueError(f"frames_paste_u8: feather must be a finite number >= 0, got {feather}")
-    N, _, Hs, Ws = x.shape
-    H, W = frames_u8.size(1), frames_u8.size(2)
-    origins, h, w = parse_boxes(box, N, H, W, "frames_paste_u8: box", inside=False)
-    xp = L.dptr(x, "x")
-    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
-        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
-    copy = out is not None and out is not frames_u8 and out.data_ptr() != frames_u8.data_ptr()
-    if out is None:
-        out = frames_u8.clone(memory_format=torch.contiguous_format)
-    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames_u8.shape):
-        raise L.SpkError(f"out: expected a uint8 HIP tensor {tuple(frames_u8.shape)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if not _packed_pixels(out):
-        raise L.SpkError(f"out: pixels must be packed and rows / frames must not overlap, got strides {out.stride()}")
-    if isinstance(origins, tuple):
-        (y0, x0), boxes = origins, None
-    else:
-        y0 = x0 = 0
-        if origins.device != x.device:
-            if origins.is_cuda:
-                raise L.SpkError(f"frames_paste_u8: box origins on {origins.device}, frames on {x.device}")
-            origins = origins.to(x.device)
-        boxes = origins
-    if copy:
-        out.copy_(frames_u8)
-    fy, cy, wy, fx, cx, wx = _device_resize_tables(Hs, Ws, h, w, x.device)
-    ay, ax = _device_feather_tables(h, w, feather, x.device) if feather > 0 else (None, None)
-    L.check(L.lib().spk_frames_paste_u8(xp, N, Hs, Ws, out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), H, W, h, w, y0, x0,
-                                        None if boxes is None else boxes.data_ptr(), swap, fy.data_ptr(), cy.data_ptr(), wy.data_ptr(),
-                                        wy.size(1), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), wx.size(1),
-                                        None if ay is None else ay.data_ptr(), None if ax is None else ax.data_ptr(), lo, k,
-                                        L.stream_ptr()), "spk_frames_paste_u8")
-    return out
-
-
-# ---- the video-frame edge in NV12 form (csrc/frame_nv12.hip; the definitions are in include/spk.h) -----------------------------
-def _yuv_standard(standard, full_range):
-    if standard not in ("bt601", "bt709"):
-        raise ValueError(f"standard must be 'bt601' or 'bt709', got {standard!r}")
-    if not isinstance(full_range, (bool, int)) or full_range not in (0, 1):
-        raise ValueError(f"full_range must be a bool, got {full_range!r}")
-    return (601 if standard == "bt601" else 709), int(full_range)
-
-
-def yuv_coeffs(standard="bt601", full_range=False):
-    """The two 3 x 4 affine maps in byte units between R'G'B' 0..255 and the Y, U, V bytes (``spk_yuv_coeffs``, built in fp64 on the
-    host from the primaries): ``to_rgb`` rows R, G, B over ``(y, u, v, 1)``; ``from_rgb`` rows Y, U, V over ``(r, g, b, 1)``.
-    ``standard``: "bt601" | "bt709"; limited range (Y 16..235, C 16..240) unless ``full_range``.  -> two CPU float64 tensors [3,4]."""
-    std, full = _yuv_standard(standard, full_range)
-    to_rgb, from_rgb = (C.c_double * 12)(), (C.c_double * 12)()
-    L.check(L.lib().spk_yuv_coeffs(std, full, to_rgb, from_rgb), "spk_yuv_coeffs")
-    return torch.tensor(list(to_rgb), dtype=torch.float64).view(3, 4), torch.tensor(list(from_rgb), dtype=torch.float64).view(3, 4)
-
-
-def nv12_planes(nv12):
-    """The two planes of NV12 frames as views.  ``nv12``: one uint8 tensor ``[N, 3H/2, W]`` (or ``[3H/2, W]``), a decoder surface
-    with unit pixel stride and any row pitch whose rows ``H..`` are the UV plane; or a pair ``(y [N,H,W], uv [N,H/2,W/2,2])``
-    (planes that live apart).  ``H`` and ``W`` are even.  -> ``(y [N,H,W], uv [N,H/2,W/2,2])``, no copy."""
-    if isinstance(nv12, (tuple, list)):
-        if len(nv12) != 2 or not all(isinstance(t, torch.Tensor) for t in nv12):
-            raise ValueError("nv12: a pair must be (y [N,H,W], uv [N,H/2,W/2,2])")
-        y, uv = nv12
-        if y.dim() == 2 and uv.dim() == 3:
-            y, uv = y.unsqueeze(0), uv.unsqueeze(0)
-        if y.dim() != 3 or uv.dim() != 4 or y.size(0) < 1 or y.size(1) % 2 or y.size(2) % 2 or y.size(1) < 2 or y.size(2) < 2 or \
-                tuple(uv.shape) != (y.size(0), y.size(1) // 2, y.size(2) // 2, 2):
-            raise ValueError(f"nv12: planes must be y [N,H,W] and uv [N,H/2,W/2,2] with even H, W, got {tuple(y.shape)} and {tuple(uv.shape)}")
-        if y.dtype != torch.uint8 or uv.dtype != torch.uint8 or y.device != uv.device:
-            raise ValueError(f"nv12: planes must be uint8 tensors on one device, got {y.dtype} on {y.device} and {uv.dtype} on {uv.device}")
-        return y, uv
-    if not isinstance(nv12, torch.Tensor):
-        raise ValueError("nv12: expected a uint8 tensor [N,3H/2,W] or a pair of planes")
-    buf = nv12.unsqueeze(0) if nv12.dim() == 2 else nv12
-    if buf.dim() != 3 or buf.size(0) < 1 or buf.size(1) % 3 or buf.size(1) < 3 or buf.size(2) % 2 or buf.size(2) < 2:
-        raise ValueError(f"nv12: a surface must be [N,3H/2,W] with even H, W, got {tuple(nv12.shape)}")
-    if buf.dtype != torch.uint8:
-        raise ValueError(f"nv12: a surface must be uint8, got {buf.dtype}")
-    N, W = buf.size(0), buf.size(2)
-    H = buf.size(1) // 3 * 2
-    if buf.stride(2) != 1:
-        raise ValueError(f"nv12: a surface must have unit pixel stride, got strides {buf.stride()}")
-    return buf[:, :H], buf[:, H:].unflatten(2, (W // 2, 2))
-
-
-def _nv12_strides(y, uv, what, written):
-    """Byte strides of the two planes as the kernels take them, checked on the host."""
-    N, H, W = y.shape
-    if not y.is_cuda or y.dtype != torch.uint8 or not uv.is_cuda:
-        raise L.SpkError(f"{what}: expected uint8 HIP tensors, got {y.dtype} on {y.device} (no CPU path)")
-    if y.stride(2) != 1 or uv.stride(3) != 1 or uv.stride(2) != 2:
-        raise L.SpkError(f"{what}: the Y pixel stride must be 1 and a UV pair packed, got strides {y.stride()} and {uv.stride()}")
-    ys, us = (y.stride(0) if N > 1 else 0, y.stride(1)), (uv.stride(0) if N > 1 else 0, uv.stride(1))
-    if ys[1] < W or us[1] < W or uv.data_ptr() % 2 or us[0] % 2 or us[1] % 2:
-        raise L.SpkError(f"{what}: rows must hold W = {W} bytes and the UV plane be 2-byte aligned with even strides, "
-                         f"got strides {y.stride()} and {uv.stride()}")
-    if N > 1 and (ys[0] < 0 or us[0] < 0 or (written and (ys[0] < (H - 1) * ys[1] + W or us[0] < (H // 2 - 1) * us[1] + W))):
-        raise L.SpkError(f"{what}: frames must not overlap, got strides {y.stride()} and {uv.stride()}")
-    return ys, us
-
-
-def frames_from_nv12(nv12, size, *, crop=None, channel_order="rgb", mean=0.5, std=0.5, standard="bt601", full_range=False):
-    """NV12 video frames -> the network's input, one launch (``spk_frames_nv12_to_f32``): crop, antialiased bilinear resize of the
-    Y, U and V fields to ``size`` x ``size`` (a number, or ``(H, W)``), YUV -> RGB (``yuv_coeffs``), clamp to 0..255 and
-    ``(x / 255 - mean) / std`` per channel, CHW.  ``nv12``: what ``nv12_planes`` takes, on the device, read in place through its
-    strides.  ``crop``: the three forms of ``parse_boxes``; an origin may be odd (chroma is sited by replication: pixel ``(Y, X)``
-    has sample ``(Y >> 1, X >> 1)``); device origins are clamped by the kernel so that the box stays inside the frame.
-    ``channel_order`` only says which plane order the network input has ("bgr": planes B, G, R).  -> float32 [N,3,size,size]."""
-    y, uv = nv12_planes(nv12)
-    N, H, W = y.shape
-    Hout, Wout = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
-    if Hout < 1 or Wout < 1:
-        raise ValueError(f"frames_from_nv12: size must be >= 1, got {size}")
-    swap = _channel_swap(channel_order)
-    code, full = _yuv_standard(standard, full_range)
-    mean, std = _triple(mean, "mean"), _triple(std, "std")
-    if any(s == 0 for s in std):
-        raise ValueError("frames_from_nv12: std must be non-zero")
-    origins, h, w = parse_boxes((0, 0, H, W) if crop is None else crop, N, H, W, "frames_from_nv12: crop")
-    ys, us = _nv12_strides(y, uv, "frames_from_nv12", written=False)
-    if isinstance(origins, tuple):
-        (y0, x0), boxes = origins, None
-    else:
-        y0 = x0 = 0
-        if origins.device != y.device:
-            if origins.is_cuda:
-                raise L.SpkError(f"frames_from_nv12: box origins on {origins.device}, frames on {y.device}")
-            origins = origins.to(y.device)
-        boxes = origins
-    scale = [1.0 / (255.0 * s) for s in std]
-    shift = [-m / s for m, s in zip(mean, std)]
-    out = torch.empty((N, 3, Hout, Wout), device=y.device, dtype=torch.float32)
-    fy, cy, wy, fx, cx, wx = _device_resize_tables(h, w, Hout, Wout, y.device)
-    L.check(L.lib().spk_frames_nv12_to_f32(y.data_ptr(), ys[0], ys[1], uv.data_ptr(), us[0], us[1], N, H, W,
-                                           None if boxes is None else boxes.data_ptr(), y0, x0, h, w, swap, code, full, fy.data_ptr(),
-                                           cy.data_ptr(), wy.data_ptr(), wy.size(1), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), wx.size(1),
-                                           out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()), "spk_frames_nv12_to_f32")
-    return out
-
-
-def _nv12_out(out, N, H, W, device, what):
-    """The surface a launcher writes: ``out`` (what ``nv12_planes`` takes) or a fresh packed ``[N, 3H/2, W]`` buffer.
-    -> ``(result, y, uv)``."""
-    if out is None:
-        out = torch.empty((N, 3 * H // 2, W), device=device, dtype=torch.uint8)
-    y, uv = nv12_planes(out)
-    if tuple(y.shape) != (N, H, W):
-        raise L.SpkError(f"{what}: out must hold {N} NV12 frames of {H} x {W}, got planes {tuple(y.shape)}")
-    return out, y, uv
-
-
-def frames_to_nv12(x, *, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
-    """Network frames -> NV12 for a hardware encoder, one launch (``spk_frames_f32_to_nv12``): float32 [N,3,H,W] (R, G, B planes,
-    ``H`` and ``W`` even) in ``value_range`` is quantised as ``frames_to_u8`` does without its rounding, converted with
-    ``from_rgb`` of ``yuv_coeffs`` in fp64, and stored as ``Y = rint(clamp(e_y))`` per pixel and ``C = rint(clamp(mean of the four
-    e_c))`` per 2 x 2 block.  ``out``: what ``nv12_planes`` takes (any row pitch).  -> uint8 [N, 3H/2, W], or ``out``."""
-    if x.dim() != 4 or x.size(1) != 3 or x.size(0) < 1:
-        raise ValueError(f"frames_to_nv12: x must be [N,3,H,W], got {tuple(x.shape)}")
-    N, _, H, W = x.shape
-    if H % 2 or W % 2 or H < 2 or W < 2:
-        raise ValueError(f"frames_to_nv12: NV12 frames have an even height and width, got {H} x {W}")
-    lo, k = quant_range(value_range)
-    code, full = _yuv_standard(standard, full_range)
-    xp = L.dptr(x, "x")
-    out, y, uv = _nv12_out(out, N, H, W, x.device, "frames_to_nv12")
-    ys, us = _nv12_strides(y, uv, "frames_to_nv12: out", written=True)
-    L.check(L.lib().spk_frames_f32_to_nv12(xp, N, H, W, y.data_ptr(), ys[0], ys[1], uv.data_ptr(), us[0], us[1], code, full, lo, k,
-                                           L.stream_ptr()), "spk_frames_f32_to_nv12")
-    return out
-
-
-def frames_paste_nv12(x, nv12, box, *, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
-    """Generated frames back into the NV12 video they were cropped from, one launch (``spk_frames_paste_nv12``): float32
-    [N,3,Hs,Ws] in ``value_range`` is resized to the box size ``h x w``, quantised, converted to YUV and blended over the box with
-    weight ``m = a_y[y] a_x[x]`` of ``feather_tables``: luma per pixel, chroma per 2 x 2 block as the quarter-weighted sum of the
-    block's box pixels over the sample underneath (include/spk.h has the arithmetic).  ``box``: the three forms of
-    ``parse_boxes``; origins may be odd; box pixels outside the frame are skipped.  ``out=None``: the result is a packed clone of
-    ``nv12``; ``out=nv12`` (the same tensor, or the same pair of planes): pasted in place through its strides; another ``out``
-    first receives a copy.  -> uint8 [N, 3H/2, W], or ``out``."""
-    if x.dim() != 4 or x.size(1) != 3 or x.size(0) < 1:
-        raise ValueError(f"frames_paste_nv12: x must be [N,3,H,W], got {tuple(x.shape)}")
-    sy, suv = nv12_planes(nv12)
-    N, _, Hs, Ws = x.shape
-    if sy.size(0) != N:
-        raise ValueError(f"frames_paste_nv12: {N} generated frames, {sy.size(0)} NV12 frames")
-    H, W = sy.shape[1:]
-    lo, k = quant_range(value_range)
-    code, full = _yuv_standard(standard, full_range)
-    feather = float(feather)
-    if not (0.0 <= feather < float("inf")):
-        raise ValueError(f"frames_paste_nv12: feather must be a finite number >= 0, got {feather}")
-    origins, h, w = parse_boxes(box, N, H, W, "frames_paste_nv12: box", inside=False)
-    xp = L.dptr(x, "x")
-    if not sy.is_cuda:
-        raise L.SpkError(f"frames: expected uint8 HIP tensors, got {sy.dtype} on {sy.device} (no CPU path)")
-    out, y, uv = _nv12_out(out, N, H, W, x.device, "frames_paste_nv12")
-    ys, us = _nv12_strides(y, uv, "frames_paste_nv12: out", written=True)
-    if isinstance(origins, tuple):
-        (y0, x0), boxes = origins, None
-    else:
-        y0 = x0 = 0
-        if origins.device != x.device:
-            if origins.is_cuda:
-                raise L.SpkError(f"frames_paste_nv12: box origins on {origins.device}, frames on {x.device}")
-            origins = origins.to(x.device)
-        boxes = origins
-    if y.data_ptr() != sy.data_ptr() or y.stride() != sy.stride():
-        y.copy_(sy)
-    if uv.data_ptr() != suv.data_ptr() or uv.stride() != suv.stride():
-        uv.copy_(suv)
-    fy, cy, wy, fx, cx, wx = _device_resize_tables(Hs, Ws, h, w, x.device)
-    ay, ax = _device_feather_tables(h, w, feather, x.device) if feather > 0 else (None, None)
-    L.check(L.lib().spk_frames_paste_nv12(xp, N, Hs, Ws, y.data_ptr(), ys[0], ys[1], uv.data_ptr(), us[0], us[1], H, W, h, w, y0, x0,
-                                          None if boxes is None else boxes.data_ptr(), code, full, fy.data_ptr(), cy.data_ptr(),
-                                          wy.data_ptr(), wy.size(1), fx.data_ptr(), cx.data_ptr(), wx.data_ptr(), wx.size(1),
-                                          None if ay is None else ay.data_ptr(), None if ax is None else ax.data_ptr(), lo, k,
-                                          L.stream_ptr()), "spk_frames_paste_nv12")
     return out
 
 

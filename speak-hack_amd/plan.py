@@ -23,6 +23,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import frames as FR
 from . import ops
 
 LRELU = 0.2
@@ -288,7 +289,7 @@ class DecoderPlan(LaunchPlan):
             else:
                 self.torgb.y = self.rgb_buf.data_ptr()
         if output == "nv12":
-            code, full = ops._yuv_standard(standard, full_range)
+            code, full = FR.yuv_standard(standard, full_range)
             Ho, Wo = x.shape[2], x.shape[3]
             if swap_rb:
                 raise ValueError("DecoderPlan: swap_rb applies to uint8 output only")

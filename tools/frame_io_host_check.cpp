@@ -7,22 +7,10 @@
 //   tools/_bin/frame_io_host_check
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "../speak-hack_amd/csrc/spk_common.hpp"
-
-// the library defines this next to its other kernels (csrc/pointwise.hip); the check links csrc/frame_io.hip alone
-extern "C" const char* spk_last_error(void) { return spk::err_buf(); }
-
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED line %d: %s (%s)\n", __LINE__, #cond, spk_last_error()); \
-            return 1;                                                      \
-        }                                                                  \
-    } while (0)
+#include "host_check.hpp"
 
 int main() {
     const int sizes[][2] = {{37, 16}, {53, 16}, {135, 32}, {240, 32}, {20, 32}, {28, 32}, {32, 32}, {2, 1}, {1, 4}, {1, 1},

@@ -7,21 +7,9 @@
 //         speak-hack_amd/csrc/noise.hip tools/noise_host_check.cpp -o tools/_bin/noise_host_check
 //   tools/_bin/noise_host_check
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 
-#include "../speak-hack_amd/csrc/spk_common.hpp"
-
-// the library defines this next to its other kernels (csrc/pointwise.hip); the check links csrc/noise.hip alone
-extern "C" const char* spk_last_error(void) { return spk::err_buf(); }
-
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED line %d: %s (%s)\n", __LINE__, #cond, spk_last_error()); \
-            return 1;                                                      \
-        }                                                                  \
-    } while (0)
+#include "host_check.hpp"
 
 int main() {
     // (ctr; key) -> output.  ctr = (q, frame lo, layer, frame hi), key = (seed lo, seed hi): the host routine maps its arguments

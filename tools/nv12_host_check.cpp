@@ -9,22 +9,10 @@
 //   tools/_bin/nv12_host_check
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "../speak-hack_amd/csrc/spk_common.hpp"
-
-// the library defines this next to its other kernels (csrc/pointwise.hip); the check links csrc/frame_nv12.hip alone
-extern "C" const char* spk_last_error(void) { return spk::err_buf(); }
-
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED line %d: %s (%s)\n", __LINE__, #cond, spk_last_error()); \
-            return 1;                                                      \
-        }                                                                  \
-    } while (0)
+#include "host_check.hpp"
 
 static bool near(double a, double b, double tol) { return std::fabs(a - b) <= tol; }
 

@@ -9,22 +9,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
-#include "../speak-hack_amd/csrc/spk_common.hpp"
-
-// the library defines this next to its other kernels (csrc/pointwise.hip); the check links csrc/frame_io.hip alone
-extern "C" const char* spk_last_error(void) { return spk::err_buf(); }
-
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED line %d: %s (%s)\n", __LINE__, #cond, spk_last_error()); \
-            return 1;                                                      \
-        }                                                                  \
-    } while (0)
+#include "host_check.hpp"
 
 int main() {
     const int sizes[] = {1, 2, 3, 9, 11, 20, 24, 32, 37, 53, 256, 264, 400, 1080, 1920};

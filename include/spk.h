@@ -310,6 +310,37 @@ typedef struct spk_wgrad_desc {
 } spk_wgrad_desc;
 int64_t spk_conv2d_wgrad_workspace_bytes(int kh, int kw, int stride, int splits, int B, int Cin, int Cout, int H, int W);
 int spk_conv2d_wgrad(const spk_wgrad_desc* desc, void* stream);
+/* The form spk_conv2d_wgrad(desc) would take, answered by the launch path's own statements on the host: nothing is launched and
+ * no device is touched (pointers are read for their ALIGNMENT only; workspace / workspace_bytes must be set, any size that passes
+ * the launcher's check).  A descriptor spk_conv2d_wgrad refuses is refused here with the same error.
+ *   kernel: SPK_WGRAD_* below.  TAP / TAP_FIXED: wgrad_kernel<kh, kw, stride> with runtime / fixed 16x4x1 geometry.
+ *   mode: 0 plain (UP: bilinear x2), 1 affine + ReLU, 2 batch scale (UP: upfirdn2d [1,3,3,1])
+ *   TW, TH, TB: the pixel tile (0 for the GEMM forms of a 1x1); MT, NT: MFMA tiles per wave of the 1x1 GEMM forms (else 0)
+ *   n_tiles: pixel tiles (GEMM forms: 32-pixel k-tiles; WINO: 16x2 chunks); splits: workgroups along the pixel axis;
+ *   tiles_per_split: the most tiles one of them walks; n_slabs: the slabs the reducer sums
+ *   slab_floats: floats of one slab; workspace_bytes: what the launcher's workspace check asks for
+ *   reducer: 0 dword, 1 vec, 2 deep (wgrad_reduce_kernel / _vec_ / _deep_), with the fold and taps it is given */
+#define SPK_WGRAD_TAP 0
+#define SPK_WGRAD_TAP_FIXED 1
+#define SPK_WGRAD_PIPE 2
+#define SPK_WGRAD_WIDE16 3
+#define SPK_WGRAD_WIDE8 4
+#define SPK_WGRAD_S2_16 5
+#define SPK_WGRAD_S2_8 6
+#define SPK_WGRAD_UP 7
+#define SPK_WGRAD_GEMM1X1 8
+#define SPK_WGRAD_GEMM1X1_DMA 9
+#define SPK_WGRAD_STEM 10
+#define SPK_WGRAD_WINO 11
+typedef struct spk_wgrad_form {
+    int32_t kernel, mode, TW, TH, TB, MT, NT;
+    int32_t n_tiles, splits, tiles_per_split, n_slabs;
+    int32_t grid_x, grid_y, grid_z;
+    int32_t reducer, fold, taps;
+    int32_t reserved;
+    int64_t lds_bytes, slab_floats, workspace_bytes;
+} spk_wgrad_form;
+int spk_conv2d_wgrad_launch_form(const spk_wgrad_desc* desc, spk_wgrad_form* out);
 /* whether spk_conv2d_wgrad takes SPK_CONV_UPSAMPLE2X for a 3x3 stride-1 problem with OUTPUT size H x W (x is then the
  * low-resolution [B,Cin,H/2,W/2] tensor and the x2 image is never materialised); 0: upsample first. */
 int spk_conv2d_wgrad_up_supported(int B, int Cin, int Cout, int H, int W);
@@ -330,6 +361,9 @@ int spk_conv2d_wgrad_wino(const spk_wgrad_desc* desc, void* stream);
  * co and co + Cout/fold add (see spk_wgrad_desc.fold) */
 int spk_wgrad_reduce_slabs(const float* slabs, float* dw, int n_slabs, int Cout, int Cin, int taps, float scale, int accumulate, int fold,
                            void* stream);
+/* which reducer spk_wgrad_reduce_slabs would run for these arguments (reducer / fold / taps / n_slabs of *out; the rest 0): the
+ * launcher's own choice, nothing is launched, the pointers are read for their alignment only */
+int spk_wgrad_reduce_form(const float* slabs, float* dw, int n_slabs, int Cout, int Cin, int taps, int fold, spk_wgrad_form* out);
 
 /* Adjoint of the fused epilogue of spk_conv2d_fwd, one pass.  With y = a*(s0+1)+s1, a = lrelu(t),
  * t = conv + bias + noise_w*noise and dy = dL/dy:

@@ -45,6 +45,17 @@ class Conv2dForm(C.Structure):
                                          "finisher", "finisher_seg")] + [("lds_bytes", C.c_int64)]
 
 
+class WgradForm(C.Structure):
+    """Mirror of spk_wgrad_form (include/spk.h): what ``spk_conv2d_wgrad_launch_form`` answers."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "mode", "TW", "TH", "TB", "MT", "NT", "n_tiles", "splits", "tiles_per_split", "n_slabs",
+                                         "grid_x", "grid_y", "grid_z", "reducer", "fold", "taps", "reserved")] + \
+               [(n, C.c_int64) for n in ("lds_bytes", "slab_floats", "workspace_bytes")]
+
+
+WGRAD_KERNELS = ("tap", "tap_fixed", "pipe", "wide16", "wide8", "s2_16", "s2_8", "up", "gemm1x1", "gemm1x1_dma", "stem", "wino")   # SPK_WGRAD_*
+WGRAD_MODES = ("plain", "affine", "bscale")
+WGRAD_REDUCERS = ("dword", "vec", "deep")
+
 CONV_IN_BATCH_SCALE = 256
 CONV_UP_FIR1331 = 512
 CONV_DGRAD_S2 = 1024
@@ -227,6 +238,8 @@ _PROTOTYPES = {
     "spk_maxpool3x3s2_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "spk_conv2d_wgrad_workspace_bytes": (C.c_int64, [C.c_int] * 9),
     "spk_conv2d_wgrad": (C.c_int, [C.POINTER(WgradDesc), C.c_void_p]),
+    "spk_conv2d_wgrad_launch_form": (C.c_int, [C.POINTER(WgradDesc), C.POINTER(WgradForm)]),
+    "spk_wgrad_reduce_form": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WgradForm)]),
     "spk_conv2d_wgrad_up_supported": (C.c_int, [C.c_int] * 5),
     "spk_conv2d_wgrad_mod_supported": (C.c_int, [C.c_int] * 6),
     "spk_conv2d_wgrad_wino_supported": (C.c_int, [C.c_int] * 5),

@@ -26,6 +26,7 @@
 // Epilogue: dg = G^T dU G per (co, ci) in registers, stored into the split's slab [co][tap][ci] -- the layout of the direct weight
 // gradient's slabs, so the SAME fixed-order reduce (spk_wgrad_reduce_slabs) finishes: bitwise reproducible, no float atomics.
 #include "conv_mfma_f32.hpp"
+#include "wgrad_form.hpp"
 
 #include <cstdlib>
 
@@ -465,21 +466,26 @@ int spk_conv2d_wgrad_wino(const spk_wgrad_desc* d, void* stream) {
     a.n_chunks = d->B * a.TY * a.TXB;
     a.chunks_per_wg = per_wg;
     a.x_bytes = (unsigned)((long long)d->B * Cx * d->H * d->W * 4 + ((long long)d->W + 4) * 4);
-    static bool raised = false;
-    if (!raised) {
-        for (const void* f : {reinterpret_cast<const void*>(&wgrad_wino_kernel<PLAIN>), reinterpret_cast<const void*>(&wgrad_wino_kernel<MODULATED>),
-                              reinterpret_cast<const void*>(&wgrad_wino_kernel<AFFINE_RELU>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        }
-        raised = true;
-    }
     dim3 grid((unsigned)splits, (unsigned)(Cy / CO_T), (unsigned)(d->Cin / CI_T));
-    if (mod) hipLaunchKernelGGL(wgrad_wino_kernel<MODULATED>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
-    else if (aff) hipLaunchKernelGGL(wgrad_wino_kernel<AFFINE_RELU>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(wgrad_wino_kernel<PLAIN>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
-    int rc = spk::check_launch("wgrad_wino_kernel");
-    if (rc != SPK_OK) return rc;
+    if (spkwg::form_probe) {        // spk_conv2d_wgrad_launch_form: answer instead of launching
+        spkwg::report_form(SPK_WGRAD_WINO, mod ? 2 : (aff ? 1 : 0), 16, 2, 1, 0, 0, a.n_chunks, splits, per_wg, grid, LDS_BYTES,
+                           (size_t)Cy * 9 * d->Cin, (size_t)splits);
+    } else {
+        static bool raised = false;
+        if (!raised) {
+            for (const void* f : {reinterpret_cast<const void*>(&wgrad_wino_kernel<PLAIN>), reinterpret_cast<const void*>(&wgrad_wino_kernel<MODULATED>),
+                                  reinterpret_cast<const void*>(&wgrad_wino_kernel<AFFINE_RELU>)}) {
+                hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
+            }
+            raised = true;
+        }
+        if (mod) hipLaunchKernelGGL(wgrad_wino_kernel<MODULATED>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
+        else if (aff) hipLaunchKernelGGL(wgrad_wino_kernel<AFFINE_RELU>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(wgrad_wino_kernel<PLAIN>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
+        int rc = spk::check_launch("wgrad_wino_kernel");
+        if (rc != SPK_OK) return rc;
+    }
     return spk_wgrad_reduce_slabs(static_cast<const float*>(d->workspace), d->dw, splits, Cy, d->Cin, 9, d->scale, d->accumulate, fold, stream);
 }
 

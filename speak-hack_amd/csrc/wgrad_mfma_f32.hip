@@ -14,6 +14,7 @@
 // replaces: the weight-gradient half of F.conv2d's backward for every conv on the path
 // (styleganv1.py:625,630 conv1/conv2; the torchvision trunk convs of model.py:60-62).
 #include "spk_common.hpp"
+#include "wgrad_form.hpp"
 #ifndef WGRAD_CI32
 #define WGRAD_CI32 0
 #endif
@@ -36,12 +37,15 @@ __device__ __forceinline__ void wg_static_for(F&& f) {
     }
 }
 
+thread_local spk_wgrad_form* spkwg::form_probe = nullptr;
+
 namespace {
 
 // WG_BATCH_SCALE: the modulated convolution (StyleGAN2 variant): the forward input was x * s[b,ci] and the gradient reaching
 // the conv output is g * d'[b,co] (demodulation x activation gain) -- both factors are applied while the tiles are staged, so
 // neither rescaled tensor exists in HBM (in_scale = s [B][Cx], g_scale = d' [B][Cy])
 enum { WG_PLAIN = 0, WG_UPSAMPLE = 1, WG_AFFINE_RELU = 2, WG_BATCH_SCALE = 3 };
+constexpr int form_mode(int mode) { return mode == WG_AFFINE_RELU ? 1 : (mode == WG_BATCH_SCALE ? 2 : 0); }      // spk_wgrad_form.mode
 
 struct WgradArgs {
     const float* g;        // [B,Cout,H,W]   output-side gradient
@@ -1304,7 +1308,13 @@ inline int launch_wgrad_reduce(hipStream_t stream, const float* slabs, float* dw
                                float scale, int accumulate, int fold) {
     const size_t slab_floats = (size_t)Cout_all * Cin * taps;
     const bool vec = Cin % 4 == 0 && (reinterpret_cast<uintptr_t>(slabs) & 15) == 0 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0;
-    if (vec && n_slabs >= 32 && slab_floats / fold / 4 / 256 < 512) {
+    const bool deep = vec && n_slabs >= 32 && slab_floats / fold / 4 / 256 < 512;
+    if (spkwg::form_probe) {
+        spk_wgrad_form& f = *spkwg::form_probe;
+        f.reducer = deep ? 2 : (vec ? 1 : 0); f.fold = fold; f.taps = taps; f.n_slabs = n_slabs;
+        return SPK_OK;
+    }
+    if (deep) {
         const unsigned blocks = (unsigned)std::min<size_t>((slab_floats / fold / 4 + RD_EL - 1) / RD_EL, 4096);
         hipLaunchKernelGGL(wgrad_reduce_deep_kernel, dim3(std::max(blocks, 1u)), dim3(256), 0, stream, slabs, dw, n_slabs, Cout_all, Cin,
                            taps, scale, accumulate, fold);
@@ -1414,16 +1424,22 @@ int run_wgrad_wide(const spk_wgrad_desc* d, hipStream_t stream) {
     if constexpr (HAS_SB) {
         if (sb) kern = &wgrad3x3_wide_kernel<TW, MODE, true>;
     }
-    static bool raised[2] = {false, false};
-    if (!raised[sb]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised[sb] = true;
-    }
     dim3 grid((unsigned)spk::ceil_div(G * d->Cout, SH::CO_T), (unsigned)spk::ceil_div(d->Cin, SH::CI_T), (unsigned)g.splits);
-    hipLaunchKernelGGL(kern, grid, dim3(256), (sb ? 1 : 2) * SH::BUF * sizeof(float), stream, a);
-    int rc = spk::check_launch("wgrad3x3_wide_kernel");
-    if (rc != SPK_OK) return rc;
+    const size_t lds_bytes = (sb ? 1 : 2) * SH::BUF * sizeof(float);
+    if (spkwg::form_probe) {
+        spkwg::report_form(TW == 16 ? SPK_WGRAD_WIDE16 : SPK_WGRAD_WIDE8, form_mode(MODE), TW, 64 / TW, 1, 0, 0, g.n_tiles, g.splits,
+                           spk::ceil_div(g.n_tiles, g.splits), grid, lds_bytes, slab_floats, g.n_slabs);
+    } else {
+        static bool raised[2] = {false, false};
+        if (!raised[sb]) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
+            raised[sb] = true;
+        }
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds_bytes, stream, a);
+        int rc = spk::check_launch("wgrad3x3_wide_kernel");
+        if (rc != SPK_OK) return rc;
+    }
     return launch_wgrad_reduce(stream, a.slabs, d->dw, g.n_slabs, G * d->Cout, d->Cin, 9, d->scale, d->accumulate ? 1 : 0,
                                d->fold > 1 ? d->fold : 1);
 }
@@ -1454,16 +1470,22 @@ int run_wgrad_up(const spk_wgrad_desc* d, hipStream_t stream) {
     a.Cy = G * d->Cout;
     a.lgTW = 4; a.lgTH = 2; a.lgTB = 0;
     a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.n_tiles = g.n_tiles;
-    static bool raised = false;
-    if (!raised) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_up_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised = true;
-    }
     dim3 grid((unsigned)spk::ceil_div(G * d->Cout, SH::CO_T), (unsigned)spk::ceil_div(d->Cin, SH::CI_T), (unsigned)g.splits);
-    hipLaunchKernelGGL(wgrad3x3_up_kernel<MODE>, grid, dim3(256), (2 * SH::BUF + 2 * US_FLOATS) * sizeof(float), stream, a);
-    int rc = spk::check_launch("wgrad3x3_up_kernel");
-    if (rc != SPK_OK) return rc;
+    const size_t lds_bytes = (2 * SH::BUF + 2 * US_FLOATS) * sizeof(float);
+    if (spkwg::form_probe) {
+        spkwg::report_form(SPK_WGRAD_UP, form_mode(MODE), 16, 4, 1, 0, 0, g.n_tiles, g.splits, spk::ceil_div(g.n_tiles, g.splits), grid,
+                           lds_bytes, slab_floats, g.n_slabs);
+    } else {
+        static bool raised = false;
+        if (!raised) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_up_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
+            raised = true;
+        }
+        hipLaunchKernelGGL(wgrad3x3_up_kernel<MODE>, grid, dim3(256), lds_bytes, stream, a);
+        int rc = spk::check_launch("wgrad3x3_up_kernel");
+        if (rc != SPK_OK) return rc;
+    }
     return launch_wgrad_reduce(stream, a.slabs, d->dw, g.n_slabs, G * d->Cout, d->Cin, 9, d->scale, d->accumulate ? 1 : 0,
                                d->fold > 1 ? d->fold : 1);
 }
@@ -1507,28 +1529,33 @@ int run_wgrad_s2(const spk_wgrad_desc* d, hipStream_t stream) {
     a.Cy = G * d->Cout;
     a.lgTW = spk::ilog2(TW); a.lgTH = spk::ilog2(64 / TW); a.lgTB = 0;
     a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.n_tiles = g.n_tiles;
-    auto kern = &wgrad3x3_s2_kernel<TW, MODE>;
-#ifdef SPK_WGRAD_S2_LAB
-    if constexpr (TW == 16 && MODE == WG_PLAIN) {
-        const char* e = getenv("SPK_WG_LAB");
-        switch (e ? atoi(e) : 0) {
-            case 16: kern = &wgrad3x3_s2_kernel<TW, MODE, 16>; break;
-            case 32: kern = &wgrad3x3_s2_kernel<TW, MODE, 32>; break;
-            default: break;
-        }
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
-    static bool raised = false;
-    if (!raised) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised = true;
-    }
     dim3 grid((unsigned)spk::ceil_div(G * d->Cout, SH::CO_T), (unsigned)spk::ceil_div(d->Cin, SH::CI_T), (unsigned)g.splits);
-    hipLaunchKernelGGL(kern, grid, dim3(256), 2 * SH::BUF * sizeof(float), stream, a);
-    int rc = spk::check_launch("wgrad3x3_s2_kernel");
-    if (rc != SPK_OK) return rc;
+    if (spkwg::form_probe) {
+        spkwg::report_form(TW == 16 ? SPK_WGRAD_S2_16 : SPK_WGRAD_S2_8, form_mode(MODE), TW, 64 / TW, 1, 0, 0, g.n_tiles, g.splits,
+                           spk::ceil_div(g.n_tiles, g.splits), grid, 2 * SH::BUF * sizeof(float), slab_floats, g.n_slabs);
+    } else {
+        auto kern = &wgrad3x3_s2_kernel<TW, MODE>;
+#ifdef SPK_WGRAD_S2_LAB
+        if constexpr (TW == 16 && MODE == WG_PLAIN) {
+            const char* e = getenv("SPK_WG_LAB");
+            switch (e ? atoi(e) : 0) {
+                case 16: kern = &wgrad3x3_s2_kernel<TW, MODE, 16>; break;
+                case 32: kern = &wgrad3x3_s2_kernel<TW, MODE, 32>; break;
+                default: break;
+            }
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        }
+#endif
+        static bool raised = false;
+        if (!raised) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
+            raised = true;
+        }
+        hipLaunchKernelGGL(kern, grid, dim3(256), 2 * SH::BUF * sizeof(float), stream, a);
+        int rc = spk::check_launch("wgrad3x3_s2_kernel");
+        if (rc != SPK_OK) return rc;
+    }
     return launch_wgrad_reduce(stream, a.slabs, d->dw, g.n_slabs, G * d->Cout, d->Cin, 9, d->scale, d->accumulate ? 1 : 0,
                                d->fold > 1 ? d->fold : 1);
 }
@@ -1571,34 +1598,45 @@ int run_wgrad(const spk_wgrad_desc* d, hipStream_t stream) {
     const bool fixed = HAS_FIXED && allow_fixed && g.TW == 16 && g.TH == 4 && g.TB == 1;
     // plain 3x3 stride-1 layers on that tile shape: the form whose staging is interleaved with the MFMAs
     static const bool allow_pipe = [] { const char* e = getenv("SPK_WGRAD_PIPE"); return !e || atoi(e) != 0; }();
+    const int tiles_per_split = spk::ceil_div(g.n_tiles, g.splits);
     if (KH == 3 && S == 1 && MODE == WG_PLAIN && allow_pipe && g.TW == 16 && g.TH == 4 && g.TB == 1) {
-        static bool pipe_raised = false;
-        if (!pipe_raised) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-            pipe_raised = true;
-        }
         dim3 pgrid((unsigned)spk::ceil_div(G * d->Cout, SH::CO_T), (unsigned)spk::ceil_div(d->Cin, SH::CI_T), (unsigned)g.splits);
-        hipLaunchKernelGGL(wgrad3x3_pipe_kernel, pgrid, dim3(256), 2 * WP_BUF * sizeof(float), stream, a);
-        int prc = spk::check_launch("wgrad3x3_pipe_kernel");
-        if (prc != SPK_OK) return prc;
+        if (spkwg::form_probe) {
+            spkwg::report_form(SPK_WGRAD_PIPE, form_mode(MODE), g.TW, g.TH, g.TB, 0, 0, g.n_tiles, g.splits, tiles_per_split, pgrid,
+                               2 * WP_BUF * sizeof(float), slab_floats, g.n_slabs);
+        } else {
+            static bool pipe_raised = false;
+            if (!pipe_raised) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
+                pipe_raised = true;
+            }
+            hipLaunchKernelGGL(wgrad3x3_pipe_kernel, pgrid, dim3(256), 2 * WP_BUF * sizeof(float), stream, a);
+            int prc = spk::check_launch("wgrad3x3_pipe_kernel");
+            if (prc != SPK_OK) return prc;
+        }
         return launch_wgrad_reduce(stream, a.slabs, d->dw, g.n_slabs, G * d->Cout, d->Cin, SH::TAPS, d->scale, d->accumulate ? 1 : 0,
                                    d->fold > 1 ? d->fold : 1);
     }
     auto kern = fixed ? &wgrad_kernel<KH, KW, S, MODE, HAS_FIXED ? 1 : 0> : &wgrad_kernel<KH, KW, S, MODE, 0>;
-    if (g.lds_bytes > 64 * 1024) {
-        static bool raised = false;
-        if (!raised) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-            raised = true;
-        }
-    }
     dim3 grid((unsigned)spk::ceil_div(G * d->Cout, SH::CO_T),
               (unsigned)(spk::ceil_div(d->Cin, SH::CI_T) * (SH::ROWPASS ? KH : 1)), (unsigned)g.splits);
-    hipLaunchKernelGGL(kern, grid, dim3(256), g.lds_bytes, stream, a);
-    int rc = spk::check_launch("wgrad_kernel");
-    if (rc != SPK_OK) return rc;
+    if (spkwg::form_probe) {
+        spkwg::report_form(fixed ? SPK_WGRAD_TAP_FIXED : SPK_WGRAD_TAP, form_mode(MODE), g.TW, g.TH, g.TB, 0, 0, g.n_tiles, g.splits,
+                           tiles_per_split, grid, g.lds_bytes, slab_floats, g.n_slabs);
+    } else {
+        if (g.lds_bytes > 64 * 1024) {
+            static bool raised = false;
+            if (!raised) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
+                raised = true;
+            }
+        }
+        hipLaunchKernelGGL(kern, grid, dim3(256), g.lds_bytes, stream, a);
+        int rc = spk::check_launch("wgrad_kernel");
+        if (rc != SPK_OK) return rc;
+    }
     return launch_wgrad_reduce(stream, a.slabs, d->dw, g.n_slabs, G * d->Cout, d->Cin, SH::TAPS, d->scale, d->accumulate ? 1 : 0,
                                d->fold > 1 ? d->fold : 1);
 }
@@ -1972,20 +2010,25 @@ int run_wgrad1x1_shape(const spk_wgrad_desc* d, hipStream_t stream) {
             dma = true;
         }
     }
-    static bool raised[2] = {false, false};
-    if (!raised[dma]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised[dma] = true;
-    }
     SPK_REQUIRE((long long)a.Cy * d->H * d->W < (1ll << 31) && (long long)a.Cx * d->Hin * d->Win < (1ll << 31),
                 "wgrad 1x1 GEMM form: an image's planes are addressed with 32-bit offsets");
     // a co block must not straddle two groups
     SPK_REQUIRE(G == 1 || d->Cout % BM == 0, "wgrad 1x1 GEMM form: grouped launches need Cout %% %d == 0 (use the tap kernel)", BM);
     dim3 grid((unsigned)spk::ceil_div(G * d->Cout, BM), (unsigned)spk::ceil_div(d->Cin, BN), (unsigned)g.splits);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a, g.tiles_per_split);
-    int rc = spk::check_launch("wgrad1x1_kernel");
-    if (rc != SPK_OK) return rc;
+    if (spkwg::form_probe) {
+        spkwg::report_form(dma ? SPK_WGRAD_GEMM1X1_DMA : SPK_WGRAD_GEMM1X1, form_mode(MODE), 0, 0, 0, MT, NT, g.n_tiles, g.splits,
+                           g.tiles_per_split, grid, lds, slab_floats, g.splits);
+    } else {
+        static bool raised[2] = {false, false};
+        if (!raised[dma]) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
+            raised[dma] = true;
+        }
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, a, g.tiles_per_split);
+        int rc = spk::check_launch("wgrad1x1_kernel");
+        if (rc != SPK_OK) return rc;
+    }
     return launch_wgrad_reduce(stream, a.slabs, d->dw, g.splits, G * d->Cout, d->Cin, 1, d->scale, d->accumulate ? 1 : 0,
                                d->fold > 1 ? d->fold : 1);
 }
@@ -2188,9 +2231,15 @@ int run_wgrad_stem(const spk_wgrad_desc* d, hipStream_t stream) {
     a.lgTW = a.lgTH = a.lgTB = 0;
     a.tiles_x = spk::ceil_div(d->W, SW_TW); a.tiles_y = spk::ceil_div(d->H, SW_TH); a.n_tiles = a.tiles_x * a.tiles_y * d->B;
     const int wgs = std::min(n_slabs, a.n_tiles);
-    hipLaunchKernelGGL(wgrad_stem_kernel, dim3((unsigned)wgs, (unsigned)G), dim3(256), SW_LDS_FL * sizeof(float), stream, a);
-    int rc = spk::check_launch("wgrad_stem_kernel");
-    if (rc != SPK_OK) return rc;
+    dim3 grid((unsigned)wgs, (unsigned)G);
+    if (spkwg::form_probe) {
+        spkwg::report_form(SPK_WGRAD_STEM, 0, SW_TW, SW_TH, 1, 0, 0, a.n_tiles, wgs, spk::ceil_div(a.n_tiles, wgs), grid,
+                           SW_LDS_FL * sizeof(float), slab_floats, n_slabs);
+    } else {
+        hipLaunchKernelGGL(wgrad_stem_kernel, grid, dim3(256), SW_LDS_FL * sizeof(float), stream, a);
+        int rc = spk::check_launch("wgrad_stem_kernel");
+        if (rc != SPK_OK) return rc;
+    }
     return launch_wgrad_reduce(stream, a.slabs, d->dw, wgs, G * 64, SW_K, 1, d->scale, d->accumulate ? 1 : 0, d->fold > 1 ? d->fold : 1);
 }
 
@@ -2264,6 +2313,25 @@ int spk_wgrad_reduce_slabs(const float* slabs, float* dw, int n_slabs, int Cout,
                            void* stream) {
     SPK_REQUIRE(slabs && dw && n_slabs > 0 && Cout > 0 && Cin > 0 && taps > 0, "wgrad reduce: bad arguments");
     return launch_wgrad_reduce((hipStream_t)stream, slabs, dw, n_slabs, Cout, Cin, taps, scale, accumulate ? 1 : 0, fold > 1 ? fold : 1);
+}
+
+int spk_wgrad_reduce_form(const float* slabs, float* dw, int n_slabs, int Cout, int Cin, int taps, int fold, spk_wgrad_form* out) {
+    SPK_REQUIRE(out, "wgrad reduce form: null pointer");
+    *out = spk_wgrad_form{};
+    spkwg::form_probe = out;         // launch_wgrad_reduce answers where it would launch
+    const int rc = spk_wgrad_reduce_slabs(slabs, dw, n_slabs, Cout, Cin, taps, 1.f, 0, fold, nullptr);
+    spkwg::form_probe = nullptr;
+    return rc;
+}
+
+int spk_conv2d_wgrad_launch_form(const spk_wgrad_desc* d, spk_wgrad_form* out) {
+    SPK_REQUIRE(d && out, "wgrad launch form: null pointer");
+    *out = spk_wgrad_form{};
+    out->kernel = -1;
+    spkwg::form_probe = out;         // the launchers and launch_wgrad_reduce answer where they would launch
+    const int rc = spk_conv2d_wgrad(d, nullptr);
+    spkwg::form_probe = nullptr;
+    return rc;
 }
 
 int spk_conv2d_wgrad(const spk_wgrad_desc* d, void* stream) {

@@ -802,12 +802,25 @@ def conv2d_wgrad(g, x, Cout, Cin, k=3, stride=1, *, upsample=False, in_affine=No
             x = upsample2x(x, zero_border=True) if up_fir else upsample2x_bilinear(x)
         return conv2d_wgrad_wino(g, x, Cout, Cin, scale=scale, out=out, accumulate=accumulate, batch_scale=batch_scale, g_scale=g_scale,
                                  in_affine=in_affine, groups=G, shared_input=shared_input, fold=fold)
+    d, out = wgrad_desc(g, x, Cout, Cin, k, stride, upsample=upsample, in_affine=in_affine, scale=scale, out=out, accumulate=accumulate,
+                        splits=splits, groups=G, shared_input=shared_input, fold=fold, batch_scale=batch_scale, g_scale=g_scale, up_fir=up_fir)
+    L.check(L.lib().spk_conv2d_wgrad(C.byref(d), L.stream_ptr()), "spk_conv2d_wgrad")
+    return out
+
+
+def wgrad_desc(g, x, Cout, Cin, k=3, stride=1, *, upsample=False, in_affine=None, scale=1.0, out=None, accumulate=False, splits=0,
+               groups=1, shared_input=False, fold=1, batch_scale=None, g_scale=None, up_fir=False, workspace=None):
+    """The ``spk_wgrad_desc`` ``conv2d_wgrad`` launches for these operands, as given (no x2 image is materialised here and the
+    Winograd router is not asked) -> (desc, out).  ``workspace``: a float32 tensor to use instead of the stream's shared scratch."""
+    B, _, H, W = g.shape
+    Hs, Ws = x.shape[-2:]
+    G, fold = int(groups), int(fold)
     if out is None:
         out = torch.empty((G // fold * Cout, Cin, k, k), device=g.device, dtype=torch.float32)
     ws_bytes = L.lib().spk_conv2d_wgrad_workspace_bytes(k, k, stride, int(splits), B, Cin, G * Cout, H, W)
     if ws_bytes < 0:
         raise L.SpkError("conv2d_wgrad: unsupported problem")
-    ws = _workspace(g.device, ws_bytes)
+    ws = _workspace(g.device, ws_bytes) if workspace is None else workspace
     flags = (L.CONV_UPSAMPLE2X if upsample else 0) | (L.CONV_IN_AFFINE_RELU if in_affine is not None else 0) | \
         (L.CONV_IN_BATCH_SCALE if batch_scale is not None else 0) | (L.CONV_UP_FIR1331 if (upsample and up_fir) else 0)
     d = L.WgradDesc(g=L.dptr(g, "g"), x=L.dptr(x, "x"),
@@ -815,10 +828,22 @@ def conv2d_wgrad(g, x, Cout, Cin, k=3, stride=1, *, upsample=False, in_affine=No
                     in_shift=L.dptr(in_affine[1], "in_shift") if in_affine is not None else None,
                     dw=L.dptr(out, "dw"), B=B, Cin=Cin, Cout=Cout, H=H, W=W, Hin=Hs, Win=Ws, kh=k, kw=k, stride=stride,
                     flags=flags, scale=float(scale), accumulate=1 if accumulate else 0, splits=int(splits),
-                    workspace=ws.data_ptr(), workspace_bytes=ws.numel() * 4, groups=G,
+                    workspace=L.dptr(ws, "workspace"), workspace_bytes=ws.numel() * 4, groups=G,
                     group_in_stride=0 if (shared_input or G == 1) else Cin, fold=fold, g_scale=L.dptr(g_scale, "g_scale"))
-    L.check(L.lib().spk_conv2d_wgrad(C.byref(d), L.stream_ptr()), "spk_conv2d_wgrad")
-    return out
+    return d, out
+
+
+def wgrad_desc_launch_form(desc):
+    """The form ``spk_conv2d_wgrad(desc)`` would take, as a dict of the ``spk_wgrad_form`` fields (``spk_conv2d_wgrad_launch_form``:
+    the launch path's own decisions, nothing is launched; pointers are read for their alignment only)."""
+    form = L.WgradForm()
+    L.check(L.lib().spk_conv2d_wgrad_launch_form(C.byref(desc), C.byref(form)), "spk_conv2d_wgrad_launch_form")
+    return {name: getattr(form, name) for name, _ in L.WgradForm._fields_}
+
+
+def wgrad_launch_form(*args, **kw):
+    """``wgrad_desc_launch_form`` of the descriptor ``wgrad_desc(*args, **kw)`` assembles."""
+    return wgrad_desc_launch_form(wgrad_desc(*args, **kw)[0])
 
 
 def wgrad_wino_supported(B, Cin, Cout, H, W) -> bool:

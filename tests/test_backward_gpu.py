@@ -36,20 +36,30 @@ def T(a):
     return torch.from_numpy(np.asarray(a))
 
 
+def wgrad_kernel_of(pkg, *args, **kw):
+    """The kernel spk_conv2d_wgrad picks for the descriptor of ``ops.wgrad_desc(*args, **kw)`` (spk_conv2d_wgrad_launch_form)."""
+    return pkg._lib.WGRAD_KERNELS[pkg.ops.wgrad_launch_form(*args, **kw)["kernel"]]
+
+
 @pytest.mark.parametrize("k,stride,B,Cin,Cout,H,W", [
     (3, 1, 2, 64, 64, 32, 32), (3, 1, 3, 20, 40, 9, 13), (3, 1, 1, 128, 72, 64, 64), (3, 1, 8, 512, 512, 8, 8),
     (1, 1, 2, 96, 160, 16, 16), (1, 2, 2, 64, 128, 16, 16), (3, 2, 2, 48, 80, 20, 20), (7, 2, 2, 3, 64, 40, 40),
     (3, 1, 1, 5, 3, 2, 2), (1, 1, 2, 2048, 512, 1, 1),
-    # the pipelined 3x3 form (16x4 tiles): partial tiles in both directions, channel blocks with 6 / 2 live rows
+    # 16x4 tiles, partial in both directions, channel blocks with 6 / 2 live rows: W % 4 == 0, so the wide form takes them (of this
+    # list only (3, 1, 3, 20, 40, 9, 13) reaches the pipelined form; tests/wgrad_cases.py has the cases of every form)
     (3, 1, 3, 24, 40, 6, 20), (3, 1, 2, 70, 130, 12, 36),
 ])
 def test_wgrad_vs_autograd(pkg, dev, k, stride, B, Cin, Cout, H, W):
+    kernel = {(3, 1, 2, 64, 64, 32, 32): "wide16", (3, 1, 3, 20, 40, 9, 13): "pipe", (3, 1, 1, 128, 72, 64, 64): "wide16", (3, 1, 8, 512, 512, 8, 8): "wide8",
+              (1, 1, 2, 96, 160, 16, 16): "gemm1x1", (1, 2, 2, 64, 128, 16, 16): "gemm1x1", (3, 2, 2, 48, 80, 20, 20): "tap", (7, 2, 2, 3, 64, 40, 40): "stem",
+              (3, 1, 1, 5, 3, 2, 2): "tap", (1, 1, 2, 2048, 512, 1, 1): "tap", (3, 1, 3, 24, 40, 6, 20): "wide16", (3, 1, 2, 70, 130, 12, 36): "wide16"}
     tag = f"wg.{k}.{stride}.{B}.{Cin}.{Cout}.{H}.{W}"
     x = recipe_input(tag + ".x", (B, Cin, H, W))
     w = recipe_tensor(tag + ".weight", (Cout, Cin, k, k)).requires_grad_(True)
     y = F.conv2d(x, w, stride=stride, padding=(k - 1) // 2)
     g = recipe_input(tag + ".g", y.shape)
     y.backward(g)
+    assert wgrad_kernel_of(pkg, g.to(dev), x.to(dev), Cout, Cin, k, stride) == kernel[(k, stride, B, Cin, Cout, H, W)]
     for splits in (0, 1, 3):
         dw = pkg.ops.conv2d_wgrad(g.to(dev), x.to(dev), Cout, Cin, k, stride, splits=splits)
         assert rel_l2(dw, w.grad) < TOL, splits
@@ -97,6 +107,7 @@ def test_wgrad_stride1_wide_form(pkg, dev, B, Cin, Cout, H, W, groups, aff):
     y.backward(g)
     ref = torch.cat([w.grad for w in ws], 0)
     kw = dict(in_affine=(a.to(dev), b.to(dev))) if aff else {}
+    assert wgrad_kernel_of(pkg, g.to(dev), x.to(dev), Cout, Cin, 3, 1, groups=G, **kw) == ("wide16" if W >= 16 else "wide8")
     for splits in (0, 1, 3):
         dw = pkg.ops.conv2d_wgrad(g.to(dev), x.to(dev), Cout, Cin, 3, 1, splits=splits, groups=G, **kw)
         assert rel_l2(dw, ref) < TOL, splits
@@ -116,6 +127,7 @@ def test_wgrad_stem_form(pkg, dev, B, Hin, Win, G, shared):
     g = recipe_input(tag + ".g", y.shape)
     y.backward(g)
     ref = torch.cat([w.grad for w in ws], 0)
+    assert wgrad_kernel_of(pkg, g.to(dev), x.to(dev), 64, 3, 7, 2, groups=G, shared_input=shared) == "stem"
     for splits in (0, 1, 7):
         dw = pkg.ops.conv2d_wgrad(g.to(dev), x.to(dev), 64, 3, 7, 2, splits=splits, groups=G, shared_input=shared)
         assert rel_l2(dw, ref) < TOL, splits
@@ -150,6 +162,7 @@ def test_wgrad_1x1_lds_dma_form(pkg, dev, B, Cin, Cout, H, W, groups, aff):
     y.backward(g)
     ref = torch.cat([w.grad for w in ws], 0)
     kw = dict(in_affine=(a.to(dev), b.to(dev))) if aff else {}
+    assert wgrad_kernel_of(pkg, g.to(dev), x.to(dev), Cout, Cin, 1, 1, groups=G, **kw) == "gemm1x1_dma"
     for splits in (0, 1, 2, 5):
         dw = pkg.ops.conv2d_wgrad(g.to(dev), x.to(dev), Cout, Cin, 1, 1, splits=splits, groups=G, **kw)
         assert rel_l2(dw, ref) < TOL, splits
@@ -183,6 +196,7 @@ def test_wgrad_stride2_wide_form(pkg, dev, B, Cin, Cout, H, W, groups, aff):
     y.backward(g)
     ref = torch.cat([w.grad for w in ws], 0)
     kw = dict(in_affine=(a.to(dev), b.to(dev))) if aff else {}
+    assert wgrad_kernel_of(pkg, g.to(dev), x.to(dev), Cout, Cin, 3, 2, groups=G, **kw) == ("s2_16" if W >= 16 else "s2_8")
     for splits in (0, 1, 5):
         dw = pkg.ops.conv2d_wgrad(g.to(dev), x.to(dev), Cout, Cin, 3, 2, splits=splits, groups=G, **kw)
         assert rel_l2(dw, ref) < TOL, splits
@@ -392,6 +406,7 @@ def test_wgrad_of_upsampled_input_without_materialising_it(pkg, dev, B, Cin, Cou
     y.backward(g)
     # (tests/conftest.py sets SPK_WGRAD_UP_MIN_W=16: in the test process every shape the folded kernel can take goes to it)
     assert pkg._lib.lib().spk_conv2d_wgrad_up_supported(B, Cin, Cout, 2 * Hs, 2 * Ws)
+    assert wgrad_kernel_of(pkg, g.to(dev), x.to(dev), Cout, Cin, 3, 1, upsample=True) == "up"
     for splits in (0, 1, 3):
         dw = pkg.ops.conv2d_wgrad(g.to(dev), x.to(dev), Cout, Cin, 3, 1, upsample=True, splits=splits)
         assert rel_l2(dw, w.grad) < TOL, splits

@@ -728,6 +728,53 @@ int spk_frames_paste_u8(const float* src, int N, int Hs, int Ws, uint8_t* dst, i
                         const float* w_y, int taps_y, const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x,
                         const float* a_y, const float* a_x, float lo, float k, void* stream);
 
+/* ---- the video-frame edge through a per-frame similarity transform: aligned crops (csrc/frame_sim.hip) ---------------------------
+ * A face pipeline in the FFHQ style fits a similarity transform to the landmarks of every frame and crops through it: the crop's
+ * scale and angle change per frame, which one host-built table per axis cannot follow.  These two entry points compute their
+ * filter weights in the kernel, in fp64, from a row per frame that lives on the device.
+ *
+ * THE TRANSFORM.  sim_dev is a DEVICE fp32 [N][4] array of rows (a, c, tx, ty), promoted to fp64.  Row n maps network-image
+ * coordinates (u, v) to coordinates (x, y) of frame n:
+ *     x = a u - c v + tx,   y = c u + a v + ty,   s = sqrt(a^2 + c^2)            (s: frame pixels per network pixel)
+ * The centre of network pixel (ox, oy) is (ox + 0.5, oy + 0.5), that of frame pixel (ix, iy) is (ix + 0.5, iy + 0.5) -- the
+ * conventions of spk_resize_table -- so (h / size, 0, x0, y0) is the square crop box (y0, x0, h, h).  A row is VALID when its four
+ * numbers are finite and 1/16 <= s <= 16 (the bound keeps a footprint, and with it a thread's loop, finite whatever a tracker
+ * wrote); the rows are not read on the host.  Coordinates are clamped in fp64 before they become indices: no row, however wild,
+ * causes an out-of-bounds access.
+ *
+ * spk_frames_u8_to_f32_sim: warp + antialias + normalise + HWC -> CHW in one pass.  src: N uint8 frames of H x W pixels, pixel
+ *   stride 3, image_stride / row_stride in BYTES, any byte address; dst [N,3,Hout,Wout] contiguous (Hout and Wout may differ).
+ *   For output (oy, ox) of frame n let p = sim_n(ox + 0.5, oy + 0.5), S = max(s, 1), and for a frame pixel centre q, (dx, dy) = q - p:
+ *     e_u = (a dx + c dy) / s,  e_v = (-c dx + a dy) / s,  w(q) = tri(e_u / S) tri(e_v / S),  tri(t) = max(0, 1 - |t|)
+ *   -- the triangle filter of interpolate(antialias=True), laid along the crop's own axes --
+ *     Wt = sum_q w(q) over the pixels of the H x W frame,   V = sum_q w(q) src[n,iy,ix,c'] / Wt,   c' = swap_rb ? 2 - c : c
+ *     dst[n,c,oy,ox] = (float) fma((double) scale_c, V, (double) shift_c)
+ *   with V = 0 when Wt <= 0 (the footprint misses the frame) or the row is invalid: such outputs are shift_c exactly.  With
+ *   c = 0 and a scale that is exact in fp32 the whole-frame result is spk_frames_u8_to_f32's to its fp32 table rounding; at the
+ *   edge of a sub-box the two differ by design (the table form clamps its windows to the box, this one to the frame).
+ * spk_frames_paste_u8_sim: inverse warp + quantise + feather-blend into the full frames + CHW -> HWC in one launch without
+ *   allocation or synchronisation.  src [N,3,Hs,Ws] fp32 contiguous; dst: N frames of H x W pixels that already hold the
+ *   background, strides in BYTES, any byte address, the frames must not overlap (as spk_frames_paste_u8).  For frame pixel (Y, X)
+ *   of frame n let (u, v) = sim_n^-1(X + 0.5, Y + 0.5).  The pixel belongs to the REGION when 0 <= u < Ws and 0 <= v < Hs and it
+ *   lies inside the frame; every other byte of dst is left untouched, and with an invalid row the whole frame is.  For a region
+ *   pixel, r = max(1, 1 / s):
+ *     w_u[i] = tri((i + 0.5 - u) / r), i < Ws;   w_v[j] = tri((j + 0.5 - v) / r), j < Hs
+ *     val = sum_j sum_i w_v[j] w_u[i] src[n,c,j,i] / (sum w_u  sum w_v)                   fp64 sums
+ *     q   = min(max(((float) val - lo) * k, 0), 255)                                      fp32 in that order, as spk_frames_paste_u8
+ *     b   = dst[n,Y,X,c']                                                                 the background byte
+ *     a_u = min(1, (s min(u, Ws - u) + 0.5) / (feather + 1)),  a_v likewise,  m = a_u a_v  (feather >= 0, finite)
+ *     dst[n,Y,X,c'] = (uint8) rint(fma(m, q - b, b))                                      fp64, ties to even
+ *   For c = 0 and a box at an integer origin, region, weights and feather are those of the spk_resize_table / spk_feather_table
+ *   composition.  A fixed number of workgroups per frame derive the region's bounding box from the row and stride over it; a thread
+ *   reads the one background byte it overwrites, so pasting in place has no hazard.
+ * Both refuse bad arguments before any launch (SPK_EINVAL, spk_last_error).  replaces: affine_grid + grid_sample (not antialiased)
+ *   on fp32 copies of full frames around inference.py:46-58,78-86. */
+int spk_frames_u8_to_f32_sim(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int H, int W, const float* sim_dev,
+                             int swap_rb, float* dst, int Hout, int Wout, float scale0, float scale1, float scale2, float shift0,
+                             float shift1, float shift2, void* stream);
+int spk_frames_paste_u8_sim(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W,
+                            const float* sim_dev, int swap_rb, double feather, float lo, float k, void* stream);
+
 /* ---- the video-frame edge in NV12 form (csrc/frame_nv12.hip) ---------------------------------------------------------------------
  * What a hardware decoder or encoder holds in device memory, in and out of the network without a packed-RGB detour.
  *

@@ -1,5 +1,6 @@
 """The video-frame edge of the inference path: uint8 frames as a video decoder / writer holds them on the device, in and out of the
-network -- packed RGB (csrc/frame_io.hip) and NV12 (csrc/frame_nv12.hip).  ``ops`` re-exports the launchers (``ops.frames_from_u8``
+network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packed RGB through a similarity transform per frame
+(csrc/frame_sim.hip: aligned crops).  ``ops`` re-exports the launchers (``ops.frames_from_u8``
 ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
 from __future__ import annotations
 
@@ -181,8 +182,8 @@ def frames_from_u8(frames_u8, size, *, crop=None, channel_order="rgb", mean=0.5,
     + ``ToTensor`` + ``Normalize`` of inference.py:29-33 with the ``cv2.cvtColor`` of :53 (``channel_order="bgr"``: the frames are
     BGR, the result is RGB).  ``frames_u8``: uint8 [N,H,W,3] (or [H,W,3]) on the device, pixels packed (any row / frame stride:
     slices of a larger frame are read in place); ``crop=(y0, x0, h, w)``: one box for all frames; a host sequence or CPU integer
-    tensor ``[N,4]``: a box per frame, all of one size (``ValueError`` otherwise: a call has one filter table), checked on the
-    host and uploaded once; ``(boxes_yx, h, w)`` with a device int32 ``[N,2]`` tensor: origins a tracker left on the device,
+    tensor ``[N,4]``: a box per frame, all of one size (``ValueError`` otherwise: a call has one filter table;
+    ``frames_from_u8_aligned`` takes a crop of any size and angle per frame), checked on the host and uploaded once; ``(boxes_yx, h, w)`` with a device int32 ``[N,2]`` tensor: origins a tracker left on the device,
     not read on the host -- the kernel clamps each so that the box stays inside the frame (``spk_frames_u8_to_f32_boxes``).
     -> float32 [N,3,size,size]."""
     if frames_u8.dim() == 3:
@@ -276,6 +277,130 @@ def frames_paste_u8(x, frames_u8, box, *, feather=0, value_range=(-1, 1), channe
     tables, ay, ax = _paste_tables(Hs, Ws, h, w, feather, x.device)
     L.check(L.lib().spk_frames_paste_u8(xp, N, Hs, Ws, out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), H, W, h, w, y0, x0,
                                         _ptr(boxes), swap, *tables, ay, ax, lo, k, L.stream_ptr()), "spk_frames_paste_u8")
+    return out
+
+
+# ---- aligned crops: a similarity transform per frame (csrc/frame_sim.hip; the definitions are in include/spk.h) ------------------
+SIM_SCALE = (1.0 / 16.0, 16.0)                                            # the valid range of s = sqrt(a^2 + c^2), ends included
+
+
+def similarity_rows(centre_yx, side, angle=0.0, size=256):
+    """Rows ``(a, c, tx, ty)`` of the similarity transform that maps the ``size`` x ``size`` network image onto the square of
+    ``side`` frame pixels centred at ``centre_yx = (y, x)`` and rotated by ``angle`` radians (``x = a u - c v + tx``,
+    ``y = c u + a v + ty``; a positive angle turns the network's u axis towards the frame's y axis).  ``centre_yx``: one pair or
+    ``[N,2]``; ``side`` and ``angle``: a number or ``N`` numbers; ``size``: a number, or ``(H, W)`` -- then ``side`` spans the
+    width ``W`` and the centre of the ``H x W`` image lands on ``centre_yx``.  Host only, computed in fp64.
+    -> CPU float32 tensor ``[N,4]``; ``angle=0`` and ``centre`` at the middle of a box ``(y0, x0, h, h)`` gives that box."""
+    Hout, Wout = _out_size(size, "similarity_rows")
+    centre = torch.as_tensor(centre_yx, dtype=torch.float64).reshape(-1, 2)
+    side = torch.as_tensor(side, dtype=torch.float64).reshape(-1)
+    angle = torch.as_tensor(angle, dtype=torch.float64).reshape(-1)
+    N = max(centre.size(0), side.numel(), angle.numel())
+    if any(n not in (1, N) for n in (centre.size(0), side.numel(), angle.numel())):
+        raise ValueError(f"similarity_rows: centre_yx, side and angle must have one length, got {centre.size(0)}, {side.numel()}, {angle.numel()}")
+    s = side / Wout
+    a, c = s * torch.cos(angle), s * torch.sin(angle)
+    u0, v0 = Wout / 2.0, Hout / 2.0
+    rows = torch.stack([a.expand(N), c.expand(N), (centre[:, 1] - (a * u0 - c * v0)).expand(N), (centre[:, 0] - (c * u0 + a * v0)).expand(N)], 1)
+    return rows.float()
+
+
+def parse_sim(sim, N, what="sim"):
+    """The two forms a launcher takes transforms in, for ``N`` frames: a DEVICE float32 tensor ``[N,4]``, which is not read here
+    (the kernels follow the invalid-row rule of include/spk.h); or a host sequence / CPU tensor ``[N,4]``, rounded to fp32 and
+    checked: every number finite and ``1/16 <= s <= 16``, else ``ValueError``.  -> float32 ``[N,4]``, contiguous, still where it was."""
+    if isinstance(sim, torch.Tensor) and sim.is_cuda:
+        if sim.dtype != torch.float32 or tuple(sim.shape) != (N, 4):
+            raise ValueError(f"{what}: device transforms must be a float32 tensor [{N},4], got {sim.dtype} {tuple(sim.shape)}")
+        return sim.contiguous()
+    try:
+        rows = torch.as_tensor(sim).to(torch.float64).to(torch.float32)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"{what}: transforms must be [{N},4] rows of (a, c, tx, ty): {e}") from None
+    if tuple(rows.shape) != (N, 4):
+        raise ValueError(f"{what}: transforms must be [{N},4] rows of (a, c, tx, ty), got {tuple(rows.shape)}")
+    r64 = rows.double()
+    s = (r64[:, 0] ** 2 + r64[:, 1] ** 2).sqrt()
+    bad = ~(torch.isfinite(r64).all(1) & (s >= SIM_SCALE[0]) & (s <= SIM_SCALE[1]))
+    if bool(bad.any()):
+        n = int(bad.nonzero()[0])
+        raise ValueError(f"{what}: row {n} = {rows[n].tolist()} is not a valid transform (finite numbers, 1/16 <= sqrt(a^2 + c^2) <= 16)")
+    return rows.contiguous()
+
+
+def _sim_on(rows, device, what):                                          # host rows: uploaded once; device rows: where the frames are
+    if rows.device != device:
+        if rows.is_cuda:
+            raise L.SpkError(f"{what}: transforms on {rows.device}, frames on {device}")
+        rows = rows.to(device)
+    return rows
+
+
+def frames_from_u8_aligned(frames_u8, size, sim, *, channel_order="rgb", mean=0.5, std=0.5):
+    """uint8 HWC video frames -> the network's input through a similarity transform PER FRAME, one launch
+    (``spk_frames_u8_to_f32_sim``): the crop of frame ``n`` is the square (rectangle) ``sim[n]`` maps the ``size`` network image
+    onto -- any scale and angle per frame, which ``frames_from_u8`` (one box size per call) cannot follow -- filtered with the
+    triangle filter of ``interpolate(antialias=True)`` laid along the crop's own axes, weights computed in the kernel in fp64;
+    then ``(x / 255 - mean) / std`` and HWC -> CHW as ``frames_from_u8``.  Pixels outside the frame take no part: an output whose
+    footprint misses the frame is ``-mean / std``.  ``sim``: rows ``(a, c, tx, ty)`` (``similarity_rows``; include/spk.h): a host
+    sequence / CPU tensor ``[N,4]``, checked on the host (``ValueError`` for a row that is not finite or has a scale outside
+    [1/16, 16]) and uploaded once; or a device float32 ``[N,4]`` tensor a tracker left there, not read on the host -- an invalid
+    row gives a frame of ``-mean / std``.  -> float32 [N,3,size,size]."""
+    what = "frames_from_u8_aligned"
+    if frames_u8.dim() == 3:
+        frames_u8 = frames_u8.unsqueeze(0)
+    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
+        raise ValueError(f"{what}: frames must be [N,H,W,3], got {tuple(frames_u8.shape)}")
+    Hout, Wout = _out_size(size, what)
+    swap = _channel_swap(channel_order)
+    scale, shift = _affine(mean, std, what)
+    rows = parse_sim(sim, frames_u8.size(0), f"{what}: sim")
+    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
+        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
+    N, H, W, _ = frames_u8.shape
+    if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * W or (N > 1 and frames_u8.stride(0) < 0):
+        frames_u8 = frames_u8.contiguous()
+    rows = _sim_on(rows, frames_u8.device, what)
+    out = torch.empty((N, 3, Hout, Wout), device=frames_u8.device, dtype=torch.float32)
+    L.check(L.lib().spk_frames_u8_to_f32_sim(frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), N, H, W,
+                                             rows.data_ptr(), swap, out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()),
+            "spk_frames_u8_to_f32_sim")
+    return out
+
+
+def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1), channel_order="rgb", out=None):
+    """Generated frames back into the video they were cropped from through ``sim``, one launch (``spk_frames_paste_u8_sim``): the
+    inverse of ``frames_from_u8_aligned``.  Every frame pixel whose centre ``sim[n]`` maps from inside the ``Hs x Ws`` image of
+    float32 ``x`` [N,3,Hs,Ws] takes the antialiased bilinear value of ``x`` there, quantised as ``frames_to_u8`` does, and is
+    blended over the background byte with weight ``a_u a_v``, a ramp over ``feather`` frame pixels at the crop's own edges
+    (``feather=0``: the crop replaces the background); every other byte of the frames is left as it is.  ``sim``: the two forms
+    of ``frames_from_u8_aligned``; a device row that is invalid leaves its frame untouched.  ``channel_order``, ``out``: as
+    ``frames_paste_u8``.  -> uint8 [N,H,W,3]."""
+    what = "frames_paste_u8_aligned"
+    _check_chw(x, what)
+    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != x.size(0):
+        raise ValueError(f"{what}: frames must be [{x.size(0)},H,W,3], got {tuple(frames_u8.shape)}")
+    swap = _channel_swap(channel_order)
+    lo, k = quant_range(value_range)
+    feather = check_feather(feather, what)
+    N, _, Hs, Ws = x.shape
+    H, W = frames_u8.size(1), frames_u8.size(2)
+    rows = parse_sim(sim, N, f"{what}: sim")
+    xp = L.dptr(x, "x")
+    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
+        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
+    copy = out is not None and out is not frames_u8 and out.data_ptr() != frames_u8.data_ptr()
+    if out is None:
+        out = frames_u8.clone(memory_format=torch.contiguous_format)
+    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames_u8.shape):
+        raise L.SpkError(f"out: expected a uint8 HIP tensor {tuple(frames_u8.shape)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if not packed_pixels(out):
+        raise L.SpkError(f"out: pixels must be packed and rows / frames must not overlap, got strides {out.stride()}")
+    rows = _sim_on(rows, x.device, what)
+    if copy:
+        out.copy_(frames_u8)
+    L.check(L.lib().spk_frames_paste_u8_sim(xp, N, Hs, Ws, out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), H, W, rows.data_ptr(),
+                                            swap, feather, lo, k, L.stream_ptr()), "spk_frames_paste_u8_sim")
     return out
 
 
@@ -431,6 +556,32 @@ def frames_paste_nv12(x, nv12, box, *, feather=0, value_range=(-1, 1), standard=
     return out
 
 
+class Aligned:
+    """``IRFD.reenact_video(align=...)``: the transforms of a clip, standing where a crop box would.  ``rows``: float32 ``[T,4]``
+    where the frames are; ``size``: ``(H, W)`` of the network image the rows map into the frames."""
+
+    def __init__(self, rows, size):
+        self.rows, self.size, self._generated = rows, size, {}
+
+    @classmethod
+    def parse(cls, sim, T, size, device):                                 # host rows: checked here, uploaded once for both edges
+        rows = parse_sim(sim, T, "reenact_video: align")
+        if not rows.is_cuda and device.type == "cuda":
+            rows = rows.to(device)
+        return cls(rows, _out_size(size, "reenact_video"))
+
+    def chunk(self, t0, t1, y):
+        """The transforms of frames ``[t0, t1)`` for pasting their generated images ``y`` [n,3,Hs,Ws]: the network image has
+        ``size`` pixels where ``y`` has ``Hs x Ws``, so ``(a, c)`` are scaled by ``size / Ws`` (once per clip, in fp32)."""
+        Hs, Ws = y.shape[2:]
+        if Hs * self.size[1] != Ws * self.size[0]:
+            raise ValueError(f"reenact_video: align needs generated frames in the shape of the network input, got {Hs} x {Ws} for {self.size}")
+        if Ws not in self._generated:
+            k = self.size[1] / Ws
+            self._generated[Ws] = self.rows if k == 1 else self.rows * torch.tensor([k, k, 1.0, 1.0], dtype=torch.float32).to(self.rows.device)
+        return Aligned(self._generated[Ws][t0:t1], (Hs, Ws))
+
+
 # ---- what IRFD.reenact_video asks of a pixel format -------------------------------------------------------------------------------
 class Rgb24:
     """Packed uint8 frames ``[T,H,W,3]`` in ``channel_order``."""
@@ -447,14 +598,19 @@ class Rgb24:
             raise L.SpkError(f"reenact_video: inplace needs packed pixels and rows / frames that do not overlap, got strides {frames.stride()}")
         return (frames, frames.device, *frames.shape[:3])
 
-    def network_input(self, frames, size, crop):
+    def network_input(self, frames, size, crop):                          # ``crop``: a box in a launcher's forms, or ``Aligned``
+        if isinstance(crop, Aligned):
+            return frames_from_u8_aligned(frames, size, crop.rows, **self.args)
         return frames_from_u8(frames, size, crop=crop, **self.args)
 
     def clone(self, frames):                                              # -> (the result, what ``paste`` takes)
         return (frames.clone(memory_format=torch.contiguous_format),) * 2
 
-    def paste(self, y, frames, t0, t1, box, feather):
-        frames_paste_u8(y, frames[t0:t1], box, feather=feather, out=frames[t0:t1], **self.args)
+    def paste(self, y, frames, t0, t1, box, feather):                     # ``box``: a box, or what ``Aligned.chunk`` gave
+        if isinstance(box, Aligned):
+            frames_paste_u8_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], **self.args)
+        else:
+            frames_paste_u8(y, frames[t0:t1], box, feather=feather, out=frames[t0:t1], **self.args)
 
 
 class Nv12:

@@ -167,14 +167,14 @@ class IRFD(nn.Module):
     @torch.no_grad()
     def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8,
                       seed=None, noise="fresh", frame0=0, paste=False, feather=0, inplace=False, pixel_format="rgb24", standard="bt601",
-                      full_range=False):
+                      full_range=False, align=None):
         """``reenact`` from and to video frames as a decoder and a video writer hold them (inference.py:29-33,46-58,78-86):
         uint8 HWC frames of any size on the device in, uint8 [T,R,R,3] out, both in ``channel_order`` ("bgr": ``cv2``'s).
         Nothing but ``ops.frames_from_u8`` -> ``reenact(output="uint8")``: ``identity_u8`` [H,W,3] or [1,H,W,3] is resized whole
         to ``size``; ``pose_u8`` / ``emotion_u8`` [T,H,W,3] are cropped to ``crop`` and resized; ``emotion_u8=None``: the pose
         frames, resized once.  ``crop``: ``(y0, x0, h, w)``, one box for all frames; a host sequence / CPU integer tensor
-        ``[T,4]``, a tracker's box per frame, all of one size; or ``(boxes_yx, h, w)`` with a device int32 ``[T,2]`` tensor of
-        origins (``ops.frames_from_u8``).  ``seed`` / ``noise`` / ``frame0``: as ``reenact``.
+        ``[T,4]``, a tracker's box per frame, all of one size (``align=`` below: any size and angle per frame); or
+        ``(boxes_yx, h, w)`` with a device int32 ``[T,2]`` tensor of origins (``ops.frames_from_u8``).  ``seed`` / ``noise`` / ``frame0``: as ``reenact``.
 
         ``paste=True``: the full frames back -- uint8 [T,H,W,3], the pose frames with every generated face resized to its box
         and pasted where the crop came from (``crop=None``: the whole frame), blended over ``feather`` pixels at the box's
@@ -187,7 +187,17 @@ class IRFD(nn.Module):
         (``ops.nv12_planes``), in the colour of ``standard`` ("bt601" | "bt709") / ``full_range`` -- and so is the result:
         ``[T,3R/2,R]``, or with ``paste=True`` the pose surfaces with every face pasted back (``ops.frames_from_nv12``,
         ``reenact(output="nv12")``, ``ops.frames_paste_nv12``: one launch per chunk).  The identity image stays a uint8 HWC photo
-        in ``channel_order``; ``crop`` keeps its three forms and may have an odd origin."""
+        in ``channel_order``; ``crop`` keeps its three forms and may have an odd origin.
+
+        ``align=sim`` (instead of ``crop``; both: ``ValueError``): an aligned crop per frame -- rows ``(a, c, tx, ty)`` of the
+        similarity transform that maps the ``size`` network image into frame ``t`` (``ops.similarity_rows``; include/spk.h), any
+        scale and angle per frame, as a landmark tracker fits them: a host sequence / CPU tensor ``[T,4]``, checked on the host
+        and uploaded once, or a device float32 ``[T,4]`` tensor, not read on the host.  ``pose_u8`` / ``emotion_u8`` go through
+        ``ops.frames_from_u8_aligned``; with ``paste=True`` each chunk's fp32 result goes through ``ops.frames_paste_u8_aligned``
+        into its slice, one ``spk_frames_paste_u8_sim`` launch per chunk, rows taken per frame, so the result does not depend on
+        ``chunk``.  The generated image has ``R`` pixels where the network image has ``size``: the paste uses the rows with
+        ``(a, c)`` scaled by ``size / R`` in fp32.  Packed RGB only: ``align`` with ``pixel_format="nv12"`` raises ``ValueError``
+        (NV12 frames take crop boxes)."""
         if pixel_format not in FR.PIXEL_FORMATS:
             raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
         if pixel_format == "rgb24" and (standard != "bt601" or full_range):
@@ -200,9 +210,16 @@ class IRFD(nn.Module):
             raise ValueError("reenact_video: feather applies to paste=True only")
         FR.check_feather(feather, "reenact_video")
         _check_noise("reenact_video", noise, seed, noises, frame0)
+        if align is not None and crop is not None:
+            raise ValueError("reenact_video: crop and align are two ways to say where the face is: give one")
+        if align is not None and pixel_format != "rgb24":
+            raise ValueError("reenact_video: align applies to pixel_format='rgb24' only (NV12 frames take crop boxes)")
         fmt = FR.PIXEL_FORMATS[pixel_format](channel_order, standard, full_range)
         pose_in = pose_u8
-        if crop is not None or paste or fmt.needs_box:
+        if align is not None:                                              # the transforms stand where a box would: checked / uploaded once
+            pose_in, device, T, H, W = fmt.open(pose_u8, inplace)
+            crop = FR.Aligned.parse(align, T, size, device)
+        elif crop is not None or paste or fmt.needs_box:
             pose_in, device, T, H, W = fmt.open(pose_u8, inplace)
             origins, h, w = FR.parse_boxes((0, 0, H, W) if crop is None else crop, T, H, W, "reenact_video: crop")
             if not isinstance(origins, tuple) and not origins.is_cuda and device.type == "cuda":
@@ -216,7 +233,8 @@ class IRFD(nn.Module):
                                 **fmt.args)
         result, out = (pose_u8, pose_in) if inplace else fmt.clone(pose_in)
         for t0, t1, y in self._reenact_chunks(ident, pose, emo, noises, chunk, "f32", "rgb", seed, noise, frame0):
-            fmt.paste(y, out, t0, t1, crop if len(crop) == 4 else (crop[0][t0:t1], h, w), feather)
+            where = crop.chunk(t0, t1, y) if align is not None else crop if len(crop) == 4 else (crop[0][t0:t1], h, w)
+            fmt.paste(y, out, t0, t1, where, feather)
         return result
 
     def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None, colour=("bt601", False)):

@@ -23,9 +23,18 @@
     chunk, so that the fp32 temporaries of the torch conversions stay at a chunk's size); both produce NV12 surfaces; alternating,
     with the ATen calls of both.
 
-    python tools/bench_frame_io.py [--paste | --nv12] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
+``--align``: the aligned edge (csrc/frame_sim.hip), a similarity transform per frame: 8 frames of 1080 x 1920 BGR, rows with
+    s = 400 / 256 and angles within +-0.3 rad, a 256^2 network.  (1) ``ops.frames_from_u8_aligned`` beside
+    ``ops.frames_from_u8(crop=(yx, 400, 400))`` (that kernel is the parent commit's) and (2) beside the torch composition a user has
+    without it, ``affine_grid`` + ``grid_sample`` on fp32 copies (not antialiased: a time baseline only); (3)
+    ``ops.frames_paste_u8_aligned`` (feather 16, in place) beside ``ops.frames_paste_u8`` and its torch composition; (4)
+    ``IRFD.reenact_video(align=, paste=True)`` beside ``reenact_video(crop=, paste=True)``.  The contenders alternate in one process,
+    medians are compared, and the aligned launcher runs twice per round: the distance of its two medians is the recorded spread.
+
+    python tools/bench_frame_io.py [--paste | --nv12 | --align] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
+import math
 import os
 import statistics
 import sys
@@ -261,6 +270,133 @@ def bench_nv12(args, lines):
                  f"{c_ours.n} against {c_other.n} ({T // chunk} chunks)")
 
 
+def torch_aligned_in(video, theta, size):
+    """The torch composition ``ops.frames_from_u8_aligned`` replaces, on fp32 copies of the full frames: ``affine_grid`` +
+    ``grid_sample`` (bilinear, NOT antialiased: a time baseline only) + normalise.  ``theta``: ``align_thetas(...)[0]``."""
+    x = video.permute(0, 3, 1, 2).flip(1).float()
+    grid = F.affine_grid(theta, (video.size(0), 3, size, size), align_corners=False)
+    return (F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=False) / 255 - 0.5) / 0.5
+
+
+def torch_aligned_paste(y, video_out, theta_inv, scale, feather):
+    """The torch composition ``ops.frames_paste_u8_aligned`` replaces, on fp32 copies of the full frames: the inverse warp of
+    every frame pixel (``affine_grid`` + ``grid_sample``), quantise, the feather ramp from the sampling grid, mask, blend, round,
+    cast, permute.  ``theta_inv``: ``align_thetas(...)[1]``; ``scale``: s per frame, [N,1,1]."""
+    N, H, W, _ = video_out.shape
+    Hs, Ws = y.shape[2:]
+    grid = F.affine_grid(theta_inv, (N, 3, H, W), align_corners=False)
+    q = ((F.grid_sample(y, grid, mode="bilinear", padding_mode="zeros", align_corners=False) + 1) * 127.5).clamp(0, 255).flip(1)
+    u, v = (grid[..., 0] + 1) * (Ws / 2), (grid[..., 1] + 1) * (Hs / 2)
+    inside = (u >= 0) & (u < Ws) & (v >= 0) & (v < Hs)
+    a_u = ((scale * torch.minimum(u, Ws - u) + 0.5) / (feather + 1.0)).clamp(max=1.0)
+    a_v = ((scale * torch.minimum(v, Hs - v) + 0.5) / (feather + 1.0)).clamp(max=1.0)
+    m = (a_u * a_v * inside).unsqueeze(-1)
+    b = video_out.float()
+    video_out.copy_((b + m * (q.permute(0, 2, 3, 1) - b)).round().to(torch.uint8))
+
+
+def align_thetas(rows, H, W, Hn, Wn):
+    """``affine_grid`` matrices (normalised coordinates, ``align_corners=False``) of rows ``(a, c, tx, ty)`` that map an
+    ``Hn x Wn`` image into ``H x W`` frames: -> (network grid -> frame [N,2,3], frame grid -> network [N,2,3], s [N,1,1])."""
+    a, c, tx, ty = rows.double().unbind(1)
+    fwd = torch.stack([torch.stack([a * Wn / W, -c * Hn / W, 2 * (a * Wn / 2 - c * Hn / 2 + tx) / W - 1], 1),
+                       torch.stack([c * Wn / H, a * Hn / H, 2 * (c * Wn / 2 + a * Hn / 2 + ty) / H - 1], 1)], 1)
+    s2 = a * a + c * c
+    ia, ic = a / s2, c / s2
+    inv = torch.stack([torch.stack([ia * W / Wn, ic * H / Wn, 2 * (ia * (W / 2 - tx) + ic * (H / 2 - ty)) / Wn - 1], 1),
+                       torch.stack([-ic * W / Hn, ia * H / Hn, 2 * (-ic * (W / 2 - tx) + ia * (H / 2 - ty)) / Hn - 1], 1)], 1)
+    return fwd.float(), inv.float(), s2.sqrt().float().view(-1, 1, 1)
+
+
+def alternate(contenders, repeats, timer):
+    """Times every contender once per round, ``repeats`` rounds, in one process: -> {name: sorted times}"""
+    times = {n: [] for n in contenders}
+    for _ in range(repeats):
+        for n, fn in contenders.items():
+            times[n].append(timer(fn))
+    return {n: sorted(ts) for n, ts in times.items()}
+
+
+def bench_align(args, lines):
+    """``--align``: the aligned edge (csrc/frame_sim.hip) beside the axis-aligned launchers (their kernels are the parent
+    commit's) and beside the torch compositions a user has without it; the aligned launcher is a contender twice, and the
+    distance of its two medians is the spread the other differences are read against."""
+    import importlib
+    import model
+    from oracle import irfd_ref as IR
+    from oracle.weights_recipe import fill_state_dict
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    T, chunk, size, Hf, Wf, side, feather = args.frames, args.chunk, 256, 1080, 1920, 400, 16
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(T)]                  # a head that moves ...
+    angles = [0.3 * math.sin(0.9 * t) for t in range(T)]                                   # ... and rolls within +-0.3 rad
+    yx = torch.tensor(boxes, dtype=torch.int32, device=dev)
+    rows = ops.similarity_rows([(y + side / 2, x + side / 2) for y, x in boxes], float(side), angles, size).to(dev)
+    fwd, inv, scale = (t.to(dev) for t in align_thetas(rows.cpu(), Hf, Wf, size, size))
+
+    def table(title, times, ours, others):
+        lines.append(title)
+        med = {n: statistics.median(ts) for n, ts in times.items()}
+        for n, ts in times.items():
+            lines.append(f"  {n:44s} median {med[n] * 1e6:9.1f} us  min {ts[0] * 1e6:9.1f}  max {ts[-1] * 1e6:9.1f}")
+        spread = abs(med[ours] - med[ours + " (again)"]) / min(med[ours], med[ours + " (again)"])
+        lines.append(f"  spread of the repeated contender: {spread * 100:.2f} %")
+        for n, verdict in others:
+            r = med[ours] / med[n]
+            how = "" if not verdict else ("  -> faster by more than the spread" if r < 1 - spread else "  -> NOT faster by more than the spread")
+            lines.append(f"  {ours} / {n} = {r:.3f}{how}")
+
+    # ---- (1), (2) the way in ----
+    video = torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    r8, y8 = rows[:chunk].contiguous(), (yx[:chunk].contiguous(), side, side)
+    ours = lambda: ops.frames_from_u8_aligned(video, size, r8, channel_order="bgr")        # noqa: E731
+    contenders = {"frames_from_u8_aligned": ours, "frames_from_u8(crop=(yx, 400, 400))": lambda: ops.frames_from_u8(video, size, crop=y8, channel_order="bgr"),
+                  "torch affine_grid + grid_sample": lambda: torch_aligned_in(video, fwd[:chunk], size), "frames_from_u8_aligned (again)": ours}
+    diff = (ours() - torch_aligned_in(video, fwd[:chunk], size)).abs().mean()
+    table(f"way in: {chunk} x {Hf}x{Wf} BGR -> 256^2, s = {side}/256, angles within +-0.3 rad; mean |ours - torch (not antialiased)| = {float(diff):.4f} "
+           f"on (-1, 1) of random frames", alternate(contenders, args.repeats, device_time), "frames_from_u8_aligned",
+           [("frames_from_u8(crop=(yx, 400, 400))", False), ("torch affine_grid + grid_sample", True)])
+
+    # ---- (3) the way out ----
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    scratch = video.clone()
+    ours = lambda: ops.frames_paste_u8_aligned(x, video, r8, feather=feather, channel_order="bgr", out=video)     # noqa: E731
+    contenders = {"frames_paste_u8_aligned": ours,
+                  "frames_paste_u8(box=(yx, 400, 400))": lambda: ops.frames_paste_u8(x, video, y8, feather=feather, channel_order="bgr", out=video),
+                  "torch affine_grid + grid_sample + blend": lambda: torch_aligned_paste(x, scratch, inv[:chunk], scale[:chunk], feather),
+                  "frames_paste_u8_aligned (again)": ours}
+    a, b = video.clone(), video.clone()
+    ops.frames_paste_u8_aligned(x, a, r8, feather=feather, channel_order="bgr", out=a)
+    torch_aligned_paste(x, b, inv[:chunk], scale[:chunk], feather)
+    d = (a.int() - b.int()).abs()
+    table(f"way out: {chunk} x 256^2 fp32 -> rotated {side}x{side} regions of {Hf}x{Wf} BGR, feather {feather}, in place; bytes that differ from the "
+           f"torch composition by more than 1: {int((d > 1).sum())} of {d.numel()}", alternate(contenders, args.repeats, device_time),
+           "frames_paste_u8_aligned", [("frames_paste_u8(box=(yx, 400, 400))", False), ("torch affine_grid + grid_sample + blend", True)])
+
+    # ---- (4) reenact_video ----
+    m = model.IRFD()
+    sd = IR.irfd_recipe_state_dict()
+    sd.update({"Gd." + k: v for k, v in fill_state_dict(m.Gd.state_dict(), prefix="Gd.").items()})
+    m.load_state_dict(sd, strict=False)
+    m.to(dev).eval()
+    ident = torch.randint(0, 256, (1, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    video = torch.randint(0, 256, (T, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    noises = [torch.randn(T, 1, 4 << (i + 1) // 2, 4 << (i + 1) // 2, generator=g).to(dev) for i in range(13)]
+    kw = dict(size=size, channel_order="bgr", noises=noises, chunk=chunk, paste=True, feather=feather)
+    ours = lambda: m.reenact_video(ident, video, align=rows, **kw)                         # noqa: E731
+    contenders = {"reenact_video(align=, paste=True)": ours, "reenact_video(crop=, paste=True)": lambda: m.reenact_video(ident, video, crop=(yx, side, side), **kw),
+                  "reenact_video(align=, paste=True) (again)": ours}
+    with torch.no_grad():
+        for _ in range(args.warmup):
+            for fn in contenders.values():
+                fn()
+        times = alternate(contenders, args.repeats, wall)
+    table(f"T = {T} frames of {Hf}x{Wf} BGR, chunk {chunk}, {args.repeats} alternating rounds after {args.warmup} warm-up rounds (wall, synchronised):",
+           times, "reenact_video(align=, paste=True)", [("reenact_video(crop=, paste=True)", False)])
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -291,9 +427,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--paste", action="store_true", help="the full-frame way out: frames_paste_u8 and reenact_video(paste=True)")
     ap.add_argument("--nv12", action="store_true", help="the NV12 form of the edge: its kernels and reenact_video(pixel_format='nv12', paste=True)")
+    ap.add_argument("--align", action="store_true", help="the aligned edge: frames_from_u8_aligned, frames_paste_u8_aligned, reenact_video(align=)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.align:
+        lines = [f"bench_frame_io --align: {torch.cuda.get_device_name(0)}, fp32"]
+        bench_align(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "align_bench.txt"))
     if args.nv12:
         lines = [f"bench_frame_io --nv12: {torch.cuda.get_device_name(0)}, fp32, HBM time at {HBM / 1e12:.1f} TB/s"]
         bench_nv12(args, lines)

@@ -775,6 +775,43 @@ int spk_frames_u8_to_f32_sim(const uint8_t* src, int64_t image_stride, int64_t r
 int spk_frames_paste_u8_sim(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W,
                             const float* sim_dev, int swap_rb, double feather, float lo, float k, void* stream);
 
+/* ---- landmarks to the rows of the aligned edge, on the device: similarity fit and smoothing (csrc/landmark_sim.hip) ---------------
+ * A landmark network leaves POINTS on the device; the two entry points above take ROWS.  These two make the rows where the points
+ * are: plain device pointers and a stream, no allocation, no synchronisation, no device value read on the host.
+ *
+ * spk_sim_fit_landmarks: pts_dev fp32 [N][K][2], landmark k of frame n as (x, y) in frame coordinates (the centre of pixel
+ *   (ix, iy) is (ix + 0.5, iy + 0.5)); `offset` is added to both coordinates in fp64 (a tracker that reports pixel indices passes
+ *   0.5).  tmpl_dev fp32 [K][2]: the same landmarks as (u, v) in network-image coordinates.  weights_dev fp32 or NULL: landmark k
+ *   of frame n has weight weights_dev[n * weight_stride + k]; weight_stride = 0: one set of K weights for all frames; NULL: every
+ *   weight is 1.  Everything is promoted to fp64.  A landmark TAKES PART when its weight is finite and > 0 and its x, y are
+ *   finite.  Over the participants, in two passes (the second is centred):
+ *     W = sum w,   um = sum w u / W,   vm = sum w v / W,   xm = sum w x / W,   ym = sum w y / W
+ *     du = u - um,  dv = v - vm,  dx = x - xm,  dy = y - ym
+ *     D = sum w (du^2 + dv^2),   a = sum w (du dx + dv dy) / D,   c = sum w (du dy - dv dx) / D
+ *     tx = xm - (a um - c vm),   ty = ym - (c um + a vm)
+ *   -- the weighted least-squares similarity without reflection: it minimises sum w |sim(u, v) - (x, y)|^2 for the transform of
+ *   the section above.  sim_dev fp32 [N][4] receives (a, c, tx, ty) rounded to fp32.  With fewer than 2 participants, when D > 0
+ *   does not hold, or when one of the four fp32 numbers is not finite, the row is four NaNs: an INVALID row to both entry points
+ *   above (the way in writes shift_c, the paste leaves the frame alone), so a tracker drop-out needs no host branch.  A scale
+ *   outside [1/16, 16] is stored as computed; the consumers refuse it by their own rule.  A wave per frame, lanes striding over k,
+ *   fp64 partial sums per lane and a butterfly over the 64 lanes: a frame's row depends on its own landmarks only -- the same
+ *   frame alone and in a batch gives the same bits.
+ *   Refused: null pts / tmpl / sim, N < 1, K < 2, K > 4096, weight_stride < 0 or in (0, K), an offset that is not finite.
+ * spk_sim_smooth: sim_in_dev, sim_out_dev fp32 [N][4], two ranges that do not overlap.  A row TAKES PART when its four numbers
+ *   are finite.  With g(d) = exp(-d^2 / (2 sigma^2)):
+ *     out[n] = (float) ( sum_d g(d) in[n + d] / sum_d g(d) )     d = -radius ... radius in that order, 0 <= n + d < N,
+ *                                                                 in[n + d] takes part; fp64
+ *   and four NaNs when no row of the window takes part: a gap of up to `radius` frames is bridged from its neighbours.  Averaging
+ *   rows is averaging the maps -- the result sends every network point to the weighted mean of where the neighbouring frames send
+ *   it -- so it is again a similarity.  radius = 0 copies the rows that take part bit for bit; a row with any number that is not
+ *   finite becomes four NaNs.  A thread per frame.
+ *   Refused: null pointers, N < 1, radius outside [0, 64], sigma not finite or <= 0, overlapping ranges.
+ * Both refuse bad arguments before any launch (SPK_EINVAL, spk_last_error).  replaces: a device -> host copy of the landmarks, a
+ *   numpy / cv2.estimateAffinePartial2D fit per frame and an upload, in the middle of decode -> crop -> network -> paste -> encode. */
+int spk_sim_fit_landmarks(const float* pts_dev, const float* weights_dev, int64_t weight_stride, const float* tmpl_dev, int N, int K,
+                          double offset, float* sim_dev, void* stream);
+int spk_sim_smooth(const float* sim_in_dev, int N, int radius, double sigma, float* sim_out_dev, void* stream);
+
 /* ---- the video-frame edge in NV12 form (csrc/frame_nv12.hip) ---------------------------------------------------------------------
  * What a hardware decoder or encoder holds in device memory, in and out of the network without a packed-RGB detour.
  *

@@ -1,7 +1,7 @@
 """The video-frame edge of the inference path: uint8 frames as a video decoder / writer holds them on the device, in and out of the
 network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packed RGB through a similarity transform per frame
-(csrc/frame_sim.hip: aligned crops).  ``ops`` re-exports the launchers (``ops.frames_from_u8``
-...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
+(csrc/frame_sim.hip: aligned crops), whose rows csrc/landmark_sim.hip fits to landmarks and smooths.  ``ops`` re-exports the
+launchers (``ops.frames_from_u8`` ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
 from __future__ import annotations
 
 import ctypes as C
@@ -404,6 +404,141 @@ def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1)
     return out
 
 
+# ---- landmarks to rows on the device: similarity fit and smoothing (csrc/landmark_sim.hip; the definitions are in include/spk.h) --
+LANDMARKS_MAX, SMOOTH_RADIUS_MAX = 4096, 64                               # K and radius as the entry points bound them
+
+
+def _check_fit(landmarks, template, weights, offset, what):
+    """What the fit checks on the host, before a device is touched: -> ``(template, weights, offset)``, host forms rounded to
+    float32 CPU tensors still to be uploaded, device forms as they came (not read)."""
+    if not isinstance(landmarks, torch.Tensor) or landmarks.dim() != 3 or landmarks.size(2) != 2 or landmarks.size(0) < 1 or \
+            not 2 <= landmarks.size(1) <= LANDMARKS_MAX:
+        got = tuple(landmarks.shape) if isinstance(landmarks, torch.Tensor) else type(landmarks).__name__
+        raise ValueError(f"{what}: landmarks must be a tensor [N,K,2] with 2 <= K <= {LANDMARKS_MAX}, got {got}")
+    N, K, _ = landmarks.shape
+    if isinstance(template, torch.Tensor) and template.is_cuda:
+        if template.dtype != torch.float32 or tuple(template.shape) != (K, 2):
+            raise ValueError(f"{what}: a device template must be a float32 tensor [{K},2], got {template.dtype} {tuple(template.shape)}")
+    else:
+        try:
+            template = torch.as_tensor(template).to(torch.float64).to(torch.float32)
+        except (ValueError, TypeError, RuntimeError) as e:
+            raise ValueError(f"{what}: template must be [{K},2] points (u, v): {e}") from None
+        if tuple(template.shape) != (K, 2):
+            raise ValueError(f"{what}: template must be [{K},2] points (u, v), one per landmark, got {tuple(template.shape)}")
+        if not bool(torch.isfinite(template).all()):
+            raise ValueError(f"{what}: template must be finite")
+        if bool((template == template[0]).all()):
+            raise ValueError(f"{what}: template needs at least two distinct points (a similarity has no scale otherwise)")
+    if isinstance(weights, torch.Tensor) and weights.is_cuda:
+        if weights.dtype != torch.float32 or tuple(weights.shape) not in ((K,), (N, K)):
+            raise ValueError(f"{what}: device weights must be a float32 tensor [{K}] or [{N},{K}], got {weights.dtype} {tuple(weights.shape)}")
+    elif weights is not None:
+        try:
+            weights = torch.as_tensor(weights).to(torch.float64).to(torch.float32)
+        except (ValueError, TypeError, RuntimeError) as e:
+            raise ValueError(f"{what}: weights must be [{K}] numbers: {e}") from None
+        if tuple(weights.shape) != (K,):
+            raise ValueError(f"{what}: host weights must be [{K}] numbers, one per landmark, got {tuple(weights.shape)}")
+    offset = float(offset)
+    if not (-float("inf") < offset < float("inf")):
+        raise ValueError(f"{what}: offset must be finite, got {offset}")
+    return template, weights, offset
+
+
+def _fit(landmarks, template, weights, offset, what):                    # checked arguments -> device float32 [N,4], one launch
+    if not landmarks.is_cuda or landmarks.dtype != torch.float32:
+        raise L.SpkError(f"{what}: landmarks: expected a float32 HIP tensor, got {landmarks.dtype} on {landmarks.device} (no CPU path)")
+    N, K, _ = landmarks.shape
+    landmarks = landmarks.contiguous()
+
+    def there(t, name):                                                   # host forms: uploaded once; device forms: where the landmarks are
+        if t.is_cuda and t.device != landmarks.device:
+            raise L.SpkError(f"{what}: {name} on {t.device}, landmarks on {landmarks.device}")
+        return t.to(landmarks.device).contiguous()
+
+    template, weights = there(template, "template"), None if weights is None else there(weights, "weights")
+    rows = torch.empty((N, 4), device=landmarks.device, dtype=torch.float32)
+    L.check(L.lib().spk_sim_fit_landmarks(landmarks.data_ptr(), _ptr(weights), K if weights is not None and weights.dim() == 2 else 0,
+                                          template.data_ptr(), N, K, offset, rows.data_ptr(), L.stream_ptr()), "spk_sim_fit_landmarks")
+    return rows
+
+
+def similarity_from_landmarks(landmarks, template, *, weights=None, offset=0.0):
+    """Landmarks -> rows ``(a, c, tx, ty)`` where the landmarks are, one launch (``spk_sim_fit_landmarks``): per frame the weighted
+    least-squares similarity without reflection that carries ``template`` onto the frame's landmarks (centred sums in fp64;
+    include/spk.h has them) -- what ``frames_from_u8_aligned`` / ``frames_paste_u8_aligned`` / ``reenact_video(align=)`` take, with
+    no copy to the host.  ``landmarks``: a device float32 ``[N,K,2]`` tensor of ``(x, y)`` in frame coordinates (the centre of pixel
+    ``(ix, iy)`` is ``(ix + 0.5, iy + 0.5)``; ``offset`` is added to both: 0.5 for a tracker that reports pixel indices), made
+    contiguous if it is not.  ``template``: the same ``K`` landmarks as ``(u, v)`` in the network image -- a host sequence / CPU
+    tensor ``[K,2]``, checked (finite, at least two distinct points, else ``ValueError``) and uploaded, or a device float32 tensor,
+    not read.  ``weights``: None (all 1); a host sequence / CPU tensor ``[K]``, uploaded; or a device float32 ``[K]`` (one set for
+    all frames) or ``[N,K]``, e.g. a tracker's confidences.  A landmark takes part when its weight is finite and > 0 and its
+    coordinates are finite; a frame with fewer than two participants, or whose participants share one template point, gives four
+    NaNs -- an invalid row, which the way in answers with ``-mean / std`` and the paste by leaving the frame alone.
+    -> device float32 ``[N,4]``."""
+    what = "similarity_from_landmarks"
+    return _fit(landmarks, *_check_fit(landmarks, template, weights, offset, what), what)
+
+
+def _check_smooth(radius, sigma, what):
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= SMOOTH_RADIUS_MAX:
+        raise ValueError(f"{what}: radius must be an integer in [0, {SMOOTH_RADIUS_MAX}], got {radius!r}")
+    sigma = max(radius, 1) / 2.0 if sigma is None else float(sigma)
+    if not (0.0 < sigma < float("inf")):
+        raise ValueError(f"{what}: sigma must be a finite number > 0, got {sigma}")
+    return radius, sigma
+
+
+def smooth_similarity_rows(rows, radius, sigma=None):
+    """Rows smoothed over time, one launch (``spk_sim_smooth``): row ``n`` becomes the mean of rows ``n - radius ... n + radius``
+    with weights ``exp(-d^2 / (2 sigma^2))`` (``sigma=None``: ``max(radius, 1) / 2``), in fp64 -- the raw per-frame fits jitter by a
+    fraction of a pixel, which shows as a pasted face swimming in its frame.  Averaging rows averages the maps, so the result is
+    again a similarity.  Rows that are not finite (a tracker drop-out) and rows beyond the clip's ends take no part, so a gap of up
+    to ``radius`` frames is BRIDGED from its neighbours; a window without a finite row gives four NaNs.  A caller who wants
+    drop-outs to stay drop-outs smooths with ``radius=0`` (a copy of the finite rows) or masks afterwards.  ``rows``: a device
+    float32 ``[N,4]`` tensor, or a host sequence / CPU tensor, uploaded unchecked (NaN rows are legal here).  -> a new device
+    float32 ``[N,4]``."""
+    what = "smooth_similarity_rows"
+    radius, sigma = _check_smooth(radius, sigma, what)
+    if not (isinstance(rows, torch.Tensor) and rows.is_cuda):
+        try:
+            rows = torch.as_tensor(rows).to(torch.float64).to(torch.float32)
+        except (ValueError, TypeError, RuntimeError) as e:
+            raise ValueError(f"{what}: rows must be [N,4] rows of (a, c, tx, ty): {e}") from None
+    if rows.dtype != torch.float32 or rows.dim() != 2 or rows.size(1) != 4 or rows.size(0) < 1:
+        raise ValueError(f"{what}: rows must be a float32 [N,4] tensor, got {rows.dtype} {tuple(rows.shape)}")
+    if not rows.is_cuda:
+        if not torch.cuda.is_available():
+            raise L.SpkError(f"{what}: no HIP device to upload the rows to (no CPU path)")
+        rows = rows.to("cuda")
+    rows = rows.contiguous()
+    out = torch.empty_like(rows)
+    L.check(L.lib().spk_sim_smooth(rows.data_ptr(), rows.size(0), radius, sigma, out.data_ptr(), L.stream_ptr()), "spk_sim_smooth")
+    return out
+
+
+class LandmarkAlign:
+    """``IRFD.reenact_video(align=...)`` / ``(identity_align=...)`` from landmarks: what ``similarity_from_landmarks`` takes, kept
+    until the call knows its frames.  ``rows(T)`` is one fit launch, plus one ``smooth_similarity_rows(rows, smooth, sigma)`` launch
+    when ``smooth > 0`` -- once per clip, so the smoothing sees every frame and the result does not depend on ``chunk``.  The host
+    arguments are checked here (``ValueError``), the device ones when the rows are made.  ``template`` is in the coordinates of the
+    ``size`` network image the call is made with: no rescaling to another ``size`` is offered."""
+
+    def __init__(self, landmarks, template, *, weights=None, offset=0.0, smooth=0, sigma=None):
+        what = "LandmarkAlign"
+        self.landmarks = landmarks
+        self.template, self.weights, self.offset = _check_fit(landmarks, template, weights, offset, what)
+        self.smooth, self.sigma = _check_smooth(smooth, sigma, f"{what}: smooth")
+
+    def rows(self, T, what="LandmarkAlign"):
+        """The rows of ``T`` frames -> device float32 ``[T,4]``"""
+        if self.landmarks.size(0) != T:
+            raise ValueError(f"{what}: landmarks of {self.landmarks.size(0)} frames for {T} frames")
+        rows = _fit(self.landmarks, self.template, self.weights, self.offset, what)
+        return smooth_similarity_rows(rows, self.smooth, self.sigma) if self.smooth > 0 else rows
+
+
 # ---- NV12 (csrc/frame_nv12.hip; the definitions are in include/spk.h) ---------------------------------------------------------------
 def yuv_standard(standard, full_range):
     if standard not in ("bt601", "bt709"):
@@ -564,8 +699,8 @@ class Aligned:
         self.rows, self.size, self._generated = rows, size, {}
 
     @classmethod
-    def parse(cls, sim, T, size, device):                                 # host rows: checked here, uploaded once for both edges
-        rows = parse_sim(sim, T, "reenact_video: align")
+    def parse(cls, sim, T, size, device, what="reenact_video: align"):    # host rows: checked here, uploaded once for both edges
+        rows = sim.rows(T, what) if isinstance(sim, LandmarkAlign) else parse_sim(sim, T, what)      # landmarks: fitted once per clip
         if not rows.is_cuda and device.type == "cuda":
             rows = rows.to(device)
         return cls(rows, _out_size(size, "reenact_video"))

@@ -167,11 +167,11 @@ class IRFD(nn.Module):
     @torch.no_grad()
     def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8,
                       seed=None, noise="fresh", frame0=0, paste=False, feather=0, inplace=False, pixel_format="rgb24", standard="bt601",
-                      full_range=False, align=None):
+                      full_range=False, align=None, identity_align=None):
         """``reenact`` from and to video frames as a decoder and a video writer hold them (inference.py:29-33,46-58,78-86):
         uint8 HWC frames of any size on the device in, uint8 [T,R,R,3] out, both in ``channel_order`` ("bgr": ``cv2``'s).
         Nothing but ``ops.frames_from_u8`` -> ``reenact(output="uint8")``: ``identity_u8`` [H,W,3] or [1,H,W,3] is resized whole
-        to ``size``; ``pose_u8`` / ``emotion_u8`` [T,H,W,3] are cropped to ``crop`` and resized; ``emotion_u8=None``: the pose
+        to ``size`` (``identity_align`` below: cropped); ``pose_u8`` / ``emotion_u8`` [T,H,W,3] are cropped to ``crop`` and resized; ``emotion_u8=None``: the pose
         frames, resized once.  ``crop``: ``(y0, x0, h, w)``, one box for all frames; a host sequence / CPU integer tensor
         ``[T,4]``, a tracker's box per frame, all of one size (``align=`` below: any size and angle per frame); or
         ``(boxes_yx, h, w)`` with a device int32 ``[T,2]`` tensor of origins (``ops.frames_from_u8``).  ``seed`` / ``noise`` / ``frame0``: as ``reenact``.
@@ -191,13 +191,20 @@ class IRFD(nn.Module):
 
         ``align=sim`` (instead of ``crop``; both: ``ValueError``): an aligned crop per frame -- rows ``(a, c, tx, ty)`` of the
         similarity transform that maps the ``size`` network image into frame ``t`` (``ops.similarity_rows``; include/spk.h), any
-        scale and angle per frame, as a landmark tracker fits them: a host sequence / CPU tensor ``[T,4]``, checked on the host
-        and uploaded once, or a device float32 ``[T,4]`` tensor, not read on the host.  ``pose_u8`` / ``emotion_u8`` go through
+        scale and angle per frame, as ``ops.similarity_from_landmarks`` fits them to a tracker's landmarks: a host sequence / CPU
+        tensor ``[T,4]``, checked on the host and uploaded once; a device float32 ``[T,4]`` tensor, not read on the host; or an
+        ``ops.LandmarkAlign`` -- the landmarks themselves, fitted (and smoothed over the whole clip) on the device once per call,
+        before the chunk loop; the pose and the emotion frames share the rows.  ``pose_u8`` / ``emotion_u8`` go through
         ``ops.frames_from_u8_aligned``; with ``paste=True`` each chunk's fp32 result goes through ``ops.frames_paste_u8_aligned``
         into its slice, one ``spk_frames_paste_u8_sim`` launch per chunk, rows taken per frame, so the result does not depend on
         ``chunk``.  The generated image has ``R`` pixels where the network image has ``size``: the paste uses the rows with
         ``(a, c)`` scaled by ``size / R`` in fp32.  Packed RGB only: ``align`` with ``pixel_format="nv12"`` raises ``ValueError``
-        (NV12 frames take crop boxes)."""
+        (NV12 frames take crop boxes).
+
+        ``identity_align``: the identity photo through an aligned crop as well, so that ``Ei`` sees a face framed as ``Ee`` / ``Ep``
+        see theirs -- one row in either form above (``[1,4]``; host rows are checked before any launch) or an ``ops.LandmarkAlign``
+        over one frame; the photo then goes through ``ops.frames_from_u8_aligned`` instead of being resized whole.  The photo is
+        packed in both pixel formats, so this works with both.  ``None``: resized whole, as ever."""
         if pixel_format not in FR.PIXEL_FORMATS:
             raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
         if pixel_format == "rgb24" and (standard != "bt601" or full_range):
@@ -215,6 +222,8 @@ class IRFD(nn.Module):
         if align is not None and pixel_format != "rgb24":
             raise ValueError("reenact_video: align applies to pixel_format='rgb24' only (NV12 frames take crop boxes)")
         fmt = FR.PIXEL_FORMATS[pixel_format](channel_order, standard, full_range)
+        if identity_align is not None:                                     # host rows: checked here, before any launch
+            identity_align = FR.Aligned.parse(identity_align, 1, size, identity_u8.device, "reenact_video: identity_align")
         pose_in = pose_u8
         if align is not None:                                              # the transforms stand where a box would: checked / uploaded once
             pose_in, device, T, H, W = fmt.open(pose_u8, inplace)
@@ -225,7 +234,10 @@ class IRFD(nn.Module):
             if not isinstance(origins, tuple) and not origins.is_cuda and device.type == "cuda":
                 origins = origins.to(device)                               # host boxes: checked above, uploaded once for both edges
             crop = (*origins, h, w) if isinstance(origins, tuple) else (origins, h, w)
-        ident = FR.frames_from_u8(identity_u8, size, channel_order=channel_order)
+        if identity_align is None:
+            ident = FR.frames_from_u8(identity_u8, size, channel_order=channel_order)
+        else:
+            ident = FR.frames_from_u8_aligned(identity_u8, size, identity_align.rows, channel_order=channel_order)
         pose = fmt.network_input(pose_in, size, crop)
         emo = None if emotion_u8 is None else fmt.network_input(emotion_u8, size, crop)
         if not paste:

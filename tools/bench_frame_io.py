@@ -31,7 +31,14 @@
     ``IRFD.reenact_video(align=, paste=True)`` beside ``reenact_video(crop=, paste=True)``.  The contenders alternate in one process,
     medians are compared, and the aligned launcher runs twice per round: the distance of its two medians is the recorded spread.
 
-    python tools/bench_frame_io.py [--paste | --nv12 | --align] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
+``--landmarks``: landmarks -> rows on the device (csrc/landmark_sim.hip): T = 64 and 1024 frames, K = 5 and 68 landmarks.
+    ``ops.similarity_from_landmarks`` and ``ops.smooth_similarity_rows(radius 2)``, each alone and both together (HIP events), and
+    the two launches beside the host route they replace -- ``.cpu()``, the numpy fit and smoothing of tests/landmark_ref.py (a
+    Python loop over the frames), ``.to(device)`` -- and beside the two copies of that route alone, the floor of any host fit, as wall
+    time with a synchronise on both sides; the contenders alternate, medians are compared, and the device route runs twice per round
+    for the spread.
+
+    python tools/bench_frame_io.py [--paste | --nv12 | --align | --landmarks] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
 import math
@@ -397,6 +404,48 @@ def bench_align(args, lines):
            times, "reenact_video(align=, paste=True)", [("reenact_video(crop=, paste=True)", False)])
 
 
+def bench_landmarks(args, lines):
+    """``--landmarks``: the fit and the smoothing launch beside a copy to the host, numpy and a copy back."""
+    import importlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import landmark_ref as R
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    radius, sigma = 2, 1.0
+    for T in (64, 1024):
+        for K in (5, 68):
+            c = R.case(K, T, bad=False)
+            lm, tmpl = torch.from_numpy(c["pts"]).to(dev), torch.from_numpy(c["tmpl"]).to(dev)
+            tmpl_host = c["tmpl"]
+            rows = ops.similarity_from_landmarks(lm, tmpl)
+
+            def device_route():
+                return ops.smooth_similarity_rows(ops.similarity_from_landmarks(lm, tmpl), radius, sigma)
+
+            def host_route():
+                return torch.from_numpy(R.smooth(R.fit(lm.cpu().numpy(), tmpl_host), radius, sigma)).to(dev)
+
+            def copies_only():                                             # the floor of any host fit: down, and rows back up
+                lm.cpu()
+                return rows_host.to(dev)
+
+            rows_host = rows.cpu()
+            ratio = R.compare(device_route().cpu().numpy(), R.smooth(rows.cpu().numpy(), radius, sigma))
+            ev = alternate({"fit": lambda: ops.similarity_from_landmarks(lm, tmpl), "smooth": lambda: ops.smooth_similarity_rows(rows, radius, sigma),
+                            "fit + smooth": device_route}, args.repeats, device_time)
+            times = alternate({"device": device_route, "host": host_route, "host, copies only": copies_only, "device (again)": device_route}, args.repeats, wall)
+            med = {n: statistics.median(ts) for n, ts in {**ev, **times}.items()}
+            spread = abs(med["device"] - med["device (again)"]) / min(med["device"], med["device (again)"])
+            lines.append(f"T = {T:4d} frames, K = {K:2d} landmarks, smoothing radius {radius} (largest |device - model| / bound = {ratio:.3f}):")
+            lines.append(f"  HIP events, launcher included, median of {args.repeats} rounds of 20: similarity_from_landmarks {med['fit'] * 1e6:7.1f} us, "
+                         f"smooth_similarity_rows {med['smooth'] * 1e6:7.1f} us, both {med['fit + smooth'] * 1e6:7.1f} us")
+            for n, ts in times.items():
+                lines.append(f"  wall, synchronised: {n:17s} median {med[n] * 1e6:10.1f} us  min {ts[0] * 1e6:10.1f}  max {ts[-1] * 1e6:10.1f}")
+            lines.append(f"  spread of the repeated contender: {spread * 100:.2f} %; device / host = {med['device'] / med['host']:.4f}, "
+                         f"device / copies only = {med['device'] / med['host, copies only']:.3f}")
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -428,9 +477,14 @@ def main():
     ap.add_argument("--paste", action="store_true", help="the full-frame way out: frames_paste_u8 and reenact_video(paste=True)")
     ap.add_argument("--nv12", action="store_true", help="the NV12 form of the edge: its kernels and reenact_video(pixel_format='nv12', paste=True)")
     ap.add_argument("--align", action="store_true", help="the aligned edge: frames_from_u8_aligned, frames_paste_u8_aligned, reenact_video(align=)")
+    ap.add_argument("--landmarks", action="store_true", help="landmarks -> rows: similarity_from_landmarks, smooth_similarity_rows, the host route")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.landmarks:
+        lines = [f"bench_frame_io --landmarks: {torch.cuda.get_device_name(0)}"]
+        bench_landmarks(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "landmark_bench.txt"))
     if args.align:
         lines = [f"bench_frame_io --align: {torch.cuda.get_device_name(0)}, fp32"]
         bench_align(args, lines)

@@ -4,6 +4,8 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <mutex>
+#include <set>
 
 #include "../../include/spk.h"
 
@@ -25,6 +27,20 @@ inline int fail(int code, const char* fmt, ...) {
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SPK_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+    return SPK_OK;
+}
+
+// A launch with more than 64 KiB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize raised on its kernel: done
+// once per kernel function, and only for launches that ask for that much.
+inline int raise_dynamic_lds(const void* kernel, size_t lds_bytes) {
+    if (lds_bytes <= 64 * 1024) return SPK_OK;
+    static std::mutex mu;
+    static std::set<const void*> raised;
+    std::lock_guard<std::mutex> lock(mu);
+    if (raised.count(kernel)) return SPK_OK;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
+    raised.insert(kernel);
     return SPK_OK;
 }
 

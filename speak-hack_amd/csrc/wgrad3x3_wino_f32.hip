@@ -26,7 +26,7 @@
 // Epilogue: dg = G^T dU G per (co, ci) in registers, stored into the split's slab [co][tap][ci] -- the layout of the direct weight
 // gradient's slabs, so the SAME fixed-order reduce (spk_wgrad_reduce_slabs) finishes: bitwise reproducible, no float atomics.
 #include "conv_mfma_f32.hpp"
-#include "wgrad_form.hpp"
+#include "wgrad_mfma_f32.hpp"
 
 #include <cstdlib>
 
@@ -434,8 +434,10 @@ int64_t spk_conv2d_wgrad_wino_workspace_bytes(int splits, int B, int Cin, int Co
     return (int64_t)s * Cout * 9 * Cin * 4;
 }
 
-// entered from spk_conv2d_wgrad when desc->flags has SPK_CONV_WINOGRAD
-int spk_conv2d_wgrad_wino(const spk_wgrad_desc* d, void* stream) {
+}  // extern "C"
+
+// every requirement of the Winograd route and its geometry: the plan, and the kernel's own argument block
+static int plan_wino_args(const spk_wgrad_desc* d, spkwg::WgradPlan& p, Args& a) {
     SPK_REQUIRE(d && d->g && d->x && d->dw, "wgrad winograd: null pointer");
     SPK_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 1, "wgrad winograd: 3x3 stride-1 convs only");
     SPK_REQUIRE(!(d->flags & ~(SPK_CONV_WINOGRAD | SPK_CONV_IN_BATCH_SCALE | SPK_CONV_IN_AFFINE_RELU)), "wgrad winograd: plain, batch-scaled or "
@@ -457,7 +459,6 @@ int spk_conv2d_wgrad_wino(const spk_wgrad_desc* d, void* stream) {
     const int64_t need = (int64_t)splits * Cy * 9 * d->Cin * 4;
     SPK_REQUIRE(d->workspace && d->workspace_bytes >= need, "wgrad winograd: workspace too small (%lld < %lld bytes)", (long long)d->workspace_bytes, (long long)need);
     SPK_REQUIRE((reinterpret_cast<uintptr_t>(d->g) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->x) & 15) == 0, "wgrad winograd: 16-byte aligned tensors");
-    Args a;
     a.g = d->g; a.x = d->x; a.slabs = static_cast<float*>(d->workspace);
     a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.g_scale = d->g_scale;
     a.G = G; a.gin = gin; a.Cx = Cx; a.Cy = Cy;
@@ -466,27 +467,43 @@ int spk_conv2d_wgrad_wino(const spk_wgrad_desc* d, void* stream) {
     a.n_chunks = d->B * a.TY * a.TXB;
     a.chunks_per_wg = per_wg;
     a.x_bytes = (unsigned)((long long)d->B * Cx * d->H * d->W * 4 + ((long long)d->W + 4) * 4);
-    dim3 grid((unsigned)splits, (unsigned)(Cy / CO_T), (unsigned)(d->Cin / CI_T));
-    if (spkwg::form_probe) {        // spk_conv2d_wgrad_launch_form: answer instead of launching
-        spkwg::report_form(SPK_WGRAD_WINO, mod ? 2 : (aff ? 1 : 0), 16, 2, 1, 0, 0, a.n_chunks, splits, per_wg, grid, LDS_BYTES,
-                           (size_t)Cy * 9 * d->Cin, (size_t)splits);
-    } else {
-        static bool raised = false;
-        if (!raised) {
-            for (const void* f : {reinterpret_cast<const void*>(&wgrad_wino_kernel<PLAIN>), reinterpret_cast<const void*>(&wgrad_wino_kernel<MODULATED>),
-                                  reinterpret_cast<const void*>(&wgrad_wino_kernel<AFFINE_RELU>)}) {
-                hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-            }
-            raised = true;
-        }
-        if (mod) hipLaunchKernelGGL(wgrad_wino_kernel<MODULATED>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
-        else if (aff) hipLaunchKernelGGL(wgrad_wino_kernel<AFFINE_RELU>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(wgrad_wino_kernel<PLAIN>, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
-        int rc = spk::check_launch("wgrad_wino_kernel");
-        if (rc != SPK_OK) return rc;
-    }
-    return spk_wgrad_reduce_slabs(static_cast<const float*>(d->workspace), d->dw, splits, Cy, d->Cin, 9, d->scale, d->accumulate, fold, stream);
+    p = spkwg::WgradPlan{};
+    p.form = SPK_WGRAD_WINO;
+    p.mode = mod ? spkwg::WG_BATCH_SCALE : (aff ? spkwg::WG_AFFINE_RELU : spkwg::WG_PLAIN);
+    p.kh = p.kw = 3; p.stride = 1;
+    p.TW = 16; p.TH = 2; p.TB = 1;                       // (tiles are the 16 x 2 chunks)
+    p.n_tiles = a.n_chunks; p.splits = splits; p.tiles_per_split = per_wg; p.n_slabs = p.ws_slabs = splits;
+    p.slab_floats = (size_t)Cy * 9 * d->Cin;
+    p.grid = dim3((unsigned)splits, (unsigned)(Cy / CO_T), (unsigned)(d->Cin / CI_T));
+    p.lds_bytes = LDS_BYTES;
+    p.fold = fold; p.taps = 9; p.red_cout = Cy; p.red_cin = d->Cin; p.accumulate = d->accumulate ? 1 : 0; p.scale = d->scale; p.dw = d->dw;
+    p.reducer = spkwg::pick_reducer(a.slabs, d->dw, splits, p.slab_floats, d->Cin, fold);
+    return SPK_OK;
+}
+
+int spkwg::plan_wino(const spk_wgrad_desc* d, WgradPlan& p) {
+    Args a;
+    return plan_wino_args(d, p, a);
+}
+
+extern "C" {
+
+// entered from spk_conv2d_wgrad when desc->flags has SPK_CONV_WINOGRAD
+int spk_conv2d_wgrad_wino(const spk_wgrad_desc* d, void* stream) {
+    spkwg::WgradPlan p;
+    Args a;
+    int rc = plan_wino_args(d, p, a);
+    if (rc != SPK_OK) return rc;
+    const void* kern = p.mode == spkwg::WG_BATCH_SCALE ? reinterpret_cast<const void*>(&wgrad_wino_kernel<MODULATED>)
+                     : p.mode == spkwg::WG_AFFINE_RELU ? reinterpret_cast<const void*>(&wgrad_wino_kernel<AFFINE_RELU>)
+                                                       : reinterpret_cast<const void*>(&wgrad_wino_kernel<PLAIN>);
+    rc = spk::raise_dynamic_lds(kern, p.lds_bytes);
+    if (rc != SPK_OK) return rc;
+    void* argv[1] = {&a};
+    (void)hipLaunchKernel(kern, p.grid, dim3(NT), argv, p.lds_bytes, (hipStream_t)stream);
+    rc = spk::check_launch("wgrad_wino_kernel");
+    if (rc != SPK_OK) return rc;
+    return spk_wgrad_reduce_slabs(a.slabs, d->dw, p.n_slabs, p.red_cout, p.red_cin, p.taps, d->scale, d->accumulate, p.fold, stream);
 }
 
 }  // extern "C"

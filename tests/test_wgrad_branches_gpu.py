@@ -10,8 +10,8 @@ second identical launch must reproduce dw bit for bit.
 The bound is measured on the reference, never on the kernel: per case max(4 x the error of the same chain in fp32 on the CPU,
 sqrt(B H W) 2^-24); a single element: |dw - ref| <= 8 x bound x rms(ref).  Which kernel, geometry and reducer each case reaches is
 asserted without a GPU in tests/test_wgrad_forms_cpu.py, which also seeds the faults these checks exist for into the reference
-(each lands >= 10 x over a limit).  Scope: the shipped dispatch (SPK_WGRAD_WIDE_SB=1 and the *_LAB builds are opt-in and stay out);
-the test fails, not skips, if one of wgrad_cases.ENV_SWITCHES is set.
+(each lands >= 10 x over a limit).  Scope: the shipped dispatch; the test fails, not skips, if one of wgrad_cases.ENV_SWITCHES
+is set.
 
 The reducers: with scale = 1 and accumulate = 0 the device result equals the NumPy float32 emulation of the documented order bit
 for bit (the dword and the vec form give the same bits on one input); with scale or accumulate it is held to the fp64 sum within

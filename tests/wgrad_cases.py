@@ -11,8 +11,8 @@ then fold, scale and accumulate.  The bound is measured on the reference, never 
 max(4 x rel-L2(fp32 chain, fp64 chain), sqrt(B H W) 2^-24) -- the rule of tests/direct_conv_cases.py with this operator's reduction
 length; a single element: |dw - ref| <= MAX_FACTOR x bound x rms(ref).
 
-Scope: the shipped dispatch.  The single-buffer wide form (SPK_WGRAD_WIDE_SB=1) and the *_LAB builds are opt-in and stay out; the
-switches the library reads once per process (ENV_SWITCHES) are assumed unset, and ``require_default_dispatch`` fails if one is set."""
+Scope: the shipped dispatch: the switches the library reads once per process (ENV_SWITCHES) are assumed unset, and
+``require_default_dispatch`` fails if one is set."""
 import functools
 import math
 import os
@@ -25,8 +25,7 @@ from oracle.weights_recipe import recipe_input, recipe_tensor
 TOL_OP = 2e-5                   # the aggregate rel-L2 of tests/test_backward_gpu.py: no case's bound may exceed it
 MAX_FACTOR = 8.0                # as tests/bf16x3_emulation.py
 GUARD = 64                      # NaN floats on either side of dw and behind the workspace
-ENV_SWITCHES = ("SPK_WGRAD_WIDE", "SPK_WGRAD_S2", "SPK_WGRAD_PIPE", "SPK_WGRAD_FIXED", "SPK_WGRAD1X1_DMA", "SPK_WGRAD_STEM", "SPK_WGRAD_WIDE_SB",
-                "SPK_WGRAD_WIDE_TARGET", "SPK_WGRAD_WIDE_SB_TARGET", "SPK_WGRAD_S2_TARGET", "SPK_WGRAD_WINO_WGS")
+ENV_SWITCHES = ("SPK_WGRAD_WIDE", "SPK_WGRAD_S2", "SPK_WGRAD_PIPE", "SPK_WGRAD_FIXED", "SPK_WGRAD1X1_DMA", "SPK_WGRAD_STEM", "SPK_WGRAD_WINO_WGS")
 KERNELS = ("tap", "tap_fixed", "pipe", "wide16", "wide8", "s2_16", "s2_8", "up", "gemm1x1", "gemm1x1_dma", "stem", "wino")     # SPK_WGRAD_*
 MODES = ("plain", "affine", "bscale")
 REDUCERS = ("dword", "vec", "deep")

@@ -775,6 +775,59 @@ int spk_frames_u8_to_f32_sim(const uint8_t* src, int64_t image_stride, int64_t r
 int spk_frames_paste_u8_sim(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W,
                             const float* sim_dev, int swap_rb, double feather, float lo, float k, void* stream);
 
+/* ---- seamless paste-back for aligned crops: face matte and colour match (csrc/frame_blend.hip) ------------------------------------
+ * spk_frames_paste_u8_sim blends the whole generated square with a rectangular ramp: the generator's own background is pasted
+ * over the real one, and the decoder's tone is not the camera's.  These entry points add what every face pipeline adds: an alpha
+ * MATTE in generated-image coordinates (the face sits at the same place in every aligned crop, so one static matte serves a clip;
+ * a per-frame matte of a segmentation network drops in), and a per-channel COLOUR MATCH of the generated face to the pixels it
+ * replaces, whose statistics are sums over exactly the pixels the paste visits.
+ *
+ * THE PER-PIXEL QUANTITIES.  For a region pixel (Y, X) of frame n: (u, v), r, w_u, w_v, val, q, b, a_u and a_v are exactly those of
+ * spk_frames_paste_u8_sim above (q: fp32, not rounded, of network channel c; b: the background byte at c' = swap_rb ? 2 - c : c).
+ * In addition
+ *     Mt = clamp01( sum_j sum_i w_v[j] w_u[i] matte[f,j,i] / (sum w_u  sum w_v) )      fp64 sums, the same (j, i) order as val
+ *     m  = a_u a_v Mt                                                                  fp64
+ *   matte_dev: fp32 [matte_frames][Hs][Ws], contiguous; f = n when matte_frames == N, f = 0 when matte_frames == 1.  A NaN matte
+ *   sample counts as 0, so clamp01(NaN) = 0.  matte_dev == NULL means Mt = 1 (then matte_frames must be 0).  Both kernels take
+ *   these quantities from one device function.
+ *
+ * spk_frames_paste_u8_sim_blend: the arguments of spk_frames_paste_u8_sim, then the matte and colour_dev, fp32 [N][3][2] rows
+ *   (g, o) per network channel c, or NULL.  One launch, no allocation, no synchronisation; in place and untouched bytes as
+ *   spk_frames_paste_u8_sim (every byte outside the region is left alone, a thread reads the one background byte it overwrites).
+ *     (g, o) = colour[n,c] if both are finite, else (1, 0);  colour_dev == NULL: no step, q' = q
+ *     q'  = min(max(fmaf(g, q, o), 0), 255)                                            fp32
+ *     dst[n,Y,X,c'] = (uint8) rint(fma(m, q' - b, b))                                  fp64, ties to even
+ *   With matte_dev == NULL and colour_dev == NULL the result is spk_frames_paste_u8_sim's bit for bit.
+ *   Refused: what spk_frames_paste_u8_sim refuses; matte_frames other than 1 or N with a matte, other than 0 without one.
+ * spk_paste_colour_match_sim: the rows (g, o) that carry the weighted mean and standard deviation of the generated face onto those
+ *   of the background under it.  The same leading arguments, but dst is const: it reads the background and writes no frame.
+ *   colour_out_dev fp32 [N][3][2].  Over the region pixels of frame n, q promoted to fp64:
+ *     S0 = sum m,   Sq_c = sum m q,   Sqq_c = sum m q^2,   Sb_c = sum m b,   Sbb_c = sum m b^2        13 fp64 sums per frame
+ *     mu_q = Sq / S0,   var_q = max(Sqq / S0 - mu_q^2, 0)       (mu_b, var_b likewise)
+ *     g = 1                                                    if var_q <= min_sigma^2
+ *     g = clamp(sqrt(var_b / var_q), 1 / max_gain, max_gain)   otherwise
+ *     o = mu_b - g mu_q
+ *     row = ((float) g, (float) o)                             each rounded once, o computed from the unrounded g
+ *     row = (1, 0)                                             when the sim row is invalid or S0 <= min_weight
+ *   DETERMINISM is part of the contract: a fixed number of workgroups per frame (the paste's) each reduce their 13 sums in a fixed
+ *   order -- per thread, across the wave, across the waves through LDS -- and store one partial in workspace[n][g][13]; a second
+ *   small kernel adds a frame's partials in index order and writes the row.  No fp64 atomics on global memory: two calls on the
+ *   same inputs give the same bits.  Two launches, no allocation, no synchronisation.
+ *   workspace_dev: at least spk_paste_colour_match_workspace_bytes(N) bytes (-1 for N < 1), 8-byte aligned; its contents need no
+ *   initialisation and mean nothing afterwards.
+ *   Refused: what the paste refuses; null colour_out_dev; max_gain < 1, min_sigma < 0, min_weight < 0 or any of them not finite;
+ *   a workspace that is null, misaligned or too small.
+ * All refuse bad arguments before any launch (SPK_EINVAL, spk_last_error).  replaces: grid_sample of a mask + masked mean / std in
+ *   ATen + blend on fp32 copies of full frames, which is what a caller has without them. */
+int spk_frames_paste_u8_sim_blend(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W,
+                                  const float* sim_dev, int swap_rb, double feather, float lo, float k, const float* matte_dev, int matte_frames,
+                                  const float* colour_dev, void* stream);
+int64_t spk_paste_colour_match_workspace_bytes(int N);
+int spk_paste_colour_match_sim(const float* src, int N, int Hs, int Ws, const uint8_t* dst, int64_t image_stride, int64_t row_stride, int H,
+                               int W, const float* sim_dev, int swap_rb, double feather, float lo, float k, const float* matte_dev,
+                               int matte_frames, double max_gain, double min_sigma, double min_weight, float* colour_out_dev,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- landmarks to the rows of the aligned edge, on the device: similarity fit and smoothing (csrc/landmark_sim.hip) ---------------
  * A landmark network leaves POINTS on the device; the two entry points above take ROWS.  These two make the rows where the points
  * are: plain device pointers and a stream, no allocation, no synchronisation, no device value read on the host.

@@ -330,6 +330,13 @@ _PROTOTYPES = {
                                            C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
     "spk_frames_paste_u8_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                           C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p]),
+    "spk_frames_paste_u8_sim_blend": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p]),
+    "spk_paste_colour_match_workspace_bytes": (C.c_int64, [C.c_int]),
+    "spk_paste_colour_match_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_double,
+                                             C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spk_sim_fit_landmarks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "spk_sim_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "spk_yuv_coeffs": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

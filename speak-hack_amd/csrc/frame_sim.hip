@@ -9,35 +9,13 @@
 // A row that is not finite or whose s is outside [1/16, 16] is INVALID: the way in writes shift_c, the way out leaves the frame
 // alone.  The bound keeps every footprint, and with it every thread's loop, finite whatever a tracker wrote.  Coordinates are
 // clamped in fp64 BEFORE they become integers, so a wild but finite tx cannot overflow an index.
-#include "frame_common.hpp"
+#include "frame_sim_common.hpp"
 
 namespace {
 
 using namespace spk::frame;
 
-constexpr double S_MIN = 1.0 / 16.0, S_MAX = 16.0;
 constexpr int TILE = 8;                 // a wave of the way in covers a TILE x TILE block of outputs: neighbouring footprints overlap
-constexpr int PASTE_WGS = 64;           // workgroups per frame of the way out (the host cannot see a device row's region)
-
-struct Sim { double a, c, tx, ty, s; bool valid; };
-
-__device__ __forceinline__ Sim load_sim(const float* __restrict__ sim, long long n) {
-    Sim m;
-    m.a = (double)sim[4 * n], m.c = (double)sim[4 * n + 1], m.tx = (double)sim[4 * n + 2], m.ty = (double)sim[4 * n + 3];
-    m.s = sqrt(m.a * m.a + m.c * m.c);
-    m.valid = isfinite(m.a) && isfinite(m.c) && isfinite(m.tx) && isfinite(m.ty) && m.s >= S_MIN && m.s <= S_MAX;
-    return m;
-}
-
-__device__ __forceinline__ double tri(double t) { return fmax(0.0, 1.0 - fabs(t)); }
-
-// The integers i with v_lo <= i <= v_hi, cut to [0, n): first = ceil(v_lo) and last = floor(v_hi) are clamped while still
-// doubles and only then become ints, so no value overflows; an empty range has first > last.  The callers' bounds are where a
-// triangle reaches zero, so an integer a rounding leaves out had a weight of the size of that rounding.
-__device__ __forceinline__ void int_range(double v_lo, double v_hi, int n, int& first, int& last) {
-    first = (int)fmin(fmax(ceil(v_lo), 0.0), (double)n);
-    last = (int)fmin(fmax(floor(v_hi), -1.0), (double)(n - 1));
-}
 
 // The way in.  Lane l of a wave owns output (8 ty + (l >> 3), 8 tx + (l & 7)) of tile (ty, tx) of one frame, all three channels.
 // Its footprint is the square |e_u|, |e_v| < S = max(s, 1) around p = sim(ox + 0.5, oy + 0.5), rotated with the crop: it walks the
@@ -114,15 +92,8 @@ __global__ __launch_bounds__(256) void frames_paste_u8_sim_kernel(const float* _
     for (long long n = blockIdx.y; n < N; n += gridDim.y) {
         const Sim m = load_sim(sim, n);
         if (!m.valid) continue;
-        // the corners of the region in the frame
-        const double cx[4] = {m.tx, m.a * Ws + m.tx, -m.c * Hs + m.tx, m.a * Ws - m.c * Hs + m.tx};
-        const double cy[4] = {m.ty, m.c * Ws + m.ty, m.a * Hs + m.ty, m.c * Ws + m.a * Hs + m.ty};
-        const double min_x = fmin(fmin(cx[0], cx[1]), fmin(cx[2], cx[3])), max_x = fmax(fmax(cx[0], cx[1]), fmax(cx[2], cx[3]));
-        const double min_y = fmin(fmin(cy[0], cy[1]), fmin(cy[2], cy[3])), max_y = fmax(fmax(cy[0], cy[1]), fmax(cy[2], cy[3]));
-        // pixel centres X + 0.5 in [min, max] with a pixel of slack on both sides (the region test below decides), inside the frame
-        int x_lo, x_hi, y_lo, y_hi;
-        int_range(min_x - 1.5, max_x + 0.5, W, x_lo, x_hi);
-        int_range(min_y - 1.5, max_y + 0.5, H, y_lo, y_hi);
+        const RegionBox box = region_box(m, Hs, Ws, H, W);
+        const int x_lo = box.x_lo, x_hi = box.x_hi, y_lo = box.y_lo, y_hi = box.y_hi;
         if (x_lo > x_hi || y_lo > y_hi) continue;
         const long long bw = x_hi - x_lo + 1, total = bw * (y_hi - y_lo + 1);
         const double is2 = 1.0 / (m.s * m.s), r = fmax(1.0, 1.0 / m.s), ir = 1.0 / r, fe = 1.0 / (feather + 1.0);

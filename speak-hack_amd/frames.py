@@ -1,6 +1,7 @@
 """The video-frame edge of the inference path: uint8 frames as a video decoder / writer holds them on the device, in and out of the
 network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packed RGB through a similarity transform per frame
-(csrc/frame_sim.hip: aligned crops), whose rows csrc/landmark_sim.hip fits to landmarks and smooths.  ``ops`` re-exports the
+(csrc/frame_sim.hip: aligned crops; csrc/frame_blend.hip: their paste with a face matte and a colour match), whose rows
+csrc/landmark_sim.hip fits to landmarks and smooths.  ``ops`` re-exports the
 launchers (``ops.frames_from_u8`` ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
 from __future__ import annotations
 
@@ -368,15 +369,38 @@ def frames_from_u8_aligned(frames_u8, size, sim, *, channel_order="rgb", mean=0.
     return out
 
 
-def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1), channel_order="rgb", out=None):
-    """Generated frames back into the video they were cropped from through ``sim``, one launch (``spk_frames_paste_u8_sim``): the
-    inverse of ``frames_from_u8_aligned``.  Every frame pixel whose centre ``sim[n]`` maps from inside the ``Hs x Ws`` image of
-    float32 ``x`` [N,3,Hs,Ws] takes the antialiased bilinear value of ``x`` there, quantised as ``frames_to_u8`` does, and is
-    blended over the background byte with weight ``a_u a_v``, a ramp over ``feather`` frame pixels at the crop's own edges
-    (``feather=0``: the crop replaces the background); every other byte of the frames is left as it is.  ``sim``: the two forms
-    of ``frames_from_u8_aligned``; a device row that is invalid leaves its frame untouched.  ``channel_order``, ``out``: as
-    ``frames_paste_u8``.  -> uint8 [N,H,W,3]."""
-    what = "frames_paste_u8_aligned"
+def _check_matte(matte, N, Hs, Ws, what):
+    """A matte as the blend takes it, its shape and dtype checked before a device is touched: -> ``(matte, matte_frames)``"""
+    if matte is None:
+        return None, 0
+    if not isinstance(matte, torch.Tensor) or matte.dtype != torch.float32 or matte.dim() not in (2, 3) or \
+            tuple(matte.shape[-2:]) != (Hs, Ws) or (matte.dim() == 3 and matte.size(0) != N):
+        got = f"{matte.dtype} {tuple(matte.shape)}" if isinstance(matte, torch.Tensor) else type(matte).__name__
+        raise ValueError(f"{what}: matte must be a float32 tensor [{Hs},{Ws}] or [{N},{Hs},{Ws}] (the generated image's size), got {got}")
+    return matte, (1 if matte.dim() == 2 else N)
+
+
+def _check_colour(colour, N, what):
+    if colour is not None and (not isinstance(colour, torch.Tensor) or colour.dtype != torch.float32 or tuple(colour.shape) != (N, 3, 2)):
+        got = f"{colour.dtype} {tuple(colour.shape)}" if isinstance(colour, torch.Tensor) else type(colour).__name__
+        raise ValueError(f"{what}: colour must be a float32 tensor [{N},3,2] of rows (gain, offset), got {got}")
+    return colour
+
+
+def _there(t, device, name, what):                                        # a checked matte / colour tensor: where the frames are, contiguous
+    if t is None:
+        return None
+    if not t.is_cuda or t.device != device:
+        raise L.SpkError(f"{what}: {name} on {t.device}, frames on {device} (no CPU path)")
+    if not t.is_contiguous():
+        raise L.SpkError(f"{what}: {name}: expected a contiguous tensor, got strides {t.stride()}")
+    return t
+
+
+def _aligned_paste_args(what, x, frames_u8, sim, feather, value_range, channel_order, matte=None, colour=None):
+    """What the aligned paste and its statistics check alike, in one order: -> ``(head, rows, tail, matte_args, colour)``: the
+    arguments of an entry point before the frames' pointer and strides, the device rows (the caller holds them until its launch
+    is queued), the arguments after the rows' pointer, the two matte arguments and the colour rows."""
     _check_chw(x, what)
     if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != x.size(0):
         raise ValueError(f"{what}: frames must be [{x.size(0)},H,W,3], got {tuple(frames_u8.shape)}")
@@ -384,11 +408,35 @@ def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1)
     lo, k = quant_range(value_range)
     feather = check_feather(feather, what)
     N, _, Hs, Ws = x.shape
-    H, W = frames_u8.size(1), frames_u8.size(2)
     rows = parse_sim(sim, N, f"{what}: sim")
+    matte, matte_frames = _check_matte(matte, N, Hs, Ws, what)
+    colour = _check_colour(colour, N, what)
     xp = L.dptr(x, "x")
     if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
         raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
+    matte, colour = _there(matte, x.device, "matte", what), _there(colour, x.device, "colour", what)
+    rows = _sim_on(rows, x.device, what)
+    return (xp, N, Hs, Ws), rows, (swap, feather, lo, k), (_ptr(matte), matte_frames), colour
+
+
+def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1), channel_order="rgb", out=None, matte=None, colour=None):
+    """Generated frames back into the video they were cropped from through ``sim``, one launch (``spk_frames_paste_u8_sim``): the
+    inverse of ``frames_from_u8_aligned``.  Every frame pixel whose centre ``sim[n]`` maps from inside the ``Hs x Ws`` image of
+    float32 ``x`` [N,3,Hs,Ws] takes the antialiased bilinear value of ``x`` there, quantised as ``frames_to_u8`` does, and is
+    blended over the background byte with weight ``a_u a_v``, a ramp over ``feather`` frame pixels at the crop's own edges
+    (``feather=0``: the crop replaces the background); every other byte of the frames is left as it is.  ``sim``: the two forms
+    of ``frames_from_u8_aligned``; a device row that is invalid leaves its frame untouched.  ``channel_order``, ``out``: as
+    ``frames_paste_u8``.
+
+    ``matte`` / ``colour`` (either one: ``spk_frames_paste_u8_sim_blend``, still one launch): ``matte`` is a device float32
+    ``[Hs,Ws]`` (one for all frames: ``ellipse_matte``) or ``[N,Hs,Ws]`` tensor in the generated image's coordinates, sampled with
+    the weights of ``x``, clamped to [0, 1] (NaN: 0) and multiplied into the blend weight, so only the face is pasted; ``colour``
+    is a device float32 ``[N,3,2]`` tensor of rows ``(gain, offset)`` per frame and channel of ``x``, applied to the quantised
+    value in front of the blend (``paste_colour_match`` makes them; a row that is not finite counts as ``(1, 0)``).  Without
+    both, the call is the one it always was.  -> uint8 [N,H,W,3]."""
+    what = "frames_paste_u8_aligned"
+    head, rows, tail, matte_args, colour = _aligned_paste_args(what, x, frames_u8, sim, feather, value_range, channel_order, matte, colour)
+    N, H, W = head[1], frames_u8.size(1), frames_u8.size(2)
     copy = out is not None and out is not frames_u8 and out.data_ptr() != frames_u8.data_ptr()
     if out is None:
         out = frames_u8.clone(memory_format=torch.contiguous_format)
@@ -396,12 +444,74 @@ def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1)
         raise L.SpkError(f"out: expected a uint8 HIP tensor {tuple(frames_u8.shape)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
     if not packed_pixels(out):
         raise L.SpkError(f"out: pixels must be packed and rows / frames must not overlap, got strides {out.stride()}")
-    rows = _sim_on(rows, x.device, what)
     if copy:
         out.copy_(frames_u8)
-    L.check(L.lib().spk_frames_paste_u8_sim(xp, N, Hs, Ws, out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), H, W, rows.data_ptr(),
-                                            swap, feather, lo, k, L.stream_ptr()), "spk_frames_paste_u8_sim")
+    where = (out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), H, W, rows.data_ptr())
+    if matte is None and colour is None:
+        L.check(L.lib().spk_frames_paste_u8_sim(*head, *where, *tail, L.stream_ptr()), "spk_frames_paste_u8_sim")
+    else:
+        L.check(L.lib().spk_frames_paste_u8_sim_blend(*head, *where, *tail, *matte_args, _ptr(colour), L.stream_ptr()),
+                "spk_frames_paste_u8_sim_blend")
     return out
+
+
+@functools.lru_cache(maxsize=8)
+def _colour_workspace(device, N):                                         # the partial sums of N frames, kept per (device, N)
+    need = L.lib().spk_paste_colour_match_workspace_bytes(N)
+    if need < 0:
+        raise L.SpkError(f"spk_paste_colour_match_workspace_bytes({N}) failed")
+    return torch.empty(need // 8, device=device, dtype=torch.float64)
+
+
+def paste_colour_match(x, frames_u8, sim, *, matte=None, feather=0, value_range=(-1, 1), channel_order="rgb", max_gain=2.0, min_sigma=1.0,
+                       min_weight=16.0, out=None):
+    """The colour rows ``frames_paste_u8_aligned(colour=)`` takes, two launches (``spk_paste_colour_match_sim``): per frame and
+    channel the ``(gain, offset)`` that carries the mean and standard deviation of the generated face ``x`` onto those of the
+    pixels of ``frames_u8`` it is about to replace, both weighted with the very blend weight ``a_u a_v Mt`` the paste will use
+    (``x``, ``frames_u8``, ``sim``, ``matte``, ``feather``, ``value_range``, ``channel_order``: as ``frames_paste_u8_aligned``;
+    include/spk.h has the sums).  ``frames_u8`` is only read -- call this BEFORE pasting in place.  The gain is kept within
+    ``[1 / max_gain, max_gain]`` and is 1 where the generated face has a standard deviation of at most ``min_sigma`` levels; a
+    frame whose weights sum to at most ``min_weight``, or whose row is invalid, gets ``(1, 0)``.  The sums are reduced in a fixed
+    order without atomics: the same inputs give the same bits.  The rows come back as a tensor so that a caller can smooth them
+    over time before pasting.  ``out``: a contiguous device float32 ``[N,3,2]`` tensor to write.  -> device float32 ``[N,3,2]``."""
+    what = "paste_colour_match"
+    max_gain, min_sigma, min_weight = float(max_gain), float(min_sigma), float(min_weight)
+    if not (1.0 <= max_gain < float("inf")):
+        raise ValueError(f"{what}: max_gain must be a finite number >= 1, got {max_gain}")
+    if not (0.0 <= min_sigma < float("inf")) or not (0.0 <= min_weight < float("inf")):
+        raise ValueError(f"{what}: min_sigma and min_weight must be finite numbers >= 0, got {min_sigma}, {min_weight}")
+    head, rows, tail, matte_args, _ = _aligned_paste_args(what, x, frames_u8, sim, feather, value_range, channel_order, matte)
+    N, H, W = head[1], frames_u8.size(1), frames_u8.size(2)
+    if not packed_pixels(frames_u8):
+        frames_u8 = frames_u8.contiguous()
+    if out is None:
+        out = torch.empty((N, 3, 2), device=x.device, dtype=torch.float32)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (N, 3, 2) or out.device != x.device or \
+            not out.is_contiguous():
+        raise L.SpkError(f"out: expected a contiguous float32 HIP tensor {(N, 3, 2)} on {x.device}")
+    ws = _colour_workspace(x.device, N)
+    L.check(L.lib().spk_paste_colour_match_sim(*head, frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), H, W,
+                                               rows.data_ptr(), *tail, *matte_args, max_gain, min_sigma, min_weight, out.data_ptr(),
+                                               ws.data_ptr(), ws.numel() * 8, L.stream_ptr()), "spk_paste_colour_match_sim")
+    return out
+
+
+def ellipse_matte(size_hw, centre=(0.5, 0.5), radii=(0.36, 0.46), softness=0.1, device=None):
+    """A static face matte for ``frames_paste_u8_aligned(matte=)``: an ellipse in the generated image, 1 inside, falling to 0 over
+    its rim.  For pixel ``(j, i)`` of an ``Hs x Ws`` image, ``rho = sqrt(((i + 0.5) / Ws - cx)^2 / rx^2 + ((j + 0.5) / Hs - cy)^2 /
+    ry^2)`` and ``M = clip((1 - rho) / softness, 0, 1)``; ``centre = (cx, cy)`` and ``radii = (rx, ry)`` are fractions of the width
+    and the height, ``softness > 0`` the fraction of the radius the rim takes.  Built in fp64 on the host, rounded to fp32.
+    -> float32 ``[Hs,Ws]`` on ``device`` (None: the CPU)."""
+    Hs, Ws = _out_size(size_hw, "ellipse_matte")
+    (cx, cy), (rx, ry), softness = (float(v) for v in centre), (float(v) for v in radii), float(softness)
+    if not (0.0 < softness < float("inf")):
+        raise ValueError(f"ellipse_matte: softness must be a finite number > 0, got {softness}")
+    if not (0.0 < rx < float("inf") and 0.0 < ry < float("inf")):
+        raise ValueError(f"ellipse_matte: radii must be finite numbers > 0, got {(rx, ry)}")
+    du = ((torch.arange(Ws, dtype=torch.float64) + 0.5) / Ws - cx) ** 2 / rx ** 2
+    dv = ((torch.arange(Hs, dtype=torch.float64) + 0.5) / Hs - cy) ** 2 / ry ** 2
+    matte = ((1.0 - (dv.view(Hs, 1) + du.view(1, Ws)).sqrt()) / softness).clamp(0.0, 1.0).float()
+    return matte if device is None else matte.to(device)
 
 
 # ---- landmarks to rows on the device: similarity fit and smoothing (csrc/landmark_sim.hip; the definitions are in include/spk.h) --
@@ -741,9 +851,15 @@ class Rgb24:
     def clone(self, frames):                                              # -> (the result, what ``paste`` takes)
         return (frames.clone(memory_format=torch.contiguous_format),) * 2
 
-    def paste(self, y, frames, t0, t1, box, feather):                     # ``box``: a box, or what ``Aligned.chunk`` gave
+    def paste(self, y, frames, t0, t1, box, feather, matte=None, colour_match=False):    # ``box``: a box, or what ``Aligned.chunk`` gave
         if isinstance(box, Aligned):
-            frames_paste_u8_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], **self.args)
+            blend = {}
+            if matte is not None or colour_match:                         # the statistics read the background before the paste writes it
+                if matte is not None and matte.dim() == 3:
+                    matte = matte[t0:t1]
+                rows = paste_colour_match(y, frames[t0:t1], box.rows, matte=matte, feather=feather, **self.args) if colour_match else None
+                blend = dict(matte=matte, colour=rows)
+            frames_paste_u8_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], **self.args, **blend)
         else:
             frames_paste_u8(y, frames[t0:t1], box, feather=feather, out=frames[t0:t1], **self.args)
 

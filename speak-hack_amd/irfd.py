@@ -167,7 +167,7 @@ class IRFD(nn.Module):
     @torch.no_grad()
     def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8,
                       seed=None, noise="fresh", frame0=0, paste=False, feather=0, inplace=False, pixel_format="rgb24", standard="bt601",
-                      full_range=False, align=None, identity_align=None):
+                      full_range=False, align=None, identity_align=None, matte=None, colour_match=False):
         """``reenact`` from and to video frames as a decoder and a video writer hold them (inference.py:29-33,46-58,78-86):
         uint8 HWC frames of any size on the device in, uint8 [T,R,R,3] out, both in ``channel_order`` ("bgr": ``cv2``'s).
         Nothing but ``ops.frames_from_u8`` -> ``reenact(output="uint8")``: ``identity_u8`` [H,W,3] or [1,H,W,3] is resized whole
@@ -204,7 +204,16 @@ class IRFD(nn.Module):
         ``identity_align``: the identity photo through an aligned crop as well, so that ``Ei`` sees a face framed as ``Ee`` / ``Ep``
         see theirs -- one row in either form above (``[1,4]``; host rows are checked before any launch) or an ``ops.LandmarkAlign``
         over one frame; the photo then goes through ``ops.frames_from_u8_aligned`` instead of being resized whole.  The photo is
-        packed in both pixel formats, so this works with both.  ``None``: resized whole, as ever."""
+        packed in both pixel formats, so this works with both.  ``None``: resized whole, as ever.
+
+        ``matte`` / ``colour_match`` (both need ``align=``, ``paste=True`` and packed RGB; anything else: ``ValueError`` before any
+        launch): a seamless paste.  ``matte``: a float32 ``[R,R]`` (one for the clip: ``ops.ellipse_matte``) or ``[T,R,R]`` tensor
+        in the generated image's size where the frames are, multiplied into the blend weight so that only the face is pasted, not
+        the generator's own background.  ``colour_match=True``: per frame and channel the generated face is brought to the mean and
+        standard deviation of the pixels it replaces (``ops.paste_colour_match``) -- each chunk makes one
+        ``spk_paste_colour_match_sim`` call, then one ``spk_frames_paste_u8_sim_blend`` call (``ops.frames_paste_u8_aligned(matte=,
+        colour=)``) with the rows the paste uses anyway.  The statistics are per frame and read the background before the paste, on
+        the same stream: the result depends neither on ``chunk`` nor on ``inplace``."""
         if pixel_format not in FR.PIXEL_FORMATS:
             raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
         if pixel_format == "rgb24" and (standard != "bt601" or full_range):
@@ -221,12 +230,24 @@ class IRFD(nn.Module):
             raise ValueError("reenact_video: crop and align are two ways to say where the face is: give one")
         if align is not None and pixel_format != "rgb24":
             raise ValueError("reenact_video: align applies to pixel_format='rgb24' only (NV12 frames take crop boxes)")
+        if not isinstance(colour_match, bool):
+            raise ValueError(f"reenact_video: colour_match must be a bool, got {colour_match!r}")
+        blend = {}
+        if matte is not None or colour_match:
+            if align is None or not paste:
+                raise ValueError("reenact_video: matte / colour_match apply to align= with paste=True only")
+            if matte is not None and (not isinstance(matte, torch.Tensor) or matte.dtype != torch.float32 or matte.dim() not in (2, 3)):
+                got = f"{matte.dtype} {tuple(matte.shape)}" if isinstance(matte, torch.Tensor) else type(matte).__name__
+                raise ValueError(f"reenact_video: matte must be a float32 tensor [R,R] or [T,R,R] in the generated image's size, got {got}")
+            blend = dict(matte=matte, colour_match=colour_match)
         fmt = FR.PIXEL_FORMATS[pixel_format](channel_order, standard, full_range)
         if identity_align is not None:                                     # host rows: checked here, before any launch
             identity_align = FR.Aligned.parse(identity_align, 1, size, identity_u8.device, "reenact_video: identity_align")
         pose_in = pose_u8
         if align is not None:                                              # the transforms stand where a box would: checked / uploaded once
             pose_in, device, T, H, W = fmt.open(pose_u8, inplace)
+            if matte is not None and matte.dim() == 3 and matte.size(0) != T:
+                raise ValueError(f"reenact_video: a per-frame matte must carry {T} frames, got {tuple(matte.shape)}")
             crop = FR.Aligned.parse(align, T, size, device)
         elif crop is not None or paste or fmt.needs_box:
             pose_in, device, T, H, W = fmt.open(pose_u8, inplace)
@@ -246,7 +267,7 @@ class IRFD(nn.Module):
         result, out = (pose_u8, pose_in) if inplace else fmt.clone(pose_in)
         for t0, t1, y in self._reenact_chunks(ident, pose, emo, noises, chunk, "f32", "rgb", seed, noise, frame0):
             where = crop.chunk(t0, t1, y) if align is not None else crop if len(crop) == 4 else (crop[0][t0:t1], h, w)
-            fmt.paste(y, out, t0, t1, where, feather)
+            fmt.paste(y, out, t0, t1, where, feather, **blend)
         return result
 
     def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None, colour=("bt601", False)):

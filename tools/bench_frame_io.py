@@ -38,7 +38,15 @@
     time with a synchronise on both sides; the contenders alternate, medians are compared, and the device route runs twice per round
     for the spread.
 
-    python tools/bench_frame_io.py [--paste | --nv12 | --align | --landmarks] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
+``--blend``: the seamless paste-back (csrc/frame_blend.hip) at the workload's own shapes: 8 generated 256^2 frames into rotated
+    400 x 400 regions (s = 400 / 256) of 1080 x 1920 BGR frames, feather 16, in place.  (1) the plain aligned paste, (2) the paste
+    with a static ellipse matte, (3) ``ops.paste_colour_match`` + the paste with the matte and its rows (and the statistics
+    alone), (4) the torch composition a user has without them: ``affine_grid`` + ``grid_sample`` of the image and of the matte,
+    masked mean / std, blend, on fp32 copies of the full frames.  The contenders alternate in one process, medians of HIP-event
+    times are compared, and the plain paste runs twice per round: the distance of its two medians is the recorded spread.
+    ``--commit`` names the commit the table is taken at.
+
+    python tools/bench_frame_io.py [--paste | --nv12 | --align | --landmarks | --blend] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
 import math
@@ -404,6 +412,87 @@ def bench_align(args, lines):
            times, "reenact_video(align=, paste=True)", [("reenact_video(crop=, paste=True)", False)])
 
 
+def torch_blend_paste(y, video_out, theta_inv, scale, feather, matte, colour_match, max_gain=2.0):
+    """The torch composition ``ops.paste_colour_match`` + ``ops.frames_paste_u8_aligned(matte=, colour=)`` replace, on fp32 copies
+    of the full frames: ``torch_aligned_paste`` with the matte sampled through the same grid and a weighted mean / std match."""
+    N, H, W, _ = video_out.shape
+    Hs, Ws = y.shape[2:]
+    grid = F.affine_grid(theta_inv, (N, 3, H, W), align_corners=False)
+    q = ((F.grid_sample(y, grid, mode="bilinear", padding_mode="zeros", align_corners=False) + 1) * 127.5).clamp(0, 255).flip(1).permute(0, 2, 3, 1)
+    u, v = (grid[..., 0] + 1) * (Ws / 2), (grid[..., 1] + 1) * (Hs / 2)
+    inside = (u >= 0) & (u < Ws) & (v >= 0) & (v < Hs)
+    a_u = ((scale * torch.minimum(u, Ws - u) + 0.5) / (feather + 1.0)).clamp(max=1.0)
+    a_v = ((scale * torch.minimum(v, Hs - v) + 0.5) / (feather + 1.0)).clamp(max=1.0)
+    m = a_u * a_v * inside
+    if matte is not None:
+        m = m * F.grid_sample(matte.expand(N, 1, Hs, Ws), grid, mode="bilinear", padding_mode="zeros", align_corners=False).squeeze(1).clamp(0, 1)
+    m = m.unsqueeze(-1)
+    b = video_out.float()
+    if colour_match:
+        S0 = m.sum((1, 2))
+        mu_q, mu_b = (m * q).sum((1, 2)) / S0, (m * b).sum((1, 2)) / S0
+        var_q = ((m * q * q).sum((1, 2)) / S0 - mu_q * mu_q).clamp(min=0)
+        var_b = ((m * b * b).sum((1, 2)) / S0 - mu_b * mu_b).clamp(min=0)
+        g = torch.where(var_q <= 1.0, torch.ones_like(var_q), (var_b / var_q.clamp(min=1e-12)).sqrt().clamp(1 / max_gain, max_gain))
+        q = (q * g[:, None, None, :] + (mu_b - g * mu_q)[:, None, None, :]).clamp(0, 255)
+    video_out.copy_((b + m * (q - b)).round().to(torch.uint8))
+
+
+def bench_blend(args, lines):
+    """``--blend``: the plain aligned paste, the paste with a matte, the statistics + the paste with matte and rows, and the torch
+    composition of the last, at 8 x 256^2 -> rotated 400 x 400 regions of 1080 x 1920 BGR frames."""
+    import importlib
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    chunk, size, Hf, Wf, side, feather = args.chunk, 256, 1080, 1920, 400, 16
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(chunk)]
+    angles = [0.3 * math.sin(0.9 * t) for t in range(chunk)]
+    rows = ops.similarity_rows([(y + side / 2, x + side / 2) for y, x in boxes], float(side), angles, size).to(dev)
+    _, inv, scale = (t.to(dev) for t in align_thetas(rows.cpu(), Hf, Wf, size, size))
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    video = torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    matte = ops.ellipse_matte((size, size), device=dev)
+    kw = dict(feather=feather, channel_order="bgr")
+    colour = ops.paste_colour_match(x, video, rows, matte=matte, **kw)
+    scratch = video.clone()
+
+    def plain():
+        return ops.frames_paste_u8_aligned(x, video, rows, out=video, **kw)
+
+    def matched():
+        c = ops.paste_colour_match(x, video, rows, matte=matte, **kw)
+        return ops.frames_paste_u8_aligned(x, video, rows, matte=matte, colour=c, out=video, **kw)
+
+    contenders = {"plain aligned paste": plain,
+                  "matte only": lambda: ops.frames_paste_u8_aligned(x, video, rows, matte=matte, out=video, **kw),
+                  "matte + colour match (statistics + paste)": matched,
+                  "  the statistics alone": lambda: ops.paste_colour_match(x, video, rows, matte=matte, out=colour, **kw),
+                  "torch affine_grid + grid_sample + masked mean/std + blend": lambda: torch_blend_paste(x, scratch, inv, scale, feather, matte, True),
+                  "plain aligned paste (again)": plain}
+    a, b = video.clone(), video.clone()
+    ops.frames_paste_u8_aligned(x, a, rows, matte=matte, colour=ops.paste_colour_match(x, a, rows, matte=matte, **kw), out=a, **kw)
+    torch_blend_paste(x, b, inv, scale, feather, matte, True)
+    d = (a.int() - b.int()).abs()
+    times = alternate(contenders, args.repeats, device_time)
+    med = {n: statistics.median(ts) for n, ts in times.items()}
+    lines.append(f"{chunk} x 256^2 fp32 -> rotated {side}x{side} regions of {Hf}x{Wf} BGR, feather {feather}, ellipse matte, in place; HIP events, launcher "
+                 f"included, median of {args.repeats} alternating rounds of 20; bytes that differ from the torch composition by more than 1: "
+                 f"{int((d > 1).sum())} of {d.numel()}")
+    for n, ts in times.items():
+        lines.append(f"  {n:58s} median {med[n] * 1e6:9.1f} us  min {ts[0] * 1e6:9.1f}  max {ts[-1] * 1e6:9.1f}")
+    p0, p1 = med["plain aligned paste"], med["plain aligned paste (again)"]
+    spread = abs(p0 - p1) / min(p0, p1)
+    lines.append(f"  spread of the repeated contender: {spread * 100:.2f} %")
+    for n in ("matte only", "matte + colour match (statistics + paste)", "  the statistics alone"):
+        lines.append(f"  {n.strip()} / plain aligned paste = {med[n] / p0:.3f}")
+    ours, other = med["matte + colour match (statistics + paste)"], med["torch affine_grid + grid_sample + masked mean/std + blend"]
+    lines.append(f"  matte + colour match / torch composition = {ours / other:.4f}")
+    verdict = "MORE than twice" if med["  the statistics alone"] > 2 * p0 else "not more than twice"
+    lines.append(f"  the statistics pass costs {med['  the statistics alone'] / p0:.2f} plain pastes: {verdict} the plain paste at this shape")
+
+
 def bench_landmarks(args, lines):
     """``--landmarks``: the fit and the smoothing launch beside a copy to the host, numpy and a copy back."""
     import importlib
@@ -477,10 +566,16 @@ def main():
     ap.add_argument("--paste", action="store_true", help="the full-frame way out: frames_paste_u8 and reenact_video(paste=True)")
     ap.add_argument("--nv12", action="store_true", help="the NV12 form of the edge: its kernels and reenact_video(pixel_format='nv12', paste=True)")
     ap.add_argument("--align", action="store_true", help="the aligned edge: frames_from_u8_aligned, frames_paste_u8_aligned, reenact_video(align=)")
+    ap.add_argument("--blend", action="store_true", help="the seamless paste-back: matte, colour match and their torch composition")
+    ap.add_argument("--commit", default="unknown", help="--blend: the commit the table is taken at, for its first line")
     ap.add_argument("--landmarks", action="store_true", help="landmarks -> rows: similarity_from_landmarks, smooth_similarity_rows, the host route")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.blend:
+        lines = [f"bench_frame_io --blend: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_blend(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "blend_bench.txt"))
     if args.landmarks:
         lines = [f"bench_frame_io --landmarks: {torch.cuda.get_device_name(0)}"]
         bench_landmarks(args, lines)

@@ -927,6 +927,57 @@ int spk_frames_paste_nv12(const float* src, int N, int Hs, int Ws, uint8_t* y, i
                           const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, const float* a_y, const float* a_x,
                           float lo, float k, void* stream);
 
+/* ---- aligned crops on NV12 surfaces: similarity warp, matte and colour match (csrc/frame_sim_nv12.hip) ---------------------------
+ * The three sections above joined: the rows (a, c, tx, ty), their validity rule, tri, the clamped integer ranges and the region of
+ * the aligned edge; the matte, the colour rows and their 13 sums of the seamless paste-back; the surfaces, the siting by
+ * replication and the colour maps of the NV12 edge (to_rgb / from_rgb of spk_yuv_coeffs for standard / full_range, built on the host
+ * and passed to the kernels by value; a row applied as one fp64 fma chain from the offset).  H and W are even.
+ *
+ * spk_frames_nv12_to_f32_sim: warp + antialias + colour + normalise -> CHW in one pass.  p, S, w(q) and Wt are exactly those of
+ *   spk_frames_u8_to_f32_sim, over the pixels q = (ix, iy) of the H x W frame in (iy, ix) order; three fp64 sums
+ *     acc_f = fma(w(q), field_f(q), acc_f),   field = Y[iy][ix], U[iy >> 1][ix >> 1], V[iy >> 1][ix >> 1]
+ *     rgb_c = min(max(to_rgb_c . (acc_Y / Wt, acc_U / Wt, acc_V / Wt, 1), 0), 255)            c = R, G, B; fp64
+ *     dst[n, c', oy, ox] = (float) fma(scale_c', rgb_c, shift_c')                             c' = swap_rb ? 2 - c : c
+ *   with rgb_c = 0 (NOT to_rgb of zeros, whose green offset is positive) when Wt <= 0 or the row is invalid: such outputs are
+ *   shift exactly.  The clamp follows the filter, as in spk_frames_nv12_to_f32.  With c = 0 and a scale that is exact in fp32 the
+ *   whole-frame result is spk_frames_nv12_to_f32's to its fp32 table rounding.
+ * spk_frames_paste_nv12_sim: inverse warp + quantise + colour rows + matte + RGB -> YUV + blend into the surfaces, one launch, no
+ *   allocation, no synchronisation.  For frame pixel (Y, X): region, val, q (fp32, not rounded, per network channel R, G, B),
+ *   a_u, a_v, Mt and m = a_u a_v Mt are exactly those of spk_frames_paste_u8_sim_blend (matte_dev NULL: Mt = 1).  Then
+ *     q'_c = min(max(fmaf(g_c, q_c, o_c), 0), 255)                          fp32; colour_dev NULL: q' = q; a row not finite: (1, 0)
+ *     e    = from_rgb . (q'_R, q'_G, q'_B, 1)                               fp64: (e_y, e_u, e_v)
+ *   luma:    Y' = rint(min(max(fma(1 - m, b, m e_y), 0), 255))              b: the byte being overwritten
+ *   chroma of sample s: over the REGION pixels of its 2 x 2 block, in row-major order,
+ *            acc = fma(0.25 m, e_c, acc) from 0,  S = sum 0.25 m,
+ *            C' = rint(min(max(fma(1 - S, b_c, acc), 0), 255))              one 16-bit load and store of the pair
+ *   -- the formulas of spk_frames_paste_nv12 with m from the aligned path; the same convex combination.  A block without a region
+ *   pixel and a frame with an invalid row are not touched; where m is exactly 0 a luma byte, and where S is exactly 0 a pair,
+ *   keeps its value by arithmetic.  A thread owns one chroma block and reads only bytes it writes: in place is legal.
+ * spk_paste_colour_match_nv12_sim: the rows (g, o) of spk_paste_colour_match_sim for a surface background: the same 13 sums, the
+ *   same weights, row formula, arguments and workspace (spk_paste_colour_match_workspace_bytes(N)), the same fixed-order
+ *   reduction without atomics (two calls give the same bits), with the background of region pixel (Y, X)
+ *     b_c = min(max(to_rgb_c . (Y[Y][X], U[Y >> 1][X >> 1], V[Y >> 1][X >> 1], 1), 0), 255)   fp64; c = R, G, B
+ *   -- what the way in makes of that pixel.  Rows are per NETWORK channel and the paste applies them in front of from_rgb, so
+ *   rows from either pixel format mean the same thing.  It reads the surfaces and writes none.
+ * Refused before any launch (SPK_EINVAL, spk_last_error): null pointers; N < 1; H or W odd or < 2; an odd UV base or stride; a row
+ *   stride below W bytes; overlapping frames of a written surface, a negative image stride of a read one; sizes < 1; a feather
+ *   that is negative or not finite; a value range that is not finite and increasing; matte_frames other than 1 or N with a matte,
+ *   other than 0 without one; a standard other than 601 / 709, a full_range other than 0 / 1; the statistics' parameters and
+ *   workspace as spk_paste_colour_match_sim.  replaces: NV12 -> BGR and BGR -> NV12 in torch ops around the packed-RGB entry points. */
+int spk_frames_nv12_to_f32_sim(const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, const uint8_t* uv, int64_t uv_image_stride,
+                               int64_t uv_row_stride, int N, int H, int W, const float* sim_dev, int swap_rb, int standard, int full_range,
+                               float* dst, int Hout, int Wout, float scale0, float scale1, float scale2, float shift0, float shift1,
+                               float shift2, void* stream);
+int spk_frames_paste_nv12_sim(const float* src, int N, int Hs, int Ws, uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, uint8_t* uv,
+                              int64_t uv_image_stride, int64_t uv_row_stride, int H, int W, const float* sim_dev, int standard, int full_range,
+                              double feather, float lo, float k, const float* matte_dev, int matte_frames, const float* colour_dev,
+                              void* stream);
+int spk_paste_colour_match_nv12_sim(const float* src, int N, int Hs, int Ws, const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride,
+                                    const uint8_t* uv, int64_t uv_image_stride, int64_t uv_row_stride, int H, int W, const float* sim_dev,
+                                    int standard, int full_range, double feather, float lo, float k, const float* matte_dev, int matte_frames,
+                                    double max_gain, double min_sigma, double min_weight, float* colour_out_dev, void* workspace_dev,
+                                    size_t workspace_bytes, void* stream);
+
 /* ---- counter-based decoder noise (csrc/noise.hip) ----------------------------------------------------------------------------
  * The noise planes of a synthesis pass as a pure function of (seed, frame, layer, pixel): no generator state, so a clip comes
  * out the same whatever the chunking or the sharding over devices, and a fixed-noise clip is every frame on one frame index.

@@ -350,6 +350,16 @@ _PROTOTYPES = {
                                         C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    "spk_frames_nv12_to_f32_sim": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 +
+                                   [C.c_void_p]),
+    "spk_frames_paste_nv12_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "spk_paste_colour_match_nv12_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                                  C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float,
+                                                  C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t, C.c_void_p]),
     "spk_noise_bits_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "spk_noise_fill": (C.c_int, [C.POINTER(NoiseFillArgs), C.c_void_p]),
 }

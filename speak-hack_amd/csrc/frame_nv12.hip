@@ -6,46 +6,13 @@
 //   one thread per chroma block (2 x 2 luma pixels); frames_f32_to_nv12 is its whole-frame case without tables.
 // Definitions (siting, colour matrices, the order of every operation) are in include/spk.h.  The resize tables are those of
 // csrc/frame_io.hip (spk_resize_table, spk_feather_table): this file holds no filter arithmetic and links without that one; what
-// the two share is in csrc/frame_common.hpp.
-#include "frame_common.hpp"
+// the two share is in csrc/frame_common.hpp, and what this file shares with the aligned NV12 edge (csrc/frame_sim_nv12.hip) --
+// the colour maps, affine_row, the surface checks -- in csrc/frame_nv12_common.hpp.
+#include "frame_nv12_common.hpp"
 
 namespace {
 
 using namespace spk::frame;
-
-struct Mat34 { double m[12]; };     // three rows [a0 a1 a2 offset], byte units
-
-// row c of a 3 x 4 affine map applied to (p0, p1, p2, 1): one fp64 fma chain that starts from the offset
-__device__ __forceinline__ double affine_row(const Mat34& M, int c, double p0, double p1, double p2) {
-    return fma(M.m[4 * c + 2], p2, fma(M.m[4 * c + 1], p1, fma(M.m[4 * c], p0, M.m[4 * c + 3])));
-}
-
-// (Kr, Kb) of a standard; false: unknown
-bool primaries(int standard, double* kr, double* kb) {
-    if (standard == 601) { *kr = 0.299; *kb = 0.114; return true; }
-    if (standard == 709) { *kr = 0.2126; *kb = 0.0722; return true; }
-    return false;
-}
-
-void yuv_coeffs(double kr, double kb, bool full, double* to_rgb, double* from_rgb) {
-    const double kg = 1.0 - kr - kb;
-    const double sy = full ? 1.0 : 219.0 / 255.0, sc = full ? 1.0 : 224.0 / 255.0, oy = full ? 0.0 : 16.0;
-    if (from_rgb) {
-        const double cb = sc / (2.0 * (1.0 - kb)), cr = sc / (2.0 * (1.0 - kr));
-        const double f[12] = {sy * kr, sy * kg, sy * kb, oy,
-                              -kr * cb, -kg * cb, (1.0 - kb) * cb, 128.0,
-                              (1.0 - kr) * cr, -kg * cr, -kb * cr, 128.0};
-        std::copy(f, f + 12, from_rgb);
-    }
-    if (to_rgb) {
-        const double ay = 1.0 / sy, rv = 2.0 * (1.0 - kr) / sc, bu = 2.0 * (1.0 - kb) / sc;
-        const double gu = -kb * bu / kg, gv = -kr * rv / kg;
-        const double t[12] = {ay, 0.0, rv, -(ay * oy + 128.0 * rv),
-                              ay, gu, gv, -(ay * oy + 128.0 * (gu + gv)),
-                              ay, bu, 0.0, -(ay * oy + 128.0 * bu)};
-        std::copy(t, t + 12, to_rgb);
-    }
-}
 
 // ---- in ----
 // A thread owns output column ox of one STRIP-row strip of one frame, as frames_u8_to_f32_kernel does, and carries the three
@@ -171,27 +138,6 @@ __global__ __launch_bounds__(256) void frames_paste_nv12_kernel(const float* __r
         const unsigned v = (unsigned)(int)rint(fmin(fmax(fma(1.0 - S, (double)(pair >> 8), acc_v), 0.0), 255.0));
         *pc = (uint16_t)(u | v << 8);
     }
-}
-
-// the checks every NV12 surface argument gets; 0: fine
-int check_surface(const char* who, const void* y, int64_t y_image_stride, int64_t y_row_stride, const void* uv, int64_t uv_image_stride,
-                  int64_t uv_row_stride, int N, int H, int W, bool written) {
-    SPK_REQUIRE(y && uv, "%s: null plane pointer", who);
-    SPK_REQUIRE(N >= 1 && H >= 2 && W >= 2, "%s: N must be >= 1 and H, W >= 2 (N %d, %d x %d)", who, N, H, W);
-    SPK_REQUIRE(H % 2 == 0 && W % 2 == 0, "%s: NV12 frames have an even height and width (got %d x %d)", who, H, W);
-    SPK_REQUIRE((uintptr_t)uv % 2 == 0, "%s: the UV plane must be 2-byte aligned", who);
-    SPK_REQUIRE(uv_row_stride % 2 == 0 && uv_image_stride % 2 == 0, "%s: the UV strides must be even (row %lld, image %lld)", who,
-                (long long)uv_row_stride, (long long)uv_image_stride);
-    SPK_REQUIRE(y_row_stride >= (long long)W, "%s: Y row stride %lld is smaller than W = %d", who, (long long)y_row_stride, W);
-    SPK_REQUIRE(uv_row_stride >= (long long)W, "%s: UV row stride %lld is smaller than the row's %d bytes", who, (long long)uv_row_stride, W);
-    if (written) {
-        SPK_REQUIRE(N == 1 || (y_image_stride >= (long long)(H - 1) * y_row_stride + W && uv_image_stride >= (long long)(H / 2 - 1) * uv_row_stride + W),
-                    "%s: image strides %lld / %lld make the frames overlap (%d rows of stride %lld / %lld)", who, (long long)y_image_stride,
-                    (long long)uv_image_stride, H, (long long)y_row_stride, (long long)uv_row_stride);
-    } else {
-        SPK_REQUIRE(y_image_stride >= 0 && uv_image_stride >= 0, "%s: negative image stride", who);
-    }
-    return SPK_OK;
 }
 
 }  // namespace

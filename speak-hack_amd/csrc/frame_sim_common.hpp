@@ -1,5 +1,5 @@
 // What the kernels of the aligned video edge share (csrc/frame_sim.hip: warp in, paste out; csrc/frame_blend.hip: the paste with a
-// matte and a colour match, and the statistics of that match): how a row (a, c, tx, ty) is read and judged, the triangle, the
+// matte and a colour match, and the statistics of that match; csrc/frame_sim_nv12.hip: all of these on NV12 surfaces): how a row (a, c, tx, ty) is read and judged, the triangle, the
 // clamped integer ranges and the bounding box of a row's region inside the frame.  Written once, so that the files agree on
 // which pixels a row touches and on every weight, to the bit.
 #pragma once

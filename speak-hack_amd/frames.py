@@ -1,7 +1,7 @@
 """The video-frame edge of the inference path: uint8 frames as a video decoder / writer holds them on the device, in and out of the
 network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packed RGB through a similarity transform per frame
-(csrc/frame_sim.hip: aligned crops; csrc/frame_blend.hip: their paste with a face matte and a colour match), whose rows
-csrc/landmark_sim.hip fits to landmarks and smooths.  ``ops`` re-exports the
+(csrc/frame_sim.hip: aligned crops; csrc/frame_blend.hip: their paste with a face matte and a colour match; csrc/frame_sim_nv12.hip:
+all of that on NV12 surfaces), whose rows csrc/landmark_sim.hip fits to landmarks and smooths.  ``ops`` re-exports the
 launchers (``ops.frames_from_u8`` ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
 from __future__ import annotations
 
@@ -798,6 +798,108 @@ def frames_paste_nv12(x, nv12, box, *, feather=0, value_range=(-1, 1), standard=
     tables, ay, ax = _paste_tables(Hs, Ws, h, w, feather, x.device)
     L.check(L.lib().spk_frames_paste_nv12(xp, N, Hs, Ws, y.data_ptr(), *ys, uv.data_ptr(), *us, H, W, h, w, y0, x0, _ptr(boxes), code, full,
                                           *tables, ay, ax, lo, k, L.stream_ptr()), "spk_frames_paste_nv12")
+    return out
+
+
+# ---- aligned crops on NV12 surfaces (csrc/frame_sim_nv12.hip; the definitions are in include/spk.h) --------------------------------
+def frames_from_nv12_aligned(nv12, size, sim, *, channel_order="rgb", mean=0.5, std=0.5, standard="bt601", full_range=False):
+    """NV12 video frames -> the network's input through a similarity transform PER FRAME, one launch
+    (``spk_frames_nv12_to_f32_sim``): ``frames_from_u8_aligned`` on surfaces.  The footprint and the fp64 weights are that
+    launcher's; they run over the Y, U and V fields (chroma by replication), then YUV -> RGB (``yuv_coeffs``), clamp to 0..255 and
+    ``(x / 255 - mean) / std`` as ``frames_from_nv12``.  An output whose footprint misses the frame is ``-mean / std`` exactly, and
+    so is every output of a frame whose device row is invalid.  ``nv12``: what ``nv12_planes`` takes, on the device, read in place
+    through its strides; ``sim``: the two forms of ``parse_sim``; ``channel_order``: the plane order of the result, as
+    ``frames_from_nv12``.  -> float32 [N,3,size,size]."""
+    what = "frames_from_nv12_aligned"
+    y, uv = nv12_planes(nv12)
+    N, H, W = y.shape
+    Hout, Wout = _out_size(size, what)
+    swap = _channel_swap(channel_order)
+    code, full = yuv_standard(standard, full_range)
+    scale, shift = _affine(mean, std, what)
+    rows = parse_sim(sim, N, f"{what}: sim")
+    ys, us = nv12_strides(y, uv, what, written=False)
+    rows = _sim_on(rows, y.device, what)
+    out = torch.empty((N, 3, Hout, Wout), device=y.device, dtype=torch.float32)
+    L.check(L.lib().spk_frames_nv12_to_f32_sim(y.data_ptr(), *ys, uv.data_ptr(), *us, N, H, W, rows.data_ptr(), swap, code, full, out.data_ptr(),
+                                               Hout, Wout, *scale, *shift, L.stream_ptr()), "spk_frames_nv12_to_f32_sim")
+    return out
+
+
+def _aligned_nv12_args(what, x, nv12, sim, feather, value_range, standard, full_range, matte=None, colour=None):
+    """What the aligned NV12 paste and its statistics check alike, in the order of ``_aligned_paste_args``:
+    -> ``(head, planes, rows, tail, matte_args, colour)``: the arguments of an entry point before the surfaces, the source planes,
+    the device rows, the arguments after the rows' pointer, the two matte arguments and the colour rows."""
+    _check_chw(x, what)
+    sy, suv = nv12_planes(nv12)
+    N, _, Hs, Ws = x.shape
+    if sy.size(0) != N:
+        raise ValueError(f"{what}: {N} generated frames, {sy.size(0)} NV12 frames")
+    lo, k = quant_range(value_range)
+    code, full = yuv_standard(standard, full_range)
+    feather = check_feather(feather, what)
+    rows = parse_sim(sim, N, f"{what}: sim")
+    matte, matte_frames = _check_matte(matte, N, Hs, Ws, what)
+    colour = _check_colour(colour, N, what)
+    xp = L.dptr(x, "x")
+    if not sy.is_cuda:
+        raise L.SpkError(f"frames: expected uint8 HIP tensors, got {sy.dtype} on {sy.device} (no CPU path)")
+    matte, colour = _there(matte, x.device, "matte", what), _there(colour, x.device, "colour", what)
+    rows = _sim_on(rows, x.device, what)
+    return (xp, N, Hs, Ws), (sy, suv), rows, (code, full, feather, lo, k), (_ptr(matte), matte_frames), colour
+
+
+def frames_paste_nv12_aligned(x, nv12, sim, *, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None, matte=None,
+                              colour=None):
+    """Generated frames back into the NV12 video they were cropped from through ``sim``, one launch (``spk_frames_paste_nv12_sim``):
+    the inverse of ``frames_from_nv12_aligned``, and ``frames_paste_u8_aligned`` on surfaces.  Region, value, ``feather`` ramp,
+    ``matte`` and ``colour`` rows are that launcher's (rows act on the R, G, B value in front of the conversion, so
+    ``paste_colour_match_nv12`` and ``paste_colour_match`` rows mean the same thing); the result is converted with ``from_rgb`` of
+    ``yuv_coeffs`` and blended as ``frames_paste_nv12`` blends: luma per pixel, chroma per 2 x 2 block as the quarter-weighted sum
+    of the block's region pixels over the sample underneath.  Every byte outside the region's pixels and blocks is left as it is; a
+    device row that is invalid leaves its frame untouched.  ``nv12``, ``out``: as ``frames_paste_nv12`` (``out=nv12`` pastes in
+    place).  -> uint8 [N, 3H/2, W], or ``out``."""
+    what = "frames_paste_nv12_aligned"
+    head, (sy, suv), rows, tail, matte_args, colour = _aligned_nv12_args(what, x, nv12, sim, feather, value_range, standard, full_range, matte,
+                                                                         colour)
+    N, (H, W) = head[1], sy.shape[1:]
+    out, y, uv = _nv12_out(out, N, H, W, x.device, what)
+    ys, us = nv12_strides(y, uv, f"{what}: out", written=True)
+    if y.data_ptr() != sy.data_ptr() or y.stride() != sy.stride():
+        y.copy_(sy)
+    if uv.data_ptr() != suv.data_ptr() or uv.stride() != suv.stride():
+        uv.copy_(suv)
+    L.check(L.lib().spk_frames_paste_nv12_sim(*head, y.data_ptr(), *ys, uv.data_ptr(), *us, H, W, rows.data_ptr(), *tail, *matte_args,
+                                              _ptr(colour), L.stream_ptr()), "spk_frames_paste_nv12_sim")
+    return out
+
+
+def paste_colour_match_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, max_gain=2.0,
+                            min_sigma=1.0, min_weight=16.0, out=None):
+    """The colour rows ``frames_paste_nv12_aligned(colour=)`` takes, two launches (``spk_paste_colour_match_nv12_sim``):
+    ``paste_colour_match`` for a surface background.  The same sums, weights, row formula and arguments; the background of a
+    region pixel is what ``frames_from_nv12_aligned`` makes of it, ``clamp(to_rgb . (Y, U, V, 1))``, so the rows are per network
+    channel R, G, B.  ``nv12`` is only read -- call this BEFORE pasting in place.  Reduced in a fixed order without atomics: the
+    same inputs give the same bits.  ``out``: a contiguous device float32 ``[N,3,2]`` tensor to write.
+    -> device float32 ``[N,3,2]``."""
+    what = "paste_colour_match_nv12"
+    max_gain, min_sigma, min_weight = float(max_gain), float(min_sigma), float(min_weight)
+    if not (1.0 <= max_gain < float("inf")):
+        raise ValueError(f"{what}: max_gain must be a finite number >= 1, got {max_gain}")
+    if not (0.0 <= min_sigma < float("inf")) or not (0.0 <= min_weight < float("inf")):
+        raise ValueError(f"{what}: min_sigma and min_weight must be finite numbers >= 0, got {min_sigma}, {min_weight}")
+    head, (y, uv), rows, tail, matte_args, _ = _aligned_nv12_args(what, x, nv12, sim, feather, value_range, standard, full_range, matte)
+    N, (H, W) = head[1], y.shape[1:]
+    ys, us = nv12_strides(y, uv, what, written=False)
+    if out is None:
+        out = torch.empty((N, 3, 2), device=x.device, dtype=torch.float32)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (N, 3, 2) or out.device != x.device or \
+            not out.is_contiguous():
+        raise L.SpkError(f"out: expected a contiguous float32 HIP tensor {(N, 3, 2)} on {x.device}")
+    ws = _colour_workspace(x.device, N)
+    L.check(L.lib().spk_paste_colour_match_nv12_sim(*head, y.data_ptr(), *ys, uv.data_ptr(), *us, H, W, rows.data_ptr(), *tail, *matte_args,
+                                                    max_gain, min_sigma, min_weight, out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                                    L.stream_ptr()), "spk_paste_colour_match_nv12_sim")
     return out
 
 

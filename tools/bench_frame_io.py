@@ -31,6 +31,13 @@
     ``IRFD.reenact_video(align=, paste=True)`` beside ``reenact_video(crop=, paste=True)``.  The contenders alternate in one process,
     medians are compared, and the aligned launcher runs twice per round: the distance of its two medians is the recorded spread.
 
+``--align-nv12``: the aligned edge on NV12 surfaces (csrc/frame_sim_nv12.hip): 8 surfaces of 1080 x 1920, the rows of ``--align``, a
+    256^2 network, feather 16, the default ellipse matte, in place.  ``ops.frames_from_nv12_aligned``, ``ops.paste_colour_match_nv12``
+    and ``ops.frames_paste_nv12_aligned``, each beside its axis-aligned NV12 sibling (``frames_from_nv12`` / ``frames_paste_nv12``
+    with tracked boxes; the statistics have none), beside its packed-RGB aligned sibling, and beside the detour a user has without
+    it: torch NV12 -> BGR in front of the RGB launcher on the way in, torch BGR -> NV12 behind it on the way out.  HIP events, the
+    contenders alternate in one process, medians of 7 rounds, each new launcher twice per round for the spread.
+
 ``--landmarks``: landmarks -> rows on the device (csrc/landmark_sim.hip): T = 64 and 1024 frames, K = 5 and 68 landmarks.
     ``ops.similarity_from_landmarks`` and ``ops.smooth_similarity_rows(radius 2)``, each alone and both together (HIP events), and
     the two launches beside the host route they replace -- ``.cpu()``, the numpy fit and smoothing of tests/landmark_ref.py (a
@@ -46,7 +53,7 @@
     times are compared, and the plain paste runs twice per round: the distance of its two medians is the recorded spread.
     ``--commit`` names the commit the table is taken at.
 
-    python tools/bench_frame_io.py [--paste | --nv12 | --align | --landmarks | --blend] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
+    python tools/bench_frame_io.py [--paste | --nv12 | --align | --align-nv12 | --landmarks | --blend] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
 import math
@@ -332,6 +339,21 @@ def alternate(contenders, repeats, timer):
     return {n: sorted(ts) for n, ts in times.items()}
 
 
+def ratio_table(lines, title, times, ours, others):
+    """One table of ``alternate``'s times: every contender, the spread of the contender entered twice (``ours`` and ``ours +
+    " (again)"``), and ``ours`` over each of ``others`` -- ``(name, True)`` adds the verdict against the spread."""
+    lines.append(title)
+    med = {n: statistics.median(ts) for n, ts in times.items()}
+    for n, ts in times.items():
+        lines.append(f"  {n:44s} median {med[n] * 1e6:9.1f} us  min {ts[0] * 1e6:9.1f}  max {ts[-1] * 1e6:9.1f}")
+    spread = abs(med[ours] - med[ours + " (again)"]) / min(med[ours], med[ours + " (again)"])
+    lines.append(f"  spread of the repeated contender: {spread * 100:.2f} %")
+    for n, verdict in others:
+        r = med[ours] / med[n]
+        how = "" if not verdict else ("  -> faster by more than the spread" if r < 1 - spread else "  -> NOT faster by more than the spread")
+        lines.append(f"  {ours} / {n} = {r:.3f}{how}")
+
+
 def bench_align(args, lines):
     """``--align``: the aligned edge (csrc/frame_sim.hip) beside the axis-aligned launchers (their kernels are the parent
     commit's) and beside the torch compositions a user has without it; the aligned launcher is a contender twice, and the
@@ -352,16 +374,7 @@ def bench_align(args, lines):
     fwd, inv, scale = (t.to(dev) for t in align_thetas(rows.cpu(), Hf, Wf, size, size))
 
     def table(title, times, ours, others):
-        lines.append(title)
-        med = {n: statistics.median(ts) for n, ts in times.items()}
-        for n, ts in times.items():
-            lines.append(f"  {n:44s} median {med[n] * 1e6:9.1f} us  min {ts[0] * 1e6:9.1f}  max {ts[-1] * 1e6:9.1f}")
-        spread = abs(med[ours] - med[ours + " (again)"]) / min(med[ours], med[ours + " (again)"])
-        lines.append(f"  spread of the repeated contender: {spread * 100:.2f} %")
-        for n, verdict in others:
-            r = med[ours] / med[n]
-            how = "" if not verdict else ("  -> faster by more than the spread" if r < 1 - spread else "  -> NOT faster by more than the spread")
-            lines.append(f"  {ours} / {n} = {r:.3f}{how}")
+        ratio_table(lines, title, times, ours, others)
 
     # ---- (1), (2) the way in ----
     video = torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
@@ -410,6 +423,73 @@ def bench_align(args, lines):
         times = alternate(contenders, args.repeats, wall)
     table(f"T = {T} frames of {Hf}x{Wf} BGR, chunk {chunk}, {args.repeats} alternating rounds after {args.warmup} warm-up rounds (wall, synchronised):",
            times, "reenact_video(align=, paste=True)", [("reenact_video(crop=, paste=True)", False)])
+
+
+def bench_align_nv12(args, lines):
+    """``--align-nv12``: the three launchers of the aligned NV12 edge (csrc/frame_sim_nv12.hip), each beside its axis-aligned NV12
+    sibling, its packed-RGB aligned sibling and the detour a user has without it (torch NV12 <-> BGR around the RGB launchers), at
+    8 x 1080 x 1920 surfaces, s = 400 / 256, angles within +-0.3 rad, 256^2, feather 16, the default ellipse matte, in place.  Each
+    launcher is a contender twice; the distance of its two medians is the spread the other differences are read against."""
+    import importlib
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    chunk, size, Hf, Wf, side, feather = args.chunk, 256, 1080, 1920, 400, 16
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(chunk)]
+    angles = [0.3 * math.sin(0.9 * t) for t in range(chunk)]
+    yx = torch.tensor(boxes, dtype=torch.int32, device=dev)
+    box = (yx, side, side)
+    rows = ops.similarity_rows([(y + side / 2, x + side / 2) for y, x in boxes], float(side), angles, size).to(dev)
+    to_rgb, from_rgb = (t.float().to(dev) for t in ops.yuv_coeffs())
+    bgr = torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    surf = torch_bgr_to_nv12(bgr, from_rgb)                                # in-gamut surfaces of the same pictures
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    matte = ops.ellipse_matte((size, size), device=dev)
+    shape = f"{chunk} x {Hf}x{Wf} NV12, 256^2, s = {side}/256, angles within +-0.3 rad"
+    how = f"HIP events, launcher included, median of {args.repeats} alternating rounds of 20"
+
+    # ---- the way in ----
+    ours = lambda: ops.frames_from_nv12_aligned(surf, size, rows)                          # noqa: E731
+    name = "frames_from_nv12_aligned"
+    contenders = {name: ours, "frames_from_nv12(crop=(yx, 400, 400))": lambda: ops.frames_from_nv12(surf, size, crop=box),
+                  "frames_from_u8_aligned (BGR frames)": lambda: ops.frames_from_u8_aligned(bgr, size, rows, channel_order="bgr"),
+                  "torch NV12 -> BGR + frames_from_u8_aligned": lambda: ops.frames_from_u8_aligned(torch_nv12_to_bgr(surf, to_rgb), size, rows, channel_order="bgr"),
+                  name + " (again)": ours}
+    diff = (ours() - contenders["torch NV12 -> BGR + frames_from_u8_aligned"]()).abs().max()
+    ratio_table(lines, f"way in: {shape}; {how}; largest |ours - detour| = {float(diff):.4f} on (-1, 1) (surfaces of random "
+                f"pictures are out of gamut at many pixels: the detour clamps and rounds every pixel before the filter, this launcher clamps once after it)",
+                alternate(contenders, args.repeats, device_time), name,
+                [("frames_from_nv12(crop=(yx, 400, 400))", False), ("frames_from_u8_aligned (BGR frames)", False), ("torch NV12 -> BGR + frames_from_u8_aligned", True)])
+
+    # ---- the statistics ----
+    kw, kw_bgr = dict(matte=matte, feather=feather), dict(matte=matte, feather=feather, channel_order="bgr")
+    colour = ops.paste_colour_match_nv12(x, surf, rows, **kw)
+    colour_bgr = ops.paste_colour_match(x, bgr, rows, **kw_bgr)
+    ours = lambda: ops.paste_colour_match_nv12(x, surf, rows, out=colour, **kw)            # noqa: E731
+    name = "paste_colour_match_nv12"
+    contenders = {name: ours, "paste_colour_match (BGR frames)": lambda: ops.paste_colour_match(x, bgr, rows, out=colour_bgr, **kw_bgr),
+                  "torch NV12 -> BGR + paste_colour_match": lambda: ops.paste_colour_match(x, torch_nv12_to_bgr(surf, to_rgb), rows, out=colour_bgr, **kw_bgr),
+                  name + " (again)": ours}
+    dg = (colour[:, :, 0] / colour_bgr[:, :, 0] - 1).abs().max()
+    ratio_table(lines, f"statistics: {shape}, ellipse matte, feather {feather}; {how}; there is no axis-aligned sibling; largest relative distance "
+                f"of the gains from those over the BGR frames the surfaces were made from = {float(dg):.4f}", alternate(contenders, args.repeats, device_time), name,
+                [("paste_colour_match (BGR frames)", False), ("torch NV12 -> BGR + paste_colour_match", True)])
+
+    # ---- the way out ----
+    ours = lambda: ops.frames_paste_nv12_aligned(x, surf, rows, colour=colour, out=surf, **kw)                    # noqa: E731
+    name = "frames_paste_nv12_aligned(matte, colour)"
+
+    def detour():                                                         # the parent's route to an NV12 encoder: paste into BGR, then convert the frames
+        ops.frames_paste_u8_aligned(x, bgr, rows, colour=colour_bgr, out=bgr, **kw_bgr)
+        return torch_bgr_to_nv12(bgr, from_rgb)
+
+    contenders = {name: ours, "frames_paste_nv12(box=(yx, 400, 400))": lambda: ops.frames_paste_nv12(x, surf, box, feather=feather, out=surf),
+                  "frames_paste_u8_aligned(matte, colour) (BGR)": lambda: ops.frames_paste_u8_aligned(x, bgr, rows, colour=colour_bgr, out=bgr, **kw_bgr),
+                  "frames_paste_u8_aligned + torch BGR -> NV12": detour, name + " (again)": ours}
+    ratio_table(lines, f"way out: {shape}, ellipse matte, colour rows, feather {feather}, in place; {how}", alternate(contenders, args.repeats, device_time),
+                name, [("frames_paste_nv12(box=(yx, 400, 400))", False), ("frames_paste_u8_aligned(matte, colour) (BGR)", False),
+                       ("frames_paste_u8_aligned + torch BGR -> NV12", True)])
 
 
 def torch_blend_paste(y, video_out, theta_inv, scale, feather, matte, colour_match, max_gain=2.0):
@@ -567,7 +647,8 @@ def main():
     ap.add_argument("--nv12", action="store_true", help="the NV12 form of the edge: its kernels and reenact_video(pixel_format='nv12', paste=True)")
     ap.add_argument("--align", action="store_true", help="the aligned edge: frames_from_u8_aligned, frames_paste_u8_aligned, reenact_video(align=)")
     ap.add_argument("--blend", action="store_true", help="the seamless paste-back: matte, colour match and their torch composition")
-    ap.add_argument("--commit", default="unknown", help="--blend: the commit the table is taken at, for its first line")
+    ap.add_argument("--align-nv12", action="store_true", help="the aligned NV12 edge: its three launchers beside their siblings and the BGR detour")
+    ap.add_argument("--commit", default="unknown", help="--blend / --align-nv12: the commit the table is taken at, for its first line")
     ap.add_argument("--landmarks", action="store_true", help="landmarks -> rows: similarity_from_landmarks, smooth_similarity_rows, the host route")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -576,6 +657,10 @@ def main():
         lines = [f"bench_frame_io --blend: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
         bench_blend(args, lines)
         return report(lines, args.out or os.path.join(ROOT, "profiles", "blend_bench.txt"))
+    if args.align_nv12:
+        lines = [f"bench_frame_io --align-nv12: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_align_nv12(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "align_nv12_bench.txt"))
     if args.landmarks:
         lines = [f"bench_frame_io --landmarks: {torch.cuda.get_device_name(0)}"]
         bench_landmarks(args, lines)

@@ -779,8 +779,8 @@ int spk_frames_paste_u8_sim(const float* src, int N, int Hs, int Ws, uint8_t* ds
  * spk_frames_paste_u8_sim blends the whole generated square with a rectangular ramp: the generator's own background is pasted
  * over the real one, and the decoder's tone is not the camera's.  These entry points add what every face pipeline adds: an alpha
  * MATTE in generated-image coordinates (the face sits at the same place in every aligned crop, so one static matte serves a clip;
- * a per-frame matte of a segmentation network drops in), and a per-channel COLOUR MATCH of the generated face to the pixels it
- * replaces, whose statistics are sums over exactly the pixels the paste visits.
+ * a per-frame matte drops in, and spk_matte_from_landmarks below makes one from the tracked contour), and a per-channel COLOUR
+ * MATCH of the generated face to the pixels it replaces, whose statistics are sums over exactly the pixels the paste visits.
  *
  * THE PER-PIXEL QUANTITIES.  For a region pixel (Y, X) of frame n: (u, v), r, w_u, w_v, val, q, b, a_u and a_v are exactly those of
  * spk_frames_paste_u8_sim above (q: fp32, not rounded, of network channel c; b: the background byte at c' = swap_rb ? 2 - c : c).
@@ -864,6 +864,47 @@ int spk_paste_colour_match_sim(const float* src, int N, int Hs, int Ws, const ui
 int spk_sim_fit_landmarks(const float* pts_dev, const float* weights_dev, int64_t weight_stride, const float* tmpl_dev, int N, int K,
                           double offset, float* sim_dev, void* stream);
 int spk_sim_smooth(const float* sim_in_dev, int N, int radius, double sigma, float* sim_out_dev, void* stream);
+
+/* ---- a face matte per frame from the landmarks' contour, rasterised and smoothed on the device (csrc/landmark_matte.hip) ----------
+ * The blend above takes a matte; this makes one that follows the tracked face: the closed outline through Kc of a frame's
+ * landmarks (jaw and brows, say), carried into the generated image, steadied over time, and turned into a signed-distance ramp.
+ * Plain device pointers and a stream: one launch, no allocation, no synchronisation, no device value read on the host.
+ *
+ * spk_matte_from_landmarks: pts_dev fp32 [N][K][2], (x, y) in frame coordinates, `offset` added to both, as spk_sim_fit_landmarks.
+ *   sim_dev fp32 [N][4]: the rows of the section "aligned crops", which map the coordinates of the Hs x Ws GENERATED image to frame
+ *   n, VALID by that section's rule (finite, 1/16 <= s <= 16).  contour_host: Kc landmark indices in outline order, an int32 HOST
+ *   array, 3 <= Kc <= 128, each in [0, K); checked on the host and handed to the kernel by value.  fallback_dev: fp32 [Kc][2] in
+ *   generated-image coordinates (the template's contour), or NULL.  matte_dev fp32 [N][Hs][Ws], contiguous.  Everything is promoted
+ *   to fp64.
+ *   THE MAPPED POINT of frame f and contour index k, with (x, y) = pts[f][contour[k]] + offset, dx = x - tx, dy = y - ty of row f:
+ *     u = (a dx + c dy) / s^2,   v = (-c dx + a dy) / s^2,   s^2 = a^2 + c^2          (the inverse of the row: p = (u, v))
+ *   It TAKES PART when row f is valid and x, y are finite.
+ *   THE TEMPORAL WINDOW is the rule of spk_sim_smooth: radius in [0, 64], sigma finite and > 0, g(d) = exp(-d^2 / (2 sigma^2)),
+ *     P[n][k] = sum_d g(d) p[n + d][k] / sum_d g(d)        d = -radius ... radius in that order, 0 <= n + d < N, p[n + d][k] takes part
+ *   so radius = 0 is the frame's own point, not averaged, and a drop-out of up to `radius` frames is bridged from its neighbours.
+ *   When no point of the window takes part (or sum_d g(d) is 0: every g underflowed), P[n][k] = fallback_dev[k]: a still outline
+ *   instead of a hole.  When that point is needed and fallback_dev is NULL, or the fallback point is not finite, the whole matte
+ *   of frame n is zeros.
+ *   THE RASTER.  For pixel (j, i) with centre p = (i + 0.5, j + 0.5), over the Kc edges (A, B) = (P[e], P[(e + 1) mod Kc]):
+ *     t      = clamp(((p - A) . (B - A)) / |B - A|^2, 0, 1)          an edge with |B - A|^2 = 0 counts as the point A (t = 0)
+ *     dist   = min_e |p - (A + t (B - A))|
+ *     inside = the parity of the number of edges with (A.y > p.y) != (B.y > p.y) and p.x < A.x + (p.y - A.y) (B.x - A.x) / (B.y - A.y)
+ *     d      = inside ? dist : -dist
+ *     matte[n][j][i] = (float) clamp((d + grow) / softness, 0, 1)
+ *   Even-odd parity: a concave or a self-crossing outline has a defined answer.  softness: finite and > 0, the width of the ramp
+ *   in generated pixels; grow: finite, moves the outline outwards (inwards when negative) -- with grow = 0 the matte is 0 ON the
+ *   outline, so nothing outside the tracked face is pasted.
+ *   A workgroup serves a band of rows of one frame: its first Kc threads build the smoothed outline and the edges' constants in
+ *   LDS (7 KiB of fp64), then every thread walks its pixels over the edges; a pixel farther than max(grow, 0) outside the
+ *   outline's bounding box is 0 without that walk, which is what the formula gives there.  A frame's matte depends on the frames
+ *   of its own window only; at radius = 0 a frame alone and the same frame in a batch give the same bits.
+ *   Refused before any launch (SPK_EINVAL, spk_last_error): null pts / sim / contour / matte; N < 1; K < 1 or K > 4096; Kc outside
+ *   [3, 128] or an index outside [0, K); Hs or Ws outside [1, 4096]; radius outside [0, 64]; sigma or softness not finite or <= 0;
+ *   grow or offset not finite.  replaces: a device -> host copy of the landmarks, cv2.fillPoly and a blur per frame, and an upload
+ *   of N Hs Ws floats in the middle of the chunk loop. */
+int spk_matte_from_landmarks(const float* pts_dev, int N, int K, double offset, const float* sim_dev, const int32_t* contour_host, int Kc,
+                             const float* fallback_dev, int radius, double sigma, double softness, double grow, float* matte_dev, int Hs,
+                             int Ws, void* stream);
 
 /* ---- the video-frame edge in NV12 form (csrc/frame_nv12.hip) ---------------------------------------------------------------------
  * What a hardware decoder or encoder holds in device memory, in and out of the network without a packed-RGB detour.

@@ -649,6 +649,172 @@ class LandmarkAlign:
         return smooth_similarity_rows(rows, self.smooth, self.sigma) if self.smooth > 0 else rows
 
 
+# ---- a matte per frame from the landmarks' contour (csrc/landmark_matte.hip; the definitions are in include/spk.h) -----------------
+CONTOUR_POINTS, MATTE_SIZE_MAX = (3, 128), 4096                           # Kc and Hs, Ws as the entry point bounds them
+
+
+def _check_contour(contour, K, what):                                     # -> a list of ints; K=None: the indices' range is checked later
+    try:
+        idx = torch.as_tensor(contour)
+    except (ValueError, TypeError, RuntimeError) as e:
+        raise ValueError(f"{what}: contour must be landmark indices in outline order: {e}") from None
+    if idx.is_cuda or idx.dim() != 1 or idx.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8) or \
+            not CONTOUR_POINTS[0] <= idx.numel() <= CONTOUR_POINTS[1]:
+        raise ValueError(f"{what}: contour must be {CONTOUR_POINTS[0]} to {CONTOUR_POINTS[1]} integer landmark indices on the host, "
+                         f"got {idx.dtype} {tuple(idx.shape)} on {idx.device}")
+    idx = idx.tolist()
+    return idx if K is None else _contour_in(idx, K, what)
+
+
+def _contour_in(idx, K, what):
+    if min(idx) < 0 or max(idx) >= K:
+        raise ValueError(f"{what}: contour holds an index outside [0, {K}): the landmarks have {K} points per frame")
+    return idx
+
+
+def _check_matte_landmarks(landmarks, what):
+    if not isinstance(landmarks, torch.Tensor) or landmarks.dim() != 3 or landmarks.size(2) != 2 or landmarks.size(0) < 1 or \
+            not 1 <= landmarks.size(1) <= LANDMARKS_MAX:
+        got = tuple(landmarks.shape) if isinstance(landmarks, torch.Tensor) else type(landmarks).__name__
+        raise ValueError(f"{what}: landmarks must be a tensor [N,K,2] with 1 <= K <= {LANDMARKS_MAX}, got {got}")
+    return landmarks
+
+
+def _finite(v, name, what, positive=False):
+    try:
+        v = float(v)
+    except (ValueError, TypeError):
+        raise ValueError(f"{what}: {name} must be a number, got {v!r}") from None
+    if not (-float("inf") < v < float("inf")) or (positive and v <= 0.0):
+        raise ValueError(f"{what}: {name} must be a finite number{' > 0' if positive else ''}, got {v}")
+    return v
+
+
+def _check_fallback(fallback, Kc, what):                                  # host points: rounded to fp32 and checked; device points: not read
+    if fallback is None:
+        return None
+    if isinstance(fallback, torch.Tensor) and fallback.is_cuda:
+        if fallback.dtype != torch.float32 or tuple(fallback.shape) != (Kc, 2):
+            raise ValueError(f"{what}: a device fallback must be a float32 tensor [{Kc},2], got {fallback.dtype} {tuple(fallback.shape)}")
+        return fallback
+    try:
+        fallback = torch.as_tensor(fallback).to(torch.float64).to(torch.float32)
+    except (ValueError, TypeError, RuntimeError) as e:
+        raise ValueError(f"{what}: fallback must be [{Kc},2] points (u, v): {e}") from None
+    if tuple(fallback.shape) != (Kc, 2) or not bool(torch.isfinite(fallback).all()):
+        raise ValueError(f"{what}: fallback must be [{Kc},2] finite points (u, v), one per contour index, got {tuple(fallback.shape)}")
+    return fallback
+
+
+def _matte_size(size_hw, what):
+    Hs, Ws = _out_size(size_hw, what)
+    if Hs > MATTE_SIZE_MAX or Ws > MATTE_SIZE_MAX:
+        raise ValueError(f"{what}: size must be <= {MATTE_SIZE_MAX}, got {size_hw}")
+    return Hs, Ws
+
+
+def _matte(landmarks, rows, Hs, Ws, idx, softness, grow, offset, fallback, radius, sigma, what):   # checked arguments -> [N,Hs,Ws], one launch
+    if not landmarks.is_cuda or landmarks.dtype != torch.float32:
+        raise L.SpkError(f"{what}: landmarks: expected a float32 HIP tensor, got {landmarks.dtype} on {landmarks.device} (no CPU path)")
+    N, K, _ = landmarks.shape
+    landmarks = landmarks.contiguous()
+    rows = _sim_on(rows, landmarks.device, what)
+    if fallback is not None:                                              # a host outline: uploaded once
+        if fallback.is_cuda and fallback.device != landmarks.device:
+            raise L.SpkError(f"{what}: fallback on {fallback.device}, landmarks on {landmarks.device}")
+        fallback = fallback.to(landmarks.device).contiguous()
+    out = torch.empty((N, Hs, Ws), device=landmarks.device, dtype=torch.float32)
+    L.check(L.lib().spk_matte_from_landmarks(landmarks.data_ptr(), N, K, offset, rows.data_ptr(), (C.c_int32 * len(idx))(*idx), len(idx),
+                                             _ptr(fallback), radius, sigma, softness, grow, out.data_ptr(), Hs, Ws, L.stream_ptr()),
+            "spk_matte_from_landmarks")
+    return out
+
+
+def matte_from_landmarks(landmarks, sim, size_hw, contour, *, softness=4.0, grow=0.0, offset=0.0, fallback=None, smooth=0, sigma=None):
+    """A face matte per frame for ``frames_paste_u8_aligned(matte=)`` / ``frames_paste_nv12_aligned(matte=)`` from the landmarks
+    themselves, one launch (``spk_matte_from_landmarks``; include/spk.h has the definitions): the closed outline through the
+    landmarks ``contour`` names (the jaw line and the brows, say, in outline order), carried through each frame's row into the
+    ``size_hw`` generated image, and ``M = clip((d + grow) / softness, 0, 1)`` of the signed distance ``d`` of every pixel centre to
+    it (positive inside; even-odd parity, so a concave or self-crossing outline is defined) -- a matte that follows the jaw when the
+    mouth opens, where ``ellipse_matte`` is one oval for the clip.  ``landmarks``: a device float32 ``[N,K,2]`` tensor of ``(x, y)``
+    in frame coordinates, ``offset`` added to both (``similarity_from_landmarks``).  ``sim``: the rows that map the GENERATED image
+    into the frames, in the two forms of ``frames_paste_u8_aligned`` (host rows are checked, device rows are not read; a point
+    of an invalid row or with a coordinate that is not finite takes no part).  ``contour``: 3 to 128 integer indices in ``[0, K)``, a
+    host sequence.  ``softness > 0``: the ramp's width in generated pixels; ``grow``: moves the outline outwards by that many pixels
+    (0: nothing outside the tracked face is pasted).  ``smooth`` / ``sigma``: every outline point is averaged over frames
+    ``n - smooth ... n + smooth`` with the weights of ``smooth_similarity_rows``, points that take no part left out, so a drop-out
+    is bridged; a point without any participant comes from ``fallback`` -- ``[Kc,2]`` points in generated-image coordinates, a
+    host sequence (checked, uploaded once) or a device float32 tensor -- and without a fallback that frame's matte is zeros.
+    -> device float32 ``[N,Hs,Ws]``."""
+    what = "matte_from_landmarks"
+    landmarks = _check_matte_landmarks(landmarks, what)
+    Hs, Ws = _matte_size(size_hw, what)
+    idx = _check_contour(contour, landmarks.size(1), what)
+    softness, grow, offset = _finite(softness, "softness", what, positive=True), _finite(grow, "grow", what), _finite(offset, "offset", what)
+    radius, sigma = _check_smooth(smooth, sigma, f"{what}: smooth")
+    rows = parse_sim(sim, landmarks.size(0), f"{what}: sim")
+    fallback = _check_fallback(fallback, len(idx), what)
+    return _matte(landmarks, rows, Hs, Ws, idx, softness, grow, offset, fallback, radius, sigma, what)
+
+
+class LandmarkMatte:
+    """``IRFD.reenact_video(matte=...)`` from landmarks: what ``matte_from_landmarks`` takes, kept until the call knows its rows and
+    the generated size ``R``.  ``landmarks=None``: the landmarks of the call's ``align=LandmarkAlign(...)`` (without one:
+    ``ValueError``); ``offset`` / ``smooth`` (with its ``sigma``) ``=None``: that ``LandmarkAlign``'s when the call has one, else 0.
+    ``fallback``: ``"template"`` -- the contour's points of the ``LandmarkAlign``'s template (it needs one) -- or ``[Kc,2]`` points, a
+    host sequence, like the template in the coordinates of the ``size`` network image and scaled to ``R`` with it; or None.  The
+    matte is made once per clip, with the rows the paste uses, so the window sees every frame and the result does not depend on
+    ``chunk``.  The host arguments are checked here and in ``bind`` (``ValueError``), the device ones when the matte is made."""
+
+    def __init__(self, contour, *, landmarks=None, softness=4.0, grow=0.0, offset=None, fallback="template", smooth=None, sigma=None):
+        what = "LandmarkMatte"
+        self.landmarks = None if landmarks is None else _check_matte_landmarks(landmarks, what)
+        self.contour = _check_contour(contour, None if landmarks is None else landmarks.size(1), what)
+        self.softness, self.grow = _finite(softness, "softness", what, positive=True), _finite(grow, "grow", what)
+        self.offset = None if offset is None else _finite(offset, "offset", what)
+        if smooth is None and sigma is not None:
+            raise ValueError(f"{what}: sigma comes with smooth")
+        self.smooth = None if smooth is None else _check_smooth(smooth, sigma, f"{what}: smooth")
+        if isinstance(fallback, str):
+            if fallback != "template":
+                raise ValueError(f"{what}: fallback must be 'template', [{len(self.contour)},2] points or None, got {fallback!r}")
+        elif isinstance(fallback, torch.Tensor) and fallback.is_cuda:
+            raise ValueError(f"{what}: fallback points are a host sequence (they are scaled to the generated size before the upload)")
+        else:
+            fallback = _check_fallback(fallback, len(self.contour), what)
+        self.fallback = fallback
+
+    def bind(self, align, T, what="reenact_video: matte"):
+        """The carrier against the call's ``align=`` and its ``T`` frames, on the host: -> ``make(aligned, size)``, which takes what
+        ``Aligned.chunk(0, T, y)`` gave (the clip's rows scaled to the generated size) and the ``(H, W)`` of the network image
+        -> device float32 ``[T,Hs,Ws]``, one launch."""
+        la = align if isinstance(align, LandmarkAlign) else None
+        landmarks = self.landmarks
+        if landmarks is None:
+            if la is None:
+                raise ValueError(f"{what}: LandmarkMatte(landmarks=None) takes its landmarks from align=LandmarkAlign(...), and align is not one")
+            landmarks = la.landmarks
+        if landmarks.size(0) != T:
+            raise ValueError(f"{what}: landmarks of {landmarks.size(0)} frames for {T} frames")
+        idx = _contour_in(self.contour, landmarks.size(1), what)
+        offset = self.offset if self.offset is not None else la.offset if la is not None else 0.0
+        radius, sigma = self.smooth if self.smooth is not None else (la.smooth, la.sigma) if la is not None else _check_smooth(0, None, what)
+        fallback = self.fallback
+        if isinstance(fallback, str):
+            if la is None or la.template.is_cuda:
+                raise ValueError(f"{what}: fallback='template' needs align=LandmarkAlign(...) with a host template")
+            if max(idx) >= la.template.size(0):
+                raise ValueError(f"{what}: contour holds an index outside the template's {la.template.size(0)} points")
+            fallback = la.template[idx]
+
+        def make(aligned, size):
+            Hs, Ws = _matte_size(aligned.size, what)
+            k = torch.tensor(Ws / size[1], dtype=torch.float32)               # the template lives in the network image: scaled in fp32
+            return _matte(landmarks, aligned.rows, Hs, Ws, idx, self.softness, self.grow, offset, None if fallback is None else fallback * k,
+                          radius, sigma, what)
+        return make
+
+
 # ---- NV12 (csrc/frame_nv12.hip; the definitions are in include/spk.h) ---------------------------------------------------------------
 def yuv_standard(standard, full_range):
     if standard not in ("bt601", "bt709"):

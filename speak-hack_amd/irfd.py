@@ -209,8 +209,11 @@ class IRFD(nn.Module):
         ``matte`` / ``colour_match`` (both need ``align=``, ``paste=True`` and packed RGB; anything else: ``ValueError`` before any
         launch): a seamless paste.  ``matte``: a float32 ``[R,R]`` (one for the clip: ``ops.ellipse_matte``) or ``[T,R,R]`` tensor
         in the generated image's size where the frames are, multiplied into the blend weight so that only the face is pasted, not
-        the generator's own background.  ``colour_match=True``: per frame and channel the generated face is brought to the mean and
-        standard deviation of the pixels it replaces (``ops.paste_colour_match``) -- each chunk makes one
+        the generator's own background; or an ``ops.LandmarkMatte`` -- the outline through some of the tracked landmarks, by default
+        those of ``align=LandmarkAlign(...)``, rasterised and smoothed over the clip on the device (``ops.matte_from_landmarks``): one
+        ``spk_matte_from_landmarks`` launch per call, at the first chunk, from the rows the paste uses, then sliced per chunk as a
+        ``[T,R,R]`` tensor is, so the result does not depend on ``chunk``.  ``colour_match=True``: per frame and channel the
+        generated face is brought to the mean and standard deviation of the pixels it replaces (``ops.paste_colour_match``) -- each chunk makes one
         ``spk_paste_colour_match_sim`` call, then one ``spk_frames_paste_u8_sim_blend`` call (``ops.frames_paste_u8_aligned(matte=,
         colour=)``) with the rows the paste uses anyway.  The statistics are per frame and read the background before the paste, on
         the same stream: the result depends neither on ``chunk`` nor on ``inplace``."""
@@ -232,13 +235,16 @@ class IRFD(nn.Module):
             raise ValueError("reenact_video: align applies to pixel_format='rgb24' only (NV12 frames take crop boxes)")
         if not isinstance(colour_match, bool):
             raise ValueError(f"reenact_video: colour_match must be a bool, got {colour_match!r}")
-        blend = {}
+        blend, landmark_matte = {}, None
         if matte is not None or colour_match:
             if align is None or not paste:
                 raise ValueError("reenact_video: matte / colour_match apply to align= with paste=True only")
-            if matte is not None and (not isinstance(matte, torch.Tensor) or matte.dtype != torch.float32 or matte.dim() not in (2, 3)):
+            if isinstance(matte, FR.LandmarkMatte):                        # made at the first chunk, when the generated size is known
+                landmark_matte, matte = matte, None
+            elif matte is not None and (not isinstance(matte, torch.Tensor) or matte.dtype != torch.float32 or matte.dim() not in (2, 3)):
                 got = f"{matte.dtype} {tuple(matte.shape)}" if isinstance(matte, torch.Tensor) else type(matte).__name__
-                raise ValueError(f"reenact_video: matte must be a float32 tensor [R,R] or [T,R,R] in the generated image's size, got {got}")
+                raise ValueError(f"reenact_video: matte must be a float32 tensor [R,R] or [T,R,R] in the generated image's size, or an "
+                                 f"ops.LandmarkMatte, got {got}")
             blend = dict(matte=matte, colour_match=colour_match)
         fmt = FR.PIXEL_FORMATS[pixel_format](channel_order, standard, full_range)
         if identity_align is not None:                                     # host rows: checked here, before any launch
@@ -248,6 +254,8 @@ class IRFD(nn.Module):
             pose_in, device, T, H, W = fmt.open(pose_u8, inplace)
             if matte is not None and matte.dim() == 3 and matte.size(0) != T:
                 raise ValueError(f"reenact_video: a per-frame matte must carry {T} frames, got {tuple(matte.shape)}")
+            if landmark_matte is not None:                                 # the carrier against align= and T: on the host, before any launch
+                landmark_matte = landmark_matte.bind(align, T)
             crop = FR.Aligned.parse(align, T, size, device)
         elif crop is not None or paste or fmt.needs_box:
             pose_in, device, T, H, W = fmt.open(pose_u8, inplace)
@@ -267,6 +275,8 @@ class IRFD(nn.Module):
         result, out = (pose_u8, pose_in) if inplace else fmt.clone(pose_in)
         for t0, t1, y in self._reenact_chunks(ident, pose, emo, noises, chunk, "f32", "rgb", seed, noise, frame0):
             where = crop.chunk(t0, t1, y) if align is not None else crop if len(crop) == 4 else (crop[0][t0:t1], h, w)
+            if landmark_matte is not None:                                 # once per clip: the window sees every frame, whatever the chunk
+                blend["matte"], landmark_matte = landmark_matte(crop.chunk(0, T, y), crop.size), None
             fmt.paste(y, out, t0, t1, where, feather, **blend)
         return result
 

@@ -1019,6 +1019,49 @@ int spk_paste_colour_match_nv12_sim(const float* src, int N, int Hs, int Ws, con
                                     double max_gain, double min_sigma, double min_weight, float* colour_out_dev, void* workspace_dev,
                                     size_t workspace_bytes, void* stream);
 
+/* ---- flicker-free colour match: the statistics pooled over a window of frames (csrc/colour_window.hip) ---------------------------
+ * The colour rows above are made one frame at a time, and the background under the matte changes from frame to frame (hair over
+ * the outline, a passing hand, hunting exposure): rows that follow every such change make the pasted face pump in brightness and
+ * contrast.  The quantity to steady over time is not the row but the 13 SUMS it comes from.  They are linear, so a weighted sum
+ * of them over neighbouring frames is again a set of sums of the same meaning; a frame that contributes nothing takes no part
+ * instead of pulling its neighbours towards the (1, 0) it got by rule; and o, which depends on g through the frame's own mean, is
+ * computed once, from pooled means.  Plain device pointers and a stream, no allocation, no synchronisation.
+ *
+ * spk_paste_colour_sums_sim / spk_paste_colour_sums_nv12_sim: the leading arguments of spk_paste_colour_match_sim /
+ *   spk_paste_colour_match_nv12_sim up to and including matte_frames, with their meaning and their refusals; then sums_out_dev,
+ *   fp64 [N][13] in the order S0, (Sq, Sqq, Sb, Sbb) of network channel 0, 1, 2 (8-byte aligned); then the same workspace and
+ *   stream.  No max_gain, min_sigma or min_weight: those belong to the row formula.  Two launches: the statistics kernel of the
+ *   match, then a reducer that adds a frame's partials in index order and stores the 13 totals -- bit for bit the sums the match
+ *   forms internally for the same inputs -- or 13 zeros for a frame whose sim row is invalid.  The same determinism clause: no
+ *   atomics, the same inputs give the same bits.
+ * spk_colour_rows_window: sums_dev fp64 [T][13], the sums of a clip of T frames; rows_out_dev fp32 [n][3][2], the rows of frames
+ *   n0 ... n0 + n - 1.  One launch.  All arithmetic is fp64.  With k_d = exp(-d^2 / (2 sigma^2)) for |d| <= radius:
+ *     frame j TAKES PART in the window of frame t (d = j - t) iff  0 <= j < T,  S0_j > min_weight (a NaN fails),  and, for d != 0,
+ *                                                                   all 13 of its sums are finite
+ *     P_i = sum_d k_d S_i[t + d]                   i = 0 ... 12, over the frames that take part, added in ascending d
+ *     row = (1, 0) for the three channels          when no frame takes part
+ *     row = the row formula of spk_paste_colour_match_sim on P (mu, var with its max(., 0), the min_sigma^2 test, the gain clamp,
+ *           o from the unrounded g, each rounded to fp32 once)                                  otherwise
+ *   Consequences.  radius = 0: k_0 = 1 exactly, so the rows are bit for bit those of the match entry points on the same inputs.
+ *   A gap of up to `radius` unusable frames is bridged from its neighbours, the rule of spk_sim_smooth.  Every frame contributes
+ *   in proportion to its weighted area S0.  A frame's row depends on the sums of its own window only: any sub-range gives the bits
+ *   of the whole clip, so a caller may ask for the rows of a chunk as soon as the sums up to its last frame + radius exist.  (When
+ *   frames take part but every k_d of theirs underflowed -- frame t itself is out and sigma is far below 1 -- P is all zeros and
+ *   the row is not finite, which the paste reads as (1, 0).)  A thread per frame, the weights once per workgroup in LDS.
+ *   Refused: null pointers; a sums array that is not 8-byte aligned; T < 1; n < 1, n0 < 0 or n0 + n > T; radius outside [0, 64];
+ *   sigma not finite or <= 0; max_gain, min_sigma, min_weight as spk_paste_colour_match_sim refuses them.
+ * All refuse bad arguments before any launch (SPK_EINVAL, spk_last_error).  replaces: the rows copied to the host, filtered in
+ *   numpy and uploaded again, a synchronisation in the middle of the chunk loop -- and a filter over (g, o) that is wrong. */
+int spk_paste_colour_sums_sim(const float* src, int N, int Hs, int Ws, const uint8_t* dst, int64_t image_stride, int64_t row_stride, int H,
+                              int W, const float* sim_dev, int swap_rb, double feather, float lo, float k, const float* matte_dev,
+                              int matte_frames, double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int spk_paste_colour_sums_nv12_sim(const float* src, int N, int Hs, int Ws, const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride,
+                                   const uint8_t* uv, int64_t uv_image_stride, int64_t uv_row_stride, int H, int W, const float* sim_dev,
+                                   int standard, int full_range, double feather, float lo, float k, const float* matte_dev, int matte_frames,
+                                   double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int spk_colour_rows_window(const double* sums_dev, int T, int n0, int n, int radius, double sigma, double max_gain, double min_sigma,
+                           double min_weight, float* rows_out_dev, void* stream);
+
 /* ---- counter-based decoder noise (csrc/noise.hip) ----------------------------------------------------------------------------
  * The noise planes of a synthesis pass as a pure function of (seed, frame, layer, pixel): no generator state, so a clip comes
  * out the same whatever the chunking or the sharding over devices, and a fixed-noise clip is every frame on one frame index.

@@ -337,6 +337,11 @@ _PROTOTYPES = {
     "spk_paste_colour_match_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                              C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_double,
                                              C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_paste_colour_sums_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_colour_rows_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         C.c_void_p, C.c_void_p]),
     "spk_sim_fit_landmarks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "spk_sim_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "spk_matte_from_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
@@ -362,6 +367,9 @@ _PROTOTYPES = {
                                                   C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float,
                                                   C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                   C.c_size_t, C.c_void_p]),
+    "spk_paste_colour_sums_nv12_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                                 C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spk_noise_bits_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "spk_noise_fill": (C.c_int, [C.POINTER(NoiseFillArgs), C.c_void_p]),
 }

@@ -1,0 +1,21 @@
+// What the makers of colour rows share (csrc/frame_blend_common.hpp: a row per frame from the frame's own sums;
+// csrc/colour_window.hip: from sums pooled over a window of frames): the layout of the 13 sums and the check of the row formula's
+// three parameters.  Kept apart from the statistics' kernels so that a file which only reads sums does not carry a copy of them.
+#pragma once
+
+#include "spk_common.hpp"
+#include <cmath>
+
+namespace spk::frame {
+
+constexpr int SUMS = 13;                // S0, then (Sq, Sqq, Sb, Sbb) for each of the three channels
+
+// the three parameters of the row formula, alike wherever rows are made from sums
+inline int check_match_params(const char* who, double max_gain, double min_sigma, double min_weight) {
+    SPK_REQUIRE(std::isfinite(max_gain) && max_gain >= 1.0, "%s: max_gain must be a finite number >= 1 (got %g)", who, max_gain);
+    SPK_REQUIRE(std::isfinite(min_sigma) && min_sigma >= 0.0, "%s: min_sigma must be a finite number >= 0 (got %g)", who, min_sigma);
+    SPK_REQUIRE(std::isfinite(min_weight) && min_weight >= 0.0, "%s: min_weight must be a finite number >= 0 (got %g)", who, min_weight);
+    return SPK_OK;
+}
+
+}  // namespace spk::frame

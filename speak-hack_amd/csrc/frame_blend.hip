@@ -3,6 +3,7 @@
 //   frames_paste_u8_sim_blend: inverse warp + quantise + (g, o) per channel + feather x matte blend into the full frames, one pass;
 //   paste_colour_match_sim:    weighted mean / variance of the generated face and of the pixels it is about to replace, per frame
 //                              and channel -> rows (g, o).  It reads the background and writes no frame.
+//   paste_colour_sums_sim:     the same statistics handed back as their 13 sums per frame, for csrc/colour_window.hip to pool.
 // Both kernels take every per-pixel quantity -- region test, taps, val, q, the feather ramp, the matte sample, m -- from ONE device
 // function, region_pixel, so the weights of the statistics are the weights of the paste and the two cannot drift.  That function
 // is the pixel loop body of frames_paste_u8_sim_kernel with the matte sum added beside the three channel sums: without a matte
@@ -113,6 +114,21 @@ int spk_paste_colour_match_sim(const float* src, int N, int Hs, int Ws, const ui
     hipLaunchKernelGGL(paste_colour_rows_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const double*)workspace_dev,
                        N, PASTE_WGS, sim_dev, max_gain, min_sigma * min_sigma, min_weight, colour_out_dev);
     return spk::check_launch("paste_colour_rows_kernel");
+}
+
+int spk_paste_colour_sums_sim(const float* src, int N, int Hs, int Ws, const uint8_t* dst, int64_t image_stride, int64_t row_stride, int H,
+                              int W, const float* sim_dev, int swap_rb, double feather, float lo, float k, const float* matte_dev,
+                              int matte_frames, double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    const char* who = "paste_colour_sums_sim";
+    if (int rc = check_paste(who, src, dst, sim_dev, N, Hs, Ws, image_stride, row_stride, H, W, feather, lo, k, matte_dev, matte_frames)) return rc;
+    if (int rc = check_colour_sums(who, N, sums_out_dev, workspace_dev, workspace_bytes)) return rc;
+    const RgbBackground bg = {dst, N > 1 ? (long long)image_stride : 0ll, (long long)row_stride, swap_rb};
+    hipLaunchKernelGGL(paste_colour_sums_kernel<RgbBackground>, dim3(PASTE_WGS, (unsigned)std::min(N, 65535)), dim3(256), 0, (hipStream_t)stream, src,
+                       N, Hs, Ws, bg, H, W, sim_dev, feather, lo, k, matte_dev, matte_frames, (double*)workspace_dev);
+    if (int rc = spk::check_launch("paste_colour_sums_kernel")) return rc;
+    hipLaunchKernelGGL(paste_colour_totals_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const double*)workspace_dev,
+                       N, PASTE_WGS, sim_dev, sums_out_dev);
+    return spk::check_launch("paste_colour_totals_kernel");
 }
 
 }  // extern "C"

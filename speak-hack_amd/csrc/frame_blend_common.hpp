@@ -5,11 +5,11 @@
 // formats cannot drift and rows from either mean the same thing.
 #pragma once
 
+#include "colour_rows_common.hpp"
 #include "frame_sim_common.hpp"
 
 namespace spk::frame {
 
-constexpr int SUMS = 13;                // S0, then (Sq, Sqq, Sb, Sbb) for each of the three channels
 constexpr int STAT_WAVES = 4;           // waves of a workgroup of the statistics kernel (256 threads)
 
 struct PixelConsts { double is2, r, ir, fe; };
@@ -168,6 +168,24 @@ __global__ __launch_bounds__(64) void paste_colour_rows_kernel(const double* __r
     }
 }
 
+// The statistics as a result, second kernel: a thread per frame adds the frame's partials in the order of paste_colour_rows_kernel
+// -- the totals are that kernel's s[] bit for bit -- and stores the 13 of them; 13 zeros for a frame whose row is invalid.
+__global__ __launch_bounds__(64) void paste_colour_totals_kernel(const double* __restrict__ part, int N, int groups, const float* __restrict__ sim,
+                                                                 double* __restrict__ sums) {
+    const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    double s[SUMS];
+#pragma unroll
+    for (int t = 0; t < SUMS; ++t) s[t] = 0.0;
+    for (int g = 0; g < groups; ++g) {
+#pragma unroll
+        for (int t = 0; t < SUMS; ++t) s[t] += part[(n * groups + g) * SUMS + t];
+    }
+    const bool valid = load_sim(sim, n).valid;
+#pragma unroll
+    for (int t = 0; t < SUMS; ++t) sums[n * SUMS + t] = valid ? s[t] : 0.0;
+}
+
 }  // namespace
 
 // ---- host ----
@@ -185,18 +203,28 @@ inline int check_blend_params(const char* who, int N, double feather, float lo, 
     return SPK_OK;
 }
 
-// the statistics' own arguments, alike for every format
-inline int check_colour_match(const char* who, int N, double max_gain, double min_sigma, double min_weight, const float* colour_out_dev,
-                              const void* workspace_dev, size_t workspace_bytes) {
-    SPK_REQUIRE(colour_out_dev, "%s: null colour row array", who);
-    SPK_REQUIRE(std::isfinite(max_gain) && max_gain >= 1.0, "%s: max_gain must be a finite number >= 1 (got %g)", who, max_gain);
-    SPK_REQUIRE(std::isfinite(min_sigma) && min_sigma >= 0.0, "%s: min_sigma must be a finite number >= 0 (got %g)", who, min_sigma);
-    SPK_REQUIRE(std::isfinite(min_weight) && min_weight >= 0.0, "%s: min_weight must be a finite number >= 0 (got %g)", who, min_weight);
+// the workspace of the partial sums of N frames
+inline int check_colour_workspace(const char* who, int N, const void* workspace_dev, size_t workspace_bytes) {
     const int64_t need = colour_match_workspace_bytes(N);
     SPK_REQUIRE(workspace_dev && workspace_bytes >= (size_t)need, "%s: the workspace holds %zu bytes, %lld are needed", who,
                 workspace_dev ? workspace_bytes : (size_t)0, (long long)need);
     SPK_REQUIRE((uintptr_t)workspace_dev % alignof(double) == 0, "%s: the workspace must be aligned to %zu bytes", who, alignof(double));
     return SPK_OK;
+}
+
+// the statistics' own arguments, alike for every format
+inline int check_colour_match(const char* who, int N, double max_gain, double min_sigma, double min_weight, const float* colour_out_dev,
+                              const void* workspace_dev, size_t workspace_bytes) {
+    SPK_REQUIRE(colour_out_dev, "%s: null colour row array", who);
+    if (int rc = check_match_params(who, max_gain, min_sigma, min_weight)) return rc;
+    return check_colour_workspace(who, N, workspace_dev, workspace_bytes);
+}
+
+// and those of the statistics handed back as sums
+inline int check_colour_sums(const char* who, int N, const double* sums_out_dev, const void* workspace_dev, size_t workspace_bytes) {
+    SPK_REQUIRE(sums_out_dev, "%s: null sums array", who);
+    SPK_REQUIRE((uintptr_t)sums_out_dev % alignof(double) == 0, "%s: the sums array must be aligned to %zu bytes", who, alignof(double));
+    return check_colour_workspace(who, N, workspace_dev, workspace_bytes);
 }
 
 }  // namespace spk::frame

@@ -5,7 +5,8 @@
 //                                 clamp + normalise -> CHW, one pass;
 //   frames_paste_nv12_sim:        inverse warp + quantise + (g, o) per channel + RGB -> YUV + feather x matte blend into the
 //                                 surfaces, one pass, one thread per chroma block (2 x 2 luma pixels);
-//   paste_colour_match_nv12_sim:  the statistics of csrc/frame_blend_common.hpp over a background read through to_rgb.
+//   paste_colour_match_nv12_sim:  the statistics of csrc/frame_blend_common.hpp over a background read through to_rgb;
+//   paste_colour_sums_nv12_sim:   the same statistics handed back as their 13 sums per frame (csrc/colour_window.hip pools them).
 // This file holds where the bytes of a surface are read and written and nothing else: rows, validity, footprints and the region
 // are csrc/frame_sim_common.hpp's, every per-pixel quantity of the way out is region_pixel's and the sums and rows are those of
 // csrc/frame_blend_common.hpp, the colour maps and the surface checks are csrc/frame_nv12_common.hpp's.  H and W are even, so
@@ -243,6 +244,26 @@ int spk_paste_colour_match_nv12_sim(const float* src, int N, int Hs, int Ws, con
     hipLaunchKernelGGL(paste_colour_rows_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const double*)workspace_dev,
                        N, PASTE_WGS, sim_dev, max_gain, min_sigma * min_sigma, min_weight, colour_out_dev);
     return spk::check_launch("paste_colour_rows_kernel");
+}
+
+int spk_paste_colour_sums_nv12_sim(const float* src, int N, int Hs, int Ws, const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride,
+                                   const uint8_t* uv, int64_t uv_image_stride, int64_t uv_row_stride, int H, int W, const float* sim_dev,
+                                   int standard, int full_range, double feather, float lo, float k, const float* matte_dev, int matte_frames,
+                                   double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    const char* who = "paste_colour_sums_nv12_sim";
+    if (int rc = check_paste(who, src, y, y_image_stride, y_row_stride, uv, uv_image_stride, uv_row_stride, sim_dev, N, Hs, Ws, H, W, false, feather,
+                             lo, k, matte_dev, matte_frames))
+        return rc;
+    if (int rc = check_colour_sums(who, N, sums_out_dev, workspace_dev, workspace_bytes)) return rc;
+    Nv12Background bg = {{y, N > 1 ? (long long)y_image_stride : 0ll, (long long)y_row_stride, uv, N > 1 ? (long long)uv_image_stride : 0ll,
+                          (long long)uv_row_stride}, {}};
+    if (int rc = colour_maps(who, standard, full_range, bg.to_rgb.m, nullptr)) return rc;
+    hipLaunchKernelGGL(paste_colour_sums_kernel<Nv12Background>, dim3(PASTE_WGS, (unsigned)std::min(N, 65535)), dim3(256), 0, (hipStream_t)stream,
+                       src, N, Hs, Ws, bg, H, W, sim_dev, feather, lo, k, matte_dev, matte_frames, (double*)workspace_dev);
+    if (int rc = spk::check_launch("paste_colour_sums_kernel<nv12>")) return rc;
+    hipLaunchKernelGGL(paste_colour_totals_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const double*)workspace_dev,
+                       N, PASTE_WGS, sim_dev, sums_out_dev);
+    return spk::check_launch("paste_colour_totals_kernel");
 }
 
 }  // extern "C"

@@ -455,12 +455,47 @@ def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1)
     return out
 
 
+COLOUR_SUMS = 13                                                          # S0, then (Sq, Sqq, Sb, Sbb) per network channel
+
+
 @functools.lru_cache(maxsize=8)
 def _colour_workspace(device, N):                                         # the partial sums of N frames, kept per (device, N)
     need = L.lib().spk_paste_colour_match_workspace_bytes(N)
     if need < 0:
         raise L.SpkError(f"spk_paste_colour_match_workspace_bytes({N}) failed")
     return torch.empty(need // 8, device=device, dtype=torch.float64)
+
+
+def _check_match_params(what, max_gain, min_sigma, min_weight):           # the three parameters of the row formula, as floats
+    max_gain, min_sigma, min_weight = float(max_gain), float(min_sigma), float(min_weight)
+    if not (1.0 <= max_gain < float("inf")):
+        raise ValueError(f"{what}: max_gain must be a finite number >= 1, got {max_gain}")
+    if not (0.0 <= min_sigma < float("inf")) or not (0.0 <= min_weight < float("inf")):
+        raise ValueError(f"{what}: min_sigma and min_weight must be finite numbers >= 0, got {min_sigma}, {min_weight}")
+    return max_gain, min_sigma, min_weight
+
+
+def _stat_out(out, shape, dtype, device):                                 # what a statistics launcher writes: ``out=`` checked, or a new tensor
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != device or not out.is_contiguous():
+        name = str(dtype).replace("torch.", "")
+        raise L.SpkError(f"out: expected a contiguous {name} HIP tensor {shape} on {device}")
+    return out
+
+
+def _colour_statistics(entry, params, shape, dtype, what, x, frames_u8, sim, matte, feather, value_range, channel_order, out):
+    """What ``paste_colour_match`` and ``paste_colour_sums`` share -- the checks, the background, ``out=``, the workspace and the call
+    of ``entry``, whose arguments differ in ``params`` (in front of the output pointer) alone"""
+    head, rows, tail, matte_args, _ = _aligned_paste_args(what, x, frames_u8, sim, feather, value_range, channel_order, matte)
+    N, H, W = head[1], frames_u8.size(1), frames_u8.size(2)
+    if not packed_pixels(frames_u8):
+        frames_u8 = frames_u8.contiguous()
+    out = _stat_out(out, (N, *shape), dtype, x.device)
+    ws = _colour_workspace(x.device, N)
+    L.check(getattr(L.lib(), entry)(*head, frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), H, W, rows.data_ptr(),
+                                    *tail, *matte_args, *params, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, L.stream_ptr()), entry)
+    return out
 
 
 def paste_colour_match(x, frames_u8, sim, *, matte=None, feather=0, value_range=(-1, 1), channel_order="rgb", max_gain=2.0, min_sigma=1.0,
@@ -472,27 +507,55 @@ def paste_colour_match(x, frames_u8, sim, *, matte=None, feather=0, value_range=
     include/spk.h has the sums).  ``frames_u8`` is only read -- call this BEFORE pasting in place.  The gain is kept within
     ``[1 / max_gain, max_gain]`` and is 1 where the generated face has a standard deviation of at most ``min_sigma`` levels; a
     frame whose weights sum to at most ``min_weight``, or whose row is invalid, gets ``(1, 0)``.  The sums are reduced in a fixed
-    order without atomics: the same inputs give the same bits.  The rows come back as a tensor so that a caller can smooth them
-    over time before pasting.  ``out``: a contiguous device float32 ``[N,3,2]`` tensor to write.  -> device float32 ``[N,3,2]``."""
+    order without atomics: the same inputs give the same bits.  The rows come back as a tensor; to steady them over time,
+    pool the SUMS (``paste_colour_sums`` + ``colour_rows_from_sums``), not the rows.  ``out``: a contiguous device float32 ``[N,3,2]``
+    tensor to write.  -> device float32 ``[N,3,2]``."""
     what = "paste_colour_match"
-    max_gain, min_sigma, min_weight = float(max_gain), float(min_sigma), float(min_weight)
-    if not (1.0 <= max_gain < float("inf")):
-        raise ValueError(f"{what}: max_gain must be a finite number >= 1, got {max_gain}")
-    if not (0.0 <= min_sigma < float("inf")) or not (0.0 <= min_weight < float("inf")):
-        raise ValueError(f"{what}: min_sigma and min_weight must be finite numbers >= 0, got {min_sigma}, {min_weight}")
-    head, rows, tail, matte_args, _ = _aligned_paste_args(what, x, frames_u8, sim, feather, value_range, channel_order, matte)
-    N, H, W = head[1], frames_u8.size(1), frames_u8.size(2)
-    if not packed_pixels(frames_u8):
-        frames_u8 = frames_u8.contiguous()
-    if out is None:
-        out = torch.empty((N, 3, 2), device=x.device, dtype=torch.float32)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (N, 3, 2) or out.device != x.device or \
-            not out.is_contiguous():
-        raise L.SpkError(f"out: expected a contiguous float32 HIP tensor {(N, 3, 2)} on {x.device}")
-    ws = _colour_workspace(x.device, N)
-    L.check(L.lib().spk_paste_colour_match_sim(*head, frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), H, W,
-                                               rows.data_ptr(), *tail, *matte_args, max_gain, min_sigma, min_weight, out.data_ptr(),
-                                               ws.data_ptr(), ws.numel() * 8, L.stream_ptr()), "spk_paste_colour_match_sim")
+    params = _check_match_params(what, max_gain, min_sigma, min_weight)
+    return _colour_statistics("spk_paste_colour_match_sim", params, (3, 2), torch.float32, what, x, frames_u8, sim, matte, feather, value_range,
+                              channel_order, out)
+
+
+def paste_colour_sums(x, frames_u8, sim, *, matte=None, feather=0, value_range=(-1, 1), channel_order="rgb", out=None):
+    """The statistics of ``paste_colour_match`` as a result, two launches (``spk_paste_colour_sums_sim``): per frame the 13 fp64 sums
+    ``S0, (Sq, Sqq, Sb, Sbb)`` x 3 network channels that its rows are made from (include/spk.h), bit for bit the sums it forms
+    internally; 13 zeros for a frame whose row is invalid.  The arguments are that launcher's without the three parameters of the
+    row formula, which ``colour_rows_from_sums`` takes -- with ``radius=0`` it turns these sums into exactly ``paste_colour_match``'s
+    rows, with a radius it pools them over neighbouring frames first.  ``out``: a contiguous device float64 ``[N,13]`` tensor to
+    write, for instance the slice ``[t0:t1]`` of a clip-long ``[T,13]`` tensor.  -> device float64 ``[N,13]``."""
+    return _colour_statistics("spk_paste_colour_sums_sim", (), (COLOUR_SUMS,), torch.float64, "paste_colour_sums", x, frames_u8, sim, matte,
+                              feather, value_range, channel_order, out)
+
+
+def colour_rows_from_sums(sums, radius=0, sigma=None, *, start=0, stop=None, max_gain=2.0, min_sigma=1.0, min_weight=16.0, out=None):
+    """Colour rows from the sums of a clip, pooled over time, one launch (``spk_colour_rows_window``): the rows of frames
+    ``start ... stop - 1`` (``stop=None``: the clip's end) of ``sums``, a device float64 ``[T,13]`` tensor as ``paste_colour_sums`` /
+    ``paste_colour_sums_nv12`` write it.  Frame ``t``'s 13 sums are replaced by the sums over frames ``t - radius ... t + radius``
+    with weights ``exp(-d^2 / (2 sigma^2))`` (``sigma=None``: ``max(radius, 1) / 2``), in fp64, and ``paste_colour_match``'s row
+    formula (``max_gain``, ``min_sigma``, ``min_weight``: its parameters) is applied to the result.  A frame takes part in a window
+    when its ``S0`` exceeds ``min_weight`` and -- as a neighbour -- its sums are finite: a drop-out of up to ``radius`` frames is
+    bridged from its neighbours, a window in which no frame takes part gives ``(1, 0)``.  The sums are linear, so this is the colour
+    match of the face over a stretch of video, every frame weighing in with its weighted area; filtering the rows ``(g, o)``
+    themselves is not (a ``(1, 0)`` got by rule drags its neighbours to the identity).  ``radius=0``: ``paste_colour_match``'s rows
+    bit for bit.  A row depends on its own window only: a sub-range gives the bits of the whole clip.  ``out``: a contiguous device
+    float32 ``[stop - start,3,2]`` tensor to write.  -> device float32 ``[stop - start,3,2]``."""
+    what = "colour_rows_from_sums"
+    radius, sigma = _check_smooth(radius, sigma, what)
+    params = _check_match_params(what, max_gain, min_sigma, min_weight)
+    if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64 or sums.dim() != 2 or sums.size(1) != COLOUR_SUMS or sums.size(0) < 1:
+        got = f"{sums.dtype} {tuple(sums.shape)}" if isinstance(sums, torch.Tensor) else type(sums).__name__
+        raise ValueError(f"{what}: sums must be a float64 tensor [T,{COLOUR_SUMS}], got {got}")
+    T = sums.size(0)
+    stop = T if stop is None else stop
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (start, stop)) or not 0 <= start < stop <= T:
+        raise ValueError(f"{what}: start / stop must be integers with 0 <= start < stop <= {T}, got {start!r}, {stop!r}")
+    if not sums.is_cuda:
+        raise L.SpkError(f"{what}: sums on {sums.device} (no CPU path)")
+    if not sums.is_contiguous():
+        raise L.SpkError(f"{what}: sums: expected a contiguous tensor, got strides {sums.stride()}")
+    out = _stat_out(out, (stop - start, 3, 2), torch.float32, sums.device)
+    L.check(L.lib().spk_colour_rows_window(sums.data_ptr(), T, start, stop - start, radius, sigma, *params, out.data_ptr(), L.stream_ptr()),
+            "spk_colour_rows_window")
     return out
 
 
@@ -1040,6 +1103,18 @@ def frames_paste_nv12_aligned(x, nv12, sim, *, feather=0, value_range=(-1, 1), s
     return out
 
 
+def _colour_statistics_nv12(entry, params, shape, dtype, what, x, nv12, sim, matte, feather, value_range, standard, full_range, out):
+    """``_colour_statistics`` for a surface background: what ``paste_colour_match_nv12`` and ``paste_colour_sums_nv12`` share"""
+    head, (y, uv), rows, tail, matte_args, _ = _aligned_nv12_args(what, x, nv12, sim, feather, value_range, standard, full_range, matte)
+    N, (H, W) = head[1], y.shape[1:]
+    ys, us = nv12_strides(y, uv, what, written=False)
+    out = _stat_out(out, (N, *shape), dtype, x.device)
+    ws = _colour_workspace(x.device, N)
+    L.check(getattr(L.lib(), entry)(*head, y.data_ptr(), *ys, uv.data_ptr(), *us, H, W, rows.data_ptr(), *tail, *matte_args, *params,
+                                    out.data_ptr(), ws.data_ptr(), ws.numel() * 8, L.stream_ptr()), entry)
+    return out
+
+
 def paste_colour_match_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, max_gain=2.0,
                             min_sigma=1.0, min_weight=16.0, out=None):
     """The colour rows ``frames_paste_nv12_aligned(colour=)`` takes, two launches (``spk_paste_colour_match_nv12_sim``):
@@ -1049,24 +1124,18 @@ def paste_colour_match_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=
     same inputs give the same bits.  ``out``: a contiguous device float32 ``[N,3,2]`` tensor to write.
     -> device float32 ``[N,3,2]``."""
     what = "paste_colour_match_nv12"
-    max_gain, min_sigma, min_weight = float(max_gain), float(min_sigma), float(min_weight)
-    if not (1.0 <= max_gain < float("inf")):
-        raise ValueError(f"{what}: max_gain must be a finite number >= 1, got {max_gain}")
-    if not (0.0 <= min_sigma < float("inf")) or not (0.0 <= min_weight < float("inf")):
-        raise ValueError(f"{what}: min_sigma and min_weight must be finite numbers >= 0, got {min_sigma}, {min_weight}")
-    head, (y, uv), rows, tail, matte_args, _ = _aligned_nv12_args(what, x, nv12, sim, feather, value_range, standard, full_range, matte)
-    N, (H, W) = head[1], y.shape[1:]
-    ys, us = nv12_strides(y, uv, what, written=False)
-    if out is None:
-        out = torch.empty((N, 3, 2), device=x.device, dtype=torch.float32)
-    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (N, 3, 2) or out.device != x.device or \
-            not out.is_contiguous():
-        raise L.SpkError(f"out: expected a contiguous float32 HIP tensor {(N, 3, 2)} on {x.device}")
-    ws = _colour_workspace(x.device, N)
-    L.check(L.lib().spk_paste_colour_match_nv12_sim(*head, y.data_ptr(), *ys, uv.data_ptr(), *us, H, W, rows.data_ptr(), *tail, *matte_args,
-                                                    max_gain, min_sigma, min_weight, out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                                                    L.stream_ptr()), "spk_paste_colour_match_nv12_sim")
-    return out
+    params = _check_match_params(what, max_gain, min_sigma, min_weight)
+    return _colour_statistics_nv12("spk_paste_colour_match_nv12_sim", params, (3, 2), torch.float32, what, x, nv12, sim, matte, feather,
+                                   value_range, standard, full_range, out)
+
+
+def paste_colour_sums_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
+    """``paste_colour_sums`` for a surface background, two launches (``spk_paste_colour_sums_nv12_sim``): the 13 sums
+    ``paste_colour_match_nv12`` makes its rows from, bit for bit, per network channel R, G, B -- so ``colour_rows_from_sums`` serves
+    both pixel formats.  ``out``: a contiguous device float64 ``[N,13]`` tensor to write (a slice of a clip-long one).
+    -> device float64 ``[N,13]``."""
+    return _colour_statistics_nv12("spk_paste_colour_sums_nv12_sim", (), (COLOUR_SUMS,), torch.float64, "paste_colour_sums_nv12", x, nv12, sim,
+                                   matte, feather, value_range, standard, full_range, out)
 
 
 class Aligned:
@@ -1130,6 +1199,17 @@ class Rgb24:
             frames_paste_u8_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], **self.args, **blend)
         else:
             frames_paste_u8(y, frames[t0:t1], box, feather=feather, out=frames[t0:t1], **self.args)
+
+    # colour_smooth > 0: the statistics of a chunk now, its paste once the sums of its whole window exist (``box``: an ``Aligned``)
+    def colour_sums(self, y, frames, t0, t1, box, feather, matte, sums):
+        if matte is not None and matte.dim() == 3:
+            matte = matte[t0:t1]
+        paste_colour_sums(y, frames[t0:t1], box.rows, matte=matte, feather=feather, out=sums[t0:t1], **self.args)
+
+    def paste_matched(self, y, frames, t0, t1, box, feather, matte, colour):
+        if matte is not None and matte.dim() == 3:
+            matte = matte[t0:t1]
+        frames_paste_u8_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], matte=matte, colour=colour, **self.args)
 
 
 class Nv12:

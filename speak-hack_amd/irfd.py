@@ -16,6 +16,7 @@ conv anyway, discarding the pretrained conv weights -- SURVEY.md 3.1 (iii)).
 """
 from __future__ import annotations
 
+import collections
 import logging
 
 import torch
@@ -167,7 +168,7 @@ class IRFD(nn.Module):
     @torch.no_grad()
     def reenact_video(self, identity_u8, pose_u8, emotion_u8=None, *, size=256, crop=None, channel_order="rgb", noises=None, chunk=8,
                       seed=None, noise="fresh", frame0=0, paste=False, feather=0, inplace=False, pixel_format="rgb24", standard="bt601",
-                      full_range=False, align=None, identity_align=None, matte=None, colour_match=False):
+                      full_range=False, align=None, identity_align=None, matte=None, colour_match=False, colour_smooth=0, colour_sigma=None):
         """``reenact`` from and to video frames as a decoder and a video writer hold them (inference.py:29-33,46-58,78-86):
         uint8 HWC frames of any size on the device in, uint8 [T,R,R,3] out, both in ``channel_order`` ("bgr": ``cv2``'s).
         Nothing but ``ops.frames_from_u8`` -> ``reenact(output="uint8")``: ``identity_u8`` [H,W,3] or [1,H,W,3] is resized whole
@@ -216,7 +217,19 @@ class IRFD(nn.Module):
         generated face is brought to the mean and standard deviation of the pixels it replaces (``ops.paste_colour_match``) -- each chunk makes one
         ``spk_paste_colour_match_sim`` call, then one ``spk_frames_paste_u8_sim_blend`` call (``ops.frames_paste_u8_aligned(matte=,
         colour=)``) with the rows the paste uses anyway.  The statistics are per frame and read the background before the paste, on
-        the same stream: the result depends neither on ``chunk`` nor on ``inplace``."""
+        the same stream: the result depends neither on ``chunk`` nor on ``inplace``.
+
+        ``colour_smooth=r`` / ``colour_sigma`` (anything but ``0`` / ``None`` needs ``colour_match=True``; ``ValueError`` before any
+        launch otherwise): the colour match without flicker.  The background under the matte changes from frame to frame, and rows
+        made per frame follow it; with ``r > 0`` the 13 sums of the statistics are pooled over frames ``t - r ... t + r`` with
+        weights ``exp(-d^2 / (2 colour_sigma^2))`` (``None``: ``max(r, 1) / 2``) before the row formula
+        (``ops.colour_rows_from_sums``; a frame without usable statistics is bridged from its neighbours).  One float64 ``[T,13]``
+        tensor per call; each chunk's sums go into its slice as soon as it is generated (``ops.paste_colour_sums``), and its paste
+        LAGS: a generated chunk ``[t0, t1)`` is held until the sums of frames up to ``t1 - 1 + r`` exist, or the clip ends, and is
+        then pasted with the rows of its own frames (one ``spk_colour_rows_window`` and one ``spk_frames_paste_u8_sim_blend`` call), so
+        at most ``r + 2 chunk`` generated frames are held.  The statistics of frame ``j`` read frame ``j`` only, before its paste, and
+        the paste of frame ``j`` writes frame ``j`` only: here too the result depends neither on ``chunk`` nor on ``inplace``.
+        ``colour_smooth=0``: the calls the method always made."""
         if pixel_format not in FR.PIXEL_FORMATS:
             raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
         if pixel_format == "rgb24" and (standard != "bt601" or full_range):
@@ -235,6 +248,10 @@ class IRFD(nn.Module):
             raise ValueError("reenact_video: align applies to pixel_format='rgb24' only (NV12 frames take crop boxes)")
         if not isinstance(colour_match, bool):
             raise ValueError(f"reenact_video: colour_match must be a bool, got {colour_match!r}")
+        if colour_smooth != 0 or colour_sigma is not None:
+            if not colour_match:
+                raise ValueError("reenact_video: colour_smooth / colour_sigma apply to colour_match=True only")
+            colour_smooth, colour_sigma = FR._check_smooth(colour_smooth, colour_sigma, "reenact_video: colour_smooth")
         blend, landmark_matte = {}, None
         if matte is not None or colour_match:
             if align is None or not paste:
@@ -273,11 +290,22 @@ class IRFD(nn.Module):
             return self.reenact(ident, pose, emo, noises=noises, chunk=chunk, output=fmt.output, seed=seed, noise=noise, frame0=frame0,
                                 **fmt.args)
         result, out = (pose_u8, pose_in) if inplace else fmt.clone(pose_in)
+        held, sums = collections.deque(), None                             # colour_smooth > 0: generated chunks whose paste lags
         for t0, t1, y in self._reenact_chunks(ident, pose, emo, noises, chunk, "f32", "rgb", seed, noise, frame0):
             where = crop.chunk(t0, t1, y) if align is not None else crop if len(crop) == 4 else (crop[0][t0:t1], h, w)
             if landmark_matte is not None:                                 # once per clip: the window sees every frame, whatever the chunk
                 blend["matte"], landmark_matte = landmark_matte(crop.chunk(0, T, y), crop.size), None
-            fmt.paste(y, out, t0, t1, where, feather, **blend)
+            if colour_smooth == 0:
+                fmt.paste(y, out, t0, t1, where, feather, **blend)
+                continue
+            if sums is None:                                               # the first chunk: the sums of the clip, one tensor per call
+                sums = torch.empty((T, FR.COLOUR_SUMS), device=device, dtype=torch.float64)
+            fmt.colour_sums(y, out, t0, t1, where, feather, blend["matte"], sums)
+            held.append((t0, t1, y, where))
+            while held and (held[0][1] + colour_smooth <= t1 or t1 == T):  # the sums of its last frame's window exist, or never will
+                p0, p1, py, pwhere = held.popleft()
+                rows = FR.colour_rows_from_sums(sums, colour_smooth, colour_sigma, start=p0, stop=p1)
+                fmt.paste_matched(py, out, p0, p1, pwhere, feather, blend["matte"], rows)
         return result
 
     def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None, colour=("bt601", False)):

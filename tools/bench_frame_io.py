@@ -59,7 +59,12 @@
     evaluates the same formula in fp64.  HIP events, the contenders alternate in one process, medians of 7 rounds of 20 calls; the
     launch runs twice per round and the distance of its two medians is the recorded spread.  The ratios are reported, not gated.
 
-    python tools/bench_frame_io.py [--paste | --nv12 | --align | --align-nv12 | --landmarks | --blend | --landmark-matte] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
+``--colour-smooth``: the colour rows of a chunk of a clip (csrc/colour_window.hip), three ways at the shapes of ``--blend``: (a)
+    ``ops.paste_colour_match``, per frame; (b) ``ops.paste_colour_sums`` into the clip's sums + ``ops.colour_rows_from_sums`` over a
+    window of radius 8; (c) what a caller had: (a), the rows to the host, a numpy filter over time, an upload.  Written to
+    profiles/colour_window_bench.txt.
+
+    python tools/bench_frame_io.py [--paste | --nv12 | --align | --align-nv12 | --landmarks | --blend | --landmark-matte | --colour-smooth] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
 import math
@@ -689,6 +694,65 @@ def bench_landmark_matte(args, lines):
     ratio_table(lines, f"HIP events, launcher included, {args.repeats} alternating rounds of 20 calls:", times, name, [(n, True) for n in others])
 
 
+def bench_colour_smooth(args, lines):
+    """``--colour-smooth``: the colour rows of a chunk of a clip, three ways, at the shapes of ``--blend`` (8 x 256^2 -> rotated
+    400 x 400 regions of 1080 x 1920 BGR frames), a clip of ``--frames`` frames, window radius 8.  (a) ``paste_colour_match``: rows
+    per frame, not steadied.  (b) ``paste_colour_sums`` into the chunk's slice of the clip's sums + ``colour_rows_from_sums`` over the
+    window.  (c) what a caller had: (a), the rows copied to the host, a Gaussian filter over the clip's rows in numpy, an upload."""
+    import importlib
+
+    import numpy as np
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    T, chunk, size, Hf, Wf, side, feather, radius = max(args.frames, args.chunk), args.chunk, 256, 1080, 1920, 400, 16, 8
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(chunk)]
+    angles = [0.3 * math.sin(0.9 * t) for t in range(chunk)]
+    rows = ops.similarity_rows([(y + side / 2, x + side / 2) for y, x in boxes], float(side), angles, size).to(dev)
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    video = torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    matte = ops.ellipse_matte((size, size), device=dev)
+    kw = dict(feather=feather, channel_order="bgr")
+    t0 = (T // chunk // 2) * chunk                                         # a chunk in the middle of the clip: a full window on both sides
+    sums = ops.paste_colour_sums(x, video, rows, matte=matte, **kw).repeat(T // chunk + 1, 1)[:T].contiguous()
+    colour, pooled = torch.empty(chunk, 3, 2, device=dev), torch.empty(chunk, 3, 2, device=dev)
+    clip_rows = ops.colour_rows_from_sums(sums).cpu().numpy().astype(np.float64)       # (c)'s host copy of the clip's rows so far
+    k = np.exp(-np.arange(-radius, radius + 1) ** 2 / (2.0 * (radius / 2.0) ** 2))
+
+    def per_frame():
+        return ops.paste_colour_match(x, video, rows, matte=matte, out=colour, **kw)
+
+    def windowed():
+        ops.paste_colour_sums(x, video, rows, matte=matte, out=sums[t0:t0 + chunk], **kw)
+        return ops.colour_rows_from_sums(sums, radius, start=t0, stop=t0 + chunk, out=pooled)
+
+    def host_filter():
+        clip_rows[t0:t0 + chunk] = ops.paste_colour_match(x, video, rows, matte=matte, out=colour, **kw).cpu().numpy()
+        lo, hi = max(t0 - radius, 0), min(t0 + chunk + radius, T)
+        pad = np.pad(clip_rows[lo:hi], ((radius, radius), (0, 0), (0, 0)), mode="edge")
+        out = np.stack([np.tensordot(k, pad[i + t0 - lo:i + t0 - lo + 2 * radius + 1], 1) / k.sum() for i in range(chunk)])
+        return torch.from_numpy(out.astype(np.float32)).to(dev)
+
+    names = ("(a) paste_colour_match", "(b) paste_colour_sums + colour_rows_from_sums", "(c) (a) + copy to the host + numpy filter + upload")
+    contenders = {names[0]: per_frame, names[1]: windowed, names[2]: host_filter, "  the window kernel alone":
+                  lambda: ops.colour_rows_from_sums(sums, radius, start=t0, stop=t0 + chunk, out=pooled), names[0] + " (again)": per_frame}
+    assert torch.equal(ops.colour_rows_from_sums(sums, 0, start=t0, stop=t0 + chunk), per_frame())      # the same statistics
+    lines.append(f"chunk of {chunk} x 256^2 fp32 over rotated {side}x{side} regions of {Hf}x{Wf} BGR, feather {feather}, ellipse matte, chunk "
+                 f"[{t0}, {t0 + chunk}) of a clip of {T} frames, window radius {radius}; median of {args.repeats} alternating rounds of 20 calls")
+    for title, timer in (("HIP events around 20 calls, launchers included (a host synchronisation inside a call shows as device idle time):", device_time),
+                         ("wall clock of one call, synchronised before and after:", wall)):
+        times = alternate(contenders, args.repeats, timer)
+        ratio_table(lines, title, times, names[0], [])
+        med = {n: statistics.median(ts) for n, ts in times.items()}
+        spread = abs(med[names[0]] - med[names[0] + " (again)"]) / min(med[names[0]], med[names[0] + " (again)"])
+        ba, bc = med[names[1]] / med[names[0]], med[names[1]] / med[names[2]]
+        lines.append(f"  per frame: (a) {med[names[0]] / chunk * 1e6:.2f} us, (b) {med[names[1]] / chunk * 1e6:.2f} us, (c) {med[names[2]] / chunk * 1e6:.2f} us")
+        lines.append(f"  (b) / (a) = {ba:.3f}" + ("  -> within the spread" if abs(ba - 1) <= spread else "  -> slower by more than the spread: three launches "
+                     "against two" if ba > 1 else "  -> faster by more than the spread"))
+        lines.append(f"  (b) / (c) = {bc:.3f}" + ("  -> (b) beats (c) by more than the spread" if bc < 1 - spread else "  -> (b) does NOT beat (c) by more than the spread"))
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -722,12 +786,17 @@ def main():
     ap.add_argument("--align", action="store_true", help="the aligned edge: frames_from_u8_aligned, frames_paste_u8_aligned, reenact_video(align=)")
     ap.add_argument("--blend", action="store_true", help="the seamless paste-back: matte, colour match and their torch composition")
     ap.add_argument("--align-nv12", action="store_true", help="the aligned NV12 edge: its three launchers beside their siblings and the BGR detour")
-    ap.add_argument("--commit", default="unknown", help="--blend / --align-nv12: the commit the table is taken at, for its first line")
+    ap.add_argument("--commit", default="unknown", help="--blend / --align-nv12 / --colour-smooth: the commit the table is taken at, for its first line")
     ap.add_argument("--landmarks", action="store_true", help="landmarks -> rows: similarity_from_landmarks, smooth_similarity_rows, the host route")
     ap.add_argument("--landmark-matte", action="store_true", help="landmarks -> matte: matte_from_landmarks, the host route, a torch composition")
+    ap.add_argument("--colour-smooth", action="store_true", help="colour rows of a chunk: per frame, pooled over a window of sums, and filtered on the host")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.colour_smooth:
+        lines = [f"bench_frame_io --colour-smooth: {torch.cuda.get_device_name(0)}, at commit {args.commit}"]
+        bench_colour_smooth(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "colour_window_bench.txt"))
     if args.landmark_matte:
         lines = [f"bench_frame_io --landmark-matte: {torch.cuda.get_device_name(0)}"]
         bench_landmark_matte(args, lines)

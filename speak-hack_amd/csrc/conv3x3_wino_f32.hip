@@ -62,6 +62,18 @@ static_assert(RAW_GATHERS == 11 && 34 * 10 <= RAW_PLANE && 18 * 18 <= RAW_PLANE,
 constexpr int UP_PLANE = 128, UP_GATHERS = 2 * UP_PLANE / 64;
 static_assert(18 * 6 <= UP_PLANE && 10 * 10 <= UP_PLANE && 2 * UP_PLANE <= RAW_WAVE, "geometry");
 constexpr int U_DMA = U_FLOATS * 4 / 1024 / 4;                               // 1 KB blocks per wave and chunk (8)
+// LAB knock-outs of the K loop (tools/build_wino_lab.py, one switch per library): a switch removes instructions
+// only -- never a wait or the barrier -- and every LDS and global address stays in range.  The results are wrong: only the time is read.
+#if defined(SPK_WINO_LAB) && defined(SPK_WINO_KO)
+constexpr int KO = SPK_WINO_KO;
+#else
+constexpr int KO = 0;
+#endif
+constexpr bool KO_U = KO & 1;            // no U pieces
+constexpr bool KO_RAW = KO & 2;          // no raw gathers
+constexpr bool KO_TVALU = KO & 4;        // no transform vector ops (the raw reads and the V writes stay: V = raw values)
+constexpr bool KO_VWRITE = KO & 8;       // no V writes
+constexpr bool KO_UBARE = KO & 16;       // U pieces without their scalar companions: m0 once per chunk, all eight to one address
 
 struct Args {
     const float* x;
@@ -182,14 +194,13 @@ __device__ __forceinline__ float fsub_(float a, float b) { float r; asm("v_sub_f
 // kL = 6 (kR = 6): with a = b, o0 = (3 - kL) b - c = -3b - c.  7 vector ops for 3 -> 4 values; nkl / nkr hold -kL / -kR.  Two passes
 // (rows, columns) give 16 V: the factor is exact and leaves through out_scale.
 __device__ __forceinline__ void up1d_(float a, float b, float c, float nkl, float nkr, float six, float& o0, float& o1, float& o2, float& o3) {
+    // ONE asm statement: between two asm statements of which the second reads a register the first wrote, the compiler -- it cannot see
+    // what the instructions are -- puts an s_nop (24.5 per chunk of 64 MFMAs in the K loop); no vector-ALU pair here needs one
     float e, s, hl, hr;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(e) : "v"(c), "v"(a));
-    asm("v_add_f32 %0, %1, %2" : "=v"(s) : "v"(a), "v"(c));
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(o1) : "v"(b), "s"(six), "v"(s));
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(hl) : "v"(b), "v"(nkl), "v"(s));
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(hr) : "v"(b), "v"(nkr), "v"(s));
-    asm("v_fma_f32 %0, %1, -2.0, %2" : "=v"(o0) : "v"(e), "v"(hl));
-    asm("v_fma_f32 %0, %1, -2.0, -%2" : "=v"(o3) : "v"(e), "v"(hr));
+    asm("v_sub_f32 %0, %9, %7\n\tv_add_f32 %1, %7, %9\n\tv_fma_f32 %2, %8, %12, %1\n\tv_fma_f32 %3, %8, %10, %1\n\t"
+        "v_fma_f32 %4, %8, %11, %1\n\tv_fma_f32 %5, %0, -2.0, %3\n\tv_fma_f32 %6, %0, -2.0, -%4"
+        : "=&v"(e), "=&v"(s), "=&v"(o1), "=&v"(hl), "=&v"(hr), "=&v"(o0), "=v"(o3)
+        : "v"(a), "v"(b), "v"(c), "v"(nkl), "v"(nkr), "s"(six));
     o2 = e;
 }
 
@@ -298,6 +309,13 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
         const float* sb_ = wsrc + (size_t)(chunk_) * U_FLOATS + (wave * U_DMA + (k_)) * 256;                            \
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(m0_), "v"(vo_), "s"(sb_));   \
     }
+#define WINO_DMA_U_BARE(chunk_, slot_, k_)        /* LAB (KO_UBARE) */                                                  \
+    {                                                                                                                   \
+        const unsigned m0_ = (unsigned)((U_OFF + (slot_) * U_FLOATS) * 4) + u_m0, vo_ = lane16;                         \
+        const float* sb_ = wsrc + (size_t)(chunk_) * U_FLOATS + (wave * U_DMA) * 256;                                   \
+        if constexpr ((k_) == 0) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" :: "s"(m0_));                               \
+        asm volatile("global_load_lds_dwordx4 %0, %1" :: "v"(vo_), "s"(sb_));                                           \
+    }
     const unsigned raw_m0 = (unsigned)(wave * RAW_WAVE * 4), u_m0 = (unsigned)(wave * U_DMA * 1024), lane16 = (unsigned)lane * 16u;
 
     // ---- per-lane LDS bases (floats); everything else is an instruction immediate ----
@@ -372,6 +390,13 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
           tv[j_][c_], tv[j_][4 + (c_)], tv[j_][8 + (c_)], tv[j_][12 + (c_)]);
 #define WINO_T_WRITE(vs_, j_, xi_)                                                                                      \
     *((volatile lds_f32_t*)0 + (v_wr + ((vs_) * V_FLOATS + ((xi_) * CI_T + 4 * (j_)) * NTILE))) = tv[j_][xi_];
+    // LAB: the K loop's write, with its knock-outs (KO_TVALU: the raw value instead of the transformed one; KO_VWRITE: the value is kept alive, not written)
+#define WINO_T_WRITE_LOOP(vs_, j_, xi_)                                                                                 \
+    {                                                                                                                   \
+        if constexpr (KO_VWRITE) { if constexpr (!KO_TVALU) asm volatile("" :: "v"(tv[j_][xi_])); }                     \
+        else if constexpr (KO_TVALU) *((volatile lds_f32_t*)0 + (v_wr + ((vs_) * V_FLOATS + ((xi_) * CI_T + 4 * (j_)) * NTILE))) = d[j_][(xi_) % (UP ? 9 : 16)]; \
+        else WINO_T_WRITE(vs_, j_, xi_)                                                                                 \
+    }
 
     if constexpr (RGB) {             // (published by the first chunk barrier, long before the first epilogue)
         if (tid < 3 * CO_T) smem[RGBW_OFF + tid] = (tid & (CO_T - 1)) < p.Cout ? p.rgb_w[(tid >> 6) * p.Cout + (tid & (CO_T - 1))] : 0.f;
@@ -444,21 +469,23 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
             else acc[s & 15] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s % (PD + 1)], fb[s % (PD + 1)], acc[s & 15], 0, 0, 0);
             // requests: the next chunk's weights into the other U slot, the raw planes of the chunk after it into THIS raw
             // slot (its planes became this chunk's V one chunk ago)
-            if constexpr (s < U_DMA) { WINO_DMA_U(c1, O, s); }
-            else if constexpr (s < U_DMA + NG) { WINO_DMA_RAW(voff[s - U_DMA], c2, S, s - U_DMA); }
+            if constexpr (s < U_DMA) {
+                if constexpr (KO_UBARE) { WINO_DMA_U_BARE(c1, O, s); }
+                else if constexpr (!KO_U) { WINO_DMA_U(c1, O, s); }
+            } else if constexpr (s < U_DMA + NG && !KO_RAW) { WINO_DMA_RAW(voff[s - U_DMA], c2, S, s - U_DMA); }
             // raw slot O -> V slot O.  plane 0: reads behind MFMAs 2-5, adds 8-15, writes 16-23; plane 1: 12-15, 24-31, 32-39
             static_for<0, 2>([&](auto j_c) {
                 constexpr int j = decltype(j_c)::value, tr = 2 + 10 * j, ta = 8 + 16 * j;
                 if constexpr (UP) {           // (the same slots: 3 reads, 3 + 4 times the 7 ops of up1d_, one call behind one MFMA)
                     if constexpr (s >= tr && s < tr + 3) { WINO_U_READ(O, j, s - tr); }
-                    if constexpr (s >= ta && s < ta + 3) { WINO_U_H(j, s - ta, nk_); }
-                    if constexpr (s >= ta + 4 && s < ta + 8) { WINO_U_V(j, s - ta - 4, nk_); }
+                    if constexpr (!KO_TVALU && s >= ta && s < ta + 3) { WINO_U_H(j, s - ta, nk_); }
+                    if constexpr (!KO_TVALU && s >= ta + 4 && s < ta + 8) { WINO_U_V(j, s - ta - 4, nk_); }
                 } else {
                 if constexpr (s >= tr && s < tr + 4) { WINO_T_READ(O, j, s - tr); }
-                if constexpr (s >= ta && s < ta + 4) { WINO_T_ROWS(j, s - ta); }
-                if constexpr (s >= ta + 4 && s < ta + 8) { WINO_T_COLS(j, s - ta - 4); if constexpr (MOD) { WINO_T_SCALE(j, s - ta - 4, msc[j]); } }
+                if constexpr (!KO_TVALU && s >= ta && s < ta + 4) { WINO_T_ROWS(j, s - ta); }
+                if constexpr (!KO_TVALU && s >= ta + 4 && s < ta + 8) { WINO_T_COLS(j, s - ta - 4); if constexpr (MOD) { WINO_T_SCALE(j, s - ta - 4, msc[j]); } }
                 }
-                if constexpr (s >= ta + 8 && s < ta + 16) { WINO_T_WRITE(O, j, 2 * (s - ta - 8)); WINO_T_WRITE(O, j, 2 * (s - ta - 8) + 1); }
+                if constexpr (s >= ta + 8 && s < ta + 16) { WINO_T_WRITE_LOOP(O, j, 2 * (s - ta - 8)); WINO_T_WRITE_LOOP(O, j, 2 * (s - ta - 8) + 1); }
             });
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -536,8 +563,17 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
         LAB_STAMP(1)
         for (int i = 0; i < n; i += 2) {
             const bool last_pair = i + 2 >= n;
+            // Plain and modulated forms: a scalar BRANCH around 11 moves instead of 11 selects per pair of chunks (5.5 vector ops per
+            // chunk that an f32 MFMA does not overlap; the empty asm keeps the compiler from turning it back into selects).  The accumulators
+            // cross this merge untouched.  UP has 4 offsets and keeps the selects: with the branch its loop slowed down by a sixth.
+            if constexpr (UP) {
 #pragma unroll
-            for (int k = 0; k < NG; ++k) voff[k] = last_pair ? voff_next[k] : voff[k];
+                for (int k = 0; k < NG; ++k) voff[k] = last_pair ? voff_next[k] : voff[k];
+            } else if (last_pair) {
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int k = 0; k < NG; ++k) voff[k] = voff_next[k];
+            }
             chunk_body(std::integral_constant<int, 0>{}, F_{}, i, nk);
             if constexpr (UP) {          // a region's last chunk transforms the first planes of the NEXT item
                 float nk2[4];
@@ -660,6 +696,7 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
         if (!more) break;
     }
 #undef WINO_FRAG
+#undef WINO_T_WRITE_LOOP
 #undef WINO_T_WRITE
 #undef WINO_U_V
 #undef WINO_U_H
@@ -668,6 +705,7 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
 #undef WINO_T_SCALE
 #undef WINO_T_ROWS
 #undef WINO_T_READ
+#undef WINO_DMA_U_BARE
 #undef WINO_DMA_U
 #undef WINO_DMA_RAW
 }

@@ -29,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--wino-only", action="store_true", help="skip the direct kernel's column (A/B runs of two Winograd builds)")
     args = ap.parse_args()
     pkg = importlib.import_module("speak-hack_amd")
     if os.environ.get("SPK_LAB_LIB"):          # A/B against another build of the library
@@ -51,7 +52,7 @@ def main():
         cfg = ops.conv2d_pick_config(3, 1, B, Cin, Cout, R, R)
         wd, ww = ops.pack_conv_weight(w, cfg), ops.pack_conv_weight_wino(w)
         kw = dict(bias=bias, noise_w=nw, noise=noise, style=style, lrelu_slope=0.2, out=out)
-        td = ev_ms(lambda: ops.conv2d_fused(x, wd, Cout, 3, 1, config=cfg, **kw), args.reps) * 1e3
+        td = float("nan") if args.wino_only else ev_ms(lambda: ops.conv2d_fused(x, wd, Cout, 3, 1, config=cfg, **kw), args.reps) * 1e3
         tw = ev_ms(lambda: ops.conv3x3_wino(x, ww, Cout, **kw), args.reps) * 1e3
         fl = 2 * 9 * Cin * Cout * R * R * B
         tot_d += td
@@ -72,8 +73,8 @@ def main():
         ww = ops.pack_conv_weight_wino(w)
         kw = dict(bias=bias, noise_w=nw, noise=noise, style=style, lrelu_slope=0.2, out=out)
         xu = ops.upsample2x_bilinear(x)
-        tp = ev_ms(lambda: ops.upsample2x_bilinear(x), args.reps) * 1e3
-        tw = ev_ms(lambda: ops.conv3x3_wino(xu, ww, Cout, **kw), args.reps) * 1e3
+        tp = float("nan") if args.wino_only else ev_ms(lambda: ops.upsample2x_bilinear(x), args.reps) * 1e3
+        tw = float("nan") if args.wino_only else ev_ms(lambda: ops.conv3x3_wino(xu, ww, Cout, **kw), args.reps) * 1e3
         tf = ev_ms(lambda: ops.conv3x3_wino(x, ww, Cout, upsample=True, **kw), args.reps) * 1e3
         tot_p += tp + tw
         tot_f += tf

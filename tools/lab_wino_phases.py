@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """LAB: cycle stamps of one workgroup's SECOND region in the Winograd kernel (a -DLAB build of csrc/conv3x3_wino_f32.hip that writes
 the stamps over the first floats of the output): region start -> K loop start -> K loop end -> half 0 transformed -> half 0 stored ->
-half 1 transformed -> half 1 stored.   SPK_LAB_LIB=tools/_bin/libspk_hip_winolab.so python tools/lab_wino_phases.py"""
+half 1 transformed -> half 1 stored.   python tools/build_wino_lab.py --ko 0;  SPK_LAB_LIB=tools/_bin/libspk_hip_winolab.so python tools/lab_wino_phases.py"""
 import importlib, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

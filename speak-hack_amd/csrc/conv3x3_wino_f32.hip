@@ -219,9 +219,16 @@ __device__ __forceinline__ void lds_barrier() {
 // channel groups (2 waves x 2 half-waves) meet through LDS.  The 134 MB activation is then neither re-read nor -- y == NULL -- written.
 // UP (SPK_CONV_UPSAMPLE2X, plain launches): p.x is the LOW-resolution tensor [B, Cx, H/2, W/2]; everything that speaks of the output
 // keeps H, W.  Raw plane, gathers and input transform change (up1d_), nothing behind V does.
-template <bool MOD, int SHAPE, bool RGB = false, bool UP = false>
+// EPI: the form of the epilogue's channel rows, chosen by the host.  GENERIC: every per-launch condition inside the row (a partial last
+// channel tile, y_pre, SPK_EPI_ACCUM, the modulated forms).  LEAN: whole channel tiles, no y_pre, no accumulate, 0 < slope <= 1 -- a row
+// is straight-line code: no branch, a wave-uniform base plus one 32-bit lane offset as store address, LeakyReLU as multiply / max.
+// LEAN_NOSTORE (RGB only): the same without the activation's stores (y == NULL: only the fused toRGB's image leaves).
+constexpr int GENERIC = 0, LEAN = 1, LEAN_NOSTORE = 2;
+template <bool MOD, int SHAPE, bool RGB = false, bool UP = false, int EPI = GENERIC>
 __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     static_assert(!(UP && MOD), "the modulated conv keeps its x2 pass");
+    static_assert(EPI == GENERIC || !MOD, "the modulated forms keep the generic rows");
+    static_assert(EPI != LEAN_NOSTORE || RGB, "only a fused toRGB launch may leave the activation unwritten");
     constexpr int RW = region_w(SHAPE), RH = region_h(SHAPE), TXN = RW / 2, TYN = RH / 2;
     constexpr int RAW_W = UP ? RW / 2 + 2 : RW + 2, RAW_H = UP ? RH / 2 + 2 : RH + 2, RAW_USED = RAW_W * RAW_H;
     constexpr int PLANE = UP ? UP_PLANE : RAW_PLANE, NG = UP ? UP_GATHERS : RAW_GATHERS;       // a raw plane's pitch; a wave's gathers per chunk
@@ -258,15 +265,20 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     };
     // per lane and gather, once: the element's byte offset from the region's origin pixel in plane 0 of the image (wraps for the
     // halo's row -1 / column -1: the sum with the origin is in range whenever the element exists), and which image edges would
-    // put it outside (bit 0: region at the top edge, 1: bottom, 2: left, 3: right, 4: the pitch's padding -- never loaded)
-    unsigned rel[NG], edge[NG];
+    // put it outside (bit 0: region at the top edge, 1: bottom, 2: left, 3: right, 4: the pitch's padding -- never loaded); the edge
+    // bits of six gathers share a register (they are alive through the whole kernel: 2 registers for 11 gathers, not 11)
+    constexpr int NE = (NG + 5) / 6;
+    unsigned rel[NG], edges[NE];
+#pragma unroll
+    for (int k = 0; k < NE; ++k) edges[k] = 0u;
+#define WINO_EDGE(k_) ((edges[(k_) / 6] >> (5 * ((k_) % 6))) & 31u)
 #pragma unroll
     for (int k = 0; k < NG; ++k) {
         const int e = k * 64 + lane;
         const int j = e >= PLANE ? 1 : 0, q = e - j * PLANE;
         const int r = q / RAW_W, c = q - r * RAW_W;
         rel[k] = ((unsigned)(wave + 4 * j) * (unsigned)HWin + (unsigned)((r - 1) * Win + (c - 1))) * 4u;
-        edge[k] = (r == 0 ? 1u : 0u) | (r == RAW_H - 1 ? 2u : 0u) | (c == 0 ? 4u : 0u) | (c == RAW_W - 1 ? 8u : 0u) | (q >= RAW_USED ? 16u : 0u);
+        edges[k / 6] |= ((r == 0 ? 1u : 0u) | (r == RAW_H - 1 ? 2u : 0u) | (c == 0 ? 4u : 0u) | (c == RAW_W - 1 ? 8u : 0u) | (q >= RAW_USED ? 16u : 0u)) << (5 * (k % 6));
     }
     auto set_voff = [&](unsigned (&vo)[NG], int b_, int y0_, int x0_) {
         // (host: the whole tensor is below 2^29 floats)
@@ -279,13 +291,13 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
             const unsigned row_bytes = (unsigned)Win * 4u;
 #pragma unroll
             for (int k = 0; k < NG; ++k) {
-                const unsigned h = edge[k] & at;
+                const unsigned h = WINO_EDGE(k) & at;
                 vo[k] = (h & 16u) ? 0x80000000u
                                   : origin + rel[k] + ((h & 1u) ? row_bytes : 0u) - ((h & 2u) ? row_bytes : 0u) + ((h & 4u) ? 4u : 0u) - ((h & 8u) ? 4u : 0u);
             }
         } else {
 #pragma unroll
-            for (int k = 0; k < NG; ++k) vo[k] = (edge[k] & at) ? 0x80000000u : origin + rel[k];
+            for (int k = 0; k < NG; ++k) vo[k] = (WINO_EDGE(k) & at) ? 0x80000000u : origin + rel[k];
         }
     };
     const unsigned chunk_bytes = (unsigned)(CI_T * HWin * 4);
@@ -500,11 +512,8 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     // half = channel row (r & 3) + 8 (r >> 2) + 4 half of the wave's 32
     const int tile = wn * 32 + l32, oy = 2 * (tile / TXN), ox = 2 * (tile % TXN);
     const int row_lane = wm * 32 + 4 * half;                              // + (r & 3) + 8 (r >> 2): row of the 64-channel tile
-    // the operand table of the epilogue: thread t fetches operand t & 3 (bias, noise weight, style scale, style shift) of channel t >> 2
-    const int prm_which = tid & 3, prm_c = co0 + (tid >> 2);
-    const bool prm_on = prm_c < p.Cout && (prm_which == 0 ? f_bias : (prm_which == 1 ? f_noise : f_style));
-    const float* const prm_src = (prm_which == 0 ? p.bias : (prm_which == 1 ? p.noise_w : p.style + (prm_which == 3 ? p.Cout : 0))) + prm_c;
-    const float prm_neutral = prm_which == 2 ? 1.f : 0.f;                 // + 0, + 0 * noise, * 1, + 0
+    float rgb_bo = 0.f;                                                   // RGB: the bias of the image channel this wave finishes
+    if constexpr (RGB) { if (p.rgb_bias) rgb_bo = p.rgb_bias[min(wave, 2)]; }
 
     using F_ = std::false_type;
 #ifdef SPK_WINO_LAB      // tools/lab_wino_phases.py: cycle stamps of one workgroup's second region, written over the output's first floats
@@ -534,12 +543,18 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
             nz0 = *reinterpret_cast<const f32x2*>(p.noise + (size_t)cur_b * HW + pix);
             nz1 = *reinterpret_cast<const f32x2*>(p.noise + (size_t)cur_b * HW + pix + p.W);
         }
-        // thread t fetches operand t & 3 of channel t >> 2: bias / noise weight / style scale + 1 / style shift, or its neutral value
-        float prm = prm_neutral;
-        if (prm_on) {                                    // ONE load per thread, no branch per operand kind
-            const float t_ = prm_src[prm_which >= 2 ? (size_t)cur_b * p.style_stride : 0];
-            prm = prm_which == 2 ? t_ + 1.f : t_;
-        }
+        // the operand table of the epilogue: thread t fetches operand t & 3 (bias, noise weight, style scale + 1, style shift) of channel
+        // t >> 2, or its neutral value.  (From an opaque copy of the thread index, per region: the operand's 64-bit address and its
+        // companions are rebuilt by a dozen vector ops instead of living in five registers through the K loop.)
+        int prm_t = tid;
+        asm volatile("" : "+v"(prm_t));
+        const int prm_which = prm_t & 3, prm_c = co0 + (prm_t >> 2);
+        const bool prm_on = prm_c < p.Cout && (prm_which == 0 ? f_bias : (prm_which == 1 ? f_noise : f_style));
+        const float* const prm_src = (prm_which == 0 ? p.bias : (prm_which == 1 ? p.noise_w : p.style + (prm_which == 3 ? p.Cout : 0))) + prm_c;
+        // The loaded value is not touched before the epilogue: an instruction on it here would wait for vmcnt(0), that is for every
+        // store of the previous region's epilogue (900 cycles in front of the K loop, measured with tools/lab_wino_phases.py).
+        float prm_raw = 0.f;                             // absent: + 0, + 0 * noise, * (0 + 1), + 0
+        if (prm_on) prm_raw = prm_src[prm_which >= 2 ? (size_t)cur_b * p.style_stride : 0];      // ONE load per thread, no branch per operand kind
         float dem = 1.f;
         if constexpr (MOD) {
             if (p.out_scale_bc && tid < CO_T && co0 + tid < p.Cout) dem = p.out_scale_bc[(size_t)cur_b * p.Cout + co0 + tid];
@@ -591,18 +606,45 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
         // whole 128-byte lines -- so the block needs no trip through LDS (which would also collide with the next region's operands).
         // Every stage runs unconditionally; an absent one has its neutral operand in the table.
         LAB_STAMP(2)
-        smem[PRM_OFF + tid] = prm;
+        smem[PRM_OFF + tid] = (tid & 3) == 2 ? prm_raw + 1.f : prm_raw;       // the table holds style scale + 1
         if constexpr (MOD) { if (tid < CO_T) smem[DEM_OFF + tid] = dem; }
         lds_barrier();
         unsigned hw_ = (unsigned)HW;                 // (opaque per region: the 16 rows' channel offsets must not be hoisted out of the region
         asm volatile("" : "+s"(hw_));                //  loop as 32 live registers)
         const size_t o0 = ((size_t)cur_b * p.Cy + (size_t)grp * p.Cout) * hw_ + pix + (size_t)(kb_cur / p.cps) * p.slice_floats;
+        // LEAN: a store's address = wave-uniform row base (64 bits, scalar ALU) + this lane's byte offset within five channel planes
+        // (32 bits, fixed for the region; host: 20 H W < 2^32)
+        const size_t hw_bytes = (size_t)hw_ * 4, w_bytes = (size_t)p.W * 4;
+        char* const y_rows = reinterpret_cast<char*>(p.y + ((size_t)cur_b * p.Cy + (size_t)grp * p.Cout + co0 + wm * 32) * hw_ +
+                                                     (size_t)(kb_cur / p.cps) * p.slice_floats);
+        const unsigned y_lane = ((unsigned)(4 * half) * hw_ + (unsigned)pix) * 4u;
         LAB_STAMP(3)
         // The accumulators are read out of the AGPR file one element at a time, by hand (v_accvgpr_read_b32 with an "a" operand):
         // left to the compiler, the first use of element r of a tile copies the whole 16-register tile to VGPRs, a row touches all
         // 16 tiles, and 256 VGPRs of copies push everything else that is alive into scratch -- whose reloads then queue, in
         // vmcnt order, behind the epilogue's own stores (25 000 cycles per region, measured).
-#define WINO_ACC(xi_, r_) ({ float v_; asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v_) : "a"(acc[xi_][r_])); v_; })
+        // A row's 16 reads and the 24 adds of Y = A^T M A are ONE asm statement (as up1d_): between dependent one-instruction statements
+        // the compiler puts an s_nop or a v_mov.  Sums in the order of the scalar form: s0_i = (m0 + m1) + m2, s1_i = (m1 - m2) - m3 over
+        // the tiles 4 i .. 4 i + 3, then top = (s_0 + s_1) + s_2, bot = (s_1 - s_2) - s_3.
+#define WINO_ROW4(a_, b_, m0_, m1_, m2_, m3_)                                                                           \
+    "v_accvgpr_read_b32 " a_ ", " m0_ "\n\tv_accvgpr_read_b32 " b_ ", " m1_ "\n\tv_accvgpr_read_b32 %4, " m2_ "\n\tv_accvgpr_read_b32 %5, " m3_ "\n\t" \
+    "v_add_f32 " a_ ", " a_ ", " b_ "\n\tv_sub_f32 " b_ ", " b_ ", %4\n\tv_add_f32 " a_ ", " a_ ", %4\n\tv_sub_f32 " b_ ", " b_ ", %5\n\t"
+#define WINO_ROW(r_, top_, bot_)                                                                                        \
+    {                                                                                                                   \
+        float tx_, ty_, bx_, by_, t0_, t1_, t2_, t3_;                                                                   \
+        asm volatile(WINO_ROW4("%0", "%1", "%8", "%9", "%10", "%11")                                                    \
+                     WINO_ROW4("%2", "%3", "%12", "%13", "%14", "%15")                                                  \
+                     "v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3\n\t"                                                \
+                     WINO_ROW4("%6", "%7", "%16", "%17", "%18", "%19")                                                  \
+                     "v_add_f32 %0, %0, %6\n\tv_sub_f32 %2, %2, %6\n\tv_add_f32 %1, %1, %7\n\tv_sub_f32 %3, %3, %7\n\t" \
+                     WINO_ROW4("%6", "%7", "%20", "%21", "%22", "%23")                                                  \
+                     "v_sub_f32 %2, %2, %6\n\tv_sub_f32 %3, %3, %7"                                                    \
+                     : "=&v"(tx_), "=&v"(ty_), "=&v"(bx_), "=&v"(by_), "=&v"(t0_), "=&v"(t1_), "=&v"(t2_), "=&v"(t3_)    \
+                     : "a"(acc[0][r_]), "a"(acc[1][r_]), "a"(acc[2][r_]), "a"(acc[3][r_]), "a"(acc[4][r_]), "a"(acc[5][r_]), \
+                       "a"(acc[6][r_]), "a"(acc[7][r_]), "a"(acc[8][r_]), "a"(acc[9][r_]), "a"(acc[10][r_]), "a"(acc[11][r_]), \
+                       "a"(acc[12][r_]), "a"(acc[13][r_]), "a"(acc[14][r_]), "a"(acc[15][r_]));                         \
+        (top_).x = tx_; (top_).y = ty_; (bot_).x = bx_; (bot_).y = by_;                                                 \
+    }
         float rgb[3][4];                                 // RGB: this lane's share (its 16 channel rows) of its tile's 2 x 2 pixels x 3 channels
 #pragma unroll
         for (int o = 0; o < 3; ++o)
@@ -612,65 +654,85 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
             constexpr int r = decltype(r_c)::value;
             const int row = row_lane + (r & 3) + 8 * (r >> 2);
             const float4 q_ = *reinterpret_cast<const float4*>(smem + PRM_OFF + 4 * row);
-            float s0[4], s1[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float m0 = WINO_ACC(4 * i, r), m1 = WINO_ACC(4 * i + 1, r), m2 = WINO_ACC(4 * i + 2, r), m3 = WINO_ACC(4 * i + 3, r);
-                s0[i] = (m0 + m1) + m2;
-                s1[i] = (m1 - m2) - m3;
-            }
             f32x2 top, bot;
-            top.x = (s0[0] + s0[1]) + s0[2]; top.y = (s1[0] + s1[1]) + s1[2];
-            bot.x = (s0[1] - s0[2]) - s0[3]; bot.y = (s1[1] - s1[2]) - s1[3];
+            WINO_ROW(r, top, bot)
             float osc_r = osc;
             if constexpr (MOD) osc_r = osc * smem[DEM_OFF + row];
             top.x = top.x * osc_r + q_.x; top.y = top.y * osc_r + q_.x; bot.x = bot.x * osc_r + q_.x; bot.y = bot.y * osc_r + q_.x;
             top.x += q_.y * nz0.x; top.y += q_.y * nz0.y; bot.x += q_.y * nz1.x; bot.y += q_.y * nz1.y;
-            top.x = (top.x > 0.f ? top.x : top.x * slope_) * gain_; top.y = (top.y > 0.f ? top.y : top.y * slope_) * gain_;
-            bot.x = (bot.x > 0.f ? bot.x : bot.x * slope_) * gain_; bot.y = (bot.y > 0.f ? bot.y : bot.y * slope_) * gain_;
-            const int co = co0 + row;
-            if constexpr (RGB) {                     // (no y_pre / accumulate with a fused toRGB: host)
+            if constexpr (EPI != GENERIC) {
+                // max(x, x slope) gain: what the select gives for every non-NaN x, +-0 included, while 0 < slope <= 1 (host)
+                top.x = __builtin_fmaxf(top.x, top.x * slope_) * gain_; top.y = __builtin_fmaxf(top.y, top.y * slope_) * gain_;
+                bot.x = __builtin_fmaxf(bot.x, bot.x * slope_) * gain_; bot.y = __builtin_fmaxf(bot.y, bot.y * slope_) * gain_;
                 top.x = top.x * q_.z + q_.w; top.y = top.y * q_.z + q_.w; bot.x = bot.x * q_.z + q_.w; bot.y = bot.y * q_.z + q_.w;
+                if constexpr (RGB) {
 #pragma unroll
-                for (int o = 0; o < 3; ++o) {
-                    const float w_ = smem[RGBW_OFF + o * CO_T + row];      // (rows past Cout: 0)
-                    rgb[o][0] += w_ * top.x; rgb[o][1] += w_ * top.y; rgb[o][2] += w_ * bot.x; rgb[o][3] += w_ * bot.y;
+                    for (int o = 0; o < 3; ++o) {
+                        const float w_ = smem[RGBW_OFF + o * CO_T + row];      // (rows past Cout: 0)
+                        rgb[o][0] += w_ * top.x; rgb[o][1] += w_ * top.y; rgb[o][2] += w_ * bot.x; rgb[o][3] += w_ * bot.y;
+                    }
                 }
-                if (p.y && co < p.Cout) {
-                    const size_t off = o0 + (size_t)co * hw_;
-                    *reinterpret_cast<f32x2*>(p.y + off) = top;
-                    *reinterpret_cast<f32x2*>(p.y + off + p.W) = bot;
-                }
-                __builtin_amdgcn_sched_barrier(0);       // one channel row at a time: hoisted table reads of 16 rows would not fit the registers
-            } else if (co < p.Cout) {
-                const size_t off = o0 + (size_t)co * hw_;
-                if (p.y_pre) {
-                    *reinterpret_cast<f32x2*>(p.y_pre + off) = top;
-                    *reinterpret_cast<f32x2*>(p.y_pre + off + p.W) = bot;
-                }
-                top.x = top.x * q_.z + q_.w; top.y = top.y * q_.z + q_.w; bot.x = bot.x * q_.z + q_.w; bot.y = bot.y * q_.z + q_.w;
-                if (f_accum) {
-                    const f32x2 o_t = *reinterpret_cast<const f32x2*>(p.y + off), o_b = *reinterpret_cast<const f32x2*>(p.y + off + p.W);
-                    top.x += o_t.x; top.y += o_t.y; bot.x += o_b.x; bot.y += o_b.y;
-                }
+                if constexpr (EPI == LEAN) {
+                    char* const yr = y_rows + (size_t)((r & 3) + 8 * (r >> 2)) * hw_bytes;       // the channel row's step: scalar
 #ifdef SPK_WINO_NOSTORE   // LAB knock-out: everything but the stores themselves
-                if (top.x == 12345.678f)
+                    if (top.x == 12345.678f)
 #endif
-                {
-                    *reinterpret_cast<f32x2*>(p.y + off) = top;
-                    *reinterpret_cast<f32x2*>(p.y + off + p.W) = bot;
+                    {
+                        *reinterpret_cast<f32x2*>(yr + y_lane) = top;
+                        *reinterpret_cast<f32x2*>(yr + w_bytes + y_lane) = bot;
+                    }
+                }
+                if constexpr (RGB) __builtin_amdgcn_sched_barrier(0);
+            } else {
+                top.x = (top.x > 0.f ? top.x : top.x * slope_) * gain_; top.y = (top.y > 0.f ? top.y : top.y * slope_) * gain_;
+                bot.x = (bot.x > 0.f ? bot.x : bot.x * slope_) * gain_; bot.y = (bot.y > 0.f ? bot.y : bot.y * slope_) * gain_;
+                const int co = co0 + row;
+                if constexpr (RGB) {                     // (no y_pre / accumulate with a fused toRGB: host)
+                    top.x = top.x * q_.z + q_.w; top.y = top.y * q_.z + q_.w; bot.x = bot.x * q_.z + q_.w; bot.y = bot.y * q_.z + q_.w;
+#pragma unroll
+                    for (int o = 0; o < 3; ++o) {
+                        const float w_ = smem[RGBW_OFF + o * CO_T + row];      // (rows past Cout: 0)
+                        rgb[o][0] += w_ * top.x; rgb[o][1] += w_ * top.y; rgb[o][2] += w_ * bot.x; rgb[o][3] += w_ * bot.y;
+                    }
+                    if (p.y && co < p.Cout) {        // (the lean rows' address: scalar row base + 32-bit lane offset)
+                        char* const yr = y_rows + (size_t)((r & 3) + 8 * (r >> 2)) * hw_bytes;
+                        *reinterpret_cast<f32x2*>(yr + y_lane) = top;
+                        *reinterpret_cast<f32x2*>(yr + w_bytes + y_lane) = bot;
+                    }
+                    __builtin_amdgcn_sched_barrier(0);       // one channel row at a time: hoisted table reads of 16 rows would not fit the registers
+                } else if (co < p.Cout) {
+                    const size_t off = o0 + (size_t)co * hw_;
+                    if (p.y_pre) {
+                        *reinterpret_cast<f32x2*>(p.y_pre + off) = top;
+                        *reinterpret_cast<f32x2*>(p.y_pre + off + p.W) = bot;
+                    }
+                    top.x = top.x * q_.z + q_.w; top.y = top.y * q_.z + q_.w; bot.x = bot.x * q_.z + q_.w; bot.y = bot.y * q_.z + q_.w;
+                    if (f_accum) {
+                        const f32x2 o_t = *reinterpret_cast<const f32x2*>(p.y + off), o_b = *reinterpret_cast<const f32x2*>(p.y + off + p.W);
+                        top.x += o_t.x; top.y += o_t.y; bot.x += o_b.x; bot.y += o_b.y;
+                    }
+#ifdef SPK_WINO_NOSTORE   // LAB knock-out: everything but the stores themselves
+                    if (top.x == 12345.678f)
+#endif
+                    {
+                        *reinterpret_cast<f32x2*>(p.y + off) = top;
+                        *reinterpret_cast<f32x2*>(p.y + off + p.W) = bot;
+                    }
                 }
             }
         });
-#undef WINO_ACC
+#undef WINO_ROW
+#undef WINO_ROW4
         if constexpr (RGB) {
             // the four channel groups of a tile: (wm, half) -> LDS [group][tile][3][4], summed in group order by thread (tile, channel)
             float* part = smem + RGB_PART_OFF + ((wm * 2 + half) * NTILE + tile) * 12;
 #pragma unroll
             for (int o = 0; o < 3; ++o) *reinterpret_cast<float4*>(part + 4 * o) = make_float4(rgb[o][0], rgb[o][1], rgb[o][2], rgb[o][3]);
             lds_barrier();
-            if (tid < 3 * NTILE) {
-                const int o = tid >> 6, t = tid & (NTILE - 1);
+            {
+                // wave o finishes image channel o; wave 3 repeats channel 2 (the same values to the same addresses) rather than
+                // stand behind a guard, which would be the only branch of the epilogue
+                const int o = min(wave, 2), t = lane;
                 const float* ps = smem + RGB_PART_OFF + t * 12 + 4 * o;
                 float4 v = *reinterpret_cast<const float4*>(ps);
 #pragma unroll
@@ -678,12 +740,13 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
                     const float4 u = *reinterpret_cast<const float4*>(ps + g * NTILE * 12);
                     v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
                 }
-                const float bo = p.rgb_bias ? p.rgb_bias[o] : 0.f;
-                const size_t off = ((size_t)cur_b * 3 + o) * hw_ + (size_t)(cur_y0 + 2 * (t / TXN)) * p.W + (cur_x0 + 2 * (t % TXN));
+                // address = scalar base (image, channel, region origin) + the tile's 32-bit byte offset within the plane
+                char* const yo = reinterpret_cast<char*>(p.rgb_y + ((size_t)cur_b * 3 + o) * hw_ + (size_t)cur_y0 * p.W + cur_x0);
+                const unsigned t_off = ((unsigned)(2 * (t / TXN)) * (unsigned)p.W + (unsigned)(2 * (t % TXN))) * 4u;
                 f32x2 a_, b_;
-                a_.x = v.x + bo; a_.y = v.y + bo; b_.x = v.z + bo; b_.y = v.w + bo;
-                *reinterpret_cast<f32x2*>(p.rgb_y + off) = a_;
-                *reinterpret_cast<f32x2*>(p.rgb_y + off + p.W) = b_;
+                a_.x = v.x + rgb_bo; a_.y = v.y + rgb_bo; b_.x = v.z + rgb_bo; b_.y = v.w + rgb_bo;
+                *reinterpret_cast<f32x2*>(yo + t_off) = a_;
+                *reinterpret_cast<f32x2*>(yo + (size_t)p.W * 4 + t_off) = b_;
             }
         }
         LAB_STAMP(4)
@@ -708,6 +771,7 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
 #undef WINO_DMA_U_BARE
 #undef WINO_DMA_U
 #undef WINO_DMA_RAW
+#undef WINO_EDGE
 }
 
 }  // namespace spkwino
@@ -869,18 +933,31 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
         f.act_gain = a.act_gain; f.out_scale_dev = d->out_scale_dev;
     }
     if (spkconv::form_probe) return spkconv::report_sliced_form(f, static_cast<const float*>(d->workspace), ks);
+    // the rows' form: LEAN for whole channel tiles without y_pre / accumulate (every inference launch of the decoder, and the sliced
+    // launches' raw partial sums); everything else -- and a slope outside (0, 1], which the lean rows' max() does not cover -- GENERIC
+    const bool lrelu_ok = !(a.flags & SPK_EPI_LRELU) || (a.slope > 0.f && a.slope <= 1.f);
+    const bool lean_ok = !mod && lrelu_ok && !a.y_pre && !(a.flags & SPK_EPI_ACCUM) && 20ll * d->H * d->W < (1ll << 32);
+    const int epi_form = !lean_ok ? GENERIC : rgb ? (!a.y ? LEAN_NOSTORE : d->Cout == CO_T ? LEAN : GENERIC) : (d->Cout % CO_T == 0 ? LEAN : GENERIC);
+    const auto pick = [&](auto rgb_c, auto up_c) -> void (*)(const Args) {
+        constexpr bool R = decltype(rgb_c)::value, U = decltype(up_c)::value;
+        if constexpr (R) {
+            if (epi_form == LEAN_NOSTORE) return shape == SQUARE ? &wino_kernel<false, SQUARE, R, U, LEAN_NOSTORE> : &wino_kernel<false, WIDE, R, U, LEAN_NOSTORE>;
+        }
+        if (epi_form == LEAN) return shape == SQUARE ? &wino_kernel<false, SQUARE, R, U, LEAN> : &wino_kernel<false, WIDE, R, U, LEAN>;
+        return shape == SQUARE ? &wino_kernel<false, SQUARE, R, U> : &wino_kernel<false, WIDE, R, U>;
+    };
+    using T_ = std::true_type;
+    using F_ = std::false_type;
     void (*kern)(const Args) = mod ? (shape == SQUARE ? &wino_kernel<true, SQUARE> : &wino_kernel<true, WIDE>)
-                               : rgb ? (shape == SQUARE ? &wino_kernel<false, SQUARE, true> : &wino_kernel<false, WIDE, true>)
-                                     : (shape == SQUARE ? &wino_kernel<false, SQUARE> : &wino_kernel<false, WIDE>);
-    if (up)
-        kern = rgb ? (shape == SQUARE ? &wino_kernel<false, SQUARE, true, true> : &wino_kernel<false, WIDE, true, true>)
-                   : (shape == SQUARE ? &wino_kernel<false, SQUARE, false, true> : &wino_kernel<false, WIDE, false, true>);
-    static bool raised[10] = {false, false, false, false, false, false, false, false, false, false};
-    const int which = (mod ? 2 : rgb ? 4 : 0) + (shape == SQUARE ? 1 : 0) + (up ? (rgb ? 4 : 6) : 0);
-    if (!raised[which]) {
+                               : rgb ? (up ? pick(T_{}, T_{}) : pick(T_{}, F_{})) : (up ? pick(F_{}, T_{}) : pick(F_{}, F_{}));
+    static const void* raised[32];          // the kernels whose LDS limit has been raised
+    static int n_raised = 0;
+    bool seen = false;
+    for (int i = 0; i < n_raised; ++i) seen = seen || raised[i] == reinterpret_cast<const void*>(kern);
+    if (!seen) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised[which] = true;
+        if (n_raised < 32) raised[n_raised++] = reinterpret_cast<const void*>(kern);
     }
     const long long n_items = (long long)a.regions_x * a.regions_y * d->B * ks;
     SPK_REQUIRE(n_items < (1ll << 31), "conv2d winograd: grid too large");

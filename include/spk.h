@@ -215,8 +215,8 @@ int spk_conv2d_fwd(const spk_conv2d_desc* desc, void* stream);
  * device is touched (pointers are read for their ALIGNMENT only, so any values of the right alignment do; a sliced launch still
  * needs workspace / workspace_bytes to be set).  Served: every descriptor that runs the tap kernel (tile configs 0-11, the 2x2
  * parity forms of SPK_CONV_DGRAD_S2 / SPK_CONV_TRANSPOSE4X4_S2 included); SPK_CONV_WINOGRAD descriptors and the exact-tap data
- * gradient (config 13) fill ksplit / finisher / finisher_seg (config = -1 / 13, everything else 0).  The GEMM forms of a 1x1,
- * the stem kernel and SPK_CONV_BF16X3 are refused.
+ * gradient (config 13) fill ksplit / finisher / finisher_seg (config = -1 / 13, everything else 0).  The GEMM forms of a 1x1
+ * and the stem kernel (spk_conv2d_gemm_form answers those) and SPK_CONV_BF16X3 are refused.
  *   mode: the kernel's input-stage build (0 plain, 1 x2, 2 affine+ReLU, 3 batch scale, 4 x2 + batch scale, 5 plain with
  *         BatchNorm sums, 6 plain with the residual epilogue)
  *   staged: the epilogue's store form -- 0 dword stores, 1 through an LDS tile, 2 through an LDS tile in two halves
@@ -231,6 +231,35 @@ typedef struct spk_conv2d_form {
     int64_t lds_bytes;
 } spk_conv2d_form;
 int spk_conv2d_launch_form(const spk_conv2d_desc* desc, spk_conv2d_form* out);
+/* The same question for the descriptors spk_conv2d_launch_form refuses: the GEMM forms of a stride-1 1x1 (tile configs 12, 14, 15)
+ * and the 7x7 stride-2 stem kernel (config 16).  Answered by run_1x1_gemm / run_1x1_gemm2 / run_stem themselves after their own
+ * requirements and argument set-up, before anything is launched; no device is touched, pointers are read for their alignment
+ * only.  Every other descriptor is refused.
+ *   build: the kernel instantiation -- GEMM forms 0 plain, 1 folded affine + ReLU input; stem 0 plain, 1 BatchNorm sums, 2 bias / lrelu
+ *   k_tiles: steps of the contraction loop (32 channels on config 12, 16 on 14 / 15; the stem has one: K = 147)
+ *   last_k_channels: channels the last k-tile adds; last_k_overlap (14 / 15): channels of the last k-tile the previous one
+ *         already covered -- the tile is moved back to end at Cin and the packed weights are zero there; 0 = not ragged, and
+ *         always 0 on config 12, whose ragged tile is zero-filled instead
+ *   co_tiles: channel tiles per group; last_co_rows: rows of the last one
+ *   passes (14 / 15): 64-row epilogue passes of a co tile; last_pass_rows: rows of the last co tile's last pass (0: it is empty)
+ *   px_tiles: pixel tiles (128 flattened (b, pixel) positions; the stem: 16 x 32 tiles of one image, over all images)
+ *   last_px_count: pixels of the last pixel tile (below 128: the masked epilogue rows; the stem: last_tile_cols x last_tile_rows)
+ *   tile_spans_images: some pixel tile holds pixels of more than one image
+ *   stats_own: with SPK_EPI_STATS, 1 = every pixel tile stores its own copy of the sums, 0 = fp64 atomics (0 without the flag)
+ *   accum_half / residual: the epilogue adds that operand
+ *   tiles_x, tiles_y, last_tile_cols, last_tile_rows: the stem's tile grid over one image and the extent of its last tile */
+typedef struct spk_gemm_form {
+    int32_t config, build;
+    int32_t k_tiles, last_k_overlap, last_k_channels;
+    int32_t co_tiles, last_co_rows, passes, last_pass_rows;
+    int32_t px_tiles, last_px_count, tile_spans_images;
+    int32_t stats_own, accum_half, residual;
+    int32_t grid_x, grid_y;
+    int32_t tiles_x, tiles_y, last_tile_cols, last_tile_rows;
+    int32_t reserved;
+    int64_t lds_bytes;
+} spk_gemm_form;
+int spk_conv2d_gemm_form(const spk_conv2d_desc* desc, spk_gemm_form* out);
 /* The SPK_CONV_BF16X3 path: packed image size in BYTES / packer (w is the fp32 [Cout,Cin,3,3] parameter; the hi / lo split
  * happens here, once per weight update) / whether a shape is served / the launch itself (spk_conv2d_fwd forwards to it). */
 int64_t spk_conv2d_packed_bytes_bf16x3(int Cin, int Cout);

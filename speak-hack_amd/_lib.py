@@ -45,6 +45,18 @@ class Conv2dForm(C.Structure):
                                          "finisher", "finisher_seg")] + [("lds_bytes", C.c_int64)]
 
 
+class GemmForm(C.Structure):
+    """Mirror of spk_gemm_form (include/spk.h): what ``spk_conv2d_gemm_form`` answers."""
+    _fields_ = [(n, C.c_int32) for n in ("config", "build", "k_tiles", "last_k_overlap", "last_k_channels", "co_tiles", "last_co_rows",
+                                         "passes", "last_pass_rows", "px_tiles", "last_px_count", "tile_spans_images", "stats_own",
+                                         "accum_half", "residual", "grid_x", "grid_y", "tiles_x", "tiles_y", "last_tile_cols",
+                                         "last_tile_rows", "reserved")] + [("lds_bytes", C.c_int64)]
+
+
+GEMM_BUILDS = ("plain", "affine")                   # spk_gemm_form.build of configs 12, 14, 15
+STEM_BUILDS = ("plain", "stats", "epi")             # ... of config 16
+
+
 class WgradForm(C.Structure):
     """Mirror of spk_wgrad_form (include/spk.h): what ``spk_conv2d_wgrad_launch_form`` answers."""
     _fields_ = [(n, C.c_int32) for n in ("kernel", "mode", "TW", "TH", "TB", "MT", "NT", "n_tiles", "splits", "tiles_per_split", "n_slabs",
@@ -280,6 +292,7 @@ _PROTOTYPES = {
                                                C.c_int, C.c_int, C.c_void_p]),
     "spk_conv2d_fwd": (C.c_int, [C.POINTER(Conv2dDesc), C.c_void_p]),
     "spk_conv2d_launch_form": (C.c_int, [C.POINTER(Conv2dDesc), C.POINTER(Conv2dForm)]),
+    "spk_conv2d_gemm_form": (C.c_int, [C.POINTER(Conv2dDesc), C.POINTER(GemmForm)]),
     "spk_conv2d_packed_bytes_bf16x3": (C.c_int64, [C.c_int, C.c_int]),
     "spk_conv2d_pack_weights_bf16x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "spk_conv2d_pack_weights_bf16x3_tf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

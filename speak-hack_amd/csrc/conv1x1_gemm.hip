@@ -305,6 +305,20 @@ int run_1x1_gemm(const spk_conv2d_desc* d, hipStream_t stream) {
     SPK_REQUIRE(gx < (1ll << 31) && (long long)a.G * a.co_tiles_g < 65536, "conv2d: grid too large");
     const size_t lds = (2 * (size_t)GBUF + 2 * GM) * sizeof(float);
     const bool aff = d->flags & SPK_CONV_IN_AFFINE_RELU;
+    if (gemm_form_probe) {
+        spk_gemm_form& f = *gemm_form_probe;
+        const int n_kt = spk::ceil_div(d->Cin, GK);
+        f.config = kGemmConfig; f.build = aff;
+        f.k_tiles = n_kt; f.last_k_overlap = 0; f.last_k_channels = d->Cin - (n_kt - 1) * GK;
+        f.co_tiles = a.co_tiles_g; f.last_co_rows = d->Cout - (a.co_tiles_g - 1) * GM;
+        f.px_tiles = (int)gx; f.last_px_count = (int)(a.n_px - (gx - 1) * GN);
+        f.tile_spans_images = d->B > 1 && a.HW % GN != 0;
+        f.stats_own = (d->flags & SPK_EPI_STATS) && a.stats_slots >= gx;
+        f.accum_half = 0; f.residual = a.residual != nullptr;
+        f.grid_x = (int)gx; f.grid_y = a.G * a.co_tiles_g;
+        f.lds_bytes = (int64_t)lds;
+        return SPK_OK;
+    }
     auto kern = aff ? &conv1x1_gemm_kernel<true> : &conv1x1_gemm_kernel<false>;
     static bool raised[2] = {false, false};
     if (!raised[aff]) {

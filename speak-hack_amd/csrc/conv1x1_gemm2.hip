@@ -455,6 +455,20 @@ int run_1x1_gemm2(const spk_conv2d_desc* d, hipStream_t stream) {
     const long long grid = (long long)a.px_tiles * a.co_tiles_g * a.G;
     SPK_REQUIRE(grid < (1ll << 31), "conv2d: grid too large");
     const bool aff = d->flags & SPK_CONV_IN_AFFINE_RELU;
+    if (gemm_form_probe) {
+        spk_gemm_form& f = *gemm_form_probe;
+        f.config = d->config; f.build = aff;
+        f.k_tiles = a.n_kt; f.last_k_overlap = a.n_kt * KT - d->Cin; f.last_k_channels = d->Cin - (a.n_kt - 1) * KT;
+        f.co_tiles = a.co_tiles_g; f.last_co_rows = d->Cout - (a.co_tiles_g - 1) * co_t;
+        f.passes = co_t / 64; f.last_pass_rows = f.last_co_rows > (f.passes - 1) * 64 ? f.last_co_rows - (f.passes - 1) * 64 : 0;
+        f.px_tiles = a.px_tiles; f.last_px_count = (int)(a.n_px - (unsigned)(a.px_tiles - 1) * PX_T);
+        f.tile_spans_images = d->B > 1 && a.HW % PX_T != 0;
+        f.stats_own = (d->flags & SPK_EPI_STATS) && a.stats_slots >= a.px_tiles;
+        f.accum_half = a.acc_half != nullptr; f.residual = a.residual != nullptr;
+        f.grid_x = (int)grid; f.grid_y = 1;
+        f.lds_bytes = 3 * (int64_t)(KT * co_t + KT * PX_T + 256) * (int64_t)sizeof(float);
+        return SPK_OK;
+    }
     if (d->config == kGemm2Config) return launch<4>(a, aff, (unsigned)grid, stream);
     return launch<2>(a, aff, (unsigned)grid, stream);
 }

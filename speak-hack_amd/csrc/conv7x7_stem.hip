@@ -266,6 +266,19 @@ int run_stem(const spk_conv2d_desc* d, hipStream_t stream) {
     auto kern = a.stats ? &stem7x7s2_kernel<true> : (epi ? &stem7x7s2_kernel<false, true> : &stem7x7s2_kernel<false>);
     static bool raised[3] = {false, false, false};
     const int which = a.stats ? 1 : (epi ? 2 : 0);
+    if (gemm_form_probe) {
+        spk_gemm_form& f = *gemm_form_probe;
+        f.config = kStemConfig; f.build = which;
+        f.k_tiles = 1; f.last_k_overlap = 0; f.last_k_channels = ST_K;
+        f.co_tiles = 1; f.last_co_rows = 64;
+        f.tiles_x = a.tiles_x; f.tiles_y = a.tiles_y;
+        f.last_tile_cols = d->W - (a.tiles_x - 1) * ST_TW; f.last_tile_rows = d->H - (a.tiles_y - 1) * ST_TH;
+        f.px_tiles = (int)tiles; f.last_px_count = f.last_tile_cols * f.last_tile_rows;
+        f.stats_own = a.stats && a.stats_slots >= tiles;
+        f.grid_x = (int)tiles; f.grid_y = G;
+        f.lds_bytes = ST_LDS_BYTES;
+        return SPK_OK;
+    }
     if (!raised[which]) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));

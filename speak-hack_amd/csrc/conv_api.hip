@@ -151,6 +151,7 @@ int splitk_finisher(const ConvArgs& a, const float* ws, int* seg) {
 }
 
 thread_local spk_conv2d_form* form_probe = nullptr;
+thread_local spk_gemm_form* gemm_form_probe = nullptr;
 
 int report_sliced_form(const ConvArgs& finisher_args, const float* ws, int ksplit) {
     spk_conv2d_form& f = *form_probe;
@@ -568,6 +569,19 @@ int spk_conv2d_launch_form(const spk_conv2d_desc* d, spk_conv2d_form* out) {
     return rc;
 }
 
+int spk_conv2d_gemm_form(const spk_conv2d_desc* d, spk_gemm_form* out) {
+    SPK_REQUIRE(d && out, "conv2d gemm form: null pointer");
+    SPK_REQUIRE(!(d->flags & (SPK_CONV_BF16X3 | SPK_CONV_WINOGRAD | SPK_CONV_TRANSPOSE4X4_S2 | SPK_CONV_DGRAD_S2)),
+                "conv2d gemm form: serves the GEMM forms of a 1x1 (configs %d, %d, %d) and the stem kernel (config %d) only", kGemmConfig,
+                kGemm2Config, kGemm2NarrowConfig, kStemConfig);
+    *out = spk_gemm_form{};
+    out->config = -1;
+    gemm_form_probe = out;       // run_1x1_gemm / run_1x1_gemm2 / run_stem answer where they would launch
+    const int rc = spk_conv2d_fwd(d, nullptr);
+    gemm_form_probe = nullptr;
+    return rc;
+}
+
 int spk_conv2d_fwd(const spk_conv2d_desc* d, void* stream) {
     SPK_REQUIRE(d, "conv2d: null descriptor");
     if (d->flags & SPK_CONV_BF16X3) return spk_conv2d_bf16x3_fwd(d, stream);
@@ -653,6 +667,7 @@ int spk_conv2d_fwd(const spk_conv2d_desc* d, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     SPK_REQUIRE(!d->out_scale_dev || !(cfg == kGemmConfig || is_gemm2(cfg)), "conv2d: out_scale_dev is built into the tap kernels (not the GEMM forms of a 1x1)");
     SPK_REQUIRE(!form_probe || !(cfg == kGemmConfig || is_gemm2(cfg) || cfg == kStemConfig), "conv2d launch form: config %d is not a tap-kernel config", cfg);
+    SPK_REQUIRE(!gemm_form_probe || cfg == kGemmConfig || is_gemm2(cfg) || cfg == kStemConfig, "conv2d gemm form: config %d is not a GEMM-form or stem config", cfg);
     if (cfg == kGemmConfig) return run_1x1_gemm(&dd, s);
     if (is_gemm2(cfg)) return run_1x1_gemm2(&dd, s);
     if (cfg == kStemConfig) {

@@ -865,6 +865,9 @@ int splitk_finisher(const ConvArgs& a, const float* ws, int* seg);
 // spk_conv2d_launch_form: while set (on the calling thread), the launch paths answer here where they would launch and return
 extern thread_local spk_conv2d_form* form_probe;
 int report_sliced_form(const ConvArgs& finisher_args, const float* ws, int ksplit);   // Winograd / config 13: the finisher alone
+// spk_conv2d_gemm_form: the same for run_1x1_gemm / run_1x1_gemm2 / run_stem, which fill it after their own requirements and
+// argument set-up and return before anything is launched
+extern thread_local spk_gemm_form* gemm_form_probe;
 
 inline int report_form(int config, int mode, const Geometry& g, const ConvArgs& a, float* y, int ksplit, bool ragged, bool use_fg,
                        long long gx, const float* ws) {

@@ -131,6 +131,14 @@ def desc_launch_form(desc, ws_bytes=0, workspace_ptr=256):
     return {name: getattr(form, name) for name, _ in L.Conv2dForm._fields_}
 
 
+def desc_gemm_form(desc):
+    """The form ``spk_conv2d_fwd(desc)`` would take on the GEMM forms of a 1x1 (configs 12, 14, 15) or on the stem kernel (config
+    16), as a dict of the ``spk_gemm_form`` fields (``spk_conv2d_gemm_form``: the launchers' own statements, nothing is launched)."""
+    form = L.GemmForm()
+    L.check(L.lib().spk_conv2d_gemm_form(C.byref(desc), C.byref(form)), "spk_conv2d_gemm_form")
+    return {name: getattr(form, name) for name, _ in L.GemmForm._fields_ if name != "reserved"}
+
+
 def conv_launch_form(*args, workspace_ptr=256, **kw):
     """``desc_launch_form`` of the descriptor ``conv_desc(*args, **kw)`` assembles."""
     d, ws_bytes = conv_desc(*args, **kw)

@@ -7,7 +7,8 @@ and DECLARES the form it reaches; ``spk_conv2d_launch_form`` -- the launch path'
 
 ``reference(case)`` evaluates the whole operator in fp64 and, the same chain, in fp32 on the CPU:
     input stage (bilinear x2 | affine + ReLU | batch scale) -> conv * out_scale * out_scale_dev * demod -> + bias + noise_w * noise
-    + residual -> LeakyReLU * act_gain -> y_pre -> style (rows wider than 2 Cy) -> + y (accumulate) -> BatchNorm sums.
+    + residual -> LeakyReLU * act_gain -> y_pre -> style (rows wider than 2 Cy) -> + y (accumulate) -> + the half-resolution
+    tensor at the even pixels (accum_half) -> BatchNorm sums.
 The bound is measured on the reference, never on the kernel: max(4 x rel-L2(fp32 chain, fp64 chain), sqrt(kh kw Cin) 2^-24),
 the bf16x3 file's rule with this kernel's contraction length; a single element: |y - ref| <= MAX_FACTOR x bound x rms(ref)."""
 import functools
@@ -30,7 +31,9 @@ FULL = ("bias", "noise", "lrelu", "style", "y_pre", "accum", "scale_dev")       
 
 def case(name, family, k, stride, B, Cin, Cout, Hs, Ws, config, ksplit=1, G=1, shared=False, opts=(), stats=None, misalign=(),
          hw=None, like=None, **declares):
-    """``Hs x Ws``: the size of x.  ``opts``: bias noise lrelu style y_pre accum scale_dev x2 affine bscale demod residual.
+    """``Hs x Ws``: the size of x.  ``opts``: bias noise lrelu style y_pre accum scale_dev x2 affine bscale demod residual, and for
+    tests/gemm_conv_cases.py accum_half (y(2h, 2w) += t(h, w)), transposed (the operator is the 1x1 of w^T -- the data gradient; Cin /
+    Cout are the OPERATOR's, the weight is [Cin, Cout, 1, 1]) and unit_scale (out_scale = 1).
     ``stats``: None, "own" (one copy of the sums per pixel tile) or "atomic" (one copy).  ``misalign``: of out / out_pre / noise /
     residual, the tensors that start 4 bytes off.  ``hw``: the destination size of a stride-2 data gradient (default 2 Hs - 1 x 2 Ws - 1).
     ``like``: the case whose operands this one shares.  ``declares``: fields of spk_conv2d_form the case says it reaches (``slices``: the resolved ksplit)."""
@@ -74,6 +77,8 @@ def _inputs(name):
         t["w"] = [recipe_tensor(f"{tag}.w", (Cin, Cout, 4, 4), (4 * Cin) ** -0.5)]
     elif c["family"] in ("dgrad_s2", "dgrad13"):   # the FORWARD conv's weight [channels of g = Cin][channels of dx = Cout][3][3]
         t["w"] = [recipe_tensor(f"{tag}.w{g}", (Cin, Cout, 3, 3), (2.25 * Cin) ** -0.5) for g in range(G)]
+    elif "transposed" in o:                    # the forward 1x1's weight: [its Cout = the contraction][its Cin = the output rows]
+        t["w"] = [recipe_tensor(f"{tag}.w{g}", (Cin, Cout, 1, 1), Cin ** -0.5) for g in range(G)]
     else:
         t["w"] = [recipe_tensor(f"{tag}.w{g}", (Cout, Cin, k, k), (k * k * Cin) ** -0.5) for g in range(G)]
     if "bias" in o:
@@ -87,6 +92,8 @@ def _inputs(name):
         t["y0"] = recipe_input(f"{tag}.y0", (B, Cy, H, W)) * 0.5
     if "residual" in o:
         t["residual"] = recipe_input(f"{tag}.res", (B, Cy, H, W)) * 0.5
+    if "accum_half" in o:
+        t["half"] = recipe_input(f"{tag}.half", (B, Cy, (H + 1) // 2, (W + 1) // 2)) * 0.5
     if "affine" in o:
         t["in_scale"] = 1.0 + 0.2 * recipe_input(f"{tag}.ia", (Cx,))
         t["in_shift"] = 0.1 * recipe_input(f"{tag}.ib", (Cx,))
@@ -104,8 +111,8 @@ def inputs(c):
 def scalars(c):
     """(out_scale, out_scale_dev | None, slope | None, act_gain) as the launch passes them."""
     o = c["opts"]
-    plain = c["family"] in ("dgrad_s2", "dgrad13", "transpose4x4")
-    return (1.0 if c["family"] == "transpose4x4" else OUT_SCALE, SCALE_DEV if "scale_dev" in o else None, SLOPE if "lrelu" in o else None,
+    plain = c["family"] in ("dgrad_s2", "dgrad13", "transpose4x4", "stem")
+    return (1.0 if (c["family"] in ("transpose4x4", "stem") or "unit_scale" in o) else OUT_SCALE, SCALE_DEV if "scale_dev" in o else None, SLOPE if "lrelu" in o else None,
             ACT_GAIN if ("lrelu" in o and not plain) else 1.0)
 
 
@@ -114,10 +121,12 @@ def _f32(v):
     return float(torch.tensor(v, dtype=torch.float32))
 
 
-def chain(c, dtype, *, t=None, drop_ci=None, shift_tap_row=None, swap=None):
+def chain(c, dtype, *, t=None, drop_ci=None, shift_tap_row=None, swap=None, double_ci=None, residual_late=False, edge_pad=None):
     """(y_pre, y) of the whole operator in ``dtype``.  The keyword arguments seed faults for the sensitivity checks:
     ``drop_ci``: input channels (per group) left out of the contraction; ``shift_tap_row``: output row computed with the tap one
-    row below; ``swap`` = (operand, c0, c1): two channels of bias / style / demod exchanged."""
+    row below; ``swap`` = (operand, c0, c1): two channels of bias / style / demod exchanged; ``double_ci``: input channels counted
+    twice; ``residual_late``: the residual added after the activation; ``edge_pad`` = "row" / "col": the padding below / right of the
+    image repeats the last row / column instead of being zero."""
     t = dict(inputs(c) if t is None else t)
     o, G, Cin, Cout, k, s = c["opts"], c["G"], c["Cin"], c["Cout"], c["k"], c["stride"]
     H, W = out_hw(c)
@@ -144,15 +153,24 @@ def chain(c, dtype, *, t=None, drop_ci=None, shift_tap_row=None, swap=None):
     for g in range(G):
         xg = x if c["shared"] else x[:, g * Cin:(g + 1) * Cin]
         w = t["w"][g].to(dtype)
-        if drop_ci is not None:
+        if "transposed" in o:
+            w = w.transpose(0, 1)
+        if drop_ci is not None or double_ci is not None:
             keep = torch.ones(Cin, dtype=dtype)
-            keep[list(drop_ci)] = 0
+            keep[list(drop_ci or ())] = 0
+            keep[list(double_ci or ())] = 2
             xg = xg * keep.view(1, -1, 1, 1)
         if c["family"] == "transpose4x4":
             outs.append(F.conv_transpose2d(xg, w, stride=2, padding=1))
         elif c["family"] in ("dgrad_s2", "dgrad13"):
             op = (H - (2 * c["Hs"] - 1), W - (2 * c["Ws"] - 1))
             outs.append(F.conv_transpose2d(xg, w, stride=2, padding=1, output_padding=op))
+        elif edge_pad is not None:
+            p = (k - 1) // 2
+            xp = F.pad(xg, (p, 0, p, 0))
+            xp = F.pad(xp, (0, 0, 0, p), mode="replicate" if edge_pad == "row" else "constant")
+            xp = F.pad(xp, (0, p, 0, 0), mode="replicate" if edge_pad == "col" else "constant")
+            outs.append(F.conv2d(xp, w, stride=s))
         else:
             yg = F.conv2d(xg, w, stride=s, padding=(k - 1) // 2)
             if shift_tap_row is not None:      # that row with every tap taken one input row lower
@@ -172,16 +190,21 @@ def chain(c, dtype, *, t=None, drop_ci=None, shift_tap_row=None, swap=None):
         v = v + t["bias"].to(dtype).view(1, Cy, 1, 1)
     if "noise" in o:
         v = v + t["noise_w"].to(dtype).view(1, Cy, 1, 1) * t["noise"].to(dtype)
-    if "residual" in o:
+    if "residual" in o and not residual_late:
         v = v + t["residual"].to(dtype)
     if slope is not None:
         v = torch.where(v > 0, v, v * _f32(slope)) * _f32(gain)
+    if "residual" in o and residual_late:
+        v = v + t["residual"].to(dtype)
     pre = v
     if "style" in o:
         st = t["style"].to(dtype)
         v = v * (st[:, :Cy, None, None] + 1.0) + st[:, Cy:2 * Cy, None, None]
     if "accum" in o:
         v = v + t["y0"].to(dtype)
+    if "accum_half" in o:                      # after the activation and the accumulate, before the sums (csrc/conv1x1_gemm2.hip)
+        v = v.clone()
+        v[:, :, ::2, ::2] += t["half"].to(dtype)
     return pre, v
 
 

@@ -67,6 +67,10 @@ def _guards_untouched(buf, start, n):
 
 class Launch:
     """One case on the device: operands, the descriptor, the form the library says it takes."""
+    extra_slots = 0          # own-slot copies of the sums beyond the launch's pixel tiles (they must stay zero)
+
+    def query(self):
+        return self.ops.desc_launch_form(self.desc)
 
     def __init__(self, pkg, dev, c):
         ops, L = pkg.ops, pkg._lib
@@ -84,6 +88,8 @@ class Launch:
             wp = ops.pack_conv_weights_list(ws, cfg, 2)
         elif fam == "transpose4x4":
             wp = ops.pack_conv_weight(ws[0], cfg, 3)
+        elif "transposed" in o:
+            wp = ops.pack_conv_weights_list(ws, cfg, 1)
         else:
             wp = ops.pack_conv_weights_list(ws, cfg)
         self.keep = [wp, ws]
@@ -100,7 +106,7 @@ class Launch:
         self.y0 = on("y0")
         self.stats = None
         if c["stats"]:
-            slots = ops.stats_slots(cfg, c["k"], c["stride"], B, c["Cin"], Cout, H, W) if c["stats"] == "own" else 1
+            slots = ops.stats_slots(cfg, c["k"], c["stride"], B, c["Cin"], Cout, H, W) + self.extra_slots if c["stats"] == "own" else 1
             self.stats = torch.zeros(slots, 2, Cy, dtype=torch.float64, device=dev)
         out_scale, scale_dev, slope, gain = D.scalars(c)
         self.scale_dev = torch.tensor([scale_dev], device=dev) if scale_dev is not None else None
@@ -110,14 +116,14 @@ class Launch:
             on("x"), wp, Cout, k, stride, flags=kind, out=self.out, hw=(H, W), bias=on("bias"), noise_w=on("noise_w"), noise=noise,
             style=on("style"), upsample="x2" in o, lrelu_slope=slope, out_scale=out_scale,
             in_affine=(on("in_scale"), on("in_shift")) if "affine" in o else None, batch_scale=on("bscale"), demod=on("demod"), act_gain=gain,
-            stats=self.stats, out_pre=self.pre, accumulate="accum" in o,
+            stats=self.stats, out_pre=self.pre, accumulate="accum" in o, accum_half=on("half"),
             out_scale_dev=self.scale_dev, config=cfg, ksplit=c["ksplit"],
             groups=G, shared_input=c["shared"], residual=residual)
         self.keep += [noise, residual]
         if ws_bytes > 0:
             scratch = self.scratch = ops._workspace(dev, ws_bytes)
             self.desc.workspace, self.desc.workspace_bytes = scratch.data_ptr(), scratch.numel() * 4
-        self.form = ops.desc_launch_form(self.desc)
+        self.form = self.query()
 
     def run(self):
         """-> (y, y_pre, (sum, sumsq)) of one launch into freshly prepared destinations."""

@@ -1091,6 +1091,59 @@ int spk_paste_colour_sums_nv12_sim(const float* src, int N, int Hs, int Ws, cons
 int spk_colour_rows_window(const double* sums_dev, int T, int n0, int n, int radius, double sigma, double max_gain, double min_sigma,
                            double min_weight, float* rows_out_dev, void* stream);
 
+/* ---- causal filters with their state on the device: what a live feed can use (csrc/causal_filter.hip) ------------------------------
+ * spk_sim_smooth, the contour window of spk_matte_from_landmarks and spk_colour_rows_window look at frames t - r ... t + r: they
+ * serve a clip that is in memory.  On a camera or call feed frame t + 1 does not exist yet.  These two are the causal counterparts:
+ * they look at the past only, and what they remember of it is a small STATE in device memory, read when a call starts and written
+ * when it ends.  Plain device pointers and a stream; one launch each; no allocation, no synchronisation, no atomics, no device value
+ * read on the host; all arithmetic in fp64.
+ *
+ * spk_causal_filter: a one-euro filter (Casiez, Roussel, Vogel, CHI 2012) -- a first-order low-pass whose cut-off rises with the
+ *   signal's own filtered speed, so a still face is held steady and a moving face is followed without lag -- over x_dev fp32 [N][D],
+ *   N consecutive frames of a signal at `rate` frames per second, in G = D / group GROUPS of `group` in {1, 2, 3, 4} consecutive
+ *   components that share one speed (a landmark is a group of 2; group must divide D).  w_dev fp32 or NULL: group g of frame n has
+ *   weight w_dev[n * weight_stride + g]; weight_stride = 0: one set of G weights for all frames; NULL: every weight is 1 (the rule
+ *   of spk_sim_fit_landmarks).  A group TAKES PART in frame n when its weight is finite and > 0 and all its components are finite:
+ *   the fit's rule.  state_dev fp64 [G][2 + 2 group] = (k, w_last, xh[group], dh[group]) per group, 8-byte aligned; all-zero bytes
+ *   are the EMPTY state.  k = 0: the group holds nothing; k >= 1: it holds an estimate xh (and its filtered speed dh), and k - 1
+ *   frames have passed since the last sample that took part.  y_dev fp32 [N][D]; wy_dev fp32 [N][G] or NULL.
+ *   With alpha(f, Te) = 1 / (1 + 1 / (2 pi f Te)), per frame in order and per group, x the frame's components and w its weight:
+ *     it takes part, and k = 0 or k - 1 > hold:   xh = x,  dh = 0,  w_last = w,  k = 1                          (re)initialised
+ *     it takes part otherwise:                    Te = k / rate,   d = (x - xh) / Te
+ *                                                 dh <- alpha(d_cutoff, Te) d + (1 - alpha(d_cutoff, Te)) dh
+ *                                                 f  = min_cutoff + beta sqrt(sum over the group of dh^2)
+ *                                                 xh <- alpha(f, Te) x + (1 - alpha(f, Te)) xh,   w_last = w,  k = 1
+ *     it does not, and 1 <= k <= hold:            the estimate is HELD: the output is xh;  k <- k + 1
+ *     it does not otherwise:                      the output is NaN in every component;  k <- k + 1 if k >= 1
+ *     y = (float) xh, or NaN;   wy = w where the group took part, w_last where it was held, 0 where y is NaN
+ *   so a fit that is given (y, wy) sees a held point with the weight it last had and drops an expired one.
+ *   Consequences.  A drop-out of up to `hold` frames is bridged with the held estimate, and the recursion goes on with the Te of
+ *   the gap.  A longer one goes NaN after `hold` frames and restarts clean, from the first sample itself.  N frames in one call and
+ *   the same frames in any split of calls give the same bits: the state is the unrounded fp64 recursion.  y_dev == x_dev is legal
+ *   (a thread reads a frame's components before it writes them).  A thread per group walks the N frames.
+ *   Refused: null x / state / y; a state that is not 8-byte aligned; N < 1; D < 1; group outside 1 ... 4 or not dividing D;
+ *   weight_stride < 0 or in (0, G); rate, min_cutoff, d_cutoff not finite or <= 0; beta not finite or < 0; hold < 0; a state range
+ *   that overlaps x, w, y or wy.
+ * spk_colour_rows_causal: the colour match with exponential forgetting.  sums_dev fp64 [N][13] as spk_paste_colour_sums_sim /
+ *   spk_paste_colour_sums_nv12_sim write them; state_dev fp64 [13] = P, zeros are empty; decay in [0, 1]; rows_out_dev fp32
+ *   [N][3][2].  Per frame in order:
+ *     frame n TAKES PART iff S0_n > min_weight (a NaN fails) and all 13 of its sums are finite
+ *     P <- decay P + S_n  when it takes part (one fma per sum);   P is kept otherwise
+ *     row = (1, 0) for the three channels when P0 <= min_weight;  the row formula of spk_paste_colour_match_sim on P otherwise
+ *   Consequences.  The sums are linear, so this is the colour match of the face over a fading stretch of the past, every frame
+ *   weighing in with its weighted area.  decay = 0: P = S_n, and a clip whose every frame takes part gets the rows of
+ *   spk_paste_colour_match_sim bit for bit.  A frame without statistics keeps the previous row instead of snapping to (1, 0).  N
+ *   frames in one call and the same frames in any split of calls give the same bits.
+ *   Refused: null pointers; sums or state not 8-byte aligned; N < 1; decay outside [0, 1] or NaN; max_gain, min_sigma, min_weight
+ *   as spk_paste_colour_match_sim refuses them; sums, state and rows that overlap.
+ * Both refuse bad arguments before any launch (SPK_EINVAL, spk_last_error).  replaces: a filter class per landmark on the host
+ *   (a device -> host copy, a Python loop and an upload per frame) and an exponential average of colour rows, which is wrong for
+ *   the reason spk_colour_rows_window gives. */
+int spk_causal_filter(const float* x_dev, const float* w_dev, int64_t weight_stride, int N, int D, int group, double rate, double min_cutoff,
+                      double beta, double d_cutoff, int hold, double* state_dev, float* y_dev, float* wy_dev, void* stream);
+int spk_colour_rows_causal(const double* sums_dev, int N, double decay, double max_gain, double min_sigma, double min_weight, double* state_dev,
+                           float* rows_out_dev, void* stream);
+
 /* ---- counter-based decoder noise (csrc/noise.hip) ----------------------------------------------------------------------------
  * The noise planes of a synthesis pass as a pure function of (seed, frame, layer, pixel): no generator state, so a clip comes
  * out the same whatever the chunking or the sharding over devices, and a fixed-noise clip is every frame on one frame index.

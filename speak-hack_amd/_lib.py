@@ -355,6 +355,9 @@ _PROTOTYPES = {
                                             C.c_void_p, C.c_size_t, C.c_void_p]),
     "spk_colour_rows_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p]),
+    "spk_causal_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spk_colour_rows_causal": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spk_sim_fit_landmarks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "spk_sim_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "spk_matte_from_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p,

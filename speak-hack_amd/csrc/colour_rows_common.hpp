@@ -18,4 +18,17 @@ inline int check_match_params(const char* who, double max_gain, double min_sigma
     return SPK_OK;
 }
 
+// THE ROW FORMULA (include/spk.h, spk_paste_colour_match_sim): the (gain, offset) of one channel from its five sums, fp64, each
+// rounded to fp32 once; (1, 0) when `ok` does not hold.  min_var = min_sigma^2.  Every maker of rows calls this one function.
+__device__ __forceinline__ void colour_row(double S0, double Sq, double Sqq, double Sb, double Sbb, bool ok, double max_gain, double min_var,
+                                           float& g, float& o) {
+    g = 1.f, o = 0.f;
+    if (ok) {
+        const double mu_q = Sq / S0, var_q = fmax(Sqq / S0 - mu_q * mu_q, 0.0);
+        const double mu_b = Sb / S0, var_b = fmax(Sbb / S0 - mu_b * mu_b, 0.0);
+        const double gain = var_q <= min_var ? 1.0 : fmin(fmax(sqrt(var_b / var_q), 1.0 / max_gain), max_gain);
+        g = (float)gain, o = (float)(mu_b - gain * mu_q);
+    }
+}
+
 }  // namespace spk::frame

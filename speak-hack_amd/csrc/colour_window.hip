@@ -50,17 +50,12 @@ __global__ __launch_bounds__(WINDOW_THREADS) void colour_rows_window_kernel(cons
 #pragma unroll
         for (int i = 0; i < SUMS; ++i) P[i] = part ? fma(k, v[i], P[i]) : P[i];
     }
-    // the row formula: the expressions of paste_colour_rows_kernel, on P
+    // the row formula of paste_colour_rows_kernel, on P
     float* out = rows + (long long)r * 6;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        float g = 1.f, o = 0.f;
-        if (any) {
-            const double mu_q = P[1 + 4 * c] / P[0], var_q = fmax(P[2 + 4 * c] / P[0] - mu_q * mu_q, 0.0);
-            const double mu_b = P[3 + 4 * c] / P[0], var_b = fmax(P[4 + 4 * c] / P[0] - mu_b * mu_b, 0.0);
-            const double gain = var_q <= min_var ? 1.0 : fmin(fmax(sqrt(var_b / var_q), 1.0 / max_gain), max_gain);
-            g = (float)gain, o = (float)(mu_b - gain * mu_q);
-        }
+        float g, o;
+        colour_row(P[0], P[1 + 4 * c], P[2 + 4 * c], P[3 + 4 * c], P[4 + 4 * c], any, max_gain, min_var, g, o);
         out[2 * c] = g, out[2 * c + 1] = o;
     }
 }

@@ -157,13 +157,8 @@ __global__ __launch_bounds__(64) void paste_colour_rows_kernel(const double* __r
     const bool ok = load_sim(sim, n).valid && s[0] > min_weight;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        float g = 1.f, o = 0.f;
-        if (ok) {
-            const double mu_q = s[1 + 4 * c] / s[0], var_q = fmax(s[2 + 4 * c] / s[0] - mu_q * mu_q, 0.0);
-            const double mu_b = s[3 + 4 * c] / s[0], var_b = fmax(s[4 + 4 * c] / s[0] - mu_b * mu_b, 0.0);
-            const double gain = var_q <= min_var ? 1.0 : fmin(fmax(sqrt(var_b / var_q), 1.0 / max_gain), max_gain);
-            g = (float)gain, o = (float)(mu_b - gain * mu_q);
-        }
+        float g, o;
+        colour_row(s[0], s[1 + 4 * c], s[2 + 4 * c], s[3 + 4 * c], s[4 + 4 * c], ok, max_gain, min_var, g, o);
         colour[n * 6 + 2 * c] = g, colour[n * 6 + 2 * c + 1] = o;
     }
 }

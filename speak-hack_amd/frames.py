@@ -1,7 +1,8 @@
 """The video-frame edge of the inference path: uint8 frames as a video decoder / writer holds them on the device, in and out of the
 network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packed RGB through a similarity transform per frame
 (csrc/frame_sim.hip: aligned crops; csrc/frame_blend.hip: their paste with a face matte and a colour match; csrc/frame_sim_nv12.hip:
-all of that on NV12 surfaces), whose rows csrc/landmark_sim.hip fits to landmarks and smooths.  ``ops`` re-exports the
+all of that on NV12 surfaces), whose rows csrc/landmark_sim.hip fits to landmarks and smooths; csrc/causal_filter.hip: the causal
+filters of a live feed, their state on the device).  ``ops`` re-exports the
 launchers (``ops.frames_from_u8`` ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
 from __future__ import annotations
 
@@ -876,6 +877,134 @@ class LandmarkMatte:
             return _matte(landmarks, aligned.rows, Hs, Ws, idx, self.softness, self.grow, offset, None if fallback is None else fallback * k,
                           radius, sigma, what)
         return make
+
+
+# ---- causal filters with their state on the device (csrc/causal_filter.hip; the definitions are in include/spk.h) -------------------
+FILTER_DEFAULTS = dict(min_cutoff=1.0, beta=0.05, d_cutoff=1.0, hold=5)   # a face in a 30 fps feed, landmarks in frame pixels
+
+
+def check_filter_params(what, group, rate, min_cutoff, beta, d_cutoff, hold):
+    """The parameters of ``causal_filter`` as the entry point takes them, checked on the host: -> the six, as ints and floats"""
+    if isinstance(group, bool) or not isinstance(group, int) or not 1 <= group <= 4:
+        raise ValueError(f"{what}: group must be 1, 2, 3 or 4, got {group!r}")
+    rate, min_cutoff, d_cutoff = (_finite(v, n, what, positive=True) for v, n in ((rate, "rate"), (min_cutoff, "min_cutoff"), (d_cutoff, "d_cutoff")))
+    beta = _finite(beta, "beta", what)
+    if beta < 0.0:
+        raise ValueError(f"{what}: beta must be a finite number >= 0, got {beta}")
+    if isinstance(hold, bool) or not isinstance(hold, int) or not 0 <= hold < 2 ** 31:
+        raise ValueError(f"{what}: hold must be an integer >= 0 (frames a drop-out is bridged over), got {hold!r}")
+    return group, rate, min_cutoff, beta, d_cutoff, hold
+
+
+def causal_filter_state(D, group, device):
+    """The empty state of ``causal_filter`` for a signal of ``D`` components in groups of ``group``: zeros, float64
+    ``[D / group, 2 + 2 group]`` on ``device`` (per group ``(k, w_last, xh[group], dh[group])``; include/spk.h).  Zeroing it again
+    (``state.zero_()``) forgets the past."""
+    what = "causal_filter_state"
+    if isinstance(group, bool) or not isinstance(group, int) or not 1 <= group <= 4:
+        raise ValueError(f"{what}: group must be 1, 2, 3 or 4, got {group!r}")
+    if isinstance(D, bool) or not isinstance(D, int) or D < 1 or D % group:
+        raise ValueError(f"{what}: D must be a positive multiple of group = {group}, got {D!r}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.SpkError(f"{what}: the state lives on a HIP device, got {device} (no CPU path)")
+    return torch.zeros((D // group, 2 + 2 * group), device=device, dtype=torch.float64)
+
+
+def causal_filter(x, state, *, weights=None, group=2, rate=30.0, min_cutoff=1.0, beta=0.05, d_cutoff=1.0, hold=5, out=None):
+    """A one-euro filter over the next ``N`` frames of a signal, one launch (``spk_causal_filter``; include/spk.h has the recursion):
+    a low-pass whose cut-off is ``min_cutoff + beta |filtered speed|`` Hz, so what stands still is held steady and what moves is
+    followed without lag -- the causal counterpart of ``smooth_similarity_rows`` for a feed whose next frame does not exist yet,
+    applied to the landmarks themselves.  ``x``: a device float32 tensor ``[N, ...]``, frame after frame at ``rate`` frames per
+    second, its trailing dimensions flattened to ``D`` components in ``G = D / group`` groups of ``group`` consecutive ones that
+    share one speed (landmarks ``[N,K,2]``: ``group=2``; a feature vector: ``group=1``).  ``state``: the float64 ``[G, 2 + 2 group]``
+    tensor of ``causal_filter_state``, read at the start and written at the end of the call -- ``N`` frames in one call and the same
+    frames in any split of calls give the same bits.  ``weights``: None (all 1); a device float32 ``[G]`` (one set for all frames)
+    or ``[N,G]`` tensor, a tracker's confidences; or a host sequence ``[G]``, uploaded.  A group takes part in a frame when its
+    weight is finite and > 0 and its components are finite (the rule of ``similarity_from_landmarks``); a drop-out of up to ``hold``
+    frames is bridged with the held estimate, a longer one gives NaN from then on and restarts from the first sample that takes
+    part.  ``out``: a contiguous device float32 tensor in the shape of ``x`` to write, ``x`` itself included.
+    -> ``(y, wy)``: the filtered signal in the shape of ``x``, and float32 ``[N,G]`` weights -- the frame's own where the group took
+    part, the last one where it was held, 0 where ``y`` is NaN -- which is what ``similarity_from_landmarks(y, ..., weights=wy)``
+    takes."""
+    what = "causal_filter"
+    group, rate, min_cutoff, beta, d_cutoff, hold = check_filter_params(what, group, rate, min_cutoff, beta, d_cutoff, hold)
+    if not isinstance(x, torch.Tensor) or x.dim() < 2 or x.size(0) < 1 or x.numel() < 1 or x.numel() >= 2 ** 31:
+        got = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"{what}: x must be a tensor [N, ...] of N >= 1 frames (fewer than 2^31 numbers), got {got}")
+    N, D = x.size(0), x.numel() // x.size(0)
+    if D % group:
+        raise ValueError(f"{what}: group = {group} does not divide the {D} components of a frame")
+    G = D // group
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or tuple(state.shape) != (G, 2 + 2 * group):
+        got = f"{state.dtype} {tuple(state.shape)}" if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f"{what}: state must be a float64 tensor [{G},{2 + 2 * group}] (causal_filter_state), got {got}")
+    if isinstance(weights, torch.Tensor) and weights.is_cuda:
+        if weights.dtype != torch.float32 or tuple(weights.shape) not in ((G,), (N, G)):
+            raise ValueError(f"{what}: device weights must be a float32 tensor [{G}] or [{N},{G}], got {weights.dtype} {tuple(weights.shape)}")
+    elif weights is not None:
+        try:
+            weights = torch.as_tensor(weights).to(torch.float64).to(torch.float32)
+        except (ValueError, TypeError, RuntimeError) as e:
+            raise ValueError(f"{what}: weights must be [{G}] numbers: {e}") from None
+        if tuple(weights.shape) != (G,):
+            raise ValueError(f"{what}: host weights must be [{G}] numbers, one per group, got {tuple(weights.shape)}")
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(x.shape)):
+        got = tuple(out.shape) if isinstance(out, torch.Tensor) else type(out).__name__
+        raise ValueError(f"{what}: out must be a tensor in the shape of x {tuple(x.shape)}, got {got}")
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise L.SpkError(f"{what}: x: expected a float32 HIP tensor, got {x.dtype} on {x.device} (no CPU path)")
+    if state.device != x.device or not state.is_contiguous():
+        raise L.SpkError(f"{what}: state: expected a contiguous tensor on {x.device}, got strides {state.stride()} on {state.device}")
+    if out is not None and (out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous()):
+        raise L.SpkError(f"{what}: out: expected a contiguous float32 tensor on {x.device}, got {out.dtype} on {out.device}")
+    if weights is not None:
+        if weights.is_cuda and weights.device != x.device:
+            raise L.SpkError(f"{what}: weights on {weights.device}, x on {x.device}")
+        weights = weights.to(x.device).contiguous()
+    x = x.contiguous()
+    y = torch.empty_like(x) if out is None else out
+    wy = torch.empty((N, G), device=x.device, dtype=torch.float32)
+    L.check(L.lib().spk_causal_filter(x.data_ptr(), _ptr(weights), G if weights is not None and weights.dim() == 2 else 0, N, D, group, rate,
+                                      min_cutoff, beta, d_cutoff, hold, state.data_ptr(), y.data_ptr(), wy.data_ptr(), L.stream_ptr()),
+            "spk_causal_filter")
+    return y, wy
+
+
+def colour_rows_causal(sums, state, decay, *, max_gain=2.0, min_sigma=1.0, min_weight=16.0, out=None):
+    """Colour rows from the sums of the next ``N`` frames with exponential forgetting, one launch (``spk_colour_rows_causal``): the
+    causal counterpart of ``colour_rows_from_sums``.  ``sums``: a device float64 ``[N,13]`` tensor as ``paste_colour_sums`` /
+    ``paste_colour_sums_nv12`` write it.  ``state``: a device float64 ``[13]`` tensor, the pooled sums ``P`` (zeros: nothing yet), read
+    at the start and written at the end of the call.  Per frame, ``P <- decay P + S`` when the frame has statistics (``S0 >
+    min_weight``, all 13 sums finite), then ``paste_colour_match``'s row formula on ``P`` (``max_gain``, ``min_sigma``, ``min_weight``:
+    its parameters; ``(1, 0)`` while ``P0 <= min_weight``).  The sums are linear, so this is the match over a fading stretch of the
+    past: ``decay=0`` gives ``paste_colour_match``'s rows bit for bit on frames that all have statistics, ``decay`` near 1 a long
+    memory; a frame without statistics keeps the previous row.  ``N`` frames in one call and the same frames in any split of calls
+    give the same bits.  ``out``: a contiguous device float32 ``[N,3,2]`` tensor to write.  -> device float32 ``[N,3,2]``."""
+    what = "colour_rows_causal"
+    try:
+        decay = float(decay)
+    except (ValueError, TypeError):
+        raise ValueError(f"{what}: decay must be a number in [0, 1], got {decay!r}") from None
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"{what}: decay must be in [0, 1], got {decay}")
+    params = _check_match_params(what, max_gain, min_sigma, min_weight)
+    if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64 or sums.dim() != 2 or sums.size(1) != COLOUR_SUMS or sums.size(0) < 1:
+        got = f"{sums.dtype} {tuple(sums.shape)}" if isinstance(sums, torch.Tensor) else type(sums).__name__
+        raise ValueError(f"{what}: sums must be a float64 tensor [N,{COLOUR_SUMS}], got {got}")
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or tuple(state.shape) != (COLOUR_SUMS,):
+        got = f"{state.dtype} {tuple(state.shape)}" if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f"{what}: state must be a float64 tensor [{COLOUR_SUMS}], got {got}")
+    if not sums.is_cuda:
+        raise L.SpkError(f"{what}: sums on {sums.device} (no CPU path)")
+    if not sums.is_contiguous():
+        raise L.SpkError(f"{what}: sums: expected a contiguous tensor, got strides {sums.stride()}")
+    if state.device != sums.device or not state.is_contiguous():
+        raise L.SpkError(f"{what}: state: expected a contiguous tensor on {sums.device}, got strides {state.stride()} on {state.device}")
+    out = _stat_out(out, (sums.size(0), 3, 2), torch.float32, sums.device)
+    L.check(L.lib().spk_colour_rows_causal(sums.data_ptr(), sums.size(0), decay, *params, state.data_ptr(), out.data_ptr(), L.stream_ptr()),
+            "spk_colour_rows_causal")
+    return out
 
 
 # ---- NV12 (csrc/frame_nv12.hip; the definitions are in include/spk.h) ---------------------------------------------------------------

@@ -308,6 +308,45 @@ class IRFD(nn.Module):
                 fmt.paste_matched(py, out, p0, p1, pwhere, feather, blend["matte"], rows)
         return result
 
+    @torch.no_grad()
+    def live(self, identity_u8, *, size=256, template, contour=None, channel_order="rgb", identity_align=None, rate=30.0,
+             track=FR.FILTER_DEFAULTS, features=None, feather=0, matte_softness=4.0, matte_grow=0.0, colour_match=False, colour_decay=0.9,
+             seed=None, noise="fresh", offset=0.0):
+        """A reenactment session for a LIVE feed -- a camera or a call, where frame ``t + 1`` does not exist yet, or a long video
+        pushed through a few frames at a time: ``reenact_video(align=LandmarkAlign(...), paste=True, ...)`` with the clip's windows
+        replaced by causal filters whose state stays on the device (speak-hack_amd/live.py; csrc/causal_filter.hip).  Everything is
+        checked on the host (``ValueError``) before a device is touched; then ``Ei`` runs ONCE, on ``identity_u8`` ([H,W,3] or
+        [1,H,W,3], resized whole to ``size``, or cropped through ``identity_align``: as ``reenact_video``), and the session keeps
+        ``fi``.  -> a ``LiveSession``; ``session.step(frames_u8 [N,H,W,3], landmarks [N,K,2] device float32, *, weights=None,
+        emotion_u8=None, inplace=False)`` -> uint8 ``[N,H,W,3]``, the next ``N`` frames with the face pasted in.  Per ``step``:
+
+          1. ``ops.causal_filter`` over the landmarks (``track``: a dict over ``min_cutoff``, ``beta``, ``d_cutoff``, ``hold``, the
+             defaults of that launcher where a key is missing; None: the raw landmarks) -- a one-euro filter per landmark at ``rate``
+             frames per second, which holds a landmark over a drop-out of up to ``hold`` frames;
+          2. ``spk_sim_fit_landmarks`` of ``template`` ([K,2], the landmarks in the ``size`` network image; ``offset``: as
+             ``ops.similarity_from_landmarks``) on the filtered points with the filter's weights: a held point counts as it last did;
+          3. ``ops.frames_from_u8_aligned`` of the frames (and of ``emotion_u8``) with these rows;
+          4. ``Ee`` and ``Ep``: two launch lists;
+          5. with ``features`` (a dict as ``track``; None: off) the same filter with ``group=1`` over the emotion and pose features --
+             the identity part is not touched -- in which a frame without a transform takes no part;
+          6. the decoder, one launch list, with ``seed`` and frame index = the frames seen so far (``noise="fixed"``: index 0);
+          7. with ``contour`` (landmark indices in outline order) ``ops.matte_from_landmarks(smooth=0, softness=matte_softness,
+             grow=matte_grow)`` from the FILTERED points, the template's contour as fallback: the filter is the matte's steadiness;
+          8. with ``colour_match`` ``ops.paste_colour_sums`` and ``ops.colour_rows_causal(decay=colour_decay)``;
+          9. ``ops.frames_paste_u8_aligned(matte=, colour=, feather=)``: one launch.
+
+        A frame whose row is not finite (the landmarks lost for more than ``hold`` frames) passes through untouched.  Nothing in
+        ``step`` reads a device value on the host, and ``N`` frames in one step and the same frames in any split of steps give the
+        same bytes.  With ``track=None``, ``features=None``, ``colour_decay=0`` and frames that all have landmarks, a ``step`` over a
+        clip is ``reenact_video(align=LandmarkAlign(landmarks, template), paste=True, matte=LandmarkMatte(contour, smooth=0, ...),
+        colour_match=True, ...)`` byte for byte.  ``session.reset()`` empties the filter states and the frame counter
+        (``session.frames``); ``fi`` stays.  Packed RGB only: a session over NV12 surfaces is a follow-up."""
+        from .live import LiveSession
+        return LiveSession(self, identity_u8, size=size, template=template, contour=contour, channel_order=channel_order,
+                           identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,
+                           matte_softness=matte_softness, matte_grow=matte_grow, colour_match=colour_match, colour_decay=colour_decay, seed=seed,
+                           noise=noise, offset=offset)
+
     def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None, colour=("bt601", False)):
         """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan
         does not serve runs its eval branch with every submodule's own ``training`` flag saved and put back.  ``seeded``: the

@@ -753,6 +753,81 @@ def bench_colour_smooth(args, lines):
         lines.append(f"  (b) / (c) = {bc:.3f}" + ("  -> (b) beats (c) by more than the spread" if bc < 1 - spread else "  -> (b) does NOT beat (c) by more than the spread"))
 
 
+def bench_live(args, lines):
+    """``--live``: the latency of ONE frame of a live feed (1080 x 1920 BGR frames, K = 68 landmarks, 256^2 network and generated
+    images, N = 1), wall clock, synchronised before and after every call, two ways.  (a) ``LiveSession.step``: ``Ei`` ran once, the
+    landmarks, the features and the colour statistics are steadied by the causal filters.  (b) what a caller could do before:
+    ``reenact_video(align=LandmarkAlign(...), paste=True, matte=LandmarkMatte(..., smooth=0), colour_match=True)`` on a clip of one
+    frame, per frame -- ``Ei`` on every call, and no temporal state at all.  Then the two new launches alone, by HIP events."""
+    import importlib
+
+    import model
+    from oracle import irfd_ref as IR
+    from oracle.weights_recipe import fill_state_dict
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    T, size, Hf, Wf, side, feather, K, per = max(args.frames, 8), 256, 1080, 1920, 400, 16, 68, 20
+    g = torch.Generator().manual_seed(0)
+    ring = torch.arange(27, dtype=torch.float64) * (2 * math.pi / 27)       # an outline of 27 points, 41 points inside it
+    inner = torch.rand(K - 27, 2, generator=g, dtype=torch.float64) * 100 + 78
+    template = torch.cat([torch.stack([128 + 100 * torch.cos(ring), 128 + 110 * torch.sin(ring)], 1), inner]).float()
+    contour = list(range(27))
+    true = ops.similarity_rows([(300 + side / 2 + (5 * t) % 97, 700 + side / 2 + (7 * t) % 131) for t in range(T)], float(side),
+                               [0.3 * math.sin(0.9 * t) for t in range(T)], size).double()
+    a, c, tx, ty = (true[:, i].view(T, 1) for i in range(4))
+    u, v = template[:, 0].double().view(1, K), template[:, 1].double().view(1, K)
+    lm = torch.stack([a * u - c * v + tx, c * u + a * v + ty], 2) + 0.5 * torch.randn(T, K, 2, generator=g, dtype=torch.float64)
+    lm = lm.float().to(dev)
+    ident = torch.randint(0, 256, (1, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    video = torch.randint(0, 256, (T, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    m = model.IRFD()
+    sd = IR.irfd_recipe_state_dict()
+    sd.update({"Gd." + k: v for k, v in fill_state_dict(m.Gd.state_dict(), prefix="Gd.").items()})
+    m.load_state_dict(sd, strict=False)
+    m.to(dev).eval()
+    common = dict(size=size, channel_order="bgr", feather=feather, colour_match=True, seed=7)
+    session = m.live(ident, template=template, contour=contour, features={}, **common)
+    bare = m.live(ident, template=template, contour=contour, track=None, features=None, colour_decay=0.0, **common)
+
+    def step(s):
+        def f(t):
+            return s.step(video[t:t + 1], lm[t:t + 1])
+        return f
+
+    def per_frame_clip(t):
+        return m.reenact_video(ident, video[t:t + 1], align=ops.LandmarkAlign(lm[t:t + 1], template), paste=True,
+                               matte=ops.LandmarkMatte(contour, smooth=0), frame0=t, **common)
+
+    def latency(fn):                                                       # the mean wall clock of `per` frames, each synchronised on its own
+        total = 0.0
+        for i in range(per):
+            total += wall(lambda: fn(i % T))
+        return total / per
+
+    names = ("(a) LiveSession.step, filters on", "(b) reenact_video on a clip of one frame", "(a') LiveSession.step, filters off")
+    contenders = {names[0]: step(session), names[1]: per_frame_clip, names[2]: step(bare), names[0] + " (again)": step(session)}
+    for fn in contenders.values():
+        for t in range(args.warmup + 1):
+            fn(t)
+    bare.reset()
+    assert torch.equal(bare.step(video[:1], lm[:1]), per_frame_clip(0))    # filters off: the same bytes
+    lines.append(f"one frame of {Hf}x{Wf} BGR, K = {K} landmarks, outline of {len(contour)}, {size}^2 in and out over a rotated {side}x{side} region, "
+                 f"feather {feather}, matte and colour match; median of {args.repeats} alternating rounds of {per} frames")
+    times = alternate(contenders, args.repeats, latency)
+    ratio_table(lines, "wall clock per frame, synchronised before and after each frame:", times, names[0], [(names[1], True), (names[2], False)])
+    x2, x1 = lm[:1].clone(), torch.randn(1, 4096, generator=g).to(dev)
+    st2, st1 = ops.causal_filter_state(2 * K, 2, dev), ops.causal_filter_state(4096, 1, dev)
+    sums = ops.paste_colour_sums(torch.zeros(1, 3, size, size, device=dev), video[:1], true[:1].float().to(dev), channel_order="bgr")
+    P, rows = torch.zeros(13, dtype=torch.float64, device=dev), torch.empty(1, 3, 2, device=dev)
+    lines.append("the new launches alone, HIP events around 20 calls, launchers included:")
+    for name, fn in ((f"causal_filter, {K} landmarks (group 2), N = 1", lambda: ops.causal_filter(x2, st2)),
+                     ("causal_filter, 4096 features (group 1), N = 1", lambda: ops.causal_filter(x1, st1, group=1)),
+                     ("colour_rows_causal, N = 1", lambda: ops.colour_rows_causal(sums, P, 0.9, out=rows))):
+        ts = sorted(device_time(fn) for _ in range(args.repeats))
+        lines.append(f"  {name:48s} median {statistics.median(ts) * 1e6:7.1f} us  min {ts[0] * 1e6:7.1f}  max {ts[-1] * 1e6:7.1f}")
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -786,13 +861,18 @@ def main():
     ap.add_argument("--align", action="store_true", help="the aligned edge: frames_from_u8_aligned, frames_paste_u8_aligned, reenact_video(align=)")
     ap.add_argument("--blend", action="store_true", help="the seamless paste-back: matte, colour match and their torch composition")
     ap.add_argument("--align-nv12", action="store_true", help="the aligned NV12 edge: its three launchers beside their siblings and the BGR detour")
-    ap.add_argument("--commit", default="unknown", help="--blend / --align-nv12 / --colour-smooth: the commit the table is taken at, for its first line")
+    ap.add_argument("--commit", default="unknown", help="--blend / --align-nv12 / --colour-smooth / --live: the commit the table is taken at, for its first line")
     ap.add_argument("--landmarks", action="store_true", help="landmarks -> rows: similarity_from_landmarks, smooth_similarity_rows, the host route")
     ap.add_argument("--landmark-matte", action="store_true", help="landmarks -> matte: matte_from_landmarks, the host route, a torch composition")
     ap.add_argument("--colour-smooth", action="store_true", help="colour rows of a chunk: per frame, pooled over a window of sums, and filtered on the host")
+    ap.add_argument("--live", action="store_true", help="one frame of a live feed: LiveSession.step beside reenact_video on a clip of one frame")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.live:
+        lines = [f"bench_frame_io --live: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_live(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "live_bench.txt"))
     if args.colour_smooth:
         lines = [f"bench_frame_io --colour-smooth: {torch.cuda.get_device_name(0)}, at commit {args.commit}"]
         bench_colour_smooth(args, lines)

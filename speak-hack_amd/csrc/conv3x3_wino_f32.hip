@@ -22,12 +22,17 @@
 //     select, no mask, no vector instruction.  Wave w stages the planes of channels w and w + 4 for itself (10 x 34 floats
 //     each, two chunks ahead, 2 slots) and transforms them: no other wave reads its raw tile;
 //   * V: wave w transforms its two planes for all 64 tiles (a lane = a tile: 8 ds_read_b64 + 32 adds + 16 ds_write_b32 per
-//     plane), 2 slots;  one barrier per chunk.
+//     plane; the x2 form: a lane = a pair of tiles of one plane, below), 2 slots;  one barrier per chunk.
 // LDS: 2 x 32 KB (U) + 2 x 32 KB (V) + 2 x 11 KB (raw) = 150 KB.  Vector instructions per chunk of 64 MFMAs: 64 adds.
 // Epilogue: output transform and the f32 kernel's epilogue element for element (out_scale, bias, noise, LeakyReLU, [y_pre], style,
 // [accumulate]) in registers; a lane stores its tile's 2 x 2 pixels as two 8-byte stores, 16 lanes a whole 128-byte line.
 // A bilinear x2 layer (SPK_CONV_UPSAMPLE2X, template parameter UP) reads the low-resolution tensor: B^T (bilinear) B collapses into one
-// 4 x 3 matrix per dimension (up1d_), 49 vector ops per plane on a 3 x 3 raw window; no x2 image exists.
+// 4 x 3 matrix per dimension (up1d_, 7 vector ops) on a 3 x 3 raw window per tile; no x2 image exists.  There a lane is NOT a tile: a
+// half-wave takes one of the wave's two planes and a lane a vertical PAIR of tiles, whose 3 x 3 windows share two raw rows -- the row
+// pass (up1d_ along a raw row; its edge coefficients depend on the tile column only) runs once per shared row: a 4 x 3 window, 4
+// ds_read2_b32 + 4 ds_read_b32, 4 + 2 x 4 = 12 up1d_ = 84 vector ops, 32 ds_write_b32 per lane and chunk, where a lane per tile and
+// plane took 12 reads, 14 up1d_ = 98 ops, 32 writes.  Every V value keeps its bits.  (The plain form's horizontal pairs --
+// 6 shared columns, 56 adds for 64 -- were measured and bought nothing: DESIGN.md 4.12.)
 #include "conv_mfma_f32.hpp"
 
 namespace spkwino {
@@ -335,29 +340,36 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     // materialising one address register per constant that does not fit)
     int a_base = U_OFF + half * CO_T + wm * 32 + l32;               // + slot * U_FLOATS + (xi * 8 + 2 kk) * 64
     int b_base = V_OFF + half * NTILE + wn * 32 + l32;              // + slot * V_FLOATS + (xi * 8 + 2 kk) * 64
-    const int ty_l = lane / TXN, tx_l = lane % TXN;
+    // The input transform's lanes.  Plain and modulated forms: a lane = tile `lane` of the region, for both of the wave's planes.
+    // UP: half-wave `half` transforms plane `half` of the wave (channel wave + 4 half of the chunk), lane l32 of it a PAIR of tiles, (ty_l,
+    // tx_l) and the one below it (ty_l is even, as is TYN): the first 1-D pass runs once over the two raw rows the tiles share.
+    static_assert(TYN % 2 == 0, "UP: vertical tile pairs");
+    const int ty_l = UP ? 2 * (l32 / TXN) : lane / TXN, tx_l = UP ? l32 % TXN : lane % TXN;
     int raw_rd = (RAW_OFF + wave * RAW_WAVE + 2 * ty_l * RAW_W + 2 * tx_l) >> 1;   // in float pairs; + slot * RAW_FLOATS + j * RAW_PLANE + r * 34 + {0, 2}
-    int v_wr = V_OFF + wave * NTILE + lane;                         // + slot * V_FLOATS + (xi * 8 + 4 j) * 64
+    // + slot * V_FLOATS + (xi * 8 + 4 j) * 64;  UP: the lane's plane is part of the base, + slot * V_FLOATS + xi * 8 * 64 (+ TXN: the tile below)
+    int v_wr = UP ? V_OFF + (wave + 4 * half) * NTILE + ty_l * TXN + tx_l : V_OFF + wave * NTILE + lane;
     asm volatile("" : "+v"(a_base), "+v"(b_base), "+v"(raw_rd), "+v"(v_wr));
-    // UP: a lane (tile ty_l, tx_l) reads rows ty_l .. ty_l + 2, columns tx_l .. tx_l + 2 of the haloed low-resolution plane: 4-byte
-    // aligned only (ds_read2_b32 + ds_read_b32, whose offsets reach 1 KB: one base per raw slot and plane)
-    int raw_u[2][2];
-    float nk[4] = {-2.f, -2.f, -2.f, -2.f}, nkn[4] = {-2.f, -2.f, -2.f, -2.f};             // -kT, -kB, -kL, -kR of this lane's tile in the item whose planes are being transformed / in the next item
+    // UP: a lane (tiles ty_l, ty_l + 1 of column tx_l) reads rows ty_l .. ty_l + 3, columns tx_l .. tx_l + 2 of the haloed low-resolution
+    // plane: 4-byte aligned only (ds_read2_b32 + ds_read_b32, whose offsets reach 1 KB: one base per raw slot)
+    int raw_u[2];
+    // -kT of the pair's top tile, -kB of its bottom tile, -kL, -kR of both, in the item whose planes are being transformed / in the next
+    // item; the pair's inner two (the top tile's kB, the bottom tile's kT) are 2 everywhere: neg2
+    float nk[4] = {-2.f, -2.f, -2.f, -2.f}, nkn[4] = {-2.f, -2.f, -2.f, -2.f};
+    float neg2 = -2.f;
     const float six = 6.f;
     auto set_nk = [&](float (&k_)[4], int y0_, int x0_) {
         k_[0] = (y0_ == 0 && ty_l == 0) ? -6.f : -2.f;
-        k_[1] = (y0_ + RH >= p.H && ty_l == TYN - 1) ? -6.f : -2.f;
+        k_[1] = (y0_ + RH >= p.H && ty_l + 1 == TYN - 1) ? -6.f : -2.f;
         k_[2] = (x0_ == 0 && tx_l == 0) ? -6.f : -2.f;
         k_[3] = (x0_ + RW >= p.W && tx_l == TXN - 1) ? -6.f : -2.f;
     };
     if constexpr (UP) {
+        asm volatile("" : "+v"(neg2));               // (one register for the kernel, not a move in front of every use)
 #pragma unroll
-        for (int rs = 0; rs < 2; ++rs)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                raw_u[rs][j] = RAW_OFF + wave * RAW_WAVE + ty_l * RAW_W + tx_l + rs * RAW_FLOATS + j * PLANE;
-                asm volatile("" : "+v"(raw_u[rs][j]));
-            }
+        for (int rs = 0; rs < 2; ++rs) {
+            raw_u[rs] = RAW_OFF + wave * RAW_WAVE + half * PLANE + ty_l * RAW_W + tx_l + rs * RAW_FLOATS;
+            asm volatile("" : "+v"(raw_u[rs]));
+        }
     }
 
     f32x16 acc[16];
@@ -387,27 +399,43 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
         tv[j_][4 * (i_)] = fsub_(tq[j_][4 * (i_)], tq[j_][4 * (i_) + 2]); tv[j_][4 * (i_) + 1] = fadd_(tq[j_][4 * (i_) + 1], tq[j_][4 * (i_) + 2]); \
         tv[j_][4 * (i_) + 2] = fsub_(tq[j_][4 * (i_) + 2], tq[j_][4 * (i_) + 1]); tv[j_][4 * (i_) + 3] = fsub_(tq[j_][4 * (i_) + 1], tq[j_][4 * (i_) + 3]); \
     }
-    // UP: three raw rows of three; the 1-D transform along each raw row (tq: 3 x 4), then along each of the 4 columns (tv: 4 x 4)
-#define WINO_U_READ(rs_, j_, r_)                                                                                        \
-    {                                                                                                                   \
-        const volatile lds_f32_t* q_ = (const volatile lds_f32_t*)0 + (raw_u[rs_][j_] + (r_) * RAW_W);                  \
-        const f32x2 lo_ = *reinterpret_cast<const volatile lds_f32x2u_t*>(q_);                                          \
-        d[j_][3 * (r_) + 0] = lo_.x; d[j_][3 * (r_) + 1] = lo_.y; d[j_][3 * (r_) + 2] = q_[2];                          \
-    }
-#define WINO_U_H(j_, r_, nk_)                                                                                           \
-    up1d_(d[j_][3 * (r_)], d[j_][3 * (r_) + 1], d[j_][3 * (r_) + 2], (nk_)[2], (nk_)[3], six,                           \
-          tq[j_][4 * (r_)], tq[j_][4 * (r_) + 1], tq[j_][4 * (r_) + 2], tq[j_][4 * (r_) + 3]);
-#define WINO_U_V(j_, c_, nk_)                                                                                           \
-    up1d_(tq[j_][c_], tq[j_][4 + (c_)], tq[j_][8 + (c_)], (nk_)[0], (nk_)[1], six,                                      \
-          tv[j_][c_], tv[j_][4 + (c_)], tv[j_][8 + (c_)], tv[j_][12 + (c_)]);
 #define WINO_T_WRITE(vs_, j_, xi_)                                                                                      \
     *((volatile lds_f32_t*)0 + (v_wr + ((vs_) * V_FLOATS + ((xi_) * CI_T + 4 * (j_)) * NTILE))) = tv[j_][xi_];
     // LAB: the K loop's write, with its knock-outs (KO_TVALU: the raw value instead of the transformed one; KO_VWRITE: the value is kept alive, not written)
 #define WINO_T_WRITE_LOOP(vs_, j_, xi_)                                                                                 \
     {                                                                                                                   \
         if constexpr (KO_VWRITE) { if constexpr (!KO_TVALU) asm volatile("" :: "v"(tv[j_][xi_])); }                     \
-        else if constexpr (KO_TVALU) *((volatile lds_f32_t*)0 + (v_wr + ((vs_) * V_FLOATS + ((xi_) * CI_T + 4 * (j_)) * NTILE))) = d[j_][(xi_) % (UP ? 9 : 16)]; \
+        else if constexpr (KO_TVALU) *((volatile lds_f32_t*)0 + (v_wr + ((vs_) * V_FLOATS + ((xi_) * CI_T + 4 * (j_)) * NTILE))) = d[j_][xi_]; \
         else WINO_T_WRITE(vs_, j_, xi_)                                                                                 \
+    }
+    // UP, the lane's pair of tiles (tv[e]: tile e of the pair, 0 the upper one) of its one plane: four raw rows of three (d[0]: 4 x 3); the
+    // 1-D transform along each raw row (tq[0]: 4 x 4), ONCE for both tiles; then, per tile e_, along each of the 4 columns of its three rows
+    // e_ .. e_ + 2 (tv[e_]: 4 x 4) -- the tile's own operations on its own operands: every V value has the bits of a lane-per-tile transform
+#define WINO_U_READ(rs_, r_)                                                                                            \
+    {                                                                                                                   \
+        const volatile lds_f32_t* q_ = (const volatile lds_f32_t*)0 + (raw_u[rs_] + (r_) * RAW_W);                      \
+        const f32x2 lo_ = *reinterpret_cast<const volatile lds_f32x2u_t*>(q_);                                          \
+        d[0][3 * (r_) + 0] = lo_.x; d[0][3 * (r_) + 1] = lo_.y; d[0][3 * (r_) + 2] = q_[2];                             \
+    }
+#define WINO_U_H(r_, nk_)                                                                                               \
+    up1d_(d[0][3 * (r_)], d[0][3 * (r_) + 1], d[0][3 * (r_) + 2], (nk_)[2], (nk_)[3], six,                              \
+          tq[0][4 * (r_)], tq[0][4 * (r_) + 1], tq[0][4 * (r_) + 2], tq[0][4 * (r_) + 3]);
+#define WINO_U_V(e_, c_, nk_)                                                                                           \
+    up1d_(tq[0][4 * (e_) + (c_)], tq[0][4 * (e_) + 4 + (c_)], tq[0][4 * (e_) + 8 + (c_)], (e_) == 0 ? (nk_)[0] : neg2, (e_) == 0 ? neg2 : (nk_)[1], six, \
+          tv[e_][c_], tv[e_][4 + (c_)], tv[e_][8 + (c_)], tv[e_][12 + (c_)]);
+    // V[xi] of both tiles: TXN floats apart in [xi][ci][tile] -- two ds_write_b32 (the offsets of ds_write2_b32, 8 bits of dwords, do not
+    // reach the 2 KB from one xi to the next: it would take an address per xi)
+#define WINO_U_WRITE2(vs_, xi_, v0_, v1_)                                                                               \
+    {                                                                                                                   \
+        *((volatile lds_f32_t*)0 + (v_wr + ((vs_) * V_FLOATS + (xi_) * CI_T * NTILE))) = (v0_);                         \
+        *((volatile lds_f32_t*)0 + (v_wr + ((vs_) * V_FLOATS + (xi_) * CI_T * NTILE + TXN))) = (v1_);                   \
+    }
+#define WINO_U_WRITE(vs_, xi_) WINO_U_WRITE2(vs_, xi_, tv[0][xi_], tv[1][xi_])
+#define WINO_U_WRITE_LOOP(vs_, xi_)               /* LAB: as WINO_T_WRITE_LOOP */                                       \
+    {                                                                                                                   \
+        if constexpr (KO_VWRITE) { if constexpr (!KO_TVALU) asm volatile("" :: "v"(tv[0][xi_]), "v"(tv[1][xi_])); }     \
+        else if constexpr (KO_TVALU) WINO_U_WRITE2(vs_, xi_, d[0][(xi_) % 12], d[0][((xi_) + 6) % 12])                  \
+        else WINO_U_WRITE(vs_, xi_)                                                                                     \
     }
 
     if constexpr (RGB) {             // (published by the first chunk barrier, long before the first epilogue)
@@ -427,23 +455,25 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
     static_for<0, NG>([&](auto k) { WINO_DMA_RAW(voff[decltype(k)::value], kb, 0, decltype(k)::value); });
     static_for<0, NG>([&](auto k) { WINO_DMA_RAW(voff[decltype(k)::value], kb + 1, 1, decltype(k)::value); });
     __builtin_amdgcn_s_waitcnt(0x0f70);              // vmcnt(0): this wave's DMA has landed (its raw planes are its own)
-    static_for<0, 2>([&](auto j) {
-        if constexpr (UP) {
-            static_for<0, 3>([&](auto r) { WINO_U_READ(0, decltype(j)::value, decltype(r)::value); });
-            static_for<0, 3>([&](auto r) { WINO_U_H(decltype(j)::value, decltype(r)::value, nk); });
-            static_for<0, 4>([&](auto c) { WINO_U_V(decltype(j)::value, decltype(c)::value, nk); });
-        } else {
+    if constexpr (UP) {
+        static_for<0, 4>([&](auto r) { WINO_U_READ(0, decltype(r)::value); });
+        static_for<0, 4>([&](auto r) { WINO_U_H(decltype(r)::value, nk); });
+        static_for<0, 8>([&](auto k) { WINO_U_V(decltype(k)::value & 1, decltype(k)::value >> 1, nk); });
+        static_for<0, 16>([&](auto xi) { WINO_U_WRITE(0, decltype(xi)::value); });
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
+        static_for<0, 2>([&](auto j) {
             static_for<0, 4>([&](auto r) { WINO_T_READ(0, decltype(j)::value, decltype(r)::value); });
             static_for<0, 4>([&](auto c) { WINO_T_ROWS(decltype(j)::value, decltype(c)::value); });
             static_for<0, 4>([&](auto i) { WINO_T_COLS(decltype(j)::value, decltype(i)::value); });
-        }
-        if constexpr (MOD) {
-            const float sc0_ = p.in_scale[(size_t)b * p.Cin + kb * CI_T + wave + 4 * decltype(j)::value];
-            static_for<0, 4>([&](auto i) { WINO_T_SCALE(decltype(j)::value, decltype(i)::value, sc0_); });
-        }
-        static_for<0, 16>([&](auto xi) { WINO_T_WRITE(0, decltype(j)::value, decltype(xi)::value); });
-        __builtin_amdgcn_sched_barrier(0);           // one plane at a time: the register peak of this block decides what is spilled kernel-wide
-    });
+            if constexpr (MOD) {
+                const float sc0_ = p.in_scale[(size_t)b * p.Cin + kb * CI_T + wave + 4 * decltype(j)::value];
+                static_for<0, 4>([&](auto i) { WINO_T_SCALE(decltype(j)::value, decltype(i)::value, sc0_); });
+            }
+            static_for<0, 16>([&](auto xi) { WINO_T_WRITE(0, decltype(j)::value, decltype(xi)::value); });
+            __builtin_amdgcn_sched_barrier(0);       // one plane at a time: the register peak of this block decides what is spilled kernel-wide
+        });
+    }
     __syncthreads();
 
     // ---- main loop.  The chunks of ALL the workgroup's regions form one stream: chunk i of a region runs out of U / V slot
@@ -485,20 +515,25 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
                 if constexpr (KO_UBARE) { WINO_DMA_U_BARE(c1, O, s); }
                 else if constexpr (!KO_U) { WINO_DMA_U(c1, O, s); }
             } else if constexpr (s < U_DMA + NG && !KO_RAW) { WINO_DMA_RAW(voff[s - U_DMA], c2, S, s - U_DMA); }
-            // raw slot O -> V slot O.  plane 0: reads behind MFMAs 2-5, adds 8-15, writes 16-23; plane 1: 12-15, 24-31, 32-39
-            static_for<0, 2>([&](auto j_c) {
-                constexpr int j = decltype(j_c)::value, tr = 2 + 10 * j, ta = 8 + 16 * j;
-                if constexpr (UP) {           // (the same slots: 3 reads, 3 + 4 times the 7 ops of up1d_, one call behind one MFMA)
-                    if constexpr (s >= tr && s < tr + 3) { WINO_U_READ(O, j, s - tr); }
-                    if constexpr (!KO_TVALU && s >= ta && s < ta + 3) { WINO_U_H(j, s - ta, nk_); }
-                    if constexpr (!KO_TVALU && s >= ta + 4 && s < ta + 8) { WINO_U_V(j, s - ta - 4, nk_); }
-                } else {
-                if constexpr (s >= tr && s < tr + 4) { WINO_T_READ(O, j, s - tr); }
-                if constexpr (!KO_TVALU && s >= ta && s < ta + 4) { WINO_T_ROWS(j, s - ta); }
-                if constexpr (!KO_TVALU && s >= ta + 4 && s < ta + 8) { WINO_T_COLS(j, s - ta - 4); if constexpr (MOD) { WINO_T_SCALE(j, s - ta - 4, msc[j]); } }
-                }
-                if constexpr (s >= ta + 8 && s < ta + 16) { WINO_T_WRITE_LOOP(O, j, 2 * (s - ta - 8)); WINO_T_WRITE_LOOP(O, j, 2 * (s - ta - 8) + 1); }
-            });
+            // raw slot O -> V slot O
+            if constexpr (UP) {
+                // the pair of tiles of the lane's plane, one piece (a row's reads, one up1d_ = 7 ops, V[xi] of both tiles) behind one MFMA:
+                // reads 2-5, the four rows' first pass 8-11, the second pass 12-19 (per column: upper tile, lower tile), writes 20-35 in the
+                // order the columns were finished (xi = c, 4 + c, 8 + c, 12 + c)
+                if constexpr (s >= 2 && s < 6) { WINO_U_READ(O, s - 2); }
+                if constexpr (!KO_TVALU && s >= 8 && s < 12) { WINO_U_H(s - 8, nk_); }
+                if constexpr (!KO_TVALU && s >= 12 && s < 20) { WINO_U_V((s - 12) & 1, (s - 12) >> 1, nk_); }
+                if constexpr (s >= 20 && s < 36) { WINO_U_WRITE_LOOP(O, 4 * ((s - 20) & 3) + ((s - 20) >> 2)); }
+            } else {
+                // plane 0: reads behind MFMAs 2-5, adds 8-15, writes 16-23; plane 1: 12-15, 24-31, 32-39
+                static_for<0, 2>([&](auto j_c) {
+                    constexpr int j = decltype(j_c)::value, tr = 2 + 10 * j, ta = 8 + 16 * j;
+                    if constexpr (s >= tr && s < tr + 4) { WINO_T_READ(O, j, s - tr); }
+                    if constexpr (!KO_TVALU && s >= ta && s < ta + 4) { WINO_T_ROWS(j, s - ta); }
+                    if constexpr (!KO_TVALU && s >= ta + 4 && s < ta + 8) { WINO_T_COLS(j, s - ta - 4); if constexpr (MOD) { WINO_T_SCALE(j, s - ta - 4, msc[j]); } }
+                    if constexpr (s >= ta + 8 && s < ta + 16) { WINO_T_WRITE_LOOP(O, j, 2 * (s - ta - 8)); WINO_T_WRITE_LOOP(O, j, 2 * (s - ta - 8) + 1); }
+                });
+            }
             __builtin_amdgcn_sched_barrier(0);
         });
         __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0): the requested weights and this wave's raw planes have landed
@@ -761,6 +796,9 @@ __global__ __launch_bounds__(NT) void wino_kernel(const Args p) {
 #undef WINO_FRAG
 #undef WINO_T_WRITE_LOOP
 #undef WINO_T_WRITE
+#undef WINO_U_WRITE_LOOP
+#undef WINO_U_WRITE
+#undef WINO_U_WRITE2
 #undef WINO_U_V
 #undef WINO_U_H
 #undef WINO_U_READ

@@ -211,9 +211,9 @@ int spk_conv2d_pack_weights(const float* w, float* w_packed, int kh, int kw, int
 int spk_conv2d_pack_weights_list(const float* const* ws, int n, float* w_packed, int kh, int kw, int Cin, int Cout, int config,
                                  int transpose_flip, void* stream);
 int spk_conv2d_fwd(const spk_conv2d_desc* desc, void* stream);
-/* The form spk_conv2d_fwd(desc) would take, answered by the launch path's own statements on the host: nothing is launched and no
- * device is touched (pointers are read for their ALIGNMENT only, so any values of the right alignment do; a sliced launch still
- * needs workspace / workspace_bytes to be set).  Served: every descriptor that runs the tap kernel (tile configs 0-11, the 2x2
+/* The form spk_conv2d_fwd(desc) would take: the same routing and the same planner as the launch, whose plan is copied out instead
+ * of being launched.  No device is touched (pointers are read for their ALIGNMENT only, so any values of the right alignment do; a
+ * sliced launch still needs workspace / workspace_bytes to be set).  Served: every descriptor that runs the tap kernel (tile configs 0-11, the 2x2
  * parity forms of SPK_CONV_DGRAD_S2 / SPK_CONV_TRANSPOSE4X4_S2 included); SPK_CONV_WINOGRAD descriptors and the exact-tap data
  * gradient (config 13) fill ksplit / finisher / finisher_seg (config = -1 / 13, everything else 0).  The GEMM forms of a 1x1
  * and the stem kernel (spk_conv2d_gemm_form answers those) and SPK_CONV_BF16X3 are refused.
@@ -232,9 +232,9 @@ typedef struct spk_conv2d_form {
 } spk_conv2d_form;
 int spk_conv2d_launch_form(const spk_conv2d_desc* desc, spk_conv2d_form* out);
 /* The same question for the descriptors spk_conv2d_launch_form refuses: the GEMM forms of a stride-1 1x1 (tile configs 12, 14, 15)
- * and the 7x7 stride-2 stem kernel (config 16).  Answered by run_1x1_gemm / run_1x1_gemm2 / run_stem themselves after their own
- * requirements and argument set-up, before anything is launched; no device is touched, pointers are read for their alignment
- * only.  Every other descriptor is refused.
+ * and the 7x7 stride-2 stem kernel (config 16).  The planners of those launches state it (every requirement, the build, the tiles,
+ * grid and LDS bytes) and nothing is launched; no device is touched, pointers are read for their alignment only.  Every other
+ * descriptor is refused.
  *   build: the kernel instantiation -- GEMM forms 0 plain, 1 folded affine + ReLU input; stem 0 plain, 1 BatchNorm sums, 2 bias / lrelu
  *   k_tiles: steps of the contraction loop (32 channels on config 12, 16 on 14 / 15; the stem has one: K = 147)
  *   last_k_channels: channels the last k-tile adds; last_k_overlap (14 / 15): channels of the last k-tile the previous one

@@ -20,7 +20,7 @@
 //
 // replaces: F.conv2d of every stride-1 1x1 conv of the torchvision trunk (conv1 / conv3 / downsample.0 of layer1,
 // model.py:60-62) forward, and -- on the transposed weight -- its data gradient.
-#include "conv_mfma_f32.hpp"
+#include "conv_plan.hpp"
 
 namespace spkconv {
 
@@ -279,54 +279,57 @@ bool gemm1x1_takes(int kh, int stride, int Cin, int H, int W) {
 
 long long gemm1x1_pixel_tiles(int B, int H, int W) { return ((long long)B * H * W + GN - 1) / GN; }
 
-int run_1x1_gemm(const spk_conv2d_desc* d, hipStream_t stream) {
+// every requirement and decision of a config-12 launch; `a`: the kernel's argument block
+static int plan_args(const spk_conv2d_desc* d, GemmPlan& p, GemmArgs& a) {
     SPK_REQUIRE(gemm1x1_takes(d->kh, d->stride, d->Cin, d->H, d->W), "conv2d: config 12 (GEMM form) takes stride-1 1x1 convs with Cin %% 4 == 0 and H*W %% 32 == 0");
     SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_RESIDUAL)) && !d->out_scale_bc && !d->y_pre,
                 "conv2d: config 12 (GEMM form) takes bias / lrelu / accum / stats / in-affine / residual only");
-    SPK_REQUIRE(!(d->flags & SPK_EPI_RESIDUAL) || (reinterpret_cast<uintptr_t>(d->residual) & 15) == 0,
-                "conv2d: config 12 with SPK_EPI_RESIDUAL needs a 16-byte aligned residual");
-    SPK_REQUIRE(((reinterpret_cast<uintptr_t>(d->x) | reinterpret_cast<uintptr_t>(d->w_packed) | reinterpret_cast<uintptr_t>(d->y)) & 15) == 0,
-                "conv2d: config 12 needs 16-byte aligned x, y and weights");
-    GemmArgs a;
+    SPK_REQUIRE(!(d->flags & SPK_EPI_RESIDUAL) || aligned16(d->residual), "conv2d: config 12 with SPK_EPI_RESIDUAL needs a 16-byte aligned residual");
+    SPK_REQUIRE(aligned16(d->x) && aligned16(d->w_packed) && aligned16(d->y), "conv2d: config 12 needs 16-byte aligned x, y and weights");
+    const Groups q = groups_of(*d);
     a.x = d->x; a.w = d->w_packed; a.bias = d->bias; a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.stats = d->stats; a.y = d->y;
     a.residual = (d->flags & SPK_EPI_RESIDUAL) ? d->residual : nullptr;
     a.B = d->B; a.Cin = d->Cin; a.Cout = d->Cout; a.HW = d->H * d->W; a.n_px = (long long)d->B * a.HW;
-    a.G = d->groups > 1 ? d->groups : 1;
-    a.gin = a.G > 1 ? d->group_in_stride : d->Cin;
-    a.Cx = a.gin * (a.G - 1) + d->Cin;
-    a.Cy = a.G * d->Cout;
+    a.G = q.G; a.gin = q.gin; a.Cx = (int)q.Cx; a.Cy = (int)q.Cy;
     a.co_tiles_g = spk::ceil_div(d->Cout, GM);
     a.stats_slots = d->stats_slots > 1 ? d->stats_slots : 1;
-    a.flags = d->flags; a.slope = d->lrelu_slope; a.out_scale = d->out_scale; a.act_gain = d->act_gain != 0.f ? d->act_gain : 1.f;
+    a.flags = d->flags; a.slope = d->lrelu_slope; a.out_scale = d->out_scale; a.act_gain = act_gain_of(*d);
 #ifdef SPK_GEMM_LAB
     { const char* e = getenv("SPK_GEMM_LAB"); a.lab = e ? atoi(e) : 0; }
 #endif
     const long long gx = gemm1x1_pixel_tiles(d->B, d->H, d->W);
     SPK_REQUIRE(gx < (1ll << 31) && (long long)a.G * a.co_tiles_g < 65536, "conv2d: grid too large");
-    const size_t lds = (2 * (size_t)GBUF + 2 * GM) * sizeof(float);
-    const bool aff = d->flags & SPK_CONV_IN_AFFINE_RELU;
-    if (gemm_form_probe) {
-        spk_gemm_form& f = *gemm_form_probe;
-        const int n_kt = spk::ceil_div(d->Cin, GK);
-        f.config = kGemmConfig; f.build = aff;
-        f.k_tiles = n_kt; f.last_k_overlap = 0; f.last_k_channels = d->Cin - (n_kt - 1) * GK;
-        f.co_tiles = a.co_tiles_g; f.last_co_rows = d->Cout - (a.co_tiles_g - 1) * GM;
-        f.px_tiles = (int)gx; f.last_px_count = (int)(a.n_px - (gx - 1) * GN);
-        f.tile_spans_images = d->B > 1 && a.HW % GN != 0;
-        f.stats_own = (d->flags & SPK_EPI_STATS) && a.stats_slots >= gx;
-        f.accum_half = 0; f.residual = a.residual != nullptr;
-        f.grid_x = (int)gx; f.grid_y = a.G * a.co_tiles_g;
-        f.lds_bytes = (int64_t)lds;
-        return SPK_OK;
-    }
-    auto kern = aff ? &conv1x1_gemm_kernel<true> : &conv1x1_gemm_kernel<false>;
-    static bool raised[2] = {false, false};
-    if (!raised[aff]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised[aff] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)(a.G * a.co_tiles_g)), dim3(256), lds, stream, a);
+    p.grid = dim3((unsigned)gx, (unsigned)(a.G * a.co_tiles_g));
+    p.lds_bytes = (2 * (size_t)GBUF + 2 * GM) * sizeof(float);
+    spk_gemm_form& f = p.form;
+    f = spk_gemm_form{};
+    const int n_kt = spk::ceil_div(d->Cin, GK);
+    f.config = kGemmConfig; f.build = (d->flags & SPK_CONV_IN_AFFINE_RELU) ? 1 : 0;
+    f.k_tiles = n_kt; f.last_k_overlap = 0; f.last_k_channels = d->Cin - (n_kt - 1) * GK;
+    f.co_tiles = a.co_tiles_g; f.last_co_rows = d->Cout - (a.co_tiles_g - 1) * GM;
+    f.px_tiles = (int)gx; f.last_px_count = (int)(a.n_px - (gx - 1) * GN);
+    f.tile_spans_images = d->B > 1 && a.HW % GN != 0;
+    f.stats_own = (d->flags & SPK_EPI_STATS) && a.stats_slots >= gx;
+    f.accum_half = 0; f.residual = a.residual != nullptr;
+    f.grid_x = (int)gx; f.grid_y = a.G * a.co_tiles_g;
+    f.lds_bytes = (int64_t)p.lds_bytes;
+    return SPK_OK;
+}
+
+int plan_1x1_gemm(const spk_conv2d_desc* d, GemmPlan& p) {
+    GemmArgs a;
+    return plan_args(d, p, a);
+}
+
+int fwd_1x1_gemm(const spk_conv2d_desc* d, hipStream_t stream) {
+    GemmPlan p;
+    GemmArgs a;
+    int rc = plan_args(d, p, a);
+    if (rc != SPK_OK) return rc;
+    auto kern = p.form.build ? &conv1x1_gemm_kernel<true> : &conv1x1_gemm_kernel<false>;
+    rc = spk::raise_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds_bytes);
+    if (rc != SPK_OK) return rc;
+    hipLaunchKernelGGL(kern, p.grid, dim3(256), p.lds_bytes, stream, a);
     return spk::check_launch("conv1x1_gemm_kernel");
 }
 

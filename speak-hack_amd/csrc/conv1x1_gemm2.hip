@@ -30,7 +30,7 @@
 // forward and -- on the transposed weight -- its data gradient.
 // hipcc-flags: -fno-slp-vectorize
 // (every vector instruction counts here, and the SLP vectoriser's v_pk_* forms come with v_mov shuffles around them)
-#include "conv_mfma_f32.hpp"
+#include "conv_plan.hpp"
 
 namespace spkconv {
 
@@ -348,9 +348,7 @@ __global__ __launch_bounds__(256, (MT >= 4 ? 3 : 4)) void gemm2_kernel(const Gem
 }
 
 template <int MT>
-int launch(const Gemm2Args& a, bool aff, unsigned grid, hipStream_t stream) {
-    constexpr int CO_T = MT * 32;
-    constexpr size_t lds = 3 * (size_t)(KT * CO_T + KT * PX_T + 256) * sizeof(float);
+const void* kernel_of(bool aff) {
     auto kern = aff ? &gemm2_kernel<MT, true> : &gemm2_kernel<MT, false>;
 #ifdef SPK_G2_LAB
     if (const char* e = getenv("SPK_G2_LAB")) {
@@ -363,8 +361,7 @@ int launch(const Gemm2Args& a, bool aff, unsigned grid, hipStream_t stream) {
         }
     }
 #endif
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-    return spk::check_launch("gemm2_kernel");
+    return reinterpret_cast<const void*>(kern);
 }
 
 }  // namespace
@@ -413,32 +410,29 @@ int pack_gemm2(const PackList& list, int n_list, float* w_packed, int Cin, int C
     return spk::check_launch("pack_gemm2_kernel");
 }
 
-int run_1x1_gemm2(const spk_conv2d_desc* d, hipStream_t stream) {
+// every requirement and decision of a config-14 / 15 launch; `a`: the kernel's argument block
+static int plan_args(const spk_conv2d_desc* d, GemmPlan& p, Gemm2Args& a) {
     SPK_REQUIRE(gemm2_takes(d->kh, d->stride, d->Cin, d->Cout, d->H, d->W),
                 "conv2d: configs 14 / 15 (GEMM form) take stride-1 1x1 convs with H*W %% 4 == 0, Cin >= 16, Cin %% 4 == 0, Cout %% 8 == 0");
-    const int G = d->groups > 1 ? d->groups : 1;
-    const int gin = G > 1 ? d->group_in_stride : d->Cin;
-    const long long Cx = (long long)gin * (G - 1) + d->Cin, Cy = (long long)G * d->Cout, HWl = (long long)d->H * d->W;
-    SPK_REQUIRE(d->B * Cx * HWl < (1ll << 30) && d->B * Cy * HWl < (1ll << 30), "conv2d: configs 14 / 15 address x and y with 32-bit byte offsets");
-    SPK_REQUIRE(!(d->flags & SPK_CONV_IN_AFFINE_RELU) || ((reinterpret_cast<uintptr_t>(d->in_scale) | reinterpret_cast<uintptr_t>(d->in_shift)) & 15) == 0,
+    const Groups q = groups_of(*d);
+    const long long HWl = (long long)d->H * d->W;
+    SPK_REQUIRE(d->B * q.Cx * HWl < (1ll << 30) && d->B * q.Cy * HWl < (1ll << 30), "conv2d: configs 14 / 15 address x and y with 32-bit byte offsets");
+    SPK_REQUIRE(!(d->flags & SPK_CONV_IN_AFFINE_RELU) || (aligned16(d->in_scale) && aligned16(d->in_shift)),
                 "conv2d: configs 14 / 15 with IN_AFFINE_RELU need 16-byte aligned in_scale / in_shift");
     SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_ACCUM_HALF | SPK_EPI_RESIDUAL)) &&
                     !d->out_scale_bc && !d->y_pre,
                 "conv2d: configs 14 / 15 (GEMM form) take bias / lrelu / accum / accum-half / stats / in-affine / residual only");
-    SPK_REQUIRE(!(d->flags & SPK_EPI_RESIDUAL) || (reinterpret_cast<uintptr_t>(d->residual) & 15) == 0,
-                "conv2d: configs 14 / 15 with SPK_EPI_RESIDUAL need a 16-byte aligned residual");
-    SPK_REQUIRE(((reinterpret_cast<uintptr_t>(d->x) | reinterpret_cast<uintptr_t>(d->w_packed) | reinterpret_cast<uintptr_t>(d->y)) & 15) == 0,
-                "conv2d: configs 14 / 15 need 16-byte aligned x, y and weights");
-    Gemm2Args a;
+    SPK_REQUIRE(!(d->flags & SPK_EPI_RESIDUAL) || aligned16(d->residual), "conv2d: configs 14 / 15 with SPK_EPI_RESIDUAL need a 16-byte aligned residual");
+    SPK_REQUIRE(aligned16(d->x) && aligned16(d->w_packed) && aligned16(d->y), "conv2d: configs 14 / 15 need 16-byte aligned x, y and weights");
     a.x = d->x; a.w = d->w_packed; a.bias = d->bias; a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.stats = d->stats; a.y = d->y;
     a.Cin = d->Cin; a.Cout = d->Cout; a.HW = d->H * d->W; a.W = d->W; a.n_px = (unsigned)(d->B * HWl);
-    a.G = G; a.gin = gin; a.Cx = (int)Cx; a.Cy = (int)Cy;
+    a.G = q.G; a.gin = q.gin; a.Cx = (int)q.Cx; a.Cy = (int)q.Cy;
     const int co_t = gemm2_co_tile(d->config);
     a.co_tiles_g = spk::ceil_div(d->Cout, co_t);
     a.px_tiles = (int)gemm2_pixel_tiles(d->B, d->H, d->W);
     a.n_kt = spk::ceil_div(d->Cin, KT);
     a.stats_slots = d->stats_slots > 1 ? d->stats_slots : 1;
-    a.flags = d->flags; a.slope = d->lrelu_slope; a.out_scale = d->out_scale; a.act_gain = d->act_gain != 0.f ? d->act_gain : 1.f;
+    a.flags = d->flags; a.slope = d->lrelu_slope; a.out_scale = d->out_scale; a.act_gain = act_gain_of(*d);
     a.acc_half = nullptr; a.Wh = a.HWh = 0;
     a.residual = (d->flags & SPK_EPI_RESIDUAL) ? d->residual : nullptr;
     a.dbg = nullptr;
@@ -454,23 +448,39 @@ int run_1x1_gemm2(const spk_conv2d_desc* d, hipStream_t stream) {
     }
     const long long grid = (long long)a.px_tiles * a.co_tiles_g * a.G;
     SPK_REQUIRE(grid < (1ll << 31), "conv2d: grid too large");
-    const bool aff = d->flags & SPK_CONV_IN_AFFINE_RELU;
-    if (gemm_form_probe) {
-        spk_gemm_form& f = *gemm_form_probe;
-        f.config = d->config; f.build = aff;
-        f.k_tiles = a.n_kt; f.last_k_overlap = a.n_kt * KT - d->Cin; f.last_k_channels = d->Cin - (a.n_kt - 1) * KT;
-        f.co_tiles = a.co_tiles_g; f.last_co_rows = d->Cout - (a.co_tiles_g - 1) * co_t;
-        f.passes = co_t / 64; f.last_pass_rows = f.last_co_rows > (f.passes - 1) * 64 ? f.last_co_rows - (f.passes - 1) * 64 : 0;
-        f.px_tiles = a.px_tiles; f.last_px_count = (int)(a.n_px - (unsigned)(a.px_tiles - 1) * PX_T);
-        f.tile_spans_images = d->B > 1 && a.HW % PX_T != 0;
-        f.stats_own = (d->flags & SPK_EPI_STATS) && a.stats_slots >= a.px_tiles;
-        f.accum_half = a.acc_half != nullptr; f.residual = a.residual != nullptr;
-        f.grid_x = (int)grid; f.grid_y = 1;
-        f.lds_bytes = 3 * (int64_t)(KT * co_t + KT * PX_T + 256) * (int64_t)sizeof(float);
-        return SPK_OK;
-    }
-    if (d->config == kGemm2Config) return launch<4>(a, aff, (unsigned)grid, stream);
-    return launch<2>(a, aff, (unsigned)grid, stream);
+    p.grid = dim3((unsigned)grid);
+    p.lds_bytes = 3 * (size_t)(KT * co_t + KT * PX_T + 256) * sizeof(float);
+    spk_gemm_form& f = p.form;
+    f = spk_gemm_form{};
+    f.config = d->config; f.build = (d->flags & SPK_CONV_IN_AFFINE_RELU) ? 1 : 0;
+    f.k_tiles = a.n_kt; f.last_k_overlap = a.n_kt * KT - d->Cin; f.last_k_channels = d->Cin - (a.n_kt - 1) * KT;
+    f.co_tiles = a.co_tiles_g; f.last_co_rows = d->Cout - (a.co_tiles_g - 1) * co_t;
+    f.passes = co_t / 64; f.last_pass_rows = f.last_co_rows > (f.passes - 1) * 64 ? f.last_co_rows - (f.passes - 1) * 64 : 0;
+    f.px_tiles = a.px_tiles; f.last_px_count = (int)(a.n_px - (unsigned)(a.px_tiles - 1) * PX_T);
+    f.tile_spans_images = d->B > 1 && a.HW % PX_T != 0;
+    f.stats_own = (d->flags & SPK_EPI_STATS) && a.stats_slots >= a.px_tiles;
+    f.accum_half = a.acc_half != nullptr; f.residual = a.residual != nullptr;
+    f.grid_x = (int)grid; f.grid_y = 1;
+    f.lds_bytes = (int64_t)p.lds_bytes;
+    return SPK_OK;
+}
+
+int plan_1x1_gemm2(const spk_conv2d_desc* d, GemmPlan& p) {
+    Gemm2Args a;
+    return plan_args(d, p, a);
+}
+
+int fwd_1x1_gemm2(const spk_conv2d_desc* d, hipStream_t stream) {
+    GemmPlan p;
+    Gemm2Args a;
+    int rc = plan_args(d, p, a);
+    if (rc != SPK_OK) return rc;
+    const void* kern = p.form.config == kGemm2Config ? kernel_of<4>(p.form.build) : kernel_of<2>(p.form.build);
+    rc = spk::raise_dynamic_lds(kern, p.lds_bytes);
+    if (rc != SPK_OK) return rc;
+    void* argv[1] = {&a};
+    (void)hipLaunchKernel(kern, p.grid, dim3(256), argv, p.lds_bytes, stream);
+    return spk::check_launch("gemm2_kernel");
 }
 
 }  // namespace spkconv

@@ -689,12 +689,8 @@ int spk_conv2d_bf16x3_fwd(const spk_conv2d_desc* d, void* stream) {
                                 a.staged ? (size_t)CO_T * (PIX_T + 4) * sizeof(float) : (size_t)0);
     SPK_REQUIRE(lds <= 160 * 1024, "conv2d bf16x3: tile does not fit LDS");
     auto kern = ups ? &conv3x3_bf16x3_kernel<true> : &conv3x3_bf16x3_kernel<false>;
-    static bool raised[2] = {false, false};
-    if (!raised[ups ? 1 : 0]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised[ups ? 1 : 0] = true;
-    }
+    const int rc = spk::raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
+    if (rc != SPK_OK) return rc;
     const long long gx = (long long)g.tiles_x * g.tiles_y * g.tiles_b;
     SPK_REQUIRE(gx < (1ll << 31), "conv2d bf16x3: grid too large");
     dim3 grid((unsigned)gx, (unsigned)spk::ceil_div(d->Cout, CO_T));

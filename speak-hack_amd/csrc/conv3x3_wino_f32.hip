@@ -33,7 +33,7 @@
 // ds_read2_b32 + 4 ds_read_b32, 4 + 2 x 4 = 12 up1d_ = 84 vector ops, 32 ds_write_b32 per lane and chunk, where a lane per tile and
 // plane took 12 reads, 14 up1d_ = 98 ops, 32 writes.  Every V value keeps its bits.  (The plain form's horizontal pairs --
 // 6 shared columns, 56 adds for 64 -- were measured and bought nothing: DESIGN.md 4.12.)
-#include "conv_mfma_f32.hpp"
+#include "conv_plan.hpp"
 
 namespace spkwino {
 
@@ -899,18 +899,29 @@ int64_t spk_conv2d_wino_workspace_bytes(int ksplit, int B, int Cin, int Cout, in
     return ks > 1 ? (int64_t)ks * B * Cout * H * W * 4 : 0;
 }
 
-// entered from spk_conv2d_fwd when desc->flags has SPK_CONV_WINOGRAD
-int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
+}  // extern "C"
+
+// The kernel choice of a Winograd launch as integers, and what its grid is derived from (the grid itself depends on the device)
+struct WinoKernel {
+    bool mod, rgb, up;
+    int shape, epi_form;
+    long long n_items;
+    int co_tiles;
+};
+
+// every requirement and decision of a SPK_CONV_WINOGRAD launch, without a HIP call; `a`: the kernel's argument block
+static int plan_args(const spk_conv2d_desc* d, spkconv::SlicedPlan& p, Args& a, WinoKernel& k) {
+    using spkconv::aligned16;
     SPK_REQUIRE(d && d->x && d->w_packed, "conv2d winograd: null pointer");
     SPK_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 1, "conv2d winograd: 3x3 stride-1 kernels only");
-    const int G = d->groups > 1 ? d->groups : 1;
+    const spkconv::Groups q = spkconv::groups_of(*d);
+    const int G = q.G, gin = q.gin, Cx = (int)q.Cx, Cy = (int)q.Cy;
     const bool up = d->flags & SPK_CONV_UPSAMPLE2X;
     SPK_REQUIRE(!up || (G == 1 && !(d->flags & (SPK_CONV_IN_BATCH_SCALE | SPK_CONV_UP_FIR1331))),
                 "conv2d winograd: SPK_CONV_UPSAMPLE2X is the bilinear x2 of a plain launch (no IN_BATCH_SCALE, no UP_FIR1331, no groups): "
                 "pass the x2 image (spk_upsample2x_fwd)");
     SPK_REQUIRE(G == 1 || !(d->flags & ~(SPK_CONV_WINOGRAD | SPK_EPI_ACCUM)), "conv2d winograd: a grouped launch takes SPK_EPI_ACCUM only (the encoders' "
                 "data gradients)");
-    const int gin = G > 1 ? d->group_in_stride : d->Cin, Cx = gin * (G - 1) + d->Cin, Cy = G * d->Cout;
     SPK_REQUIRE(G == 1 || gin >= d->Cin, "conv2d winograd: groups read disjoint channels");
     const unsigned epi = SPK_EPI_BIAS | SPK_EPI_NOISE | SPK_EPI_LRELU | SPK_EPI_STYLE | SPK_EPI_ACCUM;
     const unsigned allowed = SPK_CONV_WINOGRAD | epi | SPK_CONV_IN_BATCH_SCALE | SPK_EPI_TORGB | SPK_CONV_UPSAMPLE2X;
@@ -934,7 +945,6 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     SPK_REQUIRE(!(d->flags & SPK_EPI_BIAS) || d->bias, "conv2d winograd: SPK_EPI_BIAS without bias");
     SPK_REQUIRE(!(d->flags & SPK_EPI_NOISE) || (d->noise && d->noise_w), "conv2d winograd: SPK_EPI_NOISE without noise");
     SPK_REQUIRE(!(d->flags & SPK_EPI_STYLE) || d->style, "conv2d winograd: SPK_EPI_STYLE without style");
-    const auto aligned16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     SPK_REQUIRE(aligned16(d->w_packed) && aligned16(d->y) && aligned16(d->y_pre) && aligned16(d->noise) && (reinterpret_cast<uintptr_t>(d->x) & 3) == 0,
                 "conv2d winograd: tensors must be 16-byte aligned");
     const int shape = wino_shape(d->H, d->W);
@@ -944,7 +954,6 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
         SPK_REQUIRE(d->workspace && aligned16(d->workspace) && d->workspace_bytes >= (int64_t)ks * (int64_t)out_floats * 4,
                     "conv2d winograd: %d contraction slices need a workspace of %lld bytes (spk_conv2d_wino_workspace_bytes)", ks,
                     (long long)ks * (long long)out_floats * 4);
-    Args a;
     a.x = d->x; a.wp = d->w_packed; a.bias = d->bias; a.noise_w = d->noise_w; a.noise = d->noise; a.style = d->style;
     a.y = d->y; a.y_pre = d->y_pre; a.out_scale_dev = d->out_scale_dev;
     a.in_scale = mod ? d->in_scale : nullptr; a.out_scale_bc = d->out_scale_bc;
@@ -957,25 +966,30 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     a.style_stride = d->style_stride; a.flags = d->flags;
     a.x_bytes = (unsigned)((long long)d->B * Cx * d->Hin * d->Win * 4);
     const float up_scale = up ? 0.0625f : 1.f;      // UP: the input transform yields 16 V (up1d_)
-    a.slope = d->lrelu_slope; a.out_scale = d->out_scale * up_scale; a.act_gain = d->act_gain != 0.f ? d->act_gain : 1.f;
+    a.slope = d->lrelu_slope; a.out_scale = d->out_scale * up_scale; a.act_gain = spkconv::act_gain_of(*d);
     SPK_REQUIRE(!rgb || ks == 1, "conv2d winograd: SPK_EPI_TORGB with a sliced contraction (%d slices): pass ksplit = 1 or run the 1x1 separately", ks);
     if (ks > 1) {       // partial sums, raw: the whole epilogue (and the demodulation) belongs to the finisher
         a.y = static_cast<float*>(d->workspace); a.y_pre = nullptr; a.out_scale_dev = nullptr; a.out_scale_bc = nullptr;
         a.flags = d->flags & ~epi; a.out_scale = 1.f; a.slice_floats = out_floats;
     }
-    spkconv::ConvArgs f = {};       // the finisher's arguments
-    if (ks > 1) {
-        f.bias = d->bias; f.noise_w = d->noise_w; f.noise = d->noise; f.style = d->style; f.out_scale_bc = d->out_scale_bc;
-        f.y = d->y; f.y_pre = d->y_pre; f.B = d->B; f.Cin = d->Cin; f.Cout = d->Cout; f.Cy = Cy; f.Cx = Cx; f.G = G; f.H = d->H; f.W = d->W;
-        f.style_stride = d->style_stride; f.flags = d->flags & epi; f.slope = d->lrelu_slope; f.out_scale = d->out_scale * up_scale;
-        f.act_gain = a.act_gain; f.out_scale_dev = d->out_scale_dev;
-    }
-    if (spkconv::form_probe) return spkconv::report_sliced_form(f, static_cast<const float*>(d->workspace), ks);
+    p.config = -1;
+    p.finish.args = spkconv::finisher_args(*d, q, d->flags & epi, d->out_scale * up_scale);
+    p.finish.ws = static_cast<const float*>(d->workspace);
+    p.finish.ksplit = ks;
     // the rows' form: LEAN for whole channel tiles without y_pre / accumulate (every inference launch of the decoder, and the sliced
     // launches' raw partial sums); everything else -- and a slope outside (0, 1], which the lean rows' max() does not cover -- GENERIC
     const bool lrelu_ok = !(a.flags & SPK_EPI_LRELU) || (a.slope > 0.f && a.slope <= 1.f);
     const bool lean_ok = !mod && lrelu_ok && !a.y_pre && !(a.flags & SPK_EPI_ACCUM) && 20ll * d->H * d->W < (1ll << 32);
-    const int epi_form = !lean_ok ? GENERIC : rgb ? (!a.y ? LEAN_NOSTORE : d->Cout == CO_T ? LEAN : GENERIC) : (d->Cout % CO_T == 0 ? LEAN : GENERIC);
+    k.mod = mod; k.rgb = rgb; k.up = up; k.shape = shape;
+    k.epi_form = !lean_ok ? GENERIC : rgb ? (!a.y ? LEAN_NOSTORE : d->Cout == CO_T ? LEAN : GENERIC) : (d->Cout % CO_T == 0 ? LEAN : GENERIC);
+    k.n_items = (long long)a.regions_x * a.regions_y * d->B * ks;
+    SPK_REQUIRE(k.n_items < (1ll << 31), "conv2d winograd: grid too large");
+    k.co_tiles = G * spk::ceil_div(d->Cout, CO_T);
+    return SPK_OK;
+}
+
+static const void* wino_kernel_of(const WinoKernel& k) {
+    const int shape = k.shape, epi_form = k.epi_form;
     const auto pick = [&](auto rgb_c, auto up_c) -> void (*)(const Args) {
         constexpr bool R = decltype(rgb_c)::value, U = decltype(up_c)::value;
         if constexpr (R) {
@@ -986,21 +1000,30 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     };
     using T_ = std::true_type;
     using F_ = std::false_type;
-    void (*kern)(const Args) = mod ? (shape == SQUARE ? &wino_kernel<true, SQUARE> : &wino_kernel<true, WIDE>)
-                               : rgb ? (up ? pick(T_{}, T_{}) : pick(T_{}, F_{})) : (up ? pick(F_{}, T_{}) : pick(F_{}, F_{}));
-    static const void* raised[32];          // the kernels whose LDS limit has been raised
-    static int n_raised = 0;
-    bool seen = false;
-    for (int i = 0; i < n_raised; ++i) seen = seen || raised[i] == reinterpret_cast<const void*>(kern);
-    if (!seen) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        if (n_raised < 32) raised[n_raised++] = reinterpret_cast<const void*>(kern);
-    }
-    const long long n_items = (long long)a.regions_x * a.regions_y * d->B * ks;
-    SPK_REQUIRE(n_items < (1ll << 31), "conv2d winograd: grid too large");
+    void (*kern)(const Args) = k.mod ? (shape == SQUARE ? &wino_kernel<true, SQUARE> : &wino_kernel<true, WIDE>)
+                               : k.rgb ? (k.up ? pick(T_{}, T_{}) : pick(T_{}, F_{})) : (k.up ? pick(F_{}, T_{}) : pick(F_{}, F_{}));
+    return reinterpret_cast<const void*>(kern);
+}
+
+int spkconv::plan_wino(const spk_conv2d_desc* d, SlicedPlan& p) {
+    Args a;
+    WinoKernel k;
+    return plan_args(d, p, a, k);
+}
+
+extern "C" {
+
+// entered from spk_conv2d_fwd when desc->flags has SPK_CONV_WINOGRAD
+int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
+    spkconv::SlicedPlan p;
+    Args a;
+    WinoKernel k;
+    int rc = plan_args(d, p, a, k);
+    if (rc != SPK_OK) return rc;
+    const void* kern = wino_kernel_of(k);
+    rc = spk::raise_dynamic_lds(kern, LDS_BYTES);
+    if (rc != SPK_OK) return rc;
     // persistent: one workgroup per CU over all channel tiles, a multiple of 8 per channel tile (the XCD shares), at most one per item
-    const int co_tiles = G * spk::ceil_div(d->Cout, CO_T);
     static int n_cu = 0;
     if (n_cu == 0) {
         int dev = 0;
@@ -1008,16 +1031,15 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return spk::fail(SPK_ELAUNCH, "conv2d winograd: no device properties");
         n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    long long gx = std::max(8ll, ((long long)n_cu / co_tiles) / 8 * 8);
+    long long gx = std::max(8ll, ((long long)n_cu / k.co_tiles) / 8 * 8);
     static int lab_mult = -1;       // LAB: SPK_WINO_WGS = workgroups per CU slot (0: one workgroup per item)
     if (lab_mult < 0) { const char* e = getenv("SPK_WINO_WGS"); lab_mult = e ? atoi(e) : 1; }
-    gx = lab_mult == 0 ? (n_items + 7) / 8 * 8 : gx * lab_mult;
-    gx = std::min(gx, (n_items + 7) / 8 * 8);
-    dim3 grid((unsigned)gx, (unsigned)co_tiles);
-    hipLaunchKernelGGL(kern, grid, dim3(NT), LDS_BYTES, (hipStream_t)stream, a);
-    int rc = spk::check_launch("wino_kernel");
-    if (rc != SPK_OK || ks == 1) return rc;
-    return spkconv::launch_splitk_epilogue(f, static_cast<const float*>(d->workspace), ks, (hipStream_t)stream);
+    gx = lab_mult == 0 ? (k.n_items + 7) / 8 * 8 : gx * lab_mult;
+    gx = std::min(gx, (k.n_items + 7) / 8 * 8);
+    void* argv[1] = {&a};
+    (void)hipLaunchKernel(kern, dim3((unsigned)gx, (unsigned)k.co_tiles), dim3(NT), argv, LDS_BYTES, (hipStream_t)stream);
+    rc = spk::check_launch("wino_kernel");
+    return rc != SPK_OK ? rc : spkconv::launch_finish(p.finish, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@
 //   * no vector instruction in the k loop (on gfx950 the f32 MFMA and the vector ALU do not overlap: DESIGN.md 4.7); two
 //     workgroups per CU (69 KB of LDS each) cover each other's staging and epilogue.
 // Epilogue: plain stores (16-byte: four consecutive pixels of a channel per accumulator group) + SPK_EPI_STATS.
-#include "conv_mfma_f32.hpp"
+#include "conv_plan.hpp"
 
 namespace spkconv {
 
@@ -242,49 +242,58 @@ int pack_stem(const PackList& list, int n, float* w_packed, int Cin, int Cout, i
     return spk::check_launch("pack_stem_kernel");
 }
 
-int run_stem(const spk_conv2d_desc* d, hipStream_t stream) {
-    const int G = d->groups > 1 ? d->groups : 1;
+// every requirement and decision of a config-16 launch; `a`: the kernel's argument block
+static int plan_args(const spk_conv2d_desc* d, GemmPlan& p, StemArgs& a) {
+    SPK_REQUIRE(!(d->flags & (SPK_CONV_UPSAMPLE2X | SPK_CONV_IN_AFFINE_RELU | SPK_CONV_IN_BATCH_SCALE | SPK_EPI_ACCUM_HALF)), "conv2d: the stem form reads a plain input");
+    const Groups q = groups_of(*d);
     SPK_REQUIRE(stem_takes(d->kh, d->stride, d->Cin, d->Cout, d->H, d->W) && d->kw == 7, "conv2d: config %d is the 7x7 stride-2 stem (Cin 3, Cout 64, W %% 4 == 0)", kStemConfig);
     const bool epi = d->flags & (SPK_EPI_BIAS | SPK_EPI_LRELU);
     SPK_REQUIRE(!(d->flags & ~(SPK_EPI_STATS | SPK_EPI_BIAS | SPK_EPI_LRELU)) && !(epi && (d->flags & SPK_EPI_STATS)) && d->out_scale == 1.f &&
                     !d->out_scale_dev && !d->out_scale_bc && !d->y_pre && (d->act_gain == 0.f || d->act_gain == 1.f),
                 "conv2d: the stem form takes SPK_EPI_STATS, or SPK_EPI_BIAS / SPK_EPI_LRELU (a BatchNorm-folded stem), only");
-    SPK_REQUIRE(((reinterpret_cast<uintptr_t>(d->y) | reinterpret_cast<uintptr_t>(d->w_packed)) & 15) == 0, "conv2d: stem form: y and w_packed must be 16-byte aligned");
+    SPK_REQUIRE(aligned16(d->y) && aligned16(d->w_packed), "conv2d: stem form: y and w_packed must be 16-byte aligned");
     SPK_REQUIRE((long long)d->Hin * d->Win * 3 < (1ll << 29), "conv2d: stem form: image too large for 32-bit offsets");
-    StemArgs a;
     a.x = d->x; a.w = d->w_packed; a.y = d->y; a.stats = (d->flags & SPK_EPI_STATS) ? d->stats : nullptr;
     a.B = d->B; a.H = d->H; a.W = d->W; a.Hin = d->Hin; a.Win = d->Win;
-    a.gin = G > 1 ? d->group_in_stride : 0;
-    a.Cx = a.gin * (G - 1) + 3;
-    a.Cy = G * 64;
+    a.gin = q.G > 1 ? q.gin : 0;
+    a.Cx = (int)q.Cx;
+    a.Cy = (int)q.Cy;
     stem_tiles(d->H, d->W, &a.tiles_x, &a.tiles_y);
     a.stats_slots = d->stats_slots > 1 ? d->stats_slots : 1;
     a.bias = (d->flags & SPK_EPI_BIAS) ? d->bias : nullptr;
     a.slope = (d->flags & SPK_EPI_LRELU) ? d->lrelu_slope : 1.f;
     const long long tiles = (long long)a.tiles_x * a.tiles_y * d->B;
     SPK_REQUIRE(tiles < (1ll << 31), "conv2d: stem form: too many tiles");
-    auto kern = a.stats ? &stem7x7s2_kernel<true> : (epi ? &stem7x7s2_kernel<false, true> : &stem7x7s2_kernel<false>);
-    static bool raised[3] = {false, false, false};
-    const int which = a.stats ? 1 : (epi ? 2 : 0);
-    if (gemm_form_probe) {
-        spk_gemm_form& f = *gemm_form_probe;
-        f.config = kStemConfig; f.build = which;
-        f.k_tiles = 1; f.last_k_overlap = 0; f.last_k_channels = ST_K;
-        f.co_tiles = 1; f.last_co_rows = 64;
-        f.tiles_x = a.tiles_x; f.tiles_y = a.tiles_y;
-        f.last_tile_cols = d->W - (a.tiles_x - 1) * ST_TW; f.last_tile_rows = d->H - (a.tiles_y - 1) * ST_TH;
-        f.px_tiles = (int)tiles; f.last_px_count = f.last_tile_cols * f.last_tile_rows;
-        f.stats_own = a.stats && a.stats_slots >= tiles;
-        f.grid_x = (int)tiles; f.grid_y = G;
-        f.lds_bytes = ST_LDS_BYTES;
-        return SPK_OK;
-    }
-    if (!raised[which]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-        raised[which] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)G), dim3(256), ST_LDS_BYTES, stream, a);
+    p.grid = dim3((unsigned)tiles, (unsigned)q.G);
+    p.lds_bytes = ST_LDS_BYTES;
+    spk_gemm_form& f = p.form;
+    f = spk_gemm_form{};
+    f.config = kStemConfig; f.build = a.stats ? 1 : (epi ? 2 : 0);
+    f.k_tiles = 1; f.last_k_overlap = 0; f.last_k_channels = ST_K;
+    f.co_tiles = 1; f.last_co_rows = 64;
+    f.tiles_x = a.tiles_x; f.tiles_y = a.tiles_y;
+    f.last_tile_cols = d->W - (a.tiles_x - 1) * ST_TW; f.last_tile_rows = d->H - (a.tiles_y - 1) * ST_TH;
+    f.px_tiles = (int)tiles; f.last_px_count = f.last_tile_cols * f.last_tile_rows;
+    f.stats_own = a.stats && a.stats_slots >= tiles;
+    f.grid_x = (int)tiles; f.grid_y = q.G;
+    f.lds_bytes = ST_LDS_BYTES;
+    return SPK_OK;
+}
+
+int plan_stem(const spk_conv2d_desc* d, GemmPlan& p) {
+    StemArgs a;
+    return plan_args(d, p, a);
+}
+
+int fwd_stem(const spk_conv2d_desc* d, hipStream_t stream) {
+    GemmPlan p;
+    StemArgs a;
+    int rc = plan_args(d, p, a);
+    if (rc != SPK_OK) return rc;
+    auto kern = p.form.build == 1 ? &stem7x7s2_kernel<true> : (p.form.build == 2 ? &stem7x7s2_kernel<false, true> : &stem7x7s2_kernel<false>);
+    rc = spk::raise_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds_bytes);
+    if (rc != SPK_OK) return rc;
+    hipLaunchKernelGGL(kern, p.grid, dim3(256), p.lds_bytes, stream, a);
     return spk::check_launch("stem7x7s2_kernel");
 }
 

@@ -1,7 +1,7 @@
-// C-ABI entry points of the conv family (include/spk.h), config tables / heuristics, the split-K
-// finishing kernel and the weight packer.  The MFMA kernel template lives in conv_mfma_f32.hpp and
-// is instantiated in conv_inst_*.hip.
-#include "conv_mfma_f32.hpp"
+// C-ABI entry points of the conv family (include/spk.h), config tables / heuristics, the routing of a descriptor to its
+// family, the tap kernel's planner and launcher, the split-K finishing kernel and the weight packer.  The MFMA kernel template
+// lives in conv_mfma_f32.hpp and is instantiated in conv_inst_*.hip; the plans are declared in conv_plan.hpp.
+#include "conv_plan.hpp"
 
 namespace spkconv {
 
@@ -150,18 +150,6 @@ int splitk_finisher(const ConvArgs& a, const float* ws, int* seg) {
     return seg_ok && aligned ? 2 : 1;
 }
 
-thread_local spk_conv2d_form* form_probe = nullptr;
-thread_local spk_gemm_form* gemm_form_probe = nullptr;
-
-int report_sliced_form(const ConvArgs& finisher_args, const float* ws, int ksplit) {
-    spk_conv2d_form& f = *form_probe;
-    int seg = 0;
-    f.ksplit = ksplit;
-    f.finisher = ksplit > 1 ? splitk_finisher(finisher_args, ws, &seg) : 0;
-    f.finisher_seg = seg;
-    return SPK_OK;
-}
-
 int launch_splitk_epilogue(const ConvArgs& a_in, const float* ws, int ksplit, hipStream_t stream) {
     ConvArgs a = a_in;
     a.Cout = a_in.Cy;            // the finisher walks the output tensor: every group's channels
@@ -274,13 +262,14 @@ __global__ void pack_rowmajor_kernel(const PackList list, float* __restrict__ wp
     wp[idx] = w[(size_t)co * Cin + ci];
 }
 
+// block shape of a config: the tap kernel's tile, or the fixed blocks of configs 12-16
 struct CfgDims { int co_t, ci_t, pix_t; };
-static const CfgDims kDims[kNumConfigs] = {
-    {Cfg0::CO_T, Cfg0::CI_T, Cfg0::PIX_T},   {Cfg1::CO_T, Cfg1::CI_T, Cfg1::PIX_T},   {Cfg2::CO_T, Cfg2::CI_T, Cfg2::PIX_T},
-    {Cfg3::CO_T, Cfg3::CI_T, Cfg3::PIX_T},   {Cfg4::CO_T, Cfg4::CI_T, Cfg4::PIX_T},   {Cfg5::CO_T, Cfg5::CI_T, Cfg5::PIX_T},
-    {Cfg6::CO_T, Cfg6::CI_T, Cfg6::PIX_T},   {Cfg7::CO_T, Cfg7::CI_T, Cfg7::PIX_T},   {Cfg8::CO_T, Cfg8::CI_T, Cfg8::PIX_T},
-    {Cfg9::CO_T, Cfg9::CI_T, Cfg9::PIX_T},   {Cfg10::CO_T, Cfg10::CI_T, Cfg10::PIX_T}, {Cfg11::CO_T, Cfg11::CI_T, Cfg11::PIX_T},
-    {128, 32, 128}, {64, 8, 128}, {128, 16, 128}, {64, 16, 128}, {64, 3, 512}};
+static CfgDims config_dims(int cfg) {
+    static const CfgDims other[kNumConfigs - kTapConfigs] = {{128, 32, 128}, {64, 8, 128}, {128, 16, 128}, {64, 16, 128}, {64, 3, 512}};
+    if (cfg >= kTapConfigs) return other[cfg - kTapConfigs];
+    const TileDesc t = tile_desc(cfg, 3, 3, 1);
+    return {t.CO_T, t.CI_T, t.PIX_T};
+}
 
 static bool supported_kernel(int kh, int kw, int stride) {
     if (kh == 2 && kw == 2) return stride == 1;   // the parity form of the 3x3 stride-2 data gradient (SPK_CONV_DGRAD_S2)
@@ -297,24 +286,6 @@ static bool config_valid(int cfg, int kh, int kw, int stride) {
     if (kh == 2) return cfg <= 3;
     if (kh == 3 && stride == 1) return cfg <= 7;
     return cfg >= 4 && cfg <= 7;  // 3x3 s2, 4x4 s2, 7x7 s2
-}
-
-template <int KH, int S>
-static Geometry geom_k(int cfg, int B, int Cin, int Cout, int H, int W) {
-    switch (cfg) {
-        case 0: return geometry<Cfg0, KH, KH, S>(B, Cin, Cout, H, W);
-        case 1: return geometry<Cfg1, KH, KH, S>(B, Cin, Cout, H, W);
-        case 2: return geometry<Cfg2, KH, KH, S>(B, Cin, Cout, H, W);
-        case 3: return geometry<Cfg3, KH, KH, S>(B, Cin, Cout, H, W);
-        case 4: return geometry<Cfg4, KH, KH, S>(B, Cin, Cout, H, W);
-        case 5: return geometry<Cfg5, KH, KH, S>(B, Cin, Cout, H, W);
-        case 6: return geometry<Cfg6, KH, KH, S>(B, Cin, Cout, H, W);
-        case 7: return geometry<Cfg7, KH, KH, S>(B, Cin, Cout, H, W);
-        case 8: return geometry<Cfg8, KH, KH, S>(B, Cin, Cout, H, W);
-        case 9: return geometry<Cfg9, KH, KH, S>(B, Cin, Cout, H, W);
-        case 10: return geometry<Cfg10, KH, KH, S>(B, Cin, Cout, H, W);
-        default: return geometry<Cfg11, KH, KH, S>(B, Cin, Cout, H, W);
-    }
 }
 
 static Geometry geometry_any(int kh, int stride, int cfg, int B, int Cin, int Cout, int H, int W) {
@@ -356,11 +327,7 @@ static Geometry geometry_any(int kh, int stride, int cfg, int B, int Cin, int Co
         g.lds_bytes = 0;
         return g;
     }
-    if (kh == 1) return stride == 1 ? geom_k<1, 1>(cfg, B, Cin, Cout, H, W) : geom_k<1, 2>(cfg, B, Cin, Cout, H, W);
-    if (kh == 2) return geom_k<2, 1>(cfg, B, Cin, Cout, H, W);
-    if (kh == 3) return stride == 1 ? geom_k<3, 1>(cfg, B, Cin, Cout, H, W) : geom_k<3, 2>(cfg, B, Cin, Cout, H, W);
-    if (kh == 4) return geom_k<4, 2>(cfg, B, Cin, Cout, H, W);
-    return geom_k<7, 2>(cfg, B, Cin, Cout, H, W);
+    return geometry(tile_desc(cfg, kh, kh, stride), B, Cin, Cout, H, W);      // the tap kernel: what plan_tap plans with
 }
 
 // Heuristic from measurements on MI355X (tools/bench_conv.py, profiles/): the shallow-chunk configs
@@ -425,6 +392,231 @@ static int pick_config(int kh, int stride, int B, int Cin, int Cout, int H, int 
     return want;
 }
 
+// the tap kernel's instantiation, from the unit that builds its family; null: not built
+static const void* tap_kernel(int kh, int stride, int cfg, int mode, bool fg) {
+    if (kh == 1) return tap_kernel_1x1(stride, cfg, mode, fg);
+    if (kh == 2) return tap_kernel_2x2(cfg, mode, fg);
+    if (kh == 3 && stride == 1) {
+        if (mode == MODE_PLAIN_STATS) return tap_kernel_3x3s1_stats(cfg, mode, fg);
+        return cfg <= 3 ? tap_kernel_3x3s1_a(cfg, mode, fg) : tap_kernel_3x3s1_b(cfg, mode, fg);
+    }
+    return tap_kernel_s2(kh, cfg, mode, fg);
+}
+
+// Every requirement and decision of a tap-kernel launch (configs 0-11): argument block, geometry, the split rule, the fixed-geometry
+// rule, the staged-epilogue rule, the workspace check, grid and finisher.
+int plan_tap(const Route& r, TapPlan& p) {
+    const spk_conv2d_desc* d = &r.d;
+    SPK_REQUIRE(!(d->flags & SPK_EPI_ACCUM_HALF), "conv2d: SPK_EPI_ACCUM_HALF is built into the GEMM form of a 1x1 (configs 14, 15)");
+    int mode = r.mode;
+    if (d->kh == 1 && (d->flags & SPK_EPI_RESIDUAL)) mode = MODE_PLAIN_RESIDUAL;
+    if (d->kh == 3 && d->stride == 1 && (d->flags & SPK_EPI_STATS) && mode != MODE_AFFINE_RELU) {
+        SPK_REQUIRE(mode == MODE_PLAIN, "conv2d: SPK_EPI_STATS on a 3x3 stride-1 conv goes with a plain or BatchNorm-folded input (not upsample / batch scale)");
+        mode = MODE_PLAIN_STATS;
+    }
+    p.config = d->config; p.mode = mode;
+    p.kernel = tap_kernel(d->kh, d->stride, d->config, mode, false);
+    if (!p.kernel) {
+        if (d->kh == 7 || d->kh == 4) return spk::fail(SPK_EUNSUPPORTED, "conv2d: 7x7 / 4x4 are built for plain input only");
+        return spk::fail(SPK_EUNSUPPORTED, "conv2d: config %d is not built for %dx%d stride %d in mode %d", d->config, d->kh, d->kw, d->stride, mode);
+    }
+    const TileDesc t = tile_desc(d->config, d->kh, d->kw, d->stride);
+    const Groups q = groups_of(*d);
+    ConvArgs& a = p.args;
+    a.Hd = r.Hd; a.Wd = r.Wd; a.pshift = r.pshift;
+    a.x = d->x; a.wp = d->w_packed; a.bias = d->bias; a.noise_w = d->noise_w; a.noise = d->noise;
+    a.style = d->style; a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.stats = d->stats; a.stats_slots = d->stats_slots > 1 ? d->stats_slots : 1; a.y = d->y; a.y_pre = d->y_pre; a.out_scale_bc = d->out_scale_bc;
+    a.residual = (d->flags & SPK_EPI_RESIDUAL) ? d->residual : nullptr;
+    a.B = d->B; a.Cin = d->Cin; a.Cout = d->Cout; a.H = d->H; a.W = d->W; a.Hs = d->Hin; a.Ws = d->Win;
+    a.G = q.G; a.gin = q.gin; a.Cx = (int)q.Cx; a.Cy = (int)q.Cy;
+    Geometry& g = p.g;
+    g = geometry(t, d->B, d->Cin, d->Cout, d->H, d->W);
+    a.co_tiles_g = g.co_tiles;
+    g.co_tiles *= a.G;                                   // grid.y and the split-K fill heuristic count every group
+    SPK_REQUIRE(g.ok, "conv2d: config %d does not fit this shape (%dx%d, B=%d)", d->config, d->H, d->W, d->B);
+    // the staging tables hold 32-bit BYTE offsets relative to the image group's first plane
+    SPK_REQUIRE((size_t)g.TB * a.Cx * a.Hs * a.Ws < (1ull << 30), "conv2d: image group too large for 32-bit byte offsets");
+    a.lgTW = spk::ilog2(g.TW); a.lgTH = spk::ilog2(g.TH); a.lgTB = spk::ilog2(g.TB);
+    {
+        const unsigned pw = (unsigned)((g.TW - 1) * t.SL + t.KW), plane = (unsigned)g.PLANE;
+        a.magic_plane = plane > 1 ? (unsigned)(((1ull << 32) + plane - 1) / plane) : 0u;   // 0: divisor 1
+        a.magic_pw = pw > 1 ? (unsigned)(((1ull << 32) + pw - 1) / pw) : 0u;
+        SPK_REQUIRE((size_t)t.CI_T * g.TB * g.PLANE < 65536, "conv2d: tile too large for the index arithmetic");
+    }
+    a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
+    a.n_chunks = g.n_chunks;
+    a.style_stride = d->style_stride; a.flags = d->flags; a.slope = d->lrelu_slope; a.out_scale = d->out_scale; a.act_gain = act_gain_of(*d);
+    a.out_scale_dev = d->out_scale_dev;
+    const int ksplit = resolve_ksplit(g, d->ksplit, &a.chunks_per_split);
+    p.ragged = d->Cin % t.CI_T != 0;
+    // the fixed-geometry build of the same kernel, where there is one and the layer's tile is that one (and no chunk is ragged)
+    static const bool fg_on = [] { const char* e = getenv("SPK_CONV_FG"); return !e || atoi(e) != 0; }();
+    p.fixed_geometry = false;
+    if (fg_on && g.TW == 32 && g.TH == t.PIX_T / 32 && g.TB == 1 && !p.ragged && d->Hin >= 2 && d->Win >= 2) {
+        if (const void* fg = tap_kernel(d->kh, d->stride, d->config, mode, true)) {
+            p.kernel = fg;
+            p.fixed_geometry = true;       // planes NSLOT * 64 floats apart (see the kernel)
+            g.lds_bytes = 3 * ((size_t)t.W_FLOATS + (size_t)t.CI_T * t.NSLOT * 64 + 4) * sizeof(float);
+        }
+    }
+    // staged epilogue: whenever its LDS tile costs no workgroup slot and the vectors are whole and aligned
+    a.staged = 0;
+    {
+        static const bool allow = [] { const char* e = getenv("SPK_CONV_STAGED_EPI"); return !e || atoi(e) != 0; }();
+        const size_t tile_bytes = (size_t)t.CO_T * (t.PIX_T + 4) * sizeof(float);
+        const size_t red_bytes = (d->flags & SPK_EPI_STATS) ? 2 * (size_t)t.CO_T * sizeof(float) : 0;   // row sums behind the tile
+        const size_t lds_now = g.lds_bytes;
+        const auto same_slots = [&](size_t bytes) { return (160 * 1024) / std::max(bytes, lds_now) == (160 * 1024) / lds_now; };
+        const bool can_halve = t.MT == 2;
+        const int rounds = same_slots(tile_bytes + red_bytes) ? 1 : ((can_halve && same_slots(tile_bytes / 2 + red_bytes)) ? 2 : 0);
+        if (allow && rounds && t.KH != 2 && ksplit == 1 && g.TW >= 4 && d->W % 4 == 0 && t.NTHREADS % (t.PIX_T / 4) == 0 &&
+            (t.CO_T / rounds) % (t.NTHREADS / (t.PIX_T / 4)) == 0 && aligned16(d->y) && aligned16(d->y_pre) && aligned16(d->noise) && aligned16(a.residual)) {
+            a.staged = rounds;
+            g.lds_bytes = std::max(lds_now, tile_bytes / rounds + red_bytes);
+        }
+    }
+    const size_t out_floats = (size_t)d->B * a.Cy * d->H * d->W;
+    if (ksplit > 1) {
+        SPK_REQUIRE(d->workspace && (size_t)d->workspace_bytes >= ksplit * out_floats * sizeof(float),
+                    "conv2d: split-K x%d needs a %zu-byte workspace (see spk_conv2d_workspace_bytes)", ksplit,
+                    ksplit * out_floats * sizeof(float));
+        a.y = static_cast<float*>(d->workspace);
+    }
+    const long long gx = (long long)g.tiles_x * g.tiles_y * g.tiles_b;
+    SPK_REQUIRE(gx < (1ll << 31), "conv2d: grid too large");
+    p.grid = dim3((unsigned)gx, (unsigned)g.co_tiles, (unsigned)ksplit);
+    p.nthreads = t.NTHREADS;
+    p.finish.args = finisher_args(*d, q, d->flags, d->out_scale);
+    p.finish.ws = static_cast<const float*>(d->workspace);
+    p.finish.ksplit = ksplit;
+    return SPK_OK;
+}
+
+int launch_tap(const TapPlan& p, hipStream_t stream) {
+    int rc = spk::raise_dynamic_lds(p.kernel, p.g.lds_bytes);
+    if (rc != SPK_OK) return rc;
+    void* argv[1] = {const_cast<ConvArgs*>(&p.args)};
+    (void)hipLaunchKernel(p.kernel, p.grid, dim3(p.nthreads), argv, p.g.lds_bytes, stream);
+    rc = spk::check_launch("conv_kernel");
+    return rc != SPK_OK ? rc : launch_finish(p.finish, stream);
+}
+
+// spk_conv2d_form of a sliced launch: the split and the finisher that runs behind it
+static void sliced_form(const Finish& f, spk_conv2d_form& out) {
+    int seg = 0;
+    out.ksplit = f.ksplit;
+    out.finisher = f.ksplit > 1 ? splitk_finisher(f.args, f.ws, &seg) : 0;
+    out.finisher_seg = seg;
+}
+
+static void tap_form(const TapPlan& p, spk_conv2d_form& f) {
+    const Geometry& g = p.g;
+    f.config = p.config; f.mode = p.mode; f.TW = g.TW; f.TH = g.TH; f.TB = g.TB;
+    f.n_chunks = g.n_chunks; f.chunks_per_split = p.args.chunks_per_split;
+    f.last_split_chunks = g.n_chunks - (p.finish.ksplit - 1) * p.args.chunks_per_split;
+    f.ragged_last_chunk = p.ragged; f.fixed_geometry = p.fixed_geometry; f.one_slot_ring = g.one_slot; f.staged = p.args.staged;
+    f.grid_x = (int)p.grid.x; f.grid_y = (int)p.grid.y; f.grid_z = (int)p.grid.z;
+    f.lds_bytes = (int64_t)g.lds_bytes;
+    sliced_form(p.finish, f);
+}
+
+// The checks and the routing of spk_conv2d_fwd, for the launch and for both form queries: which family runs the descriptor, and the
+// descriptor that family plans.
+static int route(const spk_conv2d_desc* d, Route& r) {
+    SPK_REQUIRE(d, "conv2d: null descriptor");
+    r.d = *d;
+    r.mode = MODE_PLAIN; r.Hd = r.Wd = r.pshift = 0;
+    r.family = FAM_TAP;
+    if (d->flags & SPK_CONV_BF16X3) { r.family = FAM_BF16X3; return SPK_OK; }
+    if (d->flags & SPK_CONV_WINOGRAD) { r.family = FAM_WINO; return SPK_OK; }
+    SPK_REQUIRE(!(d->flags & SPK_EPI_TORGB), "conv2d: SPK_EPI_TORGB is an epilogue of the SPK_CONV_WINOGRAD launches only");
+    SPK_REQUIRE(d->x && d->w_packed && d->y, "conv2d: null tensor pointer");
+    SPK_REQUIRE(d->B > 0 && d->Cin > 0 && d->Cout > 0 && d->H > 0 && d->W > 0 && d->Hin > 0 && d->Win > 0, "conv2d: bad shape");
+    spk_conv2d_desc& dd = r.d;
+    if (d->flags & SPK_CONV_TRANSPOSE4X4_S2) {
+        // forward of nn.ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1): x [B,Cin,Hin,Win] -> y [B,Cout,2Hin,2Win]; the four
+        // output-parity classes are 2x2 kernels over the (Hin+1) x (Win+1) window anchors, stored interleaved
+        SPK_REQUIRE(d->kh == 4 && d->kw == 4 && d->stride == 2, "conv2d: TRANSPOSE4X4_S2 is a 4x4 stride-2 transposed conv");
+        SPK_REQUIRE(!(d->flags & ~(SPK_CONV_TRANSPOSE4X4_S2 | SPK_EPI_BIAS | SPK_EPI_ACCUM)) && !d->out_scale_bc && !d->y_pre,
+                    "conv2d: TRANSPOSE4X4_S2 takes SPK_EPI_BIAS / SPK_EPI_ACCUM only");
+        SPK_REQUIRE(!(d->flags & SPK_EPI_BIAS) || d->bias, "conv2d: SPK_EPI_BIAS without bias");
+        SPK_REQUIRE(d->H == 2 * d->Hin && d->W == 2 * d->Win, "conv2d: TRANSPOSE4X4_S2 output must be 2x the input (%dx%d vs %dx%d)",
+                    d->H, d->W, d->Hin, d->Win);
+        SPK_REQUIRE(d->groups <= 1, "conv2d: TRANSPOSE4X4_S2 is not grouped");
+        SPK_REQUIRE((long long)d->B * d->Cout * d->H * d->W < (1ll << 40), "conv2d: tensor too large");
+        dd.kh = dd.kw = 2; dd.stride = 1; dd.Cout = 4 * d->Cout; dd.H = d->Hin + 1; dd.W = d->Win + 1; dd.ksplit = 1;
+        dd.flags = d->flags & (SPK_EPI_BIAS | SPK_EPI_ACCUM);
+        if (dd.config < 0) dd.config = pick_config(2, 1, dd.B, dd.Cin, dd.Cout, dd.H, dd.W);
+        SPK_REQUIRE(config_valid(dd.config, 2, 2, 1), "conv2d: TRANSPOSE4X4_S2 runs tile configs 0-3 (got %d)", dd.config);
+        r.Hd = d->H; r.Wd = d->W; r.pshift = 1;
+        return SPK_OK;
+    }
+    SPK_REQUIRE(supported_kernel(d->kh, d->kw, d->stride) && d->kh != 2, "conv2d: unsupported kernel %dx%d stride %d", d->kh, d->kw, d->stride);
+    if (d->flags & SPK_CONV_DGRAD_S2) {
+        // data gradient of a 3x3 stride-2 pad-1 conv: x = the output-side gradient [B, Cin, Hin, Win], y = the input-side
+        // gradient [B, Cout, H, W]; run as the four output-parity classes (2x2 kernels, 4*Cout channels, interleaved stores)
+        SPK_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 2, "conv2d: DGRAD_S2 is the data gradient of a 3x3 stride-2 conv");
+        SPK_REQUIRE(!(d->flags & ~(SPK_CONV_DGRAD_S2 | SPK_EPI_ACCUM)) && !d->out_scale_bc && !d->y_pre,
+                    "conv2d: DGRAD_S2 takes SPK_EPI_ACCUM only");
+        SPK_REQUIRE((d->H == 2 * d->Hin || d->H == 2 * d->Hin - 1) && (d->W == 2 * d->Win || d->W == 2 * d->Win - 1),
+                    "conv2d: DGRAD_S2 output %dx%d is not the input size of a stride-2 conv with output %dx%d", d->H, d->W, d->Hin, d->Win);
+        SPK_REQUIRE(d->groups <= 1 || d->group_in_stride >= d->Cin, "conv2d: DGRAD_S2 groups read disjoint channels");
+        SPK_REQUIRE((long long)d->B * d->Cout * d->H * d->W < (1ll << 40), "conv2d: tensor too large");
+        int cfg = d->config;
+        if (cfg < 0) cfg = spk_conv2d_dgrad_s2_config(d->B, d->Cin, d->Cout, d->Hin, d->Win);
+        SPK_REQUIRE(config_valid(cfg, 2, 2, 1), "conv2d: DGRAD_S2 runs tile configs 0-3 and %d (got %d)", kDgradS2Config, cfg);
+        if (cfg == kDgradS2Config) { r.family = FAM_DGRAD_S2; return SPK_OK; }      // (plans the descriptor as it came)
+        dd.kh = dd.kw = 2; dd.stride = 1; dd.Cout = 4 * d->Cout; dd.H = d->Hin; dd.W = d->Win; dd.ksplit = 1;
+        dd.flags = d->flags & SPK_EPI_ACCUM; dd.config = cfg;
+        r.Hd = d->H; r.Wd = d->W;
+        return SPK_OK;
+    }
+    const bool ups = d->flags & SPK_CONV_UPSAMPLE2X, aff = d->flags & SPK_CONV_IN_AFFINE_RELU;
+    const bool bsc = d->flags & SPK_CONV_IN_BATCH_SCALE;
+    SPK_REQUIRE(!aff || (!ups && !bsc), "conv2d: IN_AFFINE_RELU excludes UPSAMPLE2X and IN_BATCH_SCALE");
+    SPK_REQUIRE(!(d->flags & SPK_CONV_UP_FIR1331) || ups, "conv2d: UP_FIR1331 qualifies UPSAMPLE2X");
+    SPK_REQUIRE(!bsc || (d->in_scale && d->kh == 3 && d->stride == 1), "conv2d: IN_BATCH_SCALE needs in_scale[B,Cin] and a 3x3 stride-1 kernel");
+    SPK_REQUIRE(!ups || (d->kh == 3 && d->stride == 1), "conv2d: UPSAMPLE2X needs a 3x3 stride-1 kernel");
+    const int pad = (d->kh - 1) / 2;
+    if (ups) SPK_REQUIRE(d->H == 2 * d->Hin && d->W == 2 * d->Win, "conv2d: upsampled output must be 2x the input (%dx%d vs %dx%d)", d->H, d->W, d->Hin, d->Win);
+    else SPK_REQUIRE(d->H == (d->Hin + 2 * pad - d->kh) / d->stride + 1 && d->W == (d->Win + 2 * pad - d->kw) / d->stride + 1,
+                     "conv2d: output size %dx%d does not match input %dx%d (k=%d s=%d)", d->H, d->W, d->Hin, d->Win, d->kh, d->stride);
+    SPK_REQUIRE(!(d->flags & SPK_EPI_BIAS) || d->bias, "conv2d: SPK_EPI_BIAS without bias");
+    SPK_REQUIRE(!(d->flags & SPK_EPI_NOISE) || (d->noise && d->noise_w), "conv2d: SPK_EPI_NOISE without noise");
+    SPK_REQUIRE(!(d->flags & SPK_EPI_STYLE) || d->style, "conv2d: SPK_EPI_STYLE without style");
+    SPK_REQUIRE(!(d->flags & SPK_EPI_STATS) || d->stats, "conv2d: SPK_EPI_STATS without stats");
+    SPK_REQUIRE(d->stats_slots >= 0 && d->stats_slots <= 65536, "conv2d: stats_slots must be in [0, 65536] (got %d)", d->stats_slots);
+    SPK_REQUIRE(!aff || (d->in_scale && d->in_shift), "conv2d: IN_AFFINE_RELU without in_scale/in_shift");
+    if (d->flags & SPK_EPI_RESIDUAL) {
+        SPK_REQUIRE(d->kh == 1 && d->kw == 1 && d->stride == 1, "conv2d: SPK_EPI_RESIDUAL is an epilogue of the stride-1 1x1 convs only (got %dx%d stride %d)",
+                    d->kh, d->kw, d->stride);
+        SPK_REQUIRE(d->residual && (reinterpret_cast<uintptr_t>(d->residual) & 3) == 0, "conv2d: SPK_EPI_RESIDUAL without residual");
+        SPK_REQUIRE(!(d->flags & (SPK_EPI_STATS | SPK_EPI_NOISE | SPK_EPI_STYLE | SPK_EPI_ACCUM_HALF | SPK_CONV_IN_AFFINE_RELU)) && !d->y_pre,
+                    "conv2d: SPK_EPI_RESIDUAL goes with SPK_EPI_BIAS / LRELU / ACCUM on a plain input only (not STATS / NOISE / STYLE / "
+                    "ACCUM_HALF / IN_AFFINE_RELU / y_pre)");
+    }
+    SPK_REQUIRE((long long)d->B * d->Cout * d->H * d->W < (1ll << 40), "conv2d: tensor too large");
+    if (d->groups > 1) {
+        SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_ACCUM_HALF | SPK_EPI_RESIDUAL)) && !d->out_scale_bc,
+                    "conv2d: a grouped launch takes bias / lrelu / accum / accum-half / stats / in-affine / residual only");
+        SPK_REQUIRE(d->group_in_stride == 0 || d->group_in_stride >= d->Cin, "conv2d: group_in_stride must be 0 (shared input) or >= Cin");
+    }
+    int cfg = d->config;
+    if (cfg < 0) cfg = pick_config(d->kh, d->stride, d->B, d->Cin, d->Cout, d->H, d->W);
+    SPK_REQUIRE(!bsc || cfg >= 4, "conv2d: IN_BATCH_SCALE is built for the half-depth configs (4-7)");
+    SPK_REQUIRE(!d->out_scale_bc || bsc, "conv2d: out_scale_bc (demodulation) goes with SPK_CONV_IN_BATCH_SCALE (the modulated convolution)");
+    SPK_REQUIRE(config_valid(cfg, d->kh, d->kw, d->stride), "conv2d: config %d is not built for %dx%d stride %d", cfg, d->kh, d->kw, d->stride);
+    dd.config = cfg;
+    r.mode = ups ? (bsc ? MODE_UPSAMPLE_BATCH_SCALE : MODE_UPSAMPLE) : (aff ? MODE_AFFINE_RELU : (bsc ? MODE_BATCH_SCALE : MODE_PLAIN));
+    SPK_REQUIRE(!d->out_scale_dev || !(cfg == kGemmConfig || is_gemm2(cfg)), "conv2d: out_scale_dev is built into the tap kernels (not the GEMM forms of a 1x1)");
+    r.family = cfg == kGemmConfig ? FAM_GEMM : (is_gemm2(cfg) ? FAM_GEMM2 : (cfg == kStemConfig ? FAM_STEM : FAM_TAP));
+    return SPK_OK;
+}
+
+static int plan_gemm_family(const Route& r, GemmPlan& p) {
+    return r.family == FAM_GEMM ? plan_1x1_gemm(&r.d, p) : (r.family == FAM_GEMM2 ? plan_1x1_gemm2(&r.d, p) : plan_stem(&r.d, p));
+}
+
 }  // namespace spkconv
 
 using namespace spkconv;
@@ -453,9 +645,10 @@ int spk_conv2d_dgrad_s2_config(int B, int Cin, int Cout, int Hin, int Win) {
 
 int spk_conv2d_config_info(int config, int* co_tile, int* ci_tile, int* pix_tile) {
     SPK_REQUIRE(config >= 0 && config < kNumConfigs, "conv2d: bad config %d", config);
-    if (co_tile) *co_tile = kDims[config].co_t;
-    if (ci_tile) *ci_tile = kDims[config].ci_t;
-    if (pix_tile) *pix_tile = kDims[config].pix_t;
+    const CfgDims c = config_dims(config);
+    if (co_tile) *co_tile = c.co_t;
+    if (ci_tile) *ci_tile = c.ci_t;
+    if (pix_tile) *pix_tile = c.pix_t;
     return SPK_OK;
 }
 
@@ -465,7 +658,7 @@ int64_t spk_conv2d_packed_floats(int config, int kh, int kw, int Cin, int Cout) 
     if (is_gemm2(config)) return kh == 1 && kw == 1 ? (int64_t)gemm2_packed_floats(config, Cin, Cout) : -1;
     if (config == kStemConfig) return kh == 7 && kw == 7 && Cin == 3 && Cout == 64 ? (int64_t)stem_packed_floats() : -1;
     if (config == kDgradS2Config) return (kh == 2 && kw == 2 && Cout % 4 == 0) ? (int64_t)dgrad_s2_fused_packed_floats(Cin, Cout / 4) : -1;
-    const CfgDims& c = kDims[config];
+    const CfgDims c = config_dims(config);
     return (int64_t)spk::ceil_div(Cout, c.co_t) * spk::ceil_div(Cin, c.ci_t) * kh * kw * c.ci_t * c.co_t;
 }
 
@@ -533,11 +726,11 @@ int spk_conv2d_pack_weights_list(const float* const* ws, int n, float* w_packed,
         SPK_REQUIRE(kh == 7 && kw == 7, "pack_weights: config %d packs 7x7 kernels", config);
         return pack_stem(list, n, w_packed, Cin, Cout, transpose_flip, (hipStream_t)stream);
     }
-    if (config == kDgradS2Config) {     // the transposed 3x3 operator itself, in 64-channel x 8-channel tiles (kDims[13])
+    if (config == kDgradS2Config) {     // the transposed 3x3 operator itself, in 64-channel x 8-channel tiles (config_dims(13))
         SPK_REQUIRE(transpose_flip == 2, "pack_weights: config %d packs the stride-2 data-gradient form (transpose_flip = 2)", kDgradS2Config);
         transpose_flip = 1;
     }
-    const CfgDims& c = kDims[config];
+    const CfgDims c = config_dims(config);
     const int opCin = (transpose_flip == 1 || transpose_flip == 2) ? Cout : Cin;
     const int opCout = transpose_flip == 2 ? 4 * Cin : (transpose_flip == 3 ? 4 * Cout : (transpose_flip ? Cin : Cout));
     const int taps = transpose_flip >= 2 ? 4 : kh * kw;
@@ -563,9 +756,21 @@ int spk_conv2d_launch_form(const spk_conv2d_desc* d, spk_conv2d_form* out) {
     SPK_REQUIRE(!(d->flags & SPK_CONV_BF16X3), "conv2d launch form: SPK_CONV_BF16X3 launches are not served");
     *out = spk_conv2d_form{};
     out->config = -1;
-    form_probe = out;            // the launch path answers where it would launch (run(), spk_conv2d_wino_fwd, run_dgrad_s2_fused)
-    const int rc = spk_conv2d_fwd(d, nullptr);
-    form_probe = nullptr;
+    Route r;
+    int rc = route(d, r);
+    if (rc != SPK_OK) return rc;
+    if (r.family == FAM_WINO || r.family == FAM_DGRAD_S2) {      // the sliced families: the split and the finisher alone
+        SlicedPlan p;
+        rc = r.family == FAM_WINO ? plan_wino(&r.d, p) : plan_dgrad_s2_fused(&r.d, p);
+        if (rc != SPK_OK) return rc;
+        out->config = p.config;
+        sliced_form(p.finish, *out);
+        return SPK_OK;
+    }
+    SPK_REQUIRE(r.family == FAM_TAP, "conv2d launch form: config %d is not a tap-kernel config", r.d.config);
+    TapPlan p;
+    rc = plan_tap(r, p);
+    if (rc == SPK_OK) tap_form(p, *out);
     return rc;
 }
 
@@ -576,114 +781,33 @@ int spk_conv2d_gemm_form(const spk_conv2d_desc* d, spk_gemm_form* out) {
                 kGemm2Config, kGemm2NarrowConfig, kStemConfig);
     *out = spk_gemm_form{};
     out->config = -1;
-    gemm_form_probe = out;       // run_1x1_gemm / run_1x1_gemm2 / run_stem answer where they would launch
-    const int rc = spk_conv2d_fwd(d, nullptr);
-    gemm_form_probe = nullptr;
+    Route r;
+    int rc = route(d, r);
+    if (rc != SPK_OK) return rc;
+    SPK_REQUIRE(r.family == FAM_GEMM || r.family == FAM_GEMM2 || r.family == FAM_STEM, "conv2d gemm form: config %d is not a GEMM-form or stem config", r.d.config);
+    GemmPlan p;
+    rc = plan_gemm_family(r, p);
+    if (rc == SPK_OK) *out = p.form;
     return rc;
 }
 
 int spk_conv2d_fwd(const spk_conv2d_desc* d, void* stream) {
-    SPK_REQUIRE(d, "conv2d: null descriptor");
-    if (d->flags & SPK_CONV_BF16X3) return spk_conv2d_bf16x3_fwd(d, stream);
-    if (d->flags & SPK_CONV_WINOGRAD) return spk_conv2d_wino_fwd(d, stream);
-    SPK_REQUIRE(!(d->flags & SPK_EPI_TORGB), "conv2d: SPK_EPI_TORGB is an epilogue of the SPK_CONV_WINOGRAD launches only");
-    SPK_REQUIRE(d->x && d->w_packed && d->y, "conv2d: null tensor pointer");
-    SPK_REQUIRE(d->B > 0 && d->Cin > 0 && d->Cout > 0 && d->H > 0 && d->W > 0 && d->Hin > 0 && d->Win > 0, "conv2d: bad shape");
-    if (d->flags & SPK_CONV_TRANSPOSE4X4_S2) {
-        // forward of nn.ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1): x [B,Cin,Hin,Win] -> y [B,Cout,2Hin,2Win]; the four
-        // output-parity classes are 2x2 kernels over the (Hin+1) x (Win+1) window anchors, stored interleaved
-        SPK_REQUIRE(d->kh == 4 && d->kw == 4 && d->stride == 2, "conv2d: TRANSPOSE4X4_S2 is a 4x4 stride-2 transposed conv");
-        SPK_REQUIRE(!(d->flags & ~(SPK_CONV_TRANSPOSE4X4_S2 | SPK_EPI_BIAS | SPK_EPI_ACCUM)) && !d->out_scale_bc && !d->y_pre,
-                    "conv2d: TRANSPOSE4X4_S2 takes SPK_EPI_BIAS / SPK_EPI_ACCUM only");
-        SPK_REQUIRE(!(d->flags & SPK_EPI_BIAS) || d->bias, "conv2d: SPK_EPI_BIAS without bias");
-        SPK_REQUIRE(d->H == 2 * d->Hin && d->W == 2 * d->Win, "conv2d: TRANSPOSE4X4_S2 output must be 2x the input (%dx%d vs %dx%d)",
-                    d->H, d->W, d->Hin, d->Win);
-        SPK_REQUIRE(d->groups <= 1, "conv2d: TRANSPOSE4X4_S2 is not grouped");
-        SPK_REQUIRE((long long)d->B * d->Cout * d->H * d->W < (1ll << 40), "conv2d: tensor too large");
-        spk_conv2d_desc dd = *d;
-        dd.kh = dd.kw = 2; dd.stride = 1; dd.Cout = 4 * d->Cout; dd.H = d->Hin + 1; dd.W = d->Win + 1; dd.ksplit = 1;
-        dd.flags = d->flags & (SPK_EPI_BIAS | SPK_EPI_ACCUM);
-        if (dd.config < 0) dd.config = pick_config(2, 1, dd.B, dd.Cin, dd.Cout, dd.H, dd.W);
-        SPK_REQUIRE(config_valid(dd.config, 2, 2, 1), "conv2d: TRANSPOSE4X4_S2 runs tile configs 0-3 (got %d)", dd.config);
-        return run_2x2_parity(dd.config, &dd, d->H, d->W, 1, (hipStream_t)stream);
-    }
-    SPK_REQUIRE(supported_kernel(d->kh, d->kw, d->stride) && d->kh != 2, "conv2d: unsupported kernel %dx%d stride %d", d->kh, d->kw, d->stride);
-    if (d->flags & SPK_CONV_DGRAD_S2) {
-        // data gradient of a 3x3 stride-2 pad-1 conv: x = the output-side gradient [B, Cin, Hin, Win], y = the input-side
-        // gradient [B, Cout, H, W]; run as the four output-parity classes (2x2 kernels, 4*Cout channels, interleaved stores)
-        SPK_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 2, "conv2d: DGRAD_S2 is the data gradient of a 3x3 stride-2 conv");
-        SPK_REQUIRE(!(d->flags & ~(SPK_CONV_DGRAD_S2 | SPK_EPI_ACCUM)) && !d->out_scale_bc && !d->y_pre,
-                    "conv2d: DGRAD_S2 takes SPK_EPI_ACCUM only");
-        SPK_REQUIRE((d->H == 2 * d->Hin || d->H == 2 * d->Hin - 1) && (d->W == 2 * d->Win || d->W == 2 * d->Win - 1),
-                    "conv2d: DGRAD_S2 output %dx%d is not the input size of a stride-2 conv with output %dx%d", d->H, d->W, d->Hin, d->Win);
-        SPK_REQUIRE(d->groups <= 1 || d->group_in_stride >= d->Cin, "conv2d: DGRAD_S2 groups read disjoint channels");
-        SPK_REQUIRE((long long)d->B * d->Cout * d->H * d->W < (1ll << 40), "conv2d: tensor too large");
-        spk_conv2d_desc dd = *d;
-        dd.kh = dd.kw = 2; dd.stride = 1; dd.Cout = 4 * d->Cout; dd.H = d->Hin; dd.W = d->Win; dd.ksplit = 1;
-        dd.flags = d->flags & SPK_EPI_ACCUM; dd.out_scale = d->out_scale;
-        if (dd.config < 0) dd.config = spk_conv2d_dgrad_s2_config(d->B, d->Cin, d->Cout, d->Hin, d->Win);
-        SPK_REQUIRE(config_valid(dd.config, 2, 2, 1), "conv2d: DGRAD_S2 runs tile configs 0-3 and %d (got %d)", kDgradS2Config, dd.config);
-        if (dd.config == kDgradS2Config) return run_dgrad_s2_fused(d, (hipStream_t)stream);
-        return run_2x2_parity(dd.config, &dd, d->H, d->W, 0, (hipStream_t)stream);
-    }
-    const bool ups = d->flags & SPK_CONV_UPSAMPLE2X, aff = d->flags & SPK_CONV_IN_AFFINE_RELU;
-    const bool bsc = d->flags & SPK_CONV_IN_BATCH_SCALE;
-    SPK_REQUIRE(!aff || (!ups && !bsc), "conv2d: IN_AFFINE_RELU excludes UPSAMPLE2X and IN_BATCH_SCALE");
-    SPK_REQUIRE(!(d->flags & SPK_CONV_UP_FIR1331) || ups, "conv2d: UP_FIR1331 qualifies UPSAMPLE2X");
-    SPK_REQUIRE(!bsc || (d->in_scale && d->kh == 3 && d->stride == 1), "conv2d: IN_BATCH_SCALE needs in_scale[B,Cin] and a 3x3 stride-1 kernel");
-    SPK_REQUIRE(!ups || (d->kh == 3 && d->stride == 1), "conv2d: UPSAMPLE2X needs a 3x3 stride-1 kernel");
-    const int pad = (d->kh - 1) / 2;
-    if (ups) SPK_REQUIRE(d->H == 2 * d->Hin && d->W == 2 * d->Win, "conv2d: upsampled output must be 2x the input (%dx%d vs %dx%d)", d->H, d->W, d->Hin, d->Win);
-    else SPK_REQUIRE(d->H == (d->Hin + 2 * pad - d->kh) / d->stride + 1 && d->W == (d->Win + 2 * pad - d->kw) / d->stride + 1,
-                     "conv2d: output size %dx%d does not match input %dx%d (k=%d s=%d)", d->H, d->W, d->Hin, d->Win, d->kh, d->stride);
-    SPK_REQUIRE(!(d->flags & SPK_EPI_BIAS) || d->bias, "conv2d: SPK_EPI_BIAS without bias");
-    SPK_REQUIRE(!(d->flags & SPK_EPI_NOISE) || (d->noise && d->noise_w), "conv2d: SPK_EPI_NOISE without noise");
-    SPK_REQUIRE(!(d->flags & SPK_EPI_STYLE) || d->style, "conv2d: SPK_EPI_STYLE without style");
-    SPK_REQUIRE(!(d->flags & SPK_EPI_STATS) || d->stats, "conv2d: SPK_EPI_STATS without stats");
-    SPK_REQUIRE(d->stats_slots >= 0 && d->stats_slots <= 65536, "conv2d: stats_slots must be in [0, 65536] (got %d)", d->stats_slots);
-    SPK_REQUIRE(!aff || (d->in_scale && d->in_shift), "conv2d: IN_AFFINE_RELU without in_scale/in_shift");
-    if (d->flags & SPK_EPI_RESIDUAL) {
-        SPK_REQUIRE(d->kh == 1 && d->kw == 1 && d->stride == 1, "conv2d: SPK_EPI_RESIDUAL is an epilogue of the stride-1 1x1 convs only (got %dx%d stride %d)",
-                    d->kh, d->kw, d->stride);
-        SPK_REQUIRE(d->residual && (reinterpret_cast<uintptr_t>(d->residual) & 3) == 0, "conv2d: SPK_EPI_RESIDUAL without residual");
-        SPK_REQUIRE(!(d->flags & (SPK_EPI_STATS | SPK_EPI_NOISE | SPK_EPI_STYLE | SPK_EPI_ACCUM_HALF | SPK_CONV_IN_AFFINE_RELU)) && !d->y_pre,
-                    "conv2d: SPK_EPI_RESIDUAL goes with SPK_EPI_BIAS / LRELU / ACCUM on a plain input only (not STATS / NOISE / STYLE / "
-                    "ACCUM_HALF / IN_AFFINE_RELU / y_pre)");
-    }
-    SPK_REQUIRE((long long)d->B * d->Cout * d->H * d->W < (1ll << 40), "conv2d: tensor too large");
-    if (d->groups > 1) {
-        SPK_REQUIRE(!(d->flags & ~(SPK_EPI_BIAS | SPK_EPI_LRELU | SPK_EPI_ACCUM | SPK_EPI_STATS | SPK_CONV_IN_AFFINE_RELU | SPK_EPI_ACCUM_HALF | SPK_EPI_RESIDUAL)) && !d->out_scale_bc,
-                    "conv2d: a grouped launch takes bias / lrelu / accum / accum-half / stats / in-affine / residual only");
-        SPK_REQUIRE(d->group_in_stride == 0 || d->group_in_stride >= d->Cin, "conv2d: group_in_stride must be 0 (shared input) or >= Cin");
-    }
-    int cfg = d->config;
-    if (cfg < 0) cfg = pick_config(d->kh, d->stride, d->B, d->Cin, d->Cout, d->H, d->W);
-    SPK_REQUIRE(!bsc || cfg >= 4, "conv2d: IN_BATCH_SCALE is built for the half-depth configs (4-7)");
-    SPK_REQUIRE(!d->out_scale_bc || bsc, "conv2d: out_scale_bc (demodulation) goes with SPK_CONV_IN_BATCH_SCALE (the modulated convolution)");
-    SPK_REQUIRE(config_valid(cfg, d->kh, d->kw, d->stride), "conv2d: config %d is not built for %dx%d stride %d", cfg, d->kh, d->kw, d->stride);
-    spk_conv2d_desc dd = *d;
-    dd.config = cfg;
-    const int mode = ups ? (bsc ? MODE_UPSAMPLE_BATCH_SCALE : MODE_UPSAMPLE) : (aff ? MODE_AFFINE_RELU : (bsc ? MODE_BATCH_SCALE : MODE_PLAIN));
+    Route r;
+    int rc = route(d, r);
+    if (rc != SPK_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    SPK_REQUIRE(!d->out_scale_dev || !(cfg == kGemmConfig || is_gemm2(cfg)), "conv2d: out_scale_dev is built into the tap kernels (not the GEMM forms of a 1x1)");
-    SPK_REQUIRE(!form_probe || !(cfg == kGemmConfig || is_gemm2(cfg) || cfg == kStemConfig), "conv2d launch form: config %d is not a tap-kernel config", cfg);
-    SPK_REQUIRE(!gemm_form_probe || cfg == kGemmConfig || is_gemm2(cfg) || cfg == kStemConfig, "conv2d gemm form: config %d is not a GEMM-form or stem config", cfg);
-    if (cfg == kGemmConfig) return run_1x1_gemm(&dd, s);
-    if (is_gemm2(cfg)) return run_1x1_gemm2(&dd, s);
-    if (cfg == kStemConfig) {
-        SPK_REQUIRE(mode == MODE_PLAIN && !(d->flags & SPK_EPI_ACCUM_HALF), "conv2d: the stem form reads a plain input");
-        return run_stem(&dd, s);
+    switch (r.family) {
+        case FAM_BF16X3: return spk_conv2d_bf16x3_fwd(d, stream);
+        case FAM_WINO: return spk_conv2d_wino_fwd(d, stream);
+        case FAM_DGRAD_S2: return fwd_dgrad_s2_fused(&r.d, s);
+        case FAM_GEMM: return fwd_1x1_gemm(&r.d, s);
+        case FAM_GEMM2: return fwd_1x1_gemm2(&r.d, s);
+        case FAM_STEM: return fwd_stem(&r.d, s);
+        default: break;
     }
-    SPK_REQUIRE(!(d->flags & SPK_EPI_ACCUM_HALF), "conv2d: SPK_EPI_ACCUM_HALF is built into the GEMM form of a 1x1 (configs 14, 15)");
-    if (d->kh == 1) return run_1x1(d->stride, cfg, (d->flags & SPK_EPI_RESIDUAL) ? MODE_PLAIN_RESIDUAL : mode, &dd, s);
-    if (d->kh == 3 && d->stride == 1) {
-        if ((d->flags & SPK_EPI_STATS) && mode != MODE_AFFINE_RELU) {
-            SPK_REQUIRE(mode == MODE_PLAIN, "conv2d: SPK_EPI_STATS on a 3x3 stride-1 conv goes with a plain or BatchNorm-folded input (not upsample / batch scale)");
-            return run_3x3s1_stats(cfg, &dd, s);
-        }
-        return cfg <= 3 ? run_3x3s1_a(cfg, mode, &dd, s) : run_3x3s1_b(cfg, mode, &dd, s);
-    }
-    return run_3x3s2_7x7s2(d->kh, cfg, mode, &dd, s);
+    TapPlan p;
+    rc = plan_tap(r, p);
+    return rc != SPK_OK ? rc : launch_tap(p, s);
 }
 
 }  // extern "C"

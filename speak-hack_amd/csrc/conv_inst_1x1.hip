@@ -1,28 +1,31 @@
 // 1x1 instantiations (stride 1 and 2): deep chunks (CI_T = 32 / 16) since a chunk has only CI_T/2 k-steps.
-#include "conv_mfma_f32.hpp"
+#include "conv_plan.hpp"
 
 namespace spkconv {
 
-template <class C, int S>
-static int by_mode(int mode, const spk_conv2d_desc* d, hipStream_t s) {
+template <int ID, class C, int S>
+static const void* by_mode(int mode) {
     if constexpr (S == 1) {
-        if (mode == MODE_PLAIN_RESIDUAL) return run<C, 1, 1, 1, MODE_PLAIN_RESIDUAL>(d, s);
+        if (mode == MODE_PLAIN_RESIDUAL) return tap_kernel_ptr<ID, C, 1, 1, 1, MODE_PLAIN_RESIDUAL>();
     }
-    return mode == MODE_AFFINE_RELU ? run<C, 1, 1, S, MODE_AFFINE_RELU>(d, s) : run<C, 1, 1, S, MODE_PLAIN>(d, s);
+    if (mode == MODE_AFFINE_RELU) return tap_kernel_ptr<ID, C, 1, 1, S, MODE_AFFINE_RELU>();
+    return mode == MODE_PLAIN ? tap_kernel_ptr<ID, C, 1, 1, S, MODE_PLAIN>() : nullptr;
 }
 
 template <int S>
-static int by_cfg(int cfg, int mode, const spk_conv2d_desc* d, hipStream_t s) {
+static const void* by_cfg(int cfg, int mode) {
     switch (cfg) {
-        case 8: return by_mode<Cfg8, S>(mode, d, s);
-        case 9: return by_mode<Cfg9, S>(mode, d, s);
-        case 10: return by_mode<Cfg10, S>(mode, d, s);
-        default: return by_mode<Cfg11, S>(mode, d, s);
+        case 8: return by_mode<SPK_TAP_CFG(8), S>(mode);
+        case 9: return by_mode<SPK_TAP_CFG(9), S>(mode);
+        case 10: return by_mode<SPK_TAP_CFG(10), S>(mode);
+        case 11: return by_mode<SPK_TAP_CFG(11), S>(mode);
+        default: return nullptr;
     }
 }
 
-int run_1x1(int stride, int cfg, int mode, const spk_conv2d_desc* d, hipStream_t s) {
-    return stride == 2 ? by_cfg<2>(cfg, mode, d, s) : by_cfg<1>(cfg, mode, d, s);
+const void* tap_kernel_1x1(int stride, int cfg, int mode, bool fg) {
+    if (fg) return nullptr;
+    return stride == 2 ? by_cfg<2>(cfg, mode) : by_cfg<1>(cfg, mode);
 }
 
 }  // namespace spkconv

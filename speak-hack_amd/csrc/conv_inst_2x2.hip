@@ -5,16 +5,18 @@
 // 9 at four times the pixels.  The same four-class launch, anchored one pixel up / left (pshift = 1), is the forward of
 // nn.ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1), the fused upscale of the legacy GBlock (styleganv1.py:231): every
 // output pixel (2m+py, 2n+px) takes exactly 2x2 of the 16 taps.
-#include "conv_mfma_f32.hpp"
+#include "conv_plan.hpp"
 
 namespace spkconv {
 
-int run_2x2_parity(int cfg, const spk_conv2d_desc* d, int Hd, int Wd, int pshift, hipStream_t s) {
+const void* tap_kernel_2x2(int cfg, int mode, bool fg) {
+    if (fg || mode != MODE_PLAIN) return nullptr;
     switch (cfg) {
-        case 0: return run<Cfg0, 2, 2, 1, MODE_PLAIN>(d, s, Hd, Wd, pshift);
-        case 1: return run<Cfg1, 2, 2, 1, MODE_PLAIN>(d, s, Hd, Wd, pshift);
-        case 2: return run<Cfg2, 2, 2, 1, MODE_PLAIN>(d, s, Hd, Wd, pshift);
-        default: return run<Cfg3, 2, 2, 1, MODE_PLAIN>(d, s, Hd, Wd, pshift);
+        case 0: return tap_kernel_ptr<SPK_TAP_CFG(0), 2, 2, 1, MODE_PLAIN>();
+        case 1: return tap_kernel_ptr<SPK_TAP_CFG(1), 2, 2, 1, MODE_PLAIN>();
+        case 2: return tap_kernel_ptr<SPK_TAP_CFG(2), 2, 2, 1, MODE_PLAIN>();
+        case 3: return tap_kernel_ptr<SPK_TAP_CFG(3), 2, 2, 1, MODE_PLAIN>();
+        default: return nullptr;
     }
 }
 

@@ -1,23 +1,26 @@
 // 3x3 stride-1 instantiations, full-depth chunk configs (CI_T = 8): ids 0-3.
-#include "conv_mfma_f32.hpp"
+#include "conv_plan.hpp"
 
 namespace spkconv {
 
-template <class C>
-static int by_mode(int mode, const spk_conv2d_desc* d, hipStream_t s) {
+template <int ID, class C>
+static const void* by_mode(int mode) {
     switch (mode) {
-        case MODE_PLAIN: return run<C, 3, 3, 1, MODE_PLAIN>(d, s);
-        case MODE_UPSAMPLE: return run<C, 3, 3, 1, MODE_UPSAMPLE>(d, s);
-        default: return run<C, 3, 3, 1, MODE_AFFINE_RELU>(d, s);
+        case MODE_PLAIN: return tap_kernel_ptr<ID, C, 3, 3, 1, MODE_PLAIN>();
+        case MODE_UPSAMPLE: return tap_kernel_ptr<ID, C, 3, 3, 1, MODE_UPSAMPLE>();
+        case MODE_AFFINE_RELU: return tap_kernel_ptr<ID, C, 3, 3, 1, MODE_AFFINE_RELU>();
+        default: return nullptr;
     }
 }
 
-int run_3x3s1_a(int cfg, int mode, const spk_conv2d_desc* d, hipStream_t s) {
+const void* tap_kernel_3x3s1_a(int cfg, int mode, bool fg) {
+    if (fg) return nullptr;
     switch (cfg) {
-        case 0: return by_mode<Cfg0>(mode, d, s);
-        case 1: return by_mode<Cfg1>(mode, d, s);
-        case 2: return by_mode<Cfg2>(mode, d, s);
-        default: return by_mode<Cfg3>(mode, d, s);
+        case 0: return by_mode<SPK_TAP_CFG(0)>(mode);
+        case 1: return by_mode<SPK_TAP_CFG(1)>(mode);
+        case 2: return by_mode<SPK_TAP_CFG(2)>(mode);
+        case 3: return by_mode<SPK_TAP_CFG(3)>(mode);
+        default: return nullptr;
     }
 }
 

@@ -808,169 +808,6 @@ __global__ __launch_bounds__(C::NTHREADS) void conv_kernel(const ConvArgs p) {
 #endif
 }
 
-// ---- host side -------------------------------------------------------------------------------------
-struct Geometry {
-    int TW, TH, TB, PLANE, tiles_x, tiles_y, tiles_b, n_chunks, co_tiles;
-    size_t lds_bytes;
-    bool ok, one_slot;
-};
-
-template <class C, int KH, int KW, int S>
-Geometry geometry(int B, int Cin, int Cout, int H, int W) {
-    using SH = Shape<C, KH, KW, S>;
-    Geometry g;
-    g.TW = std::min(32, spk::pow2_ceil(W));
-    g.TH = std::min(C::PIX_T / g.TW, spk::pow2_ceil(H));
-    g.TB = C::PIX_T / (g.TW * g.TH);
-    auto plane = [&]() { return ((g.TH - 1) * SH::SL + KH) * ((g.TW - 1) * SH::SL + KW); };
-    // the wave's share of the input tile must fit its prefetch slots
-    auto slots = [&]() { return spk::ceil_div(C::CI_T * g.TB / C::NW * plane(), 64); };
-    while (slots() > SH::NSLOT && g.TB > 1 && (C::CI_T * (g.TB / 2)) % C::NW == 0) g.TB >>= 1;  // idle pixel groups
-    while (slots() > SH::NSLOT && g.TH > 1) g.TH >>= 1;
-    g.PLANE = plane();
-    g.ok = slots() <= SH::NSLOT && (C::CI_T * g.TB) % C::NW == 0 && C::CI_T <= 64;
-    g.tiles_x = spk::ceil_div(W, g.TW);
-    g.tiles_y = spk::ceil_div(H, g.TH);
-    g.tiles_b = spk::ceil_div(B, g.TB);
-    g.n_chunks = spk::ceil_div(Cin, C::CI_T);
-    g.co_tiles = spk::ceil_div(Cout, C::CO_T);
-    const size_t in_floats = ((size_t)C::CI_T * g.TB * g.PLANE + 3) & ~(size_t)3;
-    g.one_slot = KH * KW > 9 && g.n_chunks == 1;   // rolled-loop kernel with a single chunk: no ring needed
-    g.lds_bytes = (g.one_slot ? 1 : 3) * (SH::W_FLOATS + in_floats + 4) * sizeof(float);   // three-slot ring
-    if (g.lds_bytes > 160 * 1024) g.ok = false;
-    return g;
-}
-
-// number of ci-chunk slices so that the grid fills the chip (about 2 workgroups per CU)
-inline int pick_ksplit(const Geometry& g) {
-    const long long tiles = (long long)g.tiles_x * g.tiles_y * g.tiles_b * g.co_tiles;
-    static const int target = [] { const char* e = getenv("SPK_KSPLIT_TARGET"); return e ? atoi(e) : 512; }();
-    int ks = 1;
-    while (tiles * ks < target && g.n_chunks / (ks * 2) >= 4 && ks < 64) ks *= 2;
-    return ks;
-}
-
-inline int resolve_ksplit(const Geometry& g, int requested, int* chunks_per_split) {
-    int ks = requested > 0 ? requested : pick_ksplit(g);
-    ks = std::max(1, std::min(ks, g.n_chunks));
-    const int cps = spk::ceil_div(g.n_chunks, ks);
-    if (chunks_per_split) *chunks_per_split = cps;
-    return spk::ceil_div(g.n_chunks, cps);
-}
-
-int launch_splitk_epilogue(const ConvArgs& a, const float* ws, int ksplit, hipStream_t stream);
-// the finisher launch_splitk_epilogue runs for these tensors: 2 = vector (*seg lanes of a wave share a plane), 1 = scalar (*seg = 0)
-int splitk_finisher(const ConvArgs& a, const float* ws, int* seg);
-
-// spk_conv2d_launch_form: while set (on the calling thread), the launch paths answer here where they would launch and return
-extern thread_local spk_conv2d_form* form_probe;
-int report_sliced_form(const ConvArgs& finisher_args, const float* ws, int ksplit);   // Winograd / config 13: the finisher alone
-// spk_conv2d_gemm_form: the same for run_1x1_gemm / run_1x1_gemm2 / run_stem, which fill it after their own requirements and
-// argument set-up and return before anything is launched
-extern thread_local spk_gemm_form* gemm_form_probe;
-
-inline int report_form(int config, int mode, const Geometry& g, const ConvArgs& a, float* y, int ksplit, bool ragged, bool use_fg,
-                       long long gx, const float* ws) {
-    spk_conv2d_form& f = *form_probe;
-    f.config = config; f.mode = mode; f.TW = g.TW; f.TH = g.TH; f.TB = g.TB;
-    f.n_chunks = g.n_chunks; f.chunks_per_split = a.chunks_per_split;
-    f.last_split_chunks = g.n_chunks - (ksplit - 1) * a.chunks_per_split;
-    f.ragged_last_chunk = ragged; f.fixed_geometry = use_fg; f.one_slot_ring = g.one_slot; f.staged = a.staged;
-    f.grid_x = (int)gx; f.grid_y = g.co_tiles; f.grid_z = ksplit;
-    f.lds_bytes = (int64_t)g.lds_bytes;
-    ConvArgs fin = a;
-    fin.y = y;
-    return report_sliced_form(fin, ws, ksplit);
-}
-
-// Fill ConvArgs from the public descriptor, pick geometry / split-K, launch (and the split-K epilogue).
-template <class C, int KH, int KW, int S, int MODE, bool TRY_FG = false>
-int run(const spk_conv2d_desc* d, hipStream_t stream, int Hd = 0, int Wd = 0, int pshift = 0) {
-    ConvArgs a;
-    a.Hd = Hd; a.Wd = Wd; a.pshift = pshift;
-    a.x = d->x; a.wp = d->w_packed; a.bias = d->bias; a.noise_w = d->noise_w; a.noise = d->noise;
-    a.style = d->style; a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.stats = d->stats; a.stats_slots = d->stats_slots > 1 ? d->stats_slots : 1; a.y = d->y; a.y_pre = d->y_pre; a.out_scale_bc = d->out_scale_bc;
-    a.residual = (d->flags & SPK_EPI_RESIDUAL) ? d->residual : nullptr;
-    a.B = d->B; a.Cin = d->Cin; a.Cout = d->Cout; a.H = d->H; a.W = d->W; a.Hs = d->Hin; a.Ws = d->Win;
-    a.G = d->groups > 1 ? d->groups : 1;
-    a.gin = a.G > 1 ? d->group_in_stride : d->Cin;
-    a.Cx = a.gin * (a.G - 1) + d->Cin;
-    a.Cy = a.G * d->Cout;
-    Geometry g = geometry<C, KH, KW, S>(d->B, d->Cin, d->Cout, d->H, d->W);
-    a.co_tiles_g = g.co_tiles;
-    g.co_tiles *= a.G;                                   // grid.y and the split-K fill heuristic count every group
-    SPK_REQUIRE(g.ok, "conv2d: config %d does not fit this shape (%dx%d, B=%d)", d->config, d->H, d->W, d->B);
-    // the staging tables hold 32-bit BYTE offsets relative to the image group's first plane
-    SPK_REQUIRE((size_t)g.TB * a.Cx * a.Hs * a.Ws < (1ull << 30), "conv2d: image group too large for 32-bit byte offsets");
-    a.lgTW = spk::ilog2(g.TW); a.lgTH = spk::ilog2(g.TH); a.lgTB = spk::ilog2(g.TB);
-    {
-        const unsigned pw = (unsigned)((g.TW - 1) * Shape<C, KH, KW, S>::SL + KW), plane = (unsigned)g.PLANE;
-        a.magic_plane = plane > 1 ? (unsigned)(((1ull << 32) + plane - 1) / plane) : 0u;   // 0: divisor 1
-        a.magic_pw = pw > 1 ? (unsigned)(((1ull << 32) + pw - 1) / pw) : 0u;
-        SPK_REQUIRE((size_t)C::CI_T * g.TB * g.PLANE < 65536, "conv2d: tile too large for the index arithmetic");
-    }
-    a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
-    a.n_chunks = g.n_chunks;
-    a.style_stride = d->style_stride; a.flags = d->flags; a.slope = d->lrelu_slope; a.out_scale = d->out_scale; a.act_gain = d->act_gain != 0.f ? d->act_gain : 1.f;
-    a.out_scale_dev = d->out_scale_dev;
-    const int ksplit = resolve_ksplit(g, d->ksplit, &a.chunks_per_split);
-    // the fixed-geometry build of the same kernel, where the layer's tile is that one (and no chunk is ragged)
-    bool use_fg = false;
-    if constexpr (TRY_FG) {
-        static const bool fg_on = [] { const char* e = getenv("SPK_CONV_FG"); return !e || atoi(e) != 0; }();
-        use_fg = fg_on && g.TW == 32 && g.TH == C::PIX_T / 32 && g.TB == 1 && d->Cin % C::CI_T == 0 && d->Hin >= 2 && d->Win >= 2;
-        if (use_fg)                       // planes NSLOT * 64 floats apart (see the kernel)
-            g.lds_bytes = 3 * ((size_t)Shape<C, KH, KW, S>::W_FLOATS + (size_t)C::CI_T * Shape<C, KH, KW, S>::NSLOT * 64 + 4) * sizeof(float);
-    }
-    // staged epilogue: whenever its LDS tile costs no workgroup slot and the vectors are whole and aligned
-    a.staged = 0;
-    {
-        static const bool allow = [] { const char* e = getenv("SPK_CONV_STAGED_EPI"); return !e || atoi(e) != 0; }();
-        const size_t tile_bytes = (size_t)C::CO_T * (C::PIX_T + 4) * sizeof(float);
-        const size_t red_bytes = (d->flags & SPK_EPI_STATS) ? 2 * (size_t)C::CO_T * sizeof(float) : 0;   // row sums behind the tile
-        const size_t lds_now = g.lds_bytes;
-        const auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        const auto same_slots = [&](size_t bytes) { return (160 * 1024) / std::max(bytes, lds_now) == (160 * 1024) / lds_now; };
-        constexpr bool can_halve = C::MT == 2;
-        const int rounds = same_slots(tile_bytes + red_bytes) ? 1 : ((can_halve && same_slots(tile_bytes / 2 + red_bytes)) ? 2 : 0);
-        if (allow && rounds && KH != 2 && ksplit == 1 && g.TW >= 4 && d->W % 4 == 0 && C::NTHREADS % (C::PIX_T / 4) == 0 &&
-            (C::CO_T / rounds) % (C::NTHREADS / (C::PIX_T / 4)) == 0 && aligned(d->y) && aligned(d->y_pre) && aligned(d->noise) && aligned(a.residual)) {
-            a.staged = rounds;
-            g.lds_bytes = std::max(lds_now, tile_bytes / rounds + red_bytes);
-        }
-    }
-    const size_t out_floats = (size_t)d->B * a.Cy * d->H * d->W;
-    if (ksplit > 1) {
-        SPK_REQUIRE(d->workspace && (size_t)d->workspace_bytes >= ksplit * out_floats * sizeof(float),
-                    "conv2d: split-K x%d needs a %zu-byte workspace (see spk_conv2d_workspace_bytes)", ksplit,
-                    ksplit * out_floats * sizeof(float));
-        a.y = static_cast<float*>(d->workspace);
-    }
-    auto kern = &conv_kernel<C, KH, KW, S, MODE>;
-    if constexpr (TRY_FG) {
-        if (use_fg) kern = &conv_kernel<C, KH, KW, S, MODE, true>;
-    }
-    const long long gx = (long long)g.tiles_x * g.tiles_y * g.tiles_b;
-    SPK_REQUIRE(gx < (1ll << 31), "conv2d: grid too large");
-    if (form_probe)
-        return report_form(d->config, MODE, g, a, d->y, ksplit, d->Cin % C::CI_T != 0, use_fg, gx, static_cast<const float*>(d->workspace));
-    if (g.lds_bytes > 64 * 1024) {  // dynamic LDS above 64 KiB needs the attribute raised (once per kernel)
-        static const void* raised[2] = {nullptr, nullptr};
-        const void* kp = reinterpret_cast<const void*>(kern);
-        if (raised[0] != kp && raised[1] != kp) {
-            hipError_t e = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return spk::fail(SPK_ELAUNCH, "hipFuncSetAttribute(LDS): %s", hipGetErrorString(e));
-            raised[raised[0] ? 1 : 0] = kp;
-        }
-    }
-    dim3 grid((unsigned)gx, (unsigned)g.co_tiles, (unsigned)ksplit);
-    hipLaunchKernelGGL(kern, grid, dim3(C::NTHREADS), g.lds_bytes, stream, a);
-    int rc = spk::check_launch("conv_kernel");
-    if (rc != SPK_OK || ksplit == 1) return rc;
-    a.y = d->y;
-    return launch_splitk_epilogue(a, static_cast<const float*>(d->workspace), ksplit, stream);
-}
-
 // ---- tile configs ------------------------------------------------------------------------------------
 //                 WM WN MT NT CI_T      CO_T  PIX_T  used by
 typedef Cfg<2, 2, 2, 2, 8> Cfg0;   //  128   128   3x3 s1
@@ -985,42 +822,5 @@ typedef Cfg<2, 2, 2, 2, 16> Cfg8;  //  128   128   1x1 s1/s2   (16-channel chunk
 typedef Cfg<1, 4, 2, 2, 16> Cfg9;  //   64   256   1x1 s1/s2
 typedef Cfg<2, 2, 1, 1, 16> Cfg10; //   64    64   1x1 s1/s2
 typedef Cfg<1, 4, 1, 1, 16> Cfg11; //   32   128   1x1 s1/s2
-constexpr int kNumConfigs = 17;   // 12 = the GEMM form of a stride-1 1x1 (conv1x1_gemm.hip): 128co x 128px block, 32-channel k-tiles
-constexpr int kGemmConfig = 12;
-constexpr int kDgradS2Config = 13;   // the exact-tap data gradient of a 3x3 stride-2 conv (dgrad3x3s2.hip): 64co x 128px block, 8-channel chunks
-constexpr int kGemm2Config = 14;     // the three-per-CU GEMM form of a stride-1 1x1 (conv1x1_gemm2.hip): 128co x 128px block, 16-channel k-tiles
-constexpr int kGemm2NarrowConfig = 15;   // the same with a 64co x 128px block (four per CU)
-inline bool is_gemm2(int cfg) { return cfg == kGemm2Config || cfg == kGemm2NarrowConfig; }
-constexpr int kStemConfig = 16;          // the 7x7 stride-2 stem, Cin 3 -> Cout 64 per group (conv7x7_stem.hip): K = 147 exactly, 16 x 32 pixel tiles
-
-// several weight tensors of one shape on one launch (blockIdx.y = which): their packed images one after another, as a
-// grouped conv launch reads them
-struct PackList { const float* w[SPK_PACK_LIST_MAX]; };
-
-// per-family dispatchers, one translation unit each (parallel compilation)
-int run_3x3s1_a(int cfg, int mode, const spk_conv2d_desc* d, hipStream_t s);  // ids 0-3
-int run_3x3s1_b(int cfg, int mode, const spk_conv2d_desc* d, hipStream_t s);  // ids 4-7
-int run_3x3s1_stats(int cfg, const spk_conv2d_desc* d, hipStream_t s);      // ids 0-7, MODE_PLAIN_STATS
-int run_3x3s2_7x7s2(int kh, int cfg, int mode, const spk_conv2d_desc* d, hipStream_t s);  // ids 4-7
-int run_1x1(int stride, int cfg, int mode, const spk_conv2d_desc* d, hipStream_t s);      // ids 8-11
-int run_2x2_parity(int cfg, const spk_conv2d_desc* d, int Hd, int Wd, int pshift, hipStream_t s);     // ids 0-3
-int run_1x1_gemm(const spk_conv2d_desc* d, hipStream_t s);                                // id 12
-int run_dgrad_s2_fused(const spk_conv2d_desc* d, hipStream_t s);                          // id 13
-bool dgrad_s2_fused_takes(int B, int K, int Cc, int Hg, int Wg);
-int dgrad_s2_ksplit(int B, int K, int Cc, int Hg, int Wg, int G);         // contraction slices of the exact-tap kernel (1 = none)
-long long dgrad_s2_fused_packed_floats(int K, int Cc);
-bool gemm1x1_takes(int kh, int stride, int Cin, int H, int W);
-long long gemm1x1_pixel_tiles(int B, int H, int W);
-int run_1x1_gemm2(const spk_conv2d_desc* d, hipStream_t s);                               // ids 14, 15
-bool gemm2_takes(int kh, int stride, int Cin, int Cout, int H, int W);
-int gemm2_co_tile(int config);
-long long gemm2_pixel_tiles(int B, int H, int W);
-long long gemm2_packed_floats(int config, int Cin, int Cout);
-int pack_gemm2(const PackList& list, int n_list, float* w_packed, int Cin, int Cout, int config, int tf, hipStream_t stream);
-int run_stem(const spk_conv2d_desc* d, hipStream_t s);                                    // id 16
-bool stem_takes(int kh, int stride, int Cin, int Cout, int H, int W);
-long long stem_packed_floats();
-void stem_tiles(int H, int W, int* tiles_x, int* tiles_y);
-int pack_stem(const PackList& list, int n_list, float* w_packed, int Cin, int Cout, int tf, hipStream_t stream);
 
 }  // namespace spkconv

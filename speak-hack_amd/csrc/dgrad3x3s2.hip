@@ -16,7 +16,7 @@
 // replaces: the input-gradient half of F.conv2d's backward for the stride-2 3x3 convs on the path -- conv2 of the first
 // bottleneck of layer2-4 of the torchvision trunk (model.py:60-62), conv2 of every StyleDiscriminator block
 // (styleganv1.py:644-657).
-#include "conv_mfma_f32.hpp"      // (ConvArgs + launch_splitk_epilogue for the sliced form)
+#include "conv_plan.hpp"      // (ConvArgs + launch_splitk_epilogue for the sliced form)
 
 #include <algorithm>
 #include <type_traits>
@@ -223,47 +223,57 @@ bool dgrad_s2_fused_takes(int B, int K, int Cc, int Hg, int Wg) {
     return B > 0 && K > 0 && Cc > 0 && Hg > 0 && Wg > 0 && (long long)(spkdg::CI_T + 1) * Hg * Wg < (1ll << 31);
 }
 
-// d = the SPK_CONV_DGRAD_S2 descriptor: x = g [B, G*Cin, Hin, Win], y = dx [B, G*Cout, H, W]
-int run_dgrad_s2_fused(const spk_conv2d_desc* d, hipStream_t stream) {
+// d = the SPK_CONV_DGRAD_S2 descriptor: x = g [B, G*Cin, Hin, Win], y = dx [B, G*Cout, H, W].  Every requirement and decision of a
+// config-13 launch; `a`: the kernel's argument block, `grid`: its launch grid.
+static int plan_args(const spk_conv2d_desc* d, SlicedPlan& p, spkdg::Args& a, dim3& grid) {
     using namespace spkdg;
-    Args a;
+    const Groups q = groups_of(*d);
     a.g = static_cast<const float*>(d->x); a.wp = static_cast<const float*>(d->w_packed); a.y = static_cast<float*>(d->y);
     a.B = d->B; a.K = d->Cin; a.Cc = d->Cout; a.Hg = d->Hin; a.Wg = d->Win; a.Hd = d->H; a.Wd = d->W;
-    a.G = d->groups > 1 ? d->groups : 1;
-    a.gin = a.G > 1 ? d->group_in_stride : d->Cin;
-    a.Cg = a.gin * (a.G - 1) + d->Cin;
-    a.Cy = a.G * d->Cout;
+    a.G = q.G; a.gin = q.gin; a.Cg = (int)q.Cx; a.Cy = (int)q.Cy;
     a.co_tiles_g = spk::ceil_div(d->Cout, CO_T);
     a.n_chunks = spk::ceil_div(d->Cin, CI_T);
     a.tiles_x = spk::ceil_div(d->Win, TW); a.tiles_y = spk::ceil_div(d->Hin, TH);
     a.accumulate = (d->flags & SPK_EPI_ACCUM) ? 1 : 0;
     a.out_scale = d->out_scale; a.out_scale_dev = d->out_scale_dev;
     SPK_REQUIRE(dgrad_s2_fused_takes(d->B, d->Cin, d->Cout, d->Hin, d->Win), "conv2d: DGRAD_S2 (config 13): gradient plane too large");
-    SPK_REQUIRE((reinterpret_cast<uintptr_t>(d->w_packed) & 15) == 0, "conv2d: DGRAD_S2 (config 13): w_packed must be 16-byte aligned");
+    SPK_REQUIRE(aligned16(d->w_packed), "conv2d: DGRAD_S2 (config 13): w_packed must be 16-byte aligned");
     const long long gx = (long long)a.tiles_x * a.tiles_y * d->B;
     SPK_REQUIRE(gx < (1ll << 31) && a.G * a.co_tiles_g < 65536, "conv2d: grid too large");
     // few workgroups (a 16^2 gradient at B = 8: 16 pixel tiles x 8 channel tiles for 512 slots of two per CU): the contraction runs in
-    // slices, partial sums through the caller's split-K workspace, the direct kernels' finisher adds them up (scale, accumulate)
+    // slices, partial sums through the caller's split-K workspace, the direct kernels' finisher adds them up (scale, accumulate).
+    // Without a usable workspace the launch runs unsliced.
     const int ks = dgrad_s2_ksplit(d->B, d->Cin, d->Cout, d->Hin, d->Win, a.G);
     const size_t out_floats = (size_t)d->B * a.Cy * d->H * d->W;
-    const bool split = ks > 1 && d->ksplit != 1 && d->workspace && (reinterpret_cast<uintptr_t>(d->workspace) & 15) == 0 &&
-                       d->workspace_bytes >= (int64_t)ks * (int64_t)out_floats * 4;
+    const bool split = ks > 1 && d->ksplit != 1 && d->workspace && aligned16(d->workspace) && d->workspace_bytes >= (int64_t)ks * (int64_t)out_floats * 4;
     a.cps = split ? spk::ceil_div(a.n_chunks, ks) : a.n_chunks;
     a.slice_floats = split ? out_floats : 0;
     const int nz = split ? spk::ceil_div(a.n_chunks, a.cps) : 1;
     if (split) { a.y = static_cast<float*>(d->workspace); a.accumulate = 0; a.out_scale = 1.f; a.out_scale_dev = nullptr; }
-    ConvArgs f = {};                // the finisher's arguments
-    f.y = static_cast<float*>(d->y); f.B = d->B; f.Cin = d->Cin; f.Cout = d->Cout; f.Cy = a.Cy; f.Cx = a.Cg; f.G = a.G; f.H = d->H; f.W = d->W;
-    f.flags = d->flags & SPK_EPI_ACCUM; f.slope = 1.f; f.out_scale = d->out_scale; f.act_gain = 1.f; f.out_scale_dev = d->out_scale_dev;
-    if (form_probe) {
-        form_probe->config = kDgradS2Config;
-        return report_sliced_form(f, static_cast<const float*>(d->workspace), nz);
-    }
-    dim3 grid((unsigned)gx, (unsigned)(a.G * a.co_tiles_g), (unsigned)nz);
-    hipLaunchKernelGGL(dgrad3x3s2_kernel, grid, dim3(256), 2 * STAGE * sizeof(float), stream, a);
-    int rc = spk::check_launch("dgrad3x3s2_kernel");
-    if (rc != SPK_OK || !split) return rc;
-    return launch_splitk_epilogue(f, static_cast<const float*>(d->workspace), nz, stream);
+    grid = dim3((unsigned)gx, (unsigned)(a.G * a.co_tiles_g), (unsigned)nz);
+    p.config = kDgradS2Config;
+    p.finish.args = finisher_args(*d, q, d->flags & SPK_EPI_ACCUM, d->out_scale);
+    p.finish.args.noise = nullptr;      // (no noise stage here: a stray pointer must not count in the finisher's alignment rule)
+    p.finish.ws = static_cast<const float*>(d->workspace);
+    p.finish.ksplit = nz;
+    return SPK_OK;
+}
+
+int plan_dgrad_s2_fused(const spk_conv2d_desc* d, SlicedPlan& p) {
+    spkdg::Args a;
+    dim3 grid;
+    return plan_args(d, p, a, grid);
+}
+
+int fwd_dgrad_s2_fused(const spk_conv2d_desc* d, hipStream_t stream) {
+    SlicedPlan p;
+    spkdg::Args a;
+    dim3 grid;
+    int rc = plan_args(d, p, a, grid);
+    if (rc != SPK_OK) return rc;
+    hipLaunchKernelGGL(spkdg::dgrad3x3s2_kernel, grid, dim3(256), 2 * spkdg::STAGE * sizeof(float), stream, a);
+    rc = spk::check_launch("dgrad3x3s2_kernel");
+    return rc != SPK_OK ? rc : launch_finish(p.finish, stream);
 }
 
 // slices of the contraction for the exact-tap kernel: 1 unless the grid fills less than half of the 512 workgroup slots

@@ -3,7 +3,7 @@ and 15) and of the 7x7 stride-2 stem kernel (csrc/conv7x7_stem.hip: config 16) -
 
 The cases are ``direct_conv_cases.case`` records and go through that module's machinery (``inputs``, ``reference``, ``figures``):
 they are entered into its ``BY_NAME``.  A case forces its config, names its operands and DECLARES the fields of ``spk_gemm_form``
-it reaches; ``spk_conv2d_gemm_form`` -- run_1x1_gemm / run_1x1_gemm2 / run_stem's own statements -- decides whether it does
+it reaches; ``spk_conv2d_gemm_form`` -- the planners those launches run (plan_1x1_gemm / plan_1x1_gemm2 / plan_stem) -- decides whether it does
 (tests/test_gemm_conv_forms_cpu.py without a GPU, tests/test_gemm_conv_branches_gpu.py again with the real pointers).
 ``branches(c, form)`` names what a case covers, from the form the library answered and the case's operands."""
 import numpy as np

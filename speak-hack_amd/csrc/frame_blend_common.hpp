@@ -1,8 +1,8 @@
 // What the seamless paste-back shares between pixel formats (csrc/frame_blend.hip: packed RGB; csrc/frame_sim_nv12.hip: NV12
-// surfaces): the one device function every per-pixel quantity of the aligned paste comes from, and the statistics of the colour
-// match -- 13 fp64 sums per frame, reduced in a fixed order -- with the kernel that turns the sums into rows.  A format's file holds
-// where its background is read and how its bytes are written; the weights, the sums and the rows are written once, here, so the
-// formats cannot drift and rows from either mean the same thing.
+// surfaces): the statistics of the colour match -- 13 fp64 sums per frame, reduced in a fixed order -- with the kernels that turn
+// the sums into rows or hand them back, and the one host path that launches them.  A format's file holds where its background is
+// read and how its bytes are written; the weights (region_pixel of csrc/frame_sim_common.hpp), the sums and the rows are written
+// once, so the formats cannot drift and rows from either mean the same thing.
 #pragma once
 
 #include "colour_rows_common.hpp"
@@ -11,69 +11,6 @@
 namespace spk::frame {
 
 constexpr int STAT_WAVES = 4;           // waves of a workgroup of the statistics kernel (256 threads)
-
-struct PixelConsts { double is2, r, ir, fe; };
-
-__device__ __forceinline__ PixelConsts pixel_consts(const Sim& m, double feather) {
-    return {1.0 / (m.s * m.s), fmax(1.0, 1.0 / m.s), 1.0 / fmax(1.0, 1.0 / m.s), 1.0 / (feather + 1.0)};
-}
-
-// Frame pixel (Y, X) of a frame with the valid row m.  false: the pixel is outside the region.  true: q[c] is the unmatched
-// quantised value of network channel c (fp32, not rounded) and mm = a_u a_v Mt.  img: the frame's first source plane; mt: the
-// frame's matte (Hs x Ws) or NULL (Mt = 1).  The matte sum runs beside the channel sums, over the same taps in the same order.
-__device__ __forceinline__ bool region_pixel(const Sim& m, const PixelConsts& pc, int X, int Y, const float* __restrict__ img, long long plane,
-                                             int Hs, int Ws, const float* __restrict__ mt, float lo, float k, float (&q)[3], double& mm) {
-    const double is2 = pc.is2, r = pc.r, ir = pc.ir, fe = pc.fe;
-    const double dx = (X + 0.5) - m.tx, dy = (Y + 0.5) - m.ty;
-    const double u = (m.a * dx + m.c * dy) * is2, v = (-m.c * dx + m.a * dy) * is2;
-    if (!(u >= 0.0 && u < (double)Ws && v >= 0.0 && v < (double)Hs)) return false;
-    int i_lo, i_hi, j_lo, j_hi;                                   // taps with |i + 0.5 - u| < r: 2 x 2 when the crop enlarges
-    int_range(u - r - 0.5, u + r - 0.5, Ws, i_lo, i_hi);
-    int_range(v - r - 0.5, v + r - 0.5, Hs, j_lo, j_hi);
-    double su = 0.0, sv = 0.0, v0 = 0.0, v1 = 0.0, v2 = 0.0, vm = 0.0;
-    for (int i = i_lo; i <= i_hi; ++i) su += tri(((i + 0.5) - u) * ir);
-    for (int j = j_lo; j <= j_hi; ++j) {
-        const double wv = tri(((j + 0.5) - v) * ir);
-        const float* p = img + (long long)j * Ws;
-        double h0 = 0.0, h1 = 0.0, h2 = 0.0, hm = 0.0;
-        for (int i = i_lo; i <= i_hi; ++i) {
-            const double wu = tri(((i + 0.5) - u) * ir);
-            h0 = fma(wu, (double)p[i], h0);
-            h1 = fma(wu, (double)p[plane + i], h1);
-            h2 = fma(wu, (double)p[2 * plane + i], h2);
-            if (mt) {
-                const float a = mt[(long long)j * Ws + i];
-                hm = fma(wu, a == a ? (double)a : 0.0, hm);       // a NaN sample counts as 0
-            }
-        }
-        sv += wv;
-        v0 = fma(wv, h0, v0);
-        v1 = fma(wv, h1, v1);
-        v2 = fma(wv, h2, v2);
-        vm = fma(wv, hm, vm);
-    }
-    const double norm = su * sv;                                  // > 0: a centre lies within half a pixel of u and of v
-    const double val[3] = {v0 / norm, v1 / norm, v2 / norm};
-    const double a_u = fmin(1.0, (m.s * fmin(u, (double)Ws - u) + 0.5) * fe), a_v = fmin(1.0, (m.s * fmin(v, (double)Hs - v) + 0.5) * fe);
-    mm = a_u * a_v;
-    if (mt) mm *= fmin(fmax(vm / norm, 0.0), 1.0);                // fmax returns its other operand for a NaN: clamp01(NaN) = 0
-#pragma unroll
-    for (int c = 0; c < 3; ++c) q[c] = quant_unrounded((float)val[c], lo, k);
-    return true;
-}
-
-// The colour rows of frame n as the paste applies them: (1, 0) without rows and for a row that is not finite.
-__device__ __forceinline__ void load_colour(const float* __restrict__ colour, long long n, float (&g)[3], float (&o)[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = 1.f, o[c] = 0.f;
-    if (colour) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float gc = colour[n * 6 + 2 * c], oc = colour[n * 6 + 2 * c + 1];
-            if (isfinite(gc) && isfinite(oc)) g[c] = gc, o[c] = oc;
-        }
-    }
-}
 
 // The sum over the 64 lanes of a wave, in every lane: a butterfly, so the order of the additions is fixed.  Every lane executes it.
 __device__ __forceinline__ double wave_sum(double v) {
@@ -189,13 +126,30 @@ inline int64_t colour_match_workspace_bytes(int N) {
     return (int64_t)N * PASTE_WGS * SUMS * (int64_t)sizeof(double);
 }
 
-// the blend's arguments that do not depend on the pixel format (pointers, sizes and strides are the format's to check)
-inline int check_blend_params(const char* who, int N, double feather, float lo, float k, const float* matte_dev, int matte_frames) {
-    SPK_REQUIRE(std::isfinite(feather) && feather >= 0.0, "%s: feather must be a finite number >= 0 (got %g)", who, feather);
-    if (int rc = check_range(who, lo, k)) return rc;
-    SPK_REQUIRE(matte_dev ? (matte_frames == 1 || matte_frames == N) : matte_frames == 0,
-                "%s: matte_frames must be 1 or N = %d with a matte and 0 without one (got %d)", who, N, matte_frames);
-    return SPK_OK;
+// What becomes of a frame's 13 sums: the rows of the colour match, or the totals themselves.
+struct ColourFinish {
+    float* colour_out;                  // rows: [N,3,2] to write, with the three parameters of the row formula; NULL: the totals
+    double max_gain, min_sigma, min_weight;
+    double* sums_out;                   // totals: [N,13] to write
+};
+
+// The statistics over checked arguments, for every format: the sums of each workgroup, then a frame's partials into rows or totals.
+template <class Background>
+int launch_colour_statistics(const char* kernel, const Background& bg, const float* src, int N, int Hs, int Ws, int H, int W, const float* sim_dev,
+                             double feather, float lo, float k, const float* matte_dev, int matte_frames, void* workspace_dev,
+                             const ColourFinish& fin, void* stream) {
+    hipLaunchKernelGGL(paste_colour_sums_kernel<Background>, dim3(PASTE_WGS, (unsigned)std::min(N, 65535)), dim3(256), 0, (hipStream_t)stream, src, N,
+                       Hs, Ws, bg, H, W, sim_dev, feather, lo, k, matte_dev, matte_frames, (double*)workspace_dev);
+    if (int rc = spk::check_launch(kernel)) return rc;
+    const dim3 grid((unsigned)((N + 63) / 64));
+    if (fin.colour_out) {
+        hipLaunchKernelGGL(paste_colour_rows_kernel, grid, dim3(64), 0, (hipStream_t)stream, (const double*)workspace_dev, N, PASTE_WGS, sim_dev,
+                           fin.max_gain, fin.min_sigma * fin.min_sigma, fin.min_weight, fin.colour_out);
+        return spk::check_launch("paste_colour_rows_kernel");
+    }
+    hipLaunchKernelGGL(paste_colour_totals_kernel, grid, dim3(64), 0, (hipStream_t)stream, (const double*)workspace_dev, N, PASTE_WGS, sim_dev,
+                       fin.sums_out);
+    return spk::check_launch("paste_colour_totals_kernel");
 }
 
 // the workspace of the partial sums of N frames

@@ -178,6 +178,60 @@ def packed_pixels(frames_u8):
         (N == 1 or frames_u8.stride(0) >= (H - 1) * frames_u8.stride(1) + 3 * W)
 
 
+class _Packed:
+    """The frames of a call as packed uint8 ``[N,H,W,3]`` (csrc/frame_io.hip, csrc/frame_sim.hip, csrc/frame_blend.hip): how they
+    are checked and opened, the argument runs their entry points take for frames that are read and for frames that are written,
+    their colour arguments and their entry points.  ``_Surfaces`` says the same of NV12; the launchers are written over either."""
+    way_in, paste, sums, match = "spk_frames_u8_to_f32_sim", "spk_frames_paste_u8_sim", "spk_paste_colour_sums_sim", "spk_paste_colour_match_sim"
+
+    def shaped(self, frames, N, what):                                    # N=None: any number, one frame may come as [H,W,3]; -> (frames, N, H, W)
+        if N is None and frames.dim() == 3:
+            frames = frames.unsqueeze(0)
+        if frames.dim() != 4 or frames.size(3) != 3 or (frames.size(0) < 1 if N is None else frames.size(0) != N):
+            raise ValueError(f"{what}: frames must be [{'N' if N is None else N},H,W,3], got {tuple(frames.shape)}")
+        return (frames, *frames.shape[:3])
+
+    def on_device(self, frames):
+        if not frames.is_cuda or frames.dtype != torch.uint8:
+            raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames.dtype} on {frames.device} (no CPU path)")
+
+    def read(self, frames, what, disjoint=False):
+        """Frames that are read, in place through their strides or made contiguous (``disjoint``: also where frames overlap):
+        -> ``(the tensor to hold until the launch is queued, its pointer and two strides)``"""
+        self.on_device(frames)
+        N, _, W, _ = frames.shape
+        if not (packed_pixels(frames) if disjoint else frames.stride(3) == 1 and frames.stride(2) == 3 and frames.stride(1) >= 3 * W and
+                (N == 1 or frames.stride(0) >= 0)):
+            frames = frames.contiguous()
+        return frames, (frames.data_ptr(), frames.stride(0) if N > 1 else 0, frames.stride(1))
+
+    def target(self, frames, out, N, H, W, device, what):
+        """Frames that are written: ``out`` checked, or a packed clone of ``frames``.  -> ``(the result, its pointer and two strides,
+        fill)``; ``fill()`` gives an ``out`` that is not ``frames`` its copy of them, once nothing can be refused any more."""
+        copy = out is not None and out is not frames and out.data_ptr() != frames.data_ptr()
+        if out is None:
+            out = frames.clone(memory_format=torch.contiguous_format)
+        elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames.shape):
+            raise L.SpkError(f"out: expected a uint8 HIP tensor {tuple(frames.shape)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        if not packed_pixels(out):
+            raise L.SpkError(f"out: pixels must be packed and rows / frames must not overlap, got strides {out.stride()}")
+        return out, (out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1)), (lambda: out.copy_(frames)) if copy else (lambda: None)
+
+    def standard(self):                                                   # what the way in takes behind the channel swap
+        return ()
+
+    def quantised(self, value_range, channel_order="rgb"):                # -> (the colour arguments of the way out, lo, k), in its check order
+        return ((_channel_swap(channel_order),), *quant_range(value_range))
+
+    def blend(self, matte_args, colour):                                  # -> (the paste's entry point, its arguments behind k)
+        if matte_args[0] is None and colour is None:
+            return self.paste, ()
+        return self.paste + "_blend", (*matte_args, _ptr(colour))
+
+
+_PACKED = _Packed()
+
+
 def frames_from_u8(frames_u8, size, *, crop=None, channel_order="rgb", mean=0.5, std=0.5):
     """uint8 HWC video frames -> the network's input, one launch (``spk_frames_u8_to_f32``): crop, antialiased bilinear resize
     to ``size`` x ``size`` (a number, or ``(H, W)``), ``(x / 255 - mean) / std`` per channel and HWC -> CHW -- ``transforms.Resize``
@@ -188,26 +242,20 @@ def frames_from_u8(frames_u8, size, *, crop=None, channel_order="rgb", mean=0.5,
     ``frames_from_u8_aligned`` takes a crop of any size and angle per frame), checked on the host and uploaded once; ``(boxes_yx, h, w)`` with a device int32 ``[N,2]`` tensor: origins a tracker left on the device,
     not read on the host -- the kernel clamps each so that the box stays inside the frame (``spk_frames_u8_to_f32_boxes``).
     -> float32 [N,3,size,size]."""
-    if frames_u8.dim() == 3:
-        frames_u8 = frames_u8.unsqueeze(0)
-    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
-        raise ValueError(f"frames_from_u8: frames must be [N,H,W,3], got {tuple(frames_u8.shape)}")
+    frames_u8, N, H, W = _PACKED.shaped(frames_u8, None, "frames_from_u8")
     Hout, Wout = _out_size(size, "frames_from_u8")
     swap = _channel_swap(channel_order)
     scale, shift = _affine(mean, std, "frames_from_u8")
     origins = None
     if crop is not None:
-        origins, h, w = parse_boxes(crop, frames_u8.size(0), frames_u8.size(1), frames_u8.size(2), "frames_from_u8: crop")
+        origins, h, w = parse_boxes(crop, N, H, W, "frames_from_u8: crop")
         if isinstance(origins, tuple):                                # one host box: a slice, read in place through its strides
             (y0, x0), origins = origins, None
             frames_u8 = frames_u8[:, y0:y0 + h, x0:x0 + w]
-    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
-        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
-    N, Hin, Win, _ = frames_u8.shape
-    if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * Win or (N > 1 and frames_u8.stride(0) < 0):
-        frames_u8 = frames_u8.contiguous()
+    frames_u8, where = _PACKED.read(frames_u8, "frames_from_u8")
+    _, Hin, Win, _ = frames_u8.shape
     out = torch.empty((N, 3, Hout, Wout), device=frames_u8.device, dtype=torch.float32)
-    entry, src = "spk_frames_u8_to_f32", (frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), N, Hin, Win)
+    entry, src = "spk_frames_u8_to_f32", (*where, N, Hin, Win)
     if origins is not None:                                               # the box is h x w of the frame, else the (sliced) frame itself
         entry, src = entry + "_boxes", (*src, _origins(origins, frames_u8.device, "frames_from_u8")[2].data_ptr(), h, w)
         Hin, Win = h, w
@@ -254,31 +302,21 @@ def frames_paste_u8(x, frames_u8, box, *, feather=0, value_range=(-1, 1), channe
     pixels that fall outside the frame are skipped.  ``channel_order="bgr"``: the frames are BGR, ``x`` is RGB.  ``out=None``:
     the result is a clone of ``frames_u8``; ``out=frames_u8``: pasted in place through its strides; another ``out`` first
     receives a copy of ``frames_u8``.  -> uint8 [N,H,W,3]."""
-    _check_chw(x, "frames_paste_u8")
-    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != x.size(0):
-        raise ValueError(f"frames_paste_u8: frames must be [{x.size(0)},H,W,3], got {tuple(frames_u8.shape)}")
-    swap = _channel_swap(channel_order)
-    lo, k = quant_range(value_range)
-    feather = check_feather(feather, "frames_paste_u8")
+    what = "frames_paste_u8"
+    _check_chw(x, what)
     N, _, Hs, Ws = x.shape
-    H, W = frames_u8.size(1), frames_u8.size(2)
-    origins, h, w = parse_boxes(box, N, H, W, "frames_paste_u8: box", inside=False)
+    frames_u8, _, H, W = _PACKED.shaped(frames_u8, N, what)
+    (swap,), lo, k = _PACKED.quantised(value_range, channel_order)
+    feather = check_feather(feather, what)
+    origins, h, w = parse_boxes(box, N, H, W, f"{what}: box", inside=False)
     xp = L.dptr(x, "x")
-    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
-        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
-    copy = out is not None and out is not frames_u8 and out.data_ptr() != frames_u8.data_ptr()
-    if out is None:
-        out = frames_u8.clone(memory_format=torch.contiguous_format)
-    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames_u8.shape):
-        raise L.SpkError(f"out: expected a uint8 HIP tensor {tuple(frames_u8.shape)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if not packed_pixels(out):
-        raise L.SpkError(f"out: pixels must be packed and rows / frames must not overlap, got strides {out.stride()}")
-    y0, x0, boxes = _origins(origins, x.device, "frames_paste_u8")
-    if copy:
-        out.copy_(frames_u8)
+    _PACKED.on_device(frames_u8)
+    out, where, fill = _PACKED.target(frames_u8, out, N, H, W, x.device, what)
+    y0, x0, boxes = _origins(origins, x.device, what)
+    fill()
     tables, ay, ax = _paste_tables(Hs, Ws, h, w, feather, x.device)
-    L.check(L.lib().spk_frames_paste_u8(xp, N, Hs, Ws, out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), H, W, h, w, y0, x0,
-                                        _ptr(boxes), swap, *tables, ay, ax, lo, k, L.stream_ptr()), "spk_frames_paste_u8")
+    L.check(L.lib().spk_frames_paste_u8(xp, N, Hs, Ws, *where, H, W, h, w, y0, x0, _ptr(boxes), swap, *tables, ay, ax, lo, k, L.stream_ptr()),
+            "spk_frames_paste_u8")
     return out
 
 
@@ -338,6 +376,21 @@ def _sim_on(rows, device, what):                                          # host
     return rows
 
 
+def _from_aligned(fmt, what, frames, size, sim, channel_order, mean, std, **standard):
+    """``frames_from_u8_aligned`` / ``frames_from_nv12_aligned``: the host checks in one order, then the device and the one launch"""
+    frames, N, H, W = fmt.shaped(frames, None, what)
+    Hout, Wout = _out_size(size, what)
+    colour = (_channel_swap(channel_order), *fmt.standard(**standard))
+    scale, shift = _affine(mean, std, what)
+    rows = parse_sim(sim, N, f"{what}: sim")
+    held, where = fmt.read(frames, what)
+    rows = _sim_on(rows, held.device, what)
+    out = torch.empty((N, 3, Hout, Wout), device=held.device, dtype=torch.float32)
+    L.check(getattr(L.lib(), fmt.way_in)(*where, N, H, W, rows.data_ptr(), *colour, out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()),
+            fmt.way_in)
+    return out
+
+
 def frames_from_u8_aligned(frames_u8, size, sim, *, channel_order="rgb", mean=0.5, std=0.5):
     """uint8 HWC video frames -> the network's input through a similarity transform PER FRAME, one launch
     (``spk_frames_u8_to_f32_sim``): the crop of frame ``n`` is the square (rectangle) ``sim[n]`` maps the ``size`` network image
@@ -348,26 +401,7 @@ def frames_from_u8_aligned(frames_u8, size, sim, *, channel_order="rgb", mean=0.
     sequence / CPU tensor ``[N,4]``, checked on the host (``ValueError`` for a row that is not finite or has a scale outside
     [1/16, 16]) and uploaded once; or a device float32 ``[N,4]`` tensor a tracker left there, not read on the host -- an invalid
     row gives a frame of ``-mean / std``.  -> float32 [N,3,size,size]."""
-    what = "frames_from_u8_aligned"
-    if frames_u8.dim() == 3:
-        frames_u8 = frames_u8.unsqueeze(0)
-    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
-        raise ValueError(f"{what}: frames must be [N,H,W,3], got {tuple(frames_u8.shape)}")
-    Hout, Wout = _out_size(size, what)
-    swap = _channel_swap(channel_order)
-    scale, shift = _affine(mean, std, what)
-    rows = parse_sim(sim, frames_u8.size(0), f"{what}: sim")
-    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
-        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
-    N, H, W, _ = frames_u8.shape
-    if frames_u8.stride(3) != 1 or frames_u8.stride(2) != 3 or frames_u8.stride(1) < 3 * W or (N > 1 and frames_u8.stride(0) < 0):
-        frames_u8 = frames_u8.contiguous()
-    rows = _sim_on(rows, frames_u8.device, what)
-    out = torch.empty((N, 3, Hout, Wout), device=frames_u8.device, dtype=torch.float32)
-    L.check(L.lib().spk_frames_u8_to_f32_sim(frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), N, H, W,
-                                             rows.data_ptr(), swap, out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()),
-            "spk_frames_u8_to_f32_sim")
-    return out
+    return _from_aligned(_PACKED, "frames_from_u8_aligned", frames_u8, size, sim, channel_order, mean, std)
 
 
 def _check_matte(matte, N, Hs, Ws, what):
@@ -398,26 +432,33 @@ def _there(t, device, name, what):                                        # a ch
     return t
 
 
-def _aligned_paste_args(what, x, frames_u8, sim, feather, value_range, channel_order, matte=None, colour=None):
-    """What the aligned paste and its statistics check alike, in one order: -> ``(head, rows, tail, matte_args, colour)``: the
-    arguments of an entry point before the frames' pointer and strides, the device rows (the caller holds them until its launch
-    is queued), the arguments after the rows' pointer, the two matte arguments and the colour rows."""
+def _aligned_args(fmt, what, x, frames, sim, feather, value_range, matte=None, colour=None, **order):
+    """What the aligned paste and its statistics check alike for every pixel format ``fmt``, in one order:
+    -> ``(head, frames, (H, W), rows, tail, matte_args, colour)``: the arguments of an entry point before the frames, the frames as
+    ``fmt`` opened them, their size, the device rows (the caller holds them until its launch is queued), the arguments after the
+    rows' pointer, the two matte arguments and the colour rows."""
     _check_chw(x, what)
-    if frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != x.size(0):
-        raise ValueError(f"{what}: frames must be [{x.size(0)},H,W,3], got {tuple(frames_u8.shape)}")
-    swap = _channel_swap(channel_order)
-    lo, k = quant_range(value_range)
-    feather = check_feather(feather, what)
     N, _, Hs, Ws = x.shape
+    frames, _, H, W = fmt.shaped(frames, N, what)
+    colour_args, lo, k = fmt.quantised(value_range, **order)
+    feather = check_feather(feather, what)
     rows = parse_sim(sim, N, f"{what}: sim")
     matte, matte_frames = _check_matte(matte, N, Hs, Ws, what)
     colour = _check_colour(colour, N, what)
     xp = L.dptr(x, "x")
-    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
-        raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames_u8.dtype} on {frames_u8.device} (no CPU path)")
+    fmt.on_device(frames)
     matte, colour = _there(matte, x.device, "matte", what), _there(colour, x.device, "colour", what)
     rows = _sim_on(rows, x.device, what)
-    return (xp, N, Hs, Ws), rows, (swap, feather, lo, k), (_ptr(matte), matte_frames), colour
+    return (xp, N, Hs, Ws), frames, (H, W), rows, (*colour_args, feather, lo, k), (_ptr(matte), matte_frames), colour
+
+
+def _paste_aligned(fmt, what, x, frames, sim, feather, value_range, out, matte, colour, **order):
+    head, frames, (H, W), rows, tail, matte_args, colour = _aligned_args(fmt, what, x, frames, sim, feather, value_range, matte, colour, **order)
+    out, where, fill = fmt.target(frames, out, head[1], H, W, x.device, what)
+    fill()
+    entry, blend = fmt.blend(matte_args, colour)
+    L.check(getattr(L.lib(), entry)(*head, *where, H, W, rows.data_ptr(), *tail, *blend, L.stream_ptr()), entry)
+    return out
 
 
 def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1), channel_order="rgb", out=None, matte=None, colour=None):
@@ -435,25 +476,7 @@ def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1)
     is a device float32 ``[N,3,2]`` tensor of rows ``(gain, offset)`` per frame and channel of ``x``, applied to the quantised
     value in front of the blend (``paste_colour_match`` makes them; a row that is not finite counts as ``(1, 0)``).  Without
     both, the call is the one it always was.  -> uint8 [N,H,W,3]."""
-    what = "frames_paste_u8_aligned"
-    head, rows, tail, matte_args, colour = _aligned_paste_args(what, x, frames_u8, sim, feather, value_range, channel_order, matte, colour)
-    N, H, W = head[1], frames_u8.size(1), frames_u8.size(2)
-    copy = out is not None and out is not frames_u8 and out.data_ptr() != frames_u8.data_ptr()
-    if out is None:
-        out = frames_u8.clone(memory_format=torch.contiguous_format)
-    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames_u8.shape):
-        raise L.SpkError(f"out: expected a uint8 HIP tensor {tuple(frames_u8.shape)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if not packed_pixels(out):
-        raise L.SpkError(f"out: pixels must be packed and rows / frames must not overlap, got strides {out.stride()}")
-    if copy:
-        out.copy_(frames_u8)
-    where = (out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), H, W, rows.data_ptr())
-    if matte is None and colour is None:
-        L.check(L.lib().spk_frames_paste_u8_sim(*head, *where, *tail, L.stream_ptr()), "spk_frames_paste_u8_sim")
-    else:
-        L.check(L.lib().spk_frames_paste_u8_sim_blend(*head, *where, *tail, *matte_args, _ptr(colour), L.stream_ptr()),
-                "spk_frames_paste_u8_sim_blend")
-    return out
+    return _paste_aligned(_PACKED, "frames_paste_u8_aligned", x, frames_u8, sim, feather, value_range, out, matte, colour, channel_order=channel_order)
 
 
 COLOUR_SUMS = 13                                                          # S0, then (Sq, Sqq, Sb, Sbb) per network channel
@@ -485,17 +508,16 @@ def _stat_out(out, shape, dtype, device):                                 # what
     return out
 
 
-def _colour_statistics(entry, params, shape, dtype, what, x, frames_u8, sim, matte, feather, value_range, channel_order, out):
-    """What ``paste_colour_match`` and ``paste_colour_sums`` share -- the checks, the background, ``out=``, the workspace and the call
-    of ``entry``, whose arguments differ in ``params`` (in front of the output pointer) alone"""
-    head, rows, tail, matte_args, _ = _aligned_paste_args(what, x, frames_u8, sim, feather, value_range, channel_order, matte)
-    N, H, W = head[1], frames_u8.size(1), frames_u8.size(2)
-    if not packed_pixels(frames_u8):
-        frames_u8 = frames_u8.contiguous()
-    out = _stat_out(out, (N, *shape), dtype, x.device)
-    ws = _colour_workspace(x.device, N)
-    L.check(getattr(L.lib(), entry)(*head, frames_u8.data_ptr(), frames_u8.stride(0) if N > 1 else 0, frames_u8.stride(1), H, W, rows.data_ptr(),
-                                    *tail, *matte_args, *params, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, L.stream_ptr()), entry)
+def _colour_statistics(fmt, params, what, x, frames, sim, matte, feather, value_range, out, **order):
+    """What the four statistics launchers share -- the checks, the background, ``out=``, the workspace and the call of the entry point
+    of ``fmt``: the rows of the match with its three ``params`` (in front of the output pointer), the sums without (``None``)"""
+    entry, shape, dtype = (fmt.sums, (COLOUR_SUMS,), torch.float64) if params is None else (fmt.match, (3, 2), torch.float32)
+    head, frames, (H, W), rows, tail, matte_args, _ = _aligned_args(fmt, what, x, frames, sim, feather, value_range, matte, **order)
+    held, where = fmt.read(frames, what, disjoint=True)
+    out = _stat_out(out, (head[1], *shape), dtype, x.device)
+    ws = _colour_workspace(x.device, head[1])
+    L.check(getattr(L.lib(), entry)(*head, *where, H, W, rows.data_ptr(), *tail, *matte_args, *(params or ()), out.data_ptr(), ws.data_ptr(),
+                                    ws.numel() * 8, L.stream_ptr()), entry)
     return out
 
 
@@ -513,8 +535,7 @@ def paste_colour_match(x, frames_u8, sim, *, matte=None, feather=0, value_range=
     tensor to write.  -> device float32 ``[N,3,2]``."""
     what = "paste_colour_match"
     params = _check_match_params(what, max_gain, min_sigma, min_weight)
-    return _colour_statistics("spk_paste_colour_match_sim", params, (3, 2), torch.float32, what, x, frames_u8, sim, matte, feather, value_range,
-                              channel_order, out)
+    return _colour_statistics(_PACKED, params, what, x, frames_u8, sim, matte, feather, value_range, out, channel_order=channel_order)
 
 
 def paste_colour_sums(x, frames_u8, sim, *, matte=None, feather=0, value_range=(-1, 1), channel_order="rgb", out=None):
@@ -524,8 +545,7 @@ def paste_colour_sums(x, frames_u8, sim, *, matte=None, feather=0, value_range=(
     row formula, which ``colour_rows_from_sums`` takes -- with ``radius=0`` it turns these sums into exactly ``paste_colour_match``'s
     rows, with a radius it pools them over neighbouring frames first.  ``out``: a contiguous device float64 ``[N,13]`` tensor to
     write, for instance the slice ``[t0:t1]`` of a clip-long ``[T,13]`` tensor.  -> device float64 ``[N,13]``."""
-    return _colour_statistics("spk_paste_colour_sums_sim", (), (COLOUR_SUMS,), torch.float64, "paste_colour_sums", x, frames_u8, sim, matte,
-                              feather, value_range, channel_order, out)
+    return _colour_statistics(_PACKED, None, "paste_colour_sums", x, frames_u8, sim, matte, feather, value_range, out, channel_order=channel_order)
 
 
 def colour_rows_from_sums(sums, radius=0, sigma=None, *, start=0, stop=None, max_gain=2.0, min_sigma=1.0, min_weight=16.0, out=None):
@@ -1095,15 +1115,54 @@ def frames_from_nv12(nv12, size, *, crop=None, channel_order="rgb", mean=0.5, st
     return out
 
 
-def _nv12_out(out, N, H, W, device, what):
-    """The surface a launcher writes: ``out`` (what ``nv12_planes`` takes) or a fresh packed ``[N, 3H/2, W]`` buffer.
-    -> ``(result, y, uv)``."""
-    if out is None:
-        out = torch.empty((N, 3 * H // 2, W), device=device, dtype=torch.uint8)
-    y, uv = nv12_planes(out)
-    if tuple(y.shape) != (N, H, W):
-        raise L.SpkError(f"{what}: out must hold {N} NV12 frames of {H} x {W}, got planes {tuple(y.shape)}")
-    return out, y, uv
+class _Surfaces:
+    """``_Packed`` for NV12: the frames of a call as what ``nv12_planes`` takes (csrc/frame_nv12.hip, csrc/frame_sim_nv12.hip)."""
+    way_in, paste = "spk_frames_nv12_to_f32_sim", "spk_frames_paste_nv12_sim"
+    sums, match = "spk_paste_colour_sums_nv12_sim", "spk_paste_colour_match_nv12_sim"
+
+    def shaped(self, nv12, N, what):                                      # -> ((y, uv), N, H, W)
+        y, uv = nv12_planes(nv12)
+        if N is not None and y.size(0) != N:
+            raise ValueError(f"{what}: {N} generated frames, {y.size(0)} NV12 frames")
+        return ((y, uv), *y.shape)
+
+    def on_device(self, planes):
+        if not planes[0].is_cuda:
+            raise L.SpkError(f"frames: expected uint8 HIP tensors, got {planes[0].dtype} on {planes[0].device} (no CPU path)")
+
+    def read(self, planes, what, disjoint=False):                         # always in place; -> (the Y plane, the two pointers with their strides)
+        y, uv = planes
+        ys, us = nv12_strides(y, uv, what, written=False)
+        return y, (y.data_ptr(), *ys, uv.data_ptr(), *us)
+
+    def target(self, planes, out, N, H, W, device, what):
+        """The surface a launcher writes: ``out`` (what ``nv12_planes`` takes) or a fresh packed ``[N, 3H/2, W]`` buffer; ``fill()``
+        copies each plane of ``planes`` that is not the result's own"""
+        if out is None:
+            out = torch.empty((N, 3 * H // 2, W), device=device, dtype=torch.uint8)
+        y, uv = nv12_planes(out)
+        if tuple(y.shape) != (N, H, W):
+            raise L.SpkError(f"{what}: out must hold {N} NV12 frames of {H} x {W}, got planes {tuple(y.shape)}")
+        ys, us = nv12_strides(y, uv, f"{what}: out", written=True)
+
+        def fill():
+            for dst, src in ((y, planes[0]), (uv, planes[1])):
+                if dst.data_ptr() != src.data_ptr() or dst.stride() != src.stride():
+                    dst.copy_(src)
+        return out, (y.data_ptr(), *ys, uv.data_ptr(), *us), fill
+
+    def standard(self, standard="bt601", full_range=False):
+        return yuv_standard(standard, full_range)
+
+    def quantised(self, value_range, standard="bt601", full_range=False):
+        lo, k = quant_range(value_range)
+        return yuv_standard(standard, full_range), lo, k
+
+    def blend(self, matte_args, colour):                                  # one entry point, with or without matte and colour rows
+        return self.paste, (*matte_args, _ptr(colour))
+
+
+_SURFACES = _Surfaces()
 
 
 def frames_to_nv12(x, *, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
@@ -1118,10 +1177,8 @@ def frames_to_nv12(x, *, value_range=(-1, 1), standard="bt601", full_range=False
     lo, k = quant_range(value_range)
     code, full = yuv_standard(standard, full_range)
     xp = L.dptr(x, "x")
-    out, y, uv = _nv12_out(out, N, H, W, x.device, "frames_to_nv12")
-    ys, us = nv12_strides(y, uv, "frames_to_nv12: out", written=True)
-    L.check(L.lib().spk_frames_f32_to_nv12(xp, N, H, W, y.data_ptr(), *ys, uv.data_ptr(), *us, code, full, lo, k, L.stream_ptr()),
-            "spk_frames_f32_to_nv12")
+    out, where, _ = _SURFACES.target(None, out, N, H, W, x.device, "frames_to_nv12")
+    L.check(L.lib().spk_frames_f32_to_nv12(xp, N, H, W, *where, code, full, lo, k, L.stream_ptr()), "spk_frames_f32_to_nv12")
     return out
 
 
@@ -1133,29 +1190,21 @@ def frames_paste_nv12(x, nv12, box, *, feather=0, value_range=(-1, 1), standard=
     ``parse_boxes``; origins may be odd; box pixels outside the frame are skipped.  ``out=None``: the result is a packed clone of
     ``nv12``; ``out=nv12`` (the same tensor, or the same pair of planes): pasted in place through its strides; another ``out``
     first receives a copy.  -> uint8 [N, 3H/2, W], or ``out``."""
-    _check_chw(x, "frames_paste_nv12")
-    sy, suv = nv12_planes(nv12)
+    what = "frames_paste_nv12"
+    _check_chw(x, what)
     N, _, Hs, Ws = x.shape
-    if sy.size(0) != N:
-        raise ValueError(f"frames_paste_nv12: {N} generated frames, {sy.size(0)} NV12 frames")
-    H, W = sy.shape[1:]
-    lo, k = quant_range(value_range)
-    code, full = yuv_standard(standard, full_range)
-    feather = check_feather(feather, "frames_paste_nv12")
-    origins, h, w = parse_boxes(box, N, H, W, "frames_paste_nv12: box", inside=False)
+    planes, _, H, W = _SURFACES.shaped(nv12, N, what)
+    (code, full), lo, k = _SURFACES.quantised(value_range, standard, full_range)
+    feather = check_feather(feather, what)
+    origins, h, w = parse_boxes(box, N, H, W, f"{what}: box", inside=False)
     xp = L.dptr(x, "x")
-    if not sy.is_cuda:
-        raise L.SpkError(f"frames: expected uint8 HIP tensors, got {sy.dtype} on {sy.device} (no CPU path)")
-    out, y, uv = _nv12_out(out, N, H, W, x.device, "frames_paste_nv12")
-    ys, us = nv12_strides(y, uv, "frames_paste_nv12: out", written=True)
-    y0, x0, boxes = _origins(origins, x.device, "frames_paste_nv12")
-    if y.data_ptr() != sy.data_ptr() or y.stride() != sy.stride():
-        y.copy_(sy)
-    if uv.data_ptr() != suv.data_ptr() or uv.stride() != suv.stride():
-        uv.copy_(suv)
+    _SURFACES.on_device(planes)
+    out, where, fill = _SURFACES.target(planes, out, N, H, W, x.device, what)
+    y0, x0, boxes = _origins(origins, x.device, what)
+    fill()
     tables, ay, ax = _paste_tables(Hs, Ws, h, w, feather, x.device)
-    L.check(L.lib().spk_frames_paste_nv12(xp, N, Hs, Ws, y.data_ptr(), *ys, uv.data_ptr(), *us, H, W, h, w, y0, x0, _ptr(boxes), code, full,
-                                          *tables, ay, ax, lo, k, L.stream_ptr()), "spk_frames_paste_nv12")
+    L.check(L.lib().spk_frames_paste_nv12(xp, N, Hs, Ws, *where, H, W, h, w, y0, x0, _ptr(boxes), code, full, *tables, ay, ax, lo, k,
+                                          L.stream_ptr()), "spk_frames_paste_nv12")
     return out
 
 
@@ -1168,43 +1217,7 @@ def frames_from_nv12_aligned(nv12, size, sim, *, channel_order="rgb", mean=0.5, 
     so is every output of a frame whose device row is invalid.  ``nv12``: what ``nv12_planes`` takes, on the device, read in place
     through its strides; ``sim``: the two forms of ``parse_sim``; ``channel_order``: the plane order of the result, as
     ``frames_from_nv12``.  -> float32 [N,3,size,size]."""
-    what = "frames_from_nv12_aligned"
-    y, uv = nv12_planes(nv12)
-    N, H, W = y.shape
-    Hout, Wout = _out_size(size, what)
-    swap = _channel_swap(channel_order)
-    code, full = yuv_standard(standard, full_range)
-    scale, shift = _affine(mean, std, what)
-    rows = parse_sim(sim, N, f"{what}: sim")
-    ys, us = nv12_strides(y, uv, what, written=False)
-    rows = _sim_on(rows, y.device, what)
-    out = torch.empty((N, 3, Hout, Wout), device=y.device, dtype=torch.float32)
-    L.check(L.lib().spk_frames_nv12_to_f32_sim(y.data_ptr(), *ys, uv.data_ptr(), *us, N, H, W, rows.data_ptr(), swap, code, full, out.data_ptr(),
-                                               Hout, Wout, *scale, *shift, L.stream_ptr()), "spk_frames_nv12_to_f32_sim")
-    return out
-
-
-def _aligned_nv12_args(what, x, nv12, sim, feather, value_range, standard, full_range, matte=None, colour=None):
-    """What the aligned NV12 paste and its statistics check alike, in the order of ``_aligned_paste_args``:
-    -> ``(head, planes, rows, tail, matte_args, colour)``: the arguments of an entry point before the surfaces, the source planes,
-    the device rows, the arguments after the rows' pointer, the two matte arguments and the colour rows."""
-    _check_chw(x, what)
-    sy, suv = nv12_planes(nv12)
-    N, _, Hs, Ws = x.shape
-    if sy.size(0) != N:
-        raise ValueError(f"{what}: {N} generated frames, {sy.size(0)} NV12 frames")
-    lo, k = quant_range(value_range)
-    code, full = yuv_standard(standard, full_range)
-    feather = check_feather(feather, what)
-    rows = parse_sim(sim, N, f"{what}: sim")
-    matte, matte_frames = _check_matte(matte, N, Hs, Ws, what)
-    colour = _check_colour(colour, N, what)
-    xp = L.dptr(x, "x")
-    if not sy.is_cuda:
-        raise L.SpkError(f"frames: expected uint8 HIP tensors, got {sy.dtype} on {sy.device} (no CPU path)")
-    matte, colour = _there(matte, x.device, "matte", what), _there(colour, x.device, "colour", what)
-    rows = _sim_on(rows, x.device, what)
-    return (xp, N, Hs, Ws), (sy, suv), rows, (code, full, feather, lo, k), (_ptr(matte), matte_frames), colour
+    return _from_aligned(_SURFACES, "frames_from_nv12_aligned", nv12, size, sim, channel_order, mean, std, standard=standard, full_range=full_range)
 
 
 def frames_paste_nv12_aligned(x, nv12, sim, *, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None, matte=None,
@@ -1217,31 +1230,8 @@ def frames_paste_nv12_aligned(x, nv12, sim, *, feather=0, value_range=(-1, 1), s
     of the block's region pixels over the sample underneath.  Every byte outside the region's pixels and blocks is left as it is; a
     device row that is invalid leaves its frame untouched.  ``nv12``, ``out``: as ``frames_paste_nv12`` (``out=nv12`` pastes in
     place).  -> uint8 [N, 3H/2, W], or ``out``."""
-    what = "frames_paste_nv12_aligned"
-    head, (sy, suv), rows, tail, matte_args, colour = _aligned_nv12_args(what, x, nv12, sim, feather, value_range, standard, full_range, matte,
-                                                                         colour)
-    N, (H, W) = head[1], sy.shape[1:]
-    out, y, uv = _nv12_out(out, N, H, W, x.device, what)
-    ys, us = nv12_strides(y, uv, f"{what}: out", written=True)
-    if y.data_ptr() != sy.data_ptr() or y.stride() != sy.stride():
-        y.copy_(sy)
-    if uv.data_ptr() != suv.data_ptr() or uv.stride() != suv.stride():
-        uv.copy_(suv)
-    L.check(L.lib().spk_frames_paste_nv12_sim(*head, y.data_ptr(), *ys, uv.data_ptr(), *us, H, W, rows.data_ptr(), *tail, *matte_args,
-                                              _ptr(colour), L.stream_ptr()), "spk_frames_paste_nv12_sim")
-    return out
-
-
-def _colour_statistics_nv12(entry, params, shape, dtype, what, x, nv12, sim, matte, feather, value_range, standard, full_range, out):
-    """``_colour_statistics`` for a surface background: what ``paste_colour_match_nv12`` and ``paste_colour_sums_nv12`` share"""
-    head, (y, uv), rows, tail, matte_args, _ = _aligned_nv12_args(what, x, nv12, sim, feather, value_range, standard, full_range, matte)
-    N, (H, W) = head[1], y.shape[1:]
-    ys, us = nv12_strides(y, uv, what, written=False)
-    out = _stat_out(out, (N, *shape), dtype, x.device)
-    ws = _colour_workspace(x.device, N)
-    L.check(getattr(L.lib(), entry)(*head, y.data_ptr(), *ys, uv.data_ptr(), *us, H, W, rows.data_ptr(), *tail, *matte_args, *params,
-                                    out.data_ptr(), ws.data_ptr(), ws.numel() * 8, L.stream_ptr()), entry)
-    return out
+    return _paste_aligned(_SURFACES, "frames_paste_nv12_aligned", x, nv12, sim, feather, value_range, out, matte, colour, standard=standard,
+                          full_range=full_range)
 
 
 def paste_colour_match_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, max_gain=2.0,
@@ -1254,8 +1244,7 @@ def paste_colour_match_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=
     -> device float32 ``[N,3,2]``."""
     what = "paste_colour_match_nv12"
     params = _check_match_params(what, max_gain, min_sigma, min_weight)
-    return _colour_statistics_nv12("spk_paste_colour_match_nv12_sim", params, (3, 2), torch.float32, what, x, nv12, sim, matte, feather,
-                                   value_range, standard, full_range, out)
+    return _colour_statistics(_SURFACES, params, what, x, nv12, sim, matte, feather, value_range, out, standard=standard, full_range=full_range)
 
 
 def paste_colour_sums_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
@@ -1263,8 +1252,19 @@ def paste_colour_sums_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=(
     ``paste_colour_match_nv12`` makes its rows from, bit for bit, per network channel R, G, B -- so ``colour_rows_from_sums`` serves
     both pixel formats.  ``out``: a contiguous device float64 ``[N,13]`` tensor to write (a slice of a clip-long one).
     -> device float64 ``[N,13]``."""
-    return _colour_statistics_nv12("spk_paste_colour_sums_nv12_sim", (), (COLOUR_SUMS,), torch.float64, "paste_colour_sums_nv12", x, nv12, sim,
-                                   matte, feather, value_range, standard, full_range, out)
+    return _colour_statistics(_SURFACES, None, "paste_colour_sums_nv12", x, nv12, sim, matte, feather, value_range, out, standard=standard,
+                              full_range=full_range)
+
+
+def generated_row_scale(size, Ws, device):
+    """The network image has ``size`` pixels where a generated one is ``Ws`` wide: -> the factor of a row ``(a, c, tx, ty)`` that maps
+    the generated image into the frames, a float32 ``[4]`` tensor on ``device`` made in fp32, or None when it is 1"""
+    k = size[1] / Ws
+    return None if k == 1 else torch.tensor([k, k, 1.0, 1.0], dtype=torch.float32).to(device)
+
+
+def chunk_matte(matte, t0, t1):                                           # a clip's matte for frames [t0, t1): a per-frame one is sliced
+    return matte[t0:t1] if matte is not None and matte.dim() == 3 else matte
 
 
 class Aligned:
@@ -1288,8 +1288,8 @@ class Aligned:
         if Hs * self.size[1] != Ws * self.size[0]:
             raise ValueError(f"reenact_video: align needs generated frames in the shape of the network input, got {Hs} x {Ws} for {self.size}")
         if Ws not in self._generated:
-            k = self.size[1] / Ws
-            self._generated[Ws] = self.rows if k == 1 else self.rows * torch.tensor([k, k, 1.0, 1.0], dtype=torch.float32).to(self.rows.device)
+            scale = generated_row_scale(self.size, Ws, self.rows.device)
+            self._generated[Ws] = self.rows if scale is None else self.rows * scale
         return Aligned(self._generated[Ws][t0:t1], (Hs, Ws))
 
 
@@ -1321,8 +1321,7 @@ class Rgb24:
         if isinstance(box, Aligned):
             blend = {}
             if matte is not None or colour_match:                         # the statistics read the background before the paste writes it
-                if matte is not None and matte.dim() == 3:
-                    matte = matte[t0:t1]
+                matte = chunk_matte(matte, t0, t1)
                 rows = paste_colour_match(y, frames[t0:t1], box.rows, matte=matte, feather=feather, **self.args) if colour_match else None
                 blend = dict(matte=matte, colour=rows)
             frames_paste_u8_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], **self.args, **blend)
@@ -1331,14 +1330,11 @@ class Rgb24:
 
     # colour_smooth > 0: the statistics of a chunk now, its paste once the sums of its whole window exist (``box``: an ``Aligned``)
     def colour_sums(self, y, frames, t0, t1, box, feather, matte, sums):
-        if matte is not None and matte.dim() == 3:
-            matte = matte[t0:t1]
-        paste_colour_sums(y, frames[t0:t1], box.rows, matte=matte, feather=feather, out=sums[t0:t1], **self.args)
+        paste_colour_sums(y, frames[t0:t1], box.rows, matte=chunk_matte(matte, t0, t1), feather=feather, out=sums[t0:t1], **self.args)
 
     def paste_matched(self, y, frames, t0, t1, box, feather, matte, colour):
-        if matte is not None and matte.dim() == 3:
-            matte = matte[t0:t1]
-        frames_paste_u8_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], matte=matte, colour=colour, **self.args)
+        frames_paste_u8_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], matte=chunk_matte(matte, t0, t1), colour=colour,
+                                **self.args)
 
 
 class Nv12:
@@ -1358,10 +1354,9 @@ class Nv12:
         return frames_from_nv12(frames, size, crop=crop, **self.args)
 
     def clone(self, planes):                                              # one clone: a packed surface per frame
-        out, y, uv = _nv12_out(None, *planes[0].shape, planes[0].device, "reenact_video")
-        y.copy_(planes[0])
-        uv.copy_(planes[1])
-        return out, (y, uv)
+        out, _, fill = _SURFACES.target(planes, None, *planes[0].shape, planes[0].device, "reenact_video")
+        fill()
+        return out, nv12_planes(out)
 
     def paste(self, y, planes, t0, t1, box, feather):
         part = (planes[0][t0:t1], planes[1][t0:t1])

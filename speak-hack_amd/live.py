@@ -95,14 +95,12 @@ class LiveSession:
 
     def _for_generated(self, Hs, Ws):
         """The network image has ``size`` pixels where the generated one has ``Hs x Ws``: -> (the factor of a row's ``(a, c)`` as a
-        device tensor, or None when it is 1; the template's contour in generated pixels), made once per session, in fp32 as
-        ``reenact_video`` makes them"""
+        device tensor, or None when it is 1; the template's contour in generated pixels), made once per session; the factor is
+        ``Aligned.chunk``'s"""
         if Hs * self.size[1] != Ws * self.size[0]:
             raise ValueError(f"live: generated frames must have the shape of the network input, got {Hs} x {Ws} for {self.size}")
         if Ws not in self._generated:
-            k = self.size[1] / Ws
-            scale = None if k == 1 else torch.tensor([k, k, 1.0, 1.0], dtype=torch.float32).to(self.device)
-            fallback = None
+            scale, fallback = FR.generated_row_scale(self.size, Ws, self.device), None
             if self.contour is not None:
                 FR._matte_size((Hs, Ws), "live")
                 points = self.template if self._template_host is None else self._template_host

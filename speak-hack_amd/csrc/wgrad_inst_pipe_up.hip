@@ -1,5 +1,5 @@
 // Weight gradient, 3x3 stride 1 on 16 x 4 tiles: the pipelined form (SPK_WGRAD_PIPE) and the upsample-folded form (SPK_WGRAD_UP).
-#include "wgrad_mfma_f32.hpp"
+#include "wgrad_tile3x3.hpp"
 
 using namespace spkwg;
 
@@ -14,22 +14,15 @@ namespace {
 // an immediate and a staging piece is a clamp, a load or store and a select -- the per-piece index arithmetic is what
 // made an earlier pipelined attempt slower than the serial kernel.
 __global__ __launch_bounds__(256) void wgrad3x3_pipe_kernel(const WgradArgs p) {
-    constexpr int TAPS = 9, CI_T = 64, CO_T = 64, TW = WP_TW, PW = WP_PW, PLANE = WP_PLANE;
-    constexpr int GPITCH = WP_GPITCH, XPITCH = WP_XPITCH, BUF = WP_BUF;
-    constexpr int NGL = 16, NXL = 32, STEPS = 32, PPS = (NGL + NXL) / (STEPS / 2);   // 3 staging pieces per k-step
+    using SH = WideShapeT<16>;                 // the tile images of the wide form at TW = 16 (idle lanes: its dump slot)
+    constexpr int TAPS = WG_TAPS, CI_T = SH::CI_T, CO_T = SH::CO_T, TW = SH::TW, PW = SH::PW, PLANE = SH::PLANE;
+    constexpr int GPITCH = SH::GPITCH, XPITCH = SH::XPITCH, BUF = SH::BUF;
+    constexpr int NGL = 16, NXL = 32, PPS = (NGL + NXL) / WG_HS;                     // 3 staging pieces per k-step
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l32 = lane & 31;
-    const int wco = wave & 1, wci = wave >> 1;
-
-    const int co0 = blockIdx.x * CO_T;
-    const int grp = co0 / p.Cout;
-    const int co_end = (grp + 1) * p.Cout;
-    const int cx0 = grp * p.gin;
-    const int ci0 = blockIdx.y * CI_T;
-    const int nci = min(CI_T, p.Cin - ci0);
+    const WgBlock bk = wg_block<CO_T, CI_T>(p);
+    const int tid = bk.tid, wave = bk.wave, half = bk.half, l32 = bk.l32, wco = wave & 1, wci = wave >> 1;
+    const int co0 = bk.co0, co_end = bk.co_end, cx0 = bk.cx0, ci0 = bk.ci0, nci = bk.nci;
     const size_t HW = (size_t)p.H * p.W, src_plane = (size_t)p.Hs * p.Ws;
 
     // staging roles.  Gradient tile: thread -> pixel tid % 64, output channels tid / 64 + 4 i.  Input tile: thread -> plane
@@ -43,10 +36,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_pipe_kernel(const WgradArgs p) {
     const int x_dst_step = xpos_ok ? XPITCH : 0;
 
     f32x16 acc[TAPS];
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    wg_zero(acc);
 
     float gg[NGL], xg[NXL];
     bool g_ok = false, x_ok = false;          // the tile being staged: this thread's pixel / plane position is inside the image
@@ -55,14 +45,12 @@ __global__ __launch_bounds__(256) void wgrad3x3_pipe_kernel(const WgradArgs p) {
 
     // tile -> pointers and validity of this thread's elements (elements outside the image read the tensor's first float)
     auto aim = [&](int tile) {
-        const int tx = tile % p.tiles_x;
-        const int q = tile / p.tiles_x;
-        const int ty = q % p.tiles_y, b = q / p.tiles_y;
-        const int yy = ty * 4 + gpy, xx = tx * TW + gpx;
+        const WgTile o = wg_tile_origin<TW, 4>(p, tile);
+        const int b = o.b, yy = o.y0 + gpy, xx = o.x0 + gpx;
         const bool live = tile < p.n_tiles;
         g_ok = live && yy < p.H && xx < p.W;
         g_ptr = p.g + (g_ok ? (size_t)b * p.Cy * HW + (size_t)yy * p.W + xx : 0);
-        const int uy = ty * 4 + xr - 1, ux = tx * TW + xc - 1;
+        const int uy = o.y0 + xr - 1, ux = o.x0 + xc - 1;
         x_ok = live && xpos_ok && uy >= 0 && uy < p.Hs && ux >= 0 && ux < p.Ws;
         x_ptr = p.x + (x_ok ? ((size_t)b * p.Cx + cx0 + ci0) * src_plane + (size_t)uy * p.Ws + ux : 0);
     };
@@ -89,77 +77,43 @@ __global__ __launch_bounds__(256) void wgrad3x3_pipe_kernel(const WgradArgs p) {
         }
     };
 
+    wg_stage_first<NGL + NXL, NGL + NXL>(p, smem, aim, load_piece, store_piece);
     int tile = blockIdx.z;
     int cur = 0;
-    if (tile < p.n_tiles) {                  // first tile: staged the serial way
-        aim(tile);
-        wg_static_for<0, NGL + NXL>([&](auto j_) { load_piece(j_); });
-        wg_static_for<0, NGL + NXL>([&](auto j_) { store_piece(smem, j_); });
-    }
-    __syncthreads();
 
-    // one tile's 32 k-steps out of buffer `cur`; PIPE: the next tile is staged into the other buffer on the way
-    auto run_tile = [&](auto pipe_) {
-        constexpr bool PIPE = decltype(pipe_)::value;
+    // one tile's 32 k-steps out of buffer `cur`; the next tile is staged into the other buffer on the way: three pieces per k-step,
+    // one staging access behind every third MFMA
+    auto run_tile = [&]() {
         const float* cbuf = smem + cur * BUF;
         float* nbuf = smem + (cur ^ 1) * BUF;
-        const volatile wg_lds_f32* ga = (const volatile wg_lds_f32*)(cbuf + (wco * 32 + l32) * GPITCH + half);              // pixel 2 st + half of this lane's channel row
-        const volatile wg_lds_f32* xb = (const volatile wg_lds_f32*)(cbuf + CO_T * GPITCH + (wci * 32 + l32) * XPITCH + half);
-        float fa[2], fb[2][TAPS];
-#define SPK_WP_FRAG(st_, slot_)                                                                               \
-    {                                                                                                         \
-        constexpr int px_ = (2 * (st_)) & (TW - 1), py_ = (2 * (st_)) >> 4;                                   \
-        fa[slot_] = ga[2 * (st_)];                                                                            \
-        _Pragma("unroll") for (int t = 0; t < TAPS; ++t) fb[slot_][t] = xb[(py_ + t / 3) * PW + px_ + t % 3];  \
-    }
-        SPK_WP_FRAG(0, 0);
-        wg_static_for<0, STEPS>([&](auto s_) {
-            constexpr int st = decltype(s_)::value;
-            if constexpr (PIPE && st == STEPS / 2) __builtin_amdgcn_sched_barrier(0);      // see wgrad3x3_wide_kernel
-            if constexpr (st + 1 < STEPS) SPK_WP_FRAG(st + 1, (st + 1) & 1);
-            if constexpr (PIPE && st < STEPS / 2)
-                wg_static_for<PPS * st, PPS * st + PPS>([&](auto j_) { load_piece(j_); });
-            if constexpr (PIPE && st >= STEPS / 2)
-                wg_static_for<PPS * (st - STEPS / 2), PPS * (st - STEPS / 2) + PPS>([&](auto j_) { store_piece(nbuf, j_); });
-#pragma unroll
-            for (int t = 0; t < TAPS; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[st & 1], fb[st & 1][t], acc[t], 0, 0, 0);
-            // order: next step's fragments, then the MFMAs with one staging access behind every third
-            if constexpr (st + 1 < STEPS) __builtin_amdgcn_sched_group_barrier(0x100, TAPS + 1, 0);
-            if constexpr (PIPE) {
+        wg_run_tile<SH, 1>(wg_grad_row<SH>(cbuf, wco * 32 + l32, half), wg_input_row<SH, 1>(cbuf, wci * 32 + l32, half), acc,
+            [&](auto s_) {
+                constexpr int st = decltype(s_)::value;
+                if constexpr (st < WG_HS) wg_static_for<PPS * st, PPS * st + PPS>([&](auto j_) { load_piece(j_); });
+                else wg_static_for<PPS * (st - WG_HS), PPS * (st - WG_HS) + PPS>([&](auto j_) { store_piece(nbuf, j_); });
+            },
+            [&](auto s_) {
+                constexpr int st = decltype(s_)::value;
+                wg_sched_frag_reads<st>();
 #pragma unroll
                 for (int k = 0; k < PPS; ++k) {
-                    __builtin_amdgcn_sched_group_barrier(0x8, TAPS / PPS, 0);
-                    __builtin_amdgcn_sched_group_barrier(st < STEPS / 2 ? 0x20 : 0x200, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x8, WG_TAPS / PPS, 0);
+                    __builtin_amdgcn_sched_group_barrier(st < WG_HS ? 0x20 : 0x200, 1, 0);
                 }
-            } else {
-                __builtin_amdgcn_sched_group_barrier(0x8, TAPS, 0);
-            }
-        });
-#undef SPK_WP_FRAG
+            });
     };
 
-    // ONE loop body: after the last tile the staging still runs, with every piece masked off (it reads the tensors' first
-    // floats and fills the idle buffer with zeros).  With a second, staging-free copy of the tile for that case the
-    // accumulators cross the if / else merge in VGPRs: 144 v_accvgpr_write before and 144 v_accvgpr_read after EVERY tile's
-    // 288 MFMAs (and twice the code).
+    // the loop of wg_persistent_tiles (one body, see there), written out: through the helper this kernel's tile loop is scheduled
+    // differently
     for (; tile < p.n_tiles; tile += gridDim.z) {
         aim(tile + (int)gridDim.z);
-        run_tile(std::true_type{});
+        run_tile();
         __syncthreads();                      // every wave is done with `cur`, and the other buffer is complete
         cur ^= 1;
     }
 
     // ---- partial block -> slab [slab][co][tap][ci] (ci contiguous: 128-B stores per half wave) ----
-    float* out = p.slabs + (size_t)blockIdx.z * p.Cy * TAPS * p.Cin;
-    const int ci = ci0 + wci * 32 + l32;
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = co0 + wco * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (co < co_end && ci < p.Cin) out[((size_t)co * TAPS + t) * p.Cin + ci] = acc[t][r];
-        }
+    wg_store_slab9(p, acc, co0 + wco * 32, co_end, ci0 + wci * 32 + l32, half);
 }
 
 // ---- 3x3 stride-1 weight gradient of a conv that reads the BILINEAR x2 UPSAMPLING of x (styleganv1.py:624-625) ---------
@@ -184,17 +138,9 @@ __global__ __launch_bounds__(256) void wgrad3x3_up_kernel(const WgradArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const sbuf = smem + 2 * BUF;                  // two source-patch buffers behind the two tile buffers
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l32 = lane & 31;
-    const int wco = wave & 1, wci = wave >> 1;
-
-    const int co0 = blockIdx.x * CO_T;
-    const int grp = co0 / p.Cout;
-    const int co_end = (grp + 1) * p.Cout;
-    const int cx0 = grp * p.gin;
-    const int ci0 = blockIdx.y * CI_T;
-    const int nci = min(CI_T, p.Cin - ci0);
+    const WgBlock bk = wg_block<CO_T, CI_T>(p);
+    const int tid = bk.tid, lane = bk.lane, wave = bk.wave, half = bk.half, l32 = bk.l32, wco = wave & 1, wci = wave >> 1;
+    const int co0 = bk.co0, co_end = bk.co_end, cx0 = bk.cx0, ci0 = bk.ci0, nci = bk.nci;
 
     // ---- staging roles ----
     const int gk = tid & 3, grow = (tid >> 2) & 3;
@@ -216,10 +162,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_up_kernel(const WgradArgs p) {
     const int s_dsth = sc * US_PITCH + rh * US_PW + (sk ? 9 : 0);    // + 2 i US_PW
 
     f32x16 acc[TAPS];
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    wg_zero(acc);
 
     // per-tile state: (g) the gradient tile being staged; (s) the source patch being staged; (i) the tile being interpolated
     f32x4 gq[NG4], sq[2];
@@ -228,14 +171,9 @@ __global__ __launch_bounds__(256) void wgrad3x3_up_kernel(const WgradArgs p) {
     const float* sbase = p.x;
     bool g_ok = false;
     int s_y0 = 0, i_y0 = 0, i_x0 = 0;
-    auto origin = [&](int tile, int& b, int& y0, int& x0) {
-        const int tx = tile % p.tiles_x;
-        const int q = tile / p.tiles_x;
-        b = q / p.tiles_y; y0 = (q % p.tiles_y) * 4; x0 = tx * 16;
-    };
     auto aim_g = [&](int tile) {
-        int b, y0, x0;
-        origin(tile, b, y0, x0);
+        const WgTile o = wg_tile_origin<16, 4>(p, tile);
+        const int b = o.b, y0 = o.y0, x0 = o.x0;
         gbase = p.g + ((size_t)b * p.Cy * p.H + y0) * p.W + x0;
         g_ok = tile < p.n_tiles && y0 + grow < p.H && x0 + 4 * gk < p.W;
         if constexpr (BSC) {
@@ -252,8 +190,8 @@ __global__ __launch_bounds__(256) void wgrad3x3_up_kernel(const WgradArgs p) {
     bool s4_out = false;
     float s_sc = 1.f;                                                 // BSC: s[b, channel] of the patch being staged
     auto aim_s = [&](int tile) {
-        int b, y0, x0;
-        origin(tile, b, y0, x0);
+        const WgTile o = wg_tile_origin<16, 4>(p, tile);
+        const int b = o.b, y0 = o.y0, x0 = o.x0;
         s_y0 = (y0 >> 1) - 1;                                         // first source row of the patch (may be -1)
         s_x0 = x0 >> 1;
         sbase = p.x + ((size_t)b * p.Cx * p.Hs) * p.Ws;
@@ -262,8 +200,8 @@ __global__ __launch_bounds__(256) void wgrad3x3_up_kernel(const WgradArgs p) {
     };
     unsigned i_rows = 0, i_cols = 0;                                  // plane rows / columns inside the x2 image (bit r / bit c)
     auto aim_i = [&](int tile) {
-        int b;
-        origin(tile, b, i_y0, i_x0);
+        const WgTile o = wg_tile_origin<16, 4>(p, tile);
+        i_y0 = o.y0; i_x0 = o.x0;
         i_rows = 0; i_cols = 0;
 #pragma unroll
         for (int r = 0; r < 6; ++r) i_rows |= ((unsigned)(i_y0 - 1 + r) < (unsigned)p.H ? 1u : 0u) << r;
@@ -348,9 +286,10 @@ __global__ __launch_bounds__(256) void wgrad3x3_up_kernel(const WgradArgs p) {
 
     // iteration k computes tile k out of buf[cur]; meanwhile G(k+1) is loaded / stored into the other tile buffer, the plane of
     // tile k+1 is interpolated into it from sbuf[(k+1) & 1], and the source patch of tile k+2 is loaded and stored into
-    // sbuf[k & 1] (whose previous content, the patch of tile k, was last read during iteration k - 1)
-    auto run_tile = [&](auto has1_, auto has2_) {
-        constexpr bool H1 = decltype(has1_)::value, H2 = decltype(has2_)::value;
+    // sbuf[k & 1] (whose previous content, the patch of tile k, was last read during iteration k - 1).
+    // Fragment reads, tile loop and epilogue are those of wgrad_tile3x3.hpp WRITTEN OUT: wg_frag3x3, wg_run_tile /
+    // wg_persistent_tiles and wg_store_slab9 each moved instructions inside this kernel's tile loop.
+    auto run_tile = [&]() {
         const float* cbuf = smem + cur * BUF;
         float* nbuf = smem + (cur ^ 1) * BUF;
         const int s_next = (par ^ 1) * US_FLOATS;                      // patch of tile k+1 (float offset behind sbuf)
@@ -367,20 +306,20 @@ __global__ __launch_bounds__(256) void wgrad3x3_up_kernel(const WgradArgs p) {
         SPK_WU_FRAG(0, 0);
         wg_static_for<0, STEPS>([&](auto s_) {
             constexpr int st = decltype(s_)::value;
-            if constexpr (H1 && st == HS) __builtin_amdgcn_sched_barrier(0);               // see wgrad3x3_wide_kernel
+            if constexpr (st == HS) __builtin_amdgcn_sched_barrier(0);               // see wg_run_tile
             if constexpr (st + 1 < STEPS) SPK_WU_FRAG(st + 1, (st + 1) & 1);
-            if constexpr (H1 && st < NG4) load_g(std::integral_constant<int, st < NG4 ? st : 0>{});
-            if constexpr (H2 && st >= NG4 && st < NG4 + 4) load_s(std::integral_constant<int, (st >= NG4 && st < NG4 + 4) ? st - NG4 : 0>{});
-            if constexpr (H1 && st >= 1 && st <= EPT) interp_write(nbuf, st - 1);
-            if constexpr (H1 && st < EPT) interp_read(s_next, st);
-            if constexpr (H1 && st >= HS) store_g(nbuf, std::integral_constant<int, st >= HS ? st - HS : 0>{});
-            if constexpr (H2 && st >= HS && st < HS + 10) store_s(s_fill, std::integral_constant<int, (st >= HS && st < HS + 10) ? st - HS : 0>{});
+            if constexpr (st < NG4) load_g(std::integral_constant<int, st>{});
+            if constexpr (st >= NG4 && st < NG4 + 4) load_s(std::integral_constant<int, st - NG4>{});
+            if constexpr (st >= 1 && st <= EPT) interp_write(nbuf, st - 1);
+            if constexpr (st < EPT) interp_read(s_next, st);
+            if constexpr (st >= HS) store_g(nbuf, std::integral_constant<int, st - HS>{});
+            if constexpr (st >= HS && st < HS + 10) store_s(s_fill, std::integral_constant<int, st - HS>{});
 #pragma unroll
             for (int t = 0; t < TAPS; ++t)
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[st & 1], fb[st & 1][t], acc[t], 0, 0, 0);
             // order: the LDS reads (next step's fragments, the next element's taps) first, then the MFMAs with the rest of the
             // step's staging (loads, LDS stores, the interpolation arithmetic) spread between them in three parts
-            if constexpr (st + 1 < STEPS) __builtin_amdgcn_sched_group_barrier(0x100, TAPS + 1 + ((H1 && st < EPT) ? 4 : 0), 0);
+            if constexpr (st + 1 < STEPS) __builtin_amdgcn_sched_group_barrier(0x100, TAPS + 1 + (st < EPT ? 4 : 0), 0);
             __builtin_amdgcn_sched_group_barrier(0x8, 3, 0);
             __builtin_amdgcn_sched_group_barrier(0x2 | 0x4 | 0x20 | 0x200, 8, 0);
             __builtin_amdgcn_sched_group_barrier(0x8, 3, 0);
@@ -391,12 +330,12 @@ __global__ __launch_bounds__(256) void wgrad3x3_up_kernel(const WgradArgs p) {
     };
 
     for (; tile < p.n_tiles; tile += stride) {
-        // one loop body (see wgrad3x3_wide_kernel): past the last tile the gradient pieces are masked off, the patch of the
+        // one loop body (see wg_persistent_tiles): past the last tile the gradient pieces are masked off, the patch of the
         // last tile is fetched again and the idle buffers are filled with values nobody reads
         aim_g(tile + stride);
         aim_i(tile + stride);
         aim_s(min(tile + 2 * stride, p.n_tiles - 1));
-        run_tile(std::true_type{}, std::true_type{});
+        run_tile();
         __syncthreads();
         cur ^= 1;
         par ^= 1;

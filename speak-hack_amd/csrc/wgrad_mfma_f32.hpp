@@ -69,11 +69,7 @@ struct WShape {
     static constexpr int KX = KH == 7 ? 3 : (S == 2 ? 2 : 1);   // plane positions (x NPT) a thread stages
 };
 
-// wgrad3x3_pipe_kernel: 16 x 4 tiles, two LDS buffers
-constexpr int WP_TW = 16, WP_PW = WP_TW + 2, WP_PLANE = 6 * WP_PW, WP_GPITCH = 65, WP_XPITCH = WP_PLANE | 1;
-constexpr int WP_BUF = 64 * WP_GPITCH + 64 * WP_XPITCH + 4;      // floats per buffer (+ a dump slot for idle lanes)
-
-// wgrad3x3_wide_kernel (and, at TW = 16, the tile of wgrad3x3_up_kernel)
+// wgrad3x3_wide_kernel (and, at TW = 16, the tile of wgrad3x3_pipe_kernel and wgrad3x3_up_kernel)
 template <int TW_>
 struct WideShapeT {
     static constexpr int CO_T = 64, CI_T = 64, NT = 256;
@@ -88,9 +84,12 @@ struct WideShapeT {
     static constexpr int NL = NG4 + NX4 + NXH, NS = 4 * NG4 + 4 * NX4 + NXH;
     static constexpr int STEPS = 32, HS = STEPS / 2;
     static constexpr int PL = (NL + HS - 1) / HS, PS = (NS + HS - 1) / HS;
-    static constexpr int NMFMA = 9, NFRAG = 10;
     static_assert(XPITCH % 2 == 1, "odd pitch");
 };
+
+// wgrad3x3_pipe_kernel: the tile images of the wide form at TW = 16, two LDS buffers
+constexpr int WP_BUF = WideShapeT<16>::BUF;
+static_assert(WP_BUF == 64 * 65 + 64 * 109 + 4, "floats per buffer (+ a dump slot for idle lanes)");
 
 // wgrad3x3_s2_kernel
 template <int TW_>

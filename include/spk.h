@@ -1143,6 +1143,18 @@ int spk_causal_filter(const float* x_dev, const float* w_dev, int64_t weight_str
                       double beta, double d_cutoff, int hold, double* state_dev, float* y_dev, float* wy_dev, void* stream);
 int spk_colour_rows_causal(const double* sums_dev, int N, double decay, double max_gain, double min_sigma, double min_weight, double* state_dev,
                            float* rows_out_dev, void* stream);
+/* spk_colour_rows_causal_feeds: spk_colour_rows_causal for S FEEDS side by side in one launch -- a server that steps several calls
+ *   per tick (speak-hack_amd/live.py: LiveRoom).  sums_dev fp64 [N][S][13]: frame n of feed s; state_dev fp64 [S][13]: one P per feed;
+ *   rows_out_dev fp32 [N][S][3][2]; one decay and one set of row-formula parameters for all feeds.  Feed s is EXACTLY
+ *   spk_colour_rows_causal over the frames sums[:, s] with the state state[s]: the same participation rule, one fma per sum, the same
+ *   row formula (csrc/colour_rows_common.hpp), evaluated by the routine the single-feed kernel runs.  A feed never reads or writes
+ *   another feed's state or rows: no atomics, no LDS.  Three lanes per feed (one per channel), 21 feeds per wave, so a feed never
+ *   straddles two waves (the three lanes read P before lane 0 of them writes it).  S = 1 gives the bits of spk_colour_rows_causal,
+ *   any S the bits of S separate calls, and any split of N the same bits.
+ *   Refused: what spk_colour_rows_causal refuses; S < 1; N * S * 13 >= 2^31 (every size is then computed without a wrap); sums, state
+ *   and rows that overlap. */
+int spk_colour_rows_causal_feeds(const double* sums_dev, int N, int S, double decay, double max_gain, double min_sigma, double min_weight,
+                                 double* state_dev, float* rows_out_dev, void* stream);
 
 /* ---- counter-based decoder noise (csrc/noise.hip) ----------------------------------------------------------------------------
  * The noise planes of a synthesis pass as a pure function of (seed, frame, layer, pixel): no generator state, so a clip comes
@@ -1183,6 +1195,23 @@ typedef struct spk_noise_fill_args {
 } spk_noise_fill_args;
 int spk_noise_bits_host(uint64_t seed, int64_t frame, int32_t layer, uint32_t q, uint32_t out[4]);
 int spk_noise_fill(const spk_noise_fill_args* args, void* stream);
+/* spk_noise_fill_rows: spk_noise_fill with one (seed, frame) PER BATCH ROW, read from device tables -- the rows of a batch are frames
+ *   of different feeds, which joined at different times and have their own seeds.  Batch row b of every layer is the noise of
+ *   (seeds_dev[b], frames_dev[b]): THE DEFINITION above, unchanged.  The tables (B entries each, 8-byte aligned) are read by the
+ *   kernel, never by the host, so a caller can keep and advance them on the device.  A table value maps onto the counter as
+ *   spk_noise_bits_host maps its arguments: two's complement, no range check.  The layout of dst, the thread-per-block shape and the
+ *   float4 / scalar-tail rule are those of spk_noise_fill, and the per-block routine is the one that kernel runs: with equal seeds
+ *   and frames f, f + 1, ... the buffer is spk_noise_fill's (frame0 = f, frame_step = 1) bit for bit.
+ *   Refused before any launch (SPK_EINVAL): what spk_noise_fill refuses of dst, B, n_layers, layer0 and hw; a null table or one that
+ *   is not 8-byte aligned; a table that overlaps dst. */
+typedef struct spk_noise_fill_rows_args {
+    float* dst;
+    const uint64_t* seeds_dev;
+    const int64_t* frames_dev;
+    int32_t B, n_layers, layer0, reserved;
+    int64_t hw[SPK_NOISE_MAX_LAYERS];
+} spk_noise_fill_rows_args;
+int spk_noise_fill_rows(const spk_noise_fill_rows_args* args, void* stream);
 
 /* ---- launch lists: a whole module forward per C call ---------------------------------------------------------------
  * The reference's callers run a decoder pass as one Python call (model.py:113-114 `self.Gd(gen_input)`,
@@ -1239,6 +1268,9 @@ typedef struct spk_frames_to_nv12_args {
     const float* x; uint8_t* y; uint8_t* uv; int64_t y_image_stride, y_row_stride, uv_image_stride, uv_row_stride;
     int32_t N, H, W, standard, full_range; float lo, k; int32_t reserved;
 } spk_frames_to_nv12_args;
+/* kind 14.  desc: spk_noise_fill_rows_args -> spk_noise_fill_rows (the first op of a rows-seeded decoder plan: the two table
+ * pointers are patched per run, as the seed and frame0 of a seeded plan are). */
+enum { SPK_OP_NOISE_FILL_ROWS = SPK_OP_FRAMES_TO_NV12 + 1 };
 int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask, void* stream);
 
 #ifdef __cplusplus

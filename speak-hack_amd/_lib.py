@@ -119,6 +119,7 @@ OP_MAXPOOL3X3S2, OP_GLOBAL_AVGPOOL = 9, 10
 OP_FRAMES_TO_U8 = 11
 OP_NOISE_FILL = 12
 OP_FRAMES_TO_NV12 = 13
+OP_NOISE_FILL_ROWS = 14
 ALL_OPS = 0xFFFFFFFF
 
 NOISE_MAX_LAYERS = 16
@@ -128,6 +129,12 @@ class NoiseFillArgs(C.Structure):
     """``spk_noise_fill_args`` (include/spk.h)."""
     _fields_ = [("dst", C.c_void_p), ("seed", C.c_uint64), ("frame0", C.c_int64), ("B", C.c_int32), ("frame_step", C.c_int32),
                 ("n_layers", C.c_int32), ("layer0", C.c_int32), ("hw", C.c_int64 * NOISE_MAX_LAYERS)]
+
+
+class NoiseFillRowsArgs(C.Structure):
+    """``spk_noise_fill_rows_args`` (include/spk.h)."""
+    _fields_ = [("dst", C.c_void_p), ("seeds_dev", C.c_void_p), ("frames_dev", C.c_void_p), ("B", C.c_int32), ("n_layers", C.c_int32),
+                ("layer0", C.c_int32), ("reserved", C.c_int32), ("hw", C.c_int64 * NOISE_MAX_LAYERS)]
 
 
 class Op(C.Structure):
@@ -358,6 +365,8 @@ _PROTOTYPES = {
     "spk_causal_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spk_colour_rows_causal": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spk_colour_rows_causal_feeds": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
     "spk_sim_fit_landmarks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "spk_sim_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     "spk_matte_from_landmarks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
@@ -388,6 +397,7 @@ _PROTOTYPES = {
                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spk_noise_bits_host": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "spk_noise_fill": (C.c_int, [C.POINTER(NoiseFillArgs), C.c_void_p]),
+    "spk_noise_fill_rows": (C.c_int, [C.POINTER(NoiseFillRowsArgs), C.c_void_p]),
 }
 
 _lib = None

@@ -78,18 +78,16 @@ __global__ __launch_bounds__(FILTER_THREADS) void causal_filter_kernel(const flo
     }
 }
 
-// One wave, of which lanes 0, 1, 2 work: each walks the N frames with the whole of P (the same loads in the three lanes: one
-// fetch) and makes the rows of its own channel, so the three row formulas of a frame -- divisions and a square root in fp64, the
-// long part of a frame -- run side by side.  Lane 0 writes the state.
-__global__ __launch_bounds__(64) void colour_rows_causal_kernel(const double* __restrict__ sums, int N, double decay, double max_gain, double min_var,
-                                                                double min_weight, double* __restrict__ state, float* __restrict__ rows) {
-    const int c = threadIdx.x;
-    if (c >= 3) return;
+// Channel c of one feed: the lane walks the feed's N frames -- `stride` frames of 13 sums apart in `sums`, `stride` colour rows
+// apart in `rows` -- with the whole of P, and makes the rows of its own channel.  The lane of channel 0 writes the state.  The three
+// lanes of a feed run in one wave: all three have read P before one of them writes it.
+__device__ __forceinline__ void colour_feed_walk(const double* __restrict__ sums, long long stride, int N, int c, double decay, double max_gain,
+                                                 double min_var, double min_weight, double* __restrict__ state, float* __restrict__ rows) {
     double P[SUMS];
 #pragma unroll
     for (int i = 0; i < SUMS; ++i) P[i] = state[i];
     for (long long n = 0; n < N; ++n) {
-        const double* s = sums + n * SUMS;
+        const double* s = sums + n * stride * SUMS;
         double v[SUMS];
         bool finite = true;
 #pragma unroll
@@ -99,12 +97,35 @@ __global__ __launch_bounds__(64) void colour_rows_causal_kernel(const double* __
         for (int i = 0; i < SUMS; ++i) P[i] = part ? fma(decay, P[i], v[i]) : P[i];
         float g, o;
         colour_row(P[0], P[1 + 4 * c], P[2 + 4 * c], P[3 + 4 * c], P[4 + 4 * c], P[0] > min_weight, max_gain, min_var, g, o);
-        rows[n * 6 + 2 * c] = g, rows[n * 6 + 2 * c + 1] = o;
+        rows[n * stride * 6 + 2 * c] = g, rows[n * stride * 6 + 2 * c + 1] = o;
     }
     if (c == 0) {
 #pragma unroll
         for (int i = 0; i < SUMS; ++i) state[i] = P[i];
     }
+}
+
+// One wave, of which lanes 0, 1, 2 work: each walks the N frames with the whole of P (the same loads in the three lanes: one
+// fetch) and makes the rows of its own channel, so the three row formulas of a frame -- divisions and a square root in fp64, the
+// long part of a frame -- run side by side.  Lane 0 writes the state.
+__global__ __launch_bounds__(64) void colour_rows_causal_kernel(const double* __restrict__ sums, int N, double decay, double max_gain, double min_var,
+                                                                double min_weight, double* __restrict__ state, float* __restrict__ rows) {
+    const int c = threadIdx.x;
+    if (c >= 3) return;
+    colour_feed_walk(sums, 1, N, c, decay, max_gain, min_var, min_weight, state, rows);
+}
+
+// S feeds side by side, sums [N][S][13], state [S][13], rows [N][S][3][2]: workgroups of one wave whose lanes 3 f + c, f < 21, are
+// channel c of feed 21 * block + f (lane 63 idles), so the three lanes of a feed never sit in two waves.  A lane touches its own
+// feed's sums, state and rows only.
+constexpr int FEEDS_PER_WAVE = 21;
+__global__ __launch_bounds__(64) void colour_rows_causal_feeds_kernel(const double* __restrict__ sums, int N, int S, double decay, double max_gain,
+                                                                      double min_var, double min_weight, double* __restrict__ state,
+                                                                      float* __restrict__ rows) {
+    const int f = threadIdx.x / 3, c = threadIdx.x - 3 * f;
+    const long long s = (long long)blockIdx.x * FEEDS_PER_WAVE + f;
+    if (f >= FEEDS_PER_WAVE || s >= S) return;
+    colour_feed_walk(sums + s * SUMS, S, N, c, decay, max_gain, min_var, min_weight, state + s * SUMS, rows + s * 6);
 }
 
 // [p, p + bytes) and [q, q + qbytes) share a byte (a null q: no)
@@ -174,6 +195,29 @@ int spk_colour_rows_causal(const double* sums_dev, int N, double decay, double m
     hipLaunchKernelGGL(colour_rows_causal_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums_dev, N, decay, max_gain, min_sigma * min_sigma,
                        min_weight, state_dev, rows_out_dev);
     return spk::check_launch("colour_rows_causal_kernel");
+}
+
+int spk_colour_rows_causal_feeds(const double* sums_dev, int N, int S, double decay, double max_gain, double min_sigma, double min_weight,
+                                 double* state_dev, float* rows_out_dev, void* stream) {
+    const char* who = "colour_rows_causal_feeds";
+    SPK_REQUIRE(sums_dev, "%s: null sums array", who);
+    SPK_REQUIRE(state_dev, "%s: null state pointer", who);
+    SPK_REQUIRE(rows_out_dev, "%s: null colour row array", who);
+    SPK_REQUIRE((uintptr_t)sums_dev % alignof(double) == 0 && (uintptr_t)state_dev % alignof(double) == 0,
+                "%s: the sums array and the state must be aligned to %zu bytes", who, alignof(double));
+    SPK_REQUIRE(N >= 1, "%s: N must be >= 1 (got %d)", who, N);
+    SPK_REQUIRE(S >= 1, "%s: S must be >= 1 (got %d)", who, S);
+    SPK_REQUIRE((int64_t)N * S <= INT32_MAX / SUMS, "%s: %d frames of %d feeds are 2^31 sums or more", who, N, S);
+    SPK_REQUIRE(decay >= 0.0 && decay <= 1.0, "%s: decay must be in [0, 1] (got %g)", who, decay);      // a NaN fails both
+    if (int rc = check_match_params(who, max_gain, min_sigma, min_weight)) return rc;
+    const uint64_t frames = (uint64_t)N * (uint64_t)S;                    // (< 2^31 / 13: no product below wraps)
+    const uint64_t state_bytes = (uint64_t)S * SUMS * sizeof(double), sums_bytes = frames * SUMS * sizeof(double), rows_bytes = frames * 6 * sizeof(float);
+    SPK_REQUIRE(!overlap(state_dev, state_bytes, sums_dev, sums_bytes) && !overlap(state_dev, state_bytes, rows_out_dev, rows_bytes) &&
+                    !overlap(sums_dev, sums_bytes, rows_out_dev, rows_bytes),
+                "%s: the sums of %d frames of %d feeds, the states and the rows overlap", who, N, S);
+    hipLaunchKernelGGL(colour_rows_causal_feeds_kernel, dim3((unsigned)((S + FEEDS_PER_WAVE - 1) / FEEDS_PER_WAVE)), dim3(64), 0, (hipStream_t)stream,
+                       sums_dev, N, S, decay, max_gain, min_sigma * min_sigma, min_weight, state_dev, rows_out_dev);
+    return spk::check_launch("colour_rows_causal_feeds_kernel");
 }
 
 }  // extern "C"

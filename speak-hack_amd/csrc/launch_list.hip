@@ -81,6 +81,9 @@ extern "C" int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask,
             case SPK_OP_NOISE_FILL:
                 rc = spk_noise_fill(static_cast<const spk_noise_fill_args*>(op.desc), stream);
                 break;
+            case SPK_OP_NOISE_FILL_ROWS:
+                rc = spk_noise_fill_rows(static_cast<const spk_noise_fill_rows_args*>(op.desc), stream);
+                break;
             default:
                 return spk::fail(SPK_EUNSUPPORTED, "launch_list: op %d: unknown kind %d", i, op.kind);
         }

@@ -278,14 +278,19 @@ class StyleGenerator(nn.Module):
         return syn.use_plan and features.is_cuda and features.dim() == 2 and len(syn.layers) * 2 + 1 <= ops.L.FC_MAX_GROUPS
 
     def plan_forward(self, features, noises=None, *, output="f32", value_range=(-1, 1), swap_rb=False, seed=None, frame0=0,
-                     fixed_noise=False, standard="bt601", full_range=False):
+                     fixed_noise=False, standard="bt601", full_range=False, seed_rows=None, frame_rows=None):
         """The eval forward -- mapping, truncation, synthesis; no style mixing, no host-RNG draw -- on the inference launch plan,
         whatever ``self.training`` is (no module state is read or touched).  No gradient flows through it.  ``output="uint8"``:
         the plan ends in the quantising op and returns uint8 [B,R,R,3] frames (``plan.DecoderPlan``); ``output="nv12"``: it ends in
         the NV12 op and returns uint8 [B,3R/2,R] surfaces in the colour of ``standard`` / ``full_range``.  ``seed``: a seeded plan
         (a cache entry of its own) draws the noise of ``ops.decoder_noise(shapes, seed, frame0=frame0, fixed=fixed_noise)`` as
-        the first op of its list."""
+        the first op of its list.  ``seed_rows`` / ``frame_rows`` (device int64 ``[B]`` tables, instead of ``seed``): a rows-seeded
+        plan (again a cache entry of its own) draws ``ops.decoder_noise_rows(shapes, seed_rows, frame_rows)``, one (seed, frame) per
+        batch row."""
         syn = self.synthesis
+        rows = seed_rows is not None or frame_rows is not None
+        if rows and (seed is not None or noises is not None or fixed_noise):
+            raise ValueError("pass either seed_rows and frame_rows, or seed / fixed_noise, or noises")
         if noises is not None and len(noises) != 2 * len(syn.layers) + 1:
             raise ValueError(f"expected {2 * len(syn.layers) + 1} noise tensors, got {len(noises)}")
         if seed is not None:
@@ -304,10 +309,15 @@ class StyleGenerator(nn.Module):
             key += (output, float(value_range[0]), float(value_range[1]), bool(swap_rb))
         if seed is not None:
             key += ("seeded",)
+        elif rows:
+            key += ("seeded rows",)
         p = PL.plan_for(self, key, lambda: PL.DecoderPlan(syn, B, features.device, generator=self, precision=syn.precision,
                                                           output=output, value_range=value_range, swap_rb=swap_rb,
-                                                          seeded=seed is not None, standard=standard, full_range=full_range))
+                                                          seeded="rows" if rows else seed is not None, standard=standard,
+                                                          full_range=full_range))
         features = features if features.stride(1) == 1 else features.contiguous()
+        if rows:
+            return p.run(features, seed_rows=seed_rows, frame_rows=frame_rows)
         if seed is not None:
             return p.run(features, seed=seed, frame0=frame0, fixed_noise=fixed_noise)
         return p.run(features, None if noises is None else [n.contiguous() for n in noises])

@@ -1027,6 +1027,42 @@ def colour_rows_causal(sums, state, decay, *, max_gain=2.0, min_sigma=1.0, min_w
     return out
 
 
+def colour_rows_causal_feeds(sums, state, decay, *, max_gain=2.0, min_sigma=1.0, min_weight=16.0, out=None):
+    """``colour_rows_causal`` for ``S`` feeds side by side, one launch (``spk_colour_rows_causal_feeds``).  ``sums``: a device float64
+    ``[N,S,13]`` tensor, frame ``n`` of feed ``s``; ``state``: a device float64 ``[S,13]`` tensor, one ``P`` per feed.  Feed ``s`` is
+    ``colour_rows_causal(sums[:, s], state[s], decay, ...)`` bit for bit, rows and state, and never touches another feed's.  ``out``:
+    a contiguous device float32 ``[N,S,3,2]`` tensor to write.  -> device float32 ``[N,S,3,2]``."""
+    what = "colour_rows_causal_feeds"
+    try:
+        decay = float(decay)
+    except (ValueError, TypeError):
+        raise ValueError(f"{what}: decay must be a number in [0, 1], got {decay!r}") from None
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"{what}: decay must be in [0, 1], got {decay}")
+    params = _check_match_params(what, max_gain, min_sigma, min_weight)
+    if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64 or sums.dim() != 3 or sums.size(2) != COLOUR_SUMS or sums.size(0) < 1 \
+            or sums.size(1) < 1 or sums.numel() >= 2 ** 31:
+        got = f"{sums.dtype} {tuple(sums.shape)}" if isinstance(sums, torch.Tensor) else type(sums).__name__
+        raise ValueError(f"{what}: sums must be a float64 tensor [N,S,{COLOUR_SUMS}] of N >= 1 frames of S >= 1 feeds (fewer than 2^31 sums), got {got}")
+    N, S = sums.size(0), sums.size(1)
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or tuple(state.shape) != (S, COLOUR_SUMS):
+        got = f"{state.dtype} {tuple(state.shape)}" if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f"{what}: state must be a float64 tensor [{S},{COLOUR_SUMS}], one row per feed of the sums, got {got}")
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (N, S, 3, 2) or out.dtype != torch.float32):
+        got = f"{out.dtype} {tuple(out.shape)}" if isinstance(out, torch.Tensor) else type(out).__name__
+        raise ValueError(f"{what}: out must be a float32 tensor [{N},{S},3,2], got {got}")
+    if not sums.is_cuda:
+        raise L.SpkError(f"{what}: sums on {sums.device} (no CPU path)")
+    if not sums.is_contiguous():
+        raise L.SpkError(f"{what}: sums: expected a contiguous tensor, got strides {sums.stride()}")
+    if state.device != sums.device or not state.is_contiguous():
+        raise L.SpkError(f"{what}: state: expected a contiguous tensor on {sums.device}, got strides {state.stride()} on {state.device}")
+    out = _stat_out(out, (N, S, 3, 2), torch.float32, sums.device)
+    L.check(L.lib().spk_colour_rows_causal_feeds(sums.data_ptr(), N, S, decay, *params, state.data_ptr(), out.data_ptr(), L.stream_ptr()),
+            "spk_colour_rows_causal_feeds")
+    return out
+
+
 # ---- NV12 (csrc/frame_nv12.hip; the definitions are in include/spk.h) ---------------------------------------------------------------
 def yuv_standard(standard, full_range):
     if standard not in ("bt601", "bt709"):

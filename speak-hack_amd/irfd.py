@@ -340,19 +340,48 @@ class IRFD(nn.Module):
         same bytes.  With ``track=None``, ``features=None``, ``colour_decay=0`` and frames that all have landmarks, a ``step`` over a
         clip is ``reenact_video(align=LandmarkAlign(landmarks, template), paste=True, matte=LandmarkMatte(contour, smooth=0, ...),
         colour_match=True, ...)`` byte for byte.  ``session.reset()`` empties the filter states and the frame counter
-        (``session.frames``); ``fi`` stays.  Packed RGB only: a session over NV12 surfaces is a follow-up."""
+        (``session.frames``); ``fi`` stays.  Packed RGB only: a session over NV12 surfaces is a follow-up.  Several feeds at once:
+        ``live_room``."""
         from .live import LiveSession
         return LiveSession(self, identity_u8, size=size, template=template, contour=contour, channel_order=channel_order,
                            identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,
                            matte_softness=matte_softness, matte_grow=matte_grow, colour_match=colour_match, colour_decay=colour_decay, seed=seed,
                            noise=noise, offset=offset)
 
+    @torch.no_grad()
+    def live_room(self, identities_u8, *, size=256, template, contour=None, channel_order="rgb", identity_align=None, rate=30.0,
+                  track=FR.FILTER_DEFAULTS, features=None, feather=0, matte_softness=4.0, matte_grow=0.0, colour_match=False,
+                  colour_decay=0.9, seed=None, noise="fresh", offset=0.0):
+        """``live`` for ``S`` feeds at once -- a server with several calls -- stepped together as ONE batch per tick
+        (speak-hack_amd/live.py: ``LiveRoom``).  The arguments are those of ``live``, with ``identities_u8`` a sequence of ``S`` photos
+        of any sizes ([H,W,3] or [1,H,W,3] each) or a tensor ``[S,H,W,3]``; ``seed`` one integer or ``S`` of them; ``identity_align``
+        None, or one entry (None or as ``live`` takes it) per photo.  Everything is checked on the host (``ValueError``) before a
+        device is touched; then ``Ei`` runs once per photo at batch 1, as a session runs it.  -> a ``LiveRoom``;
+        ``room.step(frames_u8 [S,H,W,3], landmarks [S,K,2], *, weights=None, emotion_u8=None, inplace=False)`` -> uint8 ``[S,H,W,3]``
+        takes one frame per feed per tick and runs the nine steps of ``live`` with the feeds as the batch: 3 launch lists, 1 landmark
+        filter (2 with ``features``), 1 fit, 1 crop, 1 matte, 1 sums, 1 ``spk_colour_rows_causal_feeds``, 1 paste, whatever ``S`` is; the
+        decoder's noise row ``s`` is that of ``(seed[s], the ticks slot s has seen)``, read from device tables
+        (``spk_noise_fill_rows``).  Slot ``s`` of a room is a session of its own (the networks run at batch ``S``: the same frames once
+        quantised, as the chunks of ``reenact_video`` are); a feed with nothing to show in a tick is given NaN landmarks.
+        ``room.reset(slot=None)`` and ``room.set_identity(slot, photo, identity_align=None)`` start a slot over without touching its
+        neighbours.  Packed RGB, one frame size for all feeds."""
+        from .live import LiveRoom
+        return LiveRoom(self, identities_u8, size=size, template=template, contour=contour, channel_order=channel_order,
+                        identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,
+                        matte_softness=matte_softness, matte_grow=matte_grow, colour_match=colour_match, colour_decay=colour_decay, seed=seed,
+                        noise=noise, offset=offset)
+
     def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None, colour=("bt601", False)):
         """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan
         does not serve runs its eval branch with every submodule's own ``training`` flag saved and put back.  ``seeded``: the
-        ``seed`` / ``frame0`` / ``fixed_noise`` keywords of a seeded call (``StyleGenerator`` decoders), else None."""
+        ``seed`` / ``frame0`` / ``fixed_noise`` keywords of a seeded call (``StyleGenerator`` decoders), else None; or
+        ``dict(seed_rows=, frame_rows=)``, device int64 ``[B]`` tables with one (seed, frame) per batch row (``ops.noise_fill_rows``)."""
         Gd = self.Gd
         seeded = seeded or {}
+        if "seed_rows" in seeded and not (hasattr(Gd, "plan_serves") and Gd.plan_serves(gin)):
+            if noises is not None:
+                raise ValueError("pass either seed_rows and frame_rows or noises, not both")
+            noises, seeded = ops.decoder_noise_rows(Gd.synthesis.noise_shapes(gin.size(0)), seeded["seed_rows"], seeded["frame_rows"]), {}
         if hasattr(Gd, "plan_serves") and Gd.plan_serves(gin):
             how = {"f32": {}, "uint8": dict(output=output, swap_rb=channel_order == "bgr"),
                    "nv12": dict(output=output, standard=colour[0], full_range=colour[1])}[output]

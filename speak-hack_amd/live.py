@@ -3,13 +3,17 @@ through a few frames at a time.  ``IRFD.reenact_video`` takes a clip that is in 
 landmarks, the matte's contour and the colour statistics with windows over frames ``t - r ... t + r``.  A session runs ``Ei`` once,
 keeps ``fi``, and steadies the same three things with the causal filters of csrc/causal_filter.hip, whose state lives in device
 tensors on the session: ``step`` reads no device value on the host, and ``N`` frames in one ``step`` and the same frames in any split
-of steps give the same bytes.  Packed RGB only; a session over NV12 surfaces is a follow-up."""
+of steps give the same bytes.  Packed RGB only; a session over NV12 surfaces is a follow-up.
+
+``IRFD.live_room``: S such feeds at once -- a server with several calls -- as ONE batch per tick (``LiveRoom``): the frames of a tick
+are the batch rows of the same launches a session makes, with the state of every feed, its frame counter and its seed on the device."""
 from __future__ import annotations
 
 import torch
 
 from . import _lib as L
 from . import frames as FR
+from . import ops
 
 
 def _filter_params(what, name, params, group, rate):
@@ -25,15 +29,22 @@ def _filter_params(what, name, params, group, rate):
     return dict(group=group, rate=rate, **p)
 
 
-class LiveSession:
-    """What ``IRFD.live`` returns (its docstring has the arguments).  ``step`` takes the next frames of the feed; ``frames`` counts
-    the frames seen so far; ``reset()`` forgets them.  The filter states are device tensors of the session (``lm_state``,
-    ``feature_state``, ``colour_state``)."""
+def _check_identity(what, name, identity_u8):
+    """One identity photo: [H,W,3] or [1,H,W,3]"""
+    if not isinstance(identity_u8, torch.Tensor) or identity_u8.dim() not in (3, 4) or identity_u8.size(-1) != 3 or \
+            (identity_u8.dim() == 4 and identity_u8.size(0) != 1):
+        got = tuple(identity_u8.shape) if isinstance(identity_u8, torch.Tensor) else type(identity_u8).__name__
+        raise ValueError(f"{what}: {name} must be [H,W,3] or [1,H,W,3], got {got}")
 
-    def __init__(self, model, identity_u8, *, size, template, contour, channel_order, identity_align, rate, track, features, feather,
-                 matte_softness, matte_grow, colour_match, colour_decay, seed, noise, offset):
-        from .irfd import _check_noise
-        what = "live"
+
+class _Live:
+    """What a session and a room share: the arguments of ``IRFD.live`` checked on the host, ``Ei`` on one photo, and the body of a
+    step over a batch of frames.  The two differ in what a batch row is -- the next frame of one feed, or this tick's frame of the
+    next feed -- and so in how the three filters, ``fi`` and the noise index are laid over the rows: ``_steady``,
+    ``_steady_features``, ``_fi``, ``_seeded`` and ``_colour_rows``."""
+
+    def _configure(self, what, model, *, size, template, contour, channel_order, rate, track, features, feather, matte_softness, matte_grow,
+                   colour_match, colour_decay, offset):
         self.size = FR._out_size(size, what)
         FR._channel_swap(channel_order)
         self.channel_order = channel_order
@@ -60,38 +71,24 @@ class LiveSession:
         self.colour_decay = FR._finite(colour_decay, "colour_decay", what)
         if not 0.0 <= self.colour_decay <= 1.0:
             raise ValueError(f"{what}: colour_decay must be in [0, 1], got {self.colour_decay}")
-        _check_noise(what, noise, seed, None, 0)
-        self.seed, self.fixed_noise = seed, noise == "fixed"
-        if not isinstance(identity_u8, torch.Tensor) or identity_u8.dim() not in (3, 4) or identity_u8.size(-1) != 3 or \
-                (identity_u8.dim() == 4 and identity_u8.size(0) != 1):
-            got = tuple(identity_u8.shape) if isinstance(identity_u8, torch.Tensor) else type(identity_u8).__name__
-            raise ValueError(f"{what}: identity_u8 must be [H,W,3] or [1,H,W,3], got {got}")
-        if identity_align is not None:                                     # host rows: checked here, before any launch
-            identity_align = FR.Aligned.parse(identity_align, 1, size, identity_u8.device, f"{what}: identity_align")
-        # ---- the arguments are in order: the device
-        if identity_align is None:
-            ident = FR.frames_from_u8(identity_u8, size, channel_order=channel_order)
-        else:
-            ident = FR.frames_from_u8_aligned(identity_u8, size, identity_align.rows, channel_order=channel_order)
-        self.model, self.device = model, ident.device
-        self.fi = model.encode(ident, "Ei")                                # once per session
+        self.model = model
+        return template
+
+    def _place_template(self, what, template):
         if template.is_cuda and template.device != self.device:
             raise L.SpkError(f"{what}: template on {template.device}, the identity image on {self.device}")
         self._template_host = None if template.is_cuda else template
         self.template = template.to(self.device).contiguous()
-        self.lm_state = None if self.track is None else FR.causal_filter_state(2 * K, 2, self.device)
-        self.feature_state = None if self.features is None else FR.causal_filter_state(2 * self.fi.numel(), 1, self.device)
-        self.colour_state = torch.zeros(FR.COLOUR_SUMS, device=self.device, dtype=torch.float64) if colour_match else None
         self._nan = torch.full((), float("nan"), device=self.device)
         self._generated = {}                                               # per generated width: (the rows' scale, the fallback outline)
-        self.frames = 0
 
-    def reset(self):
-        """Empties the filter states and the frame counter: the next ``step`` is the first of a feed.  ``fi`` stays."""
-        for s in (self.lm_state, self.feature_state, self.colour_state):
-            if s is not None:
-                s.zero_()
-        self.frames = 0
+    def _encode_identity(self, identity_u8, identity_align):
+        """``Ei`` on one photo at batch 1 (``identity_align``: None, or parsed ``Aligned`` rows): -> fi [1,2048,1,1]"""
+        if identity_align is None:
+            ident = FR.frames_from_u8(identity_u8, self.size, channel_order=self.channel_order)
+        else:
+            ident = FR.frames_from_u8_aligned(identity_u8, self.size, identity_align.rows, channel_order=self.channel_order)
+        return self.model.encode(ident, "Ei")
 
     def _for_generated(self, Hs, Ws):
         """The network image has ``size`` pixels where the generated one has ``Hs x Ws``: -> (the factor of a row's ``(a, c)`` as a
@@ -108,6 +105,106 @@ class LiveSession:
             self._generated[Ws] = (scale, fallback)
         return self._generated[Ws]
 
+    def _check_step(self, what, frames_u8, emotion_u8, inplace):
+        if emotion_u8 is not None and (not isinstance(emotion_u8, torch.Tensor) or tuple(emotion_u8.shape) != tuple(frames_u8.shape)):
+            raise ValueError(f"{what}: emotion_u8 must match the frames {tuple(frames_u8.shape)}")
+        if not isinstance(inplace, bool):
+            raise ValueError(f"{what}: inplace must be a bool, got {inplace!r}")
+
+    def _body(self, what, frames_u8, landmarks, weights, emotion_u8, inplace):
+        """The steps of one ``step`` over the ``N`` rows of ``frames_u8``, after the host checks: ``landmarks`` [N,K,2] and
+        ``weights`` as the filter (``track``) or else the fit takes them"""
+        if inplace and not FR.packed_pixels(frames_u8):
+            raise L.SpkError(f"{what}: inplace needs packed pixels and rows / frames that do not overlap, got strides {frames_u8.stride()}")
+        N = frames_u8.size(0)
+        model, order = self.model, dict(channel_order=self.channel_order)
+        # 1, 2: the landmarks steadied, and the rows fitted to them; a held point keeps its last weight, an expired one has none
+        if self.track is not None:
+            landmarks, weights = self._steady(landmarks, weights)
+        rows = FR._fit(landmarks, self.template, weights, self.offset, what)
+        # 3, 4: the crops, Ee and Ep
+        pose = FR.frames_from_u8_aligned(frames_u8, self.size, rows, **order)
+        emo = pose if emotion_u8 is None else FR.frames_from_u8_aligned(emotion_u8, self.size, rows, **order)
+        fe, fp = model.encode(emo, "Ee"), model.encode(pose, "Ep")
+        fi = self._fi(N)
+        if self.features is None:
+            gin = model._prepare_generator_input(fi, fe, fp)
+        else:
+            # 5: emotion and pose steadied; the features of a frame without a transform (a crop of nothing) take no part
+            f = torch.cat([fe.view(N, -1), fp.view(N, -1)], 1)
+            f = torch.where(torch.isfinite(rows).all(1, keepdim=True), f, self._nan)
+            self._steady_features(f)
+            gin = torch.cat([fi.reshape(N, -1), f], 1)
+        # 6: the decoder; frame t of a feed has noise index t
+        y = model._decode_eval(gin, None, "f32", "rgb", self._seeded())
+        # 7 - 9: matte, colour rows and the paste, with the rows scaled to the generated size
+        Hs, Ws = y.shape[2:]
+        scale, fallback = self._for_generated(Hs, Ws)
+        if scale is not None:
+            rows = rows * scale
+        matte = None
+        if self.contour is not None:
+            matte = FR._matte(landmarks, rows, Hs, Ws, self.contour, self.softness, self.grow, self.offset, fallback, *FR._check_smooth(0, None, what),
+                              what)
+        out = frames_u8 if inplace else frames_u8.clone(memory_format=torch.contiguous_format)
+        colour = None
+        if self.colour_match:                                              # the statistics read the background before the paste writes it
+            sums = FR.paste_colour_sums(y, out, rows, matte=matte, feather=self.feather, **order)
+            colour = self._colour_rows(sums)
+        FR.frames_paste_u8_aligned(y, out, rows, feather=self.feather, out=out, matte=matte, colour=colour, **order)
+        return out
+
+
+class LiveSession(_Live):
+    """What ``IRFD.live`` returns (its docstring has the arguments).  ``step`` takes the next frames of the feed; ``frames`` counts
+    the frames seen so far; ``reset()`` forgets them.  The filter states are device tensors of the session (``lm_state``,
+    ``feature_state``, ``colour_state``)."""
+
+    def __init__(self, model, identity_u8, *, size, template, contour, channel_order, identity_align, rate, track, features, feather,
+                 matte_softness, matte_grow, colour_match, colour_decay, seed, noise, offset):
+        from .irfd import _check_noise
+        what = "live"
+        template = self._configure(what, model, size=size, template=template, contour=contour, channel_order=channel_order, rate=rate, track=track,
+                                   features=features, feather=feather, matte_softness=matte_softness, matte_grow=matte_grow,
+                                   colour_match=colour_match, colour_decay=colour_decay, offset=offset)
+        _check_noise(what, noise, seed, None, 0)
+        self.seed, self.fixed_noise = seed, noise == "fixed"
+        _check_identity(what, "identity_u8", identity_u8)
+        if identity_align is not None:                                     # host rows: checked here, before any launch
+            identity_align = FR.Aligned.parse(identity_align, 1, size, identity_u8.device, f"{what}: identity_align")
+        # ---- the arguments are in order: the device
+        self.fi = self._encode_identity(identity_u8, identity_align)       # once per session
+        self.device = self.fi.device
+        self._place_template(what, template)
+        K = self.K
+        self.lm_state = None if self.track is None else FR.causal_filter_state(2 * K, 2, self.device)
+        self.feature_state = None if self.features is None else FR.causal_filter_state(2 * self.fi.numel(), 1, self.device)
+        self.colour_state = torch.zeros(FR.COLOUR_SUMS, device=self.device, dtype=torch.float64) if colour_match else None
+        self.frames = 0
+
+    def reset(self):
+        """Empties the filter states and the frame counter: the next ``step`` is the first of a feed.  ``fi`` stays."""
+        for s in (self.lm_state, self.feature_state, self.colour_state):
+            if s is not None:
+                s.zero_()
+        self.frames = 0
+
+    # ---- a batch row is the next frame of the feed: the filters walk the rows in order
+    def _steady(self, landmarks, weights):
+        return FR.causal_filter(landmarks, self.lm_state, weights=weights, **self.track)
+
+    def _steady_features(self, f):
+        FR.causal_filter(f, self.feature_state, out=f, **self.features)
+
+    def _fi(self, N):
+        return self.fi.expand(N, -1, -1, -1)
+
+    def _seeded(self):
+        return None if self.seed is None else dict(seed=self.seed, frame0=0 if self.fixed_noise else self.frames, fixed_noise=self.fixed_noise)
+
+    def _colour_rows(self, sums):
+        return FR.colour_rows_causal(sums, self.colour_state, self.colour_decay)
+
     @torch.no_grad()
     def step(self, frames_u8, landmarks, *, weights=None, emotion_u8=None, inplace=False):
         """The next ``N`` frames of the feed: ``frames_u8`` uint8 ``[N,H,W,3]`` on the device, ``landmarks`` device float32
@@ -123,49 +220,186 @@ class LiveSession:
         if not isinstance(landmarks, torch.Tensor) or tuple(landmarks.shape) != (N, self.K, 2):
             got = tuple(landmarks.shape) if isinstance(landmarks, torch.Tensor) else type(landmarks).__name__
             raise ValueError(f"{what}: landmarks must be [{N},{self.K},2], {self.K} points per frame as the template has, got {got}")
-        if emotion_u8 is not None and (not isinstance(emotion_u8, torch.Tensor) or tuple(emotion_u8.shape) != tuple(frames_u8.shape)):
-            raise ValueError(f"{what}: emotion_u8 must match the frames {tuple(frames_u8.shape)}")
-        if not isinstance(inplace, bool):
-            raise ValueError(f"{what}: inplace must be a bool, got {inplace!r}")
+        self._check_step(what, frames_u8, emotion_u8, inplace)
         if self.track is None:
             _, weights, _ = FR._check_fit(landmarks, self.template, weights, self.offset, what)
-        if inplace and not FR.packed_pixels(frames_u8):
-            raise L.SpkError(f"{what}: inplace needs packed pixels and rows / frames that do not overlap, got strides {frames_u8.stride()}")
-        model, order = self.model, dict(channel_order=self.channel_order)
-        # 1, 2: the landmarks steadied, and the rows fitted to them; a held point keeps its last weight, an expired one has none
-        if self.track is not None:
-            landmarks, weights = FR.causal_filter(landmarks, self.lm_state, weights=weights, **self.track)
-        rows = FR._fit(landmarks, self.template, weights, self.offset, what)
-        # 3, 4: the crops, Ee and Ep
-        pose = FR.frames_from_u8_aligned(frames_u8, self.size, rows, **order)
-        emo = pose if emotion_u8 is None else FR.frames_from_u8_aligned(emotion_u8, self.size, rows, **order)
-        fe, fp = model.encode(emo, "Ee"), model.encode(pose, "Ep")
-        fi = self.fi.expand(N, -1, -1, -1)
-        if self.features is None:
-            gin = model._prepare_generator_input(fi, fe, fp)
-        else:
-            # 5: emotion and pose steadied; the features of a frame without a transform (a crop of nothing) take no part
-            f = torch.cat([fe.view(N, -1), fp.view(N, -1)], 1)
-            f = torch.where(torch.isfinite(rows).all(1, keepdim=True), f, self._nan)
-            f, _ = FR.causal_filter(f, self.feature_state, out=f, **self.features)
-            gin = torch.cat([fi.reshape(N, -1), f], 1)
-        # 6: the decoder; frame t of the feed has noise index t
-        seeded = None if self.seed is None else dict(seed=self.seed, frame0=0 if self.fixed_noise else self.frames, fixed_noise=self.fixed_noise)
-        y = model._decode_eval(gin, None, "f32", "rgb", seeded)
-        # 7 - 9: matte, colour rows and the paste, with the rows scaled to the generated size
-        Hs, Ws = y.shape[2:]
-        scale, fallback = self._for_generated(Hs, Ws)
-        if scale is not None:
-            rows = rows * scale
-        matte = None
-        if self.contour is not None:
-            matte = FR._matte(landmarks, rows, Hs, Ws, self.contour, self.softness, self.grow, self.offset, fallback, *FR._check_smooth(0, None, what),
-                              what)
-        out = frames_u8 if inplace else frames_u8.clone(memory_format=torch.contiguous_format)
-        colour = None
-        if self.colour_match:                                              # the statistics read the background before the paste writes it
-            sums = FR.paste_colour_sums(y, out, rows, matte=matte, feather=self.feather, **order)
-            colour = FR.colour_rows_causal(sums, self.colour_state, self.colour_decay)
-        FR.frames_paste_u8_aligned(y, out, rows, feather=self.feather, out=out, matte=matte, colour=colour, **order)
+        out = self._body(what, frames_u8, landmarks, weights, emotion_u8, inplace)
         self.frames += N
+        return out
+
+
+class LiveRoom(_Live):
+    """What ``IRFD.live_room`` returns (its docstring has the arguments): ``S`` feeds stepped together, one frame per feed per tick,
+    in the launches of ONE session step at batch ``S``.  Slot ``s`` is a ``LiveSession`` of its own: its landmark state, its ``fi`` and
+    its noise are to the bit those of a session that saw the frames of slot ``s`` one at a time, and its frames are that session's as
+    the chunks of ``reenact_video`` are each other's -- the encoders and the decoder run at batch ``S`` where the session runs them at
+    batch 1, which is the same image once quantised except where a value sits on a rounding boundary (DESIGN 4.2k has the counts).
+    Everything a feed remembers is on the device:
+
+      ``fi``             float32 ``[S,2048,1,1]``, row ``s`` bit for bit the ``fi`` of a session on photo ``s`` (``Ei`` at batch 1);
+      ``lm_state``       float64 ``[S K, 6]``: the landmark filter's groups, slot ``s`` in rows ``s K ... (s + 1) K - 1``;
+      ``feature_state``  float64 ``[S 4096, 4]``, slot after slot;
+      ``colour_state``   float64 ``[S,13]``;
+      ``frames``         int64 ``[S]``: the ticks each slot has seen since its reset (all 0 with ``noise="fixed"``), the frame index of
+                         its noise; advanced on the device;
+      ``seeds``          int64 ``[S]``: the 64-bit patterns of the seeds (``ops.seed_rows``), or None without a seed.
+
+    A slot with nothing to show in a tick is given NaN landmarks: it is a session's lost frame, held up to ``hold`` ticks and then
+    passed through untouched, and its counter advances as a session's does.  Out of scope: feeds with frames of different sizes or
+    in separate allocations, stepping a subset of the slots, several frames per feed per tick, NV12."""
+
+    def __init__(self, model, identities_u8, *, size, template, contour, channel_order, identity_align, rate, track, features, feather,
+                 matte_softness, matte_grow, colour_match, colour_decay, seed, noise, offset):
+        from .irfd import _check_noise
+        what = "live_room"
+        template = self._configure(what, model, size=size, template=template, contour=contour, channel_order=channel_order, rate=rate, track=track,
+                                   features=features, feather=feather, matte_softness=matte_softness, matte_grow=matte_grow,
+                                   colour_match=colour_match, colour_decay=colour_decay, offset=offset)
+        if isinstance(identities_u8, torch.Tensor):
+            if identities_u8.dim() != 4:
+                raise ValueError(f"{what}: identities_u8 must be a sequence of S photos [H,W,3] or a tensor [S,H,W,3], got {tuple(identities_u8.shape)}")
+            photos = list(identities_u8.unbind(0))
+        else:
+            try:
+                photos = list(identities_u8)
+            except TypeError:
+                raise ValueError(f"{what}: identities_u8 must be a sequence of S photos [H,W,3] or a tensor [S,H,W,3], got "
+                                 f"{type(identities_u8).__name__}") from None
+        S = self.S = len(photos)
+        if S < 1:
+            raise ValueError(f"{what}: a room needs at least one feed, got S = {S} identity photos")
+        for s, photo in enumerate(photos):
+            _check_identity(what, f"identities_u8[{s}]", photo)
+            if photo.device != photos[0].device:
+                raise ValueError(f"{what}: identities_u8[{s}] on {photo.device}, identities_u8[0] on {photos[0].device}")
+        if seed is None or isinstance(seed, int):
+            _check_noise(what, noise, seed, None, 0)
+            seeds = None if seed is None else [seed] * S
+        else:
+            try:
+                seeds = list(seed)
+            except TypeError:
+                raise ValueError(f"{what}: seed must be None, one integer or {S} of them, got {type(seed).__name__}") from None
+            if len(seeds) != S:
+                raise ValueError(f"{what}: seed must be one integer or one per feed ({S}), got {len(seeds)}")
+            for v in seeds:
+                _check_noise(what, noise, v, None, 0)
+                if v is None:
+                    raise ValueError(f"{what}: a sequence of seeds holds {S} integers, got None among them")
+        self.fixed_noise = noise == "fixed"
+        aligns = self._parse_aligns(what, identity_align, photos)
+        # ---- the arguments are in order: the device
+        self.fi = torch.cat([self._encode_identity(p, a) for p, a in zip(photos, aligns)])       # Ei at batch 1, as a session runs it
+        self.device = self.fi.device
+        self._place_template(what, template)
+        K, F = self.K, 2 * self.fi[0].numel()
+        self.lm_state = None if self.track is None else FR.causal_filter_state(S * 2 * K, 2, self.device)
+        self.feature_state = None if self.features is None else FR.causal_filter_state(S * F, 1, self.device)
+        self.colour_state = torch.zeros((S, FR.COLOUR_SUMS), device=self.device, dtype=torch.float64) if colour_match else None
+        self.frames = torch.zeros(S, device=self.device, dtype=torch.int64)
+        self.seeds = None if seeds is None else ops.seed_rows(seeds, self.device)
+
+    def _parse_aligns(self, what, identity_align, photos):
+        if identity_align is None:
+            return [None] * len(photos)
+        try:
+            aligns = list(identity_align)
+        except TypeError:
+            raise ValueError(f"{what}: identity_align must be None or one per photo ({len(photos)}), got {type(identity_align).__name__}") from None
+        if len(aligns) != len(photos):
+            raise ValueError(f"{what}: identity_align must be None or one per photo ({len(photos)}), got {len(aligns)}")
+        return [None if a is None else FR.Aligned.parse(a, 1, self.size, p.device, f"{what}: identity_align[{s}]")
+                for s, (a, p) in enumerate(zip(aligns, photos))]
+
+    def _slot(self, what, slot):
+        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.S:
+            raise ValueError(f"{what}: slot must be an integer in [0, {self.S}), got {slot!r}")
+        return slot
+
+    def _states(self):
+        """The per-feed state tensors, each viewed with the slots in front"""
+        return [t.view(self.S, -1) for t in (self.lm_state, self.feature_state, self.colour_state, self.frames) if t is not None]
+
+    def reset(self, slot=None):
+        """Empties the filter states and the frame counter of ``slot`` (None: of every slot): its next tick is the first of a feed.
+        ``fi`` stays; no other slot is touched, and no device value is read."""
+        if slot is not None:
+            slot = self._slot("live_room.reset", slot)
+        for t in self._states():
+            (t if slot is None else t[slot]).zero_()
+
+    @torch.no_grad()
+    def set_identity(self, slot, identity_u8, identity_align=None):
+        """A new call in ``slot``: ``Ei`` on ``identity_u8`` ([H,W,3] or [1,H,W,3]; ``identity_align``: as ``IRFD.live``) into ``fi[slot]``,
+        and the slot reset.  No other slot's state or output changes."""
+        what = "live_room.set_identity"
+        slot = self._slot(what, slot)
+        _check_identity(what, "identity_u8", identity_u8)
+        if identity_align is not None:
+            identity_align = FR.Aligned.parse(identity_align, 1, self.size, identity_u8.device, f"{what}: identity_align")
+        fi = self._encode_identity(identity_u8, identity_align)
+        if fi.device != self.device:
+            raise L.SpkError(f"{what}: the photo on {fi.device}, the room on {self.device}")
+        self.fi[slot].copy_(fi[0])
+        self.reset(slot)
+
+    # ---- a batch row is this tick's frame of the next feed: one frame of S times the components, every feed with its own groups
+    def _steady(self, landmarks, weights):
+        S, K = self.S, self.K
+        y, wy = FR.causal_filter(landmarks.reshape(1, S * K * 2), self.lm_state, weights=weights, **self.track)
+        return y.view(S, K, 2), wy.view(S, K)
+
+    def _steady_features(self, f):
+        flat = f.view(1, -1)
+        FR.causal_filter(flat, self.feature_state, out=flat, **self.features)
+
+    def _fi(self, N):
+        return self.fi
+
+    def _seeded(self):
+        return None if self.seeds is None else dict(seed_rows=self.seeds, frame_rows=self.frames)
+
+    def _colour_rows(self, sums):
+        return FR.colour_rows_causal_feeds(sums.view(1, self.S, FR.COLOUR_SUMS), self.colour_state, self.colour_decay).view(self.S, 3, 2)
+
+    def _weights(self, what, weights):
+        """``weights``: None, or per feed ``[S,K]``, or one ``[K]`` set for every feed; host numbers or a device float32 tensor ->
+        None or a float32 tensor ``[S K]``, where it came from (not read)"""
+        if weights is None:
+            return None
+        S, K = self.S, self.K
+        if isinstance(weights, torch.Tensor) and weights.is_cuda:
+            if weights.dtype != torch.float32 or tuple(weights.shape) not in ((K,), (S, K)):
+                raise ValueError(f"{what}: device weights must be a float32 tensor [{K}] or [{S},{K}], got {weights.dtype} {tuple(weights.shape)}")
+        else:
+            try:
+                weights = torch.as_tensor(weights).to(torch.float64).to(torch.float32)
+            except (ValueError, TypeError, RuntimeError) as e:
+                raise ValueError(f"{what}: weights must be [{K}] or [{S},{K}] numbers: {e}") from None
+            if tuple(weights.shape) not in ((K,), (S, K)):
+                raise ValueError(f"{what}: weights must be [{K}] numbers for every feed or [{S},{K}], one set per feed, got {tuple(weights.shape)}")
+        return weights.expand(S, K).reshape(S * K)
+
+    @torch.no_grad()
+    def step(self, frames_u8, landmarks, *, weights=None, emotion_u8=None, inplace=False):
+        """One tick: ``frames_u8`` uint8 ``[S,H,W,3]`` on the device, this tick's frame of every feed; ``landmarks`` device float32
+        ``[S,K,2]`` (NaN for a feed with nothing to show); ``weights``: the tracker's confidences per feed ``[S,K]``, or one ``[K]`` set
+        for all feeds, host numbers or a device float32 tensor; ``emotion_u8``: the frames ``Ee`` sees (None: ``frames_u8``).  ->
+        uint8 ``[S,H,W,3]`` (``inplace=True``: ``frames_u8`` itself).  The steps are ``LiveSession.step``'s with the feeds as the batch;
+        the number of launches does not depend on ``S``, and no device value is read on the host."""
+        what = "live_room.step"
+        S, K = self.S, self.K
+        if not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != S:
+            got = tuple(frames_u8.shape) if isinstance(frames_u8, torch.Tensor) else type(frames_u8).__name__
+            raise ValueError(f"{what}: frames must be [{S},H,W,3], one frame per feed, got {got}")
+        if not isinstance(landmarks, torch.Tensor) or tuple(landmarks.shape) != (S, K, 2):
+            got = tuple(landmarks.shape) if isinstance(landmarks, torch.Tensor) else type(landmarks).__name__
+            raise ValueError(f"{what}: landmarks must be [{S},{K},2], {K} points per feed as the template has, got {got}")
+        self._check_step(what, frames_u8, emotion_u8, inplace)
+        weights = self._weights(what, weights)
+        if self.track is None and weights is not None:                     # the fit takes them per frame
+            weights = weights.view(S, K)
+        out = self._body(what, frames_u8, landmarks, weights, emotion_u8, inplace)
+        if not self.fixed_noise:
+            self.frames.add_(1)
         return out

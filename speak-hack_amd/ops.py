@@ -20,7 +20,7 @@ from .frames import (resize_tables, resize_tables_f32, feather_tables, parse_box
                      paste_colour_match, ellipse_matte, similarity_from_landmarks, smooth_similarity_rows, LandmarkAlign,
                      frames_from_nv12_aligned, frames_paste_nv12_aligned, paste_colour_match_nv12, matte_from_landmarks, LandmarkMatte,
                      paste_colour_sums, paste_colour_sums_nv12, colour_rows_from_sums, causal_filter, causal_filter_state,
-                     colour_rows_causal)
+                     colour_rows_causal, colour_rows_causal_feeds)
 
 
 def _launch_conv2d(desc):
@@ -1515,4 +1515,72 @@ def decoder_noise(shapes, seed, *, frame0=0, fixed=False, device):
     hw = [s[2] * s[3] for s in shapes]
     flat = torch.empty(B * sum(hw), device=device, dtype=torch.float32)
     noise_fill(flat, hw, B, seed, frame0=frame0, fixed=fixed)
+    return [t.view(s) for t, s in zip(flat.split([B * v for v in hw]), shapes)]
+
+
+# ---- the same noise with one (seed, frame) per batch row, read from device tables (spk_noise_fill_rows) -------------------------
+def seed_rows(seeds, device=None):
+    """Seeds (integers in [0, 2**64)) as the table ``noise_fill_rows`` reads: an int64 tensor ``[B]`` that holds their 64-bit
+    PATTERNS (a seed >= 2**63 is stored as ``seed - 2**64``), on ``device`` (None: the host)."""
+    try:
+        seeds = list(seeds)
+    except TypeError:
+        raise ValueError(f"seed_rows: seeds must be a sequence of integers, got {type(seeds).__name__}") from None
+    if not seeds:
+        raise ValueError("seed_rows: no seeds")
+    for s in seeds:
+        check_seed(s, 0, "seed_rows: every seed")
+    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device=device)
+
+
+def check_rows_tables(what, seed_rows, frame_rows, B):
+    """The two tables of a rows fill, checked on the host (the values stay on the device, unread)"""
+    for t, name in ((seed_rows, "seed_rows"), (frame_rows, "frame_rows")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != (B,):
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}: {name} must be an int64 tensor [{B}], one entry per batch row, got {got}")
+    for t, name in ((seed_rows, "seed_rows"), (frame_rows, "frame_rows")):
+        if not t.is_cuda:
+            raise L.SpkError(f"{what}: {name} on {t.device}: the tables are read on the device (no CPU path)")
+        if not t.is_contiguous():
+            raise L.SpkError(f"{what}: {name}: expected a contiguous tensor, got strides {t.stride()}")
+
+
+def noise_fill_rows_args(dst_ptr, hw, B, *, seeds_ptr=None, frames_ptr=None, layer0=0):
+    """``spk_noise_fill_rows_args`` for planes of ``hw[l]`` pixels (layer ids ``layer0 + l``), ``B`` rows each."""
+    hw = [int(v) for v in hw]
+    if not 1 <= len(hw) <= L.NOISE_MAX_LAYERS:
+        raise L.SpkError(f"noise_fill_rows: between 1 and {L.NOISE_MAX_LAYERS} layers per launch, got {len(hw)}")
+    a = L.NoiseFillRowsArgs(dst=dst_ptr, seeds_dev=seeds_ptr, frames_dev=frames_ptr, B=B, n_layers=len(hw), layer0=layer0)
+    for l, v in enumerate(hw):
+        a.hw[l] = v
+    return a
+
+
+def noise_fill_rows(dst, hw, B, seed_rows, frame_rows, *, layer0=0):
+    """``noise_fill`` with one ``(seed, frame)`` per batch row: row ``b`` of every layer is the noise of ``(seed_rows[b],
+    frame_rows[b])``, two device int64 ``[B]`` tables (``ops.seed_rows`` makes the first) that the kernel reads -- the host never
+    does, so their owner can advance them on the device.  One launch (``spk_noise_fill_rows``).  -> ``dst``."""
+    check_rows_tables("noise_fill_rows", seed_rows, frame_rows, B)
+    if dst.numel() != B * sum(int(v) for v in hw):
+        raise L.SpkError(f"noise_fill_rows: dst holds {dst.numel()} floats, the layers need {B * sum(int(v) for v in hw)}")
+    if seed_rows.device != dst.device or frame_rows.device != dst.device:
+        raise L.SpkError(f"noise_fill_rows: tables on {seed_rows.device} / {frame_rows.device}, dst on {dst.device}")
+    a = noise_fill_rows_args(L.dptr(dst, "dst"), hw, B, seeds_ptr=seed_rows.data_ptr(), frames_ptr=frame_rows.data_ptr(), layer0=layer0)
+    L.check(L.lib().spk_noise_fill_rows(C.byref(a), L.stream_ptr()), "spk_noise_fill_rows")
+    return dst
+
+
+def decoder_noise_rows(shapes, seed_rows, frame_rows):
+    """``decoder_noise`` with one ``(seed, frame)`` per batch row (``noise_fill_rows``): -> the list of [B,1,H,W] tensors whose
+    value at row ``b``, layer ``l``, pixel ``p`` is the function of ``(seed_rows[b], frame_rows[b], l, p)``, on the tables' device.
+    What a rows-seeded plan (``plan.DecoderPlan(seeded="rows")``) draws inside its launch list, bit for bit."""
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    if not shapes or any(len(s) != 4 or s[1] != 1 or s[0] != shapes[0][0] for s in shapes):
+        raise ValueError(f"decoder_noise_rows: shapes must be [B,1,H,W] with one B, got {shapes}")
+    B = shapes[0][0]
+    check_rows_tables("decoder_noise_rows", seed_rows, frame_rows, B)
+    hw = [s[2] * s[3] for s in shapes]
+    flat = torch.empty(B * sum(hw), device=seed_rows.device, dtype=torch.float32)
+    noise_fill_rows(flat, hw, B, seed_rows, frame_rows)
     return [t.view(s) for t, s in zip(flat.split([B * v for v in hw]), shapes)]

@@ -180,7 +180,11 @@ class DecoderPlan(LaunchPlan):
     ``seeded=True``: the list starts with ``SPK_OP_NOISE_FILL`` (csrc/noise.hip), which writes ``noise_flat`` from the
     ``seed`` / ``frame0`` each ``run`` patches into its descriptor -- the noise of ``ops.decoder_noise``, bit for bit, and the
     forward is the launch list alone (no ATen draw, the device generator untouched).  A seeded plan runs seeded calls only, an
-    unseeded one (the default: built and run exactly as before) unseeded calls only."""
+    unseeded one (the default: built and run exactly as before) unseeded calls only.
+    ``seeded="rows"``: the first op is ``SPK_OP_NOISE_FILL_ROWS`` instead, whose batch row ``b`` is the noise of ``(seed_rows[b],
+    frame_rows[b])``: two device int64 ``[B]`` tables (``ops.noise_fill_rows``) whose pointers each ``run`` patches in -- the noise of
+    ``ops.decoder_noise_rows``, bit for bit.  The kernel reads the tables, the host never does.  A rows-seeded plan runs calls with
+    tables only, and the other two forms refuse them."""
 
     def __init__(self, synthesis, B, device, generator=None, precision="f32", output="f32", value_range=(-1, 1), swap_rb=False,
                  seeded=False, standard="bt601", full_range=False):
@@ -190,7 +194,10 @@ class DecoderPlan(LaunchPlan):
         s = self.synthesis = synthesis
         self.precision = precision
         self.output = output
-        self.seeded = bool(seeded)
+        if isinstance(seeded, str) and seeded != "rows":
+            raise ValueError(f"DecoderPlan: seeded must be False, True or 'rows', got {seeded!r}")
+        self.seed_rows = isinstance(seeded, str)
+        self.seeded = bool(seeded) and not self.seed_rows
         self.B, self.with_mapping = B, generator is not None
         mods = [s.style_mod] + [m for layer in s.layers for m in (layer.style_mod1, layer.style_mod2)]
         if len(mods) > L.FC_MAX_GROUPS:
@@ -233,6 +240,9 @@ class DecoderPlan(LaunchPlan):
         if self.seeded:        # the draw is the FIRST op of the list; seed / frame0 / frame_step are patched per call
             self.noise_fill = ops.noise_fill_args(self.noise_flat.data_ptr(), [sh[2] * sh[3] for sh in shapes], B)
             self.ops.insert(0, (L.OP_NOISE_FILL, self.noise_fill))
+        elif self.seed_rows:   # the same place in the list; the two table pointers are patched per call
+            self.noise_fill = ops.noise_fill_rows_args(self.noise_flat.data_ptr(), [sh[2] * sh[3] for sh in shapes], B)
+            self.ops.insert(0, (L.OP_NOISE_FILL_ROWS, self.noise_fill))
         # ---- prologue (styleganv1.py:596-599) ----
         C0 = s.const_input.shape[1]
         pp = [self.buf(B * max(self._act_floats(s)))  for _ in range(2)]
@@ -311,12 +321,25 @@ class DecoderPlan(LaunchPlan):
             sizes.append(layer.out_channels * res * res)
         return sizes
 
-    def run(self, x, noises=None, kind_mask=L.ALL_OPS, *, seed=None, frame0=0, fixed_noise=False):
+    def run(self, x, noises=None, kind_mask=L.ALL_OPS, *, seed=None, frame0=0, fixed_noise=False, seed_rows=None, frame_rows=None):
         """``x``: features [B,input_dim] (plan built with the generator) or dlatents w [B,L,512].  A seeded plan takes ``seed``
         (0 <= seed < 2**64), ``frame0`` (row b is frame ``frame0 + b``) and ``fixed_noise`` (every row is frame ``frame0``) and
         patches them into the noise op's descriptor, as pointers are patched; ``seed`` together with ``noises`` is a
         ``ValueError``.  A hipGraph capture of a seeded run bakes ``seed`` and ``frame0`` into the graph, as it bakes addresses:
-        every replay draws the noise of the captured call."""
+        every replay draws the noise of the captured call.  A rows-seeded plan takes ``seed_rows`` and ``frame_rows`` instead (device
+        int64 ``[B]``, as ``ops.noise_fill_rows`` takes them) and nothing else about the noise."""
+        if (seed_rows is None) != (frame_rows is None):
+            raise ValueError("DecoderPlan.run: seed_rows and frame_rows go together")
+        if seed_rows is not None:
+            if not self.seed_rows:
+                raise ValueError("DecoderPlan.run: seed_rows / frame_rows given to a plan that was not built with seeded='rows'")
+            if seed is not None or noises is not None or fixed_noise:
+                raise ValueError("DecoderPlan.run: a rows-seeded call takes its noise from the tables alone (no seed, fixed_noise or noises)")
+            ops.check_rows_tables("DecoderPlan.run", seed_rows, frame_rows, self.B)
+            if seed_rows.device != self.device or frame_rows.device != self.device:
+                raise L.SpkError(f"DecoderPlan.run: tables on {seed_rows.device} / {frame_rows.device}, the plan on {self.device}")
+        elif self.seed_rows:
+            raise ValueError("DecoderPlan.run: a rows-seeded plan needs seed_rows and frame_rows")
         if seed is not None and noises is not None:
             raise ValueError("DecoderPlan.run: pass either seed or noises, not both")
         if self.seeded != (seed is not None):
@@ -340,6 +363,8 @@ class DecoderPlan(LaunchPlan):
             a = self.noise_fill         # (the 13 noise pointers stay on noise_views: a seeded plan never sees explicit noise)
             a.seed, a.frame0 = ops.check_seed(seed, frame0)
             a.frame_step = 0 if fixed_noise else 1
+        elif self.seed_rows:
+            self.noise_fill.seeds_dev, self.noise_fill.frames_dev = seed_rows.data_ptr(), frame_rows.data_ptr()
         elif noises is None:
             self.noise_flat.normal_()
             for d, nv in zip(self.noise_ops, self.noise_views):

@@ -753,12 +753,9 @@ def bench_colour_smooth(args, lines):
         lines.append(f"  (b) / (c) = {bc:.3f}" + ("  -> (b) beats (c) by more than the spread" if bc < 1 - spread else "  -> (b) does NOT beat (c) by more than the spread"))
 
 
-def bench_live(args, lines):
-    """``--live``: the latency of ONE frame of a live feed (1080 x 1920 BGR frames, K = 68 landmarks, 256^2 network and generated
-    images, N = 1), wall clock, synchronised before and after every call, two ways.  (a) ``LiveSession.step``: ``Ei`` ran once, the
-    landmarks, the features and the colour statistics are steadied by the causal filters.  (b) what a caller could do before:
-    ``reenact_video(align=LandmarkAlign(...), paste=True, matte=LandmarkMatte(..., smooth=0), colour_match=True)`` on a clip of one
-    frame, per frame -- ``Ei`` on every call, and no temporal state at all.  Then the two new launches alone, by HIP events."""
+def live_scene(T):
+    """What ``--live`` and ``--live-room`` measure on: the model with recipe weights, a 68-point template with an outline of 27, ``T``
+    frames of 1080 x 1920 BGR with tracked landmarks over a rotated 400 x 400 region, and the settings of a session"""
     import importlib
 
     import model
@@ -767,7 +764,7 @@ def bench_live(args, lines):
 
     ops = importlib.import_module("speak-hack_amd").ops
     dev = torch.device("cuda:0")
-    T, size, Hf, Wf, side, feather, K, per = max(args.frames, 8), 256, 1080, 1920, 400, 16, 68, 20
+    size, Hf, Wf, side, feather, K = 256, 1080, 1920, 400, 16, 68
     g = torch.Generator().manual_seed(0)
     ring = torch.arange(27, dtype=torch.float64) * (2 * math.pi / 27)       # an outline of 27 points, 41 points inside it
     inner = torch.rand(K - 27, 2, generator=g, dtype=torch.float64) * 100 + 78
@@ -787,6 +784,21 @@ def bench_live(args, lines):
     m.load_state_dict(sd, strict=False)
     m.to(dev).eval()
     common = dict(size=size, channel_order="bgr", feather=feather, colour_match=True, seed=7)
+    return dict(ops=ops, dev=dev, m=m, g=g, template=template, contour=contour, lm=lm, ident=ident, video=video, true=true, common=common,
+                size=size, Hf=Hf, Wf=Wf, side=side, feather=feather, K=K)
+
+
+def bench_live(args, lines):
+    """``--live``: the latency of ONE frame of a live feed (1080 x 1920 BGR frames, K = 68 landmarks, 256^2 network and generated
+    images, N = 1), wall clock, synchronised before and after every call, two ways.  (a) ``LiveSession.step``: ``Ei`` ran once, the
+    landmarks, the features and the colour statistics are steadied by the causal filters.  (b) what a caller could do before:
+    ``reenact_video(align=LandmarkAlign(...), paste=True, matte=LandmarkMatte(..., smooth=0), colour_match=True)`` on a clip of one
+    frame, per frame -- ``Ei`` on every call, and no temporal state at all.  Then the two new launches alone, by HIP events."""
+    T, per = max(args.frames, 8), 20
+    sc = live_scene(T)
+    ops, dev, m, g, template, contour, lm, ident, video, true, common = (sc[k] for k in ("ops", "dev", "m", "g", "template", "contour", "lm", "ident",
+                                                                                          "video", "true", "common"))
+    size, Hf, Wf, side, feather, K = (sc[k] for k in ("size", "Hf", "Wf", "side", "feather", "K"))
     session = m.live(ident, template=template, contour=contour, features={}, **common)
     bare = m.live(ident, template=template, contour=contour, track=None, features=None, colour_decay=0.0, **common)
 
@@ -828,6 +840,82 @@ def bench_live(args, lines):
         lines.append(f"  {name:48s} median {statistics.median(ts) * 1e6:7.1f} us  min {ts[0] * 1e6:7.1f}  max {ts[-1] * 1e6:7.1f}")
 
 
+def bench_live_room(args, lines):
+    """``--live-room``: one TICK of a server with S calls, S in {1, 2, 4, 8} (the frames, landmarks and settings of ``--live``), wall
+    clock, synchronised before and after every tick, two ways.  (a) ``LiveRoom.step``: the S frames as one batch.  (b) what a server
+    could do before: S ``LiveSession.step`` calls of one frame each, one after another, no synchronisation between them.  The
+    contenders alternate in one process, (a) entered twice for the spread.  Then the two new launches alone, by HIP events.
+    -> whether the one condition holds: at S = 8, (a) takes less than (b) by more than the spread."""
+    T, per, sizes = 8, 20, (1, 2, 4, 8)
+    sc = live_scene(T)
+    ops, dev, m, template, contour, lm, ident, video, common = (sc[k] for k in ("ops", "dev", "m", "template", "contour", "lm", "ident", "video", "common"))
+    size, Hf, Wf, K = (sc[k] for k in ("size", "Hf", "Wf", "K"))
+    kw = dict(common, template=template, contour=contour, features={})
+    del kw["seed"]
+    lines.append(f"a tick of S feeds of {Hf}x{Wf} BGR, one frame per feed, K = {K} landmarks, outline of {len(contour)}, {size}^2 in and out, feather "
+                 f"{sc['feather']}, matte, colour match and the three filters; median of {args.repeats} alternating rounds of {per} ticks")
+    met = None
+    for S in sizes:
+        show = torch.tensor([[(t + s) % T for s in range(S)] for t in range(T)], device=dev)
+        ticks, lms = video[show].contiguous(), lm[show].contiguous()      # [T,S,...]: feed s shows frame (t + s) % T in tick t
+        room = m.live_room([ident] * S, seed=list(range(7, 7 + S)), **kw)
+        sessions = [m.live(ident, seed=7 + s, **kw) for s in range(S)]
+
+        def tick_room(t):
+            return room.step(ticks[t], lms[t])
+
+        def tick_sessions(t):
+            return [s.step(ticks[t, i:i + 1], lms[t, i:i + 1]) for i, s in enumerate(sessions)]
+
+        def latency(fn):                                                   # the mean wall clock of `per` ticks, each synchronised on its own
+            total = 0.0
+            for i in range(per):
+                total += wall(lambda: fn(i % T))
+            return total / per
+
+        names = (f"(a) LiveRoom.step, S = {S}", f"(b) {S} x LiveSession.step, one frame each")
+        contenders = {names[0]: tick_room, names[1]: tick_sessions, names[0] + " (again)": tick_room}
+        for fn in contenders.values():
+            for t in range(args.warmup + 1):
+                fn(t)
+        room.reset()
+        for s in sessions:
+            s.reset()
+        differ = int((tick_room(0) != torch.cat(tick_sessions(0))).sum())   # slot s is session s: the same bytes
+        times = alternate(contenders, args.repeats, latency)
+        ratio_table(lines, f"S = {S}: wall clock per tick, synchronised before and after each tick:", times, names[0], [(names[1], True)])
+        med = {n: statistics.median(ts) for n, ts in times.items()}
+        lines.append(f"  per feed: (a) {med[names[0]] / S * 1e6:.1f} us, (b) {med[names[1]] / S * 1e6:.1f} us; bytes of the first tick that differ "
+                     f"between (a) and (b): {differ}")
+        if S == sizes[-1]:
+            spread = abs(med[names[0]] - med[names[0] + " (again)"]) / min(med[names[0]], med[names[0] + " (again)"])
+            met = med[names[0]] / med[names[1]] < 1 - spread
+    lines.append(f"the condition -- at S = {sizes[-1]} a room tick takes less than the {sizes[-1]} single steps beside it, by more than the spread: "
+                 + ("MET" if met else "NOT MET"))
+    S = sizes[-1]
+    shapes = m.Gd.synthesis.noise_shapes(S)
+    hw = [s[2] * s[3] for s in shapes]
+    flat = torch.empty(S * sum(hw), device=dev)
+    seeds, frames = ops.seed_rows(range(7, 7 + S), dev), torch.arange(S, device=dev)
+    sums = ops.paste_colour_sums(torch.zeros(S, 3, size, size, device=dev), video[:S], sc["true"][:S].float().to(dev), channel_order="bgr")
+    P, P1 = torch.zeros(S, 13, dtype=torch.float64, device=dev), torch.zeros(13, dtype=torch.float64, device=dev)
+    rows, rows1 = torch.empty(1, S, 3, 2, device=dev), torch.empty(1, 3, 2, device=dev)
+    feeds, ones = sums.view(1, S, 13), [sums[s:s + 1] for s in range(S)]
+
+    def one_by_one():
+        for s in range(S):
+            ops.colour_rows_causal(ones[s], P1, 0.9, out=rows1)
+
+    lines.append(f"the new launches alone at S = {S}, HIP events around 20 calls, launchers included:")
+    for name, fn in ((f"noise_fill_rows, the decoder's 13 planes, B = {S}", lambda: ops.noise_fill_rows(flat, hw, S, seeds, frames)),
+                     (f"noise_fill, the same planes, one (seed, frame0)", lambda: ops.noise_fill(flat, hw, S, 7)),
+                     (f"colour_rows_causal_feeds, S = {S}, N = 1", lambda: ops.colour_rows_causal_feeds(feeds, P, 0.9, out=rows)),
+                     (f"{S} x colour_rows_causal, N = 1", one_by_one)):
+        ts = sorted(device_time(fn) for _ in range(args.repeats))
+        lines.append(f"  {name:52s} median {statistics.median(ts) * 1e6:7.1f} us  min {ts[0] * 1e6:7.1f}  max {ts[-1] * 1e6:7.1f}")
+    return bool(met)
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -866,11 +954,18 @@ def main():
     ap.add_argument("--landmark-matte", action="store_true", help="landmarks -> matte: matte_from_landmarks, the host route, a torch composition")
     ap.add_argument("--colour-smooth", action="store_true", help="colour rows of a chunk: per frame, pooled over a window of sums, and filtered on the host")
     ap.add_argument("--live", action="store_true", help="one frame of a live feed: LiveSession.step beside reenact_video on a clip of one frame")
+    ap.add_argument("--live-room", action="store_true", help="a tick of S live feeds: LiveRoom.step beside S LiveSession.step calls; exit status 1 "
+                    "unless the room wins at S = 8 by more than the spread")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.live_room:
+        lines = [f"bench_frame_io --live-room: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        met = bench_live_room(args, lines)
+        report(lines, args.out or os.path.join(ROOT, "profiles", "live_room_bench.txt"))
+        return 0 if met else 1
     if args.live:
-        lines = [f"bench_frame_io --live: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        lines = [f"bench_frame_io --live:{torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
         bench_live(args, lines)
         return report(lines, args.out or os.path.join(ROOT, "profiles", "live_bench.txt"))
     if args.colour_smooth:
@@ -985,4 +1080,4 @@ def report(lines, out):
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

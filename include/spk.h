@@ -1091,6 +1091,50 @@ int spk_paste_colour_sums_nv12_sim(const float* src, int N, int Hs, int Ws, cons
 int spk_colour_rows_window(const double* sums_dev, int T, int n0, int n, int radius, double sigma, double max_gain, double min_sigma,
                            double min_weight, float* rows_out_dev, void* stream);
 
+/* ---- the aligned edge over a frame table: every frame its own buffer and size (csrc/frame_table.hip) -----------------------------
+ * The entry points above address N frames of ONE size through one pointer and two byte strides.  A server with several calls has
+ * neither: each call's decoder delivers into a buffer of its own, and the calls differ in resolution.  These entry points take a
+ * FRAME TABLE instead: N entries of spk_frame_ref in DEVICE memory, 8-byte aligned,
+ *     data: the first byte of the frame;  row_stride: bytes from row to row;  H, W: its size in pixels (pixel stride 3)
+ * which the kernels read and the entry points never do.  Frame n uses entry n, sim row n, matte n (or the shared matte) and colour
+ * row n.  An entry is USABLE when data != NULL, H >= 1, W >= 1 and row_stride >= 3 W; any other entry means THE FRAME IS ABSENT.
+ * The kernels test this themselves before they form an address from an entry, so an all-zero entry is safe, and an absent frame is
+ * treated exactly like an invalid sim row: the way in writes shift_c, the paste leaves everything alone, the sums are 13 zeros
+ * (the rows (1, 0)).  A usable entry is trusted as a strided call's pointer and strides are: its bytes must be the caller's.
+ *
+ * spk_frames_u8_to_f32_sim_table: frame n of dst is bit for bit spk_frames_u8_to_f32_sim called with N = 1 on entry n's (data,
+ *   row_stride, H, W), row n of sim_dev and the same remaining arguments.  One launch.
+ * spk_frames_paste_u8_sim_table: one entry point for the plain and the seamless paste, as the NV12 paste has; matte_dev and
+ *   colour_dev may be NULL.  Frame n is bit for bit spk_frames_paste_u8_sim (both NULL) or spk_frames_paste_u8_sim_blend at N = 1 on
+ *   entry n with row, matte and colour row n.  The frames of the table are WRITTEN: usable entries must not share bytes
+ *   (spk_frame_table_check with written = 1 on the host copy).  One launch.
+ * spk_paste_colour_sums_sim_table / spk_paste_colour_match_sim_table: the arguments of spk_paste_colour_sums_sim /
+ *   spk_paste_colour_match_sim with table_dev in place of dst, image_stride, row_stride, H, W: the same workspace, the same
+ *   fixed-order reduction, the same finishing kernels and row formula, frame n bit for bit the strided call at N = 1.  Two launches.
+ * Refused before any launch (SPK_EINVAL, spk_last_error): what the strided siblings refuse of the arguments they share; a null or
+ *   misaligned table; a table that overlaps dst (way in), the sums / colour rows or the workspace (statistics).
+ * spk_frame_table_check: pure host code over a HOST copy of a table, what a binder calls before it uploads.  Refused, with the
+ *   first offending index (or pair) in spk_last_error: a null table; N < 1; a half-formed entry (not usable and not all zero); an
+ *   extent (H - 1) row_stride + 3 W that overflows 64 bits, or whose last byte's address does; and, with written != 0, two usable
+ *   entries whose byte ranges [data, data + extent) overlap -- ranges that touch are apart, and written = 0 tolerates overlap (the
+ *   way in and the statistics only read).
+ * replaces: a torch.stack of the feeds' frames in front of every tick and a copy back to every feed behind it -- possible only
+ *   where the sizes agree -- or one pass of inference.py:46-58,78-86 per feed. */
+typedef struct spk_frame_ref { const uint8_t* data; int64_t row_stride; int32_t H, W; } spk_frame_ref;   /* 24 bytes: 8, 8, 4, 4 */
+int spk_frame_table_check(const spk_frame_ref* host_table, int N, int written);
+int spk_frames_u8_to_f32_sim_table(const spk_frame_ref* table_dev, int N, const float* sim_dev, int swap_rb, float* dst, int Hout, int Wout,
+                                   float scale0, float scale1, float scale2, float shift0, float shift1, float shift2, void* stream);
+int spk_frames_paste_u8_sim_table(const float* src, int N, int Hs, int Ws, const spk_frame_ref* table_dev, const float* sim_dev, int swap_rb,
+                                  double feather, float lo, float k, const float* matte_dev, int matte_frames, const float* colour_dev,
+                                  void* stream);
+int spk_paste_colour_match_sim_table(const float* src, int N, int Hs, int Ws, const spk_frame_ref* table_dev, const float* sim_dev, int swap_rb,
+                                     double feather, float lo, float k, const float* matte_dev, int matte_frames, double max_gain,
+                                     double min_sigma, double min_weight, float* colour_out_dev, void* workspace_dev, size_t workspace_bytes,
+                                     void* stream);
+int spk_paste_colour_sums_sim_table(const float* src, int N, int Hs, int Ws, const spk_frame_ref* table_dev, const float* sim_dev, int swap_rb,
+                                    double feather, float lo, float k, const float* matte_dev, int matte_frames, double* sums_out_dev,
+                                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- causal filters with their state on the device: what a live feed can use (csrc/causal_filter.hip) ------------------------------
  * spk_sim_smooth, the contour window of spk_matte_from_landmarks and spk_colour_rows_window look at frames t - r ... t + r: they
  * serve a clip that is in memory.  On a camera or call feed frame t + 1 does not exist yet.  These two are the causal counterparts:

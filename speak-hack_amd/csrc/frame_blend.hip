@@ -27,10 +27,9 @@ struct RgbBackground {
     const uint8_t* dst;
     long long image_stride, row_stride;
     int swap_rb;
-    __device__ __forceinline__ void load(long long n, int X, int Y, double (&b)[3]) const {
-        const uint8_t* bg = dst + n * image_stride + (long long)Y * row_stride + (long long)X * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) b[c] = (double)bg[swap_rb ? 2 - c : c];
+    __device__ __forceinline__ LaunchFrame frame(long long, int H, int W) const { return {H, W}; }
+    __device__ __forceinline__ void load(const LaunchFrame&, long long n, int X, int Y, double (&b)[3]) const {
+        rgb_background(dst + n * image_stride + (long long)Y * row_stride + (long long)X * 3, swap_rb, b);
     }
 };
 

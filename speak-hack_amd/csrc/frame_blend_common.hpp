@@ -20,9 +20,10 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // The statistics, first kernel.  The paste's decomposition; workgroup g of frame n leaves its 13 sums in part[n][g][0..13), zeros
-// when the row is invalid or the box is empty.  Every branch around the barriers depends on n alone: uniform in the workgroup.
-// Background: how a format reads the background of region pixel (Y, X) of frame n -- bg.load(n, X, Y, b) leaves b[c], the value
-// under NETWORK channel c, in byte units; everything else is the same code for every format.
+// when the row is invalid, the frame is absent or the box is empty.  Every branch around the barriers depends on n alone: uniform
+// in the workgroup.  Background: how a format reads the background of region pixel (Y, X) of frame n -- bg.frame(n, H, W) is the
+// frame (csrc/frame_sim_common.hpp), bg.load(frame, n, X, Y, b) leaves b[c], the value under NETWORK channel c, in byte units;
+// everything else is the same code for every format.
 template <class Background>
 __global__ __launch_bounds__(256) void paste_colour_sums_kernel(const float* __restrict__ src, int N, int Hs, int Ws, Background bg, int H, int W,
                                                                 const float* __restrict__ sim, double feather, float lo, float k,
@@ -35,8 +36,9 @@ __global__ __launch_bounds__(256) void paste_colour_sums_kernel(const float* __r
 #pragma unroll
         for (int t = 0; t < SUMS; ++t) acc[t] = 0.0;
         const Sim m = load_sim(sim, n);
+        const auto fr = bg.frame(n, H, W);
         RegionBox box = {0, -1, 0, -1};
-        if (m.valid) box = region_box(m, Hs, Ws, H, W);
+        if (m.valid && fr.usable()) box = region_box(m, Hs, Ws, fr.H, fr.W);
         if (box.x_lo <= box.x_hi && box.y_lo <= box.y_hi) {
             const long long bw = box.x_hi - box.x_lo + 1, total = bw * (box.y_hi - box.y_lo + 1);
             const PixelConsts pc = pixel_consts(m, feather);
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(256) void paste_colour_sums_kernel(const float* __r
                 double mm;
                 if (!region_pixel(m, pc, X, Y, img, plane, Hs, Ws, mt, lo, k, q, mm)) continue;
                 double bc[3];
-                bg.load(n, X, Y, bc);
+                bg.load(fr, n, X, Y, bc);
                 acc[0] += mm;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {

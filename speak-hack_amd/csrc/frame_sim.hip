@@ -17,17 +17,14 @@ namespace {
 
 using namespace spk::frame;
 
-// The way in reads packed pixels: three byte loads per tap, and the three means are R, G, B as they stand.
-struct RgbSource {
+// The way in reads packed pixels (RgbTaps) of frames addressed by byte strides, all of the launch's size.
+struct RgbSource : RgbTaps {
     const uint8_t* src;
     long long image_stride, row_stride;
-    __device__ __forceinline__ const uint8_t* row(long long n, int iy) const { return src + n * image_stride + (long long)iy * row_stride; }
-    __device__ __forceinline__ void tap(const uint8_t* p, int ix, bool, double w, double& a0, double& a1, double& a2) const {
-        a0 = fma(w, (double)p[3 * ix], a0);
-        a1 = fma(w, (double)p[3 * ix + 1], a1);
-        a2 = fma(w, (double)p[3 * ix + 2], a2);
+    __device__ __forceinline__ LaunchFrame frame(long long, int H, int W) const { return {H, W}; }
+    __device__ __forceinline__ const uint8_t* row(const LaunchFrame&, long long n, int iy) const {
+        return src + n * image_stride + (long long)iy * row_stride;
     }
-    __device__ __forceinline__ void rgb(double m0, double m1, double m2, double (&val)[3]) const { val[0] = m0, val[1] = m1, val[2] = m2; }
 };
 
 }  // namespace
@@ -44,7 +41,7 @@ int spk_frames_u8_to_f32_sim(const uint8_t* src, int64_t image_stride, int64_t r
                 Hout, Wout);
     SPK_REQUIRE(row_stride >= 3ll * W, "%s: row stride %lld is smaller than 3 * W = %lld", who, (long long)row_stride, 3ll * W);
     SPK_REQUIRE(image_stride >= 0, "%s: negative image stride", who);
-    return launch_frames_to_f32_sim("frames_u8_to_f32_sim_kernel", RgbSource{src, (long long)image_stride, (long long)row_stride}, N, H, W, sim_dev,
+    return launch_frames_to_f32_sim("frames_u8_to_f32_sim_kernel", RgbSource{{}, src, (long long)image_stride, (long long)row_stride}, N, H, W, sim_dev,
                                     swap_rb, dst, Hout, Wout, Affine3{{scale0, scale1, scale2}, {shift0, shift1, shift2}}, stream);
 }
 

@@ -49,6 +49,43 @@ __device__ __forceinline__ RegionBox region_box(const Sim& m, int Hs, int Ws, in
     return b;
 }
 
+// ---- where a frame is: the size and the byte addresses of frame n come from the format's policy ----
+// Every policy of this edge (a Source of the way in, a Background of the statistics, a Target of the paste) answers frame(n, H, W)
+// with what it needs to address frame n -- at least its size H x W and usable() -- once per frame, outside the pixel loops.  The
+// strided formats (packed frames, NV12 planes) hold one size for the launch: their answer is the launch's H and W, always usable,
+// and their addresses stay functions of n and the launch's strides.  A tabled format loads entry n of a device table instead
+// (csrc/frame_table.hip); a frame that is not usable() is treated exactly like an invalid row.
+struct LaunchFrame {
+    int H, W;
+    __device__ __forceinline__ bool usable() const { return true; }
+};
+
+// Packed pixels: three byte loads per tap of the way in, the three means are R, G, B as they stand; the background of a region
+// pixel by network channel.
+struct RgbTaps {
+    __device__ __forceinline__ void tap(const uint8_t* p, int ix, bool, double w, double& a0, double& a1, double& a2) const {
+        a0 = fma(w, (double)p[3 * ix], a0);
+        a1 = fma(w, (double)p[3 * ix + 1], a1);
+        a2 = fma(w, (double)p[3 * ix + 2], a2);
+    }
+    __device__ __forceinline__ void rgb(double m0, double m1, double m2, double (&val)[3]) const { val[0] = m0, val[1] = m1, val[2] = m2; }
+};
+
+__device__ __forceinline__ void rgb_background(const uint8_t* bg, int swap_rb, double (&b)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) b[c] = (double)bg[swap_rb ? 2 - c : c];
+}
+
+// The paste's target in packed frames addressed by byte strides: out.pixel(frame, n, X, Y) is where pixel (Y, X) of frame n lives.
+struct RgbTarget {
+    uint8_t* dst;
+    long long image_stride, row_stride;
+    __device__ __forceinline__ LaunchFrame frame(long long, int H, int W) const { return {H, W}; }
+    __device__ __forceinline__ uint8_t* pixel(const LaunchFrame&, long long n, int X, int Y) const {
+        return dst + n * image_stride + (long long)Y * row_stride + (long long)X * 3;
+    }
+};
+
 // ---- the way out: every per-pixel quantity of the aligned paste, and the paste into packed frames ----
 struct PixelConsts { double is2, r, ir, fe; };
 
@@ -147,18 +184,20 @@ __device__ __forceinline__ void blend_pixel(uint8_t* out, int swap_rb, bool matc
 // (either may be NULL: csrc/frame_blend.hip); false: they are absent at compile time, and what is left is the plain paste of
 // csrc/frame_sim.hip, with the registers of a kernel that never had them.  The plain instance hands its store to the pixel
 // function and the seamless one asks it: the same arithmetic, and the form in which each compiles to the code it had as a kernel
-// of its own (asked, the plain instance is 15 instructions longer and 6 % slower).
-template <bool SEAMLESS>
-__global__ __launch_bounds__(256) void frames_paste_u8_sim_kernel(const float* __restrict__ src, int N, int Hs, int Ws, uint8_t* dst,
-                                                                  long long image_stride, long long row_stride, int H, int W,
-                                                                  const float* __restrict__ sim, int swap_rb, double feather, float lo, float k,
+// of its own (asked, the plain instance is 15 instructions longer and 6 % slower).  Target: where the frames are (RgbTarget: byte
+// strides; csrc/frame_table.hip: a device table); the launch's H and W are what a strided target answers with.
+template <bool SEAMLESS, class Target>
+__global__ __launch_bounds__(256) void frames_paste_u8_sim_kernel(const float* __restrict__ src, int N, int Hs, int Ws, Target out_frames, int H,
+                                                                  int W, const float* __restrict__ sim, int swap_rb, double feather, float lo, float k,
                                                                   const float* __restrict__ matte, int matte_frames,
                                                                   const float* __restrict__ colour) {
     const long long plane = (long long)Hs * Ws;
     for (long long n = blockIdx.y; n < N; n += gridDim.y) {
         const Sim m = load_sim(sim, n);
         if (!m.valid) continue;
-        const RegionBox box = region_box(m, Hs, Ws, H, W);
+        const auto fr = out_frames.frame(n, H, W);
+        if (!fr.usable()) continue;
+        const RegionBox box = region_box(m, Hs, Ws, fr.H, fr.W);
         const int x_lo = box.x_lo, x_hi = box.x_hi, y_lo = box.y_lo, y_hi = box.y_hi;
         if (x_lo > x_hi || y_lo > y_hi) continue;
         const long long bw = x_hi - x_lo + 1, total = bw * (y_hi - y_lo + 1);
@@ -170,7 +209,7 @@ __global__ __launch_bounds__(256) void frames_paste_u8_sim_kernel(const float* _
         load_colour(matched ? colour : nullptr, n, g, o);
         for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
             const int X = x_lo + (int)(idx % bw), Y = y_lo + (int)(idx / bw);
-            uint8_t* out = dst + n * image_stride + (long long)Y * row_stride + (long long)X * 3;
+            uint8_t* out = out_frames.pixel(fr, n, X, Y);
             if constexpr (SEAMLESS) {
                 float q[3];
                 double mm;
@@ -191,9 +230,10 @@ constexpr int TILE = 8;                 // a wave of the way in covers a TILE x 
 // Its footprint is the square |e_u|, |e_v| < S = max(s, 1) around p = sim(ox + 0.5, oy + 0.5), rotated with the crop: it walks the
 // bounding rows of that square inside the frame and, per row, the pixels between the two pairs of edges (intersected before the
 // loop: no tap of weight zero is loaded).  Weights and sums are fp64; no LDS, no scratch.
-// Source: where a format's bytes are read.  in.row(n, iy) opens row iy of frame n; in.tap(row, ix, first, w, a0, a1, a2) adds tap
-// ix of that row, of weight w, to the three sums (first: the row's first tap; taps come with ix rising); in.rgb(m0, m1, m2, val)
-// makes R, G, B in byte units of the three means.  Everything else is the same code for every format.
+// Source: where a format's bytes are read.  in.frame(n, H, W) is frame n (above); in.row(frame, n, iy) opens its row iy;
+// in.tap(row, ix, first, w, a0, a1, a2) adds tap ix of that row, of weight w, to the three sums (first: the row's first tap; taps
+// come with ix rising); in.rgb(m0, m1, m2, val) makes R, G, B in byte units of the three means.  Everything else is the same code
+// for every format.
 template <class Source>
 __global__ __launch_bounds__(256) void frames_to_f32_sim_kernel(Source in, int H, int W, const float* __restrict__ sim, int swap_rb,
                                                                 float* __restrict__ dst, int Hout, int Wout, int tiles_y, int tiles_x,
@@ -206,15 +246,16 @@ __global__ __launch_bounds__(256) void frames_to_f32_sim_kernel(Source in, int H
         const long long n = tile / ((long long)tiles_x * tiles_y);
         if (ox >= Wout || oy >= Hout) continue;
         const Sim m = load_sim(sim, n);
+        const auto fr = in.frame(n, H, W);                        // n is the wave's: one answer per tile
         double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, wt = 0.0;
-        if (m.valid) {
+        if (m.valid && fr.usable()) {
             const double u = ox + 0.5, v = oy + 0.5;
             const double px = m.a * u - m.c * v + m.tx, py = m.c * u + m.a * v + m.ty;
             const double S = fmax(m.s, 1.0);
             const double ia = m.a / (m.s * S), ic = m.c / (m.s * S);              // t_u = ia dx + ic dy,  t_v = -ic dx + ia dy
             const double ext = S * (fabs(m.a) + fabs(m.c)) / m.s;                // half the bounding box of the rotated square
             int y_lo, y_hi;
-            int_range(py - ext - 0.5, py + ext - 0.5, H, y_lo, y_hi);             // pixel centres iy + 0.5 within ext of py
+            int_range(py - ext - 0.5, py + ext - 0.5, fr.H, y_lo, y_hi);            // pixel centres iy + 0.5 within ext of py
             for (int iy = y_lo; iy <= y_hi; ++iy) {
                 const double dy = (iy + 0.5) - py;
                 // |ia dx + ic dy| < 1 and |-ic dx + ia dy| < 1 as intervals of dx, inside the bounding box
@@ -228,8 +269,8 @@ __global__ __launch_bounds__(256) void frames_to_f32_sim_kernel(Source in, int H
                     d_lo = fmax(d_lo, fmin(r0, r1)), d_hi = fmin(d_hi, fmax(r0, r1));
                 }
                 int x_lo, x_hi;
-                int_range(px + d_lo - 0.5, px + d_hi - 0.5, W, x_lo, x_hi);
-                auto row = in.row(n, iy);
+                int_range(px + d_lo - 0.5, px + d_hi - 0.5, fr.W, x_lo, x_hi);
+                auto row = in.row(fr, n, iy);
                 for (int ix = x_lo; ix <= x_hi; ++ix) {
                     const double dx = (ix + 0.5) - px;
                     const double w = tri(fma(ia, dx, ic * dy)) * tri(fma(-ic, dx, ia * dy));
@@ -284,15 +325,23 @@ inline int check_paste_u8(const char* who, const void* src, const void* dst, con
     return check_blend_params(who, N, feather, lo, k, matte_dev, matte_frames);
 }
 
-// the launch of the packed paste over checked arguments
+// the launch of the paste into a target's frames over checked arguments (H, W: the launch's size, which a tabled target ignores)
+template <bool SEAMLESS, class Target>
+int launch_paste_sim(const char* kernel, const float* src, int N, int Hs, int Ws, const Target& out_frames, int H, int W, const float* sim_dev,
+                     int swap_rb, double feather, float lo, float k, const float* matte_dev, int matte_frames, const float* colour_dev,
+                     void* stream) {
+    hipLaunchKernelGGL((frames_paste_u8_sim_kernel<SEAMLESS, Target>), dim3(PASTE_WGS, (unsigned)std::min(N, 65535)), dim3(256), 0,
+                       (hipStream_t)stream, src, N, Hs, Ws, out_frames, H, W, sim_dev, swap_rb, feather, lo, k, matte_dev, matte_frames, colour_dev);
+    return spk::check_launch(kernel);
+}
+
+// ... into packed frames addressed by byte strides
 template <bool SEAMLESS>
 int launch_paste_u8_sim(const char* kernel, const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H,
                         int W, const float* sim_dev, int swap_rb, double feather, float lo, float k, const float* matte_dev, int matte_frames,
                         const float* colour_dev, void* stream) {
-    hipLaunchKernelGGL(frames_paste_u8_sim_kernel<SEAMLESS>, dim3(PASTE_WGS, (unsigned)std::min(N, 65535)), dim3(256), 0, (hipStream_t)stream, src, N,
-                       Hs, Ws, dst, N > 1 ? (long long)image_stride : 0ll, (long long)row_stride, H, W, sim_dev, swap_rb, feather, lo, k, matte_dev,
-                       matte_frames, colour_dev);
-    return spk::check_launch(kernel);
+    return launch_paste_sim<SEAMLESS>(kernel, src, N, Hs, Ws, RgbTarget{dst, N > 1 ? (long long)image_stride : 0ll, (long long)row_stride}, H, W,
+                                      sim_dev, swap_rb, feather, lo, k, matte_dev, matte_frames, colour_dev, stream);
 }
 
 }  // namespace spk::frame

@@ -41,7 +41,8 @@ struct Nv12Read {
     Nv12Planes p;
     Mat34 to_rgb;
     struct Row { const uint8_t* y; const uint8_t* c; unsigned pair; };
-    __device__ __forceinline__ Row row(long long n, int iy) const {
+    __device__ __forceinline__ LaunchFrame frame(long long, int H, int W) const { return {H, W}; }
+    __device__ __forceinline__ Row row(const LaunchFrame&, long long n, int iy) const {
         return {p.y + n * p.y_image_stride + (long long)iy * p.y_row_stride, p.uv + n * p.uv_image_stride + (long long)(iy >> 1) * p.uv_row_stride, 0u};
     }
     __device__ __forceinline__ void tap(Row& r, int ix, bool first, double w, double& a_y, double& a_u, double& a_v) const {
@@ -54,7 +55,7 @@ struct Nv12Read {
 #pragma unroll
         for (int c = 0; c < 3; ++c) val[c] = fmin(fmax(affine_row(to_rgb, c, y, u, v), 0.0), 255.0);
     }
-    __device__ __forceinline__ void load(long long n, int X, int Y, double (&b)[3]) const {
+    __device__ __forceinline__ void load(const LaunchFrame&, long long n, int X, int Y, double (&b)[3]) const {
         const double y = (double)p.y[n * p.y_image_stride + (long long)Y * p.y_row_stride + X];
         const unsigned pair = *reinterpret_cast<const uint16_t*>(p.uv + n * p.uv_image_stride + (long long)(Y >> 1) * p.uv_row_stride + (X & ~1));
         rgb(y, (double)(pair & 0xffu), (double)(pair >> 8), b);

@@ -1,8 +1,9 @@
 """The video-frame edge of the inference path: uint8 frames as a video decoder / writer holds them on the device, in and out of the
 network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packed RGB through a similarity transform per frame
 (csrc/frame_sim.hip: aligned crops; csrc/frame_blend.hip: their paste with a face matte and a colour match; csrc/frame_sim_nv12.hip:
-all of that on NV12 surfaces), whose rows csrc/landmark_sim.hip fits to landmarks and smooths; csrc/causal_filter.hip: the causal
-filters of a live feed, their state on the device).  ``ops`` re-exports the
+all of that on NV12 surfaces; csrc/frame_table.hip: on frames in buffers and of sizes of their own), whose rows
+csrc/landmark_sim.hip fits to landmarks and smooths; csrc/causal_filter.hip: the causal filters of a live feed, their state on
+the device).  ``ops`` re-exports the
 launchers (``ops.frames_from_u8`` ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
 from __future__ import annotations
 
@@ -172,7 +173,11 @@ def parse_boxes(box, N, H, W, what="box", inside=True):
 
 # ---- packed RGB: uint8 HWC frames in and out (csrc/frame_io.hip) ----------------------------------------------------------------
 def packed_pixels(frames_u8):
-    """uint8 [N,H,W,3] with packed pixels and rows / frames that do not overlap: what the kernels address by byte strides."""
+    """uint8 [N,H,W,3] with packed pixels and rows / frames that do not overlap: what the kernels address by byte strides.  A
+    ``FrameTable`` has packed pixels by construction: its frames must not share bytes (``SpkError`` names the two that do)."""
+    if isinstance(frames_u8, FrameTable):
+        frames_u8.check_written()
+        return True
     N, H, W, _ = frames_u8.shape
     return frames_u8.stride(3) == 1 and frames_u8.stride(2) == 3 and frames_u8.stride(1) >= 3 * W and \
         (N == 1 or frames_u8.stride(0) >= (H - 1) * frames_u8.stride(1) + 3 * W)
@@ -191,7 +196,7 @@ class _Packed:
             raise ValueError(f"{what}: frames must be [{'N' if N is None else N},H,W,3], got {tuple(frames.shape)}")
         return (frames, *frames.shape[:3])
 
-    def on_device(self, frames):
+    def on_device(self, frames, device=None):                             # device: where x is (a strided launch is not asked)
         if not frames.is_cuda or frames.dtype != torch.uint8:
             raise L.SpkError(f"frames: expected a uint8 HIP tensor, got {frames.dtype} on {frames.device} (no CPU path)")
 
@@ -228,8 +233,136 @@ class _Packed:
             return self.paste, ()
         return self.paste + "_blend", (*matte_args, _ptr(colour))
 
+    def size(self, H, W):                                                # the size arguments of an entry point: one size per launch
+        return (H, W)
+
 
 _PACKED = _Packed()
+
+
+# ---- a frame table: every frame its own buffer and size (csrc/frame_table.hip; the definitions are in include/spk.h) ------------
+class FrameTable:
+    """``N`` packed uint8 frames that share neither an allocation nor a size, as the aligned launchers address them: a device table
+    of ``spk_frame_ref`` entries ``(data, row_stride, H, W)``.  ``frames``: a sequence of device uint8 tensors ``[H_n,W_n,3]`` on one
+    device, pixels packed (``stride(2) == 1``, ``stride(1) == 3``) and ``stride(0) >= 3 W_n`` -- a region-of-interest view of a wider
+    surface is fine -- with ``None`` for a frame that is ABSENT (an all-zero entry: the launchers treat it like an invalid
+    transform); or one ``[N,H,W,3]`` tensor, which gives views of its frames.  Wrong types, shapes or strides raise ``ValueError``
+    before a device is touched; CPU tensors raise ``SpkError`` (no CPU path).  The host table is checked
+    (``spk_frame_table_check``) here and uploaded ONCE, one host -> device copy of ``24 N`` bytes on the current stream, when a launcher
+    first uses the table (so a call that is refused on the host has copied nothing); whether the frames
+    may be written is decided where the table is used (``check_written``: the paste).  The table HOLDS REFERENCES to the tensors, so
+    the addresses in it stay the tensors' for as long as it lives.
+
+    ``dev``: the device table (uint8 ``[24 N]``); ``sizes``: ``(H, W)`` per frame (``(0, 0)``: absent); ``frames``: the tensors."""
+
+    def __init__(self, frames):
+        what = "FrameTable"
+        if isinstance(frames, torch.Tensor):
+            if frames.dim() != 4 or frames.size(0) < 1:
+                raise ValueError(f"{what}: a tensor of frames must be [N,H,W,3], got {tuple(frames.shape)}")
+            frames = list(frames.unbind(0))
+        else:
+            try:
+                frames = list(frames)
+            except TypeError:
+                raise ValueError(f"{what}: frames must be a sequence of uint8 tensors [H,W,3] or a tensor [N,H,W,3], got "
+                                 f"{type(frames).__name__}") from None
+        if not frames:
+            raise ValueError(f"{what}: a table needs at least one frame")
+        for n, f in enumerate(frames):
+            if f is None:
+                continue
+            if not isinstance(f, torch.Tensor):
+                raise ValueError(f"{what}: frames[{n}] must be a uint8 tensor [H,W,3] or None, got {type(f).__name__}")
+            if f.dtype != torch.uint8 or f.dim() != 3 or f.size(2) != 3 or f.size(0) < 1 or f.size(1) < 1:
+                raise ValueError(f"{what}: frames[{n}] must be a uint8 tensor [H,W,3] with H, W >= 1, got {f.dtype} {tuple(f.shape)}")
+            if f.stride(2) != 1 or f.stride(1) != 3 or f.stride(0) < 3 * f.size(1):
+                raise ValueError(f"{what}: frames[{n}]: pixels must be packed and rows must not overlap (strides (>= {3 * f.size(1)}, 3, 1)), "
+                                 f"got {f.stride()}")
+        there = [f for f in frames if f is not None]
+        if any(not f.is_cuda for f in there):
+            raise L.SpkError(f"{what}: expected uint8 HIP tensors, got a frame on the CPU (no CPU path)")
+        if any(f.device != there[0].device for f in there):
+            raise L.SpkError(f"{what}: the frames must be on one device, got {sorted({str(f.device) for f in there})}")
+        self.frames, self.N = frames, len(frames)
+        self.sizes = [(0, 0) if f is None else (f.size(0), f.size(1)) for f in frames]
+        self._host = (L.FrameRef * self.N)()
+        for e, f in zip(self._host, frames):
+            if f is not None:
+                e.data, e.row_stride, e.H, e.W = f.data_ptr(), f.stride(0), f.size(0), f.size(1)
+        L.check(L.lib().spk_frame_table_check(C.addressof(self._host), self.N, 0), "spk_frame_table_check")
+        self._written = False
+        self.device = there[0].device if there else torch.device("cuda", torch.cuda.current_device())
+        self._dev = None
+
+    @property
+    def dev(self):
+        """The device table, uploaded when a launcher first asks for it: every host check of a call comes before the copy"""
+        if self._dev is None:
+            self._dev = torch.empty(C.sizeof(self._host), dtype=torch.uint8, device=self.device)
+            self._dev.copy_(torch.frombuffer(self._host, dtype=torch.uint8))
+        return self._dev
+
+    def __len__(self):
+        return self.N
+
+    def check_written(self):
+        """The frames are about to be written: no two of them may share bytes (``spk_frame_table_check`` with ``written``), else ``SpkError``"""
+        if not self._written:
+            L.check(L.lib().spk_frame_table_check(C.addressof(self._host), self.N, 1), "spk_frame_table_check")
+            self._written = True
+
+
+class _Tabled:
+    """``_Packed`` for a ``FrameTable``: the frames of a call as entries of a device table (csrc/frame_table.hip).  The size of a
+    frame is its entry's, so an entry point takes none; the frames are addressed where they are, never copied."""
+    way_in, paste = "spk_frames_u8_to_f32_sim_table", "spk_frames_paste_u8_sim_table"
+    sums, match = "spk_paste_colour_sums_sim_table", "spk_paste_colour_match_sim_table"
+
+    def shaped(self, table, N, what):                                     # -> (table, N, None, None): a table has no one size
+        if N is not None and table.N != N:
+            raise ValueError(f"{what}: {N} generated frames, a table of {table.N} frames")
+        return table, table.N, None, None
+
+    def on_device(self, table, device=None):                              # a table is on a device by construction: on x's?
+        if device is not None and table.device != device:
+            raise L.SpkError(f"frames: the frame table on {table.device}, x on {device}")
+
+    def read(self, table, what, disjoint=False):
+        return table.dev, (table.dev.data_ptr(),)
+
+    def target(self, table, out, N, H, W, device, what):
+        if out is not None and out is not table:
+            raise L.SpkError(f"{what}: a frame table is pasted in place: out must be None or the table itself")
+        table.check_written()                                             # (its device is x's: ``on_device`` saw to it)
+        return table, (table.dev.data_ptr(),), lambda: None
+
+    def size(self, H, W):
+        return ()
+
+    def standard(self):
+        return ()
+
+    def quantised(self, value_range, channel_order="rgb"):
+        return _PACKED.quantised(value_range, channel_order)
+
+    def blend(self, matte_args, colour):                                  # one entry point, with or without matte and colour rows
+        return self.paste, (*matte_args, _ptr(colour))
+
+
+_TABLED = _Tabled()
+
+
+def clone_frames(frames_u8):
+    """A packed copy of the frames to paste into: one clone of a tensor; of a ``FrameTable`` a new table over one clone per frame
+    (a table of its own: its host check and, at its first launch, its upload come on top of the clones)"""
+    if isinstance(frames_u8, FrameTable):
+        return FrameTable([None if f is None else f.clone(memory_format=torch.contiguous_format) for f in frames_u8.frames])
+    return frames_u8.clone(memory_format=torch.contiguous_format)
+
+
+def _u8_format(frames_u8):                                                # a tensor takes exactly the path it always took
+    return _TABLED if isinstance(frames_u8, FrameTable) else _PACKED
 
 
 def frames_from_u8(frames_u8, size, *, crop=None, channel_order="rgb", mean=0.5, std=0.5):
@@ -386,7 +519,7 @@ def _from_aligned(fmt, what, frames, size, sim, channel_order, mean, std, **stan
     held, where = fmt.read(frames, what)
     rows = _sim_on(rows, held.device, what)
     out = torch.empty((N, 3, Hout, Wout), device=held.device, dtype=torch.float32)
-    L.check(getattr(L.lib(), fmt.way_in)(*where, N, H, W, rows.data_ptr(), *colour, out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()),
+    L.check(getattr(L.lib(), fmt.way_in)(*where, N, *fmt.size(H, W), rows.data_ptr(), *colour, out.data_ptr(), Hout, Wout, *scale, *shift, L.stream_ptr()),
             fmt.way_in)
     return out
 
@@ -400,8 +533,10 @@ def frames_from_u8_aligned(frames_u8, size, sim, *, channel_order="rgb", mean=0.
     footprint misses the frame is ``-mean / std``.  ``sim``: rows ``(a, c, tx, ty)`` (``similarity_rows``; include/spk.h): a host
     sequence / CPU tensor ``[N,4]``, checked on the host (``ValueError`` for a row that is not finite or has a scale outside
     [1/16, 16]) and uploaded once; or a device float32 ``[N,4]`` tensor a tracker left there, not read on the host -- an invalid
-    row gives a frame of ``-mean / std``.  -> float32 [N,3,size,size]."""
-    return _from_aligned(_PACKED, "frames_from_u8_aligned", frames_u8, size, sim, channel_order, mean, std)
+    row gives a frame of ``-mean / std``.  ``frames_u8`` may be a ``FrameTable``: frames of their own sizes in their own buffers, still
+    one launch (``spk_frames_u8_to_f32_sim_table``), frame ``n`` bit for bit this call on frame ``n`` alone; an absent frame gives
+    ``-mean / std``.  -> float32 [N,3,size,size]."""
+    return _from_aligned(_u8_format(frames_u8), "frames_from_u8_aligned", frames_u8, size, sim, channel_order, mean, std)
 
 
 def _check_matte(matte, N, Hs, Ws, what):
@@ -446,7 +581,7 @@ def _aligned_args(fmt, what, x, frames, sim, feather, value_range, matte=None, c
     matte, matte_frames = _check_matte(matte, N, Hs, Ws, what)
     colour = _check_colour(colour, N, what)
     xp = L.dptr(x, "x")
-    fmt.on_device(frames)
+    fmt.on_device(frames, x.device)
     matte, colour = _there(matte, x.device, "matte", what), _there(colour, x.device, "colour", what)
     rows = _sim_on(rows, x.device, what)
     return (xp, N, Hs, Ws), frames, (H, W), rows, (*colour_args, feather, lo, k), (_ptr(matte), matte_frames), colour
@@ -457,7 +592,7 @@ def _paste_aligned(fmt, what, x, frames, sim, feather, value_range, out, matte, 
     out, where, fill = fmt.target(frames, out, head[1], H, W, x.device, what)
     fill()
     entry, blend = fmt.blend(matte_args, colour)
-    L.check(getattr(L.lib(), entry)(*head, *where, H, W, rows.data_ptr(), *tail, *blend, L.stream_ptr()), entry)
+    L.check(getattr(L.lib(), entry)(*head, *where, *fmt.size(H, W), rows.data_ptr(), *tail, *blend, L.stream_ptr()), entry)
     return out
 
 
@@ -475,8 +610,12 @@ def frames_paste_u8_aligned(x, frames_u8, sim, *, feather=0, value_range=(-1, 1)
     the weights of ``x``, clamped to [0, 1] (NaN: 0) and multiplied into the blend weight, so only the face is pasted; ``colour``
     is a device float32 ``[N,3,2]`` tensor of rows ``(gain, offset)`` per frame and channel of ``x``, applied to the quantised
     value in front of the blend (``paste_colour_match`` makes them; a row that is not finite counts as ``(1, 0)``).  Without
-    both, the call is the one it always was.  -> uint8 [N,H,W,3]."""
-    return _paste_aligned(_PACKED, "frames_paste_u8_aligned", x, frames_u8, sim, feather, value_range, out, matte, colour, channel_order=channel_order)
+    both, the call is the one it always was.  -> uint8 [N,H,W,3].
+
+    ``frames_u8`` may be a ``FrameTable`` (``spk_frames_paste_u8_sim_table``, one launch with or without ``matte`` / ``colour``): the
+    paste is then IN PLACE, into the table's own frames (``out``: None or the table), which must not share bytes; an absent frame is
+    left alone; frame ``n`` gets the bytes of this call on frame ``n`` alone.  -> the table."""
+    return _paste_aligned(_u8_format(frames_u8), "frames_paste_u8_aligned", x, frames_u8, sim, feather, value_range, out, matte, colour, channel_order=channel_order)
 
 
 COLOUR_SUMS = 13                                                          # S0, then (Sq, Sqq, Sb, Sbb) per network channel
@@ -516,7 +655,7 @@ def _colour_statistics(fmt, params, what, x, frames, sim, matte, feather, value_
     held, where = fmt.read(frames, what, disjoint=True)
     out = _stat_out(out, (head[1], *shape), dtype, x.device)
     ws = _colour_workspace(x.device, head[1])
-    L.check(getattr(L.lib(), entry)(*head, *where, H, W, rows.data_ptr(), *tail, *matte_args, *(params or ()), out.data_ptr(), ws.data_ptr(),
+    L.check(getattr(L.lib(), entry)(*head, *where, *fmt.size(H, W), rows.data_ptr(), *tail, *matte_args, *(params or ()), out.data_ptr(), ws.data_ptr(),
                                     ws.numel() * 8, L.stream_ptr()), entry)
     return out
 
@@ -532,10 +671,11 @@ def paste_colour_match(x, frames_u8, sim, *, matte=None, feather=0, value_range=
     frame whose weights sum to at most ``min_weight``, or whose row is invalid, gets ``(1, 0)``.  The sums are reduced in a fixed
     order without atomics: the same inputs give the same bits.  The rows come back as a tensor; to steady them over time,
     pool the SUMS (``paste_colour_sums`` + ``colour_rows_from_sums``), not the rows.  ``out``: a contiguous device float32 ``[N,3,2]``
-    tensor to write.  -> device float32 ``[N,3,2]``."""
+    tensor to write.  ``frames_u8`` may be a ``FrameTable`` (``spk_paste_colour_match_sim_table``; an absent frame gets ``(1, 0)``).
+    -> device float32 ``[N,3,2]``."""
     what = "paste_colour_match"
     params = _check_match_params(what, max_gain, min_sigma, min_weight)
-    return _colour_statistics(_PACKED, params, what, x, frames_u8, sim, matte, feather, value_range, out, channel_order=channel_order)
+    return _colour_statistics(_u8_format(frames_u8), params, what, x, frames_u8, sim, matte, feather, value_range, out, channel_order=channel_order)
 
 
 def paste_colour_sums(x, frames_u8, sim, *, matte=None, feather=0, value_range=(-1, 1), channel_order="rgb", out=None):
@@ -544,8 +684,9 @@ def paste_colour_sums(x, frames_u8, sim, *, matte=None, feather=0, value_range=(
     internally; 13 zeros for a frame whose row is invalid.  The arguments are that launcher's without the three parameters of the
     row formula, which ``colour_rows_from_sums`` takes -- with ``radius=0`` it turns these sums into exactly ``paste_colour_match``'s
     rows, with a radius it pools them over neighbouring frames first.  ``out``: a contiguous device float64 ``[N,13]`` tensor to
-    write, for instance the slice ``[t0:t1]`` of a clip-long ``[T,13]`` tensor.  -> device float64 ``[N,13]``."""
-    return _colour_statistics(_PACKED, None, "paste_colour_sums", x, frames_u8, sim, matte, feather, value_range, out, channel_order=channel_order)
+    write, for instance the slice ``[t0:t1]`` of a clip-long ``[T,13]`` tensor.  ``frames_u8`` may be a ``FrameTable``
+    (``spk_paste_colour_sums_sim_table``; 13 zeros for an absent frame).  -> device float64 ``[N,13]``."""
+    return _colour_statistics(_u8_format(frames_u8), None, "paste_colour_sums", x, frames_u8, sim, matte, feather, value_range, out, channel_order=channel_order)
 
 
 def colour_rows_from_sums(sums, radius=0, sigma=None, *, start=0, stop=None, max_gain=2.0, min_sigma=1.0, min_weight=16.0, out=None):
@@ -1162,7 +1303,7 @@ class _Surfaces:
             raise ValueError(f"{what}: {N} generated frames, {y.size(0)} NV12 frames")
         return ((y, uv), *y.shape)
 
-    def on_device(self, planes):
+    def on_device(self, planes, device=None):
         if not planes[0].is_cuda:
             raise L.SpkError(f"frames: expected uint8 HIP tensors, got {planes[0].dtype} on {planes[0].device} (no CPU path)")
 
@@ -1186,6 +1327,9 @@ class _Surfaces:
                 if dst.data_ptr() != src.data_ptr() or dst.stride() != src.stride():
                     dst.copy_(src)
         return out, (y.data_ptr(), *ys, uv.data_ptr(), *us), fill
+
+    def size(self, H, W):
+        return (H, W)
 
     def standard(self, standard="bt601", full_range=False):
         return yuv_standard(standard, full_range)

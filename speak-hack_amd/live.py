@@ -106,17 +106,25 @@ class _Live:
         return self._generated[Ws]
 
     def _check_step(self, what, frames_u8, emotion_u8, inplace):
-        if emotion_u8 is not None and (not isinstance(emotion_u8, torch.Tensor) or tuple(emotion_u8.shape) != tuple(frames_u8.shape)):
+        """-> ``emotion_u8`` as the body takes it: beside a ``FrameTable`` of frames, a table of the same sizes per feed"""
+        if isinstance(frames_u8, FR.FrameTable):
+            if emotion_u8 is not None:
+                emotion_u8 = self._table(what, "emotion_u8", emotion_u8)
+                if emotion_u8.sizes != frames_u8.sizes:
+                    raise ValueError(f"{what}: emotion_u8 must match the frames feed by feed: sizes {emotion_u8.sizes}, the frames' {frames_u8.sizes}")
+        elif emotion_u8 is not None and (not isinstance(emotion_u8, torch.Tensor) or tuple(emotion_u8.shape) != tuple(frames_u8.shape)):
             raise ValueError(f"{what}: emotion_u8 must match the frames {tuple(frames_u8.shape)}")
         if not isinstance(inplace, bool):
             raise ValueError(f"{what}: inplace must be a bool, got {inplace!r}")
+        return emotion_u8
 
     def _body(self, what, frames_u8, landmarks, weights, emotion_u8, inplace):
-        """The steps of one ``step`` over the ``N`` rows of ``frames_u8``, after the host checks: ``landmarks`` [N,K,2] and
-        ``weights`` as the filter (``track``) or else the fit takes them"""
+        """The steps of one ``step`` over the ``N`` rows of ``frames_u8`` -- a tensor ``[N,H,W,3]``, or a ``FrameTable`` of ``N`` frames
+        (``emotion_u8``: the same form) -- after the host checks: ``landmarks`` [N,K,2] and ``weights`` as the filter (``track``) or
+        else the fit takes them"""
         if inplace and not FR.packed_pixels(frames_u8):
             raise L.SpkError(f"{what}: inplace needs packed pixels and rows / frames that do not overlap, got strides {frames_u8.stride()}")
-        N = frames_u8.size(0)
+        N = len(frames_u8)
         model, order = self.model, dict(channel_order=self.channel_order)
         # 1, 2: the landmarks steadied, and the rows fitted to them; a held point keeps its last weight, an expired one has none
         if self.track is not None:
@@ -146,7 +154,7 @@ class _Live:
         if self.contour is not None:
             matte = FR._matte(landmarks, rows, Hs, Ws, self.contour, self.softness, self.grow, self.offset, fallback, *FR._check_smooth(0, None, what),
                               what)
-        out = frames_u8 if inplace else frames_u8.clone(memory_format=torch.contiguous_format)
+        out = frames_u8 if inplace else FR.clone_frames(frames_u8)
         colour = None
         if self.colour_match:                                              # the statistics read the background before the paste writes it
             sums = FR.paste_colour_sums(y, out, rows, matte=matte, feather=self.feather, **order)
@@ -245,8 +253,8 @@ class LiveRoom(_Live):
       ``seeds``          int64 ``[S]``: the 64-bit patterns of the seeds (``ops.seed_rows``), or None without a seed.
 
     A slot with nothing to show in a tick is given NaN landmarks: it is a session's lost frame, held up to ``hold`` ticks and then
-    passed through untouched, and its counter advances as a session's does.  Out of scope: feeds with frames of different sizes or
-    in separate allocations, stepping a subset of the slots, several frames per feed per tick, NV12."""
+    passed through untouched, and its counter advances as a session's does.  The feeds' frames may be one tensor or S buffers of S
+    sizes (``step``).  Out of scope: stepping a subset of the slots, several frames per feed per tick, NV12."""
 
     def __init__(self, model, identities_u8, *, size, template, contour, channel_order, identity_align, rate, track, features, feather,
                  matte_softness, matte_grow, colour_match, colour_decay, seed, noise, offset):
@@ -386,20 +394,54 @@ class LiveRoom(_Live):
         ``[S,K,2]`` (NaN for a feed with nothing to show); ``weights``: the tracker's confidences per feed ``[S,K]``, or one ``[K]`` set
         for all feeds, host numbers or a device float32 tensor; ``emotion_u8``: the frames ``Ee`` sees (None: ``frames_u8``).  ->
         uint8 ``[S,H,W,3]`` (``inplace=True``: ``frames_u8`` itself).  The steps are ``LiveSession.step``'s with the feeds as the batch;
-        the number of launches does not depend on ``S``, and no device value is read on the host."""
+        the number of launches does not depend on ``S``, and no device value is read on the host.
+
+        ``frames_u8`` may also be a list or tuple of ``S`` tensors ``[H_s,W_s,3]`` -- every feed in a buffer of its own, of its own
+        size, pixels packed, any row pitch -- or an ``ops.FrameTable`` of ``S`` frames, and ``emotion_u8`` then a list, tensor or table
+        with the same size per feed.  The launches are those above with the three ``_table`` entry points of csrc/frame_table.hip in
+        place of the strided three, plus one upload of ``24 S`` bytes per table; landmarks are in each feed's own frame coordinates.
+        ``inplace=True`` writes into the caller's buffers (which must not share bytes) and returns the list; ``inplace=False`` clones
+        every frame first -- ``S`` copies, the one cost of a tick that grows with ``S``, and a second table (host check and upload)
+        over the clones -- and returns a list of new tensors."""
         what = "live_room.step"
         S, K = self.S, self.K
-        if not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != S:
+        given = frames_u8
+        if isinstance(frames_u8, (list, tuple, FR.FrameTable)):
+            frames_u8 = self._table(what, "frames", frames_u8)
+        elif not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != S:
             got = tuple(frames_u8.shape) if isinstance(frames_u8, torch.Tensor) else type(frames_u8).__name__
             raise ValueError(f"{what}: frames must be [{S},H,W,3], one frame per feed, got {got}")
         if not isinstance(landmarks, torch.Tensor) or tuple(landmarks.shape) != (S, K, 2):
             got = tuple(landmarks.shape) if isinstance(landmarks, torch.Tensor) else type(landmarks).__name__
             raise ValueError(f"{what}: landmarks must be [{S},{K},2], {K} points per feed as the template has, got {got}")
-        self._check_step(what, frames_u8, emotion_u8, inplace)
+        emotion_u8 = self._check_step(what, frames_u8, emotion_u8, inplace)
         weights = self._weights(what, weights)
         if self.track is None and weights is not None:                     # the fit takes them per frame
             weights = weights.view(S, K)
         out = self._body(what, frames_u8, landmarks, weights, emotion_u8, inplace)
         if not self.fixed_noise:
             self.frames.add_(1)
+        if isinstance(out, FR.FrameTable):                                 # in place: the caller's own list, or the table's tensors
+            return given if inplace and isinstance(given, list) else list(out.frames)
         return out
+
+    def _table(self, what, name, frames):
+        """This tick's frames of the ``S`` feeds in buffers of their own: a list / tuple of ``S`` tensors ``[H_s,W_s,3]``, a tensor
+        ``[S,H,W,3]`` or a ``FrameTable`` -> a ``FrameTable`` of ``S`` frames on the room's device, none of them absent (a feed that
+        sits out is given NaN landmarks)"""
+        S = self.S
+        if not isinstance(frames, FR.FrameTable):
+            if not isinstance(frames, (list, tuple, torch.Tensor)):
+                raise ValueError(f"{what}: {name} must be a list of {S} frames [H,W,3], a tensor [{S},H,W,3] or a FrameTable, got {type(frames).__name__}")
+            if len(frames) != S:
+                raise ValueError(f"{what}: {name} must hold one frame per feed ({S}), got {len(frames)}")
+            if not isinstance(frames, torch.Tensor) and any(f is None for f in frames):
+                raise ValueError(f"{what}: {name} must hold a frame for every feed, got None among them (give a feed that sits out NaN landmarks)")
+            frames = FR.FrameTable(frames)
+        if len(frames) != S:
+            raise ValueError(f"{what}: {name} must hold one frame per feed ({S}), got a table of {len(frames)}")
+        if any(f is None for f in frames.frames):
+            raise ValueError(f"{what}: {name} must hold a frame for every feed, got an absent one (give a feed that sits out NaN landmarks)")
+        if frames.device != self.device:
+            raise L.SpkError(f"{what}: {name} on {frames.device}, the room on {self.device}")
+        return frames

@@ -64,6 +64,12 @@
     window of radius 8; (c) what a caller had: (a), the rows to the host, a numpy filter over time, an upload.  Written to
     profiles/colour_window_bench.txt.
 
+``--live-room-table``: a tick of S live feeds whose frames sit in S separate allocations (csrc/frame_table.hip), S in {1, 2, 4, 8}, in
+    place: ``LiveRoom.step`` on the list of buffers beside (a) ``torch.stack`` + the step + S copies back, what a server had to do,
+    and (b) the step on one contiguous tensor, the price of the table's indirection alone; then 720p / 480p feeds in one room
+    beside a ``LiveSession.step`` per feed.  Wall clock per tick, the contenders alternate, the list runs twice per round for the
+    spread.  Written to profiles/live_room_table_bench.txt; the two expectations are reported, not gated.
+
     python tools/bench_frame_io.py [--paste | --nv12 | --align | --align-nv12 | --landmarks | --blend | --landmark-matte | --colour-smooth] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
@@ -916,6 +922,92 @@ def bench_live_room(args, lines):
     return bool(met)
 
 
+def bench_live_room_table(args, lines):
+    """``--live-room-table``: one TICK of a server with S calls whose frames sit in S separately allocated buffers, S in {1, 2, 4, 8}
+    (the frames, landmarks and settings of ``--live-room``), wall clock, synchronised before and after every tick, in place, three
+    ways.  (t) ``LiveRoom.step`` on the list of buffers: a frame table.  (a) what a server had to do before: ``torch.stack`` the S
+    buffers, ``room.step(inplace=True)``, S copies back.  (b) ``room.step(inplace=True)`` on an already contiguous tensor, which no
+    server has: the price of the table's indirection alone.  The contenders alternate in one process, (t) entered twice for the
+    spread.  Then one mixed-size row: 720p and 480p feeds in one room against one ``LiveSession.step`` per feed.  Every contender
+    pastes into buffers that the one before it pasted into -- the work does not depend on the bytes.
+    -> whether the two expectations hold at every S: (t) <= (a), and (t) within the spread of (b)."""
+    T, per, sizes = 8, 20, (1, 2, 4, 8)
+    sc = live_scene(T)
+    ops, dev, m, template, contour, lm, ident, video, common = (sc[k] for k in ("ops", "dev", "m", "template", "contour", "lm", "ident", "video", "common"))
+    size, Hf, Wf, K = (sc[k] for k in ("size", "Hf", "Wf", "K"))
+    kw = dict(common, template=template, contour=contour, features={})
+    del kw["seed"]
+    lines.append(f"a tick of S feeds of {Hf}x{Wf} BGR in S separate allocations, in place, K = {K} landmarks, outline of {len(contour)}, {size}^2 in and "
+                 f"out, feather {sc['feather']}, matte, colour match and the three filters; median of {args.repeats} alternating rounds of {per} ticks")
+
+    def latency(fn):                                                       # the mean wall clock of `per` ticks, each synchronised on its own
+        total = 0.0
+        for i in range(per):
+            total += wall(lambda: fn(i % T))
+        return total / per
+
+    verdicts = []
+    for S in sizes:
+        show = torch.tensor([[(t + s) % T for s in range(S)] for t in range(T)], device=dev)
+        lms = lm[show].contiguous()                                        # feed s shows frame (t + s) % T in tick t
+        buffers = [[video[(t + s) % T].clone() for s in range(S)] for t in range(T)]      # per tick S allocations
+        packed = [torch.stack(b) for b in buffers]                         # per tick one tensor, for (b)
+        rooms = {k: m.live_room([ident] * S, seed=list(range(7, 7 + S)), **kw) for k in "tab"}
+
+        def tick_table(t):
+            return rooms["t"].step(buffers[t], lms[t], inplace=True)
+
+        def tick_stack(t):
+            out = rooms["a"].step(torch.stack(buffers[t]), lms[t], inplace=True)
+            for dst, src in zip(buffers[t], out):
+                dst.copy_(src)
+            return out
+
+        def tick_packed(t):
+            return rooms["b"].step(packed[t], lms[t], inplace=True)
+
+        names = (f"(t) LiveRoom.step on a list of {S} buffers", f"(a) stack + step + {S} copies back", "(b) step on one contiguous tensor")
+        contenders = {names[0]: tick_table, names[1]: tick_stack, names[2]: tick_packed, names[0] + " (again)": tick_table}
+        for fn in contenders.values():
+            for t in range(args.warmup + 1):
+                fn(t)
+        times = alternate(contenders, args.repeats, latency)
+        ratio_table(lines, f"S = {S}: wall clock per tick, synchronised before and after each tick:", times, names[0], [(names[1], True), (names[2], False)])
+        med = {n: statistics.median(ts) for n, ts in times.items()}
+        ours = min(med[names[0]], med[names[0] + " (again)"])
+        spread = abs(med[names[0]] - med[names[0] + " (again)"]) / ours
+        gap = med[names[0]] / med[names[2]] - 1
+        verdicts.append((S, med[names[0]] <= med[names[1]], abs(gap) <= spread, gap, spread))
+        lines.append(f"  spread of (t) between its two entries {spread * 100:.2f} %; (t) over (b) {gap * 100:+.2f} %; (t) over (a) "
+                     f"{(med[names[0]] / med[names[1]] - 1) * 100:+.2f} %")
+    # one mixed row: 720p and 480p feeds in one room, against a session per feed
+    S, shapes = 4, [(720, 1280), (480, 640), (720, 1280), (480, 640)]
+    scale = [torch.tensor([w / Wf, h / Hf], device=dev) for h, w in shapes]       # (x, y): the frames are resized per axis, so are the points
+    own = [[torch.nn.functional.interpolate(video[(t + s) % T].permute(2, 0, 1)[None].float(), size=shapes[s], mode="bilinear")[0]
+            .permute(1, 2, 0).round().to(torch.uint8).contiguous() for s in range(S)] for t in range(T)]
+    lms = torch.stack([torch.stack([lm[(t + s) % T] * scale[s] for s in range(S)]) for t in range(T)])      # landmarks in each feed's own pixels
+    room = m.live_room([ident] * S, seed=list(range(7, 7 + S)), **kw)
+    sessions = [m.live(ident, seed=7 + s, **kw) for s in range(S)]
+
+    def tick_mixed(t):
+        return room.step(own[t], lms[t], inplace=True)
+
+    def tick_sessions(t):
+        return [s.step(own[t][i].unsqueeze(0), lms[t, i:i + 1], inplace=True) for i, s in enumerate(sessions)]
+
+    names = ("(t) LiveRoom.step on 2 x 720p + 2 x 480p buffers", "(s) 4 x LiveSession.step, one frame each")
+    contenders = {names[0]: tick_mixed, names[1]: tick_sessions, names[0] + " (again)": tick_mixed}
+    for fn in contenders.values():
+        for t in range(args.warmup + 1):
+            fn(t)
+    times = alternate(contenders, args.repeats, latency)
+    ratio_table(lines, "mixed sizes, S = 4: wall clock per tick, synchronised before and after each tick:", times, names[0], [(names[1], True)])
+    for S_, le_a, near_b, gap, spread in verdicts:
+        lines.append(f"S = {S_}: (t) <= (a): {'CONFIRMED' if le_a else 'REFUTED'}; (t) within the spread of (b): "
+                     f"{'CONFIRMED' if near_b else 'REFUTED'} (gap {gap * 100:+.2f} %, spread {spread * 100:.2f} %)")
+    return all(v[1] and v[2] for v in verdicts)
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -956,9 +1048,15 @@ def main():
     ap.add_argument("--live", action="store_true", help="one frame of a live feed: LiveSession.step beside reenact_video on a clip of one frame")
     ap.add_argument("--live-room", action="store_true", help="a tick of S live feeds: LiveRoom.step beside S LiveSession.step calls; exit status 1 "
                     "unless the room wins at S = 8 by more than the spread")
+    ap.add_argument("--live-room-table", action="store_true", help="a tick of S live feeds in S separate allocations: LiveRoom.step on a list beside "
+                    "stack + step + copies back and beside the step on one tensor; one mixed-size row")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.live_room_table:
+        lines = [f"bench_frame_io --live-room-table: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_live_room_table(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "live_room_table_bench.txt"))
     if args.live_room:
         lines = [f"bench_frame_io --live-room: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
         met = bench_live_room(args, lines)

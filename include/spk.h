@@ -616,6 +616,34 @@ int spk_conv1x1_small_mod_fwd(const float* x, const float* w, const float* mod, 
 int spk_torgb_mod_skip_fwd(const float* x, const float* w, const float* mod, const float* bias, const float* skip, float* y, int B,
                            int C, int O, int H, int W, float in_scale, void* stream);
 
+/* ---- the form a small forward launch takes --------------------------------------------------------------
+ * What spk_fc_fwd, spk_upfirdn2d_fwd and the toRGB launches (spk_conv1x1_small_fwd / spk_conv1x1_small_mod_fwd /
+ * spk_torgb_mod_skip_fwd) would run for the given operands: the launchers decide their dispatch by the very functions these
+ * queries call, nothing is launched and no device is touched (pointers are read for their ALIGNMENT only; filter_host is read on
+ * the host).  What the launcher refuses for these arguments the query refuses.  Fields a query does not fill are 0.
+ *   spk_fc_fwd_form:        kernel 0 scalar (fc_kernel<false>), 1 vector generic loop, 2 vector I == 512, 3 wide (a workgroup per row),
+ *                           4 wide4 (four rows per workgroup); row_trips: trips of a lane's loop over the weight row; U: wide4's
+ *                           1024-float chunks per row; batch_passes = ceil(B / 8).
+ *                           (spk_fc_grouped_fwd needs no query: a group runs form 2 when its I == 512 and form 1 otherwise.)
+ *   spk_upfirdn2d_form:     kernel 0 generic, 1 separable <UP, DOWN, K> with NLD 64-column register segments per input row;
+ *                           Ho, Wo; grid_loop: a thread of the generic kernel takes more than one trip of its grid-stride loop.
+ *                           Honours SPK_UPFIRDN_SEP as the launch does.
+ *   spk_conv1x1_small_form: kernel 0 one pixel per thread (<false>), 1 four pixels per thread (<true>), 2 channel split with Q pixel
+ *                           quads per workgroup; has_skip / W as spk_torgb_mod_skip_fwd passes them (0 / 0 without a skip). */
+typedef struct spk_small_form {
+    int32_t kernel;
+    int32_t row_trips, U, batch_passes;
+    int32_t UP, DOWN, K, NLD, Ho, Wo, grid_loop;
+    int32_t Q;
+    int32_t grid_x, grid_y, grid_z;
+    int32_t reserved;
+    int64_t lds_bytes;
+} spk_small_form;
+int spk_fc_fwd_form(const float* x, int64_t x_stride, const float* w, int I, int O, int B, spk_small_form* out);
+int spk_upfirdn2d_form(const float* filter_host, int k, int64_t planes, int H, int W, int up, int down, int pad0, int pad1,
+                       spk_small_form* out);
+int spk_conv1x1_small_form(const float* x, const float* y, int B, int C, int O, int64_t HW, int has_skip, int W, spk_small_form* out);
+
 /* ---- stand-alone StyleGAN1 / ProGAN ops (the reference's only definitions of the PixelNorm / FIR-blur family) ----
  * spk_pixelnorm_fwd: y = x * rsqrt(mean_c x^2 + eps) over dim 1 of [B,C,HW] (HW = 1 for latents).
  *   replaces: styleganv1.py:132-136 (PixelNorm, sqrt_form = 0); stylegan.py:28-29 (x / sqrt(...), sqrt_form = 1).

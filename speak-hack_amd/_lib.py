@@ -68,6 +68,16 @@ WGRAD_KERNELS = ("tap", "tap_fixed", "pipe", "wide16", "wide8", "s2_16", "s2_8",
 WGRAD_MODES = ("plain", "affine", "bscale")
 WGRAD_REDUCERS = ("dword", "vec", "deep")
 
+class SmallForm(C.Structure):
+    """Mirror of spk_small_form (include/spk.h): what ``spk_fc_fwd_form`` / ``spk_upfirdn2d_form`` / ``spk_conv1x1_small_form`` answer."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "row_trips", "U", "batch_passes", "UP", "DOWN", "K", "NLD", "Ho", "Wo", "grid_loop", "Q",
+                                         "grid_x", "grid_y", "grid_z", "reserved")] + [("lds_bytes", C.c_int64)]
+
+
+FC_KERNELS = ("scalar", "vec", "vec512", "wide", "wide4")         # spk_small_form.kernel of spk_fc_fwd_form
+UPFIRDN_KERNELS = ("generic", "sep")                              # ... of spk_upfirdn2d_form
+CONV1X1_SMALL_KERNELS = ("scalar", "vec", "csplit")               # ... of spk_conv1x1_small_form
+
 CONV_IN_BATCH_SCALE = 256
 CONV_UP_FIR1331 = 512
 CONV_DGRAD_S2 = 1024
@@ -327,6 +337,10 @@ _PROTOTYPES = {
     "spk_global_avgpool_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "spk_fc_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                              C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "spk_fc_fwd_form": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SmallForm)]),
+    "spk_upfirdn2d_form": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(SmallForm)]),
+    "spk_conv1x1_small_form": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(SmallForm)]),
     "spk_fc_grouped_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "spk_fc_grouped_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "spk_bias_noise_style_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -257,32 +257,70 @@ __global__ __launch_bounds__(FC_WAVES * 64) void fc_grouped_kernel(const FcGroup
     }
 }
 
+enum { FC_SCALAR = 0, FC_VEC = 1, FC_VEC512 = 2, FC_WIDE = 3, FC_WIDE4 = 4 };      // spk_small_form.kernel (include/spk.h)
+
+// The one place that decides which kernel an FC runs and over which grid: spk_fc_fwd launches what this states,
+// spk_fc_fwd_form copies it out.
+int fc_plan(const float* x, int64_t x_stride, const float* w, int I, int O, int B, spk_small_form& f) {
+    SPK_REQUIRE(x && w, "fc: null pointer");
+    SPK_REQUIRE(B > 0 && I > 0 && O > 0, "fc: bad shape B=%d I=%d O=%d", B, I, O);
+    SPK_REQUIRE(x_stride >= I, "fc: row stride smaller than row");
+    f = spk_small_form{};
+    f.batch_passes = spk::ceil_div(B, FC_BT);
+    f.grid_y = f.grid_z = 1;
+    const bool vec = (I % 4 == 0) && (x_stride % 4 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0);
+    if (vec && I >= 2048 && I % 1024 == 0 && I <= 1024 * FC_WIDE_U && O % 4 == 0) {
+        f.kernel = FC_WIDE4;
+        f.U = I >> 10;
+        f.row_trips = 1;
+        f.grid_x = O / 4;
+        f.lds_bytes = 4 * 4 * FC_BT * sizeof(float);
+    } else if (vec && I >= 2048) {
+        f.kernel = FC_WIDE;
+        f.row_trips = spk::ceil_div(I, 1024 * FC_WIDE_U);
+        f.grid_x = O;
+        f.lds_bytes = 4 * FC_BT * sizeof(float);
+    } else {
+        f.kernel = !vec ? FC_SCALAR : (I == 512 ? FC_VEC512 : FC_VEC);
+        f.row_trips = f.kernel == FC_VEC512 ? 1 : spk::ceil_div(I, f.kernel == FC_VEC ? 256 : 64);
+        f.grid_x = spk::ceil_div(O, FC_WAVES);
+    }
+    return SPK_OK;
+}
+
 }  // namespace
+
+extern "C" int spk_fc_fwd_form(const float* x, int64_t x_stride, const float* w, int I, int O, int B, spk_small_form* out) {
+    SPK_REQUIRE(out, "fc form: null pointer");
+    return fc_plan(x, x_stride, w, I, O, B, *out);
+}
 
 extern "C" int spk_fc_fwd(const float* x, int64_t x_stride, const float* w, const float* bias, float* out,
                           int64_t out_stride, int B, int I, int O, float wmul, float bmul, float slope, void* stream) {
-    SPK_REQUIRE(x && w && out, "fc: null pointer");
-    SPK_REQUIRE(B > 0 && I > 0 && O > 0, "fc: bad shape B=%d I=%d O=%d", B, I, O);
-    SPK_REQUIRE(x_stride >= I && out_stride >= O, "fc: row stride smaller than row");
-    const bool vec = (I % 4 == 0) && (x_stride % 4 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0);
-    if (vec && I >= 2048 && I % 1024 == 0 && I <= 1024 * FC_WIDE_U && O % 4 == 0) {
-        hipLaunchKernelGGL(fc_wide4_kernel, dim3((unsigned)(O / 4)), dim3(256), 0, (hipStream_t)stream, x, (long long)x_stride, w, bias, out,
+    spk_small_form f;
+    if (const int e = fc_plan(x, x_stride, w, I, O, B, f)) return e;
+    SPK_REQUIRE(out, "fc: null pointer");
+    SPK_REQUIRE(out_stride >= O, "fc: row stride smaller than row");
+    const dim3 grid((unsigned)f.grid_x), block(FC_WAVES * 64);
+    switch (f.kernel) {
+    case FC_WIDE4:
+        hipLaunchKernelGGL(fc_wide4_kernel, grid, block, 0, (hipStream_t)stream, x, (long long)x_stride, w, bias, out,
                            (long long)out_stride, B, I, O, wmul, bmul, slope);
         return spk::check_launch("fc_wide4_kernel");
-    }
-    if (vec && I >= 2048) {
-        hipLaunchKernelGGL(fc_wide_kernel, dim3((unsigned)O), dim3(256), 0, (hipStream_t)stream, x, (long long)x_stride, w, bias, out,
+    case FC_WIDE:
+        hipLaunchKernelGGL(fc_wide_kernel, grid, block, 0, (hipStream_t)stream, x, (long long)x_stride, w, bias, out,
                            (long long)out_stride, B, I, O, wmul, bmul, slope);
         return spk::check_launch("fc_wide_kernel");
-    }
-    dim3 grid((unsigned)spk::ceil_div(O, FC_WAVES)), block(FC_WAVES * 64);
-    if (vec)
+    case FC_VEC:
+    case FC_VEC512:     // one instantiation: the kernel itself branches on I == 512
         hipLaunchKernelGGL(fc_kernel<true>, grid, block, 0, (hipStream_t)stream, x, (long long)x_stride, w, bias, out,
                            (long long)out_stride, B, I, O, wmul, bmul, slope);
-    else
+        return spk::check_launch("fc_kernel");
+    default:            // FC_SCALAR
         hipLaunchKernelGGL(fc_kernel<false>, grid, block, 0, (hipStream_t)stream, x, (long long)x_stride, w, bias, out,
                            (long long)out_stride, B, I, O, wmul, bmul, slope);
-    return spk::check_launch("fc_kernel");
+        return spk::check_launch("fc_kernel");
+    }
 }
 
 extern "C" int spk_fc_grouped_fwd(const spk_fc_group* groups, int n_groups, int B, void* stream) {

@@ -444,35 +444,61 @@ int spk_bias_noise_style_fwd(const float* x, int64_t x_batch_stride, const float
     return spk::check_launch("bias_noise_style_kernel");
 }
 
-static int conv1x1_small_launch(const float* x, const float* w, const float* mod, const float* bias, float* y, int B, int C, int O,
-                                int64_t HW, float in_scale, void* stream, const float* skip = nullptr, int W = 0) {
-    SPK_REQUIRE(x && w && y, "conv1x1_small: null pointer");
+// The one place that decides which kernel a toRGB 1x1 runs, over which grid and with how much LDS: conv1x1_small_launch
+// launches what this states, spk_conv1x1_small_form copies it out.  spk_small_form.kernel: 0 <false>, 1 <true>, 2 channel split.
+static int conv1x1_small_plan(const float* x, const float* y, int B, int C, int O, int64_t HW, bool skip, int W, spk_small_form& f) {
+    SPK_REQUIRE(x && y, "conv1x1_small: null pointer");
     SPK_REQUIRE(B > 0 && C > 0 && O > 0 && O <= 4 && HW > 0, "conv1x1_small: bad shape (O must be <= 4)");
     SPK_REQUIRE((size_t)O * C * sizeof(float) <= 48 * 1024, "conv1x1_small: weight too large for LDS");
     SPK_REQUIRE(!skip || (W > 0 && W % 2 == 0 && HW % W == 0 && (HW / W) % 2 == 0), "conv1x1_small: skip needs an even H x W image");
+    f = spk_small_form{};
+    f.grid_y = B;
+    f.grid_z = 1;
     // with a skip image a pixel quad must stay inside one row
     const bool vec = (HW % 4 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && (!skip || W % 4 == 0);
-    const size_t lds = (size_t)O * C * sizeof(float);
+    f.lds_bytes = (int64_t)((size_t)O * C * sizeof(float));
     if (vec && C >= 64 && (HW / 4 + 255) / 256 * B < 512) {   // too few pixel quads for one thread each: split the channels
         const long long n4 = HW / 4;
         const int lgQ = n4 >= 16 ? 4 : (n4 >= 8 ? 3 : (n4 >= 4 ? 2 : (n4 >= 2 ? 1 : 0)));      // Q = min(16, pow2 <= n4 ...)
         const int Q = 1 << lgQ, NS = 256 >> lgQ;
-        dim3 grid((unsigned)((n4 + Q - 1) / Q), (unsigned)B);
-        const size_t lds2 = ((size_t)((O * C + 3) & ~3) + (size_t)NS * 4 * Q * 4) * sizeof(float);
-        hipLaunchKernelGGL(conv1x1_small_csplit_kernel, grid, dim3(256), lds2, (hipStream_t)stream, x, w, bias, y, C, O,
+        f.kernel = 2;
+        f.Q = Q;
+        f.grid_x = (int)((n4 + Q - 1) / Q);
+        f.lds_bytes = (int64_t)(((size_t)((O * C + 3) & ~3) + (size_t)NS * 4 * Q * 4) * sizeof(float));
+    } else if (vec) {
+        f.kernel = 1;
+        f.grid_x = (int)stream_grid(HW / 4, 256);
+    } else {
+        f.grid_x = (int)stream_grid(HW, 256);
+    }
+    return SPK_OK;
+}
+
+static int conv1x1_small_launch(const float* x, const float* w, const float* mod, const float* bias, float* y, int B, int C, int O,
+                                int64_t HW, float in_scale, void* stream, const float* skip = nullptr, int W = 0) {
+    SPK_REQUIRE(w, "conv1x1_small: null pointer");
+    spk_small_form f;
+    if (const int e = conv1x1_small_plan(x, y, B, C, O, HW, skip != nullptr, W, f)) return e;
+    const dim3 grid((unsigned)f.grid_x, (unsigned)f.grid_y);
+    if (f.kernel == 2) {
+        int lgQ = 0;
+        while ((1 << lgQ) < f.Q) ++lgQ;
+        hipLaunchKernelGGL(conv1x1_small_csplit_kernel, grid, dim3(256), (size_t)f.lds_bytes, (hipStream_t)stream, x, w, bias, y, C, O,
                            (long long)HW, in_scale, mod, skip, W, lgQ);
         return spk::check_launch("conv1x1_small_csplit_kernel");
     }
-    if (vec) {
-        dim3 grid(stream_grid(HW / 4, 256), (unsigned)B);
-        hipLaunchKernelGGL(conv1x1_small_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, y, C, O,
+    if (f.kernel == 1)
+        hipLaunchKernelGGL(conv1x1_small_kernel<true>, grid, dim3(256), (size_t)f.lds_bytes, (hipStream_t)stream, x, w, bias, y, C, O,
                            (long long)HW, in_scale, mod, skip, W);
-    } else {
-        dim3 grid(stream_grid(HW, 256), (unsigned)B);
-        hipLaunchKernelGGL(conv1x1_small_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, y, C, O,
+    else
+        hipLaunchKernelGGL(conv1x1_small_kernel<false>, grid, dim3(256), (size_t)f.lds_bytes, (hipStream_t)stream, x, w, bias, y, C, O,
                            (long long)HW, in_scale, mod, skip, W);
-    }
     return spk::check_launch("conv1x1_small_kernel");
+}
+
+int spk_conv1x1_small_form(const float* x, const float* y, int B, int C, int O, int64_t HW, int has_skip, int W, spk_small_form* out) {
+    SPK_REQUIRE(out, "conv1x1_small form: null pointer");
+    return conv1x1_small_plan(x, y, B, C, O, HW, has_skip != 0, W, *out);
 }
 
 int spk_conv1x1_expand_fwd(const float* x, const float* w, const float* bias, const float* scale_dev, float* y, int B, int C, int O,

@@ -100,12 +100,13 @@ __global__ __launch_bounds__(256) void upfirdn2d_kernel(const float* __restrict_
 // registers with wave shuffles (ds_bpermute: the LDS crossbar, no memory traffic); up / down / k are compile-time, so the
 // zero-insertion is a parity select and the floor divisions are shifts -- no integer division or modulo in any loop.
 struct Fir1 { float fx[8], fy[8]; };      // FLIPPED 1-D factors (true convolution), fx * fy^T = the 2-D filter
+constexpr int sep_nld(int up, int down, int k) { return (64 * down + k + up - 1) / up / 64 + 1; }     // 64-column register segments a wave needs per input row
 
 template <int UP, int DOWN, int K>
 __global__ __launch_bounds__(256) void upfirdn2d_sep_kernel(const float* __restrict__ x, float* __restrict__ y, Fir1 fir, int H, int W, int Ho,
                                                            int Wo, int pad0, float gain) {
     constexpr int LG = UP == 2 ? 1 : 0;                    // UP in {1, 2}
-    constexpr int NLD = (64 * DOWN + K + UP - 1) / UP / 64 + 1;          // 64-column register segments a wave needs per input row
+    constexpr int NLD = sep_nld(UP, DOWN, K);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ox0 = blockIdx.x * 64, ox = ox0 + lane;
     const int oy = blockIdx.y * 4 + wave;
@@ -143,14 +144,11 @@ __global__ __launch_bounds__(256) void upfirdn2d_sep_kernel(const float* __restr
 }
 
 template <int UP, int DOWN>
-static bool launch_sep(int k, const float* x, float* y, const Fir1& fir, long long planes, int H, int W, int Ho, int Wo, int pad0,
-                       float gain, hipStream_t s) {
-    dim3 grid((unsigned)((Wo + 63) / 64), (unsigned)((Ho + 3) / 4), (unsigned)planes);
+static void launch_sep(int k, dim3 grid, const float* x, float* y, const Fir1& fir, int H, int W, int Ho, int Wo, int pad0, float gain,
+                       hipStream_t s) {
     if (k == 4) hipLaunchKernelGGL((upfirdn2d_sep_kernel<UP, DOWN, 4>), grid, dim3(256), 0, s, x, y, fir, H, W, Ho, Wo, pad0, gain);
     else if (k == 3) hipLaunchKernelGGL((upfirdn2d_sep_kernel<UP, DOWN, 3>), grid, dim3(256), 0, s, x, y, fir, H, W, Ho, Wo, pad0, gain);
-    else if (k == 2) hipLaunchKernelGGL((upfirdn2d_sep_kernel<UP, DOWN, 2>), grid, dim3(256), 0, s, x, y, fir, H, W, Ho, Wo, pad0, gain);
-    else return false;
-    return true;
+    else hipLaunchKernelGGL((upfirdn2d_sep_kernel<UP, DOWN, 2>), grid, dim3(256), 0, s, x, y, fir, H, W, Ho, Wo, pad0, gain);      // the plan admits K = 2 .. 4
 }
 
 // f2d[i][j] == fy[i] * fx[j]?  (rank one; the factors of the FLIPPED filter are the flipped factors)
@@ -171,6 +169,37 @@ static bool separate(const float* f, int k, float* fx, float* fy) {
 }
 
 inline unsigned sgrid2(long long n) { return (unsigned)std::max(1ll, std::min((n + 255) / 256, 256ll * 16)); }
+
+// The one place that decides which kernel an upfirdn2d runs and over which grid: spk_upfirdn2d_fwd launches what this states,
+// spk_upfirdn2d_form copies it out.  On the separable form fx / fy receive the factors separate() found (unflipped).
+int upfirdn2d_plan(const float* filter_host, int k, int64_t planes, int H, int W, int up, int down, int pad0, int pad1,
+                   spk_small_form& f, float* fx, float* fy) {
+    SPK_REQUIRE(filter_host && k >= 1 && k <= 7 && planes > 0 && H > 0 && W > 0 && up >= 1 && down >= 1,
+                "upfirdn2d: bad arguments (k <= 7)");
+    // (a padded extent below k is an empty output whatever `down`: C's division would round -1 / 2 up to 0)
+    SPK_REQUIRE(H * up + pad0 + pad1 >= k && W * up + pad0 + pad1 >= k, "upfirdn2d: empty output");
+    const int Ho = (H * up + pad0 + pad1 - k) / down + 1, Wo = (W * up + pad0 + pad1 - k) / down + 1;
+    f = spk_small_form{};
+    f.Ho = Ho;
+    f.Wo = Wo;
+    static const bool allow_sep = [] { const char* e = getenv("SPK_UPFIRDN_SEP"); return !e || atoi(e) != 0; }();
+    if (allow_sep && k >= 2 && k <= 4 && up <= 2 && down <= 2 && planes < 65536 && (Ho + 3) / 4 < 65536 && separate(filter_host, k, fx, fy)) {
+        f.kernel = 1;
+        f.UP = up;
+        f.DOWN = down;
+        f.K = k;
+        f.NLD = sep_nld(up, down, k);
+        f.grid_x = (Wo + 63) / 64;
+        f.grid_y = (Ho + 3) / 4;
+        f.grid_z = (int)planes;
+        return SPK_OK;
+    }
+    const long long total = (long long)planes * Ho * Wo;
+    f.grid_x = (int)sgrid2(total);
+    f.grid_y = f.grid_z = 1;
+    f.grid_loop = total > 256ll * f.grid_x;
+    return SPK_OK;
+}
 
 }  // namespace
 
@@ -202,28 +231,33 @@ int spk_modconv_demod_grouped(const spk_demod_group* groups, int n_groups, int B
 
 int spk_upfirdn2d_fwd(const float* x, float* y, const float* filter_host, int k, int64_t planes, int H, int W, int up, int down,
                       int pad0, int pad1, float gain, void* stream) {
-    SPK_REQUIRE(x && y && filter_host && k >= 1 && k <= 7 && planes > 0 && H > 0 && W > 0 && up >= 1 && down >= 1,
-                "upfirdn2d: bad arguments (k <= 7)");
-    const int Ho = (H * up + pad0 + pad1 - k) / down + 1, Wo = (W * up + pad0 + pad1 - k) / down + 1;
-    SPK_REQUIRE(Ho > 0 && Wo > 0, "upfirdn2d: empty output");
-    static const bool allow_sep = [] { const char* e = getenv("SPK_UPFIRDN_SEP"); return !e || atoi(e) != 0; }();
+    spk_small_form f;
     float fx[8], fy[8];
-    if (allow_sep && k <= 4 && up <= 2 && down <= 2 && planes < 65536 && (Ho + 3) / 4 < 65536 && separate(filter_host, k, fx, fy)) {
+    if (const int e = upfirdn2d_plan(filter_host, k, planes, H, W, up, down, pad0, pad1, f, fx, fy)) return e;
+    SPK_REQUIRE(x && y, "upfirdn2d: null pointer");
+    const dim3 grid((unsigned)f.grid_x, (unsigned)f.grid_y, (unsigned)f.grid_z);
+    if (f.kernel == 1) {
         Fir1 f1;
         for (int i = 0; i < k; ++i) { f1.fx[i] = fx[k - 1 - i]; f1.fy[i] = fy[k - 1 - i]; }     // flipped: upfirdn2d is a true convolution
-        bool ok;
-        if (up == 1) ok = down == 1 ? launch_sep<1, 1>(k, x, y, f1, planes, H, W, Ho, Wo, pad0, gain, (hipStream_t)stream)
-                                    : launch_sep<1, 2>(k, x, y, f1, planes, H, W, Ho, Wo, pad0, gain, (hipStream_t)stream);
-        else ok = down == 1 ? launch_sep<2, 1>(k, x, y, f1, planes, H, W, Ho, Wo, pad0, gain, (hipStream_t)stream)
-                            : launch_sep<2, 2>(k, x, y, f1, planes, H, W, Ho, Wo, pad0, gain, (hipStream_t)stream);
-        if (ok) return spk::check_launch("upfirdn2d_sep_kernel");
+        if (f.UP == 1) f.DOWN == 1 ? launch_sep<1, 1>(f.K, grid, x, y, f1, H, W, f.Ho, f.Wo, pad0, gain, (hipStream_t)stream)
+                                   : launch_sep<1, 2>(f.K, grid, x, y, f1, H, W, f.Ho, f.Wo, pad0, gain, (hipStream_t)stream);
+        else f.DOWN == 1 ? launch_sep<2, 1>(f.K, grid, x, y, f1, H, W, f.Ho, f.Wo, pad0, gain, (hipStream_t)stream)
+                         : launch_sep<2, 2>(f.K, grid, x, y, f1, H, W, f.Ho, f.Wo, pad0, gain, (hipStream_t)stream);
+        return spk::check_launch("upfirdn2d_sep_kernel");
     }
     Fir2 fir;
     fir.k = k;
     for (int i = 0; i < k * k; ++i) fir.f[i] = filter_host[i];
-    hipLaunchKernelGGL(upfirdn2d_kernel, dim3(sgrid2((long long)planes * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, x, y, fir,
-                       (long long)planes, H, W, Ho, Wo, up, down, pad0, gain);
+    hipLaunchKernelGGL(upfirdn2d_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, y, fir, (long long)planes, H, W, f.Ho, f.Wo, up, down,
+                       pad0, gain);
     return spk::check_launch("upfirdn2d_kernel");
+}
+
+int spk_upfirdn2d_form(const float* filter_host, int k, int64_t planes, int H, int W, int up, int down, int pad0, int pad1,
+                       spk_small_form* out) {
+    SPK_REQUIRE(out, "upfirdn2d form: null pointer");
+    float fx[8], fy[8];
+    return upfirdn2d_plan(filter_host, k, planes, H, W, up, down, pad0, pad1, *out, fx, fy);
 }
 
 }  // extern "C"

@@ -41,6 +41,9 @@ def dev():
     (1, 1, (-1, 0), (1, 3, 3, 1), (1, 1, 8, 8)),      # negative padding = crop
 ])
 def test_upfirdn2d(ops, dev, up, down, pad, k1d, shape):
+    """StyleGAN2's own uses at small sizes, held to an aggregate norm: every output here is at most 16 columns wide and every filter
+    symmetric with fx == fy.  The per-branch tests -- all twelve separable instantiations at three widths, asymmetric filters, the
+    generic kernel, exact impulses, element-wise bounds -- are tests/test_small_fwd_kernels_gpu.py's (cases: small_fwd_cases.py)."""
     x = recipe_input(f"ufd.{up}.{down}.{pad}.{shape}", shape)
     k = M.make_kernel(k1d) * (up ** 2)
     ref = M.upfirdn2d(x, k, up, down, pad)
@@ -289,8 +292,10 @@ def test_variant_launch_plan_equals_launch_by_launch(sg2, dev):
 
 @pytest.mark.parametrize("B,C,H,W", [(2, 32, 16, 16), (1, 70, 6, 10), (3, 512, 8, 8), (8, 64, 64, 64)])
 def test_to_rgb_with_fused_skip_upsample(ops, dev, B, C, H, W):
-    """Modulated 1x1 + bias + upfirdn2d(skip, up=2, [1,3,3,1]) + add in one launch -- every kernel variant (vector,
-    channel-split, scalar for W % 4 != 0) -- against the oracle's materialised Upsample and sum."""
+    """Modulated 1x1 + bias + upfirdn2d(skip, up=2, [1,3,3,1]) + add in one launch against the oracle's materialised Upsample and
+    sum.  The four cases take, in order: conv1x1_small_kernel<true> (C = 32 < 64), conv1x1_small_kernel<false> (W % 4 == 2), and the
+    channel-split kernel twice -- (8, 64, 64, 64) too: its (HW/4 + 255) / 256 * B = 32 is below the gate's 512.  <true> with a skip
+    at C >= 64 and the other branches are tests/test_small_fwd_kernels_gpu.py's, by name (spk_conv1x1_small_form)."""
     x = recipe_input(f"rgbs.x.{B}.{C}.{H}.{W}", (B, C, H, W))
     wt = recipe_input(f"rgbs.w.{C}", (3, C, 1, 1))
     mod = 1.0 + 0.3 * recipe_input(f"rgbs.m.{B}.{C}", (B, C))

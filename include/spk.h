@@ -1163,6 +1163,55 @@ int spk_paste_colour_sums_sim_table(const float* src, int N, int Hs, int Ws, con
                                     double feather, float lo, float k, const float* matte_dev, int matte_frames, double* sums_out_dev,
                                     void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- the aligned NV12 edge over a surface table: every surface its own planes, pitches and size (csrc/frame_table_nv12.hip) --------
+ * What the frame table is to packed frames, for NV12: each call's hardware decoder delivers a surface of that call's own
+ * resolution into that call's own buffer, and the encoder wants it back.  A surface is two planes with two pitches, so an entry
+ * holds more than one pointer and one stride.  A SURFACE TABLE is N entries of spk_surface_ref in DEVICE memory, 8-byte aligned,
+ *     y, uv: the first bytes of the Y plane and of the interleaved UV plane;  y_row_stride, uv_row_stride: bytes from row to row;
+ *     H, W: the size in luma pixels (the UV plane has H / 2 rows of W bytes)
+ * which the kernels read and the entry points never do.  Surface n uses entry n, sim row n, matte n (or the shared matte) and
+ * colour row n.  An entry is USABLE when y != NULL, uv != NULL, H >= 2, W >= 2, H and W even, y_row_stride >= W,
+ * uv_row_stride >= W, uv_row_stride even and uv 2-byte aligned; any other entry means THE SURFACE IS ABSENT.  The kernels decide
+ * this themselves, with the whole predicate, before they form an address from an entry, so an all-zero entry is safe, and an absent
+ * surface is treated exactly like an invalid sim row: the way in writes shift_c, the paste writes nothing, the sums are 13 zeros
+ * (the rows (1, 0)).  A usable entry is trusted as a strided call's pointers and strides are: its bytes must be the caller's.
+ *
+ * spk_frames_nv12_to_f32_sim_table, spk_frames_paste_nv12_sim_table (plain and seamless in one entry point, as the strided one),
+ * spk_paste_colour_sums_nv12_sim_table, spk_paste_colour_match_nv12_sim_table: the arguments of spk_frames_nv12_to_f32_sim,
+ *   spk_frames_paste_nv12_sim, spk_paste_colour_sums_nv12_sim and spk_paste_colour_match_nv12_sim with (table_dev, N) in place of
+ *   the two plane pointers, the four strides and H, W.  The kernels are those of the strided entry points over another way to say
+ *   where a surface is, and their work decomposition does not depend on the size: surface n of a table is bit for bit the strided
+ *   call at N = 1 on entry n's (y, y_row_stride, uv, uv_row_stride, H, W) with row, matte and colour row n.  The launches are the
+ *   strided siblings' (one; two for the statistics).  The surfaces the paste is given are WRITTEN: no two planes of usable entries
+ *   may share a byte (spk_surface_table_check with written = 1 on the host copy).
+ * Refused before any launch (SPK_EINVAL, spk_last_error): what the strided siblings refuse of the arguments they share, standard
+ *   and full_range included; a null or misaligned table; N < 1; a table that overlaps dst (way in), the sums / colour rows or the
+ *   workspace (statistics), byte counts saturating at 64 bits.
+ * spk_surface_table_check: pure host code over a HOST copy of a table, what a binder calls before it uploads.  Refused, with the
+ *   offending index (or pair) in spk_last_error: a null table; N < 1; a half-formed entry (neither usable nor all zero; the message
+ *   has its fields); a plane extent, (H - 1) y_row_stride + W for Y and (H / 2 - 1) uv_row_stride + W for UV, that leaves 64 bits, or
+ *   whose end address does; and, with written != 0, any two of the 2 x (usable entries) plane ranges that share a byte -- an
+ *   entry's own Y against its own UV included.  Ranges that touch are apart, and written = 0 tolerates overlap (the way in and the
+ *   statistics only read).
+ * replaces: a full-frame NV12 -> BGR -> NV12 round trip per feed per tick around the packed frame table, to change a face-sized region. */
+typedef struct spk_surface_ref {
+    const uint8_t* y; const uint8_t* uv; int64_t y_row_stride; int64_t uv_row_stride; int32_t H, W;
+} spk_surface_ref;                                                                                      /* 40 bytes: 8, 8, 8, 8, 4, 4 */
+int spk_surface_table_check(const spk_surface_ref* host_table, int N, int written);
+int spk_frames_nv12_to_f32_sim_table(const spk_surface_ref* table_dev, int N, const float* sim_dev, int swap_rb, int standard, int full_range,
+                                     float* dst, int Hout, int Wout, float scale0, float scale1, float scale2, float shift0, float shift1,
+                                     float shift2, void* stream);
+int spk_frames_paste_nv12_sim_table(const float* src, int N, int Hs, int Ws, const spk_surface_ref* table_dev, const float* sim_dev, int standard,
+                                    int full_range, double feather, float lo, float k, const float* matte_dev, int matte_frames,
+                                    const float* colour_dev, void* stream);
+int spk_paste_colour_match_nv12_sim_table(const float* src, int N, int Hs, int Ws, const spk_surface_ref* table_dev, const float* sim_dev,
+                                          int standard, int full_range, double feather, float lo, float k, const float* matte_dev,
+                                          int matte_frames, double max_gain, double min_sigma, double min_weight, float* colour_out_dev,
+                                          void* workspace_dev, size_t workspace_bytes, void* stream);
+int spk_paste_colour_sums_nv12_sim_table(const float* src, int N, int Hs, int Ws, const spk_surface_ref* table_dev, const float* sim_dev,
+                                         int standard, int full_range, double feather, float lo, float k, const float* matte_dev,
+                                         int matte_frames, double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- causal filters with their state on the device: what a live feed can use (csrc/causal_filter.hip) ------------------------------
  * spk_sim_smooth, the contour window of spk_matte_from_landmarks and spk_colour_rows_window look at frames t - r ... t + r: they
  * serve a clip that is in memory.  On a camera or call feed frame t + 1 does not exist yet.  These two are the causal counterparts:

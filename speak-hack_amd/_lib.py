@@ -128,6 +128,12 @@ class FrameRef(C.Structure):
     _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int64), ("H", C.c_int32), ("W", C.c_int32)]
 
 
+class SurfaceRef(C.Structure):
+    """``spk_surface_ref`` (include/spk.h): one entry of a surface table, 40 bytes."""
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("y_row_stride", C.c_int64), ("uv_row_stride", C.c_int64), ("H", C.c_int32),
+                ("W", C.c_int32)]
+
+
 # ---- launch lists (include/spk.h: spk_launch_list) ----
 OP_CONV2D, OP_FC, OP_FC_GROUPED, OP_BIAS_NOISE_STYLE, OP_TORGB, OP_DEMOD_GROUPED, OP_PIXELNORM, OP_UPSAMPLE2X = 1, 2, 3, 4, 5, 6, 7, 8
 OP_MAXPOOL3X3S2, OP_GLOBAL_AVGPOOL = 9, 10
@@ -389,6 +395,16 @@ _PROTOTYPES = {
                                                    C.c_size_t, C.c_void_p]),
     "spk_paste_colour_sums_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_float,
                                                   C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_surface_table_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "spk_frames_nv12_to_f32_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] +
+                                         [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_paste_nv12_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                  C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "spk_paste_colour_match_nv12_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                        C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_paste_colour_sums_nv12_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                       C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spk_colour_rows_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p]),
     "spk_causal_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,

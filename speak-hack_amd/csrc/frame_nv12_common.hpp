@@ -15,6 +15,41 @@ __device__ __forceinline__ double affine_row(const Mat34& M, int c, double p0, d
     return fma(M.m[4 * c + 2], p2, fma(M.m[4 * c + 1], p1, fma(M.m[4 * c], p0, M.m[4 * c + 3])));
 }
 
+// How the bytes of a surface become the sums of the way in and the background of the statistics, for every policy that says where
+// a surface is (csrc/frame_sim_nv12.hip: planes and strides; csrc/frame_table_nv12.hip: an entry of a device table), as RgbTaps of
+// csrc/frame_sim_common.hpp is for packed bytes.  The way in: the three sums run over Y[iy][ix], U[iy >> 1][ix >> 1] and
+// V[iy >> 1][ix >> 1]; luma is byte loads, a (U, V) pair is one 16-bit load that stays in a register while ix >> 1 does not change,
+// so it serves the two taps above it; the matrix and the clamp follow the means.  The statistics: the background of a region pixel
+// is what the way in makes of that pixel, by network channel.  Policy: the deriving struct, which holds to_rgb (a Mat34).
+struct Nv12Row { const uint8_t* y; const uint8_t* c; unsigned pair; };
+
+template <class Policy>
+struct Nv12Taps {
+    using Row = Nv12Row;
+    // row iy of a frame whose planes begin at y and uv
+    __device__ __forceinline__ static Row open_row(const uint8_t* y, long long y_row_stride, const uint8_t* uv, long long uv_row_stride, int iy) {
+        return {y + (long long)iy * y_row_stride, uv + (long long)(iy >> 1) * uv_row_stride, 0u};
+    }
+    __device__ __forceinline__ void tap(Row& r, int ix, bool first, double w, double& a_y, double& a_u, double& a_v) const {
+        if (first || !(ix & 1)) r.pair = *reinterpret_cast<const uint16_t*>(r.c + (ix & ~1));       // sample ix >> 1
+        a_y = fma(w, (double)r.y[ix], a_y);
+        a_u = fma(w, (double)(r.pair & 0xffu), a_u);
+        a_v = fma(w, (double)(r.pair >> 8), a_v);
+    }
+    __device__ __forceinline__ void rgb(double y, double u, double v, double (&val)[3]) const {
+        const Mat34& to_rgb = static_cast<const Policy*>(this)->to_rgb;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) val[c] = fmin(fmax(affine_row(to_rgb, c, y, u, v), 0.0), 255.0);
+    }
+    // pixel (Y, X) of a frame whose planes begin at y and uv, as R, G, B
+    __device__ __forceinline__ void background(const uint8_t* y, long long y_row_stride, const uint8_t* uv, long long uv_row_stride, int X, int Y,
+                                               double (&b)[3]) const {
+        const double l = (double)y[(long long)Y * y_row_stride + X];
+        const unsigned pair = *reinterpret_cast<const uint16_t*>(uv + (long long)(Y >> 1) * uv_row_stride + (X & ~1));
+        rgb(l, (double)(pair & 0xffu), (double)(pair >> 8), b);
+    }
+};
+
 // (Kr, Kb) of a standard; false: unknown
 inline bool primaries(int standard, double* kr, double* kb) {
     if (standard == 601) { *kr = 0.299; *kb = 0.114; return true; }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "frame_blend_common.hpp"
+#include "frame_table_common.hpp"
 
 static_assert(sizeof(spk_frame_ref) == 24 && alignof(spk_frame_ref) == 8, "spk_frame_ref is 8 + 8 + 4 + 4 bytes");
 
@@ -59,32 +60,7 @@ struct TableTarget {                    // the paste: the frames of a table that
     }
 };
 
-// ---- host ----
-bool ranges_overlap(const void* a, unsigned long long a_bytes, const void* b, unsigned long long b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 ? b0 - a0 < a_bytes : a0 - b0 < b_bytes;
-}
-
-// a table as an entry point sees it: a device pointer and a count (its entries are the kernels' to judge)
-int check_table(const char* who, const spk_frame_ref* table_dev, int N) {
-    SPK_REQUIRE(table_dev, "%s: null frame table", who);
-    SPK_REQUIRE((uintptr_t)table_dev % alignof(spk_frame_ref) == 0, "%s: the frame table must be aligned to %zu bytes", who, alignof(spk_frame_ref));
-    SPK_REQUIRE(N >= 1, "%s: N must be >= 1 (got %d)", who, N);
-    return SPK_OK;
-}
-
-// count * each bytes, saturated: a size that leaves 64 bits covers everything behind its first byte
-unsigned long long bytes_of(unsigned long long count, unsigned long long each) {
-    unsigned long long b;
-    return __builtin_mul_overflow(count, each, &b) ? ~0ull : b;
-}
-
-int check_table_apart(const char* who, const spk_frame_ref* table_dev, int N, const void* written, unsigned long long bytes, const char* name) {
-    SPK_REQUIRE(!ranges_overlap(table_dev, (unsigned long long)N * sizeof(spk_frame_ref), written, bytes), "%s: the frame table overlaps %s", who,
-                name);
-    return SPK_OK;
-}
-
+// ---- host (ranges_overlap, bytes_of, check_table and check_table_apart: csrc/frame_table_common.hpp) ----
 // what the tabled paste and its statistics check alike: check_paste_u8 without the frames' own pointer, strides and size
 int check_paste_table(const char* who, const void* src, const spk_frame_ref* table_dev, const float* sim_dev, int N, int Hs, int Ws, double feather,
                       float lo, float k, const float* matte_dev, int matte_frames) {

@@ -1,7 +1,8 @@
 """The video-frame edge of the inference path: uint8 frames as a video decoder / writer holds them on the device, in and out of the
 network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packed RGB through a similarity transform per frame
 (csrc/frame_sim.hip: aligned crops; csrc/frame_blend.hip: their paste with a face matte and a colour match; csrc/frame_sim_nv12.hip:
-all of that on NV12 surfaces; csrc/frame_table.hip: on frames in buffers and of sizes of their own), whose rows
+all of that on NV12 surfaces; csrc/frame_table.hip: on frames in buffers and of sizes of their own; csrc/frame_table_nv12.hip: on
+NV12 surfaces in planes, of pitches and of sizes of their own), whose rows
 csrc/landmark_sim.hip fits to landmarks and smooths; csrc/causal_filter.hip: the causal filters of a live feed, their state on
 the device).  ``ops`` re-exports the
 launchers (``ops.frames_from_u8`` ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
@@ -316,6 +317,7 @@ class FrameTable:
 class _Tabled:
     """``_Packed`` for a ``FrameTable``: the frames of a call as entries of a device table (csrc/frame_table.hip).  The size of a
     frame is its entry's, so an entry point takes none; the frames are addressed where they are, never copied."""
+    noun = "frame table"
     way_in, paste = "spk_frames_u8_to_f32_sim_table", "spk_frames_paste_u8_sim_table"
     sums, match = "spk_paste_colour_sums_sim_table", "spk_paste_colour_match_sim_table"
 
@@ -326,14 +328,14 @@ class _Tabled:
 
     def on_device(self, table, device=None):                              # a table is on a device by construction: on x's?
         if device is not None and table.device != device:
-            raise L.SpkError(f"frames: the frame table on {table.device}, x on {device}")
+            raise L.SpkError(f"frames: the {self.noun} on {table.device}, x on {device}")
 
     def read(self, table, what, disjoint=False):
         return table.dev, (table.dev.data_ptr(),)
 
     def target(self, table, out, N, H, W, device, what):
         if out is not None and out is not table:
-            raise L.SpkError(f"{what}: a frame table is pasted in place: out must be None or the table itself")
+            raise L.SpkError(f"{what}: a {self.noun} is pasted in place: out must be None or the table itself")
         table.check_written()                                             # (its device is x's: ``on_device`` saw to it)
         return table, (table.dev.data_ptr(),), lambda: None
 
@@ -1345,6 +1347,139 @@ class _Surfaces:
 _SURFACES = _Surfaces()
 
 
+# ---- a surface table: every NV12 surface its own planes, pitches and size (csrc/frame_table_nv12.hip; include/spk.h) ---------------
+def plane_pair(nv12) -> bool:
+    """A pair ``(y, uv)`` of planes -- the UV plane has one dimension more -- and not a sequence of two surfaces"""
+    return isinstance(nv12, (tuple, list)) and len(nv12) == 2 and all(isinstance(t, torch.Tensor) for t in nv12) and \
+        nv12[1].dim() == nv12[0].dim() + 1
+
+
+class SurfaceTable:
+    """``N`` NV12 surfaces that share neither an allocation nor a size, as the aligned NV12 launchers address them: a device table of
+    ``spk_surface_ref`` entries ``(y, uv, y_row_stride, uv_row_stride, H, W)``.  ``surfaces``: a sequence whose elements are what
+    ``nv12_planes`` takes for ONE frame -- a uint8 tensor ``[3H/2, W]`` with unit pixel stride and any (even) pitch, or a pair
+    ``(y [H,W], uv [H/2,W/2,2])`` of planes that live apart; a region of interest at even offsets of a wider surface is such a pair
+    of views -- on one device, with ``None`` for a surface that is ABSENT (an all-zero entry: the launchers treat it like an invalid
+    transform); or one ``[N,3H/2,W]`` tensor or one pair of planes ``(y [N,H,W], uv [N,H/2,W/2,2])``, which give views of their
+    frames.  Wrong types, shapes or strides raise ``ValueError`` before a device is touched; CPU tensors raise ``SpkError`` (no CPU
+    path).  The host table is checked (``spk_surface_table_check``) here and uploaded ONCE, one host -> device copy of ``40 N`` bytes
+    on the current stream, when a launcher first uses the table (so a call that is refused on the host has copied nothing); whether
+    the surfaces may be written is decided where the table is used (``check_written``: the paste).  The table HOLDS REFERENCES to the
+    tensors, so the addresses in it stay the tensors' for as long as it lives.
+
+    ``dev``: the device table (uint8 ``[40 N]``); ``sizes``: ``(H, W)`` per surface (``(0, 0)``: absent); ``surfaces``: the elements as
+    they were given; ``planes``: ``(y [H,W], uv [H/2,W/2,2])`` views per surface, or None."""
+
+    def __init__(self, surfaces):
+        what = "SurfaceTable"
+        if isinstance(surfaces, torch.Tensor) or plane_pair(surfaces):
+            if isinstance(surfaces, torch.Tensor) and surfaces.dim() != 3:
+                raise ValueError(f"{what}: a tensor of surfaces must be [N,3H/2,W], got {tuple(surfaces.shape)}")
+            y, uv = nv12_planes(surfaces)
+            surfaces = list(zip(y.unbind(0), uv.unbind(0)))
+        else:
+            try:
+                surfaces = list(surfaces)
+            except TypeError:
+                raise ValueError(f"{what}: surfaces must be a sequence of NV12 surfaces ([3H/2,W] tensors or pairs of planes), a tensor "
+                                 f"[N,3H/2,W] or a pair of planes, got {type(surfaces).__name__}") from None
+        if not surfaces:
+            raise ValueError(f"{what}: a table needs at least one surface")
+        planes = []
+        for n, s in enumerate(surfaces):
+            if s is None:
+                planes.append(None)
+                continue
+            if isinstance(s, torch.Tensor) and s.dim() != 2:
+                raise ValueError(f"{what}: surfaces[{n}] must be ONE surface, a uint8 tensor [3H/2,W] or a pair (y [H,W], uv [H/2,W/2,2]), "
+                                 f"got {tuple(s.shape)}")
+            try:
+                y, uv = nv12_planes(s)
+            except ValueError as e:
+                raise ValueError(f"{what}: surfaces[{n}]: {e}") from None
+            if y.size(0) != 1:
+                raise ValueError(f"{what}: surfaces[{n}] must be ONE surface, got planes of {y.size(0)} frames")
+            y, uv = y[0], uv[0]
+            W = y.size(1)
+            if y.stride(1) != 1 or uv.stride(2) != 1 or uv.stride(1) != 2 or y.stride(0) < W or uv.stride(0) < W or uv.stride(0) % 2:
+                raise ValueError(f"{what}: surfaces[{n}]: the Y pixel stride must be 1, a UV pair packed, rows must hold W = {W} bytes and the "
+                                 f"UV pitch be even, got strides {y.stride()} and {uv.stride()}")
+            planes.append((y, uv))
+        there = [p for p in planes if p is not None]
+        if any(not p[0].is_cuda for p in there):
+            raise L.SpkError(f"{what}: expected uint8 HIP tensors, got a surface on the CPU (no CPU path)")
+        if any(p[0].device != there[0][0].device for p in there):
+            raise L.SpkError(f"{what}: the surfaces must be on one device, got {sorted({str(p[0].device) for p in there})}")
+        self.surfaces, self.planes, self.N = surfaces, planes, len(surfaces)
+        self.sizes = [(0, 0) if p is None else tuple(p[0].shape) for p in planes]
+        self._host = (L.SurfaceRef * self.N)()
+        for e, p in zip(self._host, planes):
+            if p is not None:
+                e.y, e.uv, e.y_row_stride, e.uv_row_stride, e.H, e.W = p[0].data_ptr(), p[1].data_ptr(), p[0].stride(0), p[1].stride(0), *p[0].shape
+        L.check(L.lib().spk_surface_table_check(C.addressof(self._host), self.N, 0), "spk_surface_table_check")
+        self._written = False
+        self.device = there[0][0].device if there else torch.device("cuda", torch.cuda.current_device())
+        self._dev = None
+
+    @property
+    def dev(self):
+        """The device table, uploaded when a launcher first asks for it: every host check of a call comes before the copy"""
+        if self._dev is None:
+            self._dev = torch.empty(C.sizeof(self._host), dtype=torch.uint8, device=self.device)
+            self._dev.copy_(torch.frombuffer(self._host, dtype=torch.uint8))
+        return self._dev
+
+    def __len__(self):
+        return self.N
+
+    def check_written(self):
+        """The surfaces are about to be written: no two planes may share bytes (``spk_surface_table_check`` with ``written``), else ``SpkError``"""
+        if not self._written:
+            L.check(L.lib().spk_surface_table_check(C.addressof(self._host), self.N, 1), "spk_surface_table_check")
+            self._written = True
+
+
+class _TabledSurfaces(_Tabled):
+    """``_Surfaces`` for a ``SurfaceTable``, as ``_Tabled`` is ``_Packed`` for a ``FrameTable`` (csrc/frame_table_nv12.hip): the size
+    of a surface is its entry's, the surfaces are addressed where they are, and the colour arguments are NV12's."""
+    noun = "surface table"
+    way_in, paste = "spk_frames_nv12_to_f32_sim_table", "spk_frames_paste_nv12_sim_table"
+    sums, match = "spk_paste_colour_sums_nv12_sim_table", "spk_paste_colour_match_nv12_sim_table"
+
+    def standard(self, standard="bt601", full_range=False):
+        return yuv_standard(standard, full_range)
+
+    def quantised(self, value_range, standard="bt601", full_range=False):
+        return _SURFACES.quantised(value_range, standard, full_range)
+
+
+_TABLED_SURFACES = _TabledSurfaces()
+
+
+def _nv12_format(nv12):                                                   # a tensor or a pair takes exactly the path it always took
+    return _TABLED_SURFACES if isinstance(nv12, SurfaceTable) else _SURFACES
+
+
+def clone_surfaces(nv12):
+    """A packed copy of the surfaces to paste into: of a ``SurfaceTable`` a new table over one packed ``[3H/2, W]`` clone per surface (a
+    table of its own: its host check and, at its first launch, its upload come on top of the clones); else the one clone of
+    ``Nv12.clone``, a packed ``[N, 3H/2, W]`` tensor"""
+    if isinstance(nv12, SurfaceTable):
+        clones = []
+        for p in nv12.planes:
+            if p is None:
+                clones.append(None)
+                continue
+            out, _, fill = _SURFACES.target((p[0].unsqueeze(0), p[1].unsqueeze(0)), None, 1, *p[0].shape, p[0].device, "clone_surfaces")
+            fill()
+            clones.append(out[0])
+        return SurfaceTable(clones)
+    planes = nv12_planes(nv12)
+    out, _, fill = _SURFACES.target(planes, None, *planes[0].shape, planes[0].device, "clone_surfaces")
+    fill()
+    return out
+
+
 def frames_to_nv12(x, *, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
     """Network frames -> NV12 for a hardware encoder, one launch (``spk_frames_f32_to_nv12``): float32 [N,3,H,W] (R, G, B planes,
     ``H`` and ``W`` even) in ``value_range`` is quantised as ``frames_to_u8`` does without its rounding, converted with
@@ -1396,8 +1531,10 @@ def frames_from_nv12_aligned(nv12, size, sim, *, channel_order="rgb", mean=0.5, 
     ``(x / 255 - mean) / std`` as ``frames_from_nv12``.  An output whose footprint misses the frame is ``-mean / std`` exactly, and
     so is every output of a frame whose device row is invalid.  ``nv12``: what ``nv12_planes`` takes, on the device, read in place
     through its strides; ``sim``: the two forms of ``parse_sim``; ``channel_order``: the plane order of the result, as
-    ``frames_from_nv12``.  -> float32 [N,3,size,size]."""
-    return _from_aligned(_SURFACES, "frames_from_nv12_aligned", nv12, size, sim, channel_order, mean, std, standard=standard, full_range=full_range)
+    ``frames_from_nv12``.  ``nv12`` may be a ``SurfaceTable``: surfaces of their own sizes in their own buffers, still one launch
+    (``spk_frames_nv12_to_f32_sim_table``), frame ``n`` bit for bit this call on surface ``n`` alone; an absent surface gives
+    ``-mean / std``.  -> float32 [N,3,size,size]."""
+    return _from_aligned(_nv12_format(nv12), "frames_from_nv12_aligned", nv12, size, sim, channel_order, mean, std, standard=standard, full_range=full_range)
 
 
 def frames_paste_nv12_aligned(x, nv12, sim, *, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None, matte=None,
@@ -1409,8 +1546,12 @@ def frames_paste_nv12_aligned(x, nv12, sim, *, feather=0, value_range=(-1, 1), s
     ``yuv_coeffs`` and blended as ``frames_paste_nv12`` blends: luma per pixel, chroma per 2 x 2 block as the quarter-weighted sum
     of the block's region pixels over the sample underneath.  Every byte outside the region's pixels and blocks is left as it is; a
     device row that is invalid leaves its frame untouched.  ``nv12``, ``out``: as ``frames_paste_nv12`` (``out=nv12`` pastes in
-    place).  -> uint8 [N, 3H/2, W], or ``out``."""
-    return _paste_aligned(_SURFACES, "frames_paste_nv12_aligned", x, nv12, sim, feather, value_range, out, matte, colour, standard=standard,
+    place).  -> uint8 [N, 3H/2, W], or ``out``.
+
+    ``nv12`` may be a ``SurfaceTable`` (``spk_frames_paste_nv12_sim_table``, one launch): the paste is then IN PLACE, into the table's
+    own surfaces (``out``: None or the table), no two planes of which may share bytes; an absent surface is left alone; surface ``n``
+    gets the bytes of this call on surface ``n`` alone.  -> the table."""
+    return _paste_aligned(_nv12_format(nv12), "frames_paste_nv12_aligned", x, nv12, sim, feather, value_range, out, matte, colour, standard=standard,
                           full_range=full_range)
 
 
@@ -1420,19 +1561,21 @@ def paste_colour_match_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=
     ``paste_colour_match`` for a surface background.  The same sums, weights, row formula and arguments; the background of a
     region pixel is what ``frames_from_nv12_aligned`` makes of it, ``clamp(to_rgb . (Y, U, V, 1))``, so the rows are per network
     channel R, G, B.  ``nv12`` is only read -- call this BEFORE pasting in place.  Reduced in a fixed order without atomics: the
-    same inputs give the same bits.  ``out``: a contiguous device float32 ``[N,3,2]`` tensor to write.
+    same inputs give the same bits.  ``out``: a contiguous device float32 ``[N,3,2]`` tensor to write.  ``nv12`` may be a
+    ``SurfaceTable`` (``spk_paste_colour_match_nv12_sim_table``; an absent surface gets ``(1, 0)``).
     -> device float32 ``[N,3,2]``."""
     what = "paste_colour_match_nv12"
     params = _check_match_params(what, max_gain, min_sigma, min_weight)
-    return _colour_statistics(_SURFACES, params, what, x, nv12, sim, matte, feather, value_range, out, standard=standard, full_range=full_range)
+    return _colour_statistics(_nv12_format(nv12), params, what, x, nv12, sim, matte, feather, value_range, out, standard=standard, full_range=full_range)
 
 
 def paste_colour_sums_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
     """``paste_colour_sums`` for a surface background, two launches (``spk_paste_colour_sums_nv12_sim``): the 13 sums
     ``paste_colour_match_nv12`` makes its rows from, bit for bit, per network channel R, G, B -- so ``colour_rows_from_sums`` serves
-    both pixel formats.  ``out``: a contiguous device float64 ``[N,13]`` tensor to write (a slice of a clip-long one).
+    both pixel formats.  ``out``: a contiguous device float64 ``[N,13]`` tensor to write (a slice of a clip-long one).  ``nv12`` may
+    be a ``SurfaceTable`` (``spk_paste_colour_sums_nv12_sim_table``; 13 zeros for an absent surface).
     -> device float64 ``[N,13]``."""
-    return _colour_statistics(_SURFACES, None, "paste_colour_sums_nv12", x, nv12, sim, matte, feather, value_range, out, standard=standard,
+    return _colour_statistics(_nv12_format(nv12), None, "paste_colour_sums_nv12", x, nv12, sim, matte, feather, value_range, out, standard=standard,
                               full_range=full_range)
 
 

@@ -311,7 +311,7 @@ class IRFD(nn.Module):
     @torch.no_grad()
     def live(self, identity_u8, *, size=256, template, contour=None, channel_order="rgb", identity_align=None, rate=30.0,
              track=FR.FILTER_DEFAULTS, features=None, feather=0, matte_softness=4.0, matte_grow=0.0, colour_match=False, colour_decay=0.9,
-             seed=None, noise="fresh", offset=0.0):
+             seed=None, noise="fresh", offset=0.0, pixel_format="rgb24", standard="bt601", full_range=False):
         """A reenactment session for a LIVE feed -- a camera or a call, where frame ``t + 1`` does not exist yet, or a long video
         pushed through a few frames at a time: ``reenact_video(align=LandmarkAlign(...), paste=True, ...)`` with the clip's windows
         replaced by causal filters whose state stays on the device (speak-hack_amd/live.py; csrc/causal_filter.hip).  Everything is
@@ -340,18 +340,25 @@ class IRFD(nn.Module):
         same bytes.  With ``track=None``, ``features=None``, ``colour_decay=0`` and frames that all have landmarks, a ``step`` over a
         clip is ``reenact_video(align=LandmarkAlign(landmarks, template), paste=True, matte=LandmarkMatte(contour, smooth=0, ...),
         colour_match=True, ...)`` byte for byte.  ``session.reset()`` empties the filter states and the frame counter
-        (``session.frames``); ``fi`` stays.  Packed RGB only: a session over NV12 surfaces is a follow-up.  Several feeds at once:
-        ``live_room``."""
+        (``session.frames``); ``fi`` stays.  Several feeds at once: ``live_room``.
+
+        ``pixel_format="nv12"``: the feed is NV12 as a hardware decoder leaves it, in the colour of ``standard`` ("bt601" | "bt709") /
+        ``full_range`` (``ValueError`` with ``"rgb24"``, as ``reenact_video``).  ``step`` then takes the next ``N`` surfaces as one uint8
+        tensor ``[N,3H/2,W]`` or a pair of planes (``ops.nv12_planes``), and ``emotion_u8`` in the same form and size; steps 3, 8 and 9
+        are ``ops.frames_from_nv12_aligned`` (R, G, B planes), ``ops.paste_colour_sums_nv12`` and ``ops.frames_paste_nv12_aligned`` --
+        no packed-RGB detour -- and everything else is untouched: the landmark filter never sees a pixel.  -> a packed uint8
+        ``[N,3H/2,W]`` clone with the face pasted in, or with ``inplace=True`` the input itself (whose frames must not overlap).  The
+        identity photo stays a packed photo in ``channel_order``."""
         from .live import LiveSession
         return LiveSession(self, identity_u8, size=size, template=template, contour=contour, channel_order=channel_order,
                            identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,
                            matte_softness=matte_softness, matte_grow=matte_grow, colour_match=colour_match, colour_decay=colour_decay, seed=seed,
-                           noise=noise, offset=offset)
+                           noise=noise, offset=offset, pixel_format=pixel_format, standard=standard, full_range=full_range)
 
     @torch.no_grad()
     def live_room(self, identities_u8, *, size=256, template, contour=None, channel_order="rgb", identity_align=None, rate=30.0,
                   track=FR.FILTER_DEFAULTS, features=None, feather=0, matte_softness=4.0, matte_grow=0.0, colour_match=False,
-                  colour_decay=0.9, seed=None, noise="fresh", offset=0.0):
+                  colour_decay=0.9, seed=None, noise="fresh", offset=0.0, pixel_format="rgb24", standard="bt601", full_range=False):
         """``live`` for ``S`` feeds at once -- a server with several calls -- stepped together as ONE batch per tick
         (speak-hack_amd/live.py: ``LiveRoom``).  The arguments are those of ``live``, with ``identities_u8`` a sequence of ``S`` photos
         of any sizes ([H,W,3] or [1,H,W,3] each) or a tensor ``[S,H,W,3]``; ``seed`` one integer or ``S`` of them; ``identity_align``
@@ -364,12 +371,17 @@ class IRFD(nn.Module):
         (``spk_noise_fill_rows``).  Slot ``s`` of a room is a session of its own (the networks run at batch ``S``: the same frames once
         quantised, as the chunks of ``reenact_video`` are); a feed with nothing to show in a tick is given NaN landmarks.
         ``room.reset(slot=None)`` and ``room.set_identity(slot, photo, identity_align=None)`` start a slot over without touching its
-        neighbours.  Packed RGB, one frame size for all feeds."""
+        neighbours.  The feeds' frames may also be ``S`` buffers of ``S`` sizes (``LiveRoom.step``).
+
+        ``pixel_format="nv12"`` (``standard``, ``full_range``: as ``live``): ``room.step`` takes this tick's surfaces as ``[S,3H/2,W]`` or
+        a pair of planes -- the strided NV12 launchers -- or as a list / tuple of ``S`` surfaces of ``S`` sizes or an
+        ``ops.SurfaceTable``: the three ``_nv12_sim_table`` entry points of csrc/frame_table_nv12.hip plus one upload of ``40 S`` bytes per
+        table, each feed's decoder surface read and written where it is."""
         from .live import LiveRoom
         return LiveRoom(self, identities_u8, size=size, template=template, contour=contour, channel_order=channel_order,
                         identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,
                         matte_softness=matte_softness, matte_grow=matte_grow, colour_match=colour_match, colour_decay=colour_decay, seed=seed,
-                        noise=noise, offset=offset)
+                        noise=noise, offset=offset, pixel_format=pixel_format, standard=standard, full_range=full_range)
 
     def _decode_eval(self, gin, noises, output="f32", channel_order="rgb", seeded=None, colour=("bt601", False)):
         """``Gd`` in eval arithmetic without touching module state: its inference plan called directly; a decoder the plan

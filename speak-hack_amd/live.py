@@ -3,7 +3,8 @@ through a few frames at a time.  ``IRFD.reenact_video`` takes a clip that is in 
 landmarks, the matte's contour and the colour statistics with windows over frames ``t - r ... t + r``.  A session runs ``Ei`` once,
 keeps ``fi``, and steadies the same three things with the causal filters of csrc/causal_filter.hip, whose state lives in device
 tensors on the session: ``step`` reads no device value on the host, and ``N`` frames in one ``step`` and the same frames in any split
-of steps give the same bytes.  Packed RGB only; a session over NV12 surfaces is a follow-up.
+of steps give the same bytes.  The feed is packed RGB or (``pixel_format="nv12"``) NV12 surfaces as a hardware decoder leaves them:
+the pixel format decides which launchers read and write the frames (``_Rgb24Edge`` / ``_Nv12Edge``), and nothing else.
 
 ``IRFD.live_room``: S such feeds at once -- a server with several calls -- as ONE batch per tick (``LiveRoom``): the frames of a tick
 are the batch rows of the same launches a session makes, with the state of every feed, its frame counter and its seed on the device."""
@@ -37,6 +38,68 @@ def _check_identity(what, name, identity_u8):
         raise ValueError(f"{what}: {name} must be [H,W,3] or [1,H,W,3], got {got}")
 
 
+class _Rgb24Edge:
+    """What a step asks of packed uint8 frames in ``channel_order``: a tensor ``[N,H,W,3]``, or a ``FrameTable``"""
+    surfaces, table, noun, shape = False, FR.FrameTable, "frames [H,W,3]", "[{},H,W,3]"
+    way_in, sums, paste, clone = (staticmethod(f) for f in (FR.frames_from_u8_aligned, FR.paste_colour_sums, FR.frames_paste_u8_aligned,
+                                                            FR.clone_frames))
+
+    def __init__(self, channel_order, standard, full_range):
+        self.args = dict(channel_order=channel_order)
+
+    def count(self, frames):
+        return len(frames)
+
+    def writable(self, what, frames):
+        if not FR.packed_pixels(frames):
+            raise L.SpkError(f"{what}: inplace needs packed pixels and rows / frames that do not overlap, got strides {frames.stride()}")
+
+    def present(self, table):
+        return table.frames
+
+
+class _Nv12Edge:
+    """The same of NV12 surfaces in the colour of ``standard`` / ``full_range``: a pair of planes ``(y [N,H,W], uv [N,H/2,W/2,2])`` as
+    ``ops.nv12_planes`` opened them, or a ``SurfaceTable``.  The way in makes R, G, B planes, as ``Nv12.network_input`` does."""
+    surfaces, table, noun, shape = True, FR.SurfaceTable, "NV12 surfaces", "[{},3H/2,W]"
+    way_in, sums, paste, clone = (staticmethod(f) for f in (FR.frames_from_nv12_aligned, FR.paste_colour_sums_nv12,
+                                                            FR.frames_paste_nv12_aligned, FR.clone_surfaces))
+
+    def __init__(self, channel_order, standard, full_range):
+        self.args = dict(standard=standard, full_range=full_range)
+
+    def count(self, frames):
+        return len(frames) if isinstance(frames, FR.SurfaceTable) else frames[0].size(0)
+
+    def writable(self, what, frames):
+        if isinstance(frames, FR.SurfaceTable):
+            frames.check_written()
+        else:
+            FR.nv12_strides(*frames, f"{what}: inplace", written=True)
+
+    def present(self, table):
+        return table.planes
+
+    def open(self, what, name, nv12, N=None):
+        """``[N,3H/2,W]`` or a pair of planes -> the pair, its shape and dtype checked on the host (``N``: the count it must have)"""
+        try:
+            planes = FR.nv12_planes(nv12)
+        except ValueError as e:
+            raise ValueError(f"{what}: {name}: {e}") from None
+        if N is not None and planes[0].size(0) != N:
+            raise ValueError(f"{what}: {name} must be [{N},3H/2,W] or a pair of planes, one surface per feed, got {planes[0].size(0)} surfaces")
+        return planes
+
+    def ready(self, what, name, planes, device):
+        """What the launchers would refuse of a pair of planes, asked before the first launch of a step"""
+        FR.nv12_strides(*planes, f"{what}: {name}", written=False)
+        if planes[0].device != device or planes[1].device != device:
+            raise L.SpkError(f"{what}: {name} on {planes[0].device}, the identity image on {device}")
+
+
+_EDGES = {"rgb24": _Rgb24Edge, "nv12": _Nv12Edge}
+
+
 class _Live:
     """What a session and a room share: the arguments of ``IRFD.live`` checked on the host, ``Ei`` on one photo, and the body of a
     step over a batch of frames.  The two differ in what a batch row is -- the next frame of one feed, or this tick's frame of the
@@ -44,10 +107,16 @@ class _Live:
     ``_steady_features``, ``_fi``, ``_seeded`` and ``_colour_rows``."""
 
     def _configure(self, what, model, *, size, template, contour, channel_order, rate, track, features, feather, matte_softness, matte_grow,
-                   colour_match, colour_decay, offset):
+                   colour_match, colour_decay, offset, pixel_format, standard, full_range):
         self.size = FR._out_size(size, what)
         FR._channel_swap(channel_order)
         self.channel_order = channel_order
+        if pixel_format not in _EDGES:
+            raise ValueError(f"{what}: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
+        if pixel_format == "rgb24" and (standard != "bt601" or full_range):
+            raise ValueError(f"{what}: standard / full_range apply to pixel_format='nv12' only")
+        FR.yuv_standard(standard, full_range)
+        self.pixel_format, self.edge = pixel_format, _EDGES[pixel_format](channel_order, standard, full_range)
         if template is None:
             raise ValueError(f"{what}: a template is needed: the tracked landmarks as (u, v) in the network image"
                              + (" (contour= takes its fallback outline from it)" if contour is not None else ""))
@@ -106,33 +175,46 @@ class _Live:
         return self._generated[Ws]
 
     def _check_step(self, what, frames_u8, emotion_u8, inplace):
-        """-> ``emotion_u8`` as the body takes it: beside a ``FrameTable`` of frames, a table of the same sizes per feed"""
-        if isinstance(frames_u8, FR.FrameTable):
+        """-> ``emotion_u8`` as the body takes it: beside a table of frames, a table of the same sizes per feed; beside a pair of NV12
+        planes, a pair of the same size.  With NV12 planes, what the launchers would refuse of them is asked here, before a launch."""
+        edge = self.edge
+        if isinstance(frames_u8, edge.table):
             if emotion_u8 is not None:
                 emotion_u8 = self._table(what, "emotion_u8", emotion_u8)
                 if emotion_u8.sizes != frames_u8.sizes:
                     raise ValueError(f"{what}: emotion_u8 must match the frames feed by feed: sizes {emotion_u8.sizes}, the frames' {frames_u8.sizes}")
+        elif edge.surfaces:
+            if emotion_u8 is not None:
+                emotion_u8 = edge.open(what, "emotion_u8", emotion_u8)
+                if emotion_u8[0].shape != frames_u8[0].shape:
+                    raise ValueError(f"{what}: emotion_u8 must match the surfaces: {tuple(emotion_u8[0].shape)}, the frames' {tuple(frames_u8[0].shape)}")
         elif emotion_u8 is not None and (not isinstance(emotion_u8, torch.Tensor) or tuple(emotion_u8.shape) != tuple(frames_u8.shape)):
             raise ValueError(f"{what}: emotion_u8 must match the frames {tuple(frames_u8.shape)}")
         if not isinstance(inplace, bool):
             raise ValueError(f"{what}: inplace must be a bool, got {inplace!r}")
+        if edge.surfaces and not isinstance(frames_u8, edge.table):
+            edge.ready(what, "frames", frames_u8, self.device)
+            if emotion_u8 is not None:
+                edge.ready(what, "emotion_u8", emotion_u8, self.device)
         return emotion_u8
 
     def _body(self, what, frames_u8, landmarks, weights, emotion_u8, inplace):
-        """The steps of one ``step`` over the ``N`` rows of ``frames_u8`` -- a tensor ``[N,H,W,3]``, or a ``FrameTable`` of ``N`` frames
-        (``emotion_u8``: the same form) -- after the host checks: ``landmarks`` [N,K,2] and ``weights`` as the filter (``track``) or
-        else the fit takes them"""
-        if inplace and not FR.packed_pixels(frames_u8):
-            raise L.SpkError(f"{what}: inplace needs packed pixels and rows / frames that do not overlap, got strides {frames_u8.stride()}")
-        N = len(frames_u8)
-        model, order = self.model, dict(channel_order=self.channel_order)
+        """The steps of one ``step`` over the ``N`` rows of ``frames_u8`` -- a tensor ``[N,H,W,3]`` or a ``FrameTable`` of ``N`` frames;
+        with NV12, a pair of planes or a ``SurfaceTable`` (``emotion_u8``: the same form) -- after the host checks: ``landmarks`` [N,K,2]
+        and ``weights`` as the filter (``track``) or else the fit takes them.  The ONE routine of both pixel formats: ``edge`` says
+        which launchers read and write the frames and how they are cloned."""
+        edge = self.edge
+        if inplace:
+            edge.writable(what, frames_u8)
+        N = edge.count(frames_u8)
+        model, order = self.model, edge.args
         # 1, 2: the landmarks steadied, and the rows fitted to them; a held point keeps its last weight, an expired one has none
         if self.track is not None:
             landmarks, weights = self._steady(landmarks, weights)
         rows = FR._fit(landmarks, self.template, weights, self.offset, what)
         # 3, 4: the crops, Ee and Ep
-        pose = FR.frames_from_u8_aligned(frames_u8, self.size, rows, **order)
-        emo = pose if emotion_u8 is None else FR.frames_from_u8_aligned(emotion_u8, self.size, rows, **order)
+        pose = edge.way_in(frames_u8, self.size, rows, **order)
+        emo = pose if emotion_u8 is None else edge.way_in(emotion_u8, self.size, rows, **order)
         fe, fp = model.encode(emo, "Ee"), model.encode(pose, "Ep")
         fi = self._fi(N)
         if self.features is None:
@@ -154,12 +236,12 @@ class _Live:
         if self.contour is not None:
             matte = FR._matte(landmarks, rows, Hs, Ws, self.contour, self.softness, self.grow, self.offset, fallback, *FR._check_smooth(0, None, what),
                               what)
-        out = frames_u8 if inplace else FR.clone_frames(frames_u8)
+        out = frames_u8 if inplace else edge.clone(frames_u8)
         colour = None
         if self.colour_match:                                              # the statistics read the background before the paste writes it
-            sums = FR.paste_colour_sums(y, out, rows, matte=matte, feather=self.feather, **order)
+            sums = edge.sums(y, out, rows, matte=matte, feather=self.feather, **order)
             colour = self._colour_rows(sums)
-        FR.frames_paste_u8_aligned(y, out, rows, feather=self.feather, out=out, matte=matte, colour=colour, **order)
+        edge.paste(y, out, rows, feather=self.feather, out=out, matte=matte, colour=colour, **order)
         return out
 
 
@@ -169,12 +251,14 @@ class LiveSession(_Live):
     ``feature_state``, ``colour_state``)."""
 
     def __init__(self, model, identity_u8, *, size, template, contour, channel_order, identity_align, rate, track, features, feather,
-                 matte_softness, matte_grow, colour_match, colour_decay, seed, noise, offset):
+                 matte_softness, matte_grow, colour_match, colour_decay, seed, noise, offset, pixel_format="rgb24", standard="bt601",
+                 full_range=False):
         from .irfd import _check_noise
         what = "live"
         template = self._configure(what, model, size=size, template=template, contour=contour, channel_order=channel_order, rate=rate, track=track,
                                    features=features, feather=feather, matte_softness=matte_softness, matte_grow=matte_grow,
-                                   colour_match=colour_match, colour_decay=colour_decay, offset=offset)
+                                   colour_match=colour_match, colour_decay=colour_decay, offset=offset, pixel_format=pixel_format,
+                                   standard=standard, full_range=full_range)
         _check_noise(what, noise, seed, None, 0)
         self.seed, self.fixed_noise = seed, noise == "fixed"
         _check_identity(what, "identity_u8", identity_u8)
@@ -219,21 +303,31 @@ class LiveSession(_Live):
         ``[N,K,2]`` as the tracker left them (``weights``: its confidences, in the forms of ``ops.causal_filter``), ``emotion_u8``: the
         frames ``Ee`` sees (None: ``frames_u8``; cropped with the same rows).  -> uint8 ``[N,H,W,3]``: the frames with the generated
         face pasted in (``inplace=True``: ``frames_u8`` itself, which then needs packed pixels); a frame whose landmarks give no
-        transform -- lost for longer than ``hold`` frames, or never seen -- passes through untouched."""
+        transform -- lost for longer than ``hold`` frames, or never seen -- passes through untouched.
+
+        ``pixel_format="nv12"``: ``frames_u8`` is the next ``N`` surfaces, one uint8 tensor ``[N,3H/2,W]`` or a pair of planes
+        (``ops.nv12_planes``), and ``emotion_u8`` takes the same form and size.  -> a packed clone ``[N,3H/2,W]`` with the face pasted
+        in; ``inplace=True``: the input itself, whose frames must not overlap.  What the launchers would refuse of the surfaces (a
+        device, a pixel stride, frames that overlap) is refused before the first launch: the states stay as they were."""
         what = "live.step"
-        if not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
+        given = frames_u8
+        if self.edge.surfaces:
+            frames_u8 = self.edge.open(what, "frames", frames_u8)
+            N = frames_u8[0].size(0)
+        elif not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
             got = tuple(frames_u8.shape) if isinstance(frames_u8, torch.Tensor) else type(frames_u8).__name__
             raise ValueError(f"{what}: frames must be [N,H,W,3], got {got}")
-        N = frames_u8.size(0)
+        else:
+            N = frames_u8.size(0)
         if not isinstance(landmarks, torch.Tensor) or tuple(landmarks.shape) != (N, self.K, 2):
             got = tuple(landmarks.shape) if isinstance(landmarks, torch.Tensor) else type(landmarks).__name__
             raise ValueError(f"{what}: landmarks must be [{N},{self.K},2], {self.K} points per frame as the template has, got {got}")
-        self._check_step(what, frames_u8, emotion_u8, inplace)
+        emotion_u8 = self._check_step(what, frames_u8, emotion_u8, inplace)
         if self.track is None:
             _, weights, _ = FR._check_fit(landmarks, self.template, weights, self.offset, what)
         out = self._body(what, frames_u8, landmarks, weights, emotion_u8, inplace)
         self.frames += N
-        return out
+        return given if inplace else out
 
 
 class LiveRoom(_Live):
@@ -254,15 +348,17 @@ class LiveRoom(_Live):
 
     A slot with nothing to show in a tick is given NaN landmarks: it is a session's lost frame, held up to ``hold`` ticks and then
     passed through untouched, and its counter advances as a session's does.  The feeds' frames may be one tensor or S buffers of S
-    sizes (``step``).  Out of scope: stepping a subset of the slots, several frames per feed per tick, NV12."""
+    sizes, packed RGB or NV12 surfaces (``step``).  Out of scope: stepping a subset of the slots, several frames per feed per tick."""
 
     def __init__(self, model, identities_u8, *, size, template, contour, channel_order, identity_align, rate, track, features, feather,
-                 matte_softness, matte_grow, colour_match, colour_decay, seed, noise, offset):
+                 matte_softness, matte_grow, colour_match, colour_decay, seed, noise, offset, pixel_format="rgb24", standard="bt601",
+                 full_range=False):
         from .irfd import _check_noise
         what = "live_room"
         template = self._configure(what, model, size=size, template=template, contour=contour, channel_order=channel_order, rate=rate, track=track,
                                    features=features, feather=feather, matte_softness=matte_softness, matte_grow=matte_grow,
-                                   colour_match=colour_match, colour_decay=colour_decay, offset=offset)
+                                   colour_match=colour_match, colour_decay=colour_decay, offset=offset, pixel_format=pixel_format,
+                                   standard=standard, full_range=full_range)
         if isinstance(identities_u8, torch.Tensor):
             if identities_u8.dim() != 4:
                 raise ValueError(f"{what}: identities_u8 must be a sequence of S photos [H,W,3] or a tensor [S,H,W,3], got {tuple(identities_u8.shape)}")
@@ -402,11 +498,23 @@ class LiveRoom(_Live):
         place of the strided three, plus one upload of ``24 S`` bytes per table; landmarks are in each feed's own frame coordinates.
         ``inplace=True`` writes into the caller's buffers (which must not share bytes) and returns the list; ``inplace=False`` clones
         every frame first -- ``S`` copies, the one cost of a tick that grows with ``S``, and a second table (host check and upload)
-        over the clones -- and returns a list of new tensors."""
+        over the clones -- and returns a list of new tensors.
+
+        ``pixel_format="nv12"``: ``frames_u8`` is ``[S,3H/2,W]`` or a pair of planes (``ops.nv12_planes``) -- the strided NV12
+        launchers; -> a packed clone ``[S,3H/2,W]``, or in place the input itself -- or a list / tuple of ``S`` surfaces of ``S``
+        sizes (each a ``[3H/2,W]`` tensor of any even pitch or a pair of plane views, a region of interest included) or an
+        ``ops.SurfaceTable``: the three ``_nv12_sim_table`` entry points of csrc/frame_table_nv12.hip plus one upload of ``40 S`` bytes
+        per table.  ``inplace=True`` returns the list itself (no two planes may share bytes); ``inplace=False`` makes ``S`` packed
+        clones and a second table over them, and returns a list of new tensors."""
         what = "live_room.step"
         S, K = self.S, self.K
         given = frames_u8
-        if isinstance(frames_u8, (list, tuple, FR.FrameTable)):
+        if self.edge.surfaces:
+            if isinstance(frames_u8, FR.SurfaceTable) or (isinstance(frames_u8, (list, tuple)) and not FR.plane_pair(frames_u8)):
+                frames_u8 = self._table(what, "frames", frames_u8)
+            else:
+                frames_u8 = self.edge.open(what, "frames", frames_u8, S)
+        elif isinstance(frames_u8, (list, tuple, FR.FrameTable)):
             frames_u8 = self._table(what, "frames", frames_u8)
         elif not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != S:
             got = tuple(frames_u8.shape) if isinstance(frames_u8, torch.Tensor) else type(frames_u8).__name__
@@ -423,24 +531,29 @@ class LiveRoom(_Live):
             self.frames.add_(1)
         if isinstance(out, FR.FrameTable):                                 # in place: the caller's own list, or the table's tensors
             return given if inplace and isinstance(given, list) else list(out.frames)
-        return out
+        if isinstance(out, FR.SurfaceTable):                               # the same of surfaces, as they were given
+            return given if inplace and isinstance(given, list) else list(out.surfaces)
+        return given if inplace else out
 
     def _table(self, what, name, frames):
         """This tick's frames of the ``S`` feeds in buffers of their own: a list / tuple of ``S`` tensors ``[H_s,W_s,3]``, a tensor
         ``[S,H,W,3]`` or a ``FrameTable`` -> a ``FrameTable`` of ``S`` frames on the room's device, none of them absent (a feed that
-        sits out is given NaN landmarks)"""
-        S = self.S
-        if not isinstance(frames, FR.FrameTable):
+        sits out is given NaN landmarks); with NV12, ``S`` surfaces, ``[S,3H/2,W]``, a pair of planes or a ``SurfaceTable`` -> a
+        ``SurfaceTable``"""
+        S, edge = self.S, self.edge
+        if not isinstance(frames, edge.table):
             if not isinstance(frames, (list, tuple, torch.Tensor)):
-                raise ValueError(f"{what}: {name} must be a list of {S} frames [H,W,3], a tensor [{S},H,W,3] or a FrameTable, got {type(frames).__name__}")
-            if len(frames) != S:
+                raise ValueError(f"{what}: {name} must be a list of {S} {edge.noun}, a tensor {edge.shape.format(S)} or a {edge.table.__name__}, "
+                                 f"got {type(frames).__name__}")
+            pair = edge.surfaces and FR.plane_pair(frames)                 # one pair of planes: its count is its planes'
+            if not pair and len(frames) != S:
                 raise ValueError(f"{what}: {name} must hold one frame per feed ({S}), got {len(frames)}")
-            if not isinstance(frames, torch.Tensor) and any(f is None for f in frames):
+            if not pair and not isinstance(frames, torch.Tensor) and any(f is None for f in frames):
                 raise ValueError(f"{what}: {name} must hold a frame for every feed, got None among them (give a feed that sits out NaN landmarks)")
-            frames = FR.FrameTable(frames)
+            frames = edge.table(frames)
         if len(frames) != S:
             raise ValueError(f"{what}: {name} must hold one frame per feed ({S}), got a table of {len(frames)}")
-        if any(f is None for f in frames.frames):
+        if any(f is None for f in edge.present(frames)):
             raise ValueError(f"{what}: {name} must hold a frame for every feed, got an absent one (give a feed that sits out NaN landmarks)")
         if frames.device != self.device:
             raise L.SpkError(f"{what}: {name} on {frames.device}, the room on {self.device}")

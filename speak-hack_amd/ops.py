@@ -16,7 +16,7 @@ from . import _lib as L
 # the video-frame edge lives in frames.py; ops.frames_from_u8 and the rest stay the documented API
 from .frames import (resize_tables, resize_tables_f32, feather_tables, parse_boxes, frames_from_u8, quant_range, frames_to_u8,  # noqa: F401
                      frames_paste_u8, yuv_coeffs, nv12_planes, frames_from_nv12, frames_to_nv12, frames_paste_nv12,
-                     similarity_rows, parse_sim, frames_from_u8_aligned, frames_paste_u8_aligned, FrameTable,
+                     similarity_rows, parse_sim, frames_from_u8_aligned, frames_paste_u8_aligned, FrameTable, SurfaceTable,
                      paste_colour_match, ellipse_matte, similarity_from_landmarks, smooth_similarity_rows, LandmarkAlign,
                      frames_from_nv12_aligned, frames_paste_nv12_aligned, paste_colour_match_nv12, matte_from_landmarks, LandmarkMatte,
                      paste_colour_sums, paste_colour_sums_nv12, colour_rows_from_sums, causal_filter, causal_filter_state,

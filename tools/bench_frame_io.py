@@ -70,6 +70,13 @@
     beside a ``LiveSession.step`` per feed.  Wall clock per tick, the contenders alternate, the list runs twice per round for the
     spread.  Written to profiles/live_room_table_bench.txt; the two expectations are reported, not gated.
 
+``--live-nv12``: the same tick where every feed's decoder left a 1080 x 1920 NV12 surface in an allocation of its own
+    (csrc/frame_table_nv12.hip), S in {1, 2, 4, 8}, in place: the NV12 ``LiveRoom.step`` on the list of surfaces beside (a) what a
+    server does today, NV12 -> BGR per feed, the rgb24 room on the list, BGR -> NV12 per feed, and (b) the rgb24 room on BGR frames of
+    the same pictures, the cost with no conversion at all; then 720p / 480p surfaces in one room beside an NV12 ``LiveSession.step``
+    per feed; the host cost of a 40-byte table; the bytes that differ between (t) and (a).  The method of ``--live-room-table``.
+    Written to profiles/live_nv12_bench.txt; the two expectations are reported, not gated.
+
     python tools/bench_frame_io.py [--paste | --nv12 | --align | --align-nv12 | --landmarks | --blend | --landmark-matte | --colour-smooth] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
@@ -1008,6 +1015,117 @@ def bench_live_room_table(args, lines):
     return all(v[1] and v[2] for v in verdicts)
 
 
+def bench_live_nv12(args, lines):
+    """``--live-nv12``: one TICK of a server with S calls whose hardware decoders left S NV12 surfaces of 1080 x 1920 in S separate
+    allocations, S in {1, 2, 4, 8} (the pictures, landmarks, settings and method of ``--live-room-table``), in place, three ways.
+    (t) the NV12 room on the list of surfaces: a surface table.  (a) what a server does today: ``torch_nv12_to_bgr`` per feed, the
+    rgb24 room on the list of BGR frames, ``torch_bgr_to_nv12`` per feed back into the surface.  (b) the rgb24 room on BGR frames of
+    the same pictures: the cost with no conversion at all.  The contenders alternate in one process, (t) entered twice for the
+    spread.  Then one mixed-size row, 2 x 720p + 2 x 480p, against four NV12 ``LiveSession.step`` calls; the host cost of a 40-byte
+    table; and how many bytes of a first tick differ between (t) and (a).
+    -> whether the two expectations hold at every S: (t) <= (a), and (t) within the spread of (b) plus the table's host cost."""
+    T, per, sizes = 8, 20, (1, 2, 4, 8)
+    sc = live_scene(T)
+    ops, dev, m, template, contour, lm, ident, video, common = (sc[k] for k in ("ops", "dev", "m", "template", "contour", "lm", "ident", "video", "common"))
+    size, Hf, Wf, K = (sc[k] for k in ("size", "Hf", "Wf", "K"))
+    kw = dict(common, template=template, contour=contour, features={})
+    del kw["seed"]
+    to_rgb, from_rgb = (t.float().to(dev) for t in ops.yuv_coeffs())
+    surfaces = torch.cat([torch_bgr_to_nv12(video[t:t + 1], from_rgb) for t in range(T)])        # the pictures as a decoder would hold them
+    lines.append(f"a tick of S feeds of {Hf}x{Wf} NV12 (bt601, limited range) in S separate allocations, in place, K = {K} landmarks, outline of "
+                 f"{len(contour)}, {size}^2 in and out, feather {sc['feather']}, matte, colour match and the three filters; median of {args.repeats} "
+                 f"alternating rounds of {per} ticks")
+
+    def latency(fn):                                                       # the mean wall clock of `per` ticks, each synchronised on its own
+        total = 0.0
+        for i in range(per):
+            total += wall(lambda: fn(i % T))
+        return total / per
+
+    def host_cost(make, n=200):                                            # build, check and upload of one table, per call
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            make().dev
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n
+
+    verdicts = []
+    for S in sizes:
+        show = torch.tensor([[(t + s) % T for s in range(S)] for t in range(T)], device=dev)
+        lms = lm[show].contiguous()                                        # feed s shows picture (t + s) % T in tick t
+        nv12 = [[surfaces[(t + s) % T].clone() for s in range(S)] for t in range(T)]             # per tick S allocations
+        detour = [[surfaces[(t + s) % T].clone() for s in range(S)] for t in range(T)]
+        bgr = [[video[(t + s) % T].clone() for s in range(S)] for t in range(T)]
+        rooms = {"t": m.live_room([ident] * S, seed=list(range(7, 7 + S)), pixel_format="nv12", **kw),
+                 "a": m.live_room([ident] * S, seed=list(range(7, 7 + S)), **kw), "b": m.live_room([ident] * S, seed=list(range(7, 7 + S)), **kw)}
+
+        def tick_nv12(t):
+            return rooms["t"].step(nv12[t], lms[t], inplace=True)
+
+        def tick_detour(t):
+            frames = [torch_nv12_to_bgr(s.unsqueeze(0), to_rgb)[0] for s in detour[t]]
+            rooms["a"].step(frames, lms[t], inplace=True)
+            for s, f in zip(detour[t], frames):
+                s.copy_(torch_bgr_to_nv12(f.unsqueeze(0), from_rgb)[0])
+            return detour[t]
+
+        def tick_bgr(t):
+            return rooms["b"].step(bgr[t], lms[t], inplace=True)
+
+        # the bytes of a first tick, on fresh surfaces and fresh rooms' states
+        first_t = [s.clone() for s in tick_nv12(0)]
+        first_a = [s.clone() for s in tick_detour(0)]
+        diff = (torch.stack(first_t).int() - torch.stack(first_a).int()).abs()
+        for r in rooms.values():
+            r.reset()
+        names = (f"(t) NV12 LiveRoom.step on a list of {S} surfaces", f"(a) {S} x NV12 -> BGR, rgb24 step on the list, {S} x BGR -> NV12",
+                 f"(b) rgb24 step on a list of {S} BGR frames")
+        contenders = {names[0]: tick_nv12, names[1]: tick_detour, names[2]: tick_bgr, names[0] + " (again)": tick_nv12}
+        for fn in contenders.values():
+            for t in range(args.warmup + 1):
+                fn(t)
+        times = alternate(contenders, args.repeats, latency)
+        ratio_table(lines, f"S = {S}: wall clock per tick, synchronised before and after each tick:", times, names[0], [(names[1], True), (names[2], False)])
+        med = {n: statistics.median(ts) for n, ts in times.items()}
+        ours = min(med[names[0]], med[names[0] + " (again)"])
+        spread = abs(med[names[0]] - med[names[0] + " (again)"]) / ours
+        gap = med[names[0]] / med[names[2]] - 1
+        table40 = host_cost(lambda: ops.SurfaceTable(nv12[0]))
+        table24 = host_cost(lambda: ops.FrameTable(bgr[0]))
+        verdicts.append((S, med[names[0]] <= med[names[1]], med[names[0]] - med[names[2]] <= spread * ours + table40, gap, spread))
+        lines.append(f"  spread of (t) between its two entries {spread * 100:.2f} %; (t) over (b) {gap * 100:+.2f} % "
+                     f"({(med[names[0]] - med[names[2]]) * 1e6:+.1f} us); (t) over (a) {(med[names[0]] / med[names[1]] - 1) * 100:+.2f} %")
+        lines.append(f"  host cost of a table of {S} (build, check, upload): 40-byte entries {table40 * 1e6:.1f} us, 24-byte entries {table24 * 1e6:.1f} us")
+        lines.append(f"  bytes of a first tick that differ between (t) and (a): {int((diff > 0).sum())} of {diff.numel()} (largest step {int(diff.max())})")
+    # one mixed row: 720p and 480p surfaces in one room, against an NV12 session per feed
+    S, shapes = 4, [(720, 1280), (480, 640), (720, 1280), (480, 640)]
+    scale = [torch.tensor([w / Wf, h / Hf], device=dev) for h, w in shapes]       # (x, y): the frames are resized per axis, so are the points
+    own = [[torch_bgr_to_nv12(torch.nn.functional.interpolate(video[(t + s) % T].permute(2, 0, 1)[None].float(), size=shapes[s], mode="bilinear")
+                              .permute(0, 2, 3, 1).round().to(torch.uint8).contiguous(), from_rgb)[0] for s in range(S)] for t in range(T)]
+    lms = torch.stack([torch.stack([lm[(t + s) % T] * scale[s] for s in range(S)]) for t in range(T)])      # landmarks in each feed's own pixels
+    room = m.live_room([ident] * S, seed=list(range(7, 7 + S)), pixel_format="nv12", **kw)
+    sessions = [m.live(ident, seed=7 + s, pixel_format="nv12", **kw) for s in range(S)]
+
+    def tick_mixed(t):
+        return room.step(own[t], lms[t], inplace=True)
+
+    def tick_sessions(t):
+        return [s.step(own[t][i].unsqueeze(0), lms[t, i:i + 1], inplace=True) for i, s in enumerate(sessions)]
+
+    names = ("(t) NV12 LiveRoom.step on 2 x 720p + 2 x 480p surfaces", "(s) 4 x NV12 LiveSession.step, one surface each")
+    contenders = {names[0]: tick_mixed, names[1]: tick_sessions, names[0] + " (again)": tick_mixed}
+    for fn in contenders.values():
+        for t in range(args.warmup + 1):
+            fn(t)
+    times = alternate(contenders, args.repeats, latency)
+    ratio_table(lines, "mixed sizes, S = 4: wall clock per tick, synchronised before and after each tick:", times, names[0], [(names[1], True)])
+    for S_, le_a, near_b, gap, spread in verdicts:
+        lines.append(f"S = {S_}: (t) <= (a): {'CONFIRMED' if le_a else 'REFUTED'}; (t) within the spread of (b) plus the table's host cost: "
+                     f"{'CONFIRMED' if near_b else 'REFUTED'} (gap {gap * 100:+.2f} %, spread {spread * 100:.2f} %)")
+    return all(v[1] and v[2] for v in verdicts)
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -1050,9 +1168,15 @@ def main():
                     "unless the room wins at S = 8 by more than the spread")
     ap.add_argument("--live-room-table", action="store_true", help="a tick of S live feeds in S separate allocations: LiveRoom.step on a list beside "
                     "stack + step + copies back and beside the step on one tensor; one mixed-size row")
+    ap.add_argument("--live-nv12", action="store_true", help="a tick of S live feeds of NV12 surfaces in S separate allocations: the NV12 room on the "
+                    "list beside the NV12 -> BGR -> NV12 detour around the rgb24 room and beside the rgb24 room alone; one mixed-size row")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.live_nv12:
+        lines = [f"bench_frame_io --live-nv12: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_live_nv12(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "live_nv12_bench.txt"))
     if args.live_room_table:
         lines = [f"bench_frame_io --live-room-table: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
         bench_live_room_table(args, lines)

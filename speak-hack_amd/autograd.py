@@ -664,7 +664,8 @@ def _scale_rows(t):
 class ModConvFn(torch.autograd.Function):
     """StyleGAN2 styled conv (build-defined variant; formulas reference/styleganv2.txt:1835,1912):
     y = gain * lrelu(d[b,co] * scale * conv3x3(up?(x) * s[b,ci], w) + noise_w*noise + bias), d = rsqrt(scale^2 sum_{ci,k}
-    (w s)^2 + eps) computed HERE from (w, s) (``spk_modconv_demod``; ``demodulate`` False: d = 1).
+    (w s)^2 + eps) computed HERE from (w, s) (``spk_modconv_demod``; ``demodulate`` False: d = 1).  ``slope`` None: no activation and
+    no gain.
 
     Backward, all on the HIP kernels and without a single rescaled activation in HBM:
       1. epilogue adjoint: dz = dy * lrelu' (gain folded later) + the plane sums that give d bias, d noise_w and d d;
@@ -689,7 +690,9 @@ class ModConvFn(torch.autograd.Function):
                         lrelu_slope=slope, out_scale=scale, batch_scale=s.contiguous(), demod=d, act_gain=gain)
         if _needs(ctx, grad_mode):
             ctx.save_for_backward(x, weight, s, d, y, noise, bias, noise_w)
-            ctx.conf = (scale, upsample, slope, gain, fir, packed)
+            # (``gain`` belongs to the activation -- include/spk.h: act_gain multiplies the LeakyReLU output -- so without one the
+            # forward applied none and the adjoint must not either)
+            ctx.conf = (scale, upsample, slope, gain if slope is not None else 1.0, fir, packed)
         return y
 
     @staticmethod

@@ -1212,6 +1212,92 @@ int spk_paste_colour_sums_nv12_sim_table(const float* src, int N, int Hs, int Ws
                                          int standard, int full_range, double feather, float lo, float k, const float* matte_dev,
                                          int matte_frames, double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- aligned crops on I420 surfaces: three planes, each with a base and a pitch of its own (csrc/frame_sim_i420.hip) -------------
+ * What a software decoder / encoder (libvpx, openh264, dav1d, libavcodec's yuv420p) and WebRTC's frame buffer hold.  An I420 SURFACE
+ * of H x W pixels has H and W even and >= 2 and three planes,
+ *     Y: uint8 [H][W];   U: uint8 [H / 2][W / 2];   V: uint8 [H / 2][W / 2]
+ * each with pixel stride 1, a base address of its own and a row stride of its own in bytes: y_row_stride >= W,
+ * u_row_stride >= W / 2, v_row_stride >= W / 2 (and an image stride of its own between the N surfaces of a strided call).  Chroma
+ * is sited by replication, pixel (Y, X) has sample (Y >> 1, X >> 1), and the colour maps are spk_yuv_coeffs's for standard /
+ * full_range: exactly as for NV12.  NO ALIGNMENT OR PARITY is asked of a chroma plane: an odd u_row_stride is a valid surface (a
+ * packed plane of a width with W / 2 odd has one) and so is an odd U or V base address; the kernels read and write chroma as
+ * bytes, never as 16-bit pairs.  The planes may lie in any order and in separate allocations: YV12 is the same call with the V
+ * plane first in memory.
+ *
+ * THE DEFINING PROPERTY: these are the NV12 entry points over another way to say where a surface is.  For any I420 surface and the
+ * NV12 surface with the same Y bytes and UV[cy][cx] = (U[cy][cx], V[cy][cx]), spk_frames_i420_to_f32_sim writes the fp32 bits of
+ * spk_frames_nv12_to_f32_sim, spk_paste_colour_sums_i420_sim / spk_paste_colour_match_i420_sim the 13 fp64 sums / the rows of their
+ * NV12 siblings, and spk_frames_paste_i420_sim leaves the Y, U and V bytes spk_frames_paste_nv12_sim leaves: every formula of that
+ * section holds with U[..] and V[..] read from their own planes, every fma in the same order, and the work decomposition is the
+ * same -- one thread owns a chroma block, its U byte, its V byte and the 2 x 2 luma pixels under it, in row-major order, and reads
+ * only bytes it writes, so in place is legal.  The way in loads the two chroma bytes of sample ix >> 1 when ix >> 1 changes and
+ * keeps them for the tap above the same sample; the paste does one byte load and one byte store per chroma plane and block.
+ *
+ * The arguments are those of the _nv12_sim siblings with (y, y_image_stride, y_row_stride, u, u_image_stride, u_row_stride, v,
+ * v_image_stride, v_row_stride) in place of the two NV12 planes; image strides are not read when N = 1.
+ * Refused before any launch (SPK_EINVAL, spk_last_error): what the siblings refuse, with these surface checks in place of theirs:
+ *   a null plane; N < 1; H or W odd or < 2; a Y row stride below W, a U or V row stride below W / 2; for a written surface with
+ *   N > 1 an image stride below its plane's extent (rows - 1) row_stride + width (frames that overlap), for a read one a negative
+ *   image stride.  replaces: interleaving U and V into a scratch NV12 surface per feed per tick and splitting them again. */
+int spk_frames_i420_to_f32_sim(const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, const uint8_t* u, int64_t u_image_stride,
+                               int64_t u_row_stride, const uint8_t* v, int64_t v_image_stride, int64_t v_row_stride, int N, int H, int W,
+                               const float* sim_dev, int swap_rb, int standard, int full_range, float* dst, int Hout, int Wout, float scale0,
+                               float scale1, float scale2, float shift0, float shift1, float shift2, void* stream);
+int spk_frames_paste_i420_sim(const float* src, int N, int Hs, int Ws, uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, uint8_t* u,
+                              int64_t u_image_stride, int64_t u_row_stride, uint8_t* v, int64_t v_image_stride, int64_t v_row_stride, int H, int W,
+                              const float* sim_dev, int standard, int full_range, double feather, float lo, float k, const float* matte_dev,
+                              int matte_frames, const float* colour_dev, void* stream);
+int spk_paste_colour_match_i420_sim(const float* src, int N, int Hs, int Ws, const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride,
+                                    const uint8_t* u, int64_t u_image_stride, int64_t u_row_stride, const uint8_t* v, int64_t v_image_stride,
+                                    int64_t v_row_stride, int H, int W, const float* sim_dev, int standard, int full_range, double feather, float lo,
+                                    float k, const float* matte_dev, int matte_frames, double max_gain, double min_sigma, double min_weight,
+                                    float* colour_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int spk_paste_colour_sums_i420_sim(const float* src, int N, int Hs, int Ws, const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride,
+                                   const uint8_t* u, int64_t u_image_stride, int64_t u_row_stride, const uint8_t* v, int64_t v_image_stride,
+                                   int64_t v_row_stride, int H, int W, const float* sim_dev, int standard, int full_range, double feather, float lo,
+                                   float k, const float* matte_dev, int matte_frames, double* sums_out_dev, void* workspace_dev,
+                                   size_t workspace_bytes, void* stream);
+
+/* ---- the aligned I420 edge over a planar table: every surface its own three planes, pitches and size (csrc/frame_table_i420.hip) --
+ * What the surface table is to NV12, for I420.  A PLANAR TABLE is N entries of spk_planar_ref in DEVICE memory, 8-byte aligned,
+ *     y, u, v: the first bytes of the three planes;  y_row_stride, u_row_stride, v_row_stride: bytes from row to row;
+ *     H, W: the size in luma pixels (U and V have H / 2 rows of W / 2 bytes)
+ * which the kernels read and the entry points never do.  An entry is USABLE when y, u and v are not NULL, H >= 2, W >= 2, H and W
+ * even, y_row_stride >= W, u_row_stride >= W / 2 and v_row_stride >= W / 2 -- no alignment, no parity; any other entry means THE
+ * SURFACE IS ABSENT and is treated exactly like an invalid sim row (the way in writes shift_c, the paste writes nothing, the sums
+ * are 13 zeros, the rows (1, 0)).  The kernels judge an entry with the whole predicate before they form an address from it.
+ *
+ * spk_frames_i420_to_f32_sim_table, spk_frames_paste_i420_sim_table, spk_paste_colour_sums_i420_sim_table,
+ * spk_paste_colour_match_i420_sim_table: the arguments, launches and refusals of their _nv12_sim_table siblings with a planar table
+ *   in place of the surface table.  Surface n of a table is bit for bit the strided call at N = 1 on entry n's planes, pitches and
+ *   size with row, matte and colour row n -- and so, by the defining property above, the NV12 table call on the interleaved surfaces.
+ * spk_planar_table_check: pure host code over a HOST copy of a table, what a binder calls before it uploads.  Refused, with the
+ *   offending index (or pair) in spk_last_error: a null table; N < 1; a HALF-FORMED entry (neither usable nor all zero; the message
+ *   has its fields); a plane extent (rows - 1) row_stride + width -- H rows of W bytes for Y, H / 2 rows of W / 2 bytes for U and V
+ *   -- that leaves 64 bits, or whose end address does; and, with written != 0, any two of the 3 x (usable entries) plane ranges
+ *   that share a byte, an entry's own planes against each other included.  The rule is spk_surface_table_check's RANGE rule: a
+ *   plane counts as the bytes from its first to its last, padding columns included.  So chroma halves laid side by side on one
+ *   pitch (u = base, v = base + W / 2, both with row stride W) COUNT AS OVERLAPPING when written, although no byte of one is a
+ *   byte of the other: give such surfaces to the read-only entry points only, or paste into planes that follow each other.  Ranges
+ *   that touch are apart, and written = 0 tolerates overlap. */
+typedef struct spk_planar_ref {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v; int64_t y_row_stride; int64_t u_row_stride; int64_t v_row_stride; int32_t H, W;
+} spk_planar_ref;                                                                                       /* 56 bytes: 3 x 8, 3 x 8, 4, 4 */
+int spk_planar_table_check(const spk_planar_ref* host_table, int N, int written);
+int spk_frames_i420_to_f32_sim_table(const spk_planar_ref* table_dev, int N, const float* sim_dev, int swap_rb, int standard, int full_range,
+                                     float* dst, int Hout, int Wout, float scale0, float scale1, float scale2, float shift0, float shift1,
+                                     float shift2, void* stream);
+int spk_frames_paste_i420_sim_table(const float* src, int N, int Hs, int Ws, const spk_planar_ref* table_dev, const float* sim_dev, int standard,
+                                    int full_range, double feather, float lo, float k, const float* matte_dev, int matte_frames,
+                                    const float* colour_dev, void* stream);
+int spk_paste_colour_match_i420_sim_table(const float* src, int N, int Hs, int Ws, const spk_planar_ref* table_dev, const float* sim_dev,
+                                          int standard, int full_range, double feather, float lo, float k, const float* matte_dev,
+                                          int matte_frames, double max_gain, double min_sigma, double min_weight, float* colour_out_dev,
+                                          void* workspace_dev, size_t workspace_bytes, void* stream);
+int spk_paste_colour_sums_i420_sim_table(const float* src, int N, int Hs, int Ws, const spk_planar_ref* table_dev, const float* sim_dev,
+                                         int standard, int full_range, double feather, float lo, float k, const float* matte_dev,
+                                         int matte_frames, double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- causal filters with their state on the device: what a live feed can use (csrc/causal_filter.hip) ------------------------------
  * spk_sim_smooth, the contour window of spk_matte_from_landmarks and spk_colour_rows_window look at frames t - r ... t + r: they
  * serve a clip that is in memory.  On a camera or call feed frame t + 1 does not exist yet.  These two are the causal counterparts:

@@ -134,6 +134,12 @@ class SurfaceRef(C.Structure):
                 ("W", C.c_int32)]
 
 
+class PlanarRef(C.Structure):
+    """``spk_planar_ref`` (include/spk.h): one entry of a planar table, 56 bytes."""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_row_stride", C.c_int64), ("u_row_stride", C.c_int64),
+                ("v_row_stride", C.c_int64), ("H", C.c_int32), ("W", C.c_int32)]
+
+
 # ---- launch lists (include/spk.h: spk_launch_list) ----
 OP_CONV2D, OP_FC, OP_FC_GROUPED, OP_BIAS_NOISE_STYLE, OP_TORGB, OP_DEMOD_GROUPED, OP_PIXELNORM, OP_UPSAMPLE2X = 1, 2, 3, 4, 5, 6, 7, 8
 OP_MAXPOOL3X3S2, OP_GLOBAL_AVGPOOL = 9, 10
@@ -404,6 +410,27 @@ _PROTOTYPES = {
                                                         C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                                         C.c_void_p, C.c_size_t, C.c_void_p]),
     "spk_paste_colour_sums_nv12_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                       C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_frames_i420_to_f32_sim": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] * 3 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                                                   C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_paste_i420_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p, C.c_int64, C.c_int64] * 3 +
+                                  [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
+    "spk_paste_colour_match_i420_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p, C.c_int64, C.c_int64] * 3 +
+                                        [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int,
+                                         C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_paste_colour_sums_i420_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p, C.c_int64, C.c_int64] * 3 +
+                                       [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_planar_table_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "spk_frames_i420_to_f32_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] +
+                                         [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_paste_i420_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                  C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "spk_paste_colour_match_i420_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                        C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_paste_colour_sums_i420_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
                                                        C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spk_colour_rows_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p]),

@@ -1,5 +1,5 @@
 // What the NV12 kernels of the video-frame edge share (csrc/frame_nv12.hip: boxes through host-built tables; csrc/frame_sim_nv12.hip:
-// aligned crops through a similarity transform per frame): the 3 x 4 colour maps and how a row of one is applied, the primaries of
+// aligned crops through a similarity transform per frame; csrc/frame_i420_common.hpp: the same crops on three planes): the 3 x 4 colour maps and how a row of one is applied, the primaries of
 // a standard, and the checks every surface argument gets.  Written once, so that the two files agree on every colour coefficient
 // and on the order of every operation, to the bit; each file still links alone (the host functions are inline).
 #pragma once
@@ -15,16 +15,36 @@ __device__ __forceinline__ double affine_row(const Mat34& M, int c, double p0, d
     return fma(M.m[4 * c + 2], p2, fma(M.m[4 * c + 1], p1, fma(M.m[4 * c], p0, M.m[4 * c + 3])));
 }
 
+// What one tap and one pixel of a Y, U, V surface are worth, for every layout of the three fields (interleaved chroma: Nv12Taps
+// below; three planes: I420Taps of csrc/frame_i420_common.hpp): the three fma of a tap, the matrix and the clamp behind the means,
+// the background of a region pixel.  Written once, so that the layouts agree to the bit: a layout holds which loads bring l, u, v.
+// Policy: the deriving struct, which holds to_rgb (a Mat34).
+template <class Policy>
+struct YuvTaps {
+    __device__ __forceinline__ static void add_tap(double w, unsigned l, unsigned u, unsigned v, double& a_y, double& a_u, double& a_v) {
+        a_y = fma(w, (double)l, a_y);
+        a_u = fma(w, (double)u, a_u);
+        a_v = fma(w, (double)v, a_v);
+    }
+    __device__ __forceinline__ void rgb(double y, double u, double v, double (&val)[3]) const {
+        const Mat34& to_rgb = static_cast<const Policy*>(this)->to_rgb;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) val[c] = fmin(fmax(affine_row(to_rgb, c, y, u, v), 0.0), 255.0);
+    }
+    // the pixel with the bytes (l, u, v) as R, G, B
+    __device__ __forceinline__ void background_of(unsigned l, unsigned u, unsigned v, double (&b)[3]) const { rgb((double)l, (double)u, (double)v, b); }
+};
+
 // How the bytes of a surface become the sums of the way in and the background of the statistics, for every policy that says where
 // a surface is (csrc/frame_sim_nv12.hip: planes and strides; csrc/frame_table_nv12.hip: an entry of a device table), as RgbTaps of
 // csrc/frame_sim_common.hpp is for packed bytes.  The way in: the three sums run over Y[iy][ix], U[iy >> 1][ix >> 1] and
 // V[iy >> 1][ix >> 1]; luma is byte loads, a (U, V) pair is one 16-bit load that stays in a register while ix >> 1 does not change,
 // so it serves the two taps above it; the matrix and the clamp follow the means.  The statistics: the background of a region pixel
-// is what the way in makes of that pixel, by network channel.  Policy: the deriving struct, which holds to_rgb (a Mat34).
+// is what the way in makes of that pixel, by network channel.  The arithmetic is YuvTaps'.
 struct Nv12Row { const uint8_t* y; const uint8_t* c; unsigned pair; };
 
 template <class Policy>
-struct Nv12Taps {
+struct Nv12Taps : YuvTaps<Policy> {
     using Row = Nv12Row;
     // row iy of a frame whose planes begin at y and uv
     __device__ __forceinline__ static Row open_row(const uint8_t* y, long long y_row_stride, const uint8_t* uv, long long uv_row_stride, int iy) {
@@ -32,21 +52,14 @@ struct Nv12Taps {
     }
     __device__ __forceinline__ void tap(Row& r, int ix, bool first, double w, double& a_y, double& a_u, double& a_v) const {
         if (first || !(ix & 1)) r.pair = *reinterpret_cast<const uint16_t*>(r.c + (ix & ~1));       // sample ix >> 1
-        a_y = fma(w, (double)r.y[ix], a_y);
-        a_u = fma(w, (double)(r.pair & 0xffu), a_u);
-        a_v = fma(w, (double)(r.pair >> 8), a_v);
-    }
-    __device__ __forceinline__ void rgb(double y, double u, double v, double (&val)[3]) const {
-        const Mat34& to_rgb = static_cast<const Policy*>(this)->to_rgb;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) val[c] = fmin(fmax(affine_row(to_rgb, c, y, u, v), 0.0), 255.0);
+        this->add_tap(w, r.y[ix], r.pair & 0xffu, r.pair >> 8, a_y, a_u, a_v);
     }
     // pixel (Y, X) of a frame whose planes begin at y and uv, as R, G, B
     __device__ __forceinline__ void background(const uint8_t* y, long long y_row_stride, const uint8_t* uv, long long uv_row_stride, int X, int Y,
                                                double (&b)[3]) const {
-        const double l = (double)y[(long long)Y * y_row_stride + X];
+        const unsigned l = y[(long long)Y * y_row_stride + X];
         const unsigned pair = *reinterpret_cast<const uint16_t*>(uv + (long long)(Y >> 1) * uv_row_stride + (X & ~1));
-        rgb(l, (double)(pair & 0xffu), (double)(pair >> 8), b);
+        this->background_of(l, pair & 0xffu, pair >> 8, b);
     }
 };
 

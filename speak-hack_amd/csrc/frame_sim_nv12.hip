@@ -57,8 +57,14 @@ struct Nv12Target {
     __device__ __forceinline__ uint8_t* luma(const LaunchFrame&, long long n, int X, int Y) const {
         return y + n * y_image_stride + (long long)Y * y_row_stride + X;
     }
-    __device__ __forceinline__ uint16_t* chroma(const LaunchFrame&, long long n, int CX, int CY) const {
-        return reinterpret_cast<uint16_t*>(uv + n * uv_image_stride + (long long)CY * uv_row_stride + (long long)CX * 2);
+    __device__ __forceinline__ uint8_t* chroma(long long n, int CX, int CY) const {
+        return uv + n * uv_image_stride + (long long)CY * uv_row_stride + (long long)CX * 2;
+    }
+    __device__ __forceinline__ void load_chroma(const LaunchFrame&, long long n, int CX, int CY, unsigned& u, unsigned& v) const {
+        Nv12Pair::load(chroma(n, CX, CY), u, v);
+    }
+    __device__ __forceinline__ void store_chroma(const LaunchFrame&, long long n, int CX, int CY, unsigned u, unsigned v) const {
+        Nv12Pair::store(chroma(n, CX, CY), u, v);
     }
 };
 

@@ -1,5 +1,6 @@
 // What the aligned NV12 files share (csrc/frame_sim_nv12.hip: N surfaces of one size behind two pointers and four strides;
-// csrc/frame_table_nv12.hip: every surface an entry of a device table): the way out, a kernel over a format's Target, with its
+// csrc/frame_table_nv12.hip: every surface an entry of a device table) with the three-plane files (csrc/frame_sim_i420.hip,
+// csrc/frame_table_i420.hip): the way out, a kernel over a format's Target, with its
 // launch, and the two colour maps of a standard.  Written once, so that frame n of a table is bit for bit the strided launch at
 // N = 1 on entry n: a file holds where the bytes of its surfaces are, and nothing else.
 #pragma once
@@ -9,14 +10,24 @@
 
 namespace spk::frame {
 
+struct Nv12Pair {                       // the pair of an NV12 target at p: U in the low byte
+    __device__ __forceinline__ static void load(const uint8_t* p, unsigned& u, unsigned& v) {
+        const unsigned pair = *reinterpret_cast<const uint16_t*>(p);
+        u = pair & 0xffu, v = pair >> 8;
+    }
+    __device__ __forceinline__ static void store(uint8_t* p, unsigned u, unsigned v) { *reinterpret_cast<uint16_t*>(p) = (uint16_t)(u | v << 8); }
+};
+
 // The way out.  The decomposition of frames_paste_u8_sim_kernel over CHROMA BLOCKS: blockIdx.y walks the frames, the
 // PASTE_WGS workgroups of blockIdx.x share the blocks (x_lo >> 1 ... x_hi >> 1) x (y_lo >> 1 ... y_hi >> 1) of a frame's bounding
 // box, x fastest.  A thread owns one chroma sample and the 2 x 2 luma pixels under it, as frames_paste_nv12_kernel does, and
 // visits them in row-major order; a pixel takes part when region_pixel holds it.  It reads only bytes it writes -- a luma byte per
 // region pixel, the one UV pair of a block that has a region pixel -- so the surfaces may be pasted in place.
 // Target: where the surfaces are.  out.frame(n, H, W) is surface n (csrc/frame_sim_common.hpp: its size and usable(), asked once
-// per frame); out.luma(frame, n, X, Y) is where luma byte (Y, X) lives, out.chroma(frame, n, CX, CY) where the pair of chroma
-// sample (CY, CX) does.  H and W are even, so a chroma block lies wholly inside its surface.
+// per frame); out.luma(frame, n, X, Y) is where luma byte (Y, X) lives; out.load_chroma(frame, n, CX, CY, u, v) reads the (U, V) of
+// chroma sample (CY, CX) and out.store_chroma(frame, n, CX, CY, u, v) writes it, as the layout holds it: an NV12 target with one
+// 16-bit load and one 16-bit store of the pair (Nv12Pair), a three-plane target (csrc/frame_i420_common.hpp) with a byte
+// load and a byte store per plane.  H and W are even, so a chroma block lies wholly inside its surface.
 template <class Target>
 __global__ __launch_bounds__(256) void frames_paste_nv12_sim_kernel(const float* __restrict__ src, int N, int Hs, int Ws, Target out, int H, int W,
                                                                     const float* __restrict__ sim, double feather, float lo, float k,
@@ -63,11 +74,11 @@ __global__ __launch_bounds__(256) void frames_paste_nv12_sim_kernel(const float*
                 any = true;
             }
             if (!any) continue;
-            uint16_t* pcv = out.chroma(fr, n, CX, CY);
-            const unsigned pair = *pcv;
-            const unsigned u = (unsigned)(int)rint(fmin(fmax(fma(1.0 - S, (double)(pair & 0xffu), acc_u), 0.0), 255.0));
-            const unsigned v = (unsigned)(int)rint(fmin(fmax(fma(1.0 - S, (double)(pair >> 8), acc_v), 0.0), 255.0));
-            *pcv = (uint16_t)(u | v << 8);
+            unsigned bu, bv;
+            out.load_chroma(fr, n, CX, CY, bu, bv);
+            const unsigned u = (unsigned)(int)rint(fmin(fmax(fma(1.0 - S, (double)bu, acc_u), 0.0), 255.0));
+            const unsigned v = (unsigned)(int)rint(fmin(fmax(fma(1.0 - S, (double)bv, acc_v), 0.0), 255.0));
+            out.store_chroma(fr, n, CX, CY, u, v);
         }
     }
 }

@@ -12,9 +12,6 @@
 // not usable means the surface is absent -- it is treated exactly like an invalid row.  H and W of a usable entry are even, so a
 // chroma block lies wholly inside its surface and the clamps of the shared geometry keep every load and store in bounds.
 // spk_surface_table_check is what a binder runs over its HOST copy before it uploads.
-#include <algorithm>
-#include <vector>
-
 #include "frame_sim_nv12_common.hpp"
 #include "frame_table_common.hpp"
 
@@ -60,8 +57,14 @@ struct TableSurfaceTarget {             // the paste: the surfaces of a table th
     __device__ __forceinline__ uint8_t* luma(const TableSurface& f, long long, int X, int Y) const {
         return const_cast<uint8_t*>(f.y) + (long long)Y * f.y_row_stride + X;
     }
-    __device__ __forceinline__ uint16_t* chroma(const TableSurface& f, long long, int CX, int CY) const {
-        return reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(f.uv) + (long long)CY * f.uv_row_stride + (long long)CX * 2);
+    __device__ __forceinline__ static uint8_t* chroma(const TableSurface& f, int CX, int CY) {
+        return const_cast<uint8_t*>(f.uv) + (long long)CY * f.uv_row_stride + (long long)CX * 2;
+    }
+    __device__ __forceinline__ void load_chroma(const TableSurface& f, long long, int CX, int CY, unsigned& u, unsigned& v) const {
+        Nv12Pair::load(chroma(f, CX, CY), u, v);
+    }
+    __device__ __forceinline__ void store_chroma(const TableSurface& f, long long, int CX, int CY, unsigned u, unsigned v) const {
+        Nv12Pair::store(chroma(f, CX, CY), u, v);
     }
 };
 
@@ -81,19 +84,6 @@ bool entry_usable(const spk_surface_ref& e) {
            e.uv_row_stride >= (int64_t)e.W && e.uv_row_stride % 2 == 0 && (uintptr_t)e.uv % 2 == 0;
 }
 
-// the extent in bytes of a plane of `rows` rows of W bytes, (rows - 1) stride + W; false when it, or the address behind it, leaves 64 bits
-bool plane_extent(const uint8_t* base, int rows, int64_t stride, int W, unsigned long long* extent) {
-    long long lines, bytes;
-    if (__builtin_mul_overflow((long long)(rows - 1), (long long)stride, &lines)) return false;
-    if (__builtin_add_overflow(lines, (long long)W, &bytes)) return false;
-    unsigned long long end;
-    if (__builtin_add_overflow((unsigned long long)(uintptr_t)base, (unsigned long long)bytes, &end)) return false;
-    *extent = (unsigned long long)bytes;
-    return true;
-}
-
-struct PlaneRange { uintptr_t first; unsigned long long bytes; int entry; bool chroma; };
-
 }  // namespace
 
 extern "C" {
@@ -111,8 +101,8 @@ int spk_surface_table_check(const spk_surface_ref* host_table, int N, int writte
                         "row stride %lld overflows 64 bits", who, n, e.H, e.W, (long long)e.y_row_stride);
             SPK_REQUIRE(plane_extent(e.uv, e.H / 2, e.uv_row_stride, e.W, &uv_bytes), "%s: entry %d: the UV extent (H / 2 - 1) * uv_row_stride + W of "
                         "%d x %d with row stride %lld overflows 64 bits", who, n, e.H, e.W, (long long)e.uv_row_stride);
-            planes.push_back({(uintptr_t)e.y, y_bytes, n, false});
-            planes.push_back({(uintptr_t)e.uv, uv_bytes, n, true});
+            planes.push_back({(uintptr_t)e.y, y_bytes, n, 0});
+            planes.push_back({(uintptr_t)e.uv, uv_bytes, n, 1});
             continue;
         }
         SPK_REQUIRE(e.y == nullptr && e.uv == nullptr && e.y_row_stride == 0 && e.uv_row_stride == 0 && e.H == 0 && e.W == 0,
@@ -121,19 +111,8 @@ int spk_surface_table_check(const spk_surface_ref* host_table, int N, int writte
                     (long long)e.y_row_stride, (long long)e.uv_row_stride, e.H, e.W);
     }
     if (!written) return SPK_OK;
-    // planes that are written must not share a byte: in the order of their first bytes, each must begin where the ones before it ended
-    std::sort(planes.begin(), planes.end(), [](const PlaneRange& a, const PlaneRange& b) {
-        return a.first != b.first ? a.first < b.first : a.entry != b.entry ? a.entry < b.entry : a.chroma < b.chroma;
-    });
-    for (size_t i = 1, last = 0; i < planes.size(); ++i) {               // last: the plane before i that ends furthest
-        const PlaneRange &a = planes[last], &b = planes[i];
-        const bool a_first = a.entry < b.entry || (a.entry == b.entry && !a.chroma);
-        const PlaneRange &p = a_first ? a : b, &q = a_first ? b : a;
-        SPK_REQUIRE(b.first >= a.first + a.bytes, "%s: entries %d (%s) and %d (%s) overlap: surfaces that are written must not share bytes", who,
-                    p.entry, p.chroma ? "UV" : "Y", q.entry, q.chroma ? "UV" : "Y");
-        if (b.first + b.bytes > a.first + a.bytes) last = i;
-    }
-    return SPK_OK;
+    static const char* const names[2] = {"Y", "UV"};
+    return check_planes_apart(who, planes, names);                       // csrc/frame_table_common.hpp
 }
 
 int spk_frames_nv12_to_f32_sim_table(const spk_surface_ref* table_dev, int N, const float* sim_dev, int swap_rb, int standard, int full_range,

@@ -242,7 +242,38 @@ _PACKED = _Packed()
 
 
 # ---- a frame table: every frame its own buffer and size (csrc/frame_table.hip; the definitions are in include/spk.h) ------------
-class FrameTable:
+class _DeviceTable:
+    """What the tables of this file share once their host copy ``_host`` is filled in: the host check, the one lazy upload, the
+    count, and the check that the table's frames may be written"""
+
+    def _checked(self, check, device):
+        """``check``: the entry point that judges a host table ``(table, N, written)``; ``device``: where the tensors are, None when
+        every entry is absent"""
+        self._check = check
+        L.check(getattr(L.lib(), check)(C.addressof(self._host), self.N, 0), check)
+        self._written, self._dev = False, None
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+    @property
+    def dev(self):
+        """The device table, uploaded when a launcher first asks for it: every host check of a call comes before the copy"""
+        if self._dev is None:
+            self._dev = torch.empty(C.sizeof(self._host), dtype=torch.uint8, device=self.device)
+            self._dev.copy_(torch.frombuffer(self._host, dtype=torch.uint8))
+        return self._dev
+
+    def __len__(self):
+        return self.N
+
+    def check_written(self):
+        """The table's frames are about to be written: no two of them (of a surface: no two planes) may share bytes -- the host check
+        with ``written`` -- else ``SpkError``"""
+        if not self._written:
+            L.check(getattr(L.lib(), self._check)(C.addressof(self._host), self.N, 1), self._check)
+            self._written = True
+
+
+class FrameTable(_DeviceTable):
     """``N`` packed uint8 frames that share neither an allocation nor a size, as the aligned launchers address them: a device table
     of ``spk_frame_ref`` entries ``(data, row_stride, H, W)``.  ``frames``: a sequence of device uint8 tensors ``[H_n,W_n,3]`` on one
     device, pixels packed (``stride(2) == 1``, ``stride(1) == 3``) and ``stride(0) >= 3 W_n`` -- a region-of-interest view of a wider
@@ -291,27 +322,7 @@ class FrameTable:
         for e, f in zip(self._host, frames):
             if f is not None:
                 e.data, e.row_stride, e.H, e.W = f.data_ptr(), f.stride(0), f.size(0), f.size(1)
-        L.check(L.lib().spk_frame_table_check(C.addressof(self._host), self.N, 0), "spk_frame_table_check")
-        self._written = False
-        self.device = there[0].device if there else torch.device("cuda", torch.cuda.current_device())
-        self._dev = None
-
-    @property
-    def dev(self):
-        """The device table, uploaded when a launcher first asks for it: every host check of a call comes before the copy"""
-        if self._dev is None:
-            self._dev = torch.empty(C.sizeof(self._host), dtype=torch.uint8, device=self.device)
-            self._dev.copy_(torch.frombuffer(self._host, dtype=torch.uint8))
-        return self._dev
-
-    def __len__(self):
-        return self.N
-
-    def check_written(self):
-        """The frames are about to be written: no two of them may share bytes (``spk_frame_table_check`` with ``written``), else ``SpkError``"""
-        if not self._written:
-            L.check(L.lib().spk_frame_table_check(C.addressof(self._host), self.N, 1), "spk_frame_table_check")
-            self._written = True
+        self._checked("spk_frame_table_check", there[0].device if there else None)
 
 
 class _Tabled:
@@ -1354,7 +1365,7 @@ def plane_pair(nv12) -> bool:
         nv12[1].dim() == nv12[0].dim() + 1
 
 
-class SurfaceTable:
+class SurfaceTable(_DeviceTable):
     """``N`` NV12 surfaces that share neither an allocation nor a size, as the aligned NV12 launchers address them: a device table of
     ``spk_surface_ref`` entries ``(y, uv, y_row_stride, uv_row_stride, H, W)``.  ``surfaces``: a sequence whose elements are what
     ``nv12_planes`` takes for ONE frame -- a uint8 tensor ``[3H/2, W]`` with unit pixel stride and any (even) pitch, or a pair
@@ -1416,27 +1427,7 @@ class SurfaceTable:
         for e, p in zip(self._host, planes):
             if p is not None:
                 e.y, e.uv, e.y_row_stride, e.uv_row_stride, e.H, e.W = p[0].data_ptr(), p[1].data_ptr(), p[0].stride(0), p[1].stride(0), *p[0].shape
-        L.check(L.lib().spk_surface_table_check(C.addressof(self._host), self.N, 0), "spk_surface_table_check")
-        self._written = False
-        self.device = there[0][0].device if there else torch.device("cuda", torch.cuda.current_device())
-        self._dev = None
-
-    @property
-    def dev(self):
-        """The device table, uploaded when a launcher first asks for it: every host check of a call comes before the copy"""
-        if self._dev is None:
-            self._dev = torch.empty(C.sizeof(self._host), dtype=torch.uint8, device=self.device)
-            self._dev.copy_(torch.frombuffer(self._host, dtype=torch.uint8))
-        return self._dev
-
-    def __len__(self):
-        return self.N
-
-    def check_written(self):
-        """The surfaces are about to be written: no two planes may share bytes (``spk_surface_table_check`` with ``written``), else ``SpkError``"""
-        if not self._written:
-            L.check(L.lib().spk_surface_table_check(C.addressof(self._host), self.N, 1), "spk_surface_table_check")
-            self._written = True
+        self._checked("spk_surface_table_check", there[0][0].device if there else None)
 
 
 class _TabledSurfaces(_Tabled):
@@ -1576,6 +1567,256 @@ def paste_colour_sums_nv12(x, nv12, sim, *, matte=None, feather=0, value_range=(
     be a ``SurfaceTable`` (``spk_paste_colour_sums_nv12_sim_table``; 13 zeros for an absent surface).
     -> device float64 ``[N,13]``."""
     return _colour_statistics(_nv12_format(nv12), None, "paste_colour_sums_nv12", x, nv12, sim, matte, feather, value_range, out, standard=standard,
+                              full_range=full_range)
+
+
+# ---- aligned crops on I420 surfaces: three planes (csrc/frame_sim_i420.hip, csrc/frame_table_i420.hip; include/spk.h) --------------
+def plane_triple(i420, one=True) -> bool:
+    """A triple ``(y, u, v)`` of planes and not a sequence of three surfaces (which are 2-D packed tensors ``[3H/2, W]`` or triples
+    themselves): three 3-D tensors, or -- where ONE frame may be meant (``one``) -- three 2-D ones, the last two of half the first's
+    rows and columns"""
+    if not (isinstance(i420, (tuple, list)) and len(i420) == 3 and all(isinstance(t, torch.Tensor) for t in i420)):
+        return False
+    y, u, v = i420
+    if y.dim() == u.dim() == v.dim() == 3:
+        return True
+    return one and y.dim() == u.dim() == v.dim() == 2 and tuple(u.shape) == tuple(v.shape) == (y.size(0) // 2, y.size(1) // 2)
+
+
+def i420_planes(i420):
+    """The three planes of I420 frames as views.  ``i420``: a triple ``(y [N,H,W], u [N,H/2,W/2], v [N,H/2,W/2])`` of planes that
+    live where a decoder left them, in any order in memory and with any row pitch (2-D / 2-D / 2-D for one frame); or one CONTIGUOUS
+    uint8 tensor ``[N, 3H/2, W]`` (or ``[3H/2, W]``) in packed I420 layout -- the ``H`` rows of Y, then the ``HW/4`` bytes of U, then
+    those of V (``yuv420p`` in one buffer); a non-contiguous one is refused, since the chroma bytes are not rows of the tensor.
+    ``H`` and ``W`` are even.  -> ``(y [N,H,W], u [N,H/2,W/2], v [N,H/2,W/2])``, no copy."""
+    if isinstance(i420, (tuple, list)):
+        if len(i420) != 3 or not all(isinstance(t, torch.Tensor) for t in i420):
+            raise ValueError("i420: a triple must be (y [N,H,W], u [N,H/2,W/2], v [N,H/2,W/2])")
+        y, u, v = i420
+        if y.dim() == 2 and u.dim() == 2 and v.dim() == 2:
+            y, u, v = y.unsqueeze(0), u.unsqueeze(0), v.unsqueeze(0)
+        half = (y.size(0), y.size(1) // 2, y.size(2) // 2) if y.dim() == 3 else None
+        if y.dim() != 3 or y.size(0) < 1 or y.size(1) % 2 or y.size(2) % 2 or y.size(1) < 2 or y.size(2) < 2 or tuple(u.shape) != half or \
+                tuple(v.shape) != half:
+            raise ValueError(f"i420: planes must be y [N,H,W], u [N,H/2,W/2] and v [N,H/2,W/2] with even H, W, got {tuple(y.shape)}, "
+                             f"{tuple(u.shape)} and {tuple(v.shape)}")
+        if any(t.dtype != torch.uint8 for t in (y, u, v)) or u.device != y.device or v.device != y.device:
+            raise ValueError(f"i420: planes must be uint8 tensors on one device, got {y.dtype} on {y.device}, {u.dtype} on {u.device} and "
+                             f"{v.dtype} on {v.device}")
+        return y, u, v
+    if not isinstance(i420, torch.Tensor):
+        raise ValueError("i420: expected a uint8 tensor [N,3H/2,W] or a triple of planes")
+    buf = i420.unsqueeze(0) if i420.dim() == 2 else i420
+    if buf.dim() != 3 or buf.size(0) < 1 or buf.size(1) % 3 or buf.size(1) < 3 or buf.size(2) % 2 or buf.size(2) < 2:
+        raise ValueError(f"i420: a packed surface must be [N,3H/2,W] with even H, W, got {tuple(i420.shape)}")
+    if buf.dtype != torch.uint8:
+        raise ValueError(f"i420: a packed surface must be uint8, got {buf.dtype}")
+    if not buf.is_contiguous():
+        raise ValueError(f"i420: a packed surface must be contiguous (its U and V bytes follow the Y rows), got strides {i420.stride()}; "
+                         "give planes with a pitch as a triple (y, u, v)")
+    N, W = buf.size(0), buf.size(2)
+    H = buf.size(1) // 3 * 2
+    flat, q = buf.view(N, -1), H * W // 4
+    return buf[:, :H], flat[:, H * W:H * W + q].view(N, H // 2, W // 2), flat[:, H * W + q:].view(N, H // 2, W // 2)
+
+
+def i420_strides(y, u, v, what, written):
+    """Byte strides of the three planes as the kernels take them, checked on the host: -> three ``(image_stride, row_stride)``"""
+    N, H, W = y.shape
+    if not all(t.is_cuda and t.dtype == torch.uint8 for t in (y, u, v)):
+        raise L.SpkError(f"{what}: expected uint8 HIP tensors, got {y.dtype} on {y.device} (no CPU path)")
+    if y.stride(2) != 1 or u.stride(2) != 1 or v.stride(2) != 1:
+        raise L.SpkError(f"{what}: the pixel stride of every plane must be 1, got strides {y.stride()}, {u.stride()} and {v.stride()}")
+    strides = [(t.stride(0) if N > 1 else 0, t.stride(1)) for t in (y, u, v)]
+    if strides[0][1] < W or strides[1][1] < W // 2 or strides[2][1] < W // 2:
+        raise L.SpkError(f"{what}: rows must hold W = {W} (Y) and W / 2 (U, V) bytes, got strides {y.stride()}, {u.stride()} and {v.stride()}")
+    extents = ((H - 1) * strides[0][1] + W, (H // 2 - 1) * strides[1][1] + W // 2, (H // 2 - 1) * strides[2][1] + W // 2)
+    if N > 1 and any(s[0] < 0 or (written and s[0] < e) for s, e in zip(strides, extents)):
+        raise L.SpkError(f"{what}: frames must not overlap, got strides {y.stride()}, {u.stride()} and {v.stride()}")
+    return strides
+
+
+def _planar_where(planes, strides):                                       # the nine surface arguments of a strided entry point
+    return tuple(a for t, s in zip(planes, strides) for a in (t.data_ptr(), *s))
+
+
+class _Planar(_Surfaces):
+    """``_Surfaces`` for I420: the frames of a call as what ``i420_planes`` takes (csrc/frame_sim_i420.hip); the colour arguments
+    are NV12's"""
+    way_in, paste = "spk_frames_i420_to_f32_sim", "spk_frames_paste_i420_sim"
+    sums, match = "spk_paste_colour_sums_i420_sim", "spk_paste_colour_match_i420_sim"
+
+    def shaped(self, i420, N, what):                                      # -> ((y, u, v), N, H, W)
+        planes = i420_planes(i420)
+        if N is not None and planes[0].size(0) != N:
+            raise ValueError(f"{what}: {N} generated frames, {planes[0].size(0)} I420 frames")
+        return (planes, *planes[0].shape)
+
+    def read(self, planes, what, disjoint=False):                         # always in place; -> (the Y plane, the three pointers with their strides)
+        return planes[0], _planar_where(planes, i420_strides(*planes, what, written=False))
+
+    def target(self, planes, out, N, H, W, device, what):
+        """The surface a launcher writes: ``out`` (what ``i420_planes`` takes) or a fresh packed ``[N, 3H/2, W]`` buffer; ``fill()``
+        copies each plane of ``planes`` that is not the result's own"""
+        if out is None:
+            out = torch.empty((N, 3 * H // 2, W), device=device, dtype=torch.uint8)
+        dst = i420_planes(out)
+        if tuple(dst[0].shape) != (N, H, W):
+            raise L.SpkError(f"{what}: out must hold {N} I420 frames of {H} x {W}, got planes {tuple(dst[0].shape)}")
+        where = _planar_where(dst, i420_strides(*dst, f"{what}: out", written=True))
+
+        def fill():
+            for d, s in zip(dst, planes):
+                if d.data_ptr() != s.data_ptr() or d.stride() != s.stride():
+                    d.copy_(s)
+        return out, where, fill
+
+
+_PLANAR = _Planar()
+
+
+class PlanarTable(_DeviceTable):
+    """``N`` I420 surfaces that share neither an allocation nor a size, as the aligned I420 launchers address them: a device table of
+    ``spk_planar_ref`` entries ``(y, u, v, y_row_stride, u_row_stride, v_row_stride, H, W)``.  ``surfaces``: a sequence whose elements
+    are what ``i420_planes`` takes for ONE frame -- a contiguous uint8 tensor ``[3H/2, W]`` in packed I420 layout, or a triple
+    ``(y [H,W], u [H/2,W/2], v [H/2,W/2])`` of planes that live apart, each with unit pixel stride and any pitch (odd ones and odd
+    base addresses included; V may come first in memory); a region of interest at even luma offsets of a wider surface is such a
+    triple of views -- on one device, with ``None`` for a surface that is ABSENT (an all-zero entry: the launchers treat it like an
+    invalid transform); or one packed ``[N,3H/2,W]`` tensor or one triple of planes ``(y [N,H,W], u [N,H/2,W/2], v [N,H/2,W/2])``,
+    which give views of their frames.  Wrong types, shapes or strides raise ``ValueError`` before a device is touched; CPU tensors
+    raise ``SpkError`` (no CPU path).  The host table is checked (``spk_planar_table_check``) here and uploaded ONCE, one host ->
+    device copy of ``56 N`` bytes on the current stream, when a launcher first uses the table (so a call that is refused on the host
+    has copied nothing); whether the surfaces may be written is decided where the table is used (``check_written``: the paste; the
+    rule is over byte RANGES, so chroma halves laid side by side on one pitch count as overlapping).  The table HOLDS REFERENCES to
+    the tensors, so the addresses in it stay the tensors' for as long as it lives.
+
+    ``dev``: the device table (uint8 ``[56 N]``); ``sizes``: ``(H, W)`` per surface (``(0, 0)``: absent); ``surfaces``: the elements as
+    they were given; ``planes``: ``(y [H,W], u [H/2,W/2], v [H/2,W/2])`` views per surface, or None."""
+
+    def __init__(self, surfaces):
+        what = "PlanarTable"
+        if isinstance(surfaces, torch.Tensor) or plane_triple(surfaces, one=False):
+            if isinstance(surfaces, torch.Tensor) and surfaces.dim() != 3:
+                raise ValueError(f"{what}: a tensor of surfaces must be [N,3H/2,W], got {tuple(surfaces.shape)}")
+            surfaces = list(zip(*(p.unbind(0) for p in i420_planes(surfaces))))
+        else:
+            try:
+                surfaces = list(surfaces)
+            except TypeError:
+                raise ValueError(f"{what}: surfaces must be a sequence of I420 surfaces ([3H/2,W] tensors or triples of planes), a tensor "
+                                 f"[N,3H/2,W] or a triple of planes, got {type(surfaces).__name__}") from None
+        if not surfaces:
+            raise ValueError(f"{what}: a table needs at least one surface")
+        planes = []
+        for n, s in enumerate(surfaces):
+            if s is None:
+                planes.append(None)
+                continue
+            if isinstance(s, torch.Tensor) and s.dim() != 2:
+                raise ValueError(f"{what}: surfaces[{n}] must be ONE surface, a uint8 tensor [3H/2,W] or a triple (y [H,W], u [H/2,W/2], "
+                                 f"v [H/2,W/2]), got {tuple(s.shape)}")
+            try:
+                p = i420_planes(s)
+            except ValueError as e:
+                raise ValueError(f"{what}: surfaces[{n}]: {e}") from None
+            if p[0].size(0) != 1:
+                raise ValueError(f"{what}: surfaces[{n}] must be ONE surface, got planes of {p[0].size(0)} frames")
+            y, u, v = (t[0] for t in p)
+            W = y.size(1)
+            if any(t.stride(1) != 1 for t in (y, u, v)) or y.stride(0) < W or u.stride(0) < W // 2 or v.stride(0) < W // 2:
+                raise ValueError(f"{what}: surfaces[{n}]: the pixel stride of every plane must be 1 and rows must hold W = {W} (Y) and W / 2 "
+                                 f"(U, V) bytes, got strides {y.stride()}, {u.stride()} and {v.stride()}")
+            planes.append((y, u, v))
+        there = [p for p in planes if p is not None]
+        if any(not t.is_cuda for p in there for t in p):
+            raise L.SpkError(f"{what}: expected uint8 HIP tensors, got a surface on the CPU (no CPU path)")
+        if any(p[0].device != there[0][0].device for p in there):
+            raise L.SpkError(f"{what}: the surfaces must be on one device, got {sorted({str(p[0].device) for p in there})}")
+        self.surfaces, self.planes, self.N = surfaces, planes, len(surfaces)
+        self.sizes = [(0, 0) if p is None else tuple(p[0].shape) for p in planes]
+        self._host = (L.PlanarRef * self.N)()
+        for e, p in zip(self._host, planes):
+            if p is not None:
+                e.y, e.u, e.v = (t.data_ptr() for t in p)
+                e.y_row_stride, e.u_row_stride, e.v_row_stride = (t.stride(0) for t in p)
+                e.H, e.W = p[0].shape
+        self._checked("spk_planar_table_check", there[0][0].device if there else None)
+
+
+class _TabledPlanar(_TabledSurfaces):
+    """``_Planar`` for a ``PlanarTable``, as ``_TabledSurfaces`` is ``_Surfaces`` for a ``SurfaceTable`` (csrc/frame_table_i420.hip)"""
+    noun = "planar table"
+    way_in, paste = "spk_frames_i420_to_f32_sim_table", "spk_frames_paste_i420_sim_table"
+    sums, match = "spk_paste_colour_sums_i420_sim_table", "spk_paste_colour_match_i420_sim_table"
+
+
+_TABLED_PLANAR = _TabledPlanar()
+
+
+def _i420_format(i420):
+    return _TABLED_PLANAR if isinstance(i420, PlanarTable) else _PLANAR
+
+
+def clone_planar(i420):
+    """A packed copy of the surfaces to paste into, ``clone_surfaces`` for I420: of a ``PlanarTable`` a new table over one packed
+    ``[3H/2, W]`` clone per surface (a table of its own: its host check and, at its first launch, its upload come on top of the
+    clones); else one packed ``[N, 3H/2, W]`` tensor"""
+    if isinstance(i420, PlanarTable):
+        clones = []
+        for p in i420.planes:
+            if p is None:
+                clones.append(None)
+                continue
+            out, _, fill = _PLANAR.target(tuple(t.unsqueeze(0) for t in p), None, 1, *p[0].shape, p[0].device, "clone_planar")
+            fill()
+            clones.append(out[0])
+        return PlanarTable(clones)
+    planes = i420_planes(i420)
+    out, _, fill = _PLANAR.target(planes, None, *planes[0].shape, planes[0].device, "clone_planar")
+    fill()
+    return out
+
+
+def frames_from_i420_aligned(i420, size, sim, *, channel_order="rgb", mean=0.5, std=0.5, standard="bt601", full_range=False):
+    """``frames_from_nv12_aligned`` for I420 surfaces, one launch (``spk_frames_i420_to_f32_sim``): the same footprint, weights,
+    colour maps and arguments over three planes, and the same fp32 BITS as that launcher gives on the NV12 surface with the same Y
+    bytes and ``UV[cy][cx] = (U[cy][cx], V[cy][cx])``.  ``i420``: what ``i420_planes`` takes, on the device, read in place through
+    its strides (no alignment or parity is asked of a chroma plane), or a ``PlanarTable``: surfaces of their own sizes in their own
+    buffers, still one launch (``spk_frames_i420_to_f32_sim_table``), frame ``n`` bit for bit this call on surface ``n`` alone; an
+    absent surface gives ``-mean / std``.  -> float32 [N,3,size,size]."""
+    return _from_aligned(_i420_format(i420), "frames_from_i420_aligned", i420, size, sim, channel_order, mean, std, standard=standard, full_range=full_range)
+
+
+def frames_paste_i420_aligned(x, i420, sim, *, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None, matte=None,
+                              colour=None):
+    """``frames_paste_nv12_aligned`` for I420 surfaces, one launch (``spk_frames_paste_i420_sim``): the same region, values, ``feather``,
+    ``matte`` and ``colour`` rows and the same blend, luma per pixel and chroma per 2 x 2 block, with a byte load and a byte store
+    per chroma plane; the Y, U and V bytes are those the NV12 launcher leaves on the interleaved surface.  ``i420``, ``out``: what
+    ``i420_planes`` takes (``out=i420``, the same tensor or the same triple of planes, pastes in place; ``out=None``: a packed
+    ``[N, 3H/2, W]`` clone).  -> uint8 [N, 3H/2, W], or ``out``.
+
+    ``i420`` may be a ``PlanarTable`` (``spk_frames_paste_i420_sim_table``, one launch): the paste is then IN PLACE, into the table's
+    own surfaces (``out``: None or the table), no two planes of which may share a byte range; an absent surface is left alone.
+    -> the table."""
+    return _paste_aligned(_i420_format(i420), "frames_paste_i420_aligned", x, i420, sim, feather, value_range, out, matte, colour, standard=standard,
+                          full_range=full_range)
+
+
+def paste_colour_match_i420(x, i420, sim, *, matte=None, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, max_gain=2.0,
+                            min_sigma=1.0, min_weight=16.0, out=None):
+    """``paste_colour_match_nv12`` for an I420 background, two launches (``spk_paste_colour_match_i420_sim``): the same rows, bit
+    for bit, as on the interleaved surface.  ``i420`` is only read, and may be a ``PlanarTable``
+    (``spk_paste_colour_match_i420_sim_table``; an absent surface gets ``(1, 0)``).  -> device float32 ``[N,3,2]``."""
+    what = "paste_colour_match_i420"
+    params = _check_match_params(what, max_gain, min_sigma, min_weight)
+    return _colour_statistics(_i420_format(i420), params, what, x, i420, sim, matte, feather, value_range, out, standard=standard, full_range=full_range)
+
+
+def paste_colour_sums_i420(x, i420, sim, *, matte=None, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
+    """``paste_colour_sums_nv12`` for an I420 background, two launches (``spk_paste_colour_sums_i420_sim``): the same 13 sums per
+    frame, bit for bit, so ``colour_rows_from_sums`` and the causal rows serve all three pixel formats.  ``i420`` may be a
+    ``PlanarTable`` (``spk_paste_colour_sums_i420_sim_table``; 13 zeros for an absent surface).  -> device float64 ``[N,13]``."""
+    return _colour_statistics(_i420_format(i420), None, "paste_colour_sums_i420", x, i420, sim, matte, feather, value_range, out, standard=standard,
                               full_range=full_range)
 
 

@@ -348,7 +348,13 @@ class IRFD(nn.Module):
         are ``ops.frames_from_nv12_aligned`` (R, G, B planes), ``ops.paste_colour_sums_nv12`` and ``ops.frames_paste_nv12_aligned`` --
         no packed-RGB detour -- and everything else is untouched: the landmark filter never sees a pixel.  -> a packed uint8
         ``[N,3H/2,W]`` clone with the face pasted in, or with ``inplace=True`` the input itself (whose frames must not overlap).  The
-        identity photo stays a packed photo in ``channel_order``."""
+        identity photo stays a packed photo in ``channel_order``.
+
+        ``pixel_format="i420"`` (the name is exactly that): the feed is I420 as a software decoder or a WebRTC frame buffer holds it --
+        three planes, each with a base and a pitch of its own -- in the colour of ``standard`` / ``full_range``.  ``step`` takes one
+        contiguous packed tensor ``[N,3H/2,W]`` or a triple of planes (``ops.i420_planes``); steps 3, 8 and 9 are
+        ``ops.frames_from_i420_aligned``, ``ops.paste_colour_sums_i420`` and ``ops.frames_paste_i420_aligned`` -- no interleaving into a
+        scratch NV12 surface -- and the bytes and every state are those of the NV12 session on the interleaved surfaces."""
         from .live import LiveSession
         return LiveSession(self, identity_u8, size=size, template=template, contour=contour, channel_order=channel_order,
                            identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,
@@ -376,7 +382,11 @@ class IRFD(nn.Module):
         ``pixel_format="nv12"`` (``standard``, ``full_range``: as ``live``): ``room.step`` takes this tick's surfaces as ``[S,3H/2,W]`` or
         a pair of planes -- the strided NV12 launchers -- or as a list / tuple of ``S`` surfaces of ``S`` sizes or an
         ``ops.SurfaceTable``: the three ``_nv12_sim_table`` entry points of csrc/frame_table_nv12.hip plus one upload of ``40 S`` bytes per
-        table, each feed's decoder surface read and written where it is."""
+        table, each feed's decoder surface read and written where it is.
+
+        ``pixel_format="i420"``: the same for I420 -- ``[S,3H/2,W]`` packed and contiguous or a triple of planes, or a list / tuple of
+        ``S`` surfaces of ``S`` sizes (packed tensors or triples of plane views) or an ``ops.PlanarTable``: the three ``_i420_sim_table``
+        entry points of csrc/frame_table_i420.hip plus one upload of ``56 S`` bytes per table."""
         from .live import LiveRoom
         return LiveRoom(self, identities_u8, size=size, template=template, contour=contour, channel_order=channel_order,
                         identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,

@@ -3,8 +3,9 @@ through a few frames at a time.  ``IRFD.reenact_video`` takes a clip that is in 
 landmarks, the matte's contour and the colour statistics with windows over frames ``t - r ... t + r``.  A session runs ``Ei`` once,
 keeps ``fi``, and steadies the same three things with the causal filters of csrc/causal_filter.hip, whose state lives in device
 tensors on the session: ``step`` reads no device value on the host, and ``N`` frames in one ``step`` and the same frames in any split
-of steps give the same bytes.  The feed is packed RGB or (``pixel_format="nv12"``) NV12 surfaces as a hardware decoder leaves them:
-the pixel format decides which launchers read and write the frames (``_Rgb24Edge`` / ``_Nv12Edge``), and nothing else.
+of steps give the same bytes.  The feed is packed RGB, (``pixel_format="nv12"``) NV12 surfaces as a hardware decoder leaves them or
+(``pixel_format="i420"``) the three planes of a software decoder or a WebRTC frame buffer: the pixel format decides which launchers
+read and write the frames (``_Rgb24Edge`` / ``_Nv12Edge`` / ``_I420Edge``), and nothing else.
 
 ``IRFD.live_room``: S such feeds at once -- a server with several calls -- as ONE batch per tick (``LiveRoom``): the frames of a tick
 are the batch rows of the same launches a session makes, with the state of every feed, its frame counter and its seed on the device."""
@@ -64,40 +65,57 @@ class _Nv12Edge:
     surfaces, table, noun, shape = True, FR.SurfaceTable, "NV12 surfaces", "[{},3H/2,W]"
     way_in, sums, paste, clone = (staticmethod(f) for f in (FR.frames_from_nv12_aligned, FR.paste_colour_sums_nv12,
                                                             FR.frames_paste_nv12_aligned, FR.clone_surfaces))
+    planes_of, strides_of, form = staticmethod(FR.nv12_planes), staticmethod(FR.nv12_strides), "a pair of planes"
 
     def __init__(self, channel_order, standard, full_range):
         self.args = dict(standard=standard, full_range=full_range)
 
+    def plane_tuple(self, frames, S):
+        """The planes of ``S`` surfaces as one tuple, and not a sequence of surfaces"""
+        return FR.plane_pair(frames)
+
     def count(self, frames):
-        return len(frames) if isinstance(frames, FR.SurfaceTable) else frames[0].size(0)
+        return len(frames) if isinstance(frames, self.table) else frames[0].size(0)
 
     def writable(self, what, frames):
-        if isinstance(frames, FR.SurfaceTable):
+        if isinstance(frames, self.table):
             frames.check_written()
         else:
-            FR.nv12_strides(*frames, f"{what}: inplace", written=True)
+            self.strides_of(*frames, f"{what}: inplace", written=True)
 
     def present(self, table):
         return table.planes
 
-    def open(self, what, name, nv12, N=None):
-        """``[N,3H/2,W]`` or a pair of planes -> the pair, its shape and dtype checked on the host (``N``: the count it must have)"""
+    def open(self, what, name, surfaces, N=None):
+        """``[N,3H/2,W]`` or a tuple of planes -> the planes, their shape and dtype checked on the host (``N``: the count they must have)"""
         try:
-            planes = FR.nv12_planes(nv12)
+            planes = self.planes_of(surfaces)
         except ValueError as e:
             raise ValueError(f"{what}: {name}: {e}") from None
         if N is not None and planes[0].size(0) != N:
-            raise ValueError(f"{what}: {name} must be [{N},3H/2,W] or a pair of planes, one surface per feed, got {planes[0].size(0)} surfaces")
+            raise ValueError(f"{what}: {name} must be [{N},3H/2,W] or {self.form}, one surface per feed, got {planes[0].size(0)} surfaces")
         return planes
 
     def ready(self, what, name, planes, device):
-        """What the launchers would refuse of a pair of planes, asked before the first launch of a step"""
-        FR.nv12_strides(*planes, f"{what}: {name}", written=False)
-        if planes[0].device != device or planes[1].device != device:
+        """What the launchers would refuse of a tuple of planes, asked before the first launch of a step"""
+        self.strides_of(*planes, f"{what}: {name}", written=False)
+        if any(p.device != device for p in planes):
             raise L.SpkError(f"{what}: {name} on {planes[0].device}, the identity image on {device}")
 
 
-_EDGES = {"rgb24": _Rgb24Edge, "nv12": _Nv12Edge}
+class _I420Edge(_Nv12Edge):
+    """The same of I420 surfaces: a triple of planes ``(y [N,H,W], u [N,H/2,W/2], v [N,H/2,W/2])`` as ``ops.i420_planes`` opened
+    them, or a ``PlanarTable``"""
+    table, noun = FR.PlanarTable, "I420 surfaces"
+    way_in, sums, paste, clone = (staticmethod(f) for f in (FR.frames_from_i420_aligned, FR.paste_colour_sums_i420,
+                                                            FR.frames_paste_i420_aligned, FR.clone_planar))
+    planes_of, strides_of, form = staticmethod(FR.i420_planes), staticmethod(FR.i420_strides), "a triple of planes"
+
+    def plane_tuple(self, frames, S):                                     # three 2-D planes are ONE frame: a room of one feed only
+        return FR.plane_triple(frames, one=S == 1)
+
+
+_EDGES = {"rgb24": _Rgb24Edge, "nv12": _Nv12Edge, "i420": _I420Edge}
 
 
 class _Live:
@@ -112,9 +130,9 @@ class _Live:
         FR._channel_swap(channel_order)
         self.channel_order = channel_order
         if pixel_format not in _EDGES:
-            raise ValueError(f"{what}: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
+            raise ValueError(f"{what}: pixel_format must be 'rgb24' or 'nv12' or 'i420', got {pixel_format!r}")
         if pixel_format == "rgb24" and (standard != "bt601" or full_range):
-            raise ValueError(f"{what}: standard / full_range apply to pixel_format='nv12' only")
+            raise ValueError(f"{what}: standard / full_range apply to pixel_format='nv12' only, and to 'i420'")
         FR.yuv_standard(standard, full_range)
         self.pixel_format, self.edge = pixel_format, _EDGES[pixel_format](channel_order, standard, full_range)
         if template is None:
@@ -308,7 +326,11 @@ class LiveSession(_Live):
         ``pixel_format="nv12"``: ``frames_u8`` is the next ``N`` surfaces, one uint8 tensor ``[N,3H/2,W]`` or a pair of planes
         (``ops.nv12_planes``), and ``emotion_u8`` takes the same form and size.  -> a packed clone ``[N,3H/2,W]`` with the face pasted
         in; ``inplace=True``: the input itself, whose frames must not overlap.  What the launchers would refuse of the surfaces (a
-        device, a pixel stride, frames that overlap) is refused before the first launch: the states stay as they were."""
+        device, a pixel stride, frames that overlap) is refused before the first launch: the states stay as they were.
+
+        ``pixel_format="i420"``: the same with ``ops.i420_planes`` in place of ``ops.nv12_planes`` -- one contiguous packed tensor
+        ``[N,3H/2,W]`` or a triple of planes ``(y, u, v)`` of any pitches -- and the Y, U and V bytes of the NV12 session on the
+        interleaved surfaces."""
         what = "live.step"
         given = frames_u8
         if self.edge.surfaces:
@@ -505,12 +527,19 @@ class LiveRoom(_Live):
         sizes (each a ``[3H/2,W]`` tensor of any even pitch or a pair of plane views, a region of interest included) or an
         ``ops.SurfaceTable``: the three ``_nv12_sim_table`` entry points of csrc/frame_table_nv12.hip plus one upload of ``40 S`` bytes
         per table.  ``inplace=True`` returns the list itself (no two planes may share bytes); ``inplace=False`` makes ``S`` packed
-        clones and a second table over them, and returns a list of new tensors."""
+        clones and a second table over them, and returns a list of new tensors.
+
+        ``pixel_format="i420"``: ``frames_u8`` is a contiguous packed ``[S,3H/2,W]`` tensor or a triple of planes ``(y [S,H,W],
+        u [S,H/2,W/2], v [S,H/2,W/2])`` (``ops.i420_planes``) -- the strided I420 launchers -- or a list / tuple of ``S`` surfaces of
+        ``S`` sizes (each a contiguous packed ``[3H/2,W]`` tensor or a triple of plane views of any pitch, odd ones included; a region
+        of interest at even luma offsets is such a triple) or an ``ops.PlanarTable``: the three ``_i420_sim_table`` entry points of
+        csrc/frame_table_i420.hip plus one upload of ``56 S`` bytes per table.  The returns are NV12's; the bytes and every state are
+        those of the NV12 room on the interleaved surfaces."""
         what = "live_room.step"
         S, K = self.S, self.K
         given = frames_u8
         if self.edge.surfaces:
-            if isinstance(frames_u8, FR.SurfaceTable) or (isinstance(frames_u8, (list, tuple)) and not FR.plane_pair(frames_u8)):
+            if isinstance(frames_u8, self.edge.table) or (isinstance(frames_u8, (list, tuple)) and not self.edge.plane_tuple(frames_u8, S)):
                 frames_u8 = self._table(what, "frames", frames_u8)
             else:
                 frames_u8 = self.edge.open(what, "frames", frames_u8, S)
@@ -531,7 +560,7 @@ class LiveRoom(_Live):
             self.frames.add_(1)
         if isinstance(out, FR.FrameTable):                                 # in place: the caller's own list, or the table's tensors
             return given if inplace and isinstance(given, list) else list(out.frames)
-        if isinstance(out, FR.SurfaceTable):                               # the same of surfaces, as they were given
+        if isinstance(out, (FR.SurfaceTable, FR.PlanarTable)):             # the same of surfaces, as they were given
             return given if inplace and isinstance(given, list) else list(out.surfaces)
         return given if inplace else out
 
@@ -545,7 +574,7 @@ class LiveRoom(_Live):
             if not isinstance(frames, (list, tuple, torch.Tensor)):
                 raise ValueError(f"{what}: {name} must be a list of {S} {edge.noun}, a tensor {edge.shape.format(S)} or a {edge.table.__name__}, "
                                  f"got {type(frames).__name__}")
-            pair = edge.surfaces and FR.plane_pair(frames)                 # one pair of planes: its count is its planes'
+            pair = edge.surfaces and edge.plane_tuple(frames, S)           # one tuple of planes: its count is its planes'
             if not pair and len(frames) != S:
                 raise ValueError(f"{what}: {name} must hold one frame per feed ({S}), got {len(frames)}")
             if not pair and not isinstance(frames, torch.Tensor) and any(f is None for f in frames):

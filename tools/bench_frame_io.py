@@ -77,6 +77,10 @@
     per feed; the host cost of a 40-byte table; the bytes that differ between (t) and (a).  The method of ``--live-room-table``.
     Written to profiles/live_nv12_bench.txt; the two expectations are reported, not gated.
 
+``--live-i420``: the same tick where software decoders left I420 surfaces, three planes each in an allocation of its own: the I420
+    room on a planar table, the detour it replaces (interleave into scratch NV12 surfaces, the NV12 room, split and copy back) and
+    the NV12 room alone; then the three I420 launchers beside their NV12 siblings.  Written to profiles/live_i420_bench.txt.
+
     python tools/bench_frame_io.py [--paste | --nv12 | --align | --align-nv12 | --landmarks | --blend | --landmark-matte | --colour-smooth] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
@@ -1126,6 +1130,123 @@ def bench_live_nv12(args, lines):
     return all(v[1] and v[2] for v in verdicts)
 
 
+def nv12_to_i420(surface):
+    """One NV12 surface [3H/2,W] -> the I420 surface with the same bytes in three allocations of its own: (y [H,W], u, v [H/2,W/2])"""
+    H, W = surface.size(0) // 3 * 2, surface.size(1)
+    uv = surface[H:].view(H // 2, W // 2, 2)
+    return surface[:H].clone(), uv[..., 0].contiguous(), uv[..., 1].contiguous()
+
+
+def bench_live_i420(args, lines):
+    """``--live-i420``: one TICK of a server with S calls whose software decoders left S I420 surfaces of 1080 x 1920, three planes
+    each in an allocation of its own, S in {1, 2, 4, 8} (the pictures, landmarks, settings and method of ``--live-nv12``), in place,
+    three ways.  (p) the I420 room on the list of triples: a planar table.  (d) the detour it replaces: per feed, interleave U and V
+    into a scratch NV12 surface (``torch.stack`` into the scratch UV plane, one Y copy), step the NV12 room on the list of scratch
+    surfaces, de-interleave the chroma and copy the three planes back.  (n) the NV12 room on NV12 surfaces of the same pictures: the
+    cost with no detour at all.  The contenders alternate in one process, (p) entered twice for the spread; the bytes of a first tick
+    of (p) and (d) are compared.  Then the three launchers beside their NV12 siblings at 8 x 1080 x 1920 (HIP events, the method of
+    ``--align-nv12``): byte loads of chroma against one 16-bit load of a pair.  Nothing is gated: the figures are reported."""
+    T, per, sizes = 8, 20, (1, 2, 4, 8)
+    sc = live_scene(T)
+    ops, dev, m, template, contour, lm, ident, video, common = (sc[k] for k in ("ops", "dev", "m", "template", "contour", "lm", "ident", "video", "common"))
+    size, Hf, Wf, K = (sc[k] for k in ("size", "Hf", "Wf", "K"))
+    kw = dict(common, template=template, contour=contour, features={})
+    del kw["seed"]
+    _, from_rgb = (t.float().to(dev) for t in ops.yuv_coeffs())
+    surfaces = torch.cat([torch_bgr_to_nv12(video[t:t + 1], from_rgb) for t in range(T)])        # the pictures as a decoder would hold them
+    lines.append(f"a tick of S feeds of {Hf}x{Wf} I420 (bt601, limited range), every plane an allocation of its own, in place, K = {K} landmarks, "
+                 f"outline of {len(contour)}, {size}^2 in and out, feather {sc['feather']}, matte, colour match and the three filters; median of "
+                 f"{args.repeats} alternating rounds of {per} ticks after {args.warmup + 1} warm-up ticks per contender")
+
+    def latency(fn):                                                       # the mean wall clock of `per` ticks, each synchronised on its own
+        total = 0.0
+        for i in range(per):
+            total += wall(lambda: fn(i % T))
+        return total / per
+
+    def host_cost(make, n=200):                                            # build, check and upload of one table, per call
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            make().dev
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n
+
+    for S in sizes:
+        show = torch.tensor([[(t + s) % T for s in range(S)] for t in range(T)], device=dev)
+        lms = lm[show].contiguous()                                        # feed s shows picture (t + s) % T in tick t
+        planar = [[nv12_to_i420(surfaces[(t + s) % T]) for s in range(S)] for t in range(T)]      # per tick 3 S allocations
+        detour = [[nv12_to_i420(surfaces[(t + s) % T]) for s in range(S)] for t in range(T)]
+        nv12 = [[surfaces[(t + s) % T].clone() for s in range(S)] for t in range(T)]
+        scratch = [torch.empty_like(surfaces[0]) for _ in range(S)]        # the detour's NV12 surfaces, allocated once
+        seeds = list(range(7, 7 + S))
+        rooms = {"p": m.live_room([ident] * S, seed=seeds, pixel_format="i420", **kw), "d": m.live_room([ident] * S, seed=seeds, pixel_format="nv12", **kw),
+                 "n": m.live_room([ident] * S, seed=seeds, pixel_format="nv12", **kw)}
+
+        def tick_i420(t):
+            return rooms["p"].step(planar[t], lms[t], inplace=True)
+
+        def tick_detour(t):
+            for (y, u, v), s in zip(detour[t], scratch):
+                s[:Hf].copy_(y)
+                torch.stack([u, v], -1, out=s[Hf:].view(Hf // 2, Wf // 2, 2))
+            rooms["d"].step(scratch, lms[t], inplace=True)
+            for (y, u, v), s in zip(detour[t], scratch):
+                uv = s[Hf:].view(Hf // 2, Wf // 2, 2)
+                y.copy_(s[:Hf]), u.copy_(uv[..., 0]), v.copy_(uv[..., 1])
+            return detour[t]
+
+        def tick_nv12(t):
+            return rooms["n"].step(nv12[t], lms[t], inplace=True)
+
+        # the bytes of a first tick, on fresh surfaces and fresh rooms' states
+        first_p = [torch.cat([p.flatten() for p in s]) for s in tick_i420(0)]
+        first_d = [torch.cat([p.flatten() for p in s]) for s in tick_detour(0)]
+        differ = sum(int((a != b).sum()) for a, b in zip(first_p, first_d))
+        for r in rooms.values():
+            r.reset()
+        names = (f"(p) I420 LiveRoom.step on a list of {S} triples", f"(d) {S} x interleave, NV12 step on the scratch list, {S} x split and copy back",
+                 f"(n) NV12 step on a list of {S} NV12 surfaces")
+        contenders = {names[0]: tick_i420, names[1]: tick_detour, names[2]: tick_nv12, names[0] + " (again)": tick_i420}
+        for fn in contenders.values():
+            for t in range(args.warmup + 1):
+                fn(t)
+        times = alternate(contenders, args.repeats, latency)
+        ratio_table(lines, f"S = {S}: wall clock per tick, synchronised before and after each tick:", times, names[0], [(names[1], True), (names[2], False)])
+        table56 = host_cost(lambda: ops.PlanarTable(planar[0]))
+        table40 = host_cost(lambda: ops.SurfaceTable(nv12[0]))
+        lines.append(f"  host cost of a table of {S} (build, check, upload): 56-byte entries {table56 * 1e6:.1f} us, 40-byte entries {table40 * 1e6:.1f} us")
+        lines.append(f"  bytes of a first tick that differ between (p) and (d): {differ} of {sum(a.numel() for a in first_p)}")
+
+    # ---- the three launchers beside their NV12 siblings ----
+    chunk, side, feather = args.chunk, 400, 16
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(chunk)]
+    rows = ops.similarity_rows([(y + side / 2, x + side / 2) for y, x in boxes], float(side), [0.3 * math.sin(0.9 * t) for t in range(chunk)], size).to(dev)
+    surf = torch_bgr_to_nv12(torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev), from_rgb)
+    y, uv = ops.nv12_planes(surf)
+    planes = (y.contiguous(), uv[..., 0].contiguous(), uv[..., 1].contiguous())
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    matte = ops.ellipse_matte((size, size), device=dev)
+    stat = dict(matte=matte, feather=feather)
+    shape = f"{chunk} x {Hf}x{Wf}, {size}^2, s = {side}/{size}, angles within +-0.3 rad"
+    how = f"HIP events, launcher included, median of {args.repeats} alternating rounds of 20 after 3 warm-up calls"
+    same = torch.equal(ops.frames_from_i420_aligned(planes, size, rows), ops.frames_from_nv12_aligned(surf, size, rows))
+    sums_p, sums_n = ops.paste_colour_sums_i420(x, planes, rows, **stat), ops.paste_colour_sums_nv12(x, surf, rows, **stat)
+    same_sums = torch.equal(sums_p, sums_n)
+    colour = ops.paste_colour_match_nv12(x, surf, rows, **stat)
+    pairs = (("way in", "frames_from_i420_aligned", lambda: ops.frames_from_i420_aligned(planes, size, rows), "frames_from_nv12_aligned",
+              lambda: ops.frames_from_nv12_aligned(surf, size, rows), f"the same bits: {same}"),
+             ("statistics", "paste_colour_sums_i420", lambda: ops.paste_colour_sums_i420(x, planes, rows, out=sums_p, **stat), "paste_colour_sums_nv12",
+              lambda: ops.paste_colour_sums_nv12(x, surf, rows, out=sums_n, **stat), f"ellipse matte, feather {feather}; the same sums: {same_sums}"),
+             ("way out", "frames_paste_i420_aligned(matte, colour)", lambda: ops.frames_paste_i420_aligned(x, planes, rows, colour=colour, out=planes, **stat),
+              "frames_paste_nv12_aligned(matte, colour)", lambda: ops.frames_paste_nv12_aligned(x, surf, rows, colour=colour, out=surf, **stat),
+              f"ellipse matte, colour rows, feather {feather}, in place"))
+    for title, name, ours, sibling, theirs, note in pairs:
+        contenders = {name: ours, sibling: theirs, name + " (again)": ours}
+        ratio_table(lines, f"{title}: {shape}; {note}; {how}", alternate(contenders, args.repeats, device_time), name, [(sibling, False)])
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -1170,9 +1291,15 @@ def main():
                     "stack + step + copies back and beside the step on one tensor; one mixed-size row")
     ap.add_argument("--live-nv12", action="store_true", help="a tick of S live feeds of NV12 surfaces in S separate allocations: the NV12 room on the "
                     "list beside the NV12 -> BGR -> NV12 detour around the rgb24 room and beside the rgb24 room alone; one mixed-size row")
+    ap.add_argument("--live-i420", action="store_true", help="a tick of S live feeds of I420 surfaces, every plane an allocation of its own: the I420 room "
+                    "on the list beside interleave + NV12 room + split and beside the NV12 room alone; the three launchers beside their NV12 siblings")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.live_i420:
+        lines = [f"bench_frame_io --live-i420: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_live_i420(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "live_i420_bench.txt"))
     if args.live_nv12:
         lines = [f"bench_frame_io --live-nv12: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
         bench_live_nv12(args, lines)

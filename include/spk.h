@@ -295,6 +295,26 @@ int spk_conv2d_wino_up_supported(int B, int Cin, int Cout, int H, int W);
 int spk_conv2d_wino_ksplit(int want, int B, int Cin, int Cout, int H, int W);
 int64_t spk_conv2d_wino_workspace_bytes(int ksplit, int B, int Cin, int Cout, int H, int W);
 int spk_conv2d_wino_fwd(const spk_conv2d_desc* desc, void* stream);
+/* The form spk_conv2d_wino_fwd(desc) would take on a device of `n_cu` compute units, beside spk_conv2d_gemm_form and under the same
+ * contract: the planner the launch runs states it (every requirement, the kernel instantiation, the split, the grid), nothing is
+ * launched, no device is touched and pointers are read for their alignment only (a sliced launch still needs workspace /
+ * workspace_bytes to be set).  Descriptors without SPK_CONV_WINOGRAD are refused.
+ *   shape: the region shape -- 0 WIDE (32 x 8 output pixels), 1 SQUARE (16 x 16)
+ *   mod / rgb / up: the modulated kernel (SPK_CONV_IN_BATCH_SCALE) / the fused toRGB (SPK_EPI_TORGB) / the bilinear x2 input transform
+ *   epi: the epilogue's channel rows -- 0 GENERIC, 1 LEAN, 2 LEAN_NOSTORE (a toRGB launch with y == NULL)
+ *   n_chunks: 8-channel chunks of the whole contraction; ksplit: its slices; chunks_per_slice: chunks of one slice (even)
+ *   groups; co_tiles: groups x 64-channel tiles (gridDim.y); items: work items, (region, slice) pairs of all images
+ *   grid_x: persistent workgroups per channel tile (gridDim.x, a multiple of 8); walk_min / walk_max: items the least / the most
+ *         loaded of them walks (item list dealt in 8 contiguous shares, one per XCD; 0: a workgroup without an item)
+ *   finisher / finisher_seg: as in spk_conv2d_form; lds_bytes: dynamic LDS of the launch */
+typedef struct spk_wino_form {
+    int32_t shape, mod, rgb, up, epi;
+    int32_t n_chunks, ksplit, chunks_per_slice, groups, co_tiles, items;
+    int32_t grid_x, walk_min, walk_max;
+    int32_t finisher, finisher_seg;
+    int64_t lds_bytes;
+} spk_wino_form;
+int spk_conv2d_wino_form(const spk_conv2d_desc* desc, int n_cu, spk_wino_form* out);
 
 /* ---- backward of the convolution ---------------------------------------------------------------------
  * Data gradient: spk_conv2d_fwd itself on the output gradient with weights packed transpose_flip = 1

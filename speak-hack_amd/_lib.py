@@ -53,7 +53,15 @@ class GemmForm(C.Structure):
                                          "last_tile_rows", "reserved")] + [("lds_bytes", C.c_int64)]
 
 
-GEMM_BUILDS = ("plain", "affine")                   # spk_gemm_form.build of configs 12, 14, 15
+class WinoForm(C.Structure):
+    """Mirror of spk_wino_form (include/spk.h): what ``spk_conv2d_wino_form`` answers."""
+    _fields_ = [(n, C.c_int32) for n in ("shape", "mod", "rgb", "up", "epi", "n_chunks", "ksplit", "chunks_per_slice", "groups", "co_tiles",
+                                         "items", "grid_x", "walk_min", "walk_max", "finisher", "finisher_seg")] + [("lds_bytes", C.c_int64)]
+
+
+WINO_SHAPES = ("wide", "square")                    # spk_wino_form.shape
+WINO_EPILOGUES = ("generic", "lean", "lean_nostore")    # spk_wino_form.epi
+GEMM_BUILDS = ("plain", "affine")                 # spk_gemm_form.build of configs 12, 14, 15
 STEM_BUILDS = ("plain", "stats", "epi")             # ... of config 16
 
 
@@ -340,6 +348,7 @@ _PROTOTYPES = {
     "spk_conv2d_wino_ksplit": (C.c_int, [C.c_int] * 6),
     "spk_conv2d_wino_workspace_bytes": (C.c_int64, [C.c_int] * 6),
     "spk_conv2d_wino_fwd": (C.c_int, [C.POINTER(Conv2dDesc), C.c_void_p]),
+    "spk_conv2d_wino_form": (C.c_int, [C.POINTER(Conv2dDesc), C.c_int, C.POINTER(WinoForm)]),
     "spk_conv2d_stats_slots": (C.c_int, [C.c_int] * 9),
     "spk_bn_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                   C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

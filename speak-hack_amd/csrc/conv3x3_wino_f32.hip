@@ -1005,6 +1005,12 @@ static const void* wino_kernel_of(const WinoKernel& k) {
     return reinterpret_cast<const void*>(kern);
 }
 
+// gridDim.x of a launch, for the launch and for spk_conv2d_wino_form: persistent workgroups, one per CU over all channel tiles, a
+// multiple of 8 per channel tile (the XCD shares), at most one per item
+static long long wino_grid_x(int n_cu, int co_tiles, long long items) {
+    return std::min(std::max(8ll, ((long long)n_cu / co_tiles) / 8 * 8), (items + 7) / 8 * 8);
+}
+
 int spkconv::plan_wino(const spk_conv2d_desc* d, SlicedPlan& p) {
     Args a;
     WinoKernel k;
@@ -1023,7 +1029,6 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
     const void* kern = wino_kernel_of(k);
     rc = spk::raise_dynamic_lds(kern, LDS_BYTES);
     if (rc != SPK_OK) return rc;
-    // persistent: one workgroup per CU over all channel tiles, a multiple of 8 per channel tile (the XCD shares), at most one per item
     static int n_cu = 0;
     if (n_cu == 0) {
         int dev = 0;
@@ -1031,15 +1036,43 @@ int spk_conv2d_wino_fwd(const spk_conv2d_desc* d, void* stream) {
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return spk::fail(SPK_ELAUNCH, "conv2d winograd: no device properties");
         n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    long long gx = std::max(8ll, ((long long)n_cu / k.co_tiles) / 8 * 8);
+    long long gx = wino_grid_x(n_cu, k.co_tiles, k.n_items);
     static int lab_mult = -1;       // LAB: SPK_WINO_WGS = workgroups per CU slot (0: one workgroup per item)
     if (lab_mult < 0) { const char* e = getenv("SPK_WINO_WGS"); lab_mult = e ? atoi(e) : 1; }
-    gx = lab_mult == 0 ? (k.n_items + 7) / 8 * 8 : gx * lab_mult;
-    gx = std::min(gx, (k.n_items + 7) / 8 * 8);
+    if (lab_mult != 1) {
+        const long long every = (k.n_items + 7) / 8 * 8;
+        gx = lab_mult == 0 ? every : std::min(wino_grid_x(n_cu, k.co_tiles, 1ll << 40) * lab_mult, every);
+    }
     void* argv[1] = {&a};
     (void)hipLaunchKernel(kern, dim3((unsigned)gx, (unsigned)k.co_tiles), dim3(NT), argv, LDS_BYTES, (hipStream_t)stream);
     rc = spk::check_launch("wino_kernel");
     return rc != SPK_OK ? rc : spkconv::launch_finish(p.finish, (hipStream_t)stream);
+}
+
+int spk_conv2d_wino_form(const spk_conv2d_desc* d, int n_cu, spk_wino_form* out) {
+    SPK_REQUIRE(d && out && n_cu > 0, "conv2d winograd form: null pointer or no CUs");
+    SPK_REQUIRE(d->flags & SPK_CONV_WINOGRAD, "conv2d winograd form: serves SPK_CONV_WINOGRAD descriptors only");
+    *out = spk_wino_form{};
+    spkconv::SlicedPlan p;
+    Args a;
+    WinoKernel k;
+    const int rc = plan_args(d, p, a, k);
+    if (rc != SPK_OK) return rc;
+    out->shape = k.shape; out->mod = k.mod; out->rgb = k.rgb; out->up = k.up; out->epi = k.epi_form;
+    out->n_chunks = a.n_chunks; out->ksplit = a.ksplit; out->chunks_per_slice = a.cps; out->groups = a.G;
+    out->co_tiles = k.co_tiles; out->items = (int32_t)k.n_items;
+    const long long gx = wino_grid_x(n_cu, k.co_tiles, k.n_items);
+    out->grid_x = (int32_t)gx;
+    // the kernel's dealing: XCD share x of the item list has items / 8 (+ 1 for x < items % 8) items, its gx / 8 workgroups take
+    // every (gx / 8)-th of them: the first of the largest share walks the most, the last of the smallest share the fewest
+    const long long wpx = gx >> 3, share_q = k.n_items >> 3, share_r = k.n_items & 7;
+    out->walk_max = (int32_t)((share_q + (share_r ? 1 : 0) + wpx - 1) / wpx);
+    out->walk_min = (int32_t)(share_q / wpx);
+    int seg = 0;
+    out->finisher = a.ksplit > 1 ? spkconv::splitk_finisher(p.finish.args, p.finish.ws, &seg) : 0;
+    out->finisher_seg = seg;
+    out->lds_bytes = LDS_BYTES;
+    return SPK_OK;
 }
 
 }  // extern "C"

@@ -147,6 +147,22 @@ def conv_launch_form(*args, workspace_ptr=256, **kw):
     return desc_launch_form(d, ws_bytes, workspace_ptr)
 
 
+def desc_wino_form(desc, n_cu, ws_bytes=0, workspace_ptr=256):
+    """The form ``spk_conv2d_wino_fwd(desc)`` would take on a device of ``n_cu`` compute units, as a dict of the ``spk_wino_form``
+    fields (``spk_conv2d_wino_form``: the launch's own planner, nothing is launched); the workspace as in ``desc_launch_form``."""
+    if ws_bytes > 0 and not desc.workspace:
+        desc.workspace, desc.workspace_bytes = workspace_ptr, ws_bytes
+    form = L.WinoForm()
+    L.check(L.lib().spk_conv2d_wino_form(C.byref(desc), int(n_cu), C.byref(form)), "spk_conv2d_wino_form")
+    return {name: getattr(form, name) for name, _ in L.WinoForm._fields_}
+
+
+def wino_launch_form(*args, n_cu, workspace_ptr=256, **kw):
+    """``desc_wino_form`` of the descriptor ``conv_desc(*args, flags=SPK_CONV_WINOGRAD, **kw)`` assembles."""
+    d, ws_bytes = conv_desc(*args, flags=L.CONV_WINOGRAD, **kw)
+    return desc_wino_form(d, n_cu, ws_bytes, workspace_ptr)
+
+
 # --------------------------------------------------------------------------------------------------
 class PackedConvWeight:
     """The packed images of a [Cout,Cin,k,k] weight (``pack_image``: a tile config of the MFMA conv kernel, "wino" or "bf16x3"),

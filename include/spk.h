@@ -1278,6 +1278,45 @@ int spk_paste_colour_sums_i420_sim(const float* src, int N, int Hs, int Ws, cons
                                    float k, const float* matte_dev, int matte_frames, double* sums_out_dev, void* workspace_dev,
                                    size_t workspace_bytes, void* stream);
 
+/* ---- the axis-aligned video-frame edge on I420 surfaces (csrc/frame_i420.hip) ----------------------------------------------------
+ * The box edge of "the video-frame edge in NV12 form" for the I420 surfaces defined above: crop boxes through host-built resize
+ * tables, origins by value or per frame from a device array, the feathered paste and the whole-frame conversion, for a clip a
+ * software decoder left in three planes.  Surfaces, siting and colour are exactly those of the section above: no alignment, parity
+ * or order in memory is asked of a chroma plane (an odd pitch, an odd base address and V before U are valid), and chroma is read
+ * and written as bytes, never as 16-bit pairs.
+ *
+ * THE DEFINING PROPERTY.  Take an I420 surface and the NV12 surface with the same Y bytes and UV[cy][cx] = (U[cy][cx], V[cy][cx]).
+ * Then spk_frames_i420_to_f32 writes the fp32 bits spk_frames_nv12_to_f32 writes, and spk_frames_paste_i420 and
+ * spk_frames_f32_to_i420 leave the Y, U and V bytes spk_frames_paste_nv12 and spk_frames_f32_to_nv12 leave -- for every box, origin
+ * form, feather, value range and colour setting.  Every formula of the NV12 section holds with U[..] and V[..] read from their own
+ * planes: the kernels are the same templates (csrc/frame_nv12_axis_common.hpp), instantiated over where the chroma bytes are.
+ *   The way in, per chroma row: one byte load from U and one from V at X >> 1 when the sample changes; the two values stay in
+ *   registers for the tap above the same sample (NV12: one 16-bit load of the pair at X & ~1).
+ *   The way out: a thread owns a chroma block, reads and writes one byte in each of U and V and the block's luma bytes in the box
+ *   (NV12: a 16-bit read-modify-write of the pair).  It reads no byte that it does not write, so the planes may be pasted in place.
+ *
+ * The arguments are those of the NV12 siblings with (u, u_image_stride, u_row_stride, v, v_image_stride, v_row_stride) where they
+ * have (uv, uv_image_stride, uv_row_stride); image strides are not read when N = 1.
+ * Refused before any launch (SPK_EINVAL, spk_last_error): what the NV12 siblings refuse, with the I420 surface checks of the
+ *   section above in place of theirs (a null plane; N < 1; H or W odd or < 2; a Y row stride below W, a U or V row stride below
+ *   W / 2; written surfaces with N > 1 whose image stride is below the plane's extent, in 64-bit arithmetic; read ones with a
+ *   negative image stride).  replaces: interleaving U and V into scratch NV12 surfaces per chunk, the NV12 route, and splitting the
+ *   result back -- two extra passes, neither of which can run in place into the decoder's planes. */
+int spk_frames_i420_to_f32(const uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, const uint8_t* u, int64_t u_image_stride,
+                           int64_t u_row_stride, const uint8_t* v, int64_t v_image_stride, int64_t v_row_stride, int N, int H, int W,
+                           const int32_t* boxes_yx, int y0, int x0, int Hin, int Win, int swap_rb, int standard, int full_range,
+                           const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y, const int32_t* first_x,
+                           const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout, float scale0, float scale1,
+                           float scale2, float shift0, float shift1, float shift2, void* stream);
+int spk_frames_f32_to_i420(const float* src, int N, int H, int W, uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, uint8_t* u,
+                           int64_t u_image_stride, int64_t u_row_stride, uint8_t* v, int64_t v_image_stride, int64_t v_row_stride, int standard,
+                           int full_range, float lo, float k, void* stream);
+int spk_frames_paste_i420(const float* src, int N, int Hs, int Ws, uint8_t* y, int64_t y_image_stride, int64_t y_row_stride, uint8_t* u,
+                          int64_t u_image_stride, int64_t u_row_stride, uint8_t* v, int64_t v_image_stride, int64_t v_row_stride, int H, int W,
+                          int h, int w, int y0, int x0, const int32_t* boxes_yx, int standard, int full_range, const int32_t* first_y,
+                          const int32_t* count_y, const float* w_y, int taps_y, const int32_t* first_x, const int32_t* count_x, const float* w_x,
+                          int taps_x, const float* a_y, const float* a_x, float lo, float k, void* stream);
+
 /* ---- the aligned I420 edge over a planar table: every surface its own three planes, pitches and size (csrc/frame_table_i420.hip) --
  * What the surface table is to NV12, for I420.  A PLANAR TABLE is N entries of spk_planar_ref in DEVICE memory, 8-byte aligned,
  *     y, u, v: the first bytes of the three planes;  y_row_stride, u_row_stride, v_row_stride: bytes from row to row;
@@ -1498,6 +1537,14 @@ typedef struct spk_frames_to_nv12_args {
 /* kind 14.  desc: spk_noise_fill_rows_args -> spk_noise_fill_rows (the first op of a rows-seeded decoder plan: the two table
  * pointers are patched per run, as the seed and frame0 of a seeded plan are). */
 enum { SPK_OP_NOISE_FILL_ROWS = SPK_OP_FRAMES_TO_NV12 + 1 };
+/* kind 15.  desc: spk_frames_to_i420_args -> spk_frames_f32_to_i420 (a decoder plan that ends in I420 surfaces: x [N,3,H,W] fp32,
+ * the Y, U and V planes by pointer and byte strides). */
+enum { SPK_OP_FRAMES_TO_I420 = SPK_OP_NOISE_FILL_ROWS + 1 };
+typedef struct spk_frames_to_i420_args {
+    const float* x; uint8_t* y; uint8_t* u; uint8_t* v;
+    int64_t y_image_stride, y_row_stride, u_image_stride, u_row_stride, v_image_stride, v_row_stride;
+    int32_t N, H, W, standard, full_range; float lo, k; int32_t reserved;
+} spk_frames_to_i420_args;
 int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask, void* stream);
 
 #ifdef __cplusplus

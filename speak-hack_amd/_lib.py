@@ -155,6 +155,7 @@ OP_FRAMES_TO_U8 = 11
 OP_NOISE_FILL = 12
 OP_FRAMES_TO_NV12 = 13
 OP_NOISE_FILL_ROWS = 14
+OP_FRAMES_TO_I420 = 15
 ALL_OPS = 0xFFFFFFFF
 
 NOISE_MAX_LAYERS = 16
@@ -227,6 +228,14 @@ class FramesToNv12Args(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("uv", C.c_void_p), ("y_image_stride", C.c_int64), ("y_row_stride", C.c_int64),
                 ("uv_image_stride", C.c_int64), ("uv_row_stride", C.c_int64), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("standard", C.c_int32), ("full_range", C.c_int32), ("lo", C.c_float), ("k", C.c_float), ("reserved", C.c_int32)]
+
+
+class FramesToI420Args(C.Structure):
+    """``spk_frames_to_i420_args`` (include/spk.h)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("y_image_stride", C.c_int64),
+                ("y_row_stride", C.c_int64), ("u_image_stride", C.c_int64), ("u_row_stride", C.c_int64), ("v_image_stride", C.c_int64),
+                ("v_row_stride", C.c_int64), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("standard", C.c_int32),
+                ("full_range", C.c_int32), ("lo", C.c_float), ("k", C.c_float), ("reserved", C.c_int32)]
 
 
 class PixelNormArgs(C.Structure):
@@ -463,6 +472,16 @@ _PROTOTYPES = {
                                         C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    "spk_frames_i420_to_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] * 3 + [C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_f32_to_i420": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p, C.c_int64, C.c_int64] * 3 +
+                               [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "spk_frames_paste_i420": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p, C.c_int64, C.c_int64] * 3 +
+                              [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                               C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
     "spk_frames_nv12_to_f32_sim": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 +
                                    [C.c_void_p]),

@@ -1,5 +1,6 @@
-// What the aligned I420 files share (csrc/frame_sim_i420.hip: N surfaces of one size behind three pointers and nine strides;
-// csrc/frame_table_i420.hip: every surface an entry of a device table): how the bytes of a three-plane surface are read, how a
+// What the I420 files share (csrc/frame_sim_i420.hip: aligned crops on N surfaces of one size behind three pointers and nine strides;
+// csrc/frame_table_i420.hip: every surface an entry of a device table; csrc/frame_i420.hip: the axis-aligned edge, which takes
+// PlanarPair and check_planar_surface from here): how the bytes of a three-plane surface are read, how a
 // chroma block of one is written, and the checks every planar surface argument gets.  An I420 surface is the NV12 surface with the
 // same Y bytes and UV[cy][cx] = (U[cy][cx], V[cy][cx]) behind another way to say where its bytes are: the arithmetic is YuvTaps'
 // (csrc/frame_nv12_common.hpp), the kernels are the templates the NV12 files instantiate, so the two layouts agree to the bit.

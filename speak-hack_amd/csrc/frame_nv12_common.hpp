@@ -1,4 +1,5 @@
-// What the NV12 kernels of the video-frame edge share (csrc/frame_nv12.hip: boxes through host-built tables; csrc/frame_sim_nv12.hip:
+// What the NV12 kernels of the video-frame edge share (csrc/frame_nv12.hip and, on three planes, csrc/frame_i420.hip: boxes through
+// host-built tables, the kernels of csrc/frame_nv12_axis_common.hpp; csrc/frame_sim_nv12.hip:
 // aligned crops through a similarity transform per frame; csrc/frame_i420_common.hpp: the same crops on three planes): the 3 x 4 colour maps and how a row of one is applied, the primaries of
 // a standard, and the checks every surface argument gets.  Written once, so that the two files agree on every colour coefficient
 // and on the order of every operation, to the bit; each file still links alone (the host functions are inline).
@@ -88,6 +89,16 @@ inline void yuv_coeffs(double kr, double kb, bool full, double* to_rgb, double* 
                               ay, bu, 0.0, -(ay * oy + 128.0 * bu)};
         std::copy(t, t + 12, to_rgb);
     }
+}
+
+// the two maps of a standard, either pointer may be null; refuses what spk_yuv_coeffs refuses (for the files that link without
+// csrc/frame_nv12.hip, which defines that one)
+inline int colour_maps(const char* who, int standard, int full_range, double* to_rgb, double* from_rgb) {
+    double kr, kb;
+    SPK_REQUIRE(primaries(standard, &kr, &kb), "%s: standard must be 601 or 709 (got %d)", who, standard);
+    SPK_REQUIRE(full_range == 0 || full_range == 1, "%s: full_range must be 0 or 1 (got %d)", who, full_range);
+    yuv_coeffs(kr, kb, full_range != 0, to_rgb, from_rgb);
+    return SPK_OK;
 }
 
 // the checks every NV12 surface argument gets; 0: fine

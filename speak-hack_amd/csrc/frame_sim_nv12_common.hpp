@@ -84,15 +84,7 @@ __global__ __launch_bounds__(256) void frames_paste_nv12_sim_kernel(const float*
 }
 
 // ---- host ----
-// the two maps of a standard, either pointer may be null; refuses what spk_yuv_coeffs refuses (these files link without that one)
-inline int colour_maps(const char* who, int standard, int full_range, double* to_rgb, double* from_rgb) {
-    double kr, kb;
-    SPK_REQUIRE(primaries(standard, &kr, &kb), "%s: standard must be 601 or 709 (got %d)", who, standard);
-    SPK_REQUIRE(full_range == 0 || full_range == 1, "%s: full_range must be 0 or 1 (got %d)", who, full_range);
-    yuv_coeffs(kr, kb, full_range != 0, to_rgb, from_rgb);
-    return SPK_OK;
-}
-
+// (the two maps of a standard: colour_maps of csrc/frame_nv12_common.hpp)
 // the launch of the paste into a target's surfaces over checked arguments (H, W: the launch's size, which a tabled target ignores)
 template <class Target>
 int launch_paste_nv12_sim(const char* kernel, const float* src, int N, int Hs, int Ws, const Target& out, int H, int W, const float* sim_dev,

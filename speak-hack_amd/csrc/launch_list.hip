@@ -84,6 +84,13 @@ extern "C" int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask,
             case SPK_OP_NOISE_FILL_ROWS:
                 rc = spk_noise_fill_rows(static_cast<const spk_noise_fill_rows_args*>(op.desc), stream);
                 break;
+            case SPK_OP_FRAMES_TO_I420: {
+                const spk_frames_to_i420_args* a = static_cast<const spk_frames_to_i420_args*>(op.desc);
+                rc = spk_frames_f32_to_i420(a->x, a->N, a->H, a->W, a->y, a->y_image_stride, a->y_row_stride, a->u, a->u_image_stride,
+                                            a->u_row_stride, a->v, a->v_image_stride, a->v_row_stride, a->standard, a->full_range, a->lo, a->k,
+                                            stream);
+                break;
+            }
             default:
                 return spk::fail(SPK_EUNSUPPORTED, "launch_list: op %d: unknown kind %d", i, op.kind);
         }

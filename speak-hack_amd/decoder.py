@@ -282,7 +282,8 @@ class StyleGenerator(nn.Module):
         """The eval forward -- mapping, truncation, synthesis; no style mixing, no host-RNG draw -- on the inference launch plan,
         whatever ``self.training`` is (no module state is read or touched).  No gradient flows through it.  ``output="uint8"``:
         the plan ends in the quantising op and returns uint8 [B,R,R,3] frames (``plan.DecoderPlan``); ``output="nv12"``: it ends in
-        the NV12 op and returns uint8 [B,3R/2,R] surfaces in the colour of ``standard`` / ``full_range``.  ``seed``: a seeded plan
+        the NV12 op and returns uint8 [B,3R/2,R] surfaces in the colour of ``standard`` / ``full_range``; ``output="i420"``: it ends
+        in the I420 op and returns packed uint8 [B,3R/2,R] surfaces (``ops.i420_planes``) in that colour.  ``seed``: a seeded plan
         (a cache entry of its own) draws the noise of ``ops.decoder_noise(shapes, seed, frame0=frame0, fixed=fixed_noise)`` as
         the first op of its list.  ``seed_rows`` / ``frame_rows`` (device int64 ``[B]`` tables, instead of ``seed``): a rows-seeded
         plan (again a cache entry of its own) draws ``ops.decoder_noise_rows(shapes, seed_rows, frame_rows)``, one (seed, frame) per
@@ -303,7 +304,7 @@ class StyleGenerator(nn.Module):
         # (the truncation scale is folded into the style FCs' multipliers when the plan is built: part of the key)
         key = (B, features.device, torch.cuda.current_stream(features.device).cuda_stream, "features", syn.precision,
                self.truncation_psi, self.truncation_cutoff)
-        if output == "nv12":
+        if output in ("nv12", "i420"):
             key += (output, float(value_range[0]), float(value_range[1]), *FR.yuv_standard(standard, full_range))
         elif output != "f32":
             key += (output, float(value_range[0]), float(value_range[1]), bool(swap_rb))

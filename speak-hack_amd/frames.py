@@ -1289,26 +1289,15 @@ def frames_from_nv12(nv12, size, *, crop=None, channel_order="rgb", mean=0.5, st
     strides.  ``crop``: the three forms of ``parse_boxes``; an origin may be odd (chroma is sited by replication: pixel ``(Y, X)``
     has sample ``(Y >> 1, X >> 1)``); device origins are clamped by the kernel so that the box stays inside the frame.
     ``channel_order`` only says which plane order the network input has ("bgr": planes B, G, R).  -> float32 [N,3,size,size]."""
-    y, uv = nv12_planes(nv12)
-    N, H, W = y.shape
-    Hout, Wout = _out_size(size, "frames_from_nv12")
-    swap = _channel_swap(channel_order)
-    code, full = yuv_standard(standard, full_range)
-    scale, shift = _affine(mean, std, "frames_from_nv12")
-    origins, h, w = parse_boxes((0, 0, H, W) if crop is None else crop, N, H, W, "frames_from_nv12: crop")
-    ys, us = nv12_strides(y, uv, "frames_from_nv12", written=False)
-    y0, x0, boxes = _origins(origins, y.device, "frames_from_nv12")
-    out = torch.empty((N, 3, Hout, Wout), device=y.device, dtype=torch.float32)
-    L.check(L.lib().spk_frames_nv12_to_f32(y.data_ptr(), *ys, uv.data_ptr(), *us, N, H, W, _ptr(boxes), y0, x0, h, w, swap, code, full,
-                                           *_table_args(_device_tables(y.device, h, w, Hout, Wout)), out.data_ptr(), Hout, Wout, *scale, *shift,
-                                           L.stream_ptr()), "spk_frames_nv12_to_f32")
-    return out
+    return _from_boxes(_SURFACES, "frames_from_nv12", nv12, size, crop, channel_order, mean, std, standard, full_range)
 
 
 class _Surfaces:
     """``_Packed`` for NV12: the frames of a call as what ``nv12_planes`` takes (csrc/frame_nv12.hip, csrc/frame_sim_nv12.hip)."""
+    layout = "NV12"
     way_in, paste = "spk_frames_nv12_to_f32_sim", "spk_frames_paste_nv12_sim"
     sums, match = "spk_paste_colour_sums_nv12_sim", "spk_paste_colour_match_nv12_sim"
+    box_in, box_paste, whole = "spk_frames_nv12_to_f32", "spk_frames_paste_nv12", "spk_frames_f32_to_nv12"      # the axis-aligned edge
 
     def shaped(self, nv12, N, what):                                      # -> ((y, uv), N, H, W)
         y, uv = nv12_planes(nv12)
@@ -1356,6 +1345,55 @@ class _Surfaces:
 
 
 _SURFACES = _Surfaces()
+
+
+# The three axis-aligned launchers of a Y, U, V format (``fmt``: ``_SURFACES`` or ``_PLANAR``): one body per launcher, the format
+# says how its surfaces are parsed and addressed and which entry point takes them.
+def _from_boxes(fmt, what, frames, size, crop, channel_order, mean, std, standard, full_range):
+    planes, N, H, W = fmt.shaped(frames, None, what)
+    Hout, Wout = _out_size(size, what)
+    swap = _channel_swap(channel_order)
+    code, full = yuv_standard(standard, full_range)
+    scale, shift = _affine(mean, std, what)
+    origins, h, w = parse_boxes((0, 0, H, W) if crop is None else crop, N, H, W, f"{what}: crop")
+    y, where = fmt.read(planes, what)
+    y0, x0, boxes = _origins(origins, y.device, what)
+    out = torch.empty((N, 3, Hout, Wout), device=y.device, dtype=torch.float32)
+    L.check(getattr(L.lib(), fmt.box_in)(*where, N, H, W, _ptr(boxes), y0, x0, h, w, swap, code, full,
+                                         *_table_args(_device_tables(y.device, h, w, Hout, Wout)), out.data_ptr(), Hout, Wout, *scale, *shift,
+                                         L.stream_ptr()), fmt.box_in)
+    return out
+
+
+def _to_surfaces(fmt, what, x, value_range, standard, full_range, out):
+    _check_chw(x, what)
+    N, _, H, W = x.shape
+    if H % 2 or W % 2 or H < 2 or W < 2:
+        raise ValueError(f"{what}: {fmt.layout} frames have an even height and width, got {H} x {W}")
+    lo, k = quant_range(value_range)
+    code, full = yuv_standard(standard, full_range)
+    xp = L.dptr(x, "x")
+    out, where, _ = fmt.target(None, out, N, H, W, x.device, what)
+    L.check(getattr(L.lib(), fmt.whole)(xp, N, H, W, *where, code, full, lo, k, L.stream_ptr()), fmt.whole)
+    return out
+
+
+def _paste_boxes(fmt, what, x, frames, box, feather, value_range, standard, full_range, out):
+    _check_chw(x, what)
+    N, _, Hs, Ws = x.shape
+    planes, _, H, W = fmt.shaped(frames, N, what)
+    (code, full), lo, k = fmt.quantised(value_range, standard, full_range)
+    feather = check_feather(feather, what)
+    origins, h, w = parse_boxes(box, N, H, W, f"{what}: box", inside=False)
+    xp = L.dptr(x, "x")
+    fmt.on_device(planes)
+    out, where, fill = fmt.target(planes, out, N, H, W, x.device, what)
+    y0, x0, boxes = _origins(origins, x.device, what)
+    fill()
+    tables, ay, ax = _paste_tables(Hs, Ws, h, w, feather, x.device)
+    L.check(getattr(L.lib(), fmt.box_paste)(xp, N, Hs, Ws, *where, H, W, h, w, y0, x0, _ptr(boxes), code, full, *tables, ay, ax, lo, k,
+                                            L.stream_ptr()), fmt.box_paste)
+    return out
 
 
 # ---- a surface table: every NV12 surface its own planes, pitches and size (csrc/frame_table_nv12.hip; include/spk.h) ---------------
@@ -1476,16 +1514,7 @@ def frames_to_nv12(x, *, value_range=(-1, 1), standard="bt601", full_range=False
     ``H`` and ``W`` even) in ``value_range`` is quantised as ``frames_to_u8`` does without its rounding, converted with
     ``from_rgb`` of ``yuv_coeffs`` in fp64, and stored as ``Y = rint(clamp(e_y))`` per pixel and ``C = rint(clamp(mean of the four
     e_c))`` per 2 x 2 block.  ``out``: what ``nv12_planes`` takes (any row pitch).  -> uint8 [N, 3H/2, W], or ``out``."""
-    _check_chw(x, "frames_to_nv12")
-    N, _, H, W = x.shape
-    if H % 2 or W % 2 or H < 2 or W < 2:
-        raise ValueError(f"frames_to_nv12: NV12 frames have an even height and width, got {H} x {W}")
-    lo, k = quant_range(value_range)
-    code, full = yuv_standard(standard, full_range)
-    xp = L.dptr(x, "x")
-    out, where, _ = _SURFACES.target(None, out, N, H, W, x.device, "frames_to_nv12")
-    L.check(L.lib().spk_frames_f32_to_nv12(xp, N, H, W, *where, code, full, lo, k, L.stream_ptr()), "spk_frames_f32_to_nv12")
-    return out
+    return _to_surfaces(_SURFACES, "frames_to_nv12", x, value_range, standard, full_range, out)
 
 
 def frames_paste_nv12(x, nv12, box, *, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
@@ -1496,22 +1525,7 @@ def frames_paste_nv12(x, nv12, box, *, feather=0, value_range=(-1, 1), standard=
     ``parse_boxes``; origins may be odd; box pixels outside the frame are skipped.  ``out=None``: the result is a packed clone of
     ``nv12``; ``out=nv12`` (the same tensor, or the same pair of planes): pasted in place through its strides; another ``out``
     first receives a copy.  -> uint8 [N, 3H/2, W], or ``out``."""
-    what = "frames_paste_nv12"
-    _check_chw(x, what)
-    N, _, Hs, Ws = x.shape
-    planes, _, H, W = _SURFACES.shaped(nv12, N, what)
-    (code, full), lo, k = _SURFACES.quantised(value_range, standard, full_range)
-    feather = check_feather(feather, what)
-    origins, h, w = parse_boxes(box, N, H, W, f"{what}: box", inside=False)
-    xp = L.dptr(x, "x")
-    _SURFACES.on_device(planes)
-    out, where, fill = _SURFACES.target(planes, out, N, H, W, x.device, what)
-    y0, x0, boxes = _origins(origins, x.device, what)
-    fill()
-    tables, ay, ax = _paste_tables(Hs, Ws, h, w, feather, x.device)
-    L.check(L.lib().spk_frames_paste_nv12(xp, N, Hs, Ws, *where, H, W, h, w, y0, x0, _ptr(boxes), code, full, *tables, ay, ax, lo, k,
-                                          L.stream_ptr()), "spk_frames_paste_nv12")
-    return out
+    return _paste_boxes(_SURFACES, "frames_paste_nv12", x, nv12, box, feather, value_range, standard, full_range, out)
 
 
 # ---- aligned crops on NV12 surfaces (csrc/frame_sim_nv12.hip; the definitions are in include/spk.h) --------------------------------
@@ -1643,8 +1657,10 @@ def _planar_where(planes, strides):                                       # the 
 class _Planar(_Surfaces):
     """``_Surfaces`` for I420: the frames of a call as what ``i420_planes`` takes (csrc/frame_sim_i420.hip); the colour arguments
     are NV12's"""
+    layout = "I420"
     way_in, paste = "spk_frames_i420_to_f32_sim", "spk_frames_paste_i420_sim"
     sums, match = "spk_paste_colour_sums_i420_sim", "spk_paste_colour_match_i420_sim"
+    box_in, box_paste, whole = "spk_frames_i420_to_f32", "spk_frames_paste_i420", "spk_frames_f32_to_i420"      # csrc/frame_i420.hip
 
     def shaped(self, i420, N, what):                                      # -> ((y, u, v), N, H, W)
         planes = i420_planes(i420)
@@ -1775,6 +1791,35 @@ def clone_planar(i420):
     out, _, fill = _PLANAR.target(planes, None, *planes[0].shape, planes[0].device, "clone_planar")
     fill()
     return out
+
+
+# ---- the axis-aligned edge on I420 surfaces (csrc/frame_i420.hip; the definitions are in include/spk.h) ---------------------------
+def frames_from_i420(i420, size, *, crop=None, channel_order="rgb", mean=0.5, std=0.5, standard="bt601", full_range=False):
+    """``frames_from_nv12`` for I420 surfaces, one launch (``spk_frames_i420_to_f32``): the same crop, resize, colour maps and
+    arguments over three planes, and the same fp32 BITS as that launcher gives on the NV12 surface with the same Y bytes and
+    ``UV[cy][cx] = (U[cy][cx], V[cy][cx])``.  ``i420``: what ``i420_planes`` takes -- a contiguous packed ``[N,3H/2,W]`` tensor or a
+    triple of plane views of any pitch -- on the device, read in place through its strides; no alignment, parity or order in memory
+    is asked of a chroma plane (chroma is loaded as bytes; YV12 is the triple with the planes swapped).  ``crop``: the three forms
+    of ``parse_boxes``; an origin may be odd; device origins are clamped by the kernel.  -> float32 [N,3,size,size]."""
+    return _from_boxes(_PLANAR, "frames_from_i420", i420, size, crop, channel_order, mean, std, standard, full_range)
+
+
+def frames_to_i420(x, *, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
+    """``frames_to_nv12`` for I420, one launch (``spk_frames_f32_to_i420``): the Y, U and V bytes are those that launcher leaves in
+    its Y plane and in the two halves of its UV pairs.  ``out``: what ``i420_planes`` takes, a packed tensor or a triple of planes
+    of any pitch (bytes that belong to no plane are not touched).  -> ``out``, or a fresh packed uint8 ``[N, 3H/2, W]`` tensor: the
+    ``H`` rows of Y, then the ``HW/4`` bytes of U, then those of V."""
+    return _to_surfaces(_PLANAR, "frames_to_i420", x, value_range, standard, full_range, out)
+
+
+def frames_paste_i420(x, i420, box, *, feather=0, value_range=(-1, 1), standard="bt601", full_range=False, out=None):
+    """``frames_paste_nv12`` for I420 surfaces, one launch (``spk_frames_paste_i420``): the same resize, values, ``feather`` and
+    blend, luma per pixel and chroma per 2 x 2 block, with a byte load and a byte store per chroma plane; the Y, U and V bytes are
+    those the NV12 launcher leaves on the interleaved surface.  ``box``: the three forms of ``parse_boxes``; origins may be odd; box
+    pixels outside the frame are skipped.  ``out=None``: the result is ONE packed clone of ``i420`` with every plane copied, the
+    input unchanged; ``out=i420`` (the same tensor, or the same triple of planes): pasted in place through its strides; another
+    ``out`` first receives a copy.  -> uint8 [N, 3H/2, W], or ``out``."""
+    return _paste_boxes(_PLANAR, "frames_paste_i420", x, i420, box, feather, value_range, standard, full_range, out)
 
 
 def frames_from_i420_aligned(i420, size, sim, *, channel_order="rgb", mean=0.5, std=0.5, standard="bt601", full_range=False):
@@ -1927,4 +1972,26 @@ class Nv12:
         frames_paste_nv12(y, part, box, feather=feather, out=part, **self.args)
 
 
-PIXEL_FORMATS = {"rgb24": Rgb24, "nv12": Nv12}
+class I420(Nv12):
+    """I420 surfaces: what ``i420_planes`` takes, in the colour of ``standard`` / ``full_range``."""
+    output = "i420"
+
+    def open(self, frames, inplace):
+        planes = i420_planes(frames)
+        if inplace:
+            i420_strides(*planes, "reenact_video: inplace", written=True)
+        return (planes, planes[0].device, *planes[0].shape)
+
+    def network_input(self, frames, size, crop):
+        return frames_from_i420(frames, size, crop=crop, **self.args)
+
+    def clone(self, planes):                                              # one clone: a packed surface per frame
+        out = clone_planar(planes)
+        return out, i420_planes(out)
+
+    def paste(self, y, planes, t0, t1, box, feather):
+        part = tuple(p[t0:t1] for p in planes)
+        frames_paste_i420(y, part, box, feather=feather, out=part, **self.args)
+
+
+PIXEL_FORMATS = {"rgb24": Rgb24, "nv12": Nv12, "i420": I420}

@@ -117,7 +117,9 @@ class IRFD(nn.Module):
         uint8 [T,R,R,3] in ``channel_order`` ("rgb" | "bgr"), quantised from (-1, 1) by the last op of the decoder plan --
         ``ops.frames_to_u8`` of the fp32 result, bit for bit.  ``output="nv12"``: uint8 [T,3R/2,R] NV12 surfaces (rows ``R..`` are the
         interleaved UV plane) in the colour of ``standard`` ("bt601" | "bt709") / ``full_range``, converted by the last op of the
-        decoder plan -- ``ops.frames_to_nv12`` of the fp32 result, bit for bit.
+        decoder plan -- ``ops.frames_to_nv12`` of the fp32 result, bit for bit.  ``output="i420"``: packed uint8 [T,3R/2,R] I420
+        surfaces in that colour -- the ``R`` rows of Y, then the ``R^2 / 4`` bytes of U, then those of V, what ``ops.i420_planes``
+        takes -- ``ops.frames_to_i420`` of the fp32 result, bit for bit.
 
         ``seed`` (0 <= seed < 2**64; not together with ``noises``): reproducible noise, a function of (seed, frame index,
         layer, pixel) drawn inside the decoder's launch list (``ops.decoder_noise`` gives the same tensors explicitly); the
@@ -125,8 +127,8 @@ class IRFD(nn.Module):
         frames ``[a, b)`` of a longer clip may be rendered elsewhere with ``frame0=a``.  ``noise="fixed"`` (needs a seed): every
         frame uses frame index ``frame0`` -- one noise image per layer held over the clip, as StyleGAN video pipelines do
         against boiling texture; ``"fresh"`` (default): new noise on every frame."""
-        if output != "nv12" and (standard != "bt601" or full_range):
-            raise ValueError("reenact: standard / full_range apply to nv12 output only")
+        if output not in ("nv12", "i420") and (standard != "bt601" or full_range):
+            raise ValueError("reenact: standard / full_range apply to nv12 output only, and to i420")
         out = [y for _, _, y in self._reenact_chunks(identity_image, pose_frames, emotion_frames, noises, chunk, output, channel_order,
                                                      seed, noise, frame0, (standard, full_range))]
         return out[0] if len(out) == 1 else torch.cat(out, 0)
@@ -134,8 +136,8 @@ class IRFD(nn.Module):
     def _reenact_chunks(self, identity_image, pose_frames, emotion_frames, noises, chunk, output, channel_order, seed, noise, frame0,
                         colour=("bt601", False)):
         """``reenact``'s argument checks and chunk loop: yields ``(t0, t1, frames of [t0, t1))``."""
-        if output not in ("f32", "uint8", "nv12"):
-            raise ValueError(f"reenact: output must be 'f32', 'uint8' or 'nv12', got {output!r}")
+        if output not in ("f32", "uint8", "nv12", "i420"):
+            raise ValueError(f"reenact: output must be 'f32', 'uint8', 'nv12' or 'i420', got {output!r}")
         FR.yuv_standard(*colour)
         _check_noise("reenact", noise, seed, noises, frame0)
         if seed is None and frame0 != 0:
@@ -190,6 +192,13 @@ class IRFD(nn.Module):
         ``reenact(output="nv12")``, ``ops.frames_paste_nv12``: one launch per chunk).  The identity image stays a uint8 HWC photo
         in ``channel_order``; ``crop`` keeps its three forms and may have an odd origin.
 
+        ``pixel_format="i420"``: the same for I420 (``yuv420p``) as a software decoder leaves it -- one CONTIGUOUS packed uint8 tensor
+        ``[T,3H/2,W]`` or a triple of planes ``(y [T,H,W], u [T,H/2,W/2], v [T,H/2,W/2])`` with any pitch, base and order in memory
+        (``ops.i420_planes``; YV12 is the triple with the planes swapped) -- through ``ops.frames_from_i420``,
+        ``reenact(output="i420")`` and ``ops.frames_paste_i420``: one ``spk_frames_paste_i420`` launch per chunk, in place into the
+        decoder's own planes with ``inplace=True``, and no interleaving into scratch NV12 surfaces.  The Y, U and V bytes are those
+        of ``pixel_format="nv12"`` on the interleaved clip.  The identity photo stays packed RGB.
+
         ``align=sim`` (instead of ``crop``; both: ``ValueError``): an aligned crop per frame -- rows ``(a, c, tx, ty)`` of the
         similarity transform that maps the ``size`` network image into frame ``t`` (``ops.similarity_rows``; include/spk.h), any
         scale and angle per frame, as ``ops.similarity_from_landmarks`` fits them to a tracker's landmarks: a host sequence / CPU
@@ -199,8 +208,8 @@ class IRFD(nn.Module):
         ``ops.frames_from_u8_aligned``; with ``paste=True`` each chunk's fp32 result goes through ``ops.frames_paste_u8_aligned``
         into its slice, one ``spk_frames_paste_u8_sim`` launch per chunk, rows taken per frame, so the result does not depend on
         ``chunk``.  The generated image has ``R`` pixels where the network image has ``size``: the paste uses the rows with
-        ``(a, c)`` scaled by ``size / R`` in fp32.  Packed RGB only: ``align`` with ``pixel_format="nv12"`` raises ``ValueError``
-        (NV12 frames take crop boxes).
+        ``(a, c)`` scaled by ``size / R`` in fp32.  Packed RGB only: ``align`` with ``pixel_format="nv12"`` or ``"i420"`` raises
+        ``ValueError`` (NV12 and I420 frames take crop boxes).
 
         ``identity_align``: the identity photo through an aligned crop as well, so that ``Ei`` sees a face framed as ``Ee`` / ``Ep``
         see theirs -- one row in either form above (``[1,4]``; host rows are checked before any launch) or an ``ops.LandmarkAlign``
@@ -231,9 +240,9 @@ class IRFD(nn.Module):
         the paste of frame ``j`` writes frame ``j`` only: here too the result depends neither on ``chunk`` nor on ``inplace``.
         ``colour_smooth=0``: the calls the method always made."""
         if pixel_format not in FR.PIXEL_FORMATS:
-            raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12', got {pixel_format!r}")
+            raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12' or 'i420', got {pixel_format!r}")
         if pixel_format == "rgb24" and (standard != "bt601" or full_range):
-            raise ValueError("reenact_video: standard / full_range apply to pixel_format='nv12' only")
+            raise ValueError("reenact_video: standard / full_range apply to pixel_format='nv12' only, and to 'i420'")
         FR.yuv_standard(standard, full_range)
         feather = float(feather)
         if inplace and not paste:
@@ -406,7 +415,8 @@ class IRFD(nn.Module):
             noises, seeded = ops.decoder_noise_rows(Gd.synthesis.noise_shapes(gin.size(0)), seeded["seed_rows"], seeded["frame_rows"]), {}
         if hasattr(Gd, "plan_serves") and Gd.plan_serves(gin):
             how = {"f32": {}, "uint8": dict(output=output, swap_rb=channel_order == "bgr"),
-                   "nv12": dict(output=output, standard=colour[0], full_range=colour[1])}[output]
+                   "nv12": dict(output=output, standard=colour[0], full_range=colour[1]),
+                   "i420": dict(output=output, standard=colour[0], full_range=colour[1])}[output]
             return Gd.plan_forward(gin, noises, **how, **seeded)
         flags = [(mod, mod.training) for mod in Gd.modules()]
         try:
@@ -418,6 +428,8 @@ class IRFD(nn.Module):
                 mod.training = was
         if output == "nv12":
             return ops.frames_to_nv12(y, standard=colour[0], full_range=colour[1])
+        if output == "i420":
+            return ops.frames_to_i420(y, standard=colour[0], full_range=colour[1])
         return y if output == "f32" else ops.frames_to_u8(y, channel_order=channel_order)
 
     def forward(self, x_s, x_t, swap_type=None, noises_s=None, noises_t=None):

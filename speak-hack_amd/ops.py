@@ -21,7 +21,8 @@ from .frames import (resize_tables, resize_tables_f32, feather_tables, parse_box
                      frames_from_nv12_aligned, frames_paste_nv12_aligned, paste_colour_match_nv12, matte_from_landmarks, LandmarkMatte,
                      paste_colour_sums, paste_colour_sums_nv12, colour_rows_from_sums, causal_filter, causal_filter_state,
                      colour_rows_causal, colour_rows_causal_feeds, i420_planes, PlanarTable, clone_planar, frames_from_i420_aligned,
-                     frames_paste_i420_aligned, paste_colour_match_i420, paste_colour_sums_i420)
+                     frames_paste_i420_aligned, paste_colour_match_i420, paste_colour_sums_i420, frames_from_i420, frames_to_i420,
+                     frames_paste_i420)
 
 
 def _launch_conv2d(desc):

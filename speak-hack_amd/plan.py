@@ -176,7 +176,9 @@ class DecoderPlan(LaunchPlan):
     ``run`` returns (``swap_rb``: B, G, R order) -- what ``ops.frames_to_u8`` makes of the fp32 result, bit for bit.
     ``output="nv12"``: the same buffer and one ``SPK_OP_FRAMES_TO_NV12`` instead, which converts it from ``value_range`` with the
     colour matrix of ``standard`` / ``full_range`` into the uint8 [B,3R/2,R] NV12 surfaces ``run`` returns -- ``ops.frames_to_nv12``
-    of the fp32 result, bit for bit.
+    of the fp32 result, bit for bit.  ``output="i420"``: one ``SPK_OP_FRAMES_TO_I420`` instead, into packed uint8 [B,3R/2,R] I420
+    surfaces -- the ``R`` rows of Y, then the ``R^2 / 4`` bytes of U, then those of V, what ``ops.i420_planes`` takes --
+    ``ops.frames_to_i420`` of the fp32 result, bit for bit.
     ``seeded=True``: the list starts with ``SPK_OP_NOISE_FILL`` (csrc/noise.hip), which writes ``noise_flat`` from the
     ``seed`` / ``frame0`` each ``run`` patches into its descriptor -- the noise of ``ops.decoder_noise``, bit for bit, and the
     forward is the launch list alone (no ATen draw, the device generator untouched).  A seeded plan runs seeded calls only, an
@@ -189,8 +191,8 @@ class DecoderPlan(LaunchPlan):
     def __init__(self, synthesis, B, device, generator=None, precision="f32", output="f32", value_range=(-1, 1), swap_rb=False,
                  seeded=False, standard="bt601", full_range=False):
         super().__init__(device)
-        if output not in ("f32", "uint8", "nv12"):
-            raise ValueError(f"DecoderPlan: output must be 'f32', 'uint8' or 'nv12', got {output!r}")
+        if output not in ("f32", "uint8", "nv12", "i420"):
+            raise ValueError(f"DecoderPlan: output must be 'f32', 'uint8', 'nv12' or 'i420', got {output!r}")
         s = self.synthesis = synthesis
         self.precision = precision
         self.output = output
@@ -288,7 +290,7 @@ class DecoderPlan(LaunchPlan):
             self.torgb = self.add(L.OP_TORGB, L.ToRGBArgs(x=x.data_ptr(), w=L.dptr(s.to_rgb.weight, "weight"), mod=None,
                                                           bias=L.dptr(s.to_rgb.bias, "bias"), skip=None, y=None, B=B, C=Cc, O=O,
                                                           H=x.shape[2], W=x.shape[3], in_scale=1.0))
-        self.to_u8 = self.to_nv12 = None
+        self.to_u8 = self.to_nv12 = self.to_i420 = None
         if output != "f32":
             if O != 3:
                 raise L.SpkError(f"DecoderPlan: {output} frames need 3 output channels, toRGB has {O}")
@@ -298,11 +300,17 @@ class DecoderPlan(LaunchPlan):
                 self.rgb_fused.rgb_y = self.rgb_buf.data_ptr()
             else:
                 self.torgb.y = self.rgb_buf.data_ptr()
-        if output == "nv12":
+        if output in ("nv12", "i420"):
             code, full = FR.yuv_standard(standard, full_range)
             Ho, Wo = x.shape[2], x.shape[3]
             if swap_rb:
                 raise ValueError("DecoderPlan: swap_rb applies to uint8 output only")
+        if output == "i420":                                              # packed surfaces: a chroma plane is Ho / 2 rows of Wo / 2 bytes
+            self.to_i420 = self.add(L.OP_FRAMES_TO_I420, L.FramesToI420Args(
+                x=self.rgb_buf.data_ptr(), y=None, u=None, v=None, y_image_stride=3 * Ho // 2 * Wo, y_row_stride=Wo,
+                u_image_stride=3 * Ho // 2 * Wo, u_row_stride=Wo // 2, v_image_stride=3 * Ho // 2 * Wo, v_row_stride=Wo // 2, N=B, H=Ho, W=Wo,
+                standard=code, full_range=full, lo=lo, k=k, reserved=0))
+        if output == "nv12":
             self.to_nv12 = self.add(L.OP_FRAMES_TO_NV12, L.FramesToNv12Args(
                 x=self.rgb_buf.data_ptr(), y=None, uv=None, y_image_stride=3 * Ho // 2 * Wo, y_row_stride=Wo, uv_image_stride=3 * Ho // 2 * Wo,
                 uv_row_stride=Wo, N=B, H=Ho, W=Wo, standard=code, full_range=full, lo=lo, k=k, reserved=0))
@@ -384,6 +392,11 @@ class DecoderPlan(LaunchPlan):
             Bo, _, Ho, Wo = self.out_shape
             y = torch.empty((Bo, 3 * Ho // 2, Wo), device=self.device, dtype=torch.uint8)      # packed surfaces: rows Ho.. are the UV plane
             self.to_nv12.y, self.to_nv12.uv = y.data_ptr(), y.data_ptr() + Ho * Wo
+        elif self.to_i420 is not None:
+            Bo, _, Ho, Wo = self.out_shape
+            y = torch.empty((Bo, 3 * Ho // 2, Wo), device=self.device, dtype=torch.uint8)      # packed surfaces: Y rows, then U, then V
+            a = self.to_i420
+            a.y, a.u, a.v = y.data_ptr(), y.data_ptr() + Ho * Wo, y.data_ptr() + Ho * Wo + Ho * Wo // 4
         else:
             y = torch.empty(self.out_shape, device=self.device, dtype=torch.float32)
             if self.rgb_fused is not None:

@@ -81,6 +81,11 @@
     room on a planar table, the detour it replaces (interleave into scratch NV12 surfaces, the NV12 room, split and copy back) and
     the NV12 room alone; then the three I420 launchers beside their NV12 siblings.  Written to profiles/live_i420_bench.txt.
 
+``--i420``: the axis-aligned I420 edge with the settings of ``--nv12``: ``frames_from_i420``, ``frames_to_i420`` and
+    ``frames_paste_i420`` each beside its NV12 sibling on the interleaved surfaces, and ``reenact_video(pixel_format="i420",
+    paste=True)`` beside the detour it replaces (interleave, ``pixel_format="nv12"``, split and copy back, chunk by chunk).  Written to
+    profiles/i420_bench.txt; reported, not gated.
+
     python tools/bench_frame_io.py [--paste | --nv12 | --align | --align-nv12 | --landmarks | --blend | --landmark-matte | --colour-smooth] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
@@ -1247,6 +1252,110 @@ def bench_live_i420(args, lines):
         ratio_table(lines, f"{title}: {shape}; {note}; {how}", alternate(contenders, args.repeats, device_time), name, [(sibling, False)])
 
 
+def packed_i420(ops, nv12):
+    """NV12 surfaces [N,3H/2,W] -> the contiguous packed I420 tensor [N,3H/2,W] with the same Y, U and V bytes"""
+    y, uv = ops.nv12_planes(nv12)
+    return torch.cat([y.flatten(1), uv[..., 0].flatten(1), uv[..., 1].flatten(1)], 1).view(nv12.shape)
+
+
+def bench_i420(args, lines):
+    """``--i420``: the axis-aligned I420 edge with the settings of ``--nv12`` -- 1080 x 1920 surfaces, a 400 x 400 tracked box, feather 16,
+    256^2 in and out.  (1) ``frames_from_i420``, ``frames_to_i420`` and ``frames_paste_i420`` each beside its NV12 sibling on the
+    interleaved surfaces, by HIP events; (2) ``reenact_video(pixel_format="i420", paste=True)`` in place into the decoder's planes
+    beside the detour it replaces, chunk by chunk: interleave into scratch NV12 surfaces, ``pixel_format="nv12"`` in place, split and
+    copy back -- wall clock, synchronised.  The contenders alternate in one process, medians are compared, and the I420 contender is
+    entered twice: the distance of its two medians is the spread.  Nothing is gated."""
+    import importlib
+    import model
+    from oracle import irfd_ref as IR
+    from oracle.weights_recipe import fill_state_dict
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    T, chunk, size, Hf, Wf, h, w, feather = args.frames, args.chunk, 256, 1080, 1920, 400, 400, 16
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(T)]                  # a head that moves, origins of both parities
+    yx = torch.tensor(boxes, dtype=torch.int32, device=dev)
+    _, from_rgb = (t.float().to(dev) for t in ops.yuv_coeffs())
+
+    # ---- (1) the three launchers beside their NV12 siblings ----
+    surf = torch_bgr_to_nv12(torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev), from_rgb)
+    planes = ops.i420_planes(packed_i420(ops, surf))
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    box = (yx[:chunk], h, w)
+    how = f"HIP events, launcher included, median of {args.repeats} alternating rounds of 20 after 3 warm-up calls"
+    same_in = torch.equal(ops.frames_from_i420(planes, size, crop=box), ops.frames_from_nv12(surf, size, crop=box))
+    oi, on = ops.frames_to_i420(x), ops.frames_to_nv12(x)
+    same_out = torch.equal(oi, packed_i420(ops, on))
+    same_paste = torch.equal(ops.frames_paste_i420(x, planes, box, feather=feather), packed_i420(ops, ops.frames_paste_nv12(x, surf, box, feather=feather)))
+    pairs = ((f"way in, whole frame: {chunk} x {Hf}x{Wf} -> {size}^2", "frames_from_i420", lambda: ops.frames_from_i420(planes, size), "frames_from_nv12",
+              lambda: ops.frames_from_nv12(surf, size), ""),
+             (f"way in, tracked boxes: {chunk} x {h}x{w} of {Hf}x{Wf} -> {size}^2", "frames_from_i420(crop)", lambda: ops.frames_from_i420(planes, size, crop=box),
+              "frames_from_nv12(crop)", lambda: ops.frames_from_nv12(surf, size, crop=box), f"the same bits: {same_in}"),
+             (f"conversion out: {chunk} x {size}^2 fp32", "frames_to_i420", lambda: ops.frames_to_i420(x, out=oi), "frames_to_nv12",
+              lambda: ops.frames_to_nv12(x, out=on), f"the same bytes: {same_out}"),
+             (f"paste: {chunk} x {size}^2 fp32 -> {h}x{w} boxes of {Hf}x{Wf}, feather {feather}, in place", "frames_paste_i420",
+              lambda: ops.frames_paste_i420(x, planes, box, feather=feather, out=planes), "frames_paste_nv12",
+              lambda: ops.frames_paste_nv12(x, surf, box, feather=feather, out=surf), f"the same bytes: {same_paste}"))
+    for title, name, ours, sibling, theirs, note in pairs:
+        contenders = {name: ours, sibling: theirs, name + " (again)": ours}
+        ratio_table(lines, f"{title}; {note + '; ' if note else ''}{how}", alternate(contenders, args.repeats, device_time), name, [(sibling, False)])
+
+    # ---- (2) reenact_video(pixel_format="i420", paste=True) beside interleave + pixel_format="nv12" + split, chunk by chunk ----
+    m = model.IRFD()
+    sd = IR.irfd_recipe_state_dict()
+    sd.update({"Gd." + k: v for k, v in fill_state_dict(m.Gd.state_dict(), prefix="Gd.").items()})
+    m.load_state_dict(sd, strict=False)
+    m.to(dev).eval()
+    ident = torch.randint(0, 256, (1, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    video = torch.empty((T, 3 * Hf // 2, Wf), dtype=torch.uint8, device=dev)              # packed I420, in gamut (as --nv12 makes its clip)
+    for t0 in range(0, T, chunk):
+        coarse = torch.randint(0, 256, (min(chunk, T - t0), Hf // 2, Wf // 2, 3), generator=g, dtype=torch.uint8).to(dev)
+        video[t0:t0 + chunk] = packed_i420(ops, torch_bgr_to_nv12(coarse.repeat_interleave(2, 1).repeat_interleave(2, 2), from_rgb))
+    noises = [torch.randn(T, 1, 4 << (i + 1) // 2, 4 << (i + 1) // 2, generator=g).to(dev) for i in range(13)]
+    kw = dict(size=size, channel_order="bgr", chunk=chunk, paste=True, feather=feather, inplace=True)
+    work = video.clone()
+
+    def ours():
+        return m.reenact_video(ident, work, crop=(yx, h, w), noises=noises, pixel_format="i420", **kw)
+
+    def detour():
+        y, u, v = ops.i420_planes(work)
+        for t0 in range(0, T, chunk):
+            t1 = min(T, t0 + chunk)
+            scratch = torch.empty((t1 - t0, 3 * Hf // 2, Wf), dtype=torch.uint8, device=dev)
+            sy, suv = ops.nv12_planes(scratch)
+            sy.copy_(y[t0:t1]), suv[..., 0].copy_(u[t0:t1]), suv[..., 1].copy_(v[t0:t1])                  # interleave
+            m.reenact_video(ident, scratch, crop=(yx[t0:t1], h, w), noises=[n[t0:t1] for n in noises], pixel_format="nv12", **kw)
+            y[t0:t1].copy_(sy), u[t0:t1].copy_(suv[..., 0]), v[t0:t1].copy_(suv[..., 1])                  # split and copy back
+        return work
+
+    names = ("pixel_format=i420", "interleave + nv12 + split", "pixel_format=i420 (again)")
+    fns = dict(zip(names, (ours, detour, ours)))
+    with torch.no_grad():
+        work.copy_(video)
+        a = ours().clone()
+        work.copy_(video)
+        b = detour().clone()
+        for _ in range(args.warmup):
+            ours(), detour()
+        times = alternate(fns, args.repeats, wall)
+        c_ours, c_other = CountAten(), CountAten()
+        with c_ours:
+            ours()
+        with c_other:
+            detour()
+    lines.append(f"T = {T} I420 frames of {Hf}x{Wf}, a {h}x{w} tracked box, feather {feather}, chunk {chunk}, in place; wall clock, synchronised, "
+                 f"{args.repeats} alternating rounds after {args.warmup} warm-up rounds; the same bytes: {torch.equal(a, b)}; ATen calls per run: "
+                 f"{c_ours.n} against {c_other.n} ({T // chunk} chunks)")
+    med = {n: statistics.median(ts) for n, ts in times.items()}
+    for n, ts in times.items():
+        lines.append(f"  {n:28s} median {med[n] * 1e3:8.2f} ms  min {ts[0] * 1e3:8.2f}  max {ts[-1] * 1e3:8.2f}  -> {T / med[n]:8.1f} frames/s")
+    spread = abs(med[names[0]] - med[names[2]]) / min(med[names[0]], med[names[2]])
+    lines.append(f"  spread of the repeated contender: {spread * 100:.2f} %; pixel_format=i420 / detour = {med[names[0]] / med[names[1]]:.3f} "
+                 f"({(med[names[1]] - med[names[0]]) * 1e3:.2f} ms less per clip)")
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -1277,6 +1386,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--paste", action="store_true", help="the full-frame way out: frames_paste_u8 and reenact_video(paste=True)")
     ap.add_argument("--nv12", action="store_true", help="the NV12 form of the edge: its kernels and reenact_video(pixel_format='nv12', paste=True)")
+    ap.add_argument("--i420", action="store_true", help="the axis-aligned I420 edge: its three launchers beside their NV12 siblings, and "
+                    "reenact_video(pixel_format='i420', paste=True) beside interleave + pixel_format='nv12' + split")
     ap.add_argument("--align", action="store_true", help="the aligned edge: frames_from_u8_aligned, frames_paste_u8_aligned, reenact_video(align=)")
     ap.add_argument("--blend", action="store_true", help="the seamless paste-back: matte, colour match and their torch composition")
     ap.add_argument("--align-nv12", action="store_true", help="the aligned NV12 edge: its three launchers beside their siblings and the BGR detour")
@@ -1296,6 +1407,10 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.i420:
+        lines = [f"bench_frame_io --i420: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_i420(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "i420_bench.txt"))
     if args.live_i420:
         lines = [f"bench_frame_io --live-i420: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
         bench_live_i420(args, lines)

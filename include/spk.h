@@ -1183,6 +1183,64 @@ int spk_paste_colour_sums_sim_table(const float* src, int N, int Hs, int Ws, con
                                     double feather, float lo, float k, const float* matte_dev, int matte_frames, double* sums_out_dev,
                                     void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- the aligned edge on RGB32 frames: four bytes per pixel, strided and tabled (csrc/frame_sim_rgb32.hip, csrc/frame_table_rgb32.hip) ----
+ * Packed 24-bit RGB is a host format; what holds an RGB picture on a GPU -- capture surfaces, interop textures, compositors, ARGB
+ * buffers -- holds four bytes per pixel.  An RGB32 FRAME is uint8 [H][W][4] with pixel stride 4:
+ *     data: 4-byte aligned;  row_stride: in bytes, a multiple of 4, >= 4 W  (with N > 1 frames: image_stride a multiple of 4 too)
+ * so a region-of-interest view at any pixel offset of a wider surface qualifies.  Two integers say where the colour is:
+ *     alpha_first: 0: colour in bytes 0..2, the fourth byte is byte 3;  1: the fourth byte is byte 0, colour in bytes 1..3
+ *     swap_rb:     as everywhere else (0: the colour bytes are R, G, B in memory order; 1: B, G, R)
+ * which gives the four orders rgba, bgra, argb, abgr; an X byte (bgr0 and the like) is the same call.  THE FOURTH BYTE IS NEVER
+ * INTERPRETED, AND NO CALL CHANGES IT.  A tap of the way in and a background pixel of the statistics are one aligned 32-bit load; a
+ * pasted pixel is one 32-bit load and one 32-bit store that carries the fourth byte as loaded.  Every region pixel is written by
+ * exactly one thread.  The sums are formed from the same byte values, in the same order, as by the packed entry points: every
+ * result is bit for bit that of the packed sibling on a copy of the colour bytes.
+ *
+ * spk_frames_rgb32_to_f32_sim, spk_frames_paste_rgb32_sim, spk_frames_paste_rgb32_sim_blend, spk_paste_colour_match_rgb32_sim,
+ * spk_paste_colour_sums_rgb32_sim: the arguments, launches and refusals of spk_frames_u8_to_f32_sim, spk_frames_paste_u8_sim,
+ *   spk_frames_paste_u8_sim_blend, spk_paste_colour_match_sim and spk_paste_colour_sums_sim, with alpha_first behind swap_rb and 4 W
+ *   where those say 3 W.  The workspace is spk_paste_colour_match_workspace_bytes'.  Refused on top, before any launch and before
+ *   anything is dereferenced: a base that is not 4-byte aligned; a row_stride (with N > 1: an image_stride) that is not a multiple
+ *   of 4; alpha_first outside {0, 1}.
+ * The four _rgb32_sim_table entry points: those of the frame table above over THE SAME 24-byte spk_frame_ref entries, with
+ *   alpha_first behind swap_rb.  An entry is USABLE when data != NULL, H >= 1, W >= 1, row_stride >= 4 W, row_stride % 4 == 0 and
+ *   data % 4 == 0; any other entry means the frame is absent, judged by the kernels before they form an address from it.
+ * spk_frame_table_check_rgb32: spk_frame_table_check with that predicate and the extent (H - 1) row_stride + 4 W: an all-zero entry
+ *   is an absent frame, any other entry that is not usable is half-formed and refused (a misaligned one included); with written != 0,
+ *   usable entries may not share a byte (ranges that touch are apart).
+ * replaces: a strip of the fourth byte into packed scratch frames in front of every tick and a scatter of three of every four bytes
+ *   behind it. */
+int spk_frames_rgb32_to_f32_sim(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int H, int W, const float* sim_dev,
+                                int swap_rb, int alpha_first, float* dst, int Hout, int Wout, float scale0, float scale1, float scale2,
+                                float shift0, float shift1, float shift2, void* stream);
+int spk_frames_paste_rgb32_sim(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W,
+                               const float* sim_dev, int swap_rb, int alpha_first, double feather, float lo, float k, void* stream);
+int spk_frames_paste_rgb32_sim_blend(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W,
+                                     const float* sim_dev, int swap_rb, int alpha_first, double feather, float lo, float k,
+                                     const float* matte_dev, int matte_frames, const float* colour_dev, void* stream);
+int spk_paste_colour_match_rgb32_sim(const float* src, int N, int Hs, int Ws, const uint8_t* dst, int64_t image_stride, int64_t row_stride, int H,
+                                     int W, const float* sim_dev, int swap_rb, int alpha_first, double feather, float lo, float k,
+                                     const float* matte_dev, int matte_frames, double max_gain, double min_sigma, double min_weight,
+                                     float* colour_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int spk_paste_colour_sums_rgb32_sim(const float* src, int N, int Hs, int Ws, const uint8_t* dst, int64_t image_stride, int64_t row_stride, int H,
+                                    int W, const float* sim_dev, int swap_rb, int alpha_first, double feather, float lo, float k,
+                                    const float* matte_dev, int matte_frames, double* sums_out_dev, void* workspace_dev, size_t workspace_bytes,
+                                    void* stream);
+int spk_frame_table_check_rgb32(const spk_frame_ref* host_table, int N, int written);
+int spk_frames_rgb32_to_f32_sim_table(const spk_frame_ref* table_dev, int N, const float* sim_dev, int swap_rb, int alpha_first, float* dst,
+                                      int Hout, int Wout, float scale0, float scale1, float scale2, float shift0, float shift1, float shift2,
+                                      void* stream);
+int spk_frames_paste_rgb32_sim_table(const float* src, int N, int Hs, int Ws, const spk_frame_ref* table_dev, const float* sim_dev, int swap_rb,
+                                     int alpha_first, double feather, float lo, float k, const float* matte_dev, int matte_frames,
+                                     const float* colour_dev, void* stream);
+int spk_paste_colour_match_rgb32_sim_table(const float* src, int N, int Hs, int Ws, const spk_frame_ref* table_dev, const float* sim_dev,
+                                           int swap_rb, int alpha_first, double feather, float lo, float k, const float* matte_dev,
+                                           int matte_frames, double max_gain, double min_sigma, double min_weight, float* colour_out_dev,
+                                           void* workspace_dev, size_t workspace_bytes, void* stream);
+int spk_paste_colour_sums_rgb32_sim_table(const float* src, int N, int Hs, int Ws, const spk_frame_ref* table_dev, const float* sim_dev,
+                                          int swap_rb, int alpha_first, double feather, float lo, float k, const float* matte_dev,
+                                          int matte_frames, double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- the aligned NV12 edge over a surface table: every surface its own planes, pitches and size (csrc/frame_table_nv12.hip) --------
  * What the frame table is to packed frames, for NV12: each call's hardware decoder delivers a surface of that call's own
  * resolution into that call's own buffer, and the encoder wants it back.  A surface is two planes with two pitches, so an entry

@@ -419,6 +419,29 @@ _PROTOTYPES = {
                                                    C.c_size_t, C.c_void_p]),
     "spk_paste_colour_sums_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_float,
                                                   C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_frames_rgb32_to_f32_sim": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_paste_rgb32_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p]),
+    "spk_frames_paste_rgb32_sim_blend": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+                                                   C.c_void_p]),
+    "spk_paste_colour_match_rgb32_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_double,
+                                                   C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_paste_colour_sums_rgb32_sim": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                  C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_frame_table_check_rgb32": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "spk_frames_rgb32_to_f32_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] +
+                                          [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_paste_rgb32_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                   C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "spk_paste_colour_match_rgb32_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                         C.c_double, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spk_paste_colour_sums_rgb32_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                        C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "spk_surface_table_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "spk_frames_nv12_to_f32_sim_table": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] +
                                          [C.c_float] * 6 + [C.c_void_p]),

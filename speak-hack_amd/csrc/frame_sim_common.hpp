@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void frames_paste_u8_sim_kernel(const float* _
         load_colour(matched ? colour : nullptr, n, g, o);
         for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
             const int X = x_lo + (int)(idx % bw), Y = y_lo + (int)(idx / bw);
-            uint8_t* out = out_frames.pixel(fr, n, X, Y);
+            const auto out = out_frames.pixel(fr, n, X, Y);      // what blend_pixel writes: packed bytes, or a format's own pixel
             if constexpr (SEAMLESS) {
                 float q[3];
                 double mm;

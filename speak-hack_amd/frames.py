@@ -2,7 +2,8 @@
 network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packed RGB through a similarity transform per frame
 (csrc/frame_sim.hip: aligned crops; csrc/frame_blend.hip: their paste with a face matte and a colour match; csrc/frame_sim_nv12.hip:
 all of that on NV12 surfaces; csrc/frame_table.hip: on frames in buffers and of sizes of their own; csrc/frame_table_nv12.hip: on
-NV12 surfaces in planes, of pitches and of sizes of their own), whose rows
+NV12 surfaces in planes, of pitches and of sizes of their own; csrc/frame_sim_rgb32.hip, csrc/frame_table_rgb32.hip: on RGB32
+frames, four bytes per pixel), whose rows
 csrc/landmark_sim.hip fits to landmarks and smooths; csrc/causal_filter.hip: the causal filters of a live feed, their state on
 the device).  ``ops`` re-exports the
 launchers (``ops.frames_from_u8`` ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
@@ -1863,6 +1864,213 @@ def paste_colour_sums_i420(x, i420, sim, *, matte=None, feather=0, value_range=(
     ``PlanarTable`` (``spk_paste_colour_sums_i420_sim_table``; 13 zeros for an absent surface).  -> device float64 ``[N,13]``."""
     return _colour_statistics(_i420_format(i420), None, "paste_colour_sums_i420", x, i420, sim, matte, feather, value_range, out, standard=standard,
                               full_range=full_range)
+
+
+# ---- RGB32: uint8 [H,W,4] frames, a pixel one aligned 32-bit word (csrc/frame_sim_rgb32.hip, csrc/frame_table_rgb32.hip) -----------
+RGB32_ORDERS = {"rgba": ("rgb", 0), "bgra": ("bgr", 0), "argb": ("rgb", 1), "abgr": ("bgr", 1)}
+
+
+def rgb32_order(channel_order):
+    """One of the four orders of an RGB32 pixel -> ``(the order of its colour bytes, "rgb" or "bgr"; alpha_first)``; an ``X`` byte in
+    the alpha's place is the same order.  Anything else raises ``ValueError``."""
+    if not isinstance(channel_order, str) or channel_order not in RGB32_ORDERS:
+        raise ValueError(f"channel_order must be one of {', '.join(repr(o) for o in RGB32_ORDERS)}, got {channel_order!r}")
+    return RGB32_ORDERS[channel_order]
+
+
+def _aligned32(t, row):                                                   # a tensor's base and the strides in front of ``row`` lead to aligned pixels
+    return t.data_ptr() % 4 == 0 and all(t.stride(d) % 4 == 0 for d in range(row + 1) if t.size(d) > 1 or d == row)
+
+
+def rgb32_pixels(frames):
+    """uint8 [N,H,W,4] whose pixels are aligned 32-bit words -- ``stride(3) == 1``, ``stride(2) == 4``, a row stride that is a multiple
+    of 4 and ``>= 4 W``, a 4-aligned ``data_ptr()`` (with ``N > 1``: a frame stride that is a multiple of 4) -- and whose rows / frames
+    do not overlap: what the kernels address by byte strides.  An ``Rgb32Table`` has such pixels by construction: its frames must
+    not share bytes (``SpkError`` names the two that do)."""
+    if isinstance(frames, Rgb32Table):
+        frames.check_written()
+        return True
+    N, H, W, _ = frames.shape
+    return frames.stride(3) == 1 and frames.stride(2) == 4 and frames.stride(1) >= 4 * W and _aligned32(frames, 1) and \
+        (N == 1 or frames.stride(0) >= (H - 1) * frames.stride(1) + 4 * W)
+
+
+class _Packed32(_Packed):
+    """``_Packed`` for RGB32 frames, uint8 ``[N,H,W,4]``: the same launchers over the ``_rgb32_sim`` entry points, which take
+    ``alpha_first`` behind the channel swap.  Frames that are only read and do not fit are made contiguous; frames that are written
+    and do not fit are refused."""
+    way_in, paste = "spk_frames_rgb32_to_f32_sim", "spk_frames_paste_rgb32_sim"
+    sums, match = "spk_paste_colour_sums_rgb32_sim", "spk_paste_colour_match_rgb32_sim"
+
+    def shaped(self, frames, N, what):                                    # N=None: any number, one frame may come as [H,W,4]; -> (frames, N, H, W)
+        if not isinstance(frames, torch.Tensor):
+            raise ValueError(f"{what}: frames must be a uint8 tensor [N,H,W,4] or an Rgb32Table, got {type(frames).__name__}")
+        if N is None and frames.dim() == 3:
+            frames = frames.unsqueeze(0)
+        if frames.dim() != 4 or frames.size(3) != 4 or (frames.size(0) < 1 if N is None else frames.size(0) != N):
+            raise ValueError(f"{what}: frames must be [{'N' if N is None else N},H,W,4], got {tuple(frames.shape)}")
+        return (frames, *frames.shape[:3])
+
+    def read(self, frames, what, disjoint=False):
+        self.on_device(frames)
+        N, _, W, _ = frames.shape
+        if not (rgb32_pixels(frames) if disjoint else frames.stride(3) == 1 and frames.stride(2) == 4 and frames.stride(1) >= 4 * W and
+                _aligned32(frames, 1) and (N == 1 or frames.stride(0) >= 0)):
+            frames = frames.contiguous()
+            if frames.data_ptr() % 4:                                     # (an allocator's block is aligned; a view into one need not be)
+                frames = frames.clone(memory_format=torch.contiguous_format)
+        return frames, (frames.data_ptr(), frames.stride(0) if N > 1 else 0, frames.stride(1))
+
+    def target(self, frames, out, N, H, W, device, what):
+        copy = out is not None and out is not frames and out.data_ptr() != frames.data_ptr()
+        if out is None:
+            out = frames.clone(memory_format=torch.contiguous_format)
+        elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames.shape):
+            raise L.SpkError(f"out: expected a uint8 HIP tensor {tuple(frames.shape)}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        if not rgb32_pixels(out):
+            raise L.SpkError(f"out: pixels must be aligned 32-bit words (strides (4 k, 4 k >= 4 W, 4, 1), a data pointer that is a multiple of "
+                             f"4) and rows / frames must not overlap, got strides {out.stride()} at {out.data_ptr():#x}")
+        return out, (out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1)), (lambda: out.copy_(frames)) if copy else (lambda: None)
+
+    def standard(self, alpha_first=0):
+        return (alpha_first,)
+
+    def quantised(self, value_range, channel_order="rgb", alpha_first=0):
+        return ((_channel_swap(channel_order), alpha_first), *quant_range(value_range))
+
+
+_PACKED32 = _Packed32()
+
+
+class Rgb32Table(_DeviceTable):
+    """``FrameTable`` for RGB32 frames: ``N`` uint8 frames ``[H_n,W_n,4]`` that share neither an allocation nor a size, as the aligned
+    RGB32 launchers address them -- a device table of the same 24-byte ``spk_frame_ref`` entries ``(data, row_stride, H, W)``.
+    ``frames``: a sequence of device uint8 tensors ``[H_n,W_n,4]`` on one device, each with ``stride(2) == 1``, ``stride(1) == 4``, a
+    ``stride(0)`` that is a multiple of 4 and ``>= 4 W_n`` and a 4-aligned ``data_ptr()`` -- a region-of-interest view at any pixel
+    offset of a wider surface is fine -- with ``None`` for a frame that is ABSENT (an all-zero entry: the launchers treat it like an
+    invalid transform); or one ``[N,H,W,4]`` tensor, which gives views of its frames.  Wrong types, shapes or strides raise
+    ``ValueError`` before a device is touched; CPU tensors raise ``SpkError`` (no CPU path).  The host table is checked
+    (``spk_frame_table_check_rgb32``) here and uploaded ONCE, one host -> device copy of ``24 N`` bytes on the current stream, when a
+    launcher first uses the table; whether the frames may be written is decided where the table is used (``check_written``: the
+    paste).  The table HOLDS REFERENCES to the tensors.
+
+    ``dev``: the device table (uint8 ``[24 N]``); ``sizes``: ``(H, W)`` per frame (``(0, 0)``: absent); ``frames``: the tensors."""
+
+    def __init__(self, frames):
+        what = "Rgb32Table"
+        if isinstance(frames, torch.Tensor):
+            if frames.dim() != 4 or frames.size(0) < 1:
+                raise ValueError(f"{what}: a tensor of frames must be [N,H,W,4], got {tuple(frames.shape)}")
+            frames = list(frames.unbind(0))
+        else:
+            try:
+                frames = list(frames)
+            except TypeError:
+                raise ValueError(f"{what}: frames must be a sequence of uint8 tensors [H,W,4] or a tensor [N,H,W,4], got "
+                                 f"{type(frames).__name__}") from None
+        if not frames:
+            raise ValueError(f"{what}: a table needs at least one frame")
+        for n, f in enumerate(frames):
+            if f is None:
+                continue
+            if not isinstance(f, torch.Tensor):
+                raise ValueError(f"{what}: frames[{n}] must be a uint8 tensor [H,W,4] or None, got {type(f).__name__}")
+            if f.dtype != torch.uint8 or f.dim() != 3 or f.size(2) != 4 or f.size(0) < 1 or f.size(1) < 1:
+                raise ValueError(f"{what}: frames[{n}] must be a uint8 tensor [H,W,4] with H, W >= 1, got {f.dtype} {tuple(f.shape)}")
+            if f.stride(2) != 1 or f.stride(1) != 4 or f.stride(0) < 4 * f.size(1) or f.stride(0) % 4:
+                raise ValueError(f"{what}: frames[{n}]: pixels must be 4 bytes apart and rows a multiple of 4 bytes apart that do not overlap "
+                                 f"(strides (4 k >= {4 * f.size(1)}, 4, 1)), got {f.stride()}")
+            if f.data_ptr() % 4:
+                raise ValueError(f"{what}: frames[{n}]: the first pixel must be aligned to 4 bytes, got data_ptr() = {f.data_ptr():#x}")
+        there = [f for f in frames if f is not None]
+        if any(not f.is_cuda for f in there):
+            raise L.SpkError(f"{what}: expected uint8 HIP tensors, got a frame on the CPU (no CPU path)")
+        if any(f.device != there[0].device for f in there):
+            raise L.SpkError(f"{what}: the frames must be on one device, got {sorted({str(f.device) for f in there})}")
+        self.frames, self.N = frames, len(frames)
+        self.sizes = [(0, 0) if f is None else (f.size(0), f.size(1)) for f in frames]
+        self._host = (L.FrameRef * self.N)()
+        for e, f in zip(self._host, frames):
+            if f is not None:
+                e.data, e.row_stride, e.H, e.W = f.data_ptr(), f.stride(0), f.size(0), f.size(1)
+        self._checked("spk_frame_table_check_rgb32", there[0].device if there else None)
+
+
+class _Tabled32(_Tabled):
+    """``_Packed32`` for an ``Rgb32Table`` (csrc/frame_table_rgb32.hip)"""
+    noun = "RGB32 table"
+    way_in, paste = "spk_frames_rgb32_to_f32_sim_table", "spk_frames_paste_rgb32_sim_table"
+    sums, match = "spk_paste_colour_sums_rgb32_sim_table", "spk_paste_colour_match_rgb32_sim_table"
+
+    def standard(self, alpha_first=0):
+        return (alpha_first,)
+
+    def quantised(self, value_range, channel_order="rgb", alpha_first=0):
+        return _PACKED32.quantised(value_range, channel_order, alpha_first)
+
+
+_TABLED32 = _Tabled32()
+
+
+def _rgb32_format(frames):
+    return _TABLED32 if isinstance(frames, Rgb32Table) else _PACKED32
+
+
+def clone_rgb32(frames):
+    """A contiguous copy of the RGB32 frames to paste into, ``clone_frames`` for ``[.,.,.,4]``: one clone of a tensor; of an
+    ``Rgb32Table`` a new table over one clone per frame"""
+    if isinstance(frames, Rgb32Table):
+        return Rgb32Table([None if f is None else f.clone(memory_format=torch.contiguous_format) for f in frames.frames])
+    return frames.clone(memory_format=torch.contiguous_format)
+
+
+def frames_from_rgb32_aligned(frames, size, sim, *, channel_order="rgba", mean=0.5, std=0.5):
+    """``frames_from_u8_aligned`` for RGB32 frames, one launch (``spk_frames_rgb32_to_f32_sim``): the same footprint, weights and
+    arguments, a tap one aligned 32-bit load, and the fp32 BITS that launcher gives on a packed copy of the colour bytes.
+    ``frames``: uint8 ``[N,H,W,4]`` (one frame: ``[H,W,4]``) on the device, read in place through its strides when its pixels are
+    aligned words (``rgb32_pixels`` without the overlap rule; a region-of-interest view at any pixel offset is), else through a
+    contiguous copy.  ``channel_order``: ``"rgba"``, ``"bgra"``, ``"argb"`` or ``"abgr"``, the bytes of a pixel in memory order (an
+    ``X`` byte counts as the ``a``; it is never interpreted); the network gets R, G, B planes.  ``frames`` may be an ``Rgb32Table``:
+    frames of their own sizes in their own buffers, still one launch (``spk_frames_rgb32_to_f32_sim_table``), frame ``n`` bit for bit
+    this call on frame ``n`` alone; an absent frame gives ``-mean / std``.  -> float32 [N,3,size,size]."""
+    order, alpha_first = rgb32_order(channel_order)
+    return _from_aligned(_rgb32_format(frames), "frames_from_rgb32_aligned", frames, size, sim, order, mean, std, alpha_first=alpha_first)
+
+
+def frames_paste_rgb32_aligned(x, frames, sim, *, feather=0, value_range=(-1, 1), channel_order="rgba", out=None, matte=None, colour=None):
+    """``frames_paste_u8_aligned`` for RGB32 frames, one launch (``spk_frames_paste_rgb32_sim``, with ``matte`` / ``colour``
+    ``spk_frames_paste_rgb32_sim_blend``): the same region, values, ``feather``, ``matte`` and ``colour`` rows and the same blend; a
+    pasted pixel is one 32-bit load and one 32-bit store, its colour bytes those the packed launcher leaves on a packed copy, ITS
+    FOURTH BYTE AS IT WAS.  ``out=None``: a contiguous clone of ``frames`` (alpha included) is pasted into; ``out=frames``: in place;
+    another ``out`` first receives a copy.  Frames that are written must have aligned pixels and must not overlap
+    (``rgb32_pixels``), else ``SpkError``.  -> uint8 [N,H,W,4].
+
+    ``frames`` may be an ``Rgb32Table`` (``spk_frames_paste_rgb32_sim_table``, one launch): the paste is then IN PLACE, into the
+    table's own frames (``out``: None or the table), which must not share bytes; an absent frame is left alone.  -> the table."""
+    order, alpha_first = rgb32_order(channel_order)
+    return _paste_aligned(_rgb32_format(frames), "frames_paste_rgb32_aligned", x, frames, sim, feather, value_range, out, matte, colour,
+                          channel_order=order, alpha_first=alpha_first)
+
+
+def paste_colour_match_rgb32(x, frames, sim, *, matte=None, feather=0, value_range=(-1, 1), channel_order="rgba", max_gain=2.0, min_sigma=1.0,
+                             min_weight=16.0, out=None):
+    """``paste_colour_match`` for an RGB32 background, two launches (``spk_paste_colour_match_rgb32_sim``): the same rows, bit for
+    bit, as on a packed copy of the colour bytes.  ``frames`` is only read, and may be an ``Rgb32Table``
+    (``spk_paste_colour_match_rgb32_sim_table``; an absent frame gets ``(1, 0)``).  -> device float32 ``[N,3,2]``."""
+    what = "paste_colour_match_rgb32"
+    order, alpha_first = rgb32_order(channel_order)
+    params = _check_match_params(what, max_gain, min_sigma, min_weight)
+    return _colour_statistics(_rgb32_format(frames), params, what, x, frames, sim, matte, feather, value_range, out, channel_order=order,
+                              alpha_first=alpha_first)
+
+
+def paste_colour_sums_rgb32(x, frames, sim, *, matte=None, feather=0, value_range=(-1, 1), channel_order="rgba", out=None):
+    """``paste_colour_sums`` for an RGB32 background, two launches (``spk_paste_colour_sums_rgb32_sim``): the same 13 sums per frame,
+    bit for bit, so ``colour_rows_from_sums`` and the causal rows serve every pixel format.  ``frames`` may be an ``Rgb32Table``
+    (``spk_paste_colour_sums_rgb32_sim_table``; 13 zeros for an absent frame).  -> device float64 ``[N,13]``."""
+    order, alpha_first = rgb32_order(channel_order)
+    return _colour_statistics(_rgb32_format(frames), None, "paste_colour_sums_rgb32", x, frames, sim, matte, feather, value_range, out,
+                              channel_order=order, alpha_first=alpha_first)
 
 
 def generated_row_scale(size, Ws, device):

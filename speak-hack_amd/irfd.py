@@ -363,7 +363,15 @@ class IRFD(nn.Module):
         three planes, each with a base and a pitch of its own -- in the colour of ``standard`` / ``full_range``.  ``step`` takes one
         contiguous packed tensor ``[N,3H/2,W]`` or a triple of planes (``ops.i420_planes``); steps 3, 8 and 9 are
         ``ops.frames_from_i420_aligned``, ``ops.paste_colour_sums_i420`` and ``ops.frames_paste_i420_aligned`` -- no interleaving into a
-        scratch NV12 surface -- and the bytes and every state are those of the NV12 session on the interleaved surfaces."""
+        scratch NV12 surface -- and the bytes and every state are those of the NV12 session on the interleaved surfaces.
+
+        ``pixel_format="rgb32"``: the feed is four bytes per pixel as a capture surface, an interop texture or an ARGB buffer holds it,
+        and ``channel_order`` is one of ``"rgba"``, ``"bgra"``, ``"argb"``, ``"abgr"`` (an ``X`` byte counts as the ``a``).  ``step`` takes
+        uint8 ``[N,H,W,4]`` whose pixels are aligned 32-bit words (``ops.frames_from_rgb32_aligned``); steps 3, 8 and 9 are
+        ``ops.frames_from_rgb32_aligned``, ``ops.paste_colour_sums_rgb32`` and ``ops.frames_paste_rgb32_aligned`` -- no strip of the
+        alpha into scratch frames -- and the colour bytes and every state are those of the rgb24 session on the stripped feed; the
+        fourth byte of every pixel is left as it was.  The identity photo stays a packed ``[H,W,3]`` photo in the colour order with the
+        alpha dropped (``rgba`` / ``argb``: ``rgb``; ``bgra`` / ``abgr``: ``bgr``).  ``standard`` / ``full_range`` are refused."""
         from .live import LiveSession
         return LiveSession(self, identity_u8, size=size, template=template, contour=contour, channel_order=channel_order,
                            identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,
@@ -395,7 +403,11 @@ class IRFD(nn.Module):
 
         ``pixel_format="i420"``: the same for I420 -- ``[S,3H/2,W]`` packed and contiguous or a triple of planes, or a list / tuple of
         ``S`` surfaces of ``S`` sizes (packed tensors or triples of plane views) or an ``ops.PlanarTable``: the three ``_i420_sim_table``
-        entry points of csrc/frame_table_i420.hip plus one upload of ``56 S`` bytes per table."""
+        entry points of csrc/frame_table_i420.hip plus one upload of ``56 S`` bytes per table.
+
+        ``pixel_format="rgb32"`` (``channel_order``: as ``live``): ``room.step`` takes ``[S,H,W,4]``, or a list / tuple of ``S`` frames
+        ``[H_s,W_s,4]`` of ``S`` sizes (region-of-interest views at any pixel offset included) or an ``ops.Rgb32Table``: the three
+        ``_rgb32_sim_table`` entry points of csrc/frame_table_rgb32.hip plus one upload of ``24 S`` bytes per table."""
         from .live import LiveRoom
         return LiveRoom(self, identities_u8, size=size, template=template, contour=contour, channel_order=channel_order,
                         identity_align=identity_align, rate=rate, track=track, features=features, feather=feather,

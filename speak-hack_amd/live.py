@@ -4,8 +4,9 @@ landmarks, the matte's contour and the colour statistics with windows over frame
 keeps ``fi``, and steadies the same three things with the causal filters of csrc/causal_filter.hip, whose state lives in device
 tensors on the session: ``step`` reads no device value on the host, and ``N`` frames in one ``step`` and the same frames in any split
 of steps give the same bytes.  The feed is packed RGB, (``pixel_format="nv12"``) NV12 surfaces as a hardware decoder leaves them or
-(``pixel_format="i420"``) the three planes of a software decoder or a WebRTC frame buffer: the pixel format decides which launchers
-read and write the frames (``_Rgb24Edge`` / ``_Nv12Edge`` / ``_I420Edge``), and nothing else.
+(``pixel_format="i420"``) the three planes of a software decoder or a WebRTC frame buffer, or (``pixel_format="rgb32"``) four bytes per pixel
+as a capture surface or an interop texture holds them: the pixel format decides which launchers read and write the frames
+(``_Rgb24Edge`` / ``_Nv12Edge`` / ``_I420Edge`` / ``_Rgb32Edge``), and nothing else.
 
 ``IRFD.live_room``: S such feeds at once -- a server with several calls -- as ONE batch per tick (``LiveRoom``): the frames of a tick
 are the batch rows of the same launches a session makes, with the state of every feed, its frame counter and its seed on the device."""
@@ -41,7 +42,7 @@ def _check_identity(what, name, identity_u8):
 
 class _Rgb24Edge:
     """What a step asks of packed uint8 frames in ``channel_order``: a tensor ``[N,H,W,3]``, or a ``FrameTable``"""
-    surfaces, table, noun, shape = False, FR.FrameTable, "frames [H,W,3]", "[{},H,W,3]"
+    surfaces, table, noun, shape, channels = False, FR.FrameTable, "frames [H,W,3]", "[{},H,W,3]", 3
     way_in, sums, paste, clone = (staticmethod(f) for f in (FR.frames_from_u8_aligned, FR.paste_colour_sums, FR.frames_paste_u8_aligned,
                                                             FR.clone_frames))
 
@@ -57,6 +58,27 @@ class _Rgb24Edge:
 
     def present(self, table):
         return table.frames
+
+    def ready(self, what, name, frames, device):                          # a packed tensor takes exactly the path it always took
+        pass
+
+
+class _Rgb32Edge(_Rgb24Edge):
+    """The same of RGB32 frames in one of the four orders of ``frames.RGB32_ORDERS``: a tensor ``[N,H,W,4]``, or an ``Rgb32Table``.
+    The fourth byte of a pixel is neither read into the network nor changed by the paste."""
+    table, noun, shape, channels = FR.Rgb32Table, "frames [H,W,4]", "[{},H,W,4]", 4
+    way_in, sums, paste, clone = (staticmethod(f) for f in (FR.frames_from_rgb32_aligned, FR.paste_colour_sums_rgb32,
+                                                            FR.frames_paste_rgb32_aligned, FR.clone_rgb32))
+
+    def writable(self, what, frames):
+        if not FR.rgb32_pixels(frames):
+            raise L.SpkError(f"{what}: inplace needs pixels that are aligned 32-bit words (a data pointer and strides that are multiples of 4) "
+                             f"and rows / frames that do not overlap, got strides {frames.stride()} at {frames.data_ptr():#x}")
+
+    def ready(self, what, name, frames, device):
+        """What the launchers would refuse of a tensor of frames, asked before the first launch of a step"""
+        if not frames.is_cuda or frames.dtype != torch.uint8 or frames.device != device:
+            raise L.SpkError(f"{what}: {name}: expected a uint8 HIP tensor on {device}, got {frames.dtype} on {frames.device} (no CPU path)")
 
 
 class _Nv12Edge:
@@ -115,7 +137,7 @@ class _I420Edge(_Nv12Edge):
         return FR.plane_triple(frames, one=S == 1)
 
 
-_EDGES = {"rgb24": _Rgb24Edge, "nv12": _Nv12Edge, "i420": _I420Edge}
+_EDGES = {"rgb24": _Rgb24Edge, "nv12": _Nv12Edge, "i420": _I420Edge, "rgb32": _Rgb32Edge}
 
 
 class _Live:
@@ -127,11 +149,14 @@ class _Live:
     def _configure(self, what, model, *, size, template, contour, channel_order, rate, track, features, feather, matte_softness, matte_grow,
                    colour_match, colour_decay, offset, pixel_format, standard, full_range):
         self.size = FR._out_size(size, what)
-        FR._channel_swap(channel_order)
-        self.channel_order = channel_order
+        if pixel_format == "rgb32":                                        # the identity photo: the colour order with the alpha dropped
+            self.channel_order = FR.rgb32_order(channel_order)[0]
+        else:
+            FR._channel_swap(channel_order)
+            self.channel_order = channel_order
         if pixel_format not in _EDGES:
-            raise ValueError(f"{what}: pixel_format must be 'rgb24' or 'nv12' or 'i420', got {pixel_format!r}")
-        if pixel_format == "rgb24" and (standard != "bt601" or full_range):
+            raise ValueError(f"{what}: pixel_format must be 'rgb24' or 'nv12' or 'i420' or 'rgb32', got {pixel_format!r}")
+        if pixel_format in ("rgb24", "rgb32") and (standard != "bt601" or full_range):
             raise ValueError(f"{what}: standard / full_range apply to pixel_format='nv12' only, and to 'i420'")
         FR.yuv_standard(standard, full_range)
         self.pixel_format, self.edge = pixel_format, _EDGES[pixel_format](channel_order, standard, full_range)
@@ -210,7 +235,7 @@ class _Live:
             raise ValueError(f"{what}: emotion_u8 must match the frames {tuple(frames_u8.shape)}")
         if not isinstance(inplace, bool):
             raise ValueError(f"{what}: inplace must be a bool, got {inplace!r}")
-        if edge.surfaces and not isinstance(frames_u8, edge.table):
+        if not isinstance(frames_u8, edge.table):
             edge.ready(what, "frames", frames_u8, self.device)
             if emotion_u8 is not None:
                 edge.ready(what, "emotion_u8", emotion_u8, self.device)
@@ -330,15 +355,21 @@ class LiveSession(_Live):
 
         ``pixel_format="i420"``: the same with ``ops.i420_planes`` in place of ``ops.nv12_planes`` -- one contiguous packed tensor
         ``[N,3H/2,W]`` or a triple of planes ``(y, u, v)`` of any pitches -- and the Y, U and V bytes of the NV12 session on the
-        interleaved surfaces."""
+        interleaved surfaces.
+
+        ``pixel_format="rgb32"``: ``frames_u8`` (and ``emotion_u8``) is uint8 ``[N,H,W,4]`` in the session's ``channel_order``
+        (``"rgba"``, ``"bgra"``, ``"argb"``, ``"abgr"``), read in place where its pixels are aligned 32-bit words
+        (``ops.frames_from_rgb32_aligned``), else through a copy.  -> a contiguous clone ``[N,H,W,4]`` with the face pasted in;
+        ``inplace=True``: the input itself, which then needs aligned pixels and frames that do not overlap.  The colour bytes are
+        those of the rgb24 session on the stripped feed; the fourth byte of every pixel is what it was."""
         what = "live.step"
         given = frames_u8
         if self.edge.surfaces:
             frames_u8 = self.edge.open(what, "frames", frames_u8)
             N = frames_u8[0].size(0)
-        elif not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) < 1:
+        elif not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != self.edge.channels or frames_u8.size(0) < 1:
             got = tuple(frames_u8.shape) if isinstance(frames_u8, torch.Tensor) else type(frames_u8).__name__
-            raise ValueError(f"{what}: frames must be [N,H,W,3], got {got}")
+            raise ValueError(f"{what}: frames must be [N,H,W,{self.edge.channels}], got {got}")
         else:
             N = frames_u8.size(0)
         if not isinstance(landmarks, torch.Tensor) or tuple(landmarks.shape) != (N, self.K, 2):
@@ -534,7 +565,13 @@ class LiveRoom(_Live):
         ``S`` sizes (each a contiguous packed ``[3H/2,W]`` tensor or a triple of plane views of any pitch, odd ones included; a region
         of interest at even luma offsets is such a triple) or an ``ops.PlanarTable``: the three ``_i420_sim_table`` entry points of
         csrc/frame_table_i420.hip plus one upload of ``56 S`` bytes per table.  The returns are NV12's; the bytes and every state are
-        those of the NV12 room on the interleaved surfaces."""
+        those of the NV12 room on the interleaved surfaces.
+
+        ``pixel_format="rgb32"``: ``frames_u8`` is ``[S,H,W,4]`` -- the strided RGB32 launchers -- or a list / tuple of ``S`` tensors
+        ``[H_s,W_s,4]`` (pixels aligned 32-bit words, any row pitch that is a multiple of 4: a region of interest at any pixel
+        offset of a wider surface is one) or an ``ops.Rgb32Table``: the three ``_rgb32_sim_table`` entry points of
+        csrc/frame_table_rgb32.hip plus one upload of ``24 S`` bytes per table.  The returns are rgb24's; the colour bytes and every
+        state are those of the rgb24 room on the stripped feeds, and no fourth byte changes."""
         what = "live_room.step"
         S, K = self.S, self.K
         given = frames_u8
@@ -543,11 +580,11 @@ class LiveRoom(_Live):
                 frames_u8 = self._table(what, "frames", frames_u8)
             else:
                 frames_u8 = self.edge.open(what, "frames", frames_u8, S)
-        elif isinstance(frames_u8, (list, tuple, FR.FrameTable)):
+        elif isinstance(frames_u8, (list, tuple, self.edge.table)):
             frames_u8 = self._table(what, "frames", frames_u8)
-        elif not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != 3 or frames_u8.size(0) != S:
+        elif not isinstance(frames_u8, torch.Tensor) or frames_u8.dim() != 4 or frames_u8.size(3) != self.edge.channels or frames_u8.size(0) != S:
             got = tuple(frames_u8.shape) if isinstance(frames_u8, torch.Tensor) else type(frames_u8).__name__
-            raise ValueError(f"{what}: frames must be [{S},H,W,3], one frame per feed, got {got}")
+            raise ValueError(f"{what}: frames must be [{S},H,W,{self.edge.channels}], one frame per feed, got {got}")
         if not isinstance(landmarks, torch.Tensor) or tuple(landmarks.shape) != (S, K, 2):
             got = tuple(landmarks.shape) if isinstance(landmarks, torch.Tensor) else type(landmarks).__name__
             raise ValueError(f"{what}: landmarks must be [{S},{K},2], {K} points per feed as the template has, got {got}")
@@ -558,7 +595,7 @@ class LiveRoom(_Live):
         out = self._body(what, frames_u8, landmarks, weights, emotion_u8, inplace)
         if not self.fixed_noise:
             self.frames.add_(1)
-        if isinstance(out, FR.FrameTable):                                 # in place: the caller's own list, or the table's tensors
+        if isinstance(out, (FR.FrameTable, FR.Rgb32Table)):                # in place: the caller's own list, or the table's tensors
             return given if inplace and isinstance(given, list) else list(out.frames)
         if isinstance(out, (FR.SurfaceTable, FR.PlanarTable)):             # the same of surfaces, as they were given
             return given if inplace and isinstance(given, list) else list(out.surfaces)

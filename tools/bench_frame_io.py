@@ -81,6 +81,11 @@
     room on a planar table, the detour it replaces (interleave into scratch NV12 surfaces, the NV12 room, split and copy back) and
     the NV12 room alone; then the three I420 launchers beside their NV12 siblings.  Written to profiles/live_i420_bench.txt.
 
+``--live-rgb32``: the same tick, S = 1 and S = 8, where capture surfaces left BGRA frames, each an allocation of its own: the RGB32
+    room on an ``Rgb32Table``, the detour it replaces (strip into contiguous rgb24 scratch frames, the rgb24 room, write the three
+    colour bytes back) and the rgb24 room alone; then the four RGB32 launchers beside their rgb24 siblings.  Written to
+    profiles/live_rgb32_bench.txt; reported, not gated.
+
 ``--i420``: the axis-aligned I420 edge with the settings of ``--nv12``: ``frames_from_i420``, ``frames_to_i420`` and
     ``frames_paste_i420`` each beside its NV12 sibling on the interleaved surfaces, and ``reenact_video(pixel_format="i420",
     paste=True)`` beside the detour it replaces (interleave, ``pixel_format="nv12"``, split and copy back, chunk by chunk).  Written to
@@ -1252,6 +1257,122 @@ def bench_live_i420(args, lines):
         ratio_table(lines, f"{title}: {shape}; {note}; {how}", alternate(contenders, args.repeats, device_time), name, [(sibling, False)])
 
 
+def bench_live_rgb32(args, lines):
+    """``--live-rgb32``: one TICK of a server with S calls whose capture surfaces are S BGRA frames of 1080 x 1920, each an allocation
+    of its own, S in {1, 8} (the pictures, landmarks, settings and method of ``--live-i420``), in place, three ways.  (q) the RGB32
+    room on the list of frames: an ``Rgb32Table``.  (d) the detour a caller has today: per feed, strip the frame into a contiguous
+    rgb24 scratch frame, step the rgb24 room on the list of scratch frames, write the three colour bytes of every pixel back.  (b)
+    the rgb24 room on BGR frames of the same pictures: the cost with no detour at all.  The contenders alternate in one process, (q)
+    entered twice for the spread; the colour bytes of a first tick of (q) and (d) are compared, and the alpha bytes of (q) with what
+    they were.  Then the four launchers beside their rgb24 siblings at 8 x 1080 x 1920 (HIP events, the method of ``--align-nv12``):
+    one 32-bit access per pixel against three byte accesses.  Nothing is gated: the figures are reported."""
+    T, per, sizes = 8, 20, (1, 8)
+    sc = live_scene(T)
+    ops, dev, m, template, contour, lm, ident, video, common = (sc[k] for k in ("ops", "dev", "m", "template", "contour", "lm", "ident", "video", "common"))
+    size, Hf, Wf, K = (sc[k] for k in ("size", "Hf", "Wf", "K"))
+    kw = dict(common, template=template, contour=contour, features={})
+    del kw["seed"]
+    kw32 = dict(kw, pixel_format="rgb32", channel_order="bgra")
+    g = torch.Generator().manual_seed(1)
+    alpha = torch.randint(0, 255, (T, Hf, Wf, 1), generator=g, dtype=torch.uint8).to(dev)
+    bgra = torch.cat([video, alpha], 3)                                    # the pictures as a capture surface would hold them
+    lines.append(f"a tick of S feeds of {Hf}x{Wf} BGRA, every frame an allocation of its own, in place, K = {K} landmarks, outline of "
+                 f"{len(contour)}, {size}^2 in and out, feather {sc['feather']}, matte, colour match and the three filters; median of "
+                 f"{args.repeats} alternating rounds of {per} ticks after {args.warmup + 1} warm-up ticks per contender")
+
+    def latency(fn):                                                       # the mean wall clock of `per` ticks, each synchronised on its own
+        total = 0.0
+        for i in range(per):
+            total += wall(lambda: fn(i % T))
+        return total / per
+
+    def host_cost(make, n=200):                                            # build, check and upload of one table, per call
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            make().dev
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n
+
+    for S in sizes:
+        show = torch.tensor([[(t + s) % T for s in range(S)] for t in range(T)], device=dev)
+        lms = lm[show].contiguous()                                        # feed s shows picture (t + s) % T in tick t
+        wide = [[bgra[(t + s) % T].clone() for s in range(S)] for t in range(T)]                 # per tick S allocations
+        detour = [[bgra[(t + s) % T].clone() for s in range(S)] for t in range(T)]
+        bgr = [[video[(t + s) % T].clone() for s in range(S)] for t in range(T)]
+        scratch = [torch.empty_like(video[0]) for _ in range(S)]           # the detour's rgb24 frames, allocated once
+        seeds = list(range(7, 7 + S))
+        rooms = {"q": m.live_room([ident] * S, seed=seeds, **kw32), "d": m.live_room([ident] * S, seed=seeds, **kw),
+                 "b": m.live_room([ident] * S, seed=seeds, **kw)}
+
+        def tick_rgb32(t):
+            return rooms["q"].step(wide[t], lms[t], inplace=True)
+
+        def tick_detour(t):
+            for f, s in zip(detour[t], scratch):
+                s.copy_(f[..., :3])
+            rooms["d"].step(scratch, lms[t], inplace=True)
+            for f, s in zip(detour[t], scratch):
+                f[..., :3].copy_(s)
+            return detour[t]
+
+        def tick_bgr(t):
+            return rooms["b"].step(bgr[t], lms[t], inplace=True)
+
+        # the bytes of a first tick, on fresh frames and fresh rooms' states
+        first_q, first_d = [f.clone() for f in tick_rgb32(0)], [f.clone() for f in tick_detour(0)]
+        differ = sum(int((a[..., :3] != b[..., :3]).sum()) for a, b in zip(first_q, first_d))
+        alpha_moved = sum(int((a[..., 3] != bgra[s % T][..., 3]).sum()) for s, a in enumerate(first_q))
+        pasted = sum(int((a[..., :3] != bgra[s % T][..., :3]).any(-1).sum()) for s, a in enumerate(first_q))
+        for r in rooms.values():
+            r.reset()
+        names = (f"(q) RGB32 LiveRoom.step on a list of {S} BGRA frames", f"(d) {S} x strip, rgb24 step on the scratch list, {S} x write back",
+                 f"(b) rgb24 step on a list of {S} BGR frames")
+        contenders = {names[0]: tick_rgb32, names[1]: tick_detour, names[2]: tick_bgr, names[0] + " (again)": tick_rgb32}
+        for fn in contenders.values():
+            for t in range(args.warmup + 1):
+                fn(t)
+        times = alternate(contenders, args.repeats, latency)
+        ratio_table(lines, f"S = {S}: wall clock per tick, synchronised before and after each tick:", times, names[0], [(names[1], True), (names[2], False)])
+        table32 = host_cost(lambda: ops.Rgb32Table(wide[0]))
+        table24 = host_cost(lambda: ops.FrameTable(bgr[0]))
+        lines.append(f"  host cost of a table of {S} (build, check, upload): Rgb32Table {table32 * 1e6:.1f} us, FrameTable {table24 * 1e6:.1f} us")
+        lines.append(f"  a first tick: colour bytes that differ between (q) and (d): {differ} of {sum(3 * a[..., 0].numel() for a in first_q)}; alpha bytes "
+                     f"of (q) that moved: {alpha_moved}; pixels (q) pasted: {pasted}")
+
+    # ---- the four launchers beside their rgb24 siblings ----
+    chunk, side, feather = args.chunk, 400, 16
+    g = torch.Generator().manual_seed(0)
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(chunk)]
+    rows = ops.similarity_rows([(y + side / 2, x + side / 2) for y, x in boxes], float(side), [0.3 * math.sin(0.9 * t) for t in range(chunk)], size).to(dev)
+    packed = torch.randint(0, 256, (chunk, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    frames = torch.cat([packed, torch.randint(0, 255, (chunk, Hf, Wf, 1), generator=g, dtype=torch.uint8).to(dev)], 3)
+    x = (torch.randn(chunk, 3, size, size, generator=g) * 0.7).to(dev)
+    matte = ops.ellipse_matte((size, size), device=dev)
+    stat = dict(matte=matte, feather=feather)
+    o32, o24 = dict(channel_order="bgra"), dict(channel_order="bgr")
+    shape = f"{chunk} x {Hf}x{Wf}, {size}^2, s = {side}/{size}, angles within +-0.3 rad"
+    how = f"HIP events, launcher included, median of {args.repeats} alternating rounds of 20 after 3 warm-up calls"
+    same = torch.equal(ops.frames_from_rgb32_aligned(frames, size, rows, **o32), ops.frames_from_u8_aligned(packed, size, rows, **o24))
+    sums_q, sums_b = ops.paste_colour_sums_rgb32(x, frames, rows, **stat, **o32), ops.paste_colour_sums(x, packed, rows, **stat, **o24)
+    same_sums = torch.equal(sums_q, sums_b)
+    colour = ops.paste_colour_match(x, packed, rows, **stat, **o24)
+    pairs = (("way in", "frames_from_rgb32_aligned", lambda: ops.frames_from_rgb32_aligned(frames, size, rows, **o32), "frames_from_u8_aligned",
+              lambda: ops.frames_from_u8_aligned(packed, size, rows, **o24), f"the same bits: {same}"),
+             ("statistics", "paste_colour_sums_rgb32", lambda: ops.paste_colour_sums_rgb32(x, frames, rows, out=sums_q, **stat, **o32), "paste_colour_sums",
+              lambda: ops.paste_colour_sums(x, packed, rows, out=sums_b, **stat, **o24), f"ellipse matte, feather {feather}; the same sums: {same_sums}"),
+             ("way out, plain", "frames_paste_rgb32_aligned", lambda: ops.frames_paste_rgb32_aligned(x, frames, rows, feather=feather, out=frames, **o32),
+              "frames_paste_u8_aligned", lambda: ops.frames_paste_u8_aligned(x, packed, rows, feather=feather, out=packed, **o24),
+              f"feather {feather}, in place"),
+             ("way out, seamless", "frames_paste_rgb32_aligned(matte, colour)",
+              lambda: ops.frames_paste_rgb32_aligned(x, frames, rows, colour=colour, out=frames, **stat, **o32), "frames_paste_u8_aligned(matte, colour)",
+              lambda: ops.frames_paste_u8_aligned(x, packed, rows, colour=colour, out=packed, **stat, **o24),
+              f"ellipse matte, colour rows, feather {feather}, in place"))
+    for title, name, ours, sibling, theirs, note in pairs:
+        contenders = {name: ours, sibling: theirs, name + " (again)": ours}
+        ratio_table(lines, f"{title}: {shape}; {note}; {how}", alternate(contenders, args.repeats, device_time), name, [(sibling, False)])
+
+
 def packed_i420(ops, nv12):
     """NV12 surfaces [N,3H/2,W] -> the contiguous packed I420 tensor [N,3H/2,W] with the same Y, U and V bytes"""
     y, uv = ops.nv12_planes(nv12)
@@ -1404,9 +1525,16 @@ def main():
                     "list beside the NV12 -> BGR -> NV12 detour around the rgb24 room and beside the rgb24 room alone; one mixed-size row")
     ap.add_argument("--live-i420", action="store_true", help="a tick of S live feeds of I420 surfaces, every plane an allocation of its own: the I420 room "
                     "on the list beside interleave + NV12 room + split and beside the NV12 room alone; the three launchers beside their NV12 siblings")
+    ap.add_argument("--live-rgb32", action="store_true", help="a tick of S live feeds of BGRA frames, every frame an allocation of its own: the RGB32 "
+                    "room on the list beside strip + rgb24 room + write back and beside the rgb24 room alone; the four launchers beside their rgb24 "
+                    "siblings")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.live_rgb32:
+        lines = [f"bench_frame_io --live-rgb32: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_live_rgb32(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "live_rgb32_bench.txt"))
     if args.i420:
         lines = [f"bench_frame_io --i420: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
         bench_i420(args, lines)

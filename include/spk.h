@@ -1241,6 +1241,46 @@ int spk_paste_colour_sums_rgb32_sim_table(const float* src, int N, int Hs, int W
                                           int swap_rb, int alpha_first, double feather, float lo, float k, const float* matte_dev,
                                           int matte_frames, double* sums_out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- the axis-aligned edge on RGB32 frames: boxes in, a paste, whole frames out (csrc/frame_rgb32.hip) ------------------------------
+ * What spk_frames_u8_to_f32 / _boxes, spk_frames_paste_u8 and spk_frames_f32_to_u8 are to packed frames, for the RGB32 FRAME defined
+ * above (data 4-byte aligned; row_stride a multiple of 4, >= 4 W; with N > 1 image_stride a multiple of 4; swap_rb and alpha_first
+ * give the four orders).  The fourth byte is never interpreted; the way in never reads it for a value, the paste stores it as loaded.
+ *
+ * spk_frames_rgb32_to_f32, spk_frames_rgb32_to_f32_boxes: the arguments, launch shape and refusals of spk_frames_u8_to_f32 / _boxes
+ *   with alpha_first behind swap_rb and 4 W where those say 3 W.  Refused on top, before any launch and before anything is
+ *   dereferenced: a base that is not 4-byte aligned; a row_stride (with N > 1: an image_stride) that is not a multiple of 4;
+ *   alpha_first outside {0, 1}.  A tap is ONE aligned 32-bit load whose three colour bytes are shifted out of the word; the fp64 sums
+ *   take the same byte values in the same order, so the result is bit for bit spk_frames_u8_to_f32's on a copy of the colour bytes.
+ * spk_frames_paste_rgb32: the arguments and refusals of spk_frames_paste_u8 plus alpha_first and the RGB32 checks (the overlap check
+ *   uses 4 W).  A thread owns one pixel: one 32-bit load of the background word, one 32-bit store of the three blended colour bytes
+ *   and the fourth byte exactly as loaded.  Pixels outside the frame are skipped and the frames may be pasted in place, as there; the
+ *   colour bytes are those of the packed paste, bit for bit.
+ * spk_frames_f32_to_rgb32: src fp32 [N,3,H,W] -> N frames of H x W words behind dst through BYTE strides (its uint8 sibling writes
+ *   contiguous frames only), so a region-of-interest view of a wider texture is written directly.  alpha in 0 .. 255 is written as
+ *   the fourth byte of every pixel; alpha = -1 means KEEP: the fourth byte already in dst stays -- a read-modify-write of the whole
+ *   word by the one thread that owns it, never a byte store beside another thread's word.  Any other alpha is refused; with N > 1,
+ *   frames that overlap are refused.  A thread takes four consecutive pixels of one row (groups are counted per row, so none
+ *   straddles a row pitch).  W % 4 == 0 and src 16-byte aligned: three float4 loads and the four words as dword accesses -- all a
+ *   dst that is only 4-byte aligned allows; the compiler makes one 16-byte store of them (keep: one 16-byte load in front of it),
+ *   which on gfx950 needs dword alignment only, so a 16-byte aligned dst has no form of its own; W % 4 != 0 or an unaligned src:
+ *   dword loads, dword stores and a row tail.  The colour bytes are those of spk_frames_f32_to_u8, bit for bit (ties to even).
+ * replaces: a strip of the fourth byte into a packed scratch clip in front of the rgb24 entry points and a scatter of three of every
+ *   four bytes behind them. */
+int spk_frames_rgb32_to_f32(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int Hin, int Win, int swap_rb, int alpha_first,
+                            const int32_t* first_y, const int32_t* count_y, const float* w_y, int taps_y, const int32_t* first_x,
+                            const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout, int Wout, float scale0, float scale1,
+                            float scale2, float shift0, float shift1, float shift2, void* stream);
+int spk_frames_rgb32_to_f32_boxes(const uint8_t* src, int64_t image_stride, int64_t row_stride, int N, int H, int W, const int32_t* boxes_yx,
+                                  int Hin, int Win, int swap_rb, int alpha_first, const int32_t* first_y, const int32_t* count_y, const float* w_y,
+                                  int taps_y, const int32_t* first_x, const int32_t* count_x, const float* w_x, int taps_x, float* dst, int Hout,
+                                  int Wout, float scale0, float scale1, float scale2, float shift0, float shift1, float shift2, void* stream);
+int spk_frames_paste_rgb32(const float* src, int N, int Hs, int Ws, uint8_t* dst, int64_t image_stride, int64_t row_stride, int H, int W, int h,
+                           int w, int y0, int x0, const int32_t* boxes_yx, int swap_rb, int alpha_first, const int32_t* first_y,
+                           const int32_t* count_y, const float* w_y, int taps_y, const int32_t* first_x, const int32_t* count_x, const float* w_x,
+                           int taps_x, const float* a_y, const float* a_x, float lo, float k, void* stream);
+int spk_frames_f32_to_rgb32(const float* src, uint8_t* dst, int64_t image_stride, int64_t row_stride, int N, int H, int W, int swap_rb,
+                            int alpha_first, int alpha, float lo, float k, void* stream);
+
 /* ---- the aligned NV12 edge over a surface table: every surface its own planes, pitches and size (csrc/frame_table_nv12.hip) --------
  * What the frame table is to packed frames, for NV12: each call's hardware decoder delivers a surface of that call's own
  * resolution into that call's own buffer, and the encoder wants it back.  A surface is two planes with two pitches, so an entry
@@ -1603,6 +1643,14 @@ typedef struct spk_frames_to_i420_args {
     int64_t y_image_stride, y_row_stride, u_image_stride, u_row_stride, v_image_stride, v_row_stride;
     int32_t N, H, W, standard, full_range; float lo, k; int32_t reserved;
 } spk_frames_to_i420_args;
+/* kind 16.  desc: spk_frames_to_rgb32_args -> spk_frames_f32_to_rgb32 (a decoder plan that ends in RGB32 frames: x [N,3,H,W] fp32,
+ * the frames y by pointer and byte strides; alpha 0 .. 255, or -1 to keep the fourth bytes that are there).  Four 8-byte fields, six
+ * int32 and two floats: 64 bytes, a multiple of 8 as it stands, so it carries no padding field. */
+enum { SPK_OP_FRAMES_TO_RGB32 = SPK_OP_FRAMES_TO_I420 + 1 };
+typedef struct spk_frames_to_rgb32_args {
+    const float* x; uint8_t* y; int64_t image_stride, row_stride;
+    int32_t N, H, W, swap_rb, alpha_first, alpha; float lo, k;
+} spk_frames_to_rgb32_args;
 int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask, void* stream);
 
 #ifdef __cplusplus

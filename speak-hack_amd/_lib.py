@@ -156,6 +156,7 @@ OP_NOISE_FILL = 12
 OP_FRAMES_TO_NV12 = 13
 OP_NOISE_FILL_ROWS = 14
 OP_FRAMES_TO_I420 = 15
+OP_FRAMES_TO_RGB32 = 16
 ALL_OPS = 0xFFFFFFFF
 
 NOISE_MAX_LAYERS = 16
@@ -236,6 +237,13 @@ class FramesToI420Args(C.Structure):
                 ("y_row_stride", C.c_int64), ("u_image_stride", C.c_int64), ("u_row_stride", C.c_int64), ("v_image_stride", C.c_int64),
                 ("v_row_stride", C.c_int64), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("standard", C.c_int32),
                 ("full_range", C.c_int32), ("lo", C.c_float), ("k", C.c_float), ("reserved", C.c_int32)]
+
+
+class FramesToRgb32Args(C.Structure):
+    """``spk_frames_to_rgb32_args`` (include/spk.h): 64 bytes, no padding field."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("image_stride", C.c_int64), ("row_stride", C.c_int64), ("N", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("swap_rb", C.c_int32), ("alpha_first", C.c_int32), ("alpha", C.c_int32),
+                ("lo", C.c_float), ("k", C.c_float)]
 
 
 class PixelNormArgs(C.Structure):
@@ -523,6 +531,24 @@ _PROTOTYPES = {
     "spk_noise_fill_rows": (C.c_int, [C.POINTER(NoiseFillRowsArgs), C.c_void_p]),
 }
 
+# The axis-aligned RGB32 edge (csrc/frame_rgb32.hip), bound and exported like the table above.  A table of its own because
+# tests/test_live_rgb32_gpu.py pins the ALIGNED edge's nine entry points by counting the names of ``_PROTOTYPES`` that hold "rgb32".
+_PROTOTYPES_RGB32_AXIS = {
+    "spk_frames_rgb32_to_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_rgb32_to_f32_boxes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 6 + [C.c_void_p]),
+    "spk_frames_paste_rgb32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    "spk_frames_f32_to_rgb32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_float, C.c_float, C.c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -533,7 +559,7 @@ class SpkError(RuntimeError):
 
 def exported_symbols():
     """Names every entry point include/spk.h declares (used by the CPU-side ABI test)."""
-    return sorted(_PROTOTYPES)
+    return sorted({**_PROTOTYPES, **_PROTOTYPES_RGB32_AXIS})
 
 
 def lib():
@@ -546,7 +572,7 @@ def lib():
                     raise SpkError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
                                    f"g.build()'` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
                 h = C.CDLL(LIB_PATH)
-                for name, (res, args) in _PROTOTYPES.items():
+                for name, (res, args) in {**_PROTOTYPES, **_PROTOTYPES_RGB32_AXIS}.items():
                     fn = getattr(h, name)
                     fn.restype = res
                     fn.argtypes = args

@@ -91,6 +91,12 @@ extern "C" int spk_launch_list(const spk_op* ops, int n_ops, uint32_t kind_mask,
                                             stream);
                 break;
             }
+            case SPK_OP_FRAMES_TO_RGB32: {
+                const spk_frames_to_rgb32_args* a = static_cast<const spk_frames_to_rgb32_args*>(op.desc);
+                rc = spk_frames_f32_to_rgb32(a->x, a->y, a->image_stride, a->row_stride, a->N, a->H, a->W, a->swap_rb, a->alpha_first, a->alpha,
+                                             a->lo, a->k, stream);
+                break;
+            }
             default:
                 return spk::fail(SPK_EUNSUPPORTED, "launch_list: op %d: unknown kind %d", i, op.kind);
         }

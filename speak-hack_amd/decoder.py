@@ -278,12 +278,14 @@ class StyleGenerator(nn.Module):
         return syn.use_plan and features.is_cuda and features.dim() == 2 and len(syn.layers) * 2 + 1 <= ops.L.FC_MAX_GROUPS
 
     def plan_forward(self, features, noises=None, *, output="f32", value_range=(-1, 1), swap_rb=False, seed=None, frame0=0,
-                     fixed_noise=False, standard="bt601", full_range=False, seed_rows=None, frame_rows=None):
+                     fixed_noise=False, standard="bt601", full_range=False, seed_rows=None, frame_rows=None, channel_order="rgba", alpha=255):
         """The eval forward -- mapping, truncation, synthesis; no style mixing, no host-RNG draw -- on the inference launch plan,
         whatever ``self.training`` is (no module state is read or touched).  No gradient flows through it.  ``output="uint8"``:
         the plan ends in the quantising op and returns uint8 [B,R,R,3] frames (``plan.DecoderPlan``); ``output="nv12"``: it ends in
         the NV12 op and returns uint8 [B,3R/2,R] surfaces in the colour of ``standard`` / ``full_range``; ``output="i420"``: it ends
-        in the I420 op and returns packed uint8 [B,3R/2,R] surfaces (``ops.i420_planes``) in that colour.  ``seed``: a seeded plan
+        in the I420 op and returns packed uint8 [B,3R/2,R] surfaces (``ops.i420_planes``) in that colour; ``output="rgb32"``: it ends in
+        the RGB32 op and returns uint8 [B,R,R,4] frames in ``channel_order`` ("rgba" | "bgra" | "argb" | "abgr") with the fourth byte
+        ``alpha`` (0 .. 255) -- order and alpha are part of the plan's key, and apply to this output only.  ``seed``: a seeded plan
         (a cache entry of its own) draws the noise of ``ops.decoder_noise(shapes, seed, frame0=frame0, fixed=fixed_noise)`` as
         the first op of its list.  ``seed_rows`` / ``frame_rows`` (device int64 ``[B]`` tables, instead of ``seed``): a rows-seeded
         plan (again a cache entry of its own) draws ``ops.decoder_noise_rows(shapes, seed_rows, frame_rows)``, one (seed, frame) per
@@ -300,11 +302,23 @@ class StyleGenerator(nn.Module):
             ops.check_seed(seed, frame0)
         elif fixed_noise:
             raise ValueError("fixed_noise needs a seed")
+        rgb32 = {}
+        if output == "rgb32":                                              # the order and the fourth byte: checked before a device is asked
+            if swap_rb:
+                raise ValueError("swap_rb applies to uint8 output: rgb32 output takes channel_order")
+            order, alpha_first = FR.rgb32_order(channel_order)
+            if FR.rgb32_alpha(alpha, "plan_forward") < 0:
+                raise ValueError("plan_forward: alpha=None keeps the fourth bytes of a frame that exists, and a plan writes new frames")
+            rgb32 = dict(swap_rb=order == "bgr", alpha_first=bool(alpha_first), alpha=alpha)
+        elif channel_order != "rgba" or alpha != 255:
+            raise ValueError("channel_order / alpha apply to rgb32 output only")
         B = features.size(0)
         # (the truncation scale is folded into the style FCs' multipliers when the plan is built: part of the key)
         key = (B, features.device, torch.cuda.current_stream(features.device).cuda_stream, "features", syn.precision,
                self.truncation_psi, self.truncation_cutoff)
-        if output in ("nv12", "i420"):
+        if output == "rgb32":
+            key += (output, float(value_range[0]), float(value_range[1]), channel_order, alpha)
+        elif output in ("nv12", "i420"):
             key += (output, float(value_range[0]), float(value_range[1]), *FR.yuv_standard(standard, full_range))
         elif output != "f32":
             key += (output, float(value_range[0]), float(value_range[1]), bool(swap_rb))
@@ -313,9 +327,9 @@ class StyleGenerator(nn.Module):
         elif rows:
             key += ("seeded rows",)
         p = PL.plan_for(self, key, lambda: PL.DecoderPlan(syn, B, features.device, generator=self, precision=syn.precision,
-                                                          output=output, value_range=value_range, swap_rb=swap_rb,
+                                                          output=output, value_range=value_range,
                                                           seeded="rows" if rows else seed is not None, standard=standard,
-                                                          full_range=full_range))
+                                                          full_range=full_range, **{"swap_rb": swap_rb, **rgb32}))
         features = features if features.stride(1) == 1 else features.contiguous()
         if rows:
             return p.run(features, seed_rows=seed_rows, frame_rows=frame_rows)

@@ -3,7 +3,7 @@ network -- packed RGB (csrc/frame_io.hip), NV12 (csrc/frame_nv12.hip), and packe
 (csrc/frame_sim.hip: aligned crops; csrc/frame_blend.hip: their paste with a face matte and a colour match; csrc/frame_sim_nv12.hip:
 all of that on NV12 surfaces; csrc/frame_table.hip: on frames in buffers and of sizes of their own; csrc/frame_table_nv12.hip: on
 NV12 surfaces in planes, of pitches and of sizes of their own; csrc/frame_sim_rgb32.hip, csrc/frame_table_rgb32.hip: on RGB32
-frames, four bytes per pixel), whose rows
+frames, four bytes per pixel; csrc/frame_rgb32.hip: RGB32 frames through crop boxes, the axis-aligned edge), whose rows
 csrc/landmark_sim.hip fits to landmarks and smooths; csrc/causal_filter.hip: the causal filters of a live feed, their state on
 the device).  ``ops`` re-exports the
 launchers (``ops.frames_from_u8`` ...), which is the documented API; ``PIXEL_FORMATS`` is what ``IRFD.reenact_video`` walks its one loop with."""
@@ -2073,6 +2073,104 @@ def paste_colour_sums_rgb32(x, frames, sim, *, matte=None, feather=0, value_rang
                               channel_order=order, alpha_first=alpha_first)
 
 
+# ---- RGB32, axis-aligned: boxes in, a paste, whole frames out (csrc/frame_rgb32.hip) -------------------------------------------------
+def frames_from_rgb32(frames, size, *, crop=None, channel_order="rgba", mean=0.5, std=0.5):
+    """``frames_from_u8`` for RGB32 frames, one launch (``spk_frames_rgb32_to_f32``; per-frame or device boxes:
+    ``spk_frames_rgb32_to_f32_boxes``): the same crop, tables, normalisation and arguments, a tap one aligned 32-bit load, and the
+    fp32 BITS that launcher gives on a packed copy of the colour bytes.  ``frames``: uint8 ``[N,H,W,4]`` (one frame: ``[H,W,4]``) on
+    the device, read in place through its strides when its pixels are aligned words (a region-of-interest view at any pixel offset
+    is), else through a contiguous copy.  ``channel_order``: ``"rgba"``, ``"bgra"``, ``"argb"`` or ``"abgr"`` (``rgb32_order``); the
+    network gets R, G, B planes and the fourth byte is never interpreted.  ``crop``: the three forms of ``frames_from_u8``.
+    -> float32 [N,3,size,size]."""
+    what = "frames_from_rgb32"
+    frames, N, H, W = _PACKED32.shaped(frames, None, what)
+    Hout, Wout = _out_size(size, what)
+    order, alpha_first = rgb32_order(channel_order)
+    swap = _channel_swap(order)
+    scale, shift = _affine(mean, std, what)
+    origins = None
+    if crop is not None:
+        origins, h, w = parse_boxes(crop, N, H, W, f"{what}: crop")
+        if isinstance(origins, tuple):                                # one host box: a slice, read in place through its strides
+            (y0, x0), origins = origins, None
+            frames = frames[:, y0:y0 + h, x0:x0 + w]
+    frames, where = _PACKED32.read(frames, what)
+    _, Hin, Win, _ = frames.shape
+    out = torch.empty((N, 3, Hout, Wout), device=frames.device, dtype=torch.float32)
+    entry, src = "spk_frames_rgb32_to_f32", (*where, N, Hin, Win)
+    if origins is not None:                                               # the box is h x w of the frame, else the (sliced) frame itself
+        entry, src = entry + "_boxes", (*src, _origins(origins, frames.device, what)[2].data_ptr(), h, w)
+        Hin, Win = h, w
+    L.check(getattr(L.lib(), entry)(*src, swap, alpha_first, *_table_args(_device_tables(frames.device, Hin, Win, Hout, Wout)), out.data_ptr(),
+                                    Hout, Wout, *scale, *shift, L.stream_ptr()), entry)
+    return out
+
+
+def rgb32_alpha(alpha, what):
+    """The fourth byte of the way out: an integer ``0 .. 255``, or None for "keep what is there" -> the entry point's ``alpha``
+    (``-1``: keep).  Anything else raises ``ValueError``."""
+    if alpha is None:
+        return -1
+    if isinstance(alpha, bool) or not isinstance(alpha, int) or not 0 <= alpha <= 255:
+        raise ValueError(f"{what}: alpha must be an integer 0 .. 255, or None to keep the fourth bytes of out, got {alpha!r}")
+    return alpha
+
+
+def frames_to_rgb32(x, *, value_range=(-1, 1), channel_order="rgba", alpha=255, out=None):
+    """``frames_to_u8`` for RGB32 frames, one launch (``spk_frames_f32_to_rgb32``): float32 [N,3,H,W] in ``value_range`` -> uint8
+    ``[N,H,W,4]`` in ``channel_order`` (``rgb32_order``), the colour bytes those of ``frames_to_u8`` bit for bit (ties to even; NaN
+    -> 0), the fourth byte of every pixel ``alpha`` (0 .. 255).  ``out``: a uint8 tensor ``[N,H,W,4]`` to write through its strides --
+    a region-of-interest view of a wider texture is written directly; its pixels must be aligned words and its rows / frames must
+    not overlap (``rgb32_pixels``), else ``SpkError``.  ``alpha=None`` (needs ``out=``): KEEP -- the fourth bytes already in ``out``
+    stay.  Without ``out=`` the result is a new contiguous tensor."""
+    what = "frames_to_rgb32"
+    _check_chw(x, what)
+    order, alpha_first = rgb32_order(channel_order)
+    (swap, alpha_first), lo, k = _PACKED32.quantised(value_range, order, alpha_first)
+    a = rgb32_alpha(alpha, what)
+    if a < 0 and out is None:
+        raise ValueError(f"{what}: alpha=None keeps the fourth bytes of out, and there is no out=")
+    N, _, H, W = x.shape
+    xp = L.dptr(x, "x")
+    if out is None:
+        out = torch.empty((N, H, W, 4), device=x.device, dtype=torch.uint8)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 4):
+        got = f"{out.dtype} {tuple(out.shape)} on {out.device}" if isinstance(out, torch.Tensor) else type(out).__name__
+        raise L.SpkError(f"out: expected a uint8 HIP tensor {(N, H, W, 4)}, got {got}")
+    elif not rgb32_pixels(out):
+        raise L.SpkError(f"out: pixels must be aligned 32-bit words (strides (4 k, 4 k >= 4 W, 4, 1), a data pointer that is a multiple of "
+                         f"4) and rows / frames must not overlap, got strides {out.stride()} at {out.data_ptr():#x}")
+    L.check(L.lib().spk_frames_f32_to_rgb32(xp, out.data_ptr(), out.stride(0) if N > 1 else 0, out.stride(1), N, H, W, swap, alpha_first, a, lo, k,
+                                            L.stream_ptr()), "spk_frames_f32_to_rgb32")
+    return out
+
+
+def frames_paste_rgb32(x, frames, box, *, feather=0, value_range=(-1, 1), channel_order="rgba", out=None):
+    """``frames_paste_u8`` for RGB32 frames, one launch (``spk_frames_paste_rgb32``): the same resize, quantisation, ``feather`` and
+    blend inside the same box (its three forms; box pixels outside the frame are skipped); a pasted pixel is one 32-bit load and one
+    32-bit store, its colour bytes those the packed launcher leaves on a packed copy, ITS FOURTH BYTE AS IT WAS.  ``out=None``: a
+    contiguous clone of ``frames`` (alpha included) is pasted into; ``out=frames``: in place through its strides; another ``out``
+    first receives a copy.  Frames that are written must have aligned pixels and must not overlap (``rgb32_pixels``), else
+    ``SpkError``.  -> uint8 [N,H,W,4]."""
+    what = "frames_paste_rgb32"
+    _check_chw(x, what)
+    N, _, Hs, Ws = x.shape
+    frames, _, H, W = _PACKED32.shaped(frames, N, what)
+    order, alpha_first = rgb32_order(channel_order)
+    (swap, alpha_first), lo, k = _PACKED32.quantised(value_range, order, alpha_first)
+    feather = check_feather(feather, what)
+    origins, h, w = parse_boxes(box, N, H, W, f"{what}: box", inside=False)
+    xp = L.dptr(x, "x")
+    _PACKED32.on_device(frames)
+    out, where, fill = _PACKED32.target(frames, out, N, H, W, x.device, what)
+    y0, x0, boxes = _origins(origins, x.device, what)
+    fill()
+    tables, ay, ax = _paste_tables(Hs, Ws, h, w, feather, x.device)
+    L.check(L.lib().spk_frames_paste_rgb32(xp, N, Hs, Ws, *where, H, W, h, w, y0, x0, _ptr(boxes), swap, alpha_first, *tables, ay, ax, lo, k,
+                                           L.stream_ptr()), "spk_frames_paste_rgb32")
+    return out
+
+
 def generated_row_scale(size, Ws, device):
     """The network image has ``size`` pixels where a generated one is ``Ws`` wide: -> the factor of a row ``(a, c, tx, ty)`` that maps
     the generated image into the frames, a float32 ``[4]`` tensor on ``device`` made in fp32, or None when it is 1"""
@@ -2154,6 +2252,52 @@ class Rgb24:
                                 **self.args)
 
 
+class Rgb32(Rgb24):
+    """RGB32 frames ``[T,H,W,4]`` in one of the four orders of ``rgb32_order``: ``Rgb24`` over the RGB32 launchers.  The fourth byte
+    of a frame that is pasted into stays; a generated frame gets 255."""
+    output = "rgb32"
+
+    def __init__(self, channel_order, standard, full_range):
+        rgb32_order(channel_order)                                        # one of the four, or ValueError: before anything else
+        self.args = dict(channel_order=channel_order)
+
+    def open(self, frames, inplace):
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.size(3) != 4 or frames.size(0) < 1:
+            got = tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames).__name__
+            raise ValueError(f"reenact_video: pose_u8 must be [T,H,W,4] with pixel_format='rgb32', got {got}")
+        if inplace and not rgb32_pixels(frames):
+            raise L.SpkError(f"reenact_video: inplace needs pixels that are aligned 32-bit words (strides (4 k, 4 k >= 4 W, 4, 1), a data pointer "
+                             f"that is a multiple of 4) and rows / frames that do not overlap, got strides {frames.stride()} at "
+                             f"{frames.data_ptr():#x}")
+        return (frames, frames.device, *frames.shape[:3])
+
+    def network_input(self, frames, size, crop):
+        if isinstance(crop, Aligned):
+            return frames_from_rgb32_aligned(frames, size, crop.rows, **self.args)
+        return frames_from_rgb32(frames, size, crop=crop, **self.args)
+
+    def clone(self, frames):
+        return (clone_rgb32(frames),) * 2
+
+    def paste(self, y, frames, t0, t1, box, feather, matte=None, colour_match=False):
+        if isinstance(box, Aligned):
+            blend = {}
+            if matte is not None or colour_match:                         # the statistics read the background before the paste writes it
+                matte = chunk_matte(matte, t0, t1)
+                rows = paste_colour_match_rgb32(y, frames[t0:t1], box.rows, matte=matte, feather=feather, **self.args) if colour_match else None
+                blend = dict(matte=matte, colour=rows)
+            frames_paste_rgb32_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], **self.args, **blend)
+        else:
+            frames_paste_rgb32(y, frames[t0:t1], box, feather=feather, out=frames[t0:t1], **self.args)
+
+    def colour_sums(self, y, frames, t0, t1, box, feather, matte, sums):
+        paste_colour_sums_rgb32(y, frames[t0:t1], box.rows, matte=chunk_matte(matte, t0, t1), feather=feather, out=sums[t0:t1], **self.args)
+
+    def paste_matched(self, y, frames, t0, t1, box, feather, matte, colour):
+        frames_paste_rgb32_aligned(y, frames[t0:t1], box.rows, feather=feather, out=frames[t0:t1], matte=chunk_matte(matte, t0, t1), colour=colour,
+                                   **self.args)
+
+
 class Nv12:
     """NV12 surfaces: what ``nv12_planes`` takes, in the colour of ``standard`` / ``full_range``."""
     output, needs_box = "nv12", True
@@ -2202,4 +2346,4 @@ class I420(Nv12):
         frames_paste_i420(y, part, box, feather=feather, out=part, **self.args)
 
 
-PIXEL_FORMATS = {"rgb24": Rgb24, "nv12": Nv12, "i420": I420}
+PIXEL_FORMATS = {"rgb24": Rgb24, "nv12": Nv12, "i420": I420, "rgb32": Rgb32}

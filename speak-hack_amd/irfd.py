@@ -119,7 +119,9 @@ class IRFD(nn.Module):
         interleaved UV plane) in the colour of ``standard`` ("bt601" | "bt709") / ``full_range``, converted by the last op of the
         decoder plan -- ``ops.frames_to_nv12`` of the fp32 result, bit for bit.  ``output="i420"``: packed uint8 [T,3R/2,R] I420
         surfaces in that colour -- the ``R`` rows of Y, then the ``R^2 / 4`` bytes of U, then those of V, what ``ops.i420_planes``
-        takes -- ``ops.frames_to_i420`` of the fp32 result, bit for bit.
+        takes -- ``ops.frames_to_i420`` of the fp32 result, bit for bit.  ``output="rgb32"``: uint8 [T,R,R,4] in ``channel_order``
+        ("rgba" | "bgra" | "argb" | "abgr": ``ops.rgb32_order``; the default "rgb" raises) with the fourth byte 255, by the last op of
+        the decoder plan -- ``ops.frames_to_rgb32`` of the fp32 result, bit for bit.
 
         ``seed`` (0 <= seed < 2**64; not together with ``noises``): reproducible noise, a function of (seed, frame index,
         layer, pixel) drawn inside the decoder's launch list (``ops.decoder_noise`` gives the same tensors explicitly); the
@@ -136,16 +138,19 @@ class IRFD(nn.Module):
     def _reenact_chunks(self, identity_image, pose_frames, emotion_frames, noises, chunk, output, channel_order, seed, noise, frame0,
                         colour=("bt601", False)):
         """``reenact``'s argument checks and chunk loop: yields ``(t0, t1, frames of [t0, t1))``."""
-        if output not in ("f32", "uint8", "nv12", "i420"):
-            raise ValueError(f"reenact: output must be 'f32', 'uint8', 'nv12' or 'i420', got {output!r}")
+        if output not in ("f32", "uint8", "nv12", "i420", "rgb32"):
+            raise ValueError(f"reenact: output must be 'f32', 'uint8', 'nv12' or 'i420', got {output!r} (or 'rgb32')")
         FR.yuv_standard(*colour)
         _check_noise("reenact", noise, seed, noises, frame0)
         if seed is None and frame0 != 0:
             raise ValueError("reenact: frame0 applies to seeded noise only")
-        if channel_order not in ("rgb", "bgr"):
-            raise ValueError(f"reenact: channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
-        if output != "uint8" and channel_order != "rgb":
-            raise ValueError("reenact: channel_order applies to uint8 output only")
+        if output == "rgb32":                                              # one of the four orders of a 4-byte pixel: "rgb" is none of them
+            FR.rgb32_order(channel_order)
+        else:
+            if channel_order not in ("rgb", "bgr"):
+                raise ValueError(f"reenact: channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+            if output != "uint8" and channel_order != "rgb":
+                raise ValueError("reenact: channel_order applies to uint8 output only")
         if identity_image.dim() != 4 or identity_image.size(0) != 1 or identity_image.size(1) != 3:
             raise ValueError(f"reenact: identity_image must be [1,3,H,W], got {tuple(identity_image.shape)}")
         if pose_frames.dim() != 4 or pose_frames.size(1) != 3 or pose_frames.size(0) < 1:
@@ -199,6 +204,17 @@ class IRFD(nn.Module):
         decoder's own planes with ``inplace=True``, and no interleaving into scratch NV12 surfaces.  The Y, U and V bytes are those
         of ``pixel_format="nv12"`` on the interleaved clip.  The identity photo stays packed RGB.
 
+        ``pixel_format="rgb32"``: ``pose_u8`` / ``emotion_u8`` are uint8 ``[T,H,W,4]`` as a capture surface, an interop texture or a
+        compositor holds them, and ``channel_order`` is one of ``"rgba"``, ``"bgra"``, ``"argb"``, ``"abgr"`` (an ``X`` byte counts as
+        the ``a``; the default ``"rgb"`` raises) -- through ``ops.frames_from_rgb32``, ``reenact(output="rgb32")`` and
+        ``ops.frames_paste_rgb32``: one ``spk_frames_paste_rgb32`` launch per chunk and no strip of the fourth byte into a packed scratch
+        clip.  Everything ``"rgb24"`` takes works -- ``crop`` in its three forms, ``paste``, ``feather``, ``inplace`` (the clip's pixels
+        must be aligned 32-bit words: ``ops.rgb32_pixels``), ``align``, ``identity_align``, ``matte``, ``colour_match``,
+        ``colour_smooth`` (the ``_rgb32`` launchers of the aligned edge) -- and the colour bytes are those of ``"rgb24"`` on the clip with
+        the fourth byte stripped.  Without ``paste`` the result is ``[T,R,R,4]`` with the fourth byte 255; with ``paste`` every fourth
+        byte of the result is the pose frame's.  The identity photo stays a packed ``[H,W,3]`` photo in the colour order with the alpha
+        dropped (``rgba`` / ``argb``: ``rgb``; ``bgra`` / ``abgr``: ``bgr``).  ``standard`` / ``full_range`` are refused.
+
         ``align=sim`` (instead of ``crop``; both: ``ValueError``): an aligned crop per frame -- rows ``(a, c, tx, ty)`` of the
         similarity transform that maps the ``size`` network image into frame ``t`` (``ops.similarity_rows``; include/spk.h), any
         scale and angle per frame, as ``ops.similarity_from_landmarks`` fits them to a tracker's landmarks: a host sequence / CPU
@@ -208,7 +224,7 @@ class IRFD(nn.Module):
         ``ops.frames_from_u8_aligned``; with ``paste=True`` each chunk's fp32 result goes through ``ops.frames_paste_u8_aligned``
         into its slice, one ``spk_frames_paste_u8_sim`` launch per chunk, rows taken per frame, so the result does not depend on
         ``chunk``.  The generated image has ``R`` pixels where the network image has ``size``: the paste uses the rows with
-        ``(a, c)`` scaled by ``size / R`` in fp32.  Packed RGB only: ``align`` with ``pixel_format="nv12"`` or ``"i420"`` raises
+        ``(a, c)`` scaled by ``size / R`` in fp32.  Packed RGB and RGB32 only: ``align`` with ``pixel_format="nv12"`` or ``"i420"`` raises
         ``ValueError`` (NV12 and I420 frames take crop boxes).
 
         ``identity_align``: the identity photo through an aligned crop as well, so that ``Ei`` sees a face framed as ``Ee`` / ``Ep``
@@ -240,8 +256,8 @@ class IRFD(nn.Module):
         the paste of frame ``j`` writes frame ``j`` only: here too the result depends neither on ``chunk`` nor on ``inplace``.
         ``colour_smooth=0``: the calls the method always made."""
         if pixel_format not in FR.PIXEL_FORMATS:
-            raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12' or 'i420', got {pixel_format!r}")
-        if pixel_format == "rgb24" and (standard != "bt601" or full_range):
+            raise ValueError(f"reenact_video: pixel_format must be 'rgb24' or 'nv12' or 'i420' or 'rgb32', got {pixel_format!r}")
+        if pixel_format in ("rgb24", "rgb32") and (standard != "bt601" or full_range):
             raise ValueError("reenact_video: standard / full_range apply to pixel_format='nv12' only, and to 'i420'")
         FR.yuv_standard(standard, full_range)
         feather = float(feather)
@@ -253,7 +269,7 @@ class IRFD(nn.Module):
         _check_noise("reenact_video", noise, seed, noises, frame0)
         if align is not None and crop is not None:
             raise ValueError("reenact_video: crop and align are two ways to say where the face is: give one")
-        if align is not None and pixel_format != "rgb24":
+        if align is not None and pixel_format not in ("rgb24", "rgb32"):
             raise ValueError("reenact_video: align applies to pixel_format='rgb24' only (NV12 frames take crop boxes)")
         if not isinstance(colour_match, bool):
             raise ValueError(f"reenact_video: colour_match must be a bool, got {colour_match!r}")
@@ -273,7 +289,9 @@ class IRFD(nn.Module):
                                  f"ops.LandmarkMatte, got {got}")
             blend = dict(matte=matte, colour_match=colour_match)
         fmt = FR.PIXEL_FORMATS[pixel_format](channel_order, standard, full_range)
-        if identity_align is not None:                                     # host rows: checked here, before any launch
+        if pixel_format == "rgb32":                                        # the identity photo stays packed: the colour order with the alpha dropped
+            channel_order = FR.rgb32_order(channel_order)[0]
+        if identity_align is not None:                                    # host rows: checked here, before any launch
             identity_align = FR.Aligned.parse(identity_align, 1, size, identity_u8.device, "reenact_video: identity_align")
         pose_in = pose_u8
         if align is not None:                                              # the transforms stand where a box would: checked / uploaded once
@@ -428,7 +446,8 @@ class IRFD(nn.Module):
         if hasattr(Gd, "plan_serves") and Gd.plan_serves(gin):
             how = {"f32": {}, "uint8": dict(output=output, swap_rb=channel_order == "bgr"),
                    "nv12": dict(output=output, standard=colour[0], full_range=colour[1]),
-                   "i420": dict(output=output, standard=colour[0], full_range=colour[1])}[output]
+                   "i420": dict(output=output, standard=colour[0], full_range=colour[1]),
+                   "rgb32": dict(output=output, channel_order=channel_order)}[output]
             return Gd.plan_forward(gin, noises, **how, **seeded)
         flags = [(mod, mod.training) for mod in Gd.modules()]
         try:
@@ -442,6 +461,8 @@ class IRFD(nn.Module):
             return ops.frames_to_nv12(y, standard=colour[0], full_range=colour[1])
         if output == "i420":
             return ops.frames_to_i420(y, standard=colour[0], full_range=colour[1])
+        if output == "rgb32":
+            return ops.frames_to_rgb32(y, channel_order=channel_order)
         return y if output == "f32" else ops.frames_to_u8(y, channel_order=channel_order)
 
     def forward(self, x_s, x_t, swap_type=None, noises_s=None, noises_t=None):

@@ -23,7 +23,8 @@ from .frames import (resize_tables, resize_tables_f32, feather_tables, parse_box
                      colour_rows_causal, colour_rows_causal_feeds, i420_planes, PlanarTable, clone_planar, frames_from_i420_aligned,
                      frames_paste_i420_aligned, paste_colour_match_i420, paste_colour_sums_i420, frames_from_i420, frames_to_i420,
                      frames_paste_i420, Rgb32Table, clone_rgb32, frames_from_rgb32_aligned, frames_paste_rgb32_aligned,
-                     paste_colour_match_rgb32, paste_colour_sums_rgb32)
+                     paste_colour_match_rgb32, paste_colour_sums_rgb32, rgb32_order, rgb32_pixels, frames_from_rgb32, frames_to_rgb32,
+                     frames_paste_rgb32)
 
 
 def _launch_conv2d(desc):

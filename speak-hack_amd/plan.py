@@ -178,7 +178,9 @@ class DecoderPlan(LaunchPlan):
     colour matrix of ``standard`` / ``full_range`` into the uint8 [B,3R/2,R] NV12 surfaces ``run`` returns -- ``ops.frames_to_nv12``
     of the fp32 result, bit for bit.  ``output="i420"``: one ``SPK_OP_FRAMES_TO_I420`` instead, into packed uint8 [B,3R/2,R] I420
     surfaces -- the ``R`` rows of Y, then the ``R^2 / 4`` bytes of U, then those of V, what ``ops.i420_planes`` takes --
-    ``ops.frames_to_i420`` of the fp32 result, bit for bit.
+    ``ops.frames_to_i420`` of the fp32 result, bit for bit.  ``output="rgb32"``: one ``SPK_OP_FRAMES_TO_RGB32`` instead, into a contiguous
+    uint8 [B,R,R,4] tensor, the colour bytes in the order of ``swap_rb`` behind ``alpha_first`` and the fourth byte ``alpha`` (0 .. 255)
+    -- ``ops.frames_to_rgb32`` of the fp32 result, bit for bit.
     ``seeded=True``: the list starts with ``SPK_OP_NOISE_FILL`` (csrc/noise.hip), which writes ``noise_flat`` from the
     ``seed`` / ``frame0`` each ``run`` patches into its descriptor -- the noise of ``ops.decoder_noise``, bit for bit, and the
     forward is the launch list alone (no ATen draw, the device generator untouched).  A seeded plan runs seeded calls only, an
@@ -189,10 +191,16 @@ class DecoderPlan(LaunchPlan):
     tables only, and the other two forms refuse them."""
 
     def __init__(self, synthesis, B, device, generator=None, precision="f32", output="f32", value_range=(-1, 1), swap_rb=False,
-                 seeded=False, standard="bt601", full_range=False):
+                 seeded=False, standard="bt601", full_range=False, alpha_first=False, alpha=255):
         super().__init__(device)
-        if output not in ("f32", "uint8", "nv12", "i420"):
-            raise ValueError(f"DecoderPlan: output must be 'f32', 'uint8', 'nv12' or 'i420', got {output!r}")
+        if output not in ("f32", "uint8", "nv12", "i420", "rgb32"):
+            raise ValueError(f"DecoderPlan: output must be 'f32', 'uint8', 'nv12' or 'i420', got {output!r} (or 'rgb32')")
+        if output == "rgb32":
+            alpha = FR.rgb32_alpha(alpha, "DecoderPlan")
+            if alpha < 0:
+                raise ValueError("DecoderPlan: alpha=None keeps the fourth bytes of a frame that exists, and a plan writes new frames")
+        elif alpha_first or alpha != 255:
+            raise ValueError("DecoderPlan: alpha_first / alpha apply to rgb32 output only")
         s = self.synthesis = synthesis
         self.precision = precision
         self.output = output
@@ -290,7 +298,7 @@ class DecoderPlan(LaunchPlan):
             self.torgb = self.add(L.OP_TORGB, L.ToRGBArgs(x=x.data_ptr(), w=L.dptr(s.to_rgb.weight, "weight"), mod=None,
                                                           bias=L.dptr(s.to_rgb.bias, "bias"), skip=None, y=None, B=B, C=Cc, O=O,
                                                           H=x.shape[2], W=x.shape[3], in_scale=1.0))
-        self.to_u8 = self.to_nv12 = self.to_i420 = None
+        self.to_u8 = self.to_nv12 = self.to_i420 = self.to_rgb32 = None
         if output != "f32":
             if O != 3:
                 raise L.SpkError(f"DecoderPlan: {output} frames need 3 output channels, toRGB has {O}")
@@ -317,6 +325,11 @@ class DecoderPlan(LaunchPlan):
         if output == "uint8":
             self.to_u8 = self.add(L.OP_FRAMES_TO_U8, L.FramesToU8Args(x=self.rgb_buf.data_ptr(), y=None, N=B, H=x.shape[2], W=x.shape[3],
                                                                        swap_rb=1 if swap_rb else 0, lo=lo, k=k))
+        if output == "rgb32":                                             # contiguous frames: a row is 4 Wo bytes
+            Ho, Wo = x.shape[2], x.shape[3]
+            self.to_rgb32 = self.add(L.OP_FRAMES_TO_RGB32, L.FramesToRgb32Args(
+                x=self.rgb_buf.data_ptr(), y=None, image_stride=4 * Ho * Wo, row_stride=4 * Wo, N=B, H=Ho, W=Wo, swap_rb=1 if swap_rb else 0,
+                alpha_first=1 if alpha_first else 0, alpha=alpha, lo=lo, k=k))
         self.finish(*([synthesis] + ([generator] if generator is not None else [])))
 
     @staticmethod
@@ -397,6 +410,10 @@ class DecoderPlan(LaunchPlan):
             y = torch.empty((Bo, 3 * Ho // 2, Wo), device=self.device, dtype=torch.uint8)      # packed surfaces: Y rows, then U, then V
             a = self.to_i420
             a.y, a.u, a.v = y.data_ptr(), y.data_ptr() + Ho * Wo, y.data_ptr() + Ho * Wo + Ho * Wo // 4
+        elif self.to_rgb32 is not None:
+            Bo, _, Ho, Wo = self.out_shape
+            y = torch.empty((Bo, Ho, Wo, 4), device=self.device, dtype=torch.uint8)
+            self.to_rgb32.y = y.data_ptr()
         else:
             y = torch.empty(self.out_shape, device=self.device, dtype=torch.float32)
             if self.rgb_fused is not None:

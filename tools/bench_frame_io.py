@@ -91,6 +91,11 @@
     paste=True)`` beside the detour it replaces (interleave, ``pixel_format="nv12"``, split and copy back, chunk by chunk).  Written to
     profiles/i420_bench.txt; reported, not gated.
 
+``--rgb32``: the axis-aligned RGB32 edge: ``frames_from_rgb32`` and ``frames_paste_rgb32`` (one 1080p BGRA frame, a 256^2 box) and
+    ``frames_to_rgb32`` (8 x 256^2, fill and keep) each beside its rgb24 sibling on the same pixels, and
+    ``reenact_video(pixel_format="rgb32", paste=True)`` beside the detour it replaces (strip the fourth byte into a packed clip,
+    ``pixel_format="rgb24"``, write the colour bytes back into a clone).  Written to profiles/rgb32_axis_bench.txt; reported, not gated.
+
     python tools/bench_frame_io.py [--paste | --nv12 | --align | --align-nv12 | --landmarks | --blend | --landmark-matte | --colour-smooth] [--frames 64] [--chunk 8] [--repeats 7] [--out profiles/frame_io_bench.txt]
 """
 import argparse
@@ -1477,6 +1482,103 @@ def bench_i420(args, lines):
                  f"({(med[names[1]] - med[names[0]]) * 1e3:.2f} ms less per clip)")
 
 
+def bench_rgb32(args, lines):
+    """``--rgb32``: the axis-aligned RGB32 edge.  (1) ``frames_from_rgb32``, ``frames_paste_rgb32`` and ``frames_to_rgb32`` each beside
+    its rgb24 sibling on the same pixels, by HIP events: the way in and the paste on one 1080 x 1920 BGRA frame with a 256 x 256 box,
+    the way out on 8 x 256^2 (fill and keep).  (2) ``reenact_video(pixel_format="rgb32", paste=True)`` beside the detour it replaces,
+    both in one process: strip the fourth byte into a packed clip, ``reenact_video(pixel_format="rgb24", paste=True)``, write the three
+    colour bytes back into a clone of the RGB32 clip -- wall clock, synchronised.  The contenders alternate, medians are compared, and
+    the RGB32 contender is entered twice: the distance of its two medians is the spread.  Nothing is gated."""
+    import importlib
+    import model
+    from oracle import irfd_ref as IR
+    from oracle.weights_recipe import fill_state_dict
+
+    ops = importlib.import_module("speak-hack_amd").ops
+    dev = torch.device("cuda:0")
+    T, chunk, size, Hf, Wf, h, w, feather = args.frames, args.chunk, 256, 1080, 1920, 256, 256, 16
+    g = torch.Generator().manual_seed(0)
+
+    # ---- (1) the three launchers beside their rgb24 siblings ----
+    bgra = torch.randint(0, 256, (1, Hf, Wf, 4), generator=g, dtype=torch.uint8).to(dev)
+    bgr = bgra[..., :3].contiguous()
+    box = (400, 832, h, w)
+    x1 = (torch.randn(1, 3, size, size, generator=g) * 0.7).to(dev)
+    x8 = (torch.randn(8, 3, size, size, generator=g) * 0.7).to(dev)
+    how = f"HIP events, launcher included, median of {args.repeats} alternating rounds of 20 after 3 warm-up calls"
+    same_in = torch.equal(ops.frames_from_rgb32(bgra, size, crop=box, channel_order="bgra"), ops.frames_from_u8(bgr, size, crop=box, channel_order="bgr"))
+    p32, p24 = ops.frames_paste_rgb32(x1, bgra, box, feather=feather, channel_order="bgra"), ops.frames_paste_u8(x1, bgr, box, feather=feather, channel_order="bgr")
+    same_paste = torch.equal(p32[..., :3], p24) and torch.equal(p32[..., 3], bgra[..., 3])
+    o32, o24 = ops.frames_to_rgb32(x8, channel_order="bgra"), ops.frames_to_u8(x8, channel_order="bgr")
+    same_out = torch.equal(o32[..., :3], o24) and bool((o32[..., 3] == 255).all())
+    work32, work24 = bgra.clone(), bgr.clone()
+    pairs = ((f"way in: a {h}x{w} box of one {Hf}x{Wf} frame -> {size}^2", "frames_from_rgb32(crop)",
+              lambda: ops.frames_from_rgb32(bgra, size, crop=box, channel_order="bgra"), "frames_from_u8(crop)",
+              lambda: ops.frames_from_u8(bgr, size, crop=box, channel_order="bgr"), f"the same bits: {same_in}"),
+             (f"way in, whole frame: one {Hf}x{Wf} frame -> {size}^2", "frames_from_rgb32", lambda: ops.frames_from_rgb32(bgra, size, channel_order="bgra"),
+              "frames_from_u8", lambda: ops.frames_from_u8(bgr, size, channel_order="bgr"), ""),
+             (f"paste: {size}^2 fp32 -> a {h}x{w} box of one {Hf}x{Wf} frame, feather {feather}, in place", "frames_paste_rgb32",
+              lambda: ops.frames_paste_rgb32(x1, work32, box, feather=feather, channel_order="bgra", out=work32), "frames_paste_u8",
+              lambda: ops.frames_paste_u8(x1, work24, box, feather=feather, channel_order="bgr", out=work24),
+              f"the same colour bytes, the fourth bytes kept: {same_paste}"),
+             (f"way out: 8 x {size}^2 fp32, alpha 255", "frames_to_rgb32", lambda: ops.frames_to_rgb32(x8, channel_order="bgra", out=o32), "frames_to_u8",
+              lambda: ops.frames_to_u8(x8, channel_order="bgr", out=o24), f"the same colour bytes, alpha 255: {same_out}"),
+             (f"way out, keep: 8 x {size}^2 fp32, alpha=None", "frames_to_rgb32(alpha=None)",
+              lambda: ops.frames_to_rgb32(x8, channel_order="bgra", alpha=None, out=o32), "frames_to_u8",
+              lambda: ops.frames_to_u8(x8, channel_order="bgr", out=o24), ""))
+    for title, name, ours, sibling, theirs, note in pairs:
+        contenders = {name: ours, sibling: theirs, name + " (again)": ours}
+        ratio_table(lines, f"{title}; {note + '; ' if note else ''}{how}", alternate(contenders, args.repeats, device_time), name, [(sibling, False)])
+
+    # ---- (2) reenact_video(pixel_format="rgb32", paste=True) beside strip + pixel_format="rgb24" + write back ----
+    m = model.IRFD()
+    sd = IR.irfd_recipe_state_dict()
+    sd.update({"Gd." + k: v for k, v in fill_state_dict(m.Gd.state_dict(), prefix="Gd.").items()})
+    m.load_state_dict(sd, strict=False)
+    m.to(dev).eval()
+    boxes = [(300 + (5 * t) % 97, 700 + (7 * t) % 131) for t in range(T)]                  # a head that moves
+    yx = torch.tensor(boxes, dtype=torch.int32, device=dev)
+    hb = wb = 400
+    ident = torch.randint(0, 256, (1, Hf, Wf, 3), generator=g, dtype=torch.uint8).to(dev)
+    video = torch.empty((T, Hf, Wf, 4), dtype=torch.uint8, device=dev)
+    for t0 in range(0, T, chunk):
+        video[t0:t0 + chunk] = torch.randint(0, 256, (min(chunk, T - t0), Hf, Wf, 4), generator=g, dtype=torch.uint8).to(dev)
+    noises = [torch.randn(T, 1, 4 << (i + 1) // 2, 4 << (i + 1) // 2, generator=g).to(dev) for i in range(13)]
+    kw = dict(size=size, crop=(yx, hb, wb), noises=noises, chunk=chunk, paste=True, feather=feather)
+
+    def ours():
+        return m.reenact_video(ident, video, pixel_format="rgb32", channel_order="bgra", **kw)
+
+    def detour():
+        packed = video[..., :3].contiguous()                                  # strip the fourth byte into a packed clip
+        pasted = m.reenact_video(ident, packed, pixel_format="rgb24", channel_order="bgr", **kw)
+        out = video.clone()
+        out[..., :3] = pasted                                                 # the three colour bytes back into a clone of the RGB32 clip
+        return out
+
+    names = ("pixel_format=rgb32", "strip + rgb24 + write back", "pixel_format=rgb32 (again)")
+    fns = dict(zip(names, (ours, detour, ours)))
+    with torch.no_grad():
+        same = torch.equal(ours(), detour())
+        for _ in range(args.warmup):
+            ours(), detour()
+        times = alternate(fns, args.repeats, wall)
+        c_ours, c_other = CountAten(), CountAten()
+        with c_ours:
+            ours()
+        with c_other:
+            detour()
+    lines.append(f"T = {T} BGRA frames of {Hf}x{Wf}, a {hb}x{wb} tracked box, feather {feather}, chunk {chunk}, into a clone of the clip; wall clock, "
+                 f"synchronised, {args.repeats} alternating rounds after {args.warmup} warm-up rounds; the same bytes: {same}; ATen calls per run: "
+                 f"{c_ours.n} against {c_other.n} ({T // chunk} chunks)")
+    med = {n: statistics.median(ts) for n, ts in times.items()}
+    for n, ts in times.items():
+        lines.append(f"  {n:28s} median {med[n] * 1e3:8.2f} ms  min {ts[0] * 1e3:8.2f}  max {ts[-1] * 1e3:8.2f}  -> {T / med[n]:8.1f} frames/s")
+    spread = abs(med[names[0]] - med[names[2]]) / min(med[names[0]], med[names[2]])
+    lines.append(f"  spread of the repeated contender: {spread * 100:.2f} %; pixel_format=rgb32 / detour = {med[names[0]] / med[names[1]]:.3f} "
+                 f"({(med[names[1]] - med[names[0]]) * 1e3:.2f} ms less per clip)")
+
+
 def device_time(fn, n=20, warm=3):
     for _ in range(warm):
         fn()
@@ -1528,9 +1630,15 @@ def main():
     ap.add_argument("--live-rgb32", action="store_true", help="a tick of S live feeds of BGRA frames, every frame an allocation of its own: the RGB32 "
                     "room on the list beside strip + rgb24 room + write back and beside the rgb24 room alone; the four launchers beside their rgb24 "
                     "siblings")
+    ap.add_argument("--rgb32", action="store_true", help="the axis-aligned RGB32 edge: its three launchers beside their rgb24 siblings, and "
+                    "reenact_video(pixel_format='rgb32', paste=True) beside strip + pixel_format='rgb24' + write back")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_frame_io needs a HIP device: nothing is measured without one")
+    if args.rgb32:
+        lines = [f"bench_frame_io --rgb32: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
+        bench_rgb32(args, lines)
+        return report(lines, args.out or os.path.join(ROOT, "profiles", "rgb32_axis_bench.txt"))
     if args.live_rgb32:
         lines = [f"bench_frame_io --live-rgb32: {torch.cuda.get_device_name(0)}, fp32, at commit {args.commit}"]
         bench_live_rgb32(args, lines)
